@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: interpolated frames/sec @720p x8 MFI, N_tst=3 (BASELINE.json metric, configs[1]).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -48,7 +48,12 @@ def parse():
     ap.add_argument('--checkpoint', default='', help="reference checkpoint (.pt with 'state_dict_Model', main.py:316,351) to load instead of the random-init weights")
     ap.add_argument('--auto', action='store_true', help='let the runner probe the free memory for n_ctx / n_trunk (default: fixed values)')
     ap.add_argument('--with-png', action='store_true', help='side figure: PNG folder -> PNG folder frames/s of this rank (codec + threads inside)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write the frames the last timed step delivered as DIR/<name>.npy (float32, at most 64 MB in all)')
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return a
 
 
 def cpu_baseline(n_tst, full_px, model=None, dev=None):
@@ -100,6 +105,31 @@ def synthetic_clip_u8(h, w, n_frames, seed):
         f = ((acc / taps).permute(1, 2, 0) + 1) * 127.5
         out.append(f.clamp(0, 255).to(torch.uint8).contiguous().pin_memory())
     return out
+
+
+DUMP_BYTES = 64 * 10 ** 6                               # --dump-outputs: .npy payload of all arrays together
+DUMP_SEED = 0
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: the uint8 frames the timed path delivered for its last window, as float32 ``d/<name>.npy``, so that two builds
+    can be compared output for output.  When all of them together exceed DUMP_BYTES, each array is cut to a fixed sample of its
+    flat elements (sorted indices drawn by numpy.random.default_rng(DUMP_SEED), a share of the budget proportional to its size):
+    the same elements in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(int(v.numel()) for v in arrays.values())
+    cap = DUMP_BYTES // 4 - 1024                                    # float32 elements, headroom for the .npy headers
+    info = {}
+    for name, v in arrays.items():
+        x = v.cpu().numpy()
+        if total > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, x.size * cap // total, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(d, name + '.npy'), x.astype(np.float32))
+        info[name] = {'shape': list(v.shape), 'dtype': str(v.dtype).replace('torch.', ''), 'elements_written': int(x.size),
+                      'sample': 'flat elements at sorted default_rng(%d) indices' % DUMP_SEED if total > cap else None}
+    return {'dir': os.path.abspath(d), 'arrays': info}
 
 
 def png_side_figure(a, model, runner):
@@ -329,6 +359,7 @@ def main():
                   'mismatching_bytes': bad, 'against': 'DeMFInet.forward per t via harness.pad_forward_crop + demfi_frame_to_u8 (module path)'}
         if bad:
             raise SystemExit('bench.py: the timed path delivered %d bytes that differ from the module path: %s' % (bad, json.dumps(verify)))
+    dumped = dump_outputs(a.dump_outputs, {'st': kept['st'], 's01': kept['s01']}) if a.dump_outputs and rank == 0 else None
     frames_out = (a.mfi - 1) * a.steps * world
     eng = runner.engine
     if rank == 0:
@@ -353,6 +384,8 @@ def main():
         }
         if verify is not None:
             out['verified'] = verify
+        if dumped is not None:
+            out['dumped_outputs'] = dumped
         # ---- roofline of the dominant kernel, measured live with HIP events on the launch stream, IN SEQUENCE: the whole launch plan
         # runs op after op with an event between consecutive launches (mean of 5 passes), so every kernel sees the clock and cache
         # state the pipeline leaves it -- an isolated repeat loop lets the clock recover and read 4-5 % faster ----

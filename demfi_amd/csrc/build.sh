@@ -82,6 +82,6 @@ SAN="-O1 -g -fsanitize=address,undefined -fno-sanitize=pointer-overflow -fno-gpu
       *) aso+=("$o") ;;
     esac
   done
-  $HIPCC --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -shared-libsan "${aso[@]}" -o libdemfi_hip_asan.so -lz -lpthread
+  $HIPCC --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -fno-gpu-sanitize -shared-libsan "${aso[@]}" -o libdemfi_hip_asan.so -lz -lpthread
   echo "built $(pwd)/libdemfi_hip_asan.so"
 fi

@@ -3,6 +3,11 @@ import sys
 
 import pytest
 
+# torch.exp on CPU runs through MKL's vector math, whose default code path depends on the CPU vendor (AMD hosts always get the
+# compatible one, Intel hosts a faster one that rounds ~1.6 % of results differently).  The bit-exact oracle fixtures in tests/golden
+# were frozen on the compatible path; pin it on every host.  MKL reads this at its first call, so before any test runs.
+os.environ['MKL_CBWR'] = 'COMPATIBLE'
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)

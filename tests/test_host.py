@@ -389,6 +389,36 @@ def test_bench_self_launches_under_torch_distributed_run(monkeypatch):
     assert calls == [2] and ei.value.code == 3
 
 
+def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path, monkeypatch):
+    """``bench.py --dump-outputs DIR``: float32 .npy files of the delivered frames; small outputs are written whole, a 720p x8 window
+    (7 St + S0/S1) is cut to the same seeded sample of at most 64 MB on every run; --steps below 1 is refused."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(root, 'bench.py'))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    g = torch.Generator().manual_seed(3)
+    st = torch.randint(0, 256, (7, 720, 1280, 3), dtype=torch.uint8, generator=g)
+    s01 = torch.randint(0, 256, (2, 720, 1280, 3), dtype=torch.uint8, generator=g)
+    small = b.dump_outputs(str(tmp_path / 'small'), {'st': st[:, :8, :16], 's01': s01[:, :8, :16]})
+    assert small['arrays']['st']['sample'] is None
+    got = np.load(str(tmp_path / 'small' / 'st.npy'))
+    assert got.dtype == np.float32 and np.array_equal(got, st[:, :8, :16].numpy())
+    runs = []
+    for d in ('a', 'b'):
+        info = b.dump_outputs(str(tmp_path / d), {'st': st, 's01': s01})
+        assert info['arrays']['st']['shape'] == [7, 720, 1280, 3] and info['arrays']['st']['sample']
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))) <= 64 * 10 ** 6
+        runs.append({n: np.load(str(tmp_path / d / (n + '.npy'))) for n in ('st', 's01')})
+    for n, v in (('st', st), ('s01', s01)):
+        assert runs[0][n].dtype == np.float32 and np.array_equal(runs[0][n], runs[1][n])
+        idx = np.sort(np.random.default_rng(b.DUMP_SEED).choice(v.numel(), runs[0][n].size, replace=False))
+        assert np.array_equal(runs[0][n], v.numpy().reshape(-1)[idx])
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '0'])
+    with pytest.raises(SystemExit):
+        b.parse()
+
+
 def test_rank_affinity_slices_a_numa_node_between_its_ranks():
     """tools/run_node.sh: ranks whose GPUs share a NUMA node get disjoint slices of that node's cores, the node comes
     from the PCI address of HIP device LOCAL_RANK; without NUMA information the cores are split evenly by rank."""

@@ -2,6 +2,7 @@
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from demfi_amd.weights import synthetic_window
@@ -12,6 +13,16 @@ E2E = ['e2e_64x96_t0500_n3', 'e2e_64x96_t0125_n1', 'e2e_64x96_t0875_n2', 'e2e_32
 
 def _load(golden_dir, name):
     return np.load(os.path.join(golden_dir, name + '.npz'))
+
+
+@pytest.fixture(autouse=True)
+def _fixture_thread_count():
+    """oneDNN's CPU convolutions sum in an order that depends on the thread count; the fixtures are checked at 8 threads, whatever
+    the host has (at 16 or more on a 64-core EPYC the FGAC extras drift past their 5e-6 tolerance)."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
 
 
 def test_e2e_matches_reference_goldens(golden_dir, synthetic_sd):

@@ -20,7 +20,7 @@ for u in ctx abi png_codec; do
   $HIPCC --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -I../../include -Wno-unused-result $SAN -x hip -c $u.cpp -o ${u}_asan.o
   objs+=(${u}_asan.o)
 done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -shared-libsan "${objs[@]}" -o libdemfi_hip_asan.so -lz -lpthread
+$HIPCC --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -fno-gpu-sanitize -shared-libsan "${objs[@]}" -o libdemfi_hip_asan.so -lz -lpthread
 RT=$($HIPCC -print-file-name=libclang_rt.asan-x86_64.so)
 cd "$ROOT"
 export DEMFI_HIP_LIB=$ROOT/demfi_amd/csrc/libdemfi_hip_asan.so

@@ -12,6 +12,7 @@ import sys
 import types
 import warnings
 
+os.environ['MKL_CBWR'] = 'COMPATIBLE'                    # MKL's vendor-independent code path, as tests/conftest.py pins it
 import numpy as np
 import torch
 
