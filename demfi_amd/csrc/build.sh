@@ -4,7 +4,7 @@ set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include -Wno-unused-result -Wno-pass-failed -Werror=inline-asm -Werror=unused-value"
-# experiment builds only (--ablation / --trace below) take extra flags from the environment; the product compile line is fixed
+# the trace build (--trace below) takes extra flags from the environment; the product compile line is fixed
 XFLAGS="$DEMFI_EXTRA_FLAGS"
 # conv.hip = the dispatcher (demfi_conv2d); the convolution kernels are units of their own (round 6: they compile in parallel, 2 min -> 1 min)
 CONV_UNITS="conv conv_general conv_c64 conv_narrow conv_sep conv_wstream"
@@ -38,9 +38,7 @@ done
 for p in "${pids[@]}"; do wait "$p"; done      # 'wait PID' returns that job's status: set -e stops on the first failure
 $HIPCC --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o libdemfi_hip.so -lz -lpthread
 echo "built $(pwd)/libdemfi_hip.so"
-# --ablation: second library with the ablation variants / experimental kernels (DEMFI_PERSIST_VARIANT, DEMFI_SEP_VARIANT,
-# DEMFI_CONV_Z, ...); use it with DEMFI_HIP_LIB=$(pwd)/libdemfi_hip_abl.so.  Never loaded by default.
-# --trace: third library whose persistent 64->64 kernels stamp s_memtime at their phase boundaries (tools/phase_trace.py)
+# --trace: second library whose persistent 64->64 kernels stamp s_memtime at their phase boundaries (tools/phase_trace.py)
 if [ "$1" = "--trace" ]; then
   tp=()
   for u in $CONV_UNITS gru resblock; do
@@ -53,19 +51,6 @@ if [ "$1" = "--trace" ]; then
   done
   $HIPCC --offload-arch=gfx950 -shared -fPIC "${trc[@]}" -o libdemfi_hip_trace.so -lz -lpthread
   echo "built $(pwd)/libdemfi_hip_trace.so"
-fi
-if [ "$1" = "--ablation" ]; then
-  ap=()
-  for u in $CONV_UNITS; do
-    $HIPCC $FLAGS $XFLAGS $CONV_FLAGS -DDEMFI_ABLATION -c $u.hip -o ${u}_abl.o & ap+=($!)
-  done
-  for p in "${ap[@]}"; do wait "$p"; done
-  abl=()
-  for o in "${objs[@]}"; do
-    case "$o" in conv*.o) abl+=("${o%.o}_abl.o") ;; *) abl+=("$o") ;; esac
-  done
-  $HIPCC --offload-arch=gfx950 -shared -fPIC "${abl[@]}" -o libdemfi_hip_abl.so -lz -lpthread
-  echo "built $(pwd)/libdemfi_hip_abl.so"
 fi
 # --asan: host-side AddressSanitizer + UBSan build: the three host translation units -- the plan builder / arena
 # planner / op interpreter (ctx.cpp), the ABI glue (abi.cpp) and the PNG codec that parses untrusted bytes (png_codec.cpp) --

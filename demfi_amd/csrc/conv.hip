@@ -12,7 +12,6 @@ namespace {
 
 bool sep_eligible(const demfi_conv* h) { return demfi_sep_eligible(h); }
 bool wstream_eligible(const demfi_conv* h, int ks = 7, int nch = 2) { return demfi_wstream_eligible(h, ks, nch); }
-bool wstream3_on() { return demfi_wstream3_on(); }
 
 // epilogue of the persistent 3x3 kernels: ONE NHWC fp16 destination holding all NCO*32 channels (optional residual)
 static bool persist_out_eligible(const demfi_conv* h, bool allow_tanh = false);
@@ -85,7 +84,7 @@ static bool persist_out_eligible(const demfi_conv* h, bool allow_tanh)
 // 3x3 kernel, the narrow kernel with an NHWC destination, the SepConvGRU kernel.  Their layers are packed with cout_perm.
 bool demfi_persist_eligible(const demfi_conv* h)
 {
-    return sep_eligible(h) || wstream_eligible(h) || (wstream3_on() && wstream_eligible(h, 3, 1)) || persist_eligible(h) || (narrow_eligible(h) && persist_out_eligible(h)) ||
+    return sep_eligible(h) || wstream_eligible(h) || wstream_eligible(h, 3, 1) || persist_eligible(h) || (narrow_eligible(h) && persist_out_eligible(h)) ||
            demfi_ws2_eligible(h);
 }
 
@@ -150,16 +149,6 @@ extern "C" int demfi_conv2d(const demfi_conv* h, const demfi_conv* dev, void* st
         if (!ok) return demfi_set_error(DEMFI_ERR_ARG, "demfi_conv2d: subtile %d is not eligible for the staged epilogue", sb);
     }
     hipStream_t st = (hipStream_t)stream;
-#if defined(DEMFI_ABLATION) || defined(DEMFI_TRACE)
-    {   // experiment builds only (a synchronous copy on the first launch: never inside a stream capture)
-        static const int knob_set = [] {
-            const int k = getenv("DEMFI_KNOB") ? atoi(getenv("DEMFI_KNOB")) : 0;
-            if (k) { demfi_c64_set_knob(k); demfi_narrow_set_knob(k); }
-            return k;
-        }();
-        (void)knob_set;
-    }
-#endif
     if (h->pack.ptr != nullptr) {
         // the packed copy is an epilogue of the thin-output narrow kernel only: any other layer asking for it must fail loudly
         bool ok = h->dtype == DEMFI_F16 && narrow_eligible(h) && thin_out_eligible(h) && !persist_out_eligible(h) && h->pack.sc == 1 && !h->pack.is_f32;
@@ -169,25 +158,15 @@ extern "C" int demfi_conv2d(const demfi_conv* h, const demfi_conv* dev, void* st
     if ((h->cout_perm != 0) != demfi_persist_eligible(h))
         return demfi_set_error(DEMFI_ERR_ARG, h->cout_perm ? "demfi_conv2d: descriptor packed for a persistent kernel (cout_perm) but not eligible for one (zero_page missing?)"
                                                            : "demfi_conv2d: persistent-kernel layer without cout_perm (build the descriptor with demfi_conv_build)");
-    bool fall = false, handled = false;
-    if (sep_eligible(h)) {
-        const int rc = demfi_sep_launch(h, dev, st, &fall);
-        if (!fall) return rc;
-    }
+    if (sep_eligible(h)) return demfi_sep_launch(h, dev, st);
     if (wstream_eligible(h)) return demfi_wstream_launch(h, dev, st);
     if (!persist_eligible(h) && !narrow_eligible(h) && demfi_ws2_eligible(h)) return demfi_ws2_launch(h, dev, st);      // wsconv.hip (round 6)
-    if (wstream3_on() && wstream_eligible(h, 3, 1)) return demfi_wstream3_launch(h, dev, st);
-    if (persist_eligible(h)) {
-        const int rc = demfi_c64_launch(h, dev, st, &fall);
-        if (!fall) return rc;
-    } else if (narrow_eligible(h)) {
-#ifdef DEMFI_ABLATION
-        if (!(getenv("DEMFI_NARROW_OFF") && atoi(getenv("DEMFI_NARROW_OFF"))))
-#endif
-        {
-            const int rc = demfi_narrow_launch(h, dev, st, !persist_out_eligible(h), &handled);
-            if (handled) return rc;
-        }
+    if (wstream_eligible(h, 3, 1)) return demfi_wstream3_launch(h, dev, st);
+    if (persist_eligible(h)) return demfi_c64_launch(h, dev, st);
+    if (narrow_eligible(h)) {
+        bool handled = false;
+        const int rc = demfi_narrow_launch(h, dev, st, !persist_out_eligible(h), &handled);
+        if (handled) return rc;
     }
     return demfi_conv_general_launch(h, dev, st, (size_t)lds);
 }

@@ -31,11 +31,8 @@ constexpr int P_NT = NT + 64;                                   // 4 MFMA waves 
 #ifndef DEMFI_P_NDMA
 #define DEMFI_P_NDMA 2
 #endif
-#ifndef DEMFI_P_KYREUSE
-#define DEMFI_P_KYREUSE 1        // 0: one (tap, k-step pair) at a time, 12 ds_reads per 12 MFMAs (A/B builds)
-#endif
 constexpr int P_NDMA = DEMFI_P_NDMA;                            // waves issuing the tile DMA (instruction i -> wave i % P_NDMA)
-template <int NCO, int VAR, bool RES = true>   // RES: the segment has a residual input (compile time: keeps the loads free of phis).  VAR: 0 = product; 1 no epilogue, 2 no MFMA phase, 3 no tile DMA, 4 epilogue only (ablation builds)
+template <int NCO, bool RES = true>   // RES: the segment has a residual input (compile time: keeps the loads free of phis)
 __global__ __launch_bounds__(NT + 64 * P_NDMA, 1) void conv3x3_c64_persist_kernel(const demfi_conv* __restrict__ d)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -79,7 +76,6 @@ __global__ __launch_bounds__(NT + 64 * P_NDMA, 1) void conv3x3_c64_persist_kerne
 
     if (wave >= 4) {
         // ================= DMA waves: own every global->LDS transfer, so only THEIR vmcnt tracks them ============
-        if (DEMFI_KNOB_BIT(1)) __builtin_amdgcn_s_setprio(3);
         const int dw = wave - 4;
         const demfi_piece& pc = d->pieces[0];
         const char* const src = (const char*)pc.v.ptr;
@@ -135,7 +131,7 @@ __global__ __launch_bounds__(NT + 64 * P_NDMA, 1) void conv3x3_c64_persist_kerne
             TRACE_STAMP(wave, trk, 0);
             __syncthreads();                                    // A: hand tile t to the MFMA waves
             TRACE_STAMP(wave, trk, 1);
-            if (VAR != 3 && VAR != 4 && VAR != 10 && t + t_step < t_end) issue_tile(t + t_step, buf ^ 1);   // streams in under the MFMAs
+            if (t + t_step < t_end) issue_tile(t + t_step, buf ^ 1);   // streams in under the MFMAs
             TRACE_STAMP(wave, trk, 2);
             ++trk;
         }
@@ -205,163 +201,54 @@ __global__ __launch_bounds__(NT + 64 * P_NDMA, 1) void conv3x3_c64_persist_kerne
             for (int i = 0; i < 16; ++i) { acc[s][0][i] = 0.0f; acc[s][1][i] = 0.0f; }
         }
         const char* tb = tbuf + buf * P_TILE_BYTES + (wave * 2) * (P_LW * 128);
-        if (VAR != 2 && VAR != 4) {
-            // software pipeline over 18 k-step pairs: the fragments of pair i+1 are in flight while the 4*NCO MFMAs
-            // of pair i run (one wave per SIMD: nothing else hides the LDS latency)
-            auto load_pair = [&](FragSet<NCO>& f, int pair) {
-                const int tap = pair >> 1, ks0 = (pair & 1) * 2;
-                const int ky = tap / 3, kx = tap % 3;
+        // software pipeline over the taps: the fragments of group g+1 are in flight while the MFMAs of group g run (one wave per SIMD:
+        // nothing else hides the LDS latency).
+        // Input-row reuse across ky: for one (kx, k-step) the taps ky = 0..2 of output rows p = 0, 1 read input rows
+        // p + ky = 0..3 at the same column offset -- 4 distinct B fragments feed 6 (ky, p) combinations.  One group =
+        // 4 row fragments + 3*NCO weight fragments -> 6*NCO MFMAs: 10 ds_reads per 12 MFMAs instead of 12 (NCO = 2).
+        struct RowFrag { uint4 a[3][NCO]; uint4 b[4]; };
+        auto load_g = [&](RowFrag& f, int g) {          // g = kx*4 + ks
+            const int kx = g >> 2, ks = g & 3;
 #pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int ks = ks0 + k;
+            for (int ky = 0; ky < 3; ++ky) {
 #pragma unroll
-                    for (int s = 0; s < NCO; ++s) f.a[k][s] = *(const uint4*)(wl + ((tap * NKS + ks) * NCO + s) * 1024);
-                    const char* p0 = tb + boff[kx * 4 + ks];            // row index is an immediate of the ds_read
-                    f.b[k][0] = *(const uint4*)(p0 + ky * (P_LW * 128));
-                    f.b[k][1] = *(const uint4*)(p0 + (ky + 1) * (P_LW * 128));
-                }
-            };
-            auto mma_pair = [&](const FragSet<NCO>& f) {
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-#pragma unroll
-                    for (int s = 0; s < NCO; ++s) {
-                        Mma<half_t>::run(acc[s][0], f.a[k][s], f.b[k][0]);
-                        Mma<half_t>::run(acc[s][1], f.a[k][s], f.b[k][1]);
-                    }
-                }
-            };
-            if constexpr (VAR == 0 && DEMFI_P_KYREUSE != 0) {
-                // Input-row reuse across ky: for one (kx, k-step) the taps ky = 0..2 of output rows p = 0, 1 read input rows
-                // p + ky = 0..3 at the same column offset -- 4 distinct B fragments feed 6 (ky, p) combinations.  One group =
-                // 4 row fragments + 3*NCO weight fragments -> 6*NCO MFMAs: 10 ds_reads per 12 MFMAs instead of 12 (NCO = 2).
-                struct RowFrag { uint4 a[3][NCO]; uint4 b[4]; };
-                auto load_g = [&](RowFrag& f, int g) {          // g = kx*4 + ks
-                    const int kx = g >> 2, ks = g & 3;
-#pragma unroll
-                    for (int ky = 0; ky < 3; ++ky) {
-#pragma unroll
-                        for (int s = 0; s < NCO; ++s) f.a[ky][s] = *(const uint4*)(wl + (((ky * 3 + kx) * NKS + ks) * NCO + s) * 1024);
-                    }
-                    const char* p0 = tb + boff[kx * 4 + ks];    // row index is an immediate of the ds_read
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) f.b[r] = *(const uint4*)(p0 + r * (P_LW * 128));
-                };
-                auto mma_g = [&](const RowFrag& f) {
-#pragma unroll
-                    for (int ky = 0; ky < 3; ++ky) {
-#pragma unroll
-                        for (int s = 0; s < NCO; ++s) {
-                            Mma<half_t>::run(acc[s][0], f.a[ky][s], f.b[ky]);
-                            Mma<half_t>::run(acc[s][1], f.a[ky][s], f.b[ky + 1]);
-                        }
-                    }
-                };
-                auto groups = [&](bool loads) {
-#pragma unroll
-                    for (int q = 0; q < 6 * NCO; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                      // 1 MFMA
-                        if (loads && q < 3 * NCO + 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 DS read of the next group
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                };
-                RowFrag f0, f1;
-                load_g(f0, 0);
-                static_for<0, 6>([&](auto I) {
-                    constexpr int i = decltype(I)::value;
-                    load_g(f1, 2 * i + 1);
-                    mma_g(f0);
-                    groups(true);
-                    if constexpr (i < 5) load_g(f0, 2 * i + 2);
-                    mma_g(f1);
-                    groups(i < 5);
-                });
-            } else
-            if constexpr (VAR == 11) {
-                // ablation: ring of four k-step fragment sets, loads three k-steps (12 MFMAs) ahead of their use, one ds_read
-                // issued per MFMA
-                struct StepFrag { uint4 a[NCO]; uint4 b[2]; };
-                auto load_step = [&](StepFrag& f, int g) {      // g = tap*4 + ks
-                    const int tap = g >> 2, ks = g & 3;
-                    const int ky = tap / 3, kx = tap % 3;
-#pragma unroll
-                    for (int s = 0; s < NCO; ++s) f.a[s] = *(const uint4*)(wl + (g * NCO + s) * 1024);
-                    const char* p0 = tb + boff[kx * 4 + ks];
-                    f.b[0] = *(const uint4*)(p0 + ky * (P_LW * 128));
-                    f.b[1] = *(const uint4*)(p0 + (ky + 1) * (P_LW * 128));
-                };
-                StepFrag fr[4];
-                load_step(fr[0], 0);
-                load_step(fr[1], 1);
-                load_step(fr[2], 2);
-                __builtin_amdgcn_sched_barrier(0);
-                static_for<0, 36>([&](auto G) {
-                    constexpr int g = decltype(G)::value;
-                    if constexpr (g + 3 < 36) load_step(fr[(g + 3) & 3], g + 3);
-#pragma unroll
-                    for (int s = 0; s < NCO; ++s) {
-                        Mma<half_t>::run(acc[s][0], fr[g & 3].a[s], fr[g & 3].b[0]);
-                        Mma<half_t>::run(acc[s][1], fr[g & 3].a[s], fr[g & 3].b[1]);
-                    }
-                    if constexpr (g + 3 < 36) {
-#pragma unroll
-                        for (int q = 0; q < 2 * NCO; ++q) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                });
-            } else {
-            FragSet<NCO> f0, f1;
-            load_pair(f0, 0);
-            if constexpr (VAR == 7) load_pair(f1, 1);           // ablation: fragments loaded once per tile, no LDS traffic below
-            static_for<0, 9>([&](auto I) {
-                constexpr int i = decltype(I)::value;
-                if constexpr (VAR != 7 && VAR != 9) {
-                    // ds_reads of the next pair interleaved 1:1 with the MFMAs of this pair (sched_group_barrier): the matrix
-                    // pipe does not idle while 8 ds_reads issue back to back (+3 % over the block schedule, VAR 9)
-                    load_pair(f1, 2 * i + 1);
-                    mma_pair(f0);
-#pragma unroll
-                    for (int q = 0; q < 4 * NCO; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 DS read
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (i < 8) load_pair(f0, 2 * i + 2);
-                    mma_pair(f1);
-#pragma unroll
-                    for (int q = 0; q < 4 * NCO; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    return;
-                }
-                if constexpr (VAR != 7) load_pair(f1, 2 * i + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_pair(f0);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (i < 8 && VAR != 7) load_pair(f0, 2 * i + 2);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_pair(f1);
-                __builtin_amdgcn_sched_barrier(0);
-            });
+                for (int s = 0; s < NCO; ++s) f.a[ky][s] = *(const uint4*)(wl + (((ky * 3 + kx) * NKS + ks) * NCO + s) * 1024);
             }
-        }
+            const char* p0 = tb + boff[kx * 4 + ks];    // row index is an immediate of the ds_read
+#pragma unroll
+            for (int r = 0; r < 4; ++r) f.b[r] = *(const uint4*)(p0 + r * (P_LW * 128));
+        };
+        auto mma_g = [&](const RowFrag& f) {
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+                for (int s = 0; s < NCO; ++s) {
+                    Mma<half_t>::run(acc[s][0], f.a[ky][s], f.b[ky]);
+                    Mma<half_t>::run(acc[s][1], f.a[ky][s], f.b[ky + 1]);
+                }
+            }
+        };
+        auto groups = [&](bool loads) {
+#pragma unroll
+            for (int q = 0; q < 6 * NCO; ++q) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                      // 1 MFMA
+                if (loads && q < 3 * NCO + 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 DS read of the next group
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        RowFrag f0, f1;
+        load_g(f0, 0);
+        static_for<0, 6>([&](auto I) {
+            constexpr int i = decltype(I)::value;
+            load_g(f1, 2 * i + 1);
+            mma_g(f0);
+            groups(true);
+            if constexpr (i < 5) load_g(f0, 2 * i + 2);
+            mma_g(f1);
+            groups(i < 5);
+        });
         // no second barrier: the epilogue works from registers, and tile t's buffer is only overwritten by the DMA of
         // tile t+2, issued after barrier A of tile t+1, which every MFMA wave reaches after this MFMA phase
-        if (VAR == 1 || VAR == 10) {                            // 10: MFMA phase only (no tile DMA, no epilogue)
-#pragma unroll
-            for (int s = 0; s < NCO; ++s) {
-#if defined(__HIP_DEVICE_COMPILE__)
-                asm volatile("" ::"v"(acc[s][0]));
-                asm volatile("" ::"v"(acc[s][1]));
-#endif
-            }
-            continue;
-        }
         // ---- epilogue straight from the accumulators (the tile buffer is not reused: barrier B only orders the DMA) ----
 #if defined(DEMFI_TRACE) && defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
@@ -413,18 +300,18 @@ __global__ __launch_bounds__(NT + 64 * P_NDMA, 1) void conv3x3_c64_persist_kerne
     }
 }
 
-template <int NCO, int VAR = 0>
+template <int NCO>
 int launch_persist(const demfi_conv* h, const demfi_conv* dev, hipStream_t st)
 {
     const size_t lds = 9 * 4 * NCO * 1024 + 2 * P_TILE_BYTES + 1024;      // weights + 2 tiles + bias
-    DEMFI_LDS_ATTR((conv3x3_c64_persist_kernel<NCO, VAR, true>));
-    DEMFI_LDS_ATTR((conv3x3_c64_persist_kernel<NCO, VAR, false>));
+    DEMFI_LDS_ATTR((conv3x3_c64_persist_kernel<NCO, true>));
+    DEMFI_LDS_ATTR((conv3x3_c64_persist_kernel<NCO, false>));
     const int total = ((h->W + TW - 1) / TW) * ((h->H + TH - 1) / TH) * h->batch;
     const int grid = total >= 256 ? 256 : total;
     if (h->segs[h->sub_seg[0]].res.ptr != nullptr)
-        hipLaunchKernelGGL((conv3x3_c64_persist_kernel<NCO, VAR, true>), dim3(grid), dim3(NT + 64 * P_NDMA), lds, st, dev);
+        hipLaunchKernelGGL((conv3x3_c64_persist_kernel<NCO, true>), dim3(grid), dim3(NT + 64 * P_NDMA), lds, st, dev);
     else
-        hipLaunchKernelGGL((conv3x3_c64_persist_kernel<NCO, VAR, false>), dim3(grid), dim3(NT + 64 * P_NDMA), lds, st, dev);
+        hipLaunchKernelGGL((conv3x3_c64_persist_kernel<NCO, false>), dim3(grid), dim3(NT + 64 * P_NDMA), lds, st, dev);
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }
@@ -446,20 +333,11 @@ int launch_persist(const demfi_conv* h, const demfi_conv* dev, hipStream_t st)
 // Round 2 built this once on the 2-DMA-wave kernel and measured nothing (profiles/r02_notes.md); the trace shows why: there the
 // helper path (stores, then 3 300 cycles of DMA issue starved by the MFMA waves, then the landing) was as long as the period.
 // ======================================================================================================
-// Streaming (nt) hints of the staged-store kernel.  Bit 1 (default): the helper waves' output stores -- whole 128-byte lines of tensors
-// of hundreds of MB that the next launch re-reads from HBM anyway; without the hint the written lines compete with the input tiles for
-// the L2s and the Infinity Cache: residual launches -1.5..-2 %, the window -0.6 ms (profiles/r04_notes.md section 11).  Experiment
-// bits, both measured negative there: 2 = nt residual loads (+15 % on the residual launches), 4 = nt tile DMA.  The same hint on the
-// 16-byte-per-lane stores of the MFMA waves of the GRU / narrow / streamed-weight kernels is 1.8x / 1.1x / 1.02x SLOWER (partial lines).
-#ifndef DEMFI_STG_NT
-#define DEMFI_STG_NT 1
-#endif
-#ifndef DEMFI_STG_RES_AHEAD
-#define DEMFI_STG_RES_AHEAD 0                                    // 1: the residual of tile k+1 is fetched during tile k (two register sets: measured no better than 0 with an early issue point)
-#endif
-#ifndef DEMFI_STG_RES_AT
-#define DEMFI_STG_RES_AT -1                                      // k-loop third after which the residual loads are issued (-1: before barrier A, at the head of the tile)
-#endif
+// Streaming (nt) hint of the staged-store kernel on the helper waves' output stores -- whole 128-byte lines of tensors of hundreds of MB
+// that the next launch re-reads from HBM anyway; without the hint the written lines compete with the input tiles for the L2s and the
+// Infinity Cache: residual launches -1.5..-2 %, the window -0.6 ms (profiles/r04_notes.md section 11).  Measured negative there: nt
+// residual loads (+15 % on the residual launches), nt tile DMA.  The same hint on the 16-byte-per-lane stores of the MFMA waves of the
+// GRU / narrow / streamed-weight kernels is 1.8x / 1.1x / 1.02x SLOWER (partial lines).
 constexpr int SG_NH = 4;                                         // helper waves
 constexpr int SG_NT = NT + 64 * SG_NH;
 template <bool RES, bool TANH = false>   // TANH: tanh after the residual add (Refine_Module.dec3's feature halves, DeMFInet.py:86-87) instead of ReLU / identity
@@ -506,7 +384,6 @@ __global__ __launch_bounds__(SG_NT, 1) void conv3x3_c64_stg_kernel(const demfi_c
 
     if (wave >= 4) {
         // ================= helper waves: tile DMA + the global stores of the staged outputs ==========================
-        if (DEMFI_KNOB_BIT(1)) __builtin_amdgcn_s_setprio(2);
         const int dw = wave - 4;
         constexpr int NIW = (P_NI + SG_NH - 1) / SG_NH;          // DMA instructions per helper (11; the last one may not exist)
         const demfi_piece& pc = d->pieces[0];
@@ -539,7 +416,7 @@ __global__ __launch_bounds__(SG_NT, 1) void conv3x3_c64_stg_kernel(const demfi_c
                     if (i >= P_NI) continue;                     // wave-uniform
                     const char* g = base + off[k];
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                     (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, (DEMFI_STG_NT & 4) ? 2 : 0);
+                                                     (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
                 }
             } else {
 #pragma unroll
@@ -549,7 +426,7 @@ __global__ __launch_bounds__(SG_NT, 1) void conv3x3_c64_stg_kernel(const demfi_c
                     const int iy = oy0 - 1 + (lyx[k] & 255), ix = ox0 - 1 + (lyx[k] >> 8);
                     const char* g = (lyx[k] != 0xffff && iy >= 0 && iy < H && ix >= 0 && ix < W) ? base + off[k] : zeros;
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                     (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, (DEMFI_STG_NT & 4) ? 2 : 0);
+                                                     (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
                 }
             }
         };
@@ -575,10 +452,7 @@ __global__ __launch_bounds__(SG_NT, 1) void conv3x3_c64_stg_kernel(const demfi_c
             char* const obase = (char*)(dstp + bimg * d_sb + oy0 * d_sy + ox0 * d_sx);      // wave-uniform
             if (oy0 + TH <= H && ox0 + TW <= W) {
 #pragma unroll
-                for (int k = 0; k < NCH; ++k) {
-                    if constexpr ((DEMFI_STG_NT & 1) != 0) __builtin_nontemporal_store(stage[k], gp<u4_t>(obase + doff[k]));
-                    else *gp<u4_t>(obase + doff[k]) = stage[k];
-                }
+                for (int k = 0; k < NCH; ++k) __builtin_nontemporal_store(stage[k], gp<u4_t>(obase + doff[k]));
             } else {
 #pragma unroll
                 for (int k = 0; k < NCH; ++k) {
@@ -604,17 +478,6 @@ __global__ __launch_bounds__(SG_NT, 1) void conv3x3_c64_stg_kernel(const demfi_c
             // acknowledgements of stores issued late in the phase
             if (have_prev) { stage_read(buf ^ 1); stage_store(pb, py, px); }
             if (t + t_step < t_end) issue_tile(t + t_step, buf ^ 1);
-#ifdef DEMFI_ABLATION
-            // experiment (DEMFI_KNOB bit 6; round 4): what would STREAMING the 72 KiB of weights per tile through the helpers cost (the
-            // design VERDICT r3 item 1 proposes to free LDS for a third tile buffer)?  The helpers re-issue the LDS-DMA of the resident
-            // weights every tile: the same bytes land on top of themselves, results stay correct, and the helper path carries the 72
-            // extra DMA instructions + 72 KiB of L2 -> LDS traffic per tile that a weight ring would add.  profiles/r04_notes.md section 6.
-            if (DEMFI_KNOB_BIT(64)) {
-                for (int i = dw; i < NTAPS * NKS * NCO; i += SG_NH)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wsrc + i * 64 + lane),
-                                                     (__attribute__((address_space(3))) void*)(wlds + i * 1024), 16, 0, 0);
-            }
-#endif
             TRACE_STAMP(wave, trk, 2);
             tile_coords(t, pb, py, px);
             have_prev = true;
@@ -666,41 +529,25 @@ __global__ __launch_bounds__(SG_NT, 1) void conv3x3_c64_stg_kernel(const demfi_c
 #pragma unroll
         for (int m2 = 0; m2 < 2; ++m2) soff[s][m2] = lx * 128 + (((s * 4 + m2 * 2 + hi) ^ ((lx >> 1) & 7)) << 4);
     }
-    // Residual: issued in the MIDDLE of an MFMA phase (after a third of the k-loop).  At the head of the period the CU's memory pipe
-    // belongs to the helper waves' stores of the previous tile and to the DMA of the next one.  Round 4: the loads issued during tile k
-    // are those of tile k+1 (two register sets, the tile loop unrolled by two so that both are statically named): on the memory wall
-    // the residual variant sits on (4.85 TB/s) loads issued 4 000 cycles before their use were 1 100-2 300 cycles late; a whole period
-    // of lead takes that wait out of the epilogue (DEMFI_STG_RES_AHEAD 0: the tile's own residual, the round-3 schedule).
+    // Residual: the tile's own, issued at the head of the tile (before barrier A).  Issued in the middle of the MFMA phase, or a tile
+    // ahead into a second register set, it measured no better (profiles/r04_notes.md).  The tile loop is unrolled by two so that the
+    // tile buffer index is static.
     using ResRegs = u4_t[NCO][2][2];
-    constexpr bool AHEAD = RES && DEMFI_STG_RES_AHEAD != 0;
-    auto tile_body = [&](const int t, const int buf, ResRegs& rreg, ResRegs& rnext) {
+    auto tile_body = [&](const int t, const int buf, ResRegs& rreg) {
         int bimg, oy0, ox0;
         tile_coords(t, bimg, oy0, ox0);
-        auto load_res_of = [&](ResRegs& rr, int tt) {
-            if constexpr (RES) {
-                int rb, ry0, rx0;
-                tile_coords(tt, rb, ry0, rx0);
+        if constexpr (RES) {
 #pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    const int oy = min(ry0 + wave * 2 + p, H - 1), oxx = min(rx0 + lx, W - 1);
-                    const half_t* rp = resp + rb * r_sb + oy * r_sy + oxx * r_sx + ch0 + hi * 8;
+            for (int p = 0; p < 2; ++p) {
+                const int oy = min(oy0 + wave * 2 + p, H - 1), oxx = min(ox0 + lx, W - 1);
+                const half_t* rp = resp + bimg * r_sb + oy * r_sy + oxx * r_sx + ch0 + hi * 8;
 #pragma unroll
-                    for (int s = 0; s < NCO; ++s) {
+                for (int s = 0; s < NCO; ++s) {
 #pragma unroll
-                        for (int m2 = 0; m2 < 2; ++m2) {
-                            if constexpr ((DEMFI_STG_NT & 2) != 0) rr[s][p][m2] = __builtin_nontemporal_load(gcp<u4_t>(rp + s * 32 + m2 * 16));
-                            else rr[s][p][m2] = *gcp<u4_t>(rp + s * 32 + m2 * 16);
-                        }
-                    }
+                    for (int m2 = 0; m2 < 2; ++m2) rreg[s][p][m2] = *gcp<u4_t>(rp + s * 32 + m2 * 16);
                 }
             }
-        };
-        auto load_res = [&]() {
-            // no branch inside the MFMA phase: the last tile of the walk re-reads its own residual into the idle set
-            if constexpr (AHEAD) load_res_of(rnext, t + t_step < t_end ? t + t_step : t);
-            else load_res_of(rreg, t);
-        };
-        if constexpr (DEMFI_STG_RES_AT < 0) load_res();
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the staged outputs of the previous tile are in LDS
         TRACE_STAMP(wave, trk, 0);
         asm volatile("s_barrier" ::: "memory");                 // A
@@ -751,7 +598,6 @@ __global__ __launch_bounds__(SG_NT, 1) void conv3x3_c64_stg_kernel(const demfi_c
                 load_g(f1, 2 * i + 1);
                 mma_g(f0, std::integral_constant<bool, i == 0>{});
                 groups(true);
-                if constexpr (i == DEMFI_STG_RES_AT) load_res();
                 if constexpr (i < 5) load_g(f0, 2 * i + 2);
                 mma_g(f1, std::false_type{});
                 groups(i < 5);
@@ -809,25 +655,11 @@ __global__ __launch_bounds__(SG_NT, 1) void conv3x3_c64_stg_kernel(const demfi_c
         ++trk;
     };
     ResRegs r_even, r_odd;
-    if constexpr (AHEAD) {                                      // the first tile's residual (tile_body only fetches ahead)
-        int rb, ry0, rx0;
-        tile_coords(t_first, rb, ry0, rx0);
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const int oy = min(ry0 + wave * 2 + p, H - 1), oxx = min(rx0 + lx, W - 1);
-            const half_t* rp = resp + rb * r_sb + oy * r_sy + oxx * r_sx + ch0 + hi * 8;
-#pragma unroll
-            for (int s = 0; s < NCO; ++s) {
-#pragma unroll
-                for (int m2 = 0; m2 < 2; ++m2) r_even[s][p][m2] = *gcp<u4_t>(rp + s * 32 + m2 * 16);
-            }
-        }
-    }
     for (int t = t_first; t < t_end;) {
-        tile_body(t, 0, r_even, r_odd);
+        tile_body(t, 0, r_even);
         t += t_step;
         if (t >= t_end) break;
-        tile_body(t, 1, r_odd, r_even);
+        tile_body(t, 1, r_odd);
         t += t_step;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the last tile is staged
@@ -856,36 +688,9 @@ static int launch_stg(const demfi_conv* h, const demfi_conv* dev, hipStream_t st
 
 }  // namespace
 
-DEMFI_TU_KNOB(demfi_c64_set_knob)
 DEMFI_TU_TRACE(demfi_c64_trace_collect)
 
-int demfi_c64_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, bool* fall_through)
+int demfi_c64_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st)
 {
-    *fall_through = false;
-#ifdef DEMFI_ABLATION
-    static const int var = getenv("DEMFI_PERSIST_VARIANT") ? atoi(getenv("DEMFI_PERSIST_VARIANT")) : 0;
-    if (var == -1) { *fall_through = true; return DEMFI_OK; }
-    if (h->nco == 2 && var == 1) return launch_persist<2, 1>(h, dev, st);
-    if (h->nco == 2 && var == 2) return launch_persist<2, 2>(h, dev, st);
-    if (h->nco == 2 && var == 3) return launch_persist<2, 3>(h, dev, st);
-    if (h->nco == 2 && var == 4) return launch_persist<2, 4>(h, dev, st);
-    if (h->nco == 2 && var == 7) return launch_persist<2, 7>(h, dev, st);
-    if (h->nco == 2 && var == 9) return launch_persist<2, 9>(h, dev, st);
-    if (h->nco == 2 && var == 15) return launch_persist<2, 10>(h, dev, st);
-    if (h->nco == 2 && var == 16) return launch_persist<2, 11>(h, dev, st);
-#endif
-    if (h->nco == 2) {
-#ifdef DEMFI_ABLATION
-        if (var == 5) return launch_persist<2>(h, dev, st);
-        // DEMFI_PAIR: 4 the round-2 product (stores from the MFMA waves); the round-3 double-accumulator experiment (5) was deleted
-        // in round 5 (measured negative, profiles/r03_notes.md; git history: conv_exp_dacc.inc)
-        static const int pair = getenv("DEMFI_PAIR") ? atoi(getenv("DEMFI_PAIR")) : 0;
-        if (pair == 4) return launch_persist<2>(h, dev, st);
-#endif
-#ifdef DEMFI_TRACE
-        if (getenv("DEMFI_PAIR") && atoi(getenv("DEMFI_PAIR")) == 4) return launch_persist<2>(h, dev, st);   // phase trace of the 4-wave kernel
-#endif
-        return launch_stg(h, dev, st);
-    }
-    return launch_persist<1>(h, dev, st);
+    return h->nco == 2 ? launch_stg(h, dev, st) : launch_persist<1>(h, dev, st);
 }

@@ -1,6 +1,6 @@
 // Shared device helpers of the convolution kernels (conv_general.hip, conv_c64.hip, conv_narrow.hip, conv_sep.hip, conv_wstream.hip):
-// tile constants, the MFMA wrappers, the epilogue the general and the 32-cout persistent kernel share, and -- experiment builds only --
-// the per-translation-unit knob word / phase-trace buffer (each unit has its own copy; conv.hip collects them).
+// tile constants, the MFMA wrappers, the epilogue the general and the 32-cout persistent kernel share, and -- trace build only -- the
+// per-translation-unit phase-trace buffer (each unit has its own copy; conv.hip collects them).
 #pragma once
 #include "common.h"
 #include "conv_kernels.h"
@@ -9,16 +9,6 @@
 
 namespace {
 
-
-// Run-time experiment switches of the persistent kernels (env DEMFI_KNOB, read once on the host and copied into this
-// word; 0 = product behaviour):  bit 0: DMA waves at s_setprio 3;  bit 1 (pair kernel): epilogue at priority 2, MFMA
-// phase at 0;  bit 2 (pair kernel): MFMA phase at priority 2, epilogue at 0.
-#if defined(DEMFI_ABLATION) || defined(DEMFI_TRACE)
-__device__ int g_knob = 0;
-#define DEMFI_KNOB_BIT(b) (g_knob & (b))
-#else
-#define DEMFI_KNOB_BIT(b) 0                                      // product build: no device global, no lazy hipMemcpyToSymbol in a launch path
-#endif
 
 // In-kernel phase trace (libdemfi_hip_trace.so, build.sh --trace; never in the product): s_memtime stamps of the first
 // TR_TILES tiles of workgroups 0..TR_WGS-1, [wg][wave][tile][stamp].  MFMA waves: 0 = arrived at barrier A, 1 = released,
@@ -344,12 +334,7 @@ template <int NCO> struct FragSet { uint4 a[2][NCO]; uint4 b[2][2]; };
 
 }  // namespace
 
-// experiment builds: this unit's knob word / trace buffer behind a function conv.hip can call (device globals are per translation unit)
-#if defined(DEMFI_ABLATION) || defined(DEMFI_TRACE)
-#define DEMFI_TU_KNOB(fn) void fn(int k) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_knob), &k, sizeof(k)); }
-#else
-#define DEMFI_TU_KNOB(fn) void fn(int) { }
-#endif
+// trace build: this unit's trace buffer behind a function conv.hip can call (device globals are per translation unit)
 #ifdef DEMFI_TRACE
 #define DEMFI_TU_TRACE(fn)                                                                                  \
     int fn(unsigned long long* acc)                                                                         \

@@ -97,9 +97,6 @@ __global__ __launch_bounds__(NT, (NCO <= 1 ? 4 : (NCO == 2 ? 3 : 2))) void conv_
         issue_weights(wchunk, 0, nks);                              // overlaps the tile staging below
         // ---------------- stage the haloed input tile of this chunk into LDS ----------------------------
         for (int pi = ch.first_piece; pi < ch.first_piece + ch.n_pieces; ++pi) {
-#ifdef DEMFI_ABLATION
-            if (DEMFI_KNOB_BIT(32)) break;                              // experiment: no tile staging (garbage operands): what the staging costs
-#endif
             const demfi_piece& p = d->pieces[pi];
             const char* src = (const char*)p.v.ptr;
             const int ush = p.up_shift;
@@ -218,8 +215,7 @@ int launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, size_t ld
     dim3 grid(tiles, h->cout_pad / (32 * h->nco), h->batch);
     bool all_staged = true;                                      // no subtile needs the direct (thin / planar / ragged) epilogue
     for (int sb = 0; sb < h->cout_pad / 32; ++sb) all_staged = all_staged && h->sub_seg[sb] >= 0;
-    static const int nodirect = getenv("DEMFI_CONV_NODIRECT") ? atoi(getenv("DEMFI_CONV_NODIRECT")) : 1;      // A/B switch
-    if (all_staged && nodirect) {
+    if (all_staged) {
         DEMFI_LDS_ATTR((conv_kernel<T, NCO, false>));
         hipLaunchKernelGGL((conv_kernel<T, NCO, false>), grid, dim3(NT), lds, st, dev);
     } else {

@@ -71,12 +71,6 @@ __device__ __forceinline__ void quad_transpose4(float (&a)[4], int lane)
     for (int j = 0; j < 4; ++j) q[j] = dpp(y[j], std::integral_constant<int, 0x4E>{});       // quad_perm [2,3,0,1]: lane ^ 2
     a[0] = b1 ? q[2] : y[0]; a[1] = b1 ? q[3] : y[1]; a[2] = b1 ? y[2] : q[0]; a[3] = b1 ? y[3] : q[1];
 }
-#ifndef DEMFI_THIN_VEC
-#define DEMFI_THIN_VEC 1                                         // 0: A/B builds without the quad-transposed 16-byte epilogue accesses
-#endif
-#ifndef DEMFI_THIN_REGW
-#define DEMFI_THIN_REGW 1
-#endif
 #ifndef DEMFI_THIN_REGW_G128
 #define DEMFI_THIN_REGW_G128 6
 #endif
@@ -90,7 +84,7 @@ __global__ __launch_bounds__(NT + 64 * NDMA, 1) void conv3x3_narrow_persist_kern
 {
     static_assert(!P7 || (KS == 7 && NCO == 1 && REC == 32), "paired taps: the 7x7 / 16-channel / 32-cout instantiation");
     constexpr bool RES = EPI == 1, THIN = EPI == 2;
-    constexpr bool REGW = THIN && KS == 3 && NCO == 1 && DEMFI_THIN_REGW != 0;
+    constexpr bool REGW = THIN && KS == 3 && NCO == 1;
     // (kx, k-step) groups whose three ky fragments are register resident: all 6 of a 64-byte-record layer (18 fragments, 72 registers),
     // 6 of the 12 of a 128-byte-record layer (all 36 = 144 registers spill in the 256-register budget of this 8-wave workgroup); the
     // other groups keep reading the LDS copy
@@ -144,7 +138,6 @@ __global__ __launch_bounds__(NT + 64 * NDMA, 1) void conv3x3_narrow_persist_kern
 
     if (wave >= 4) {
         // ================= DMA wave(s) =======================================================================
-        if (DEMFI_KNOB_BIT(1)) __builtin_amdgcn_s_setprio(3);
         const int dw = wave - 4;                                 // this wave issues instructions i with i % NDMA == dw
         constexpr int NIW = NI / NDMA;                           // instructions per tile and wave, rounded DOWN (vmcnt waits err on the safe side)
         // the (at most two) real pieces of the chunk; everything else of the record is zero padding
@@ -317,7 +310,7 @@ __global__ __launch_bounds__(NT + 64 * NDMA, 1) void conv3x3_narrow_persist_kern
     const int q4 = lx & 3;
     float* t_dstq[4];
     const float* t_resq[4];
-    bool tv_ok = THIN && DEMFI_THIN_VEC != 0;
+    bool tv_ok = THIN;
     if constexpr (THIN) {
         auto al16 = [](const void* pp, int64_t a, int64_t b, int64_t c) { return (((uintptr_t)pp) & 15) == 0 && ((a | b | c) & 3) == 0; };
 #pragma unroll
@@ -722,10 +715,9 @@ int launch_narrow(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, bo
         hipLaunchKernelGGL((conv3x3_narrow_persist_kernel<NCO, REC, 1, KS>), dim3(grid), dim3(NT + 64 * NarrowCfg<REC, KS>::NDMA), lds, st, dev);
     else {
         if constexpr (KS == 7 && NCO == 1 && REC == 32) {
-            // paired taps (P7): the chunk is one 8-channel NHWC piece + 8 zero channels; DEMFI_N7_PAIR=0: one tap per k-step (rounds 2-5)
-            static const bool pair_on = !(getenv("DEMFI_N7_PAIR") && atoi(getenv("DEMFI_N7_PAIR")) == 0);
+            // paired taps (P7): the chunk is one 8-channel NHWC piece + 8 zero channels; other chunks take one tap per k-step
             const demfi_chunk& ch = h->chunks[0];
-            if (pair_on && ch.n_pieces == 2 && h->pieces[ch.first_piece].nch == 8 && h->pieces[ch.first_piece].v.ptr && h->pieces[ch.first_piece].lds_ch == 0 &&
+            if (ch.n_pieces == 2 && h->pieces[ch.first_piece].nch == 8 && h->pieces[ch.first_piece].v.ptr && h->pieces[ch.first_piece].lds_ch == 0 &&
                 h->pieces[ch.first_piece + 1].v.ptr == nullptr) {
                 // four DMA waves: with the matrix phase at 2 400 cycles the two of the unpaired form (4 000 cycles for their 9 instructions each:
                 // per-lane piece / bounds arithmetic beside an MFMA wave) would set the period
@@ -745,7 +737,6 @@ int launch_narrow(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, bo
 
 }  // namespace
 
-DEMFI_TU_KNOB(demfi_narrow_set_knob)
 DEMFI_TU_TRACE(demfi_narrow_trace_collect)
 
 int demfi_narrow_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, bool thin, bool* handled)

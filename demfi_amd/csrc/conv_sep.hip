@@ -1,4 +1,5 @@
-// The SepConvGRU kernel of rounds 1-5 (DEMFI_GRU6=0; a unit of its own since round 6; the kernel is unchanged).  Round 6: gru.hip.
+// The SepConvGRU kernel of rounds 1-5 (a unit of its own since round 6; the kernel is unchanged).  Round 6: the fp16 plan runs the
+// GRU half-steps on gru.hip; this kernel serves the 1x5 / 5x1 layers gru.hip does not take.
 #include "conv_common.h"
 
 namespace {
@@ -29,14 +30,6 @@ constexpr int S_LDS_BYTES = S_WBYTES + S_NBUF * S_BUF_BYTES + 1024;   // + bias
 static_assert(TH * S_LL % 16 == 0, "unit buffer must be a whole number of DMA instructions");
 static_assert(3 * S_NI <= 63, "three units in flight must be countable in vmcnt");
 enum { SEP_SIG = 0, SEP_MUL = 1, SEP_GRU = 2 };
-#ifndef DEMFI_SEP_GRU_PREFETCH_UNIT
-#define DEMFI_SEP_GRU_PREFETCH_UNIT 1
-#endif
-constexpr int SEP_GRU_PREFETCH_UNIT = DEMFI_SEP_GRU_PREFETCH_UNIT;
-#ifndef DEMFI_SEP_PAIRS
-#define DEMFI_SEP_PAIRS 1        // round 3: -5 % (z|r) / -6 % (q) against one barrier per unit, same box
-#endif
-constexpr bool SEP_PAIRS = DEMFI_SEP_PAIRS != 0;
 
 struct SepArgs {
     int t_first, t_end, t_step, nh_shift, cb;
@@ -54,7 +47,7 @@ __device__ __forceinline__ void sep_item_coords(const SepArgs& a, int it, int& b
     ol0 = (rem - ts * a.tiles_l) * TW;
 }
 
-template <int EPI, int VAR>   // VAR (ablation builds only): 0 product, 1 no epilogue, 2 no MFMA phase, 3 no unit DMA, 4 no aux prefetch
+template <int EPI>
 __device__ __forceinline__ void sep_mfma_waves(const demfi_conv* __restrict__ d, const SepArgs& a, const char* wlds,
                                                const char* tbuf, const float* bias_lds, int wave, int lane)
 {
@@ -86,7 +79,7 @@ __device__ __forceinline__ void sep_mfma_waves(const demfi_conv* __restrict__ d,
         // h (and z) of this tile: unconditional clamped loads issued before the MFMA phases (see the 3x3 kernel)
         u4_t rreg[NCO][2][2] = {}, zreg[NCO][2][2] = {};
         auto prefetch_aux = [&]() {
-          if constexpr (EPI != SEP_SIG && VAR != 4 && VAR != 1) {
+          if constexpr (EPI != SEP_SIG) {
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
                 const int os = min(os0 + wave * 2 + p, Slen - 1), ol = min(ol0 + lx, Llen - 1);
@@ -117,91 +110,27 @@ __device__ __forceinline__ void sep_mfma_waves(const demfi_conv* __restrict__ d,
 #pragma unroll
             for (int i = 0; i < 16; ++i) { acc[s][0][i] = 0.0f; acc[s][1][i] = 0.0f; }
         }
-        if constexpr (SEP_PAIRS) {
-            // ---- the units in pairs: one barrier, then the ten taps of the two units as ONE software pipeline (the per-unit version
-            //      restarted it -- two exposed LDS round trips -- at every unit)
-            static_for<0, 2>([&](auto P_) {
-                constexpr int pr = decltype(P_)::value;
-                if constexpr (pr == 0) TRACE_STAMP(wave, trk, 0);
-                if constexpr (pr == 1) TRACE_STAMP(wave, trk, 4);
-                asm volatile("s_barrier" ::: "memory");
-                if constexpr (pr == 0) TRACE_STAMP(wave, trk, 1);
-                if constexpr (pr == 1) TRACE_STAMP(wave, trk, 5);
-                const char* const tb0 = tbuf + ub * S_BUF_BYTES + (wave * 2) * (S_LL * 64);
-                const char* const tb1 = tbuf + ((ub + 1) & (S_NBUF - 1)) * S_BUF_BYTES + (wave * 2) * (S_LL * 64);
-                ub = (ub + 2) & (S_NBUF - 1);
-                if constexpr (EPI == SEP_GRU && pr == (SEP_GRU_PREFETCH_UNIT >> 1)) {
-                    prefetch_aux();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (VAR == 2) return;
-                auto load_tap = [&](FragSet<NCO>& f, auto T_) {       // T = 5 * (unit of the pair) + tap
-                    constexpr int T = decltype(T_)::value, q = 2 * pr + T / 5, tap = T % 5;
-                    const char* const tb = T < 5 ? tb0 : tb1;
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-#pragma unroll
-                        for (int s = 0; s < NCO; ++s)
-                            f.a[k][s] = *(const uint4*)(wl + ((((q >> 1) * 5 + tap) * 4 + (q & 1) * 2 + k) * NCO + s) * 1024);
-                        const char* p0 = tb + boff[tap * 2 + k];
-                        f.b[k][0] = *(const uint4*)(p0);
-                        f.b[k][1] = *(const uint4*)(p0 + S_LL * 64);
-                    }
-                };
-                auto mma_tap = [&](const FragSet<NCO>& f) {
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-#pragma unroll
-                        for (int s = 0; s < NCO; ++s) {
-                            Mma<half_t>::run(acc[s][0], f.a[k][s], f.b[k][0]);
-                            Mma<half_t>::run(acc[s][1], f.a[k][s], f.b[k][1]);
-                        }
-                    }
-                };
-                auto interleave = [&]() {                               // the 8 ds_reads of the next tap 1:1 with the 8 MFMAs of the current one
-#pragma unroll
-                    for (int q8 = 0; q8 < 8; ++q8) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                };
-                FragSet<NCO> f[2];
-                load_tap(f[0], std::integral_constant<int, 0>{});
-                __builtin_amdgcn_sched_barrier(0);
-                load_tap(f[1], std::integral_constant<int, 1>{});
-                __builtin_amdgcn_sched_barrier(0);
-                mma_tap(f[0]);
-                __builtin_amdgcn_sched_barrier(0);
-                static_for<2, 10>([&](auto T_) {
-                    constexpr int T = decltype(T_)::value;
-                    load_tap(f[T & 1], T_);
-                    mma_tap(f[(T - 1) & 1]);
-                    interleave();
-                });
-                mma_tap(f[1]);
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        } else {
-        static_for<0, 4>([&](auto Q_) {
-            constexpr int q = decltype(Q_)::value;              // unit q: channels 32q .. 32q+31 of the 128
-            // unit q of this tile is in ring slot ub (the DMA wave waited for it); raw barrier: nothing of this wave
-            // has to drain (its stores and aux loads stay in flight)
-            if constexpr (q == 0) TRACE_STAMP(wave, trk, 0);
-            if constexpr (q == 2) TRACE_STAMP(wave, trk, 4);    // arrival at the third unit's barrier
-            if constexpr (!SEP_PAIRS || (q & 1) == 0) asm volatile("s_barrier" ::: "memory");
-            if constexpr (q == 0) TRACE_STAMP(wave, trk, 1);
-            if constexpr (q == 2) TRACE_STAMP(wave, trk, 5);
-            const char* tb = tbuf + ub * S_BUF_BYTES + (wave * 2) * (S_LL * 64);
-            ub = (ub + 1) & (S_NBUF - 1);
-            if constexpr (EPI == SEP_GRU && q == SEP_GRU_PREFETCH_UNIT) {
+        // ---- the units in pairs: one barrier, then the ten taps of the two units as ONE software pipeline (the per-unit version
+        //      restarted it -- two exposed LDS round trips -- at every unit; round 3: -5 % (z|r) / -6 % (q), same box)
+        static_for<0, 2>([&](auto P_) {
+            constexpr int pr = decltype(P_)::value;
+            if constexpr (pr == 0) TRACE_STAMP(wave, trk, 0);
+            if constexpr (pr == 1) TRACE_STAMP(wave, trk, 4);
+            asm volatile("s_barrier" ::: "memory");
+            if constexpr (pr == 0) TRACE_STAMP(wave, trk, 1);
+            if constexpr (pr == 1) TRACE_STAMP(wave, trk, 5);
+            const char* const tb0 = tbuf + ub * S_BUF_BYTES + (wave * 2) * (S_LL * 64);
+            const char* const tb1 = tbuf + ((ub + 1) & (S_NBUF - 1)) * S_BUF_BYTES + (wave * 2) * (S_LL * 64);
+            ub = (ub + 2) & (S_NBUF - 1);
+            if constexpr (EPI == SEP_GRU && pr == 0) {
                 prefetch_aux();
                 __builtin_amdgcn_sched_barrier(0);
             }
-            auto load_tap = [&](FragSet<NCO>& f, int tap) {
+            auto load_tap = [&](FragSet<NCO>& f, auto T_) {       // T = 5 * (unit of the pair) + tap
+                constexpr int T = decltype(T_)::value, q = 2 * pr + T / 5, tap = T % 5;
+                const char* const tb = T < 5 ? tb0 : tb1;
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
-                    // packed weights: [chunk q/2][tap][ks = (q&1)*2 + k][subtile]
 #pragma unroll
                     for (int s = 0; s < NCO; ++s)
                         f.a[k][s] = *(const uint4*)(wl + ((((q >> 1) * 5 + tap) * 4 + (q & 1) * 2 + k) * NCO + s) * 1024);
@@ -220,9 +149,7 @@ __device__ __forceinline__ void sep_mfma_waves(const demfi_conv* __restrict__ d,
                     }
                 }
             };
-            if constexpr (VAR == 2) return;
-            // the 8 ds_reads of the next tap are interleaved 1:1 with the 8 MFMAs of the current one
-            auto interleave = [&]() {
+            auto interleave = [&]() {                               // the 8 ds_reads of the next tap 1:1 with the 8 MFMAs of the current one
 #pragma unroll
                 for (int q8 = 0; q8 < 8; ++q8) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -230,42 +157,28 @@ __device__ __forceinline__ void sep_mfma_waves(const demfi_conv* __restrict__ d,
                 }
                 __builtin_amdgcn_sched_barrier(0);
             };
-            FragSet<NCO> f0, f1;
-            load_tap(f0, 0);
+            FragSet<NCO> f[2];
+            load_tap(f[0], std::integral_constant<int, 0>{});
             __builtin_amdgcn_sched_barrier(0);
-            load_tap(f1, 1);
+            load_tap(f[1], std::integral_constant<int, 1>{});
             __builtin_amdgcn_sched_barrier(0);
-            mma_tap(f0);
+            mma_tap(f[0]);
             __builtin_amdgcn_sched_barrier(0);
-            load_tap(f0, 2);
-            mma_tap(f1);
-            interleave();
-            load_tap(f1, 3);
-            mma_tap(f0);
-            interleave();
-            load_tap(f0, 4);
-            mma_tap(f1);
-            interleave();
-            mma_tap(f0);
+            static_for<2, 10>([&](auto T_) {
+                constexpr int T = decltype(T_)::value;
+                load_tap(f[T & 1], T_);
+                mma_tap(f[(T - 1) & 1]);
+                interleave();
+            });
+            mma_tap(f[1]);
             __builtin_amdgcn_sched_barrier(0);
         });
-        }
 #if defined(DEMFI_TRACE) && defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
         for (int s = 0; s < NCO; ++s) { asm volatile("" ::"v"(acc[s][0])); asm volatile("" ::"v"(acc[s][1])); }
         TRACE_STAMP(wave, trk, 2);
 #endif
         // ---- register epilogue ----
-        if constexpr (VAR == 1) {
-#pragma unroll
-            for (int s = 0; s < NCO; ++s) {
-#if defined(__HIP_DEVICE_COMPILE__)
-                asm volatile("" ::"v"(acc[s][0]));
-                asm volatile("" ::"v"(acc[s][1]));
-#endif
-            }
-            continue;
-        }
         if constexpr (EPI != SEP_SIG) {
 #pragma unroll
             for (int s = 0; s < NCO; ++s) {
@@ -326,7 +239,6 @@ __device__ __forceinline__ void sep_mfma_waves(const demfi_conv* __restrict__ d,
 #endif
 constexpr int S_NDMA = DEMFI_S_NDMA;                            // waves issuing the unit DMA (S_NI must divide evenly: exact vmcnt counts)
 static_assert(S_NI % S_NDMA == 0, "unit DMA instructions must split evenly over the DMA waves");
-template <int VAR>
 __global__ __launch_bounds__(NT + 64 * S_NDMA, 1) void conv_sep5_c128_persist_kernel(const demfi_conv* __restrict__ d)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -362,7 +274,6 @@ __global__ __launch_bounds__(NT + 64 * S_NDMA, 1) void conv_sep5_c128_persist_ke
 
     if (wave >= 4) {
         // ================= DMA waves (instruction i of a unit belongs to wave i % S_NDMA) ======================
-        if (DEMFI_KNOB_BIT(1)) __builtin_amdgcn_s_setprio(3);
         const int dw = wave - 4;
         const demfi_piece& p0 = d->pieces[d->chunks[0].first_piece];
         const demfi_piece& p1 = d->pieces[d->chunks[1].first_piece];
@@ -426,39 +337,21 @@ __global__ __launch_bounds__(NT + 64 * S_NDMA, 1) void conv_sep5_c128_persist_ke
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // weights landed: from here on vmcnt counts unit loads only
         const int n_units = 4 * ((a.t_end - a.t_first + a.t_step - 1) / a.t_step);   // >= 4
-        if constexpr (SEP_PAIRS) {
-            // units handed over in PAIRS: two barriers per tile instead of four; pair k + 1 is issued behind pair k's barrier (the MFMA waves
-            // have finished pair k - 1 when they arrive there) and has one pair's MFMA time to land
-            issue_unit(0);
-            issue_unit(1);
-            issue_unit(2);
-            issue_unit(3);
-            const int n_pairs = n_units >> 1;
-            for (int k = 0; k < n_pairs; ++k) {
-                if (k == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * S_NI / S_NDMA) : "memory");
-                else        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if ((k & 1) == 0) TRACE_STAMP(wave, k >> 1, 0);
-                __syncthreads();
-                if ((k & 1) == 0) TRACE_STAMP(wave, k >> 1, 1);
-                if (k >= 1 && k + 1 < n_pairs) { issue_unit(2 * k + 2); issue_unit(2 * k + 3); }
-                if ((k & 1) == 0) TRACE_STAMP(wave, k >> 1, 2);
-            }
-            return;
-        }
+        // units handed over in PAIRS: two barriers per tile instead of four; pair k + 1 is issued behind pair k's barrier (the MFMA waves
+        // have finished pair k - 1 when they arrive there) and has one pair's MFMA time to land
         issue_unit(0);
         issue_unit(1);
         issue_unit(2);
-        for (int u = 0; u < n_units; ++u) {
-            // units u+1, u+2 (if they exist) may stay in flight; loads retire in order
-            if (u + 2 < n_units)      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * S_NI / S_NDMA) : "memory");
-            else if (u + 1 < n_units) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(S_NI / S_NDMA) : "memory");
-            else                      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if ((u & 3) == 0) TRACE_STAMP(wave, u >> 2, 0);
-            __syncthreads();                                    // hand unit u to the MFMA waves
-            if ((u & 3) == 0) TRACE_STAMP(wave, u >> 2, 1);
-            // ring slot of unit u+3 = slot of unit u-1: every MFMA wave finished reading it before reaching this barrier
-            if (VAR != 3 && u + 3 < n_units) issue_unit(u + 3);
-            if ((u & 3) == 0) TRACE_STAMP(wave, u >> 2, 2);
+        issue_unit(3);
+        const int n_pairs = n_units >> 1;
+        for (int k = 0; k < n_pairs; ++k) {
+            if (k == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * S_NI / S_NDMA) : "memory");
+            else        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if ((k & 1) == 0) TRACE_STAMP(wave, k >> 1, 0);
+            __syncthreads();
+            if ((k & 1) == 0) TRACE_STAMP(wave, k >> 1, 1);
+            if (k >= 1 && k + 1 < n_pairs) { issue_unit(2 * k + 2); issue_unit(2 * k + 3); }
+            if ((k & 1) == 0) TRACE_STAMP(wave, k >> 1, 2);
         }
         return;
     }
@@ -469,9 +362,9 @@ __global__ __launch_bounds__(NT + 64 * S_NDMA, 1) void conv_sep5_c128_persist_ke
     // bias pre-multiplied by the scale of the epilogue's exponent: e^(2x) = 2^(2 log2(e) x) (tanh), e^(-x) = 2^(-log2(e) x) (sigmoid)
     if (tid < 64) bias_lds[tid] = d->bias[a.cb * 64 + tid] * (sg.mode == DEMFI_MODE_GRU ? 2.8853900817779268f : -1.4426950408889634f);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (sg.mode == DEMFI_MODE_GRU)      sep_mfma_waves<SEP_GRU, VAR>(d, a, wlds, tbuf, bias_lds, wave, lane);
-    else if (sg.mode == DEMFI_MODE_MUL) sep_mfma_waves<SEP_MUL, VAR>(d, a, wlds, tbuf, bias_lds, wave, lane);
-    else                                sep_mfma_waves<SEP_SIG, VAR>(d, a, wlds, tbuf, bias_lds, wave, lane);
+    if (sg.mode == DEMFI_MODE_GRU)      sep_mfma_waves<SEP_GRU>(d, a, wlds, tbuf, bias_lds, wave, lane);
+    else if (sg.mode == DEMFI_MODE_MUL) sep_mfma_waves<SEP_MUL>(d, a, wlds, tbuf, bias_lds, wave, lane);
+    else                                sep_mfma_waves<SEP_SIG>(d, a, wlds, tbuf, bias_lds, wave, lane);
 }
 
 static bool sep_eligible(const demfi_conv* h)
@@ -510,15 +403,14 @@ static bool sep_eligible(const demfi_conv* h)
     return true;
 }
 
-template <int VAR = 0>
 static int launch_sep(const demfi_conv* h, const demfi_conv* dev, hipStream_t st)
 {
-    DEMFI_LDS_ATTR((conv_sep5_c128_persist_kernel<VAR>));
+    DEMFI_LDS_ATTR((conv_sep5_c128_persist_kernel));
     const bool tr = h->kh == 5;
     const int Llen = tr ? h->H : h->W, Slen = tr ? h->W : h->H;
     const int total = ((Llen + TW - 1) / TW) * ((Slen + TH - 1) / TH) * h->batch * (h->cout_pad / 64);
     const int grid = total >= 256 ? 256 : total;              // total < 256: one item per workgroup (stride = total, even for 2 halves)
-    hipLaunchKernelGGL(conv_sep5_c128_persist_kernel<VAR>, dim3(grid), dim3(NT + 64 * S_NDMA), (size_t)S_LDS_BYTES, st, dev);
+    hipLaunchKernelGGL(conv_sep5_c128_persist_kernel, dim3(grid), dim3(NT + 64 * S_NDMA), (size_t)S_LDS_BYTES, st, dev);
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }
@@ -530,16 +422,4 @@ DEMFI_TU_TRACE(demfi_sep_trace_collect)
 
 bool demfi_sep_eligible(const demfi_conv* h) { return sep_eligible(h); }
 
-int demfi_sep_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, bool* fall_through)
-{
-    *fall_through = false;
-#ifdef DEMFI_ABLATION
-    static const int svar = getenv("DEMFI_SEP_VARIANT") ? atoi(getenv("DEMFI_SEP_VARIANT")) : 0;
-    if (svar == 1) return launch_sep<1>(h, dev, st);
-    if (svar == 2) return launch_sep<2>(h, dev, st);
-    if (svar == 3) return launch_sep<3>(h, dev, st);
-    if (svar == 4) return launch_sep<4>(h, dev, st);
-    if (svar == -1) { *fall_through = true; return DEMFI_OK; }
-#endif
-    return launch_sep(h, dev, st);
-}
+int demfi_sep_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st) { return launch_sep(h, dev, st); }

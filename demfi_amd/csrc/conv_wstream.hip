@@ -282,11 +282,6 @@ static bool wstream_eligible(const demfi_conv* h, int ks = 7, int nch = 2)
     return true;
 }
 
-static bool wstream3_on()
-{
-    static const bool on = !(getenv("DEMFI_WS3") && atoi(getenv("DEMFI_WS3")) == 0);     // A/B: 0 = the general kernel for the RDB growth convolutions
-    return on;
-}
 static int launch_wstream3(const demfi_conv* h, const demfi_conv* dev, hipStream_t st)
 {
     DEMFI_LDS_ATTR((conv_wstream_c64_kernel<3, 4, 1, 32>));
@@ -315,6 +310,5 @@ static int launch_wstream(const demfi_conv* h, const demfi_conv* dev, hipStream_
 DEMFI_TU_TRACE(demfi_wstream_trace_collect)
 
 bool demfi_wstream_eligible(const demfi_conv* h, int ks, int nch) { return wstream_eligible(h, ks, nch); }
-bool demfi_wstream3_on() { return wstream3_on(); }
 int demfi_wstream_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st) { return launch_wstream(h, dev, st); }
 int demfi_wstream3_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st) { return launch_wstream3(h, dev, st); }

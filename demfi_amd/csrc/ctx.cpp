@@ -53,13 +53,12 @@ int build_conv(int dtype, int H, int W, int stride, int batch, const float* w, c
     // most one 16-channel tail) and whose outputs are 64-channel blocks of one NHWC tensor belong to the phase-decomposed streamed-weight
     // kernel (wsconv.hip): units of 32 channels (64-byte records, a 16-channel tail padded to a whole unit), two 32-cout subtiles per
     // work item
-    static const bool ws2 = !(getenv("DEMFI_WS2") && atoi(getenv("DEMFI_WS2")) == 0);
     // ... and so do the 3x3 stride-1 layers of that output shape with >= 96 input channels (the UNet decoders dec0 / dec1 / dec2 with their
     // upsampled pieces, FGAC's w_gen): the 64 -> 64 and the narrow layers keep their own kernels
     int src_nch = 0;
     for (int i = 0; i < n_srcs; ++i) src_nch += srcs[i].nch;
     const bool ws2_s2 = stride == 2 && kh == 4 && kw == 4, ws2_s1 = stride == 1 && kh == 3 && kw == 3 && src_nch > 64;
-    bool ws2_shape = ws2 && esz == 2 && (ws2_s2 || ws2_s1) && pad_y < 0 && pad_x < 0 && n_dsts == 1 && dsts[0].n % 64 == 0 &&
+    bool ws2_shape = esz == 2 && (ws2_s2 || ws2_s1) && pad_y < 0 && pad_x < 0 && n_dsts == 1 && dsts[0].n % 64 == 0 &&
                      dsts[0].mode == DEMFI_MODE_STORE && (dsts[0].act == DEMFI_ACT_NONE || dsts[0].act == DEMFI_ACT_RELU) && dsts[0].scale <= 1 &&
                      dsts[0].dst.sc == 1 && !dsts[0].dst.is_f32 && (!dsts[0].res.ptr || (dsts[0].res.sc == 1 && !dsts[0].res.is_f32));
     for (int i = 0; ws2_shape && i < n_srcs; ++i)
@@ -87,8 +86,7 @@ int build_conv(int dtype, int H, int W, int stride, int batch, const float* w, c
         if (!sep && !persist_shape && rec == 128 && nco <= 2 && n_wg <= 5 * 256) rec = 64;
         // round 5: the RDB growth shape (3x3, <= 32 couts, >= 3 units of 32 channels from NHWC pieces) belongs to the 3x3 instantiation
         // of the streamed-weight kernel at any grid size: it walks 32-channel units (64-byte records)
-        static const bool ws3 = !(getenv("DEMFI_WS3") && atoi(getenv("DEMFI_WS3")) == 0);
-        bool rdb_shape = ws3 && !sep && esz == 2 && kh == 3 && kw == 3 && stride == 1 && sub == 1 && n_dsts == 1 && dsts[0].n == 32 && cin >= 96 && pad_y < 0 && pad_x < 0;
+        bool rdb_shape = !sep && esz == 2 && kh == 3 && kw == 3 && stride == 1 && sub == 1 && n_dsts == 1 && dsts[0].n == 32 && cin >= 96 && pad_y < 0 && pad_x < 0;
         for (int i = 0; rdb_shape && i < n_srcs; ++i) rdb_shape = srcs[i].fat && !srcs[i].up_shift && srcs[i].nch % 32 == 0;
         if (rdb_shape || ws2_shape) rec = 64;
     }
@@ -876,14 +874,10 @@ struct Builder {
         // were SLOWER (pack 23 -> 31 us per context; fat warp with the contexts innermost per tile 85 -> 73 / 90 us: the gathered
         // neighbourhoods of a tile do not survive in the 4 MB L2 across seven time instants with these incoherent flows).
         // Round 5: the fat warps too, as ONE launch with one grid slice per context (demfi_batch._pad = 1): the same tiles in the same
-        // order as tb launches, without their launch gaps and tails (a launch is ~80 us; DEMFI_WARP_TB=0: one launch per context,
-        // 2: contexts innermost per tile, the round-3 form that was slower for the rF warps)
-        static const int warp_tb = getenv("DEMFI_WARP_TB") ? atoi(getenv("DEMFI_WARP_TB")) : 1;
-        const bool fat_warp = kind == DEMFI_OP_WARP && op.nch != 3 && warp_tb != 0;
-        static const int pack_tb = getenv("DEMFI_PACK_TB") ? atoi(getenv("DEMFI_PACK_TB")) : 1;   // plane packs as one launch, grid.y = context (22 -> 4 launches per window: -0.1 ms; 0 = one launch per context)
-        const bool one_launch = kind == DEMFI_OP_CFR || (kind == DEMFI_OP_WARP && op.nch == 3) || fat_warp || (kind == DEMFI_OP_PACK && pack_tb);
-        if (one_launch) {
-            op.bt._pad = fat_warp && warp_tb == 1 ? 1 : 0;
+        // order as tb launches, without their launch gaps and tails (a launch is ~80 us).  The plane packs too, grid.y = context
+        // (22 -> 4 launches per window: -0.1 ms)
+        if (kind == DEMFI_OP_CFR || kind == DEMFI_OP_WARP || kind == DEMFI_OP_PACK) {
+            op.bt._pad = kind == DEMFI_OP_WARP && op.nch != 3 ? 1 : 0;
             auto stride = [&](const void* p) { const int64_t cs = ctx_stride_of(p); return cs > 0 ? cs : (int64_t)0; };
             op.bt.nb = tb;
             op.bt.a = cs_a > 0 ? cs_a : 0; op.bt.b = cs_b > 0 ? cs_b : 0; op.bt.o = cs_o > 0 ? cs_o : 0; op.bt.t = stride(op.t);
@@ -916,12 +910,10 @@ struct Builder {
     // residual-block kernel when the pair qualifies (fp16 plan, 3x3 64 -> 64, persistent-kernel packing): the intermediate stays in
     // LDS, the scratch buffer t is not touched -- and under the workspace arena it has NO memory (its views point at the arena's first
     // bytes, which belong to a live tenant): a RESBLOCK op must never be executed as its two convolutions on the bound workspace.  Both
-    // descriptors are kept as they are for the CPU plan interpreter (which gives the intermediate private memory, tests/plan_sim.py)
-    // and for DEMFI_RESBLOCK=0, which changes the sizing pass too (the scratch then has memory).
+    // descriptors are kept as they are for the CPU plan interpreter (which gives the intermediate private memory, tests/plan_sim.py).
     void fuse_resblock(OpList& seg, const std::string& name)
     {
-        static const bool on = !(getenv("DEMFI_RESBLOCK") && atoi(getenv("DEMFI_RESBLOCK")) == 0);
-        if (status < 0 || !on || seg.size() < 2) return;
+        if (status < 0 || seg.size() < 2) return;
         const demfi_op o2 = seg[seg.size() - 1], o1 = seg[seg.size() - 2];
         if (o1.kind != DEMFI_OP_CONV || o2.kind != DEMFI_OP_CONV) return;
         demfi_conv h1 = c->descs[o1.conv], h2 = c->descs[o2.conv];
@@ -947,12 +939,11 @@ struct Builder {
     // Round 6: one SepConvGRU half-step (DeMFInet.py:844-849 / 851-856).  conv() has just appended the three plain 64-cout layers
     //     convr: [h, x] -> r*h (MUL)     convz: [h, x] -> z (sigmoid, into the z buffer)     convq: [r*h, x] -> h' (GRU epilogue, aux = z)
     // The first becomes a launch of the round-6 kernel's R mode, the other two ONE launch of its ZQ mode (gru.hip: z stays on chip, the z
-    // buffer is never touched) when they qualify (fp16 plan).  The descriptors stay as they are: DEMFI_GRU6=0 and the CPU plan
-    // interpreter run the three layers through demfi_conv2d (the round-5 kernel at 64 couts).
+    // buffer is never touched) when they qualify (fp16 plan).  The descriptors stay as they are: the CPU plan interpreter runs the
+    // three layers through demfi_conv2d (the round-5 kernel at 64 couts).
     void fuse_gru(OpList& seg, const std::string& name)
     {
-        static const bool on = !(getenv("DEMFI_GRU6") && atoi(getenv("DEMFI_GRU6")) == 0);
-        if (status < 0 || !on || seg.size() < 3) return;
+        if (status < 0 || seg.size() < 3) return;
         const demfi_op oq = seg[seg.size() - 1], oz = seg[seg.size() - 2], orr = seg[seg.size() - 3];
         if (oq.kind != DEMFI_OP_CONV || oz.kind != DEMFI_OP_CONV || orr.kind != DEMFI_OP_CONV) return;
         demfi_conv hq = c->descs[oq.conv], hz = c->descs[oz.conv], hr = c->descs[orr.conv];
@@ -1014,8 +1005,7 @@ struct Builder {
                     zb.insert(zb.end(), ib->second.data.begin(), ib->second.data.end());
                 }
                 const Tensor& hnext = s2 == 0 ? B["h1"] : B["out"];
-                static const bool gru6_env = !(getenv("DEMFI_GRU6") && atoi(getenv("DEMFI_GRU6")) == 0);
-                if (gru6_env && c->dtype == DEMFI_F16) {         // round 6: r*h, then z + q + blend in one launch (fuse_gru)
+                if (c->dtype == DEMFI_F16) {         // round 6: r*h, then z + q + blend in one launch (fuse_gru)
                     conv(tr, "convr" + sfx, {fsrc(*h, 0), fsrc(B["x"], 64)}, {D(fview(B["rh"]), range(0, 64), DEMFI_ACT_NONE, DEMFI_MODE_MUL, fview(*h))}, H, W, 1, nb);
                     conv(tr, "convz" + sfx, {fsrc(*h, 0), fsrc(B["x"], 64)}, {D(fview(B["z"]), range(0, 64), S)}, H, W, 1, nb);
                     conv(tr, "convq" + sfx, {fsrc(B["rh"], 0), fsrc(B["x"], 64)},
@@ -1096,9 +1086,8 @@ struct Builder {
         }
         // UPNet.2 (3x3, 64 -> 133 = F0 | F1 | flow_01, flow_10, occlusion logit; DeMFInet.py:231, 247-253).  Round 6, fp16 plan: one launch per
         // output group -- the two tanh feature halves on the staged-store 64 -> 64 kernel, the 5 planes on the thin-output kernel -- instead
-        // of ONE 160-cout launch of the general kernel (0.32 ms at 0.18 of the matrix peak).  DEMFI_UP2_SPLIT=0: the single launch.
-        static const bool up2_split = !(getenv("DEMFI_UP2_SPLIT") && atoi(getenv("DEMFI_UP2_SPLIT")) == 0);
-        if (c->dtype == DEMFI_F16 && up2_split) {
+        // of ONE 160-cout launch of the general kernel (0.32 ms at 0.18 of the matrix peak).
+        if (c->dtype == DEMFI_F16) {
             SubW w0 = sub_weight_cout(p + "UPNet.2", 0, 64), w1 = sub_weight_cout(p + "UPNet.2", 64, 64), w2 = sub_weight_cout(p + "UPNet.2", 128, 5);
             conv(tr, p + "UPNet.2#F0", {fsrc(B["up"], 0)}, {D(fview(B["F01"], 0, 0), range(0, 64), T)}, H, W, 1, 1, &w0.w, &w0.b, &w0.shape);
             conv(tr, p + "UPNet.2#F1", {fsrc(B["up"], 0)}, {D(fview(B["F01"], 0, 1), range(0, 64), T)}, H, W, 1, 1, &w1.w, &w1.b, &w1.shape);
@@ -1218,7 +1207,6 @@ struct Builder {
         const Tensor& aF = TB["aF"];
         const Tensor& x = TB["x"];
         const void* tp = ptr(B["t"]);
-        static const bool cfr_pack = !(getenv("DEMFI_CFR_PACK") && atoi(getenv("DEMFI_CFR_PACK")) == 0);
         auto delta_v = [&](int step, int ch) { return tview(B["delta"], 5 * step + ch); };
         auto delta_p = [&](int step, int ch) { return plane(B["delta"], 5 * step + ch); };
         // ============================ per-t head: CFR, FWB, refinement, D1, Ch_Reducer ==============================
@@ -1226,20 +1214,14 @@ struct Builder {
             demfi_op o = blank();
             o.p[0] = ptr(ffo); o.p[1] = ptr(ffo) + 2 * hw4; o.p[2] = ptr(B["cfr_acc"]); o.p[3] = ptr(B["ft"]); o.t = tp;
             // round 6: the finish also writes misc16 = [flow_t0, flow_t1 | flow_01, flow_10, occ logit | 0] (the thin members of Agg1, 77) as the
-            // NHWC record enc1 stages: one plane-pack launch per window less (DEMFI_CFR_PACK=0: the pack launch of rounds 1-5)
-            if (cfr_pack) { o.p[4] = ptr(ffo) + 4 * hw4; o.p[5] = ptr(B["misc16"]); }
+            // NHWC record enc1 stages: one plane-pack launch per window less
+            o.p[4] = ptr(ffo) + 4 * hw4; o.p[5] = ptr(B["misc16"]);
             simple(th, DEMFI_OP_CFR, "cfr", o);
         }
         warp(th, "warp_fat", 64, fview(TB["F01"], 0, 0), fview(TB["F01"], 0, 1), fview(B["Ft"], 0, 0), ptr(B["ft"]), ptr(B["ft"]) + 2 * hw4,
              ptr(ffo) + 4 * hw4, nullptr, tp);
         std::string p = "Refine_Module.";
         // Agg1 = cat[aF0, aF1, Ft, flow_t0, flow_t1, flow_01, flow_10, occ_0_logit] (DeMFInet.py:77)
-        if (!cfr_pack) {
-            std::vector<const float*> pl;
-            for (int i = 0; i < 4; ++i) pl.push_back(plane(B["ft"], i));
-            for (int i = 0; i < 5; ++i) pl.push_back(plane(ffo, i));
-            pack(th, pl, B["misc16"]);
-        }
         {
             std::vector<int32_t> m = range(192, 201);
             m.insert(m.end(), 7, -1);
@@ -1286,8 +1268,7 @@ struct Builder {
             // planes to a 32-cout launch.
             const Layer l9 = {l3.cout, l3.cin, 3, 3};
             // round 6: the flow / occlusion planes of the two column parities of a row parity in ONE launch (10 couts = 4 live octets of a
-            // 32-cout subtile that the per-parity launches filled with 5): 4 -> 2 launches of the thin kernel (DEMFI_DEC3F_PAIR=0: one per parity)
-            static const bool f_pair = !(getenv("DEMFI_DEC3F_PAIR") && atoi(getenv("DEMFI_DEC3F_PAIR")) == 0);
+            // 32-cout subtile that the per-parity launches filled with 5): 4 -> 2 launches of the thin kernel
             for (int dy = 0; dy < 2 && status >= 0; ++dy) {
                 std::vector<float> wf2, bf2;
                 for (int dx = 0; dx < 2 && status >= 0; ++dx) {
@@ -1316,27 +1297,19 @@ struct Builder {
                     };
                     std::vector<float> wa, ba, wb, bb, wf, bf;
                     slice(5, 69, wa, ba); slice(69, 133, wb, bb); slice(0, 5, wf, bf);
-                    const Layer l64 = {64, l3.cin, 3, 3}, l5 = {5, l3.cin, 3, 3};
+                    const Layer l64 = {64, l3.cin, 3, 3};
                     conv(th, nm + "a", {fsrc(B["d2"], 0)},
                          {D(phase_view(fview(B["rF"], 0, 0), dy, dx), range(0, 64), T, DEMFI_MODE_STORE, phase_view(fview(aF, 0, 0), dy, dx))},
                          H2, W2, 1, 1, &wa, &ba, &l64);
                     conv(th, nm + "b", {fsrc(B["d2"], 0)},
                          {D(phase_view(fview(B["rF"], 0, 1), dy, dx), range(0, 64), T, DEMFI_MODE_STORE, phase_view(fview(aF, 0, 1), dy, dx))},
                          H2, W2, 1, 1, &wb, &bb, &l64);
-                    if (f_pair) {
-                        wf2.insert(wf2.end(), wf.begin(), wf.end());
-                        bf2.insert(bf2.end(), bf.begin(), bf.end());
-                        continue;
-                    }
-                    // the 5 planes also go, as fp16, into the record Mixer.conv_delta1 stages (delta16): no plane-packing launch
-                    pack_next(phase_view(fview(B["delta16"]), dy, dx), 0, 4);
-                    conv(th, nm + "f", {fsrc(B["d2"], 0)},
-                         {D(phase_view(delta_v(0, 0), dy, dx), range(0, 4), DEMFI_ACT_NONE, DEMFI_MODE_STORE, phase_view(tview(B["ft"]), dy, dx)),
-                          D(phase_view(delta_v(0, 4), dy, dx), {4}, DEMFI_ACT_NONE, DEMFI_MODE_STORE, phase_view(tview(ffo, 4), dy, dx))},
-                         H2, W2, 1, 1, &wf, &bf, &l5);
+                    wf2.insert(wf2.end(), wf.begin(), wf.end());
+                    bf2.insert(bf2.end(), bf.begin(), bf.end());
                 }
-                if (f_pair && status >= 0) {
-                    // couts 0..4: column parity 0, 5..9: column parity 1; the packed copy of parity 1 lies one pixel (16 channels) further in delta16
+                if (status >= 0) {
+                    // couts 0..4: column parity 0, 5..9: column parity 1; the 5 planes also go, as fp16, into the record Mixer.conv_delta1
+                    // stages (delta16): no plane-packing launch.  The packed copy of parity 1 lies one pixel (16 channels) further in delta16
                     const Layer l10 = {10, l3.cin, 3, 3};
                     pack_next(phase_view(fview(B["delta16"]), dy, 0), 0, 4, 16, 20);
                     conv(th, p + "dec3#p" + std::to_string(dy) + "xf", {fsrc(B["d2"], 0)},
@@ -1414,28 +1387,12 @@ struct Builder {
         // Dec_first_2 = relu(conv3x3(Agg3)) with Agg3 = cat[F_rec (64, changes per recursion) | 27 recursion-invariant planes |
         // 8 planes of the current recursion] (DeMFInet.py:151-157), split by linearity in the fp16 plan (see below).
         const std::vector<int32_t> a3d_sel = {6, 7, 8, 82, 83, 84, 85, 86};
-        SubW w_dyn, w_rec, w_df2;
-        std::vector<int32_t> dyn_m16 = range(0, 11), df2_m16, df2_m8;
-        // round 6 EXPERIMENT (DEMFI_DF2_FUSE=1; the product keeps the two launches of rounds 2-5): ONE launch per recursion on the
-        // streamed-weight kernel (wsconv.hip): units [F_rec lo | F_rec hi | ref16 + agg3d + 0], the window-constant share (g_pw) as the
-        // residual, so that the partial sum g_p2 makes no round trip through HBM (256 B per pixel and recursion).  Built, parity-green,
-        // measured 0.98 ms against 0.44 + 0.51 ms (same box): the kernel's epilogue (64 KiB of residual loads + 64 KiB of stores issued by
-        // the MFMA waves themselves) costs 15 000 of an item's 33 000 cycles (profiles/r06_notes.md section 6, the phase stamps).
-        static const bool df2_fuse = getenv("DEMFI_DF2_FUSE") && atoi(getenv("DEMFI_DF2_FUSE")) != 0 &&
-                                     !(getenv("DEMFI_WS2") && atoi(getenv("DEMFI_WS2")) == 0);
-        if (c->dtype == DEMFI_F16 && df2_fuse) {
-            std::vector<int32_t> sel = range(9, 73);                 // F_rec -> sub-layer inputs 0..63
-            for (int i = 0; i < 6; ++i) sel.push_back(i);            // S0p, S1p -> 64..69
-            for (int i = 73; i < 78; ++i) sel.push_back(i);          // occ_0 -> 70; rflow_t0, rflow_t1 -> 71..74
-            sel.insert(sel.end(), a3d_sel.begin(), a3d_sel.end());   // the 8 planes of the recursion -> 75..82
-            w_df2 = sub_weight("Dec_first_2", sel, true);
-            // ref16 = [S0p, S1p, Stp | rflow_t0, rflow_t1, occ logit | occ_0 | 0]
-            df2_m16 = {64, 65, 66, 67, 68, 69, -1, -1, -1, 71, 72, 73, 74, -1, 70, -1};
-            df2_m8 = range(75, 83);
-        } else
+        SubW w_dyn, w_rec;
+        std::vector<int32_t> dyn_m16 = range(0, 11);
         if (c->dtype == DEMFI_F16) {
             // per recursion: ONE narrow launch over [ref16 (its 11 planes Agg3 holds: t-dependent, recursion-invariant) | agg3d (8 planes of this
-            // recursion)] + bias + the window-constant share (g_pw, trunk) -> g_p2; then the F_rec part on the 64 -> 64 kernel
+            // recursion)] + bias + the window-constant share (g_pw, trunk) -> g_p2; then the F_rec part on the 64 -> 64 kernel.  ONE launch
+            // on wsconv.hip with g_pw as the residual was measured slower (0.98 ms against 0.44 + 0.51 ms, profiles/r06_notes.md section 6)
             std::vector<int32_t> sel = range(0, 6);                  // S0p, S1p | occ_0 | rflow_t0, rflow_t1 (agg16 order)
             for (int i = 73; i < 78; ++i) sel.push_back(i);
             sel.insert(sel.end(), a3d_sel.begin(), a3d_sel.end());
@@ -1446,9 +1403,8 @@ struct Builder {
             dyn_m16 = {0, 1, 2, 3, 4, 5, -1, -1, -1, 7, 8, 9, 10, -1, 6, -1};
         }
         // ============================ recursive boosting, one list per iteration ====================================
-        // SepConvGRU (838-857): z | r share their input -> one 128-cout conv (fp32 plan, DEMFI_GRU6=0); round 6, fp16: see fuse_gru
-        static const bool gru6_env = !(getenv("DEMFI_GRU6") && atoi(getenv("DEMFI_GRU6")) == 0);
-        const bool gru6 = gru6_env && c->dtype == DEMFI_F16;
+        // SepConvGRU (838-857): z | r share their input -> one 128-cout conv (fp32 plan); round 6, fp16: see fuse_gru
+        const bool gru6 = c->dtype == DEMFI_F16;
         std::vector<float> zrw[2], zrb[2];
         const Layer zr_shape[2] = {{128, 128, 1, 5}, {128, 128, 5, 1}};
         for (int s = 0; s < 2 && status >= 0 && !dry && !gru6; ++s) {
@@ -1511,10 +1467,6 @@ struct Builder {
             // (DeMFInet.py:151-155) as the NHWC record Dec_first_2 reads (agg3d): no plane-packing launch
             warp(sg, "warp_thin", 3, tview(B["sharp1"], 0), tview(B["sharp1"], 3), tview(B["stnew"]), delta_p(it + 1, 0), delta_p(it + 1, 2),
                  delta_p(it + 1, 4), plane(B["occ"], it + 1), tp, ptr(B["agg3d"]));
-            if (c->dtype == DEMFI_F16 && df2_fuse) {
-                conv(sg, "Dec_first_2#t", {fsrc(hout, 0), fsrc_map(B["ref16"], df2_m16), fsrc_map(B["agg3d"], df2_m8)},
-                     {D(fview(B["g_a"]), range(0, 64), R, DEMFI_MODE_STORE, fview(TB["g_pw"]))}, H, W, 1, 1, &w_df2.w, &w_df2.b, &w_df2.shape);
-            } else
             if (c->dtype == DEMFI_F16) {
                 conv(sg, "Dec_first_2#dyn", {fsrc_map(B["ref16"], dyn_m16), fsrc_map(B["agg3d"], range(11, 19))},
                      {D(fview(B["g_p2"]), range(0, 64), DEMFI_ACT_NONE, DEMFI_MODE_STORE, fview(TB["g_pw"]))}, H, W, 1, 1, &w_dyn.w, &w_dyn.b,

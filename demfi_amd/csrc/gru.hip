@@ -7,7 +7,7 @@
 // (640 B/px at 4.9 TB/s, profiles/r03_gru_hbm_bytes_pmc.txt).  This file splits the step the other way round:
 //     launch R  : r * h                         (reads h, x; writes r * h)                           384 B/px
 //     launch ZQ : z AND q AND the blend         (reads h, r * h, x; writes h')                       512 B/px
-// z never leaves the CU: the z waves hand it to the q waves through LDS (rounded to fp16 exactly as the stored z was).
+// z never leaves the CU: it meets q~ in the lane that blends them.
 //
 // Tile orientation: the MFMA's 32-pixel axis runs ACROSS the filter axis, lines run ALONG it, so a filter
 // tap shifts the LINE index: the B fragment of input line l serves output line p at tap l - p, one ds_read_b128 feeds up to five
@@ -16,11 +16,11 @@
 // fragments do not live in LDS: one global_load_dwordx4 per (tap, k-step) from the packed, L2-resident weights into a register ring
 // (resblock.hip's scheme), which is what frees the LDS for whole 64-channel windows.
 //
-// ZQ: a workgroup = 4 MFMA waves (z cout halves, q cout halves) + 4 helper waves, tile = 32 pixels x 8 lines, three window pieces
-// of 12 lines x 32 px x 128 B in LDS (h | r*h | x = 144 KiB), each with a fixed address and refilled for the next tile as soon as the
-// last wave is done with it.  Phase A: the z waves contract h, the q waves r*h; phase B: both contract x.  Then z -> sigmoid ->
-// fp16 -> LDS (into the x piece, dead by then), the q waves tanh their accumulators, blend with z and h (h prefetched from global)
-// and stage h' as fp16 in the same place; the helper waves store it as whole 128-byte lines (streaming) and issue the DMA.
+// ZQ: a workgroup = 4 MFMA waves (cout half x line half, both gates in each) + 4 helper waves, tile = 32 pixels x 8 lines, three window
+// pieces of 12 lines x 32 px x 128 B in LDS (h | r*h | x = 144 KiB), each with a fixed address and refilled for the next tile as soon as
+// the last wave is done with it.  A wave contracts h with z's weights, r*h with q's, then x with both; its epilogue (sigmoid, tanh, blend
+// with h prefetched from global) stages h' as fp16 in the x piece (dead by then); the helper waves store it as whole 128-byte lines
+// (streaming) and issue the DMA.
 // R: tile = 32 pixels x 16 lines, wave = cout half x line half, pieces x | h of 20 lines (160 KiB), sigmoid * h from the h window.
 #include "common.h"
 #include <cstdlib>
@@ -32,18 +32,14 @@ namespace {
 constexpr int G_LS = 32 * 128;                                   // bytes per window line (32 records of 64 channels)
 constexpr int G_NH = 4;                                          // helper waves
 constexpr int G_NTHREADS = 256 + 64 * G_NH;
-#ifndef DEMFI_ZQS_PRIME_EARLY
-#define DEMFI_ZQS_PRIME_EARLY 0
-#endif
 #ifndef DEMFI_GRU_DEPTH
 #define DEMFI_GRU_DEPTH 4                                        // A prefetch distance in steps of 8 MFMAs
 #endif
 constexpr int G_DEPTH = DEMFI_GRU_DEPTH;
 constexpr int G_NSTEP = 20;                                      // (k-step, tap) steps per 64-channel piece
 static_assert(G_NSTEP % G_DEPTH == 0, "static ring indices");
-enum { GM_ZQ = 0, GM_R = 1, GM_ZQS = 2 };                        // ZQS: ZQ with both gates of a cout block in one wave (below)
+enum { GM_R = 1, GM_ZQS = 2 };                                   // ZQS: z and q with both gates of a cout block in one wave (below)
 template <int MODE> struct GCfg;
-template <> struct GCfg<GM_ZQ>  { static constexpr int TL = 8, WL = 12, NPIECE = 3, LDS = 3 * 12 * G_LS; };
 template <> struct GCfg<GM_R>   { static constexpr int TL = 16, WL = 20, NPIECE = 2, LDS = 2 * 20 * G_LS; };
 template <> struct GCfg<GM_ZQS> { static constexpr int TL = 8, WL = 12, NPIECE = 3, LDS = 3 * 12 * G_LS + 512; };   // + 128 bias floats
 static_assert(GCfg<GM_R>::LDS <= 160 * 1024 && GCfg<GM_ZQS>::LDS <= 160 * 1024, "LDS budget");
@@ -310,7 +306,6 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
                 // ... r*h (8) under the sigmoid / tanh pass.  Both there (16) delay barrier D by ~1 400 cycles: measured, profiles/r06_notes.md
                 if (more) issue_piece(a.rh, S1, nimg, nP0, nL0, carry);
                 G_STAMP(wave, trk, 3);
-                if constexpr (MODE == GM_ZQ) asm volatile("s_barrier" ::: "memory");         // D: q~ is in LDS  (ZQS: wave-local epilogue, no D)
                 bool exact = false;
                 if (have_prev) exact = do_stores(pimg, pP0, pL0);                          // the previous tile's outputs (8 stores) under the blend
                 if (exact) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TL) : "memory");      // the next tile's h, r*h (older than the stores) have landed:
@@ -368,7 +363,7 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
 
     // ================= MFMA waves, ZQS ===========================================================================
     // Both gates of a cout block in one wave: wave = cout half cs x line half lh, four z and four q accumulators (4 lines x 32 couts each).
-    // What that buys over ZQ (where two waves own z and two own q, 8 lines each): the epilogue is wave-local -- no q~ exchange through LDS and
+    // What that bought over the round-6a form (two waves owned z and two q, 8 lines each): the epilogue is wave-local -- no q~ exchange through LDS and
     // no barrier D; z and q~ of an output meet in one lane, so h' = h + ((b - 1) - h (b + 1)) / ((b + 1)(1 + a)) with a = e^-z', b = e^2q' takes
     // THREE transcendentals per output instead of four (the pass sits on the quarter-rate transcendental unit); and the blend runs on all four
     // SIMDs instead of the z waves' two.  What it costs: one A fragment per four MFMAs instead of eight in the h and r*h phases (the x phase feeds
@@ -528,10 +523,6 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
 #endif
                 __builtin_amdgcn_sched_barrier(0);               // ALL of pass 1 first (interleaved with pass 2, the first h load's latency was exposed)
                 G_STAMP(wave, trk, 6);
-#if DEMFI_ZQS_PRIME_EARLY
-                prime();                                         // the next tile's first A fragments: in flight under pass 2
-                __builtin_amdgcn_sched_barrier(0);
-#endif
                 // pass 2: h' = h + ((b - 1) - h (b + 1)) r, fp16, staged in the x piece (line lh 4 + p) for the helpers' whole-line stores
                 g_for<0, 4>([&](auto P) {
                     constexpr int p = decltype(P)::value;
@@ -556,9 +547,7 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
                 });
             }
             G_STAMP(wave, trk, 7);
-#if !DEMFI_ZQS_PRIME_EARLY
             prime();
-#endif
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             G_STAMP(wave, trk, 8);
             asm volatile("s_barrier" ::: "memory");             // E: h' is staged; the next tile's h, r*h have landed
@@ -569,14 +558,14 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
         return;
     }
 
-    // ================= MFMA waves ================================================================================
+    // ================= MFMA waves, R ============================================================================
     const int hi = lane >> 5, lx = lane & 31;
-    const int cs = wave & 1, role = wave >> 1;                   // cout half; ZQ: 0 = z, 1 = q;  R: line half
+    const int cs = wave & 1, role = wave >> 1;                   // cout half, line half
     const unsigned lane16 = lane * 16;
     // weights of this wave: chunk 0 / chunk 1 in the order the phases walk them
-    const char* const wA = (MODE == GM_ZQ ? (role ? a.w1[0] : a.w0[0]) : a.w0[1]) + cs * 1024;     // phase A: ZQ h / r*h; R: x
-    const char* const wB = (MODE == GM_ZQ ? (role ? a.w1[1] : a.w0[1]) : a.w0[0]) + cs * 1024;     // phase B: ZQ x;       R: h
-    const float* const bias = (MODE == GM_ZQ && role) ? a.b1 : a.b0;
+    const char* const wA = a.w0[1] + cs * 1024;                  // phase A: x
+    const char* const wB = a.w0[0] + cs * 1024;                  // phase B: h
+    const float* const bias = a.b0;
     const int boff0 = lx * 128 + ((hi ^ ((lx >> 1) & 7)) << 4);  // B fragment of k-step ks: boff0 ^ (ks << 5) (swizzle touches bits 4-6 only)
     auto boff = [&](auto KS) {
         int b = boff0;
@@ -666,196 +655,59 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
     int it = it0;
     [[maybe_unused]] int trk = 0;
     f16x_t c1;
-    load_bias(c1);
-    if constexpr (MODE == GM_ZQ) {
-        G_STAMP(wave, trk, 0);
-        asm volatile("s_barrier" ::: "memory");                 // A0: the first tile's h, r*h have landed (later tiles: barrier E says so)
-    }
     for (;;) {
         int img, P0, L0;
         pos_of(it, img, P0, L0);
-        if constexpr (MODE == GM_R) load_bias(c1);
-        if constexpr (MODE == GM_ZQ) {
-            const bool is_q = role != 0;
-            G_STAMP(wave, trk, 1);
-            conv_phase(is_q ? S1 : S0, wA, wB, std::true_type{}, c1, std::false_type{});
-            G_STAMP(wave, trk, 2);
-            asm volatile("s_barrier" ::: "memory");             // B: x has landed; h, r*h are free
-            G_STAMP(wave, trk, 3);
-            {
-                const f16x_t none = {};
-                conv_phase(S2, wB, wA, std::false_type{}, none, std::true_type{});
-            }
-#if defined(DEMFI_TRACE) && defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("" ::"v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]));
-#endif
-            G_STAMP(wave, trk, 4);
-            asm volatile("s_barrier" ::: "memory");             // C: the x piece is free
-            G_STAMP(wave, trk, 5);
-            // two separate paths from here to the end of the tile (barriers D, E inside both): merged, the allocator carried a second copy
-            // of the accumulators through the other path and spilled.  The multiplies / adds are packed fp32 (v_pk_*: two values per issue
-            // slot; a lone wave's epilogue is priced by its instruction count), the transcendentals cannot be.
-            if (is_q) {
-                // q~ = tanh(.) = 1 - 2 / (1 + e^(2 .)), 16 values at a time (the transcendentals' latency needs the ILP), handed to the z waves
-                // as fp16 through the x piece
-                g_for<0, 8>([&](auto P) {
-                    constexpr int p = decltype(P)::value;
-                    f2_t v[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        f2_t e = f2_t{acc[p][2 * i], acc[p][2 * i + 1]} * KS_TANH;
-                        e = f2_t{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)} + 1.0f;
-                        e = f2_t{__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
-                        v[i] = e * -2.0f + 1.0f;
-                    }
-#pragma unroll
-                    for (int m2 = 0; m2 < 2; ++m2) {
-                        h8_t o;
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {           // quads 2 m2, 2 m2 + 1 = pairs 4 m2 .. 4 m2 + 3
-                            o[2 * j] = (half_t)v[4 * m2 + j].x;
-                            o[2 * j + 1] = (half_t)v[4 * m2 + j].y;
-                            o[4 + 2 * j] = (half_t)v[4 * m2 + 2 + j].x;
-                            o[4 + 2 * j + 1] = (half_t)v[4 * m2 + 2 + j].y;
-                        }
-                        *(u4_t*)(S2 + p * G_LS + soff[m2]) = __builtin_bit_cast(u4_t, o);
-                    }
-                });
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                G_STAMP(wave, trk, 6);
-                asm volatile("s_barrier" ::: "memory");         // D: q~ is in LDS
-                G_STAMP(wave, trk, 7);
-                g_for<0, G_DEPTH>([&](auto T) { A[decltype(T)::value] = a_load(wA, T); });
-                load_bias(c1);
-                G_STAMP(wave, trk, 8);
-                asm volatile("s_barrier" ::: "memory");         // E: h' is staged; the next tile's h, r*h have landed
-            } else {
-                // z waves: z = sigmoid(.) stays in the accumulators (fp32); then the blend h' = h + z (q~ - h) for this wave's values.
-                // h: clamped addresses, unconditional loads, two lines per batch, three batches in flight
-                const char* hb = a.h.ptr + (int64_t)img * a.h.sb + (int64_t)min(P0 + lx, a.Plen - 1) * a.h.sp + (cs * 32 + hi * 8) * 2;
-                u4_t hreg[3][2][2];
-                auto h_fetch = [&](auto PB) {
-                    constexpr int pb = decltype(PB)::value;
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        const char* hp = hb + (int64_t)min(L0 + pb + p, a.Llen - 1) * a.h.sl;
-                        hreg[(pb >> 1) % 3][p][0] = *gcp<u4_t>(hp);
-                        hreg[(pb >> 1) % 3][p][1] = *gcp<u4_t>(hp + 32);
-                    }
-                };
-                h_fetch(std::integral_constant<int, 0>{});
-                h_fetch(std::integral_constant<int, 2>{});
-                h_fetch(std::integral_constant<int, 4>{});
-                __builtin_amdgcn_sched_barrier(0);               // the loads go out BEFORE the sigmoids (the scheduler sank them to the barrier)
-                g_for<0, 8>([&](auto P) {
-                    constexpr int p = decltype(P)::value;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        f2_t e = f2_t{acc[p][2 * i], acc[p][2 * i + 1]} * KS_SIG;
-                        e = f2_t{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)} + 1.0f;
-                        acc[p][2 * i] = __builtin_amdgcn_rcpf(e.x);
-                        acc[p][2 * i + 1] = __builtin_amdgcn_rcpf(e.y);
-                    }
-                });
-#if defined(__HIP_DEVICE_COMPILE__)
-                // the sigmoids run HERE, beside the q waves' tanh (pure register arithmetic would otherwise sink below the barrier)
-                asm volatile("" ::"v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]));
-#endif
-                G_STAMP(wave, trk, 6);
-                asm volatile("s_barrier" ::: "memory");         // D: q~ is in LDS
-                G_STAMP(wave, trk, 7);
-                g_for<0, 4>([&](auto PP) {
-                    constexpr int pb = 2 * decltype(PP)::value;
-                    // both lines' q~ first (four LDS reads in flight), then the differences, then the packed fmas: independent chains side by side
-                    u4_t qq[2][2];
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-                        for (int m2 = 0; m2 < 2; ++m2) qq[p][m2] = *(const u4_t*)(S2 + (pb + p) * G_LS + soff[m2]);
-                    }
-                    g_for<0, 2>([&](auto P) {
-                        constexpr int p = pb + decltype(P)::value;
-#pragma unroll
-                        for (int m2 = 0; m2 < 2; ++m2) {
-                            const u4_t rr = hreg[(pb >> 1) % 3][p - pb][m2];
-                            const u4_t qv = qq[p - pb][m2];
-                            float dl[8];
-#pragma unroll
-                            for (int d = 0; d < 4; ++d) {
-                                dl[2 * d] = g_sub16_lo(qv[d], rr[d]);
-                                dl[2 * d + 1] = g_sub16_hi(qv[d], rr[d]);
-                            }
-                            u4_t o = {0u, 0u, 0u, 0u};
-#pragma unroll
-                            for (int d = 0; d < 4; ++d) {       // dword d = channels 2 d, 2 d + 1 of the lane's 8: quad 2 m2 + (d >> 1), elements 2 (d & 1), + 1
-                                const int i0 = (2 * m2 + (d >> 1)) * 4 + 2 * (d & 1);
-                                unsigned pk = 0u;
-                                g_fma16_lo(pk, acc[p][i0], dl[2 * d], rr[d]);
-                                g_fma16_hi(pk, acc[p][i0 + 1], dl[2 * d + 1], rr[d]);
-                                o[d] = pk;
-                            }
-                            *(u4_t*)(S2 + p * G_LS + soff[m2]) = o;
-                        }
-                    });
-                    if constexpr (pb + 6 < 8) h_fetch(std::integral_constant<int, pb + 6>{});
-                });
-                g_for<0, G_DEPTH>([&](auto T) { A[decltype(T)::value] = a_load(wA, T); });
-                load_bias(c1);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                G_STAMP(wave, trk, 8);
-                asm volatile("s_barrier" ::: "memory");         // E: h' is staged; the next tile's h, r*h have landed
-            }
-        } else {
-            // R: phase A contracts x (piece 0), phase B h (piece 1); r * h from the h window's centre lines
-            const char* const t0 = S0 + role * 8 * G_LS;
-            const char* const t1 = S1 + role * 8 * G_LS;
-            G_STAMP(wave, trk, 0);
-            asm volatile("s_barrier" ::: "memory");             // A
-            G_STAMP(wave, trk, 1);
-            conv_phase(t0, wA, wB, std::true_type{}, c1, std::false_type{});
-            G_STAMP(wave, trk, 2);
-            asm volatile("s_barrier" ::: "memory");             // B
-            G_STAMP(wave, trk, 3);
-            {
-                const f16x_t none = {};
-                conv_phase(t1, wB, wA, std::false_type{}, none, std::false_type{});
-            }
-#if defined(DEMFI_TRACE) && defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("" ::"v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]));
-#endif
-            G_STAMP(wave, trk, 4);
-            // r * h: h from the window's centre lines; barrier C (the h piece is free) AFTER the epilogue.  Measured alternative (round 6): h
-            // into registers first and C before the epilogue, so that the helpers issue the next h under it -- the tile got 20 % SLOWER
-            // (epilogue + stores 5 500 -> 11 200 cycles: the helpers' DMA and these 16 partial-line stores share the CU's memory pipe)
-            char* const ob = a.dst + (int64_t)img * a.d_sb + (int64_t)(P0 + lx) * a.d_sp + (cs * 32 + hi * 8) * 2;
-            const bool pok = P0 + lx < a.Plen;
-            g_for<0, 8>([&](auto P) {
-                constexpr int p = decltype(P)::value;
-                const int l = L0 + role * 8 + p;
-                f2_t sg[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {                    // sigmoid, 16 values at a time, packed multiplies / adds
-                    f2_t e = f2_t{acc[p][2 * i], acc[p][2 * i + 1]} * KS_SIG;
-                    e = f2_t{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)} + 1.0f;
-                    sg[i] = f2_t{__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
-                }
-#pragma unroll
-                for (int m2 = 0; m2 < 2; ++m2) {
-                    const h8_t r = __builtin_bit_cast(h8_t, *(const u4_t*)(t1 + (2 + p) * G_LS + soff[m2]));
-                    h8_t o;
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {               // quads 2 m2, 2 m2 + 1 = pairs 4 m2 .. 4 m2 + 3
-                        o[2 * j] = (half_t)__builtin_fmaf(sg[4 * m2 + j].x, (float)r[2 * j], 0.0f);
-                        o[2 * j + 1] = (half_t)__builtin_fmaf(sg[4 * m2 + j].y, (float)r[2 * j + 1], 0.0f);
-                        o[4 + 2 * j] = (half_t)__builtin_fmaf(sg[4 * m2 + 2 + j].x, (float)r[4 + 2 * j], 0.0f);
-                        o[4 + 2 * j + 1] = (half_t)__builtin_fmaf(sg[4 * m2 + 2 + j].y, (float)r[4 + 2 * j + 1], 0.0f);
-                    }
-                    if (pok && l < a.Llen) *gp<u4_t>(ob + (int64_t)l * a.d_sl + m2 * 32) = __builtin_bit_cast(u4_t, o);
-                }
-            });
-            G_STAMP(wave, trk, 5);
-            asm volatile("s_barrier" ::: "memory");             // C: the h piece is free
+        load_bias(c1);
+        // R: phase A contracts x (piece 0), phase B h (piece 1); r * h from the h window's centre lines
+        const char* const t0 = S0 + role * 8 * G_LS;
+        const char* const t1 = S1 + role * 8 * G_LS;
+        G_STAMP(wave, trk, 0);
+        asm volatile("s_barrier" ::: "memory");             // A
+        G_STAMP(wave, trk, 1);
+        conv_phase(t0, wA, wB, std::true_type{}, c1, std::false_type{});
+        G_STAMP(wave, trk, 2);
+        asm volatile("s_barrier" ::: "memory");             // B
+        G_STAMP(wave, trk, 3);
+        {
+            const f16x_t none = {};
+            conv_phase(t1, wB, wA, std::false_type{}, none, std::false_type{});
         }
+#if defined(DEMFI_TRACE) && defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" ::"v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]));
+#endif
+        G_STAMP(wave, trk, 4);
+        // r * h: h from the window's centre lines; barrier C (the h piece is free) AFTER the epilogue.  Measured alternative (round 6): h
+        // into registers first and C before the epilogue, so that the helpers issue the next h under it -- the tile got 20 % SLOWER
+        // (epilogue + stores 5 500 -> 11 200 cycles: the helpers' DMA and these 16 partial-line stores share the CU's memory pipe)
+        char* const ob = a.dst + (int64_t)img * a.d_sb + (int64_t)(P0 + lx) * a.d_sp + (cs * 32 + hi * 8) * 2;
+        const bool pok = P0 + lx < a.Plen;
+        g_for<0, 8>([&](auto P) {
+            constexpr int p = decltype(P)::value;
+            const int l = L0 + role * 8 + p;
+            f2_t sg[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {                    // sigmoid, 16 values at a time, packed multiplies / adds
+                f2_t e = f2_t{acc[p][2 * i], acc[p][2 * i + 1]} * KS_SIG;
+                e = f2_t{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)} + 1.0f;
+                sg[i] = f2_t{__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
+            }
+#pragma unroll
+            for (int m2 = 0; m2 < 2; ++m2) {
+                const h8_t r = __builtin_bit_cast(h8_t, *(const u4_t*)(t1 + (2 + p) * G_LS + soff[m2]));
+                h8_t o;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {               // quads 2 m2, 2 m2 + 1 = pairs 4 m2 .. 4 m2 + 3
+                    o[2 * j] = (half_t)__builtin_fmaf(sg[4 * m2 + j].x, (float)r[2 * j], 0.0f);
+                    o[2 * j + 1] = (half_t)__builtin_fmaf(sg[4 * m2 + j].y, (float)r[2 * j + 1], 0.0f);
+                    o[4 + 2 * j] = (half_t)__builtin_fmaf(sg[4 * m2 + 2 + j].x, (float)r[4 + 2 * j], 0.0f);
+                    o[4 + 2 * j + 1] = (half_t)__builtin_fmaf(sg[4 * m2 + 2 + j].y, (float)r[4 + 2 * j + 1], 0.0f);
+                }
+                if (pok && l < a.Llen) *gp<u4_t>(ob + (int64_t)l * a.d_sl + m2 * 32) = __builtin_bit_cast(u4_t, o);
+            }
+        });
+        G_STAMP(wave, trk, 5);
+        asm volatile("s_barrier" ::: "memory");             // C: the h piece is free
         ++trk;
         ++it;
         if (it >= it1) break;
@@ -983,9 +835,7 @@ extern "C" int demfi_gru_zq(const demfi_conv* hz, const demfi_conv* hq, void* st
     a.w0[0] = g_wchunk(hz, 0); a.w0[1] = g_wchunk(hz, 1);
     a.w1[0] = g_wchunk(hq, 0); a.w1[1] = g_wchunk(hq, 1);
     a.b0 = hz->bias; a.b1 = hq->bias;
-    // DEMFI_GRU_ZQS=0: the round-6a form (z waves and q waves, q~ through LDS)
-    static const bool zqs = [] { const char* e = getenv("DEMFI_GRU_ZQS"); return !(e && e[0] == '0'); }();
-    return zqs ? g_launch<GM_ZQS>(a, hq, hq->segs[hq->sub_seg[0]], stream) : g_launch<GM_ZQ>(a, hq, hq->segs[hq->sub_seg[0]], stream);
+    return g_launch<GM_ZQS>(a, hq, hq->segs[hq->sub_seg[0]], stream);
 }
 
 #ifdef DEMFI_TRACE

@@ -391,13 +391,10 @@ __device__ __forceinline__ void store16(char* p, const float* v)
 // (16 bytes of channels per lane): broadcast LDS reads, 8 unconditional 16-byte gathers, FMA accumulation.
 // Byte strides between the per-t contexts of a batched launch (demfi_batch): context q uses pointer + q * stride.
 struct WarpBatch { int nb; int outer; int64_t a, b, o, fa, fb, logit, t, occ, pack; };     // outer: context = blockIdx.y (one launch, contexts one after the other) instead of the innermost loop of a tile
-#ifndef DEMFI_WARP_MINW
-#define DEMFI_WARP_MINW 1                                        // minimum waves per SIMD the register allocation must allow (A/B builds)
-#endif
-#ifndef DEMFI_WARP_WGS_DEFAULT
-#define DEMFI_WARP_WGS_DEFAULT 0                                 // one tile per workgroup: persistent walks measured 0-14 % SLOWER (profiles/r04_notes.md)
-#define DEMFI_WARP_VAR_DEFAULT 1                                 // streaming output stores: -7 % in sequence (the outputs no longer evict F0 / F1 from the Infinity Cache)
-#endif
+// Tiles of WARP_ROWS rows x 64 pixels (wave w = row w), one per workgroup: persistent walks over fewer workgroups measured 0-14 % SLOWER
+// (profiles/r04_notes.md), 8-row tiles and streaming gathers did not pay either.  The output stores are streaming: -7 % in sequence (the
+// outputs no longer evict F0 / F1 from the Infinity Cache).
+constexpr int WARP_ROWS = 4;
 
 struct WarpRec {                    // 20 dwords per pixel
     int offa[4], offb[4];           // byte offsets of the 4 (clamped) corner records of the two warps
@@ -405,14 +402,14 @@ struct WarpRec {                    // 20 dwords per pixel
     float ka, kb, inv_den, den;     // (1-t)*o0, t*(1-o0), 1/den, den
 };
 
-template <typename T, int ROWS = 4, bool NTS = false, bool NTL = false>      // ROWS: rows of the tile = waves of the workgroup; NTS: streaming output stores; NTL: streaming gathers (A/B)
-__global__ __launch_bounds__(ROWS * 64, DEMFI_WARP_MINW) void warp_blend_fat_kernel(demfi_view A0, const float* __restrict__ fa0, demfi_view B0,
+template <typename T>
+__global__ __launch_bounds__(WARP_ROWS * 64, 1) void warp_blend_fat_kernel(demfi_view A0, const float* __restrict__ fa0, demfi_view B0,
                                       const float* __restrict__ fb0, const float* __restrict__ logit0,
                                       const float* __restrict__ tptr0, demfi_view O0, int lpp_shift, int H, int W,
                                       float* __restrict__ occ_out0, int* __restrict__ dbg, WarpBatch bt)
 {
     constexpr int N = Vec16<T>::N;
-    __shared__ WarpRec recs[ROWS * 64];                           // 64 records per wave
+    __shared__ WarpRec recs[WARP_ROWS * 64];                      // 64 records per wave
     const int hw = H * W;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -421,7 +418,7 @@ __global__ __launch_bounds__(ROWS * 64, DEMFI_WARP_MINW) void warp_blend_fat_ker
     // CU's L1 or the XCD's own L2 instead of being fetched once per XCD (linear 64-pixel spans: rows y and y+1 of one
     // image column sat on different XCDs).
     const int tiles_x = (W + 63) >> 6;
-    const int ntile = tiles_x * ((H + ROWS - 1) / ROWS);
+    const int ntile = tiles_x * ((H + WARP_ROWS - 1) / WARP_ROWS);
     const int per = (ntile + 7) >> 3;
     WarpRec* wr = recs + wave * 64;
     // PERSISTENT tile walk (round 4): gridDim.x / 8 workgroups per XCD walk that XCD's contiguous band of tiles with a stride of
@@ -437,7 +434,7 @@ __global__ __launch_bounds__(ROWS * 64, DEMFI_WARP_MINW) void warp_blend_fat_ker
         const int tile = band0 + ti;
         if (ti >= per || tile >= ntile) return false;
         const int ty = tile / tiles_x;
-        y = ty * ROWS + wave;
+        y = ty * WARP_ROWS + wave;
         x0 = (tile - ty * tiles_x) << 6;
         nvalid = min(64, W - x0);
         return y < H;
@@ -525,13 +522,8 @@ __global__ __launch_bounds__(ROWS * 64, DEMFI_WARP_MINW) void warp_blend_fat_ker
         for (int k = 0; k < 4; ++k) { oa[k] = r.offa[k]; ob[k] = r.offb[k]; }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            if constexpr (NTL) {
-                ra[k] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(gcp<u4_t>(ap + oa[k])));
-                rb[k] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(gcp<u4_t>(bp + ob[k])));
-            } else {
-                ra[k] = ld_global16(ap + oa[k]);
-                rb[k] = ld_global16(bp + ob[k]);
-            }
+            ra[k] = ld_global16(ap + oa[k]);
+            rb[k] = ld_global16(bp + ob[k]);
         }
     };
     auto finish = [&](int it, const uint4 (&ra)[4], const uint4 (&rb)[4]) {
@@ -571,20 +563,16 @@ __global__ __launch_bounds__(ROWS * 64, DEMFI_WARP_MINW) void warp_blend_fat_ker
             else o[j] = (r.ka * wa[j] + r.kb * wb[j]) / r.den;                                              // Eq.(2), exact fp32 steps
         }
         char* op = (char*)O.ptr + ((int64_t)y * O.sy + (int64_t)x * O.sx) * sizeof(T) + part * 16;
-        if constexpr (NTS) {
-            if constexpr (sizeof(T) == 2) {
-                h8_t hv;
+        if constexpr (sizeof(T) == 2) {
+            h8_t hv;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) hv[j] = (half_t)o[j];
-                st_global16_nt(op, __builtin_bit_cast(uint4, hv));
-            } else {
-                f4_t fv;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) fv[j] = o[j];
-                st_global16_nt(op, __builtin_bit_cast(uint4, fv));
-            }
+            for (int j = 0; j < 8; ++j) hv[j] = (half_t)o[j];
+            st_global16_nt(op, __builtin_bit_cast(uint4, hv));
         } else {
-            store16<T>(op, o);
+            f4_t fv;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) fv[j] = o[j];
+            st_global16_nt(op, __builtin_bit_cast(uint4, fv));
         }
     };
     uint4 ra0[4], rb0[4], ra1[4], rb1[4];
@@ -995,24 +983,15 @@ static int warp_blend_impl(const demfi_view* A, const float* fa, const demfi_vie
         if (((int64_t)(H - 1) * A->sy + (int64_t)(W - 1) * A->sx + C) * elt >= ((int64_t)1 << 31) ||
             ((int64_t)(H - 1) * B->sy + (int64_t)(W - 1) * B->sx + C) * elt >= ((int64_t)1 << 31))
             return demfi_set_error(DEMFI_ERR_ARG, "demfi_warp_blend: image spans >= 2^31 bytes (32-bit corner offsets)");
-        // ROWS-row x 64-pixel tiles, 8 XCD bands of ceil(ntile / 8) tiles each
-        static const int var = getenv("DEMFI_WARP_VAR") ? atoi(getenv("DEMFI_WARP_VAR")) : DEMFI_WARP_VAR_DEFAULT;   // probe switch (tools/conv_probe.py warp): bit 0 = non-temporal output stores, bit 1 = 8-row tiles
-        static const int wgs = getenv("DEMFI_WARP_WGS") ? atoi(getenv("DEMFI_WARP_WGS")) : DEMFI_WARP_WGS_DEFAULT;   // persistent workgroups per launch (multiple of 8; 0 = one tile per workgroup)
-        const int rows = (var & 2) ? 8 : 4;
-        unsigned nblk = 8u * (unsigned)((((W + 63) / 64) * ((H + rows - 1) / rows) + 7) / 8);
-        if (wgs >= 8 && (unsigned)(wgs & ~7) < nblk) nblk = (unsigned)(wgs & ~7);
-#define DEMFI_WARP_LAUNCH(TT, R, N, NL)                                                                               \
-        hipLaunchKernelGGL((warp_blend_fat_kernel<TT, R, N, NL>), dim3(nblk, wb.outer ? wb.nb : 1), dim3(R * 64), 0, st, *A, fa, *B, fb, logit, t, *out, sh, H, W, \
-                           occ_out, dbg_maps, wb)
-        if (f32) {
-            if ((var & 3) == 0) DEMFI_WARP_LAUNCH(float, 4, false, false); else if ((var & 3) == 1) DEMFI_WARP_LAUNCH(float, 4, true, false);
-            else if ((var & 3) == 2) DEMFI_WARP_LAUNCH(float, 8, false, false); else DEMFI_WARP_LAUNCH(float, 8, true, false);
-        } else {
-            if (var == 0) DEMFI_WARP_LAUNCH(half_t, 4, false, false); else if (var == 1) DEMFI_WARP_LAUNCH(half_t, 4, true, false);
-            else if (var == 2) DEMFI_WARP_LAUNCH(half_t, 8, false, false); else if (var == 3) DEMFI_WARP_LAUNCH(half_t, 8, true, false);
-            else if (var == 4) DEMFI_WARP_LAUNCH(half_t, 4, false, true); else DEMFI_WARP_LAUNCH(half_t, 4, true, true);      // 4, 5: streaming gathers
-        }
-#undef DEMFI_WARP_LAUNCH
+        // one workgroup per tile, 8 XCD bands of ceil(ntile / 8) tiles each
+        const unsigned nblk = 8u * (unsigned)((((W + 63) / 64) * ((H + WARP_ROWS - 1) / WARP_ROWS) + 7) / 8);
+        const dim3 grid(nblk, wb.outer ? wb.nb : 1);
+        if (f32)
+            hipLaunchKernelGGL(warp_blend_fat_kernel<float>, grid, dim3(WARP_ROWS * 64), 0, st, *A, fa, *B, fb, logit, t, *out, sh, H, W,
+                               occ_out, dbg_maps, wb);
+        else
+            hipLaunchKernelGGL(warp_blend_fat_kernel<half_t>, grid, dim3(WARP_ROWS * 64), 0, st, *A, fa, *B, fb, logit, t, *out, sh, H, W,
+                               occ_out, dbg_maps, wb);
     } else {
         if (pack8 && C != 3) return demfi_set_error(DEMFI_ERR_ARG, "demfi_warp_blend_pack: the packed record is defined for C == 3");
         hipLaunchKernelGGL(warp_blend_thin_kernel, dim3(blocks_for(hw), wb.nb), dim3(NT), 0, st, *A, fa, *B, fb, logit, t, *out, C,

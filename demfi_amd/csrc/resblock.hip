@@ -49,10 +49,6 @@ constexpr int RB_NIW = (RB_IN_NI + RB_NH - 1) / RB_NH;           // 20 DMA instr
 #define DEMFI_RB_DEPTH 4                                         // A prefetch distance in steps of 8 MFMAs (6: 14 registers spilled at the 256-register limit)
 #endif
 constexpr int RB_DEPTH = DEMFI_RB_DEPTH;
-#ifndef DEMFI_RB_STORE_AT
-#define DEMFI_RB_STORE_AT 1                                      // round 6: the output stores under conv1's EPILOGUE (0: under its MFMA phase, round 5)
-#endif
-constexpr int RB_STORE_AT = DEMFI_RB_STORE_AT;
 constexpr int RB_NSTEP = 36;                                     // (kx, k-step) groups x ky
 static_assert(RB_NSTEP % RB_DEPTH == 0, "static ring indices");
 static_assert(RB_LDS <= 160 * 1024, "LDS budget");
@@ -226,14 +222,13 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
             RB_STAMP(wave, trk, 0);
             asm volatile("s_barrier" ::: "memory");             // A
             RB_STAMP(wave, trk, 1);
-            // DEMFI_RB_STORE_AT: 0 = the 16 output stores right here, under the conv1 MFMA phase (round 5); 1 (product since round 6) =
-            // behind barrier B, under conv1's EPILOGUE: the stores and the MFMA waves' A-fragment loads share the CU's one memory pipe, and
+            // The 16 output stores go behind barrier B, under conv1's EPILOGUE, not here under its MFMA phase (round 5): the stores and the MFMA waves' A-fragment loads share the CU's one memory pipe, and
             // a matrix phase without the helpers' VMEM traffic runs at 0.93 of the pipe instead of 0.81 (conv1 phase 11 400 -> 9 950
             // cycles, step 28 900 -> 27 400, launch -3 %: profiles/r06_resblock_store_timing_ab.txt); the epilogue issues no VMEM itself
-            if (have_prev) { stage_read(); if constexpr (RB_STORE_AT == 0) stage_store(p_img, p_x0, p_row0); }
+            if (have_prev) stage_read();
             RB_STAMP(wave, trk, 2);
             asm volatile("s_barrier" ::: "memory");             // B: the staged outputs are in registers -> the M lines are free
-            if constexpr (RB_STORE_AT == 1) { if (have_prev) stage_store(p_img, p_x0, p_row0); }
+            if (have_prev) stage_store(p_img, p_x0, p_row0);
             RB_STAMP(wave, trk, 3);
             asm volatile("s_barrier" ::: "memory");             // C: every MFMA wave is done with the input window
             RB_STAMP(wave, trk, 4);
@@ -260,9 +255,6 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
     }
 
     // ================= MFMA waves ================================================================================
-#ifdef DEMFI_RB_PRIO
-    __builtin_amdgcn_s_setprio(DEMFI_RB_PRIO);                  // experiment: MFMA waves above the helper waves of their SIMD
-#endif
     const int hi = lane >> 5, lx = lane & 31;
     const int cs = wave & 1, rh = wave >> 1;                    // cout half, row half (8 rows each)
     const unsigned lane16 = lane * 16;

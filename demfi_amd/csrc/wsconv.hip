@@ -451,26 +451,16 @@ __global__ __launch_bounds__(WS_NTHREADS, 1) void conv_ws2_kernel(const WsArgs a
     }
 }
 
-static bool ws2_on()
-{
-    static const bool on = !(getenv("DEMFI_WS2") && atoi(getenv("DEMFI_WS2")) == 0);      // A/B: 0 = these layers stay on the kernels of rounds 1-5
-    return on;
-}
-
 }  // namespace
 
 // 3x3 stride 1 / 4x4 stride 2, fp16, units of 32 channels (64-byte records; a unit = one NHWC piece of 32 channels, or of 16 + zero
 // padding), 64-cout blocks each routed to 64 consecutive channels of one NHWC fp16 destination (optional NHWC fp16 residual)
 bool demfi_ws2_eligible(const demfi_conv* h)
 {
-    if (!ws2_on() || h->dtype != DEMFI_F16 || !h->zero_page || h->rec_bytes != 64 || (h->nco != 2 && h->nco != 1) || h->cout_pad % (32 * h->nco)) return false;
+    if (h->dtype != DEMFI_F16 || !h->zero_page || h->rec_bytes != 64 || (h->nco != 2 && h->nco != 1) || h->cout_pad % (32 * h->nco)) return false;
     const int nco = h->nco, nblk = h->cout_pad / (32 * nco);
     const bool s2 = h->stride == 2;
-    if (nco == 1) {
-        // 32-cout blocks (the RDB growth convolutions, DeMFInet.py:266-281): 3x3 only; DEMFI_WS2_RDB=0 leaves them on the round-5 kernel
-        static const bool rdb = !(getenv("DEMFI_WS2_RDB") && atoi(getenv("DEMFI_WS2_RDB")) == 0);
-        if (!rdb || s2) return false;
-    }
+    if (nco == 1 && s2) return false;                            // 32-cout blocks (the RDB growth convolutions, DeMFInet.py:266-281): 3x3 only
     if (s2) {
         if (h->kh != 4 || h->kw != 4 || h->pad_y != 1 || h->pad_x != 1 || h->inH != 2 * h->H || h->inW != 2 * h->W) return false;
     } else {

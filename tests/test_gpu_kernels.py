@@ -155,9 +155,10 @@ def test_fused_resblock_vs_two_launches_and_torch(case):
 @pytest.mark.parametrize('H,W,q', [(16, 32, 1), (37, 75, 2), (70, 100, 3), (368, 640, 0), (368, 640, 3), (133, 530, 2)])
 def test_rdb_growth_conv_streamed_weights(H, W, q):
     """Round 5: the RDB growth convolutions (DeMFInet.py:266-281: 3x3, 96 + 32 q -> 32, ReLU, written into the next 32 channels of the
-    128-channel growth buffer it also reads) on the 3x3 / 32-cout instantiation of the streamed-weight kernel: 32-channel units from
-    two pieces with DIFFERENT pixel strides (a 96-channel slice of the 1152-channel GFF input, the growth buffer), 32 x 32-pixel tiles,
-    ragged edges, several tiles per workgroup (133 x 530), against an fp64 convolution of the same fp16 operands."""
+    128-channel growth buffer it also reads): 32-channel units from two pieces with DIFFERENT pixel strides (a 96-channel slice of the
+    1152-channel GFF input, the growth buffer), ragged edges, several tiles per workgroup (133 x 530), against an fp64 convolution of the
+    same fp16 operands.  Since round 6 these shapes run on wsconv.hip's 32-cout form (64-byte records, one 32-cout block per work item);
+    the 3x3 / 32-cout instantiation of the streamed-weight kernel (conv_wstream.hip) only takes the shapes wsconv.hip declines."""
     torch.manual_seed(H + W + q)
     pl = Plan(H, W, torch.float16, DEV)
     cat = pl._fat(H, W, 1152)
@@ -337,7 +338,7 @@ def test_narrow_persistent_conv_7x7(H, W):
     """Mixer.conv_delta1 (7x7, 5 -> 32, DeMFInet.py:800-812): the 7x7 instantiation of the narrow persistent kernel (49 taps of
     resident weights, one 16-channel k-step per tap, 14x38-pixel tiles) instead of the general kernel's 49 per-tap barriers.  Round 6: the chunk
     [8-channel piece | 8 zero channels] of this test (and of the plan) takes the PAIRED-TAP mode -- the upper-half lanes of the B operand read the next
-    column, one MFMA covers the taps (ky, 2j) and (ky, 2j + 1): 28 k-steps instead of 49, four DMA waves (DEMFI_N7_PAIR=0: one tap per k-step)."""
+    column, one MFMA covers the taps (ky, 2j) and (ky, 2j + 1): 28 k-steps instead of 49, four DMA waves."""
     torch.manual_seed(5)
     pl = Plan(H, W, torch.float16, DEV)
     b = pl._fat(H, W, 8)

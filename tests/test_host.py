@@ -265,33 +265,6 @@ def test_unet_layers_carry_the_shape_of_the_phase_kernel(synthetic_sd):
     assert e32.conv_desc(op.conv).cout_perm == 0
 
 
-def test_fused_dec_first_2_experiment_is_still_the_network(synthetic_sd):
-    """DEMFI_DF2_FUSE=1 (round-6 experiment, measured neutral, not the product): Dec_first_2's per-recursion part as ONE launch whose third
-    unit is [16 channels of ref16 through a channel map | the recursion's 8-channel record | 0].  The switch is read once per process:
-    a child interprets that plan on the CPU against the oracle."""
-    import subprocess
-    import sys
-    code = (
-        "import torch\n"
-        "from demfi_amd.engine import Engine\n"
-        "from demfi_amd.weights import synthetic_state_dict, synthetic_window\n"
-        "from tests.plan_sim import PlanSim\n"
-        "from oracle import demfi_oracle as O\n"
-        "sd = synthetic_state_dict(0)\n"
-        "eng = Engine(sd, 32, 64, torch.float16, 'cpu', max_updates=2)\n"
-        "names = [op.name.decode() for op in eng.ops(2, 0)]\n"
-        "assert 'Dec_first_2#t' in names and 'Dec_first_2#rec' not in names, names\n"
-        "x = synthetic_window(32, 64, 4)\n"
-        "PlanSim(eng).forward(x, 0.375, 2)\n"
-        "ref = O.forward(sd, x, torch.tensor([[0.375]]), 2)\n"
-        "for i in range(3):\n"
-        "    assert O.psnr(eng.finals[1, i].float().numpy(), ref[1][1][i][0].numpy()) > 42.0\n"
-        "print('ok')\n")
-    e = dict(os.environ, DEMFI_DF2_FUSE='1')
-    r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and 'ok' in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]
-
-
 @pytest.mark.parametrize('dtype', [torch.float16, torch.float32])
 def test_batched_per_t_plan_equals_per_context_plans(synthetic_sd, dtype):
     """demfi_forward_tb: ONE op list for all per-t contexts (convolutions batched over the contexts through the contiguous

@@ -14,7 +14,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 SAN="-O1 -g -fsanitize=address,undefined -fno-sanitize=pointer-overflow -fno-gpu-sanitize -fno-omit-frame-pointer -shared-libsan -fno-sanitize-recover=undefined"
 objs=()
 for o in *.o; do
-  case "$o" in *_asan.o|*_trace.o|*_abl.o|ctx.o|abi.o|png_codec.o) ;; *) objs+=("$o") ;; esac
+  case "$o" in *_asan.o|*_trace.o|ctx.o|abi.o|png_codec.o) ;; *) objs+=("$o") ;; esac
 done
 for u in ctx abi png_codec; do
   $HIPCC --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -I../../include -Wno-unused-result $SAN -x hip -c $u.cpp -o ${u}_asan.o

@@ -1,10 +1,9 @@
 """GPU-box tool: in-sequence time of named ops of the batched 720p plan (736x1280, fp16, N_tst = 3, 7 contexts).
 
-    [DEMFI_HIP_LIB=.../libdemfi_hip_abl.so DEMFI_SEP_VARIANT=1] python tools/op_time.py <op name> [<op name> ...]
+    python tools/op_time.py <op name> [<op name> ...]
 
 Each op is timed with HIP events right after a launch that sweeps several GB through the caches (the batch-21 `Dec_first`
-convolution of the same plan), so its inputs come from HBM as they do in the pipeline; mean of 6 launches after 2 untimed ones.
-With the ablation library the environment variables of conv.hip (DEMFI_SEP_VARIANT, DEMFI_PERSIST_VARIANT, ...) select a variant."""
+convolution of the same plan), so its inputs come from HBM as they do in the pipeline; mean of 6 launches after 2 untimed ones."""
 import os
 import sys
 

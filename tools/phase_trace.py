@@ -1,10 +1,9 @@
 """GPU-box tool: where does a tile period of the persistent 64->64 kernels go?  Needs the trace build
 (demfi_amd/csrc/build.sh --trace) and DEMFI_HIP_LIB=demfi_amd/csrc/libdemfi_hip_trace.so.
 
-    DEMFI_HIP_LIB=... [DEMFI_PAIR=4] [PROBE_DATA=relu|zero] python tools/phase_trace.py [c3x3|c3x3res] [batch]
+    DEMFI_HIP_LIB=... [PROBE_DATA=relu|zero] python tools/phase_trace.py [c3x3|c3x3res] [batch]
 
-DEMFI_PAIR unset: the product (staged-store kernel, 4 MFMA + 4 helper waves); 4: the round-2 4-wave kernel (stores from the MFMA
-waves); 1 / 2: the pair experiments (ablation build only).
+Traced: the staged-store kernel (4 MFMA + 4 helper waves).
 
 The kernels stamp s_memtime (shader cycles) at their phase boundaries for the first 24 tiles of workgroups 0..31
 (conv.hip: TRACE_STAMP).  Printed: mean cycles per tile of each phase, per wave role, over tiles 4..19.
@@ -102,14 +101,10 @@ def main():
     ms = e0.elapsed_time(e1)
     L.check(lib.demfi_trace_dump(buf.ctypes.data, buf.size))
     tr = buf.reshape(WGS, WAVES, TILES, STAMPS).astype(np.int64)
-    pair = int(os.environ.get('DEMFI_PAIR', 0))
-    if pair == 0:
-        pair = 3                                          # the product is the staged-store kernel
-    n_m = 8 if pair in (1, 2) else 4
-    n_h = 4 if pair == 3 else 2                            # helper (DMA) waves
+    n_m, n_h = 4, 4                                        # MFMA waves, helper (DMA) waves
     lo, hi = 4, 20
-    print('case %s batch %d  PAIR=%d  data=%s : launch %.4f ms (traced build: stamps cost a few %%)' %
-          (case, batch, pair, os.environ.get('PROBE_DATA', 'rand'), ms))
+    print('case %s batch %d  data=%s : launch %.4f ms (traced build: stamps cost a few %%)' %
+          (case, batch, os.environ.get('PROBE_DATA', 'rand'), ms))
     period = (tr[:, 0, hi, 1] - tr[:, 0, lo, 1]) / float(hi - lo)
     print('  period (release to release, wave 0): mean %.0f cycles  (min %.0f max %.0f over %d workgroups)' % (period.mean(), period.min(), period.max(), WGS))
     cyc = (tr[:, 0, hi, 1] - tr[:, 0, lo, 1]).mean()
@@ -117,16 +112,15 @@ def main():
         t = tr[:, w, lo:hi, :]
         nxt = tr[:, w, lo + 1:hi + 1, :]
         if w < n_m:
-            skew_half = pair == 1 and w >= 4
-            names = ('wait at barrier', 'epilogue(k-1)' if skew_half else 'MFMA phase', 'res loads + MFMA phase' if skew_half else ('barrier B + epilogue + staging' if pair == 3 else 'epilogue'), 'to next barrier arrival')
+            names = ('wait at barrier', 'MFMA phase', 'barrier B + epilogue + staging', 'to next barrier arrival')
             d = [t[..., 1] - t[..., 0], t[..., 2] - t[..., 1], t[..., 3] - t[..., 2], nxt[..., 0] - t[..., 3]]
             role = 'MFMA wave %d' % w
         else:
-            names = ('landed -> released (wait at barrier)', 'stores + issue of next tile' if pair == 3 else 'issue of next tile', 'issued -> landed (barrier B + vmcnt wait)' if pair == 3 else 'issued -> landed (vmcnt wait)', '')
+            names = ('landed -> released (wait at barrier)', 'stores + issue of next tile', 'issued -> landed (barrier B + vmcnt wait)', '')
             d = [t[..., 1] - t[..., 0], t[..., 2] - t[..., 1], nxt[..., 0] - t[..., 2], None]
             role = 'DMA wave %d' % (w - n_m)
         parts = ['%s %6.0f' % (nm, x.mean()) for nm, x in zip(names, d) if x is not None]
-        if pair == 3 and w < n_m:
+        if w < n_m:
             parts.append('(of which wait at barrier B %6.0f)' % (t[..., 4] - t[..., 2]).mean())
         print('  %-12s %s' % (role, ' | '.join(parts)))
     # skew between waves at the barrier: who arrives last?
