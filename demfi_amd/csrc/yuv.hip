@@ -1,0 +1,307 @@
+// YUV 4:2:0 <-> BGR uint8 colour conversion of the Y4M stream edge (demfi_amd/video.py).
+//
+// The definition is the numpy pair yuv420_to_bgr_np / bgr_to_yuv420_np in demfi_amd/y4m.py; these kernels match it bit for
+// bit.  Integer arithmetic only: Q16 matrix coefficients rounded from the float64 matrices (computed here by the same float64
+// expressions as in y4m.py, built with -ffp-contract=off), int32 accumulators, ONE round-half-up, clamp to [0, 255].
+//   upsampling (YUV -> BGR): chroma kept in 1/16 units -- 420jpeg: 9/3/3/1 over the 2x2 nearest chroma samples; 420mpeg2:
+//     co-sited horizontally (even x: the sample, odd x: 1/2 + 1/2), centred vertically (3/4 + 1/4); neighbours clamp to the edge;
+//   downsampling (BGR -> YUV, always 420jpeg): a 2x2 box over the full-resolution Q16 Cb / Cr, rounded once; at an odd edge the
+//     clamped neighbour repeats the pixel that exists, which is the mean of the 2 or 1 pixels there.
+//
+// Memory-bound on bytes: a lane owns a strip of 8 luma pixels x 2 rows (one chroma row): Y as one 8-byte access per row, the
+// 24 bytes of BGR per row as three 8-byte accesses, 4 bytes per chroma plane.  Strips that are cut by the right edge or whose
+// rows are not 8-byte aligned (widths that are not a multiple of 8) take the byte path; the data are the same.
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int SX = 8;                 // luma pixels per lane strip
+
+struct ToBgr {                        // Q16; chroma arrives in 1/16 units -> one shift by 20
+    int cy, r_cr, g_cb, g_cr, b_cb, yoff;
+};
+struct ToYuv {                        // Q16 over 8-bit B, G, R
+    int y_r, y_g, y_b, cb_r, cb_g, cb_b, cr_r, cr_g, cr_b, yoff;
+};
+
+inline int fix16(double c) { return (int)floor(c * 65536.0 + 0.5); }
+
+inline void kr_kb(int matrix, double* kr, double* kb)
+{
+    if (matrix == DEMFI_BT709) { *kr = 0.2126; *kb = 0.0722; }
+    else { *kr = 0.299; *kb = 0.114; }
+}
+
+// y4m.py: to_bgr_coefs
+ToBgr to_bgr_coefs(int matrix, int full)
+{
+    double kr, kb;
+    kr_kb(matrix, &kr, &kb);
+    const double kg = 1.0 - kr - kb;
+    const double ys = full ? 1.0 : 255.0 / 219.0, cs = full ? 1.0 : 255.0 / 224.0;
+    ToBgr c;
+    c.cy = fix16(ys);
+    c.r_cr = fix16(cs * 2.0 * (1.0 - kr));
+    c.g_cb = fix16(-(cs * 2.0 * kb * (1.0 - kb) / kg));
+    c.g_cr = fix16(-(cs * 2.0 * kr * (1.0 - kr) / kg));
+    c.b_cb = fix16(cs * 2.0 * (1.0 - kb));
+    c.yoff = full ? 0 : 16;
+    return c;
+}
+
+// y4m.py: to_yuv_coefs
+ToYuv to_yuv_coefs(int matrix, int full)
+{
+    double kr, kb;
+    kr_kb(matrix, &kr, &kb);
+    const double kg = 1.0 - kr - kb;
+    const double ys = full ? 1.0 : 219.0 / 255.0, cs = full ? 1.0 : 224.0 / 255.0;
+    ToYuv c;
+    c.y_r = fix16(ys * kr);
+    c.y_g = fix16(ys * kg);
+    c.y_b = fix16(ys * kb);
+    c.cb_r = fix16(-(cs * kr / (2.0 * (1.0 - kb))));
+    c.cb_g = fix16(-(cs * kg / (2.0 * (1.0 - kb))));
+    c.cb_b = fix16(cs * 0.5);
+    c.cr_r = fix16(cs * 0.5);
+    c.cr_g = fix16(-(cs * kg / (2.0 * (1.0 - kr))));
+    c.cr_b = fix16(-(cs * kb / (2.0 * (1.0 - kr))));
+    c.yoff = full ? 0 : 16;
+    return c;
+}
+
+// clamp255(acc >> S), written as a clamp of the accumulator and then the shift: the shift-then-saturate form is matched to
+// v_ashr_pk_u8_i32 on gfx950, which packs two results into the low half of a register and -- as the code came out -- left the
+// upper half's old bits in place, to be OR-ed into the neighbouring bytes of the packed word.  Same value for every acc.
+template <int S> __device__ __forceinline__ int sat_shr(int acc) { return min(max(acc, 0), (256 << S) - 1) >> S; }
+
+// 8 bytes row[x0 .. x0+7]; indices past the right edge repeat row[w-1]
+__device__ __forceinline__ uint64_t load8(const uint8_t* row, int x0, int w)
+{
+    const uint8_t* p = row + x0;
+    if (x0 + 8 <= w && ((uintptr_t)p & 7) == 0) return *gcp<uint64_t>(p);
+    uint64_t v = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v |= (uint64_t)gcp<uint8_t>(row)[min(x0 + i, w - 1)] << (8 * i);
+    return v;
+}
+
+// store the first n (<= 8) bytes of v at p
+__device__ __forceinline__ void store8(uint8_t* p, uint64_t v, int n)
+{
+    if (n >= 8 && ((uintptr_t)p & 7) == 0) { *gp<uint64_t>(p) = v; return; }
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        if (i < n) gp<uint8_t>(p)[i] = (uint8_t)(v >> (8 * i));
+}
+
+// 6 chroma samples c0-1 .. c0+4 of one row, clamped to [0, cw-1]
+__device__ __forceinline__ void load_c6(const uint8_t* row, int c0, int cw, int* c)
+{
+    c[0] = gcp<uint8_t>(row)[max(c0 - 1, 0)];
+    const uint8_t* p = row + c0;
+    if (c0 + 4 <= cw && ((uintptr_t)p & 3) == 0) {
+        const uint32_t v = *gcp<uint32_t>(p);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c[1 + i] = (v >> (8 * i)) & 0xff;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c[1 + i] = gcp<uint8_t>(row)[min(c0 + i, cw - 1)];
+    }
+    c[5] = gcp<uint8_t>(row)[min(c0 + 4, cw - 1)];
+}
+
+// 24 bytes of 8 BGR pixels (3 words); n = pixels inside the frame
+__device__ __forceinline__ void store_bgr8(uint8_t* p, const uint64_t* q, int n)
+{
+    if (n >= 8 && ((uintptr_t)p & 7) == 0) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) gp<uint64_t>(p)[i] = q[i];
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 24; ++i)                   // edge / unaligned strip: constant byte positions, guarded
+        if (i < 3 * n) gp<uint8_t>(p)[i] = (uint8_t)(q[i >> 3] >> (8 * (i & 7)));
+}
+
+__device__ __forceinline__ void load_bgr8(const uint8_t* row, int x0, int w, uint64_t* q)
+{
+    const uint8_t* p = row + 3 * x0;
+    if (x0 + 8 <= w && ((uintptr_t)p & 7) == 0) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) q[i] = gcp<uint64_t>(p)[i];
+        return;
+    }
+    q[0] = q[1] = q[2] = 0;
+#pragma unroll
+    for (int px = 0; px < 8; ++px) {               // past the right edge: the last pixel again
+        const int x = min(x0 + px, w - 1);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const int b = 3 * px + ch;
+            q[b >> 3] |= (uint64_t)gcp<uint8_t>(row)[3 * x + ch] << (8 * (b & 7));
+        }
+    }
+}
+
+__device__ __forceinline__ int byte_of(const uint64_t* q, int b) { return (int)((q[b >> 3] >> (8 * (b & 7))) & 0xff); }
+
+// one lane: chroma row cy (luma rows 2cy, 2cy+1) x luma columns x0 .. x0+7 of one frame
+__global__ __launch_bounds__(NT) void yuv420_to_bgr_kernel(const uint8_t* __restrict__ src, int64_t src_stride, uint8_t* __restrict__ dst,
+                                                          int64_t dst_stride, int n, int h, int w, int mpeg2, ToBgr k)
+{
+    const int cw = (w + 1) >> 1, ch = (h + 1) >> 1, ns = (w + SX - 1) / SX;
+    const int id = blockIdx.x * NT + threadIdx.x;
+    if (id >= ch * ns) return;
+    const int cy = id / ns, x0 = (id - cy * ns) * SX, c0 = x0 >> 1;
+    for (int f = blockIdx.y; f < n; f += gridDim.y) {
+        const uint8_t* Y = src + (int64_t)f * src_stride;
+        const uint8_t* planes[2] = {Y + (int64_t)h * w, Y + (int64_t)h * w + (int64_t)ch * cw};
+        // vertical 3/4 + 1/4 (both sitings are centred vertically): V[r][plane][i], weight 4
+        int V[2][2][6];
+        for (int pl = 0; pl < 2; ++pl) {
+            int cm[6], c_[6], cp[6];
+            load_c6(planes[pl] + (int64_t)max(cy - 1, 0) * cw, c0, cw, cm);
+            load_c6(planes[pl] + (int64_t)cy * cw, c0, cw, c_);
+            load_c6(planes[pl] + (int64_t)min(cy + 1, ch - 1) * cw, c0, cw, cp);
+            for (int i = 0; i < 6; ++i) {
+                V[0][pl][i] = 3 * c_[i] + cm[i];
+                V[1][pl][i] = 3 * c_[i] + cp[i];
+            }
+        }
+        for (int r = 0; r < 2; ++r) {
+            const int y = 2 * cy + r;
+            if (y >= h) break;
+            const uint64_t yv8 = load8(Y + (int64_t)y * w, x0, w);
+            uint64_t q[3] = {0, 0, 0};
+#pragma unroll
+            for (int px = 0; px < SX; ++px) {
+                const int li = (px >> 1) + 1;      // V index of the pixel's own chroma sample
+                int u[2];
+                for (int pl = 0; pl < 2; ++pl) {
+                    const int* v = V[r][pl];
+                    if (mpeg2) u[pl] = (px & 1) ? 2 * (v[li] + v[li + 1]) : 4 * v[li];
+                    else u[pl] = 3 * v[li] + ((px & 1) ? v[li + 1] : v[li - 1]);
+                }
+                const int yy = (((int)(yv8 >> (8 * px)) & 0xff) - k.yoff) * 16;
+                const int cb = u[0] - 128 * 16, cr = u[1] - 128 * 16;
+                const int R = sat_shr<20>(k.cy * yy + k.r_cr * cr + (1 << 19));
+                const int G = sat_shr<20>(k.cy * yy + k.g_cb * cb + k.g_cr * cr + (1 << 19));
+                const int B = sat_shr<20>(k.cy * yy + k.b_cb * cb + (1 << 19));
+                const int b = 3 * px;
+                q[b >> 3] |= (uint64_t)B << (8 * (b & 7));
+                q[(b + 1) >> 3] |= (uint64_t)G << (8 * ((b + 1) & 7));
+                q[(b + 2) >> 3] |= (uint64_t)R << (8 * ((b + 2) & 7));
+            }
+            store_bgr8(dst + (int64_t)f * dst_stride + ((int64_t)y * w + x0) * 3, q, w - x0);
+        }
+    }
+}
+
+// one lane: luma rows 2cy, 2cy+1 (the second clamped to h-1 at an odd bottom edge) x columns x0 .. x0+7 -> 16 Y, 4 Cb, 4 Cr
+__global__ __launch_bounds__(NT) void bgr_to_yuv420_kernel(const uint8_t* __restrict__ src, int64_t src_stride, int group,
+                                                          int64_t group_stride, uint8_t* __restrict__ dst, int64_t dst_stride, int n,
+                                                          int h, int w, ToYuv k)
+{
+    const int cw = (w + 1) >> 1, ch = (h + 1) >> 1, ns = (w + SX - 1) / SX;
+    const int id = blockIdx.x * NT + threadIdx.x;
+    if (id >= ch * ns) return;
+    const int cy = id / ns, x0 = (id - cy * ns) * SX, c0 = x0 >> 1;
+    for (int f = blockIdx.y; f < n; f += gridDim.y) {
+        const int g = f / group;
+        const uint8_t* S = src + (int64_t)g * group_stride + (int64_t)(f - g * group) * src_stride;
+        uint8_t* Y = dst + (int64_t)f * dst_stride;
+        int cbs[4] = {0, 0, 0, 0}, crs[4] = {0, 0, 0, 0};
+        for (int r = 0; r < 2; ++r) {
+            const int y = min(2 * cy + r, h - 1);
+            uint64_t q[3];
+            load_bgr8(S + (int64_t)y * w * 3, x0, w, q);
+            uint64_t yo = 0;
+#pragma unroll
+            for (int px = 0; px < SX; ++px) {
+                const int B = byte_of(q, 3 * px), G = byte_of(q, 3 * px + 1), R = byte_of(q, 3 * px + 2);
+                const int yv = sat_shr<16>(k.y_r * R + k.y_g * G + k.y_b * B + (k.yoff << 16) + (1 << 15));
+                yo |= (uint64_t)yv << (8 * px);
+                cbs[px >> 1] += k.cb_r * R + k.cb_g * G + k.cb_b * B;
+                crs[px >> 1] += k.cr_r * R + k.cr_g * G + k.cr_b * B;
+            }
+            if (2 * cy + r < h) store8(Y + (int64_t)y * w + x0, yo, w - x0);
+        }
+        uint32_t cbo = 0, cro = 0;
+        for (int i = 0; i < 4; ++i) {
+            cbo |= (uint32_t)sat_shr<18>(cbs[i] + (128 << 18) + (1 << 17)) << (8 * i);
+            cro |= (uint32_t)sat_shr<18>(crs[i] + (128 << 18) + (1 << 17)) << (8 * i);
+        }
+        uint8_t* pcb = Y + (int64_t)h * w + (int64_t)cy * cw + c0;
+        uint8_t* pcr = pcb + (int64_t)ch * cw;
+        if (c0 + 4 <= cw && ((uintptr_t)pcb & 3) == 0 && ((uintptr_t)pcr & 3) == 0) {
+            *gp<uint32_t>(pcb) = cbo;
+            *gp<uint32_t>(pcr) = cro;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (i < cw - c0) {
+                    gp<uint8_t>(pcb)[i] = (uint8_t)(cbo >> (8 * i));
+                    gp<uint8_t>(pcr)[i] = (uint8_t)(cro >> (8 * i));
+                }
+            }
+        }
+    }
+}
+
+int check_common(const char* fn, const void* src, const void* dst, int n, int h, int w, int matrix, int full_range)
+{
+    if (!src || !dst || n < 0)
+        return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer or n=%d", fn, n);
+    if (h < 2 || w < 2 || h > 16384 || w > 16384)
+        return demfi_set_error(DEMFI_ERR_ARG, "%s: frame size %dx%d outside 2..16384", fn, h, w);
+    if ((matrix != DEMFI_BT601 && matrix != DEMFI_BT709) || (full_range != 0 && full_range != 1))
+        return demfi_set_error(DEMFI_ERR_ARG, "%s: matrix %d / full_range %d", fn, matrix, full_range);
+    return DEMFI_OK;
+}
+
+dim3 grid_for(int n, int h, int w)
+{
+    const int64_t lanes = (int64_t)((h + 1) / 2) * ((w + SX - 1) / SX);
+    return dim3((unsigned)((lanes + NT - 1) / NT), (unsigned)min(n, 65535));
+}
+
+}  // namespace
+
+extern "C" int demfi_yuv420_to_bgr(const uint8_t* src, int64_t src_stride, uint8_t* dst, int64_t dst_stride, int n, int h, int w,
+                                   int matrix, int full_range, int siting, void* stream)
+{
+    int st = check_common("demfi_yuv420_to_bgr", src, dst, n, h, w, matrix, full_range);
+    if (st < 0) return st;
+    const int64_t payload = (int64_t)h * w + 2 * (int64_t)((h + 1) / 2) * ((w + 1) / 2);
+    if (siting != DEMFI_420JPEG && siting != DEMFI_420MPEG2)
+        return demfi_set_error(DEMFI_ERR_ARG, "demfi_yuv420_to_bgr: chroma siting %d", siting);
+    if (n > 1 && (src_stride < payload || dst_stride < (int64_t)h * w * 3))
+        return demfi_set_error(DEMFI_ERR_ARG, "demfi_yuv420_to_bgr: strides %lld / %lld below the frame sizes %lld / %lld",
+                               (long long)src_stride, (long long)dst_stride, (long long)payload, (long long)h * w * 3);
+    if (n == 0) return DEMFI_OK;
+    hipLaunchKernelGGL(yuv420_to_bgr_kernel, grid_for(n, h, w), dim3(NT), 0, (hipStream_t)stream, src, src_stride, dst, dst_stride, n, h,
+                       w, siting == DEMFI_420MPEG2 ? 1 : 0, to_bgr_coefs(matrix, full_range));
+    DEMFI_HIP_CHECK(hipGetLastError());
+    return DEMFI_OK;
+}
+
+extern "C" int demfi_bgr_to_yuv420(const uint8_t* src, int64_t src_stride, int group, int64_t group_stride, uint8_t* dst,
+                                   int64_t dst_stride, int n, int h, int w, int matrix, int full_range, void* stream)
+{
+    int st = check_common("demfi_bgr_to_yuv420", src, dst, n, h, w, matrix, full_range);
+    if (st < 0) return st;
+    const int64_t payload = (int64_t)h * w + 2 * (int64_t)((h + 1) / 2) * ((w + 1) / 2);
+    if (group <= 0) group = n > 0 ? n : 1;
+    if (n > 1 && (dst_stride < payload || (group > 1 && src_stride < (int64_t)h * w * 3) ||
+                  (n > group && group_stride < (int64_t)(group - 1) * src_stride + (int64_t)h * w * 3)))
+        return demfi_set_error(DEMFI_ERR_ARG, "demfi_bgr_to_yuv420: strides %lld / %lld (group %d) / %lld below the frame sizes",
+                               (long long)src_stride, (long long)group_stride, group, (long long)dst_stride);
+    if (n == 0) return DEMFI_OK;
+    hipLaunchKernelGGL(bgr_to_yuv420_kernel, grid_for(n, h, w), dim3(NT), 0, (hipStream_t)stream, src, src_stride, group, group_stride,
+                       dst, dst_stride, n, h, w, to_yuv_coefs(matrix, full_range));
+    DEMFI_HIP_CHECK(hipGetLastError());
+    return DEMFI_OK;
+}

@@ -13,12 +13,14 @@ Scheduling (all on ONE GPU, results bit-identical to one forward per (window, t)
   * ``run_windows`` pipelines windows over ``n_trunk`` = 2 trunk contexts: the trunk of window w+1 is queued beside the
     time instants of window w."""
 import ctypes as C
+import itertools
 import os
 
 import torch
 
 from . import _lib as L
 from .harness import t_schedule
+from .y4m import payload_size
 
 
 class WindowRunner:
@@ -356,19 +358,19 @@ class WindowRunner:
         """Device table of demfi_u8_sink records, one per (window, time instant) of the output buffers out [n,M-1,h,w,3] /
         s01 [n,2,h,w,3]: segment 0 / 1 / 2 of the last layer = S0 / S1 / St (S0, S1 are kept from the first time instant
         only, main.py:1165-1172).  Cached per output buffer."""
-        key = (out.data_ptr(), s01.data_ptr(), out.shape[0])
+        key = (out.data_ptr(), s01.data_ptr(), out.shape[0], out.stride()[:2], s01.stride()[:2])
         tab = self._sink_tabs.get(key) if hasattr(self, '_sink_tabs') else None
         if tab is None:
             import numpy as np
             n, m1 = out.shape[0], self.mfi - 1
             a = np.zeros((n, m1, 32), np.int64)                  # 256-byte records (the context's "sink" buffer)
-            fsz = self.h * self.w * 3
+            (so0, so1), (ss0, ss1) = out.stride()[:2], s01.stride()[:2]          # uint8: element strides are bytes
             for i in range(n):
                 for j in range(m1):
-                    a[i, j, 2] = out.data_ptr() + (i * m1 + j) * fsz                 # frame[2] = St
+                    a[i, j, 2] = out.data_ptr() + i * so0 + j * so1                  # frame[2] = St
                     if j == 0:
-                        a[i, j, 0] = s01.data_ptr() + (i * 2 + 0) * fsz              # frame[0] = S0
-                        a[i, j, 1] = s01.data_ptr() + (i * 2 + 1) * fsz              # frame[1] = S1
+                        a[i, j, 0] = s01.data_ptr() + i * ss0                         # frame[0] = S0
+                        a[i, j, 1] = s01.data_ptr() + i * ss0 + ss1                   # frame[1] = S1
                     a[i, j, 8] = self.h | (self.w << 32)                              # int32 h, w
                     a[i, j, 9] = self.n_tst - 1                                        # int32 iter, pad
             tab = torch.from_numpy(a).to(self.engine.device)
@@ -438,7 +440,7 @@ class WindowRunner:
         return out, s01
 
     # ---------------------------------------------------------------------------------------------------------
-    def run_clip_u8(self, host_frames, windows, sink=None, batch=4, reuse_frames=True):
+    def run_clip_u8(self, host_frames, windows, sink=None, batch=4, reuse_frames=True, yuv=None):
         """Host-to-host run of a list of windows: the counterpart of the test_custom loop (/root/reference/main.py:
         1121-1178) between cv2.imread and cv2.imwrite.
 
@@ -448,22 +450,44 @@ class WindowRunner:
         the sink returns).  Windows are processed in batches of ``batch``: the H2D of a batch's frames (own stream), the
         pipelined compute and the D2H of the previous batch's uint8 frames (own stream) overlap; a frame is uploaded
         once when ``reuse_frames`` (consecutive windows share three frames), else once per window it appears in.
-        Returns the number of windows run."""
+        ``windows`` may also be an iterator of unknown length (a stream): it is pulled one batch at a time.
+
+        yuv: Y4M stream edge (``demfi_amd.video.YuvEdge``: matrix, full_range, siting, with_s1(k)).  host_frames[i] is then
+        a 4:2:0 payload (1-D uint8 CPU tensor): its H2D copy is followed by ONE ``demfi_yuv420_to_bgr`` launch per run of
+        consecutive slots, so each frame is converted once.  After the sink's buffers of a batch are written, one
+        ``demfi_bgr_to_yuv420`` launch puts its frames in stream order (per window S0, then St for t = 1/M .. (M-1)/M; plus
+        S1 when ``with_s1(k)`` says window k is the clip's last) into a device buffer that is copied to pinned memory, and
+        sink(k, payloads) gets uint8 [M or M+1, payload] per window.  Returns the number of windows run."""
         dev = self.engine.device
-        n = len(windows)
-        if n == 0:
+        it = iter(windows)
+        wins = list(itertools.islice(it, batch))
+        if not wins:
             return 0
         M1 = self.mfi - 1
-        if getattr(self, '_clip', None) is None or self._clip['batch'] != batch:
+        mode = 'yuv' if yuv is not None else 'bgr'
+        if getattr(self, '_clip', None) is None or self._clip['batch'] != batch or self._clip['mode'] != mode:
+            self._clip = None
             nslot = 4 * batch + 4 if not reuse_frames else 2 * batch + 8
-            self._clip = {
-                'batch': batch, 'h2d': torch.cuda.Stream(dev), 'd2h': torch.cuda.Stream(dev),
-                'slots': torch.empty((max(nslot, 4 * batch * 2), self.h, self.w, 3), dtype=torch.uint8, device=dev),
-                'out': [torch.empty((batch, M1, self.h, self.w, 3), dtype=torch.uint8, device=dev) for _ in range(2)],
-                's01': [torch.empty((batch, 2, self.h, self.w, 3), dtype=torch.uint8, device=dev) for _ in range(2)],
-                'h_out': [torch.empty((batch, M1, self.h, self.w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)],
-                'h_s01': [torch.empty((batch, 2, self.h, self.w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)],
-            }
+            cl = {'batch': batch, 'mode': mode, 'h2d': torch.cuda.Stream(dev), 'd2h': torch.cuda.Stream(dev),
+                  'slots': torch.empty((max(nslot, 4 * batch * 2), self.h, self.w, 3), dtype=torch.uint8, device=dev)}
+            if yuv is None:
+                cl.update({
+                    'out': [torch.empty((batch, M1, self.h, self.w, 3), dtype=torch.uint8, device=dev) for _ in range(2)],
+                    's01': [torch.empty((batch, 2, self.h, self.w, 3), dtype=torch.uint8, device=dev) for _ in range(2)],
+                    'h_out': [torch.empty((batch, M1, self.h, self.w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)],
+                    'h_s01': [torch.empty((batch, 2, self.h, self.w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)],
+                })
+            else:
+                # per window [S0, St x (M-1), S1]: the frames of a batch in stream order are M per window at a fixed stride
+                P = payload_size(self.h, self.w)
+                comb = [torch.empty((batch, self.mfi + 1, self.h, self.w, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
+                cl.update({
+                    'comb': comb, 'out': [c[:, 1:self.mfi] for c in comb], 's01': [c[:, 0::self.mfi] for c in comb],
+                    'yuv_in': torch.empty((cl['slots'].shape[0], P), dtype=torch.uint8, device=dev),
+                    'yuv_out': [torch.empty((batch * self.mfi + 1, P), dtype=torch.uint8, device=dev) for _ in range(2)],
+                    'h_yuv': [torch.empty((batch * self.mfi + 1, P), dtype=torch.uint8).pin_memory() for _ in range(2)],
+                })
+            self._clip = cl
         cl = self._clip
         slots = cl['slots']
         nslot = slots.shape[0]
@@ -473,13 +497,14 @@ class WindowRunner:
         next_slot = 0
         ev_done = [None, None]            # compute of the batch that last wrote device output buffer i
         ev_d2h = [None, None]             # D2H of that batch
-        pending = None                    # (first window, count, buffer) whose D2H is in flight
-        nb = (n + batch - 1) // batch
-        for b in range(nb):
-            wins = windows[b * batch:(b + 1) * batch]
+        pending = None                    # (first window, count, buffer[, frames per window]) whose D2H is in flight
+        n = 0
+        b = 0
+        while wins:
             i = b & 1
             # ---- H2D of the frames this batch needs (copy stream) -------------------------------------------------
             dev_wins = []
+            new_slots = []
             with torch.cuda.stream(cl['h2d']):
                 for wi, win in enumerate(wins):
                     fr = []
@@ -495,12 +520,21 @@ class WindowRunner:
                             if slot_busy[sl] is not None:
                                 cl['h2d'].wait_event(slot_busy[sl])
                             f = host_frames[idx]
-                            if tuple(f.shape) != (self.h, self.w, 3) or f.dtype != torch.uint8:
-                                raise ValueError('frame %d: expected uint8 [%d,%d,3], got %s %s' % (idx, self.h, self.w, f.dtype, tuple(f.shape)))
-                            slots[sl].copy_(f, non_blocking=True)
+                            if yuv is not None:
+                                if tuple(f.shape) != tuple(cl['yuv_in'].shape[1:]) or f.dtype != torch.uint8:
+                                    raise ValueError('frame %d: expected a uint8 [%d] 4:2:0 payload, got %s %s' %
+                                                     (idx, cl['yuv_in'].shape[1], f.dtype, tuple(f.shape)))
+                                cl['yuv_in'][sl].copy_(f, non_blocking=True)
+                                new_slots.append(sl)
+                            else:
+                                if tuple(f.shape) != (self.h, self.w, 3) or f.dtype != torch.uint8:
+                                    raise ValueError('frame %d: expected uint8 [%d,%d,3], got %s %s' % (idx, self.h, self.w, f.dtype, tuple(f.shape)))
+                                slots[sl].copy_(f, non_blocking=True)
                             slot_of[key] = sl
                         fr.append(slots[sl])
                     dev_wins.append(fr)
+                if yuv is not None:
+                    self._yuv_ingest(new_slots, yuv)
                 ev_up = torch.cuda.Event()
                 ev_up.record(cl['h2d'])
             # ---- compute (pipelined windows) ---------------------------------------------------------------------
@@ -508,6 +542,7 @@ class WindowRunner:
             if ev_d2h[i] is not None:
                 cur.wait_event(ev_d2h[i])                     # the D2H of batch b-2 has read this output buffer
             self.run_windows_u8(dev_wins, out=cl['out'][i][:len(wins)], s01=cl['s01'][i][:len(wins)])
+            nf = self._yuv_egress(i, n, len(wins), yuv, cur) if yuv is not None else None
             ev = torch.cuda.Event()
             ev.record(cur)
             ev_done[i] = ev
@@ -520,21 +555,64 @@ class WindowRunner:
             # ---- D2H of this batch (copy stream), into pinned staging ------------------------------------------------
             with torch.cuda.stream(cl['d2h']):
                 cl['d2h'].wait_event(ev)
-                cl['h_out'][i][:len(wins)].copy_(cl['out'][i][:len(wins)], non_blocking=True)
-                cl['h_s01'][i][:len(wins)].copy_(cl['s01'][i][:len(wins)], non_blocking=True)
+                if yuv is not None:
+                    cl['h_yuv'][i][:nf].copy_(cl['yuv_out'][i][:nf], non_blocking=True)
+                else:
+                    cl['h_out'][i][:len(wins)].copy_(cl['out'][i][:len(wins)], non_blocking=True)
+                    cl['h_s01'][i][:len(wins)].copy_(cl['s01'][i][:len(wins)], non_blocking=True)
                 e2 = torch.cuda.Event()
                 e2.record(cl['d2h'])
                 ev_d2h[i] = e2
-            pending = (b * batch, len(wins), i)
+            pending = (n, len(wins), i, nf)
+            n += len(wins)
+            b += 1
+            wins = list(itertools.islice(it, batch))
         self._drain(pending, ev_d2h, sink)
         return n
 
     def _drain(self, pending, ev_d2h, sink):
-        k0, cnt, i = pending
+        k0, cnt, i, nf = pending
         ev_d2h[i].synchronize()
-        if sink is not None:
+        if sink is None:
+            return
+        if nf is not None:                               # Y4M: M payloads per window, the last one's S1 after them
+            hy = self._clip['h_yuv'][i]
             for j in range(cnt):
-                sink(k0 + j, self._clip['h_out'][i][j], self._clip['h_s01'][i][j])
+                sink(k0 + j, hy[j * self.mfi:(j + 1) * self.mfi + (1 if j == cnt - 1 and nf > cnt * self.mfi else 0)])
+            return
+        for j in range(cnt):
+            sink(k0 + j, self._clip['h_out'][i][j], self._clip['h_s01'][i][j])
+
+    def _yuv_ingest(self, slots, yuv):
+        """4:2:0 payloads already copied to yuv_in[slot] -> BGR slots[slot], one launch per run of consecutive slots (h2d stream)."""
+        cl = self._clip
+        h2d = cl['h2d'].cuda_stream
+        P = cl['yuv_in'].shape[1]
+        fsz = self.h * self.w * 3
+        r = 0
+        while r < len(slots):
+            e = r + 1
+            while e < len(slots) and slots[e] == slots[e - 1] + 1:
+                e += 1
+            L.check(self.lib.demfi_yuv420_to_bgr(cl['yuv_in'][slots[r]].data_ptr(), P, cl['slots'][slots[r]].data_ptr(), fsz, e - r,
+                                                 self.h, self.w, yuv.matrix, int(yuv.full_range), yuv.siting, h2d), 'yuv420_to_bgr')
+            r = e
+
+    def _yuv_egress(self, i, k0, cnt, yuv, cur):
+        """Frames of a computed batch (comb[i]: per window S0, St..., S1) -> yuv_out[i] in stream order on the compute stream;
+        returns the number of payloads."""
+        cl = self._clip
+        comb, dst = cl['comb'][i], cl['yuv_out'][i]
+        P = dst.shape[1]
+        fsz = self.h * self.w * 3
+        nf = cnt * self.mfi
+        L.check(self.lib.demfi_bgr_to_yuv420(comb.data_ptr(), fsz, self.mfi, comb.stride(0), dst.data_ptr(), P, nf, self.h, self.w,
+                                             yuv.matrix, int(yuv.full_range), cur.cuda_stream), 'bgr_to_yuv420')
+        if yuv.with_s1(k0 + cnt - 1):                    # the clip's last window: its S1 closes the stream
+            L.check(self.lib.demfi_bgr_to_yuv420(comb[cnt - 1, self.mfi].data_ptr(), fsz, 1, 0, dst[nf].data_ptr(), P, 1, self.h,
+                                                 self.w, yuv.matrix, int(yuv.full_range), cur.cuda_stream), 'bgr_to_yuv420')
+            nf += 1
+        return nf
 
     def __del__(self):
         try:

@@ -1,0 +1,182 @@
+"""Video streams in, video streams out: x M interpolation of a YUV4MPEG2 (Y4M) stream.
+
+    ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe - | python -m demfi_amd.video - - --mfi 8 | ffmpeg -f yuv4mpegpipe -i - out.mp4
+
+The frames are those of the folder path (``python -m demfi_amd.clip``) for the same pixels, in the order of the reference's
+``test_custom`` folder sorted by name (``clip.output_names`` / ``clip.deblurred_writes``): per window k, S0 (deblurred B0) and
+then St for t = 1/M .. (M-1)/M; after the last window its S1.  n input frames give (n-3)*M + 1 output frames: the first and
+the last input frame have no output of their own, as in the reference.
+
+The colour conversion runs on the GPU next to the uint8 ingest / sink (csrc/yuv.hip, defined by ``y4m.yuv420_to_bgr_np`` /
+``y4m.bgr_to_yuv420_np``): 4:2:0 payloads go host -> HBM (half the bytes of BGR), are converted once per frame into the
+runner's BGR frame slots, and every computed batch is converted back into a stream-order device buffer in one launch
+(``WindowRunner.run_clip_u8(yuv=...)``).  One rank reads a stream (stdin included) in bounded batches and writes each batch
+as it drains; under ``torch.distributed.run`` every rank takes ``dist.shard_windows``' block of a regular file and writes its
+frames at their byte offsets of the output file (no collective on the data path).
+"""
+import os
+import sys
+
+import torch
+
+from . import _lib as L
+from . import dist as D
+from . import y4m
+from .clip import ClipRunner
+
+
+class YuvEdge:
+    """Y4M edge of ``WindowRunner.run_clip_u8``: conversion parameters of the stream (library codes) and ``with_s1(k)``: does
+    window k (index in the runner's window sequence) close the stream, i.e. is its S1 written?"""
+
+    def __init__(self, matrix, full_range, siting, with_s1):
+        self.matrix = {'bt601': L.BT601, 'bt709': L.BT709}[matrix]
+        self.full_range = bool(full_range)
+        self.siting = {'420jpeg': L.SITING_420JPEG, '420mpeg2': L.SITING_420MPEG2}[siting]
+        self.with_s1 = with_s1
+
+
+class VideoRunner:
+    """x M interpolation of Y4M input on this rank's GPU.  ``matrix``: 'auto' (BT.709 when H >= 720, else BT.601), 'bt601'
+    or 'bt709'; the output uses the input's matrix and range, so an ffmpeg round trip keeps the colours."""
+
+    def __init__(self, model, n_tst=3, mfi=8, batch=4, matrix='auto', **runner_kw):
+        if matrix not in ('auto',) + tuple(y4m.MATRICES):
+            raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
+        self.model, self.n_tst, self.mfi, self.batch, self.matrix = model, n_tst, mfi, batch, matrix
+        self.runner_kw = runner_kw
+        self._runners = {}
+        self.last_decode_peak = 0
+
+    def _clip_runner(self, hdr, world, rank):
+        key = (hdr.h, hdr.w, world, rank)
+        cr = self._runners.get(key)
+        if cr is None:
+            cr = self._runners[key] = ClipRunner(self.model, hdr.h, hdr.w, self.n_tst, self.mfi, batch=self.batch, world=world,
+                                                 rank=rank, **self.runner_kw)
+        return cr
+
+    def _edge(self, hdr, with_s1):
+        return YuvEdge(y4m.auto_matrix(hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1)
+
+    def run_stream(self, src, dst):
+        """One rank, sequential binary streams (stdin / stdout work): nothing is seeked, the input is read in batches of
+        windows and every batch is written (and flushed) as it drains.  Returns (windows, frames written)."""
+        rd = y4m.Reader(src)
+        hdr = rd.header
+        wr = y4m.Writer(dst, y4m.output_header(hdr, self.mfi))
+        frames = y4m.Frames(rd)
+
+        def sink(k, payloads):
+            wr.write(payloads)
+            dst.flush()
+        cr = self._clip_runner(hdr, 1, 0)
+        n = cr.runner.run_clip_u8(frames, frames.windows(), sink, batch=self.batch, yuv=self._edge(hdr, frames.is_last))
+        dst.flush()
+        self.last_decode_peak = frames.peak
+        return n, wr.frames
+
+    def run_file(self, in_path, out_path, world=1, rank=0):
+        """Rank ``rank`` of ``world`` on regular files: one scan of the input's frame headers, this rank's block of windows
+        (``dist.shard_windows``), its frames written at ``header + i*(6 + payload)``.  Rank 0 writes the header and sizes the
+        output file; all ranks meet at a barrier before writing.  Returns (windows, frames written) of this rank."""
+        with open(in_path, 'rb') as f:
+            hdr, _, offs = y4m.scan(f)
+            n_in = len(offs)
+            ohdr = y4m.output_header(hdr, self.mfi)
+            hb = ohdr.encode()
+            total = y4m.n_output_frames(n_in, self.mfi)
+            if rank == 0:
+                with open(out_path, 'wb') as o:
+                    o.write(hb)
+                    o.truncate(y4m.frame_offset(len(hb), total, hdr.payload))
+            D.barrier()
+            cr = self._clip_runner(hdr, world, rank)
+            lo, wins = cr.my_windows(n_in)
+            if not wins:
+                return 0, 0
+            n_windows = n_in - 3
+            frames = y4m.Frames.from_file(f, offs, lo, lo + len(wins) + 3, hdr.payload)
+            with open(out_path, 'r+b') as o:
+                wr = y4m.Writer(o, ohdr, at=y4m.frame_offset(len(hb), y4m.output_index(lo, 0, self.mfi), hdr.payload))
+                n = cr.runner.run_clip_u8(frames, wins, lambda k, p: wr.write(p), batch=self.batch,
+                                          yuv=self._edge(hdr, lambda k: lo + k == n_windows - 1))
+            self.last_decode_peak = frames.peak
+            return n, wr.frames
+
+
+def _is_regular(path):
+    return path != '-' and (not os.path.exists(path) or os.path.isfile(path))
+
+
+def main(argv=None):
+    """``python -m demfi_amd.video IN OUT`` -- x M interpolation of a Y4M stream; ``-`` is stdin / stdout.  The first and the last
+    input frame have no output (as in the reference's test_custom): n frames in, (n-3)*M + 1 out, at M times the frame rate."""
+    import argparse
+    import json
+    import time
+    ap = argparse.ArgumentParser(prog='python -m demfi_amd.video', description=main.__doc__.split('\n\n')[0],
+                                 epilog='Input: 8-bit 4:2:0 progressive Y4M (C420jpeg, C420, C420mpeg2; XCOLORRANGE=FULL|LIMITED), '
+                                        'e.g. ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe -.  Output: C420jpeg, the input\'s '
+                                        'matrix and range.  n input frames give (n-3)*M + 1 output frames: the first and the last '
+                                        'input frame have no output, as in the reference.  All logging goes to stderr.')
+    ap.add_argument('input', help="Y4M file, or - for stdin")
+    ap.add_argument('output', help="Y4M file, or - for stdout")
+    ap.add_argument('--mfi', type=int, default=8, help='multiple_MFI: output frame rate = M x input (main.py:98)')
+    ap.add_argument('--n-tst', type=int, default=3, help='N_tst recursive boosts (main.py:101)')
+    ap.add_argument('--dtype', default='fp16', choices=['fp16', 'fp32'])
+    ap.add_argument('--checkpoint', default='', help="reference checkpoint (.pt holding 'state_dict_Model')")
+    ap.add_argument('--matrix', default='auto', choices=['auto', 'bt601', 'bt709'],
+                    help='YCbCr matrix of the input (and output); auto: BT.709 when H >= 720, else BT.601')
+    ap.add_argument('--batch', type=int, default=4, help='windows per batch (the input frames held are bounded by it)')
+    a = ap.parse_args(argv)
+    rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
+    if world > 1 and not (_is_regular(a.input) and os.path.isfile(a.input) and _is_regular(a.output)):
+        raise SystemExit('demfi_amd.video: with %d ranks IN and OUT must be regular files (ranks write at byte offsets)' % world)
+    out_fd = None
+    if a.output == '-':
+        # the stream owns stdout: anything a library prints goes to stderr instead
+        out_fd = os.dup(1)
+        os.dup2(2, 1)
+        sys.stdout = sys.stderr
+    if not torch.cuda.is_available():
+        raise SystemExit('demfi_amd.video: no GPU visible -- the forward path is HIP-only (no CPU fallback)')
+    from . import DeMFInet, HyperParams, synthetic_state_dict
+    from .weights import load_checkpoint
+    torch.cuda.set_device(local)
+    dev = torch.device('cuda', local)
+    D.init(world, rank, local)
+    model = DeMFInet(HyperParams(gpu=local), dtype=torch.float16 if a.dtype == 'fp16' else torch.float32)
+    if rank == 0:
+        model.load_state_dict(load_checkpoint(a.checkpoint) if a.checkpoint else synthetic_state_dict(0))
+    model = model.to(dev).eval()
+    D.broadcast_state_dict(model, world, device=dev)
+    vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix)
+    t0 = time.perf_counter()
+    if world > 1:
+        nw, nf = vr.run_file(a.input, a.output, world, rank)
+    else:
+        src = sys.stdin.buffer if a.input == '-' else open(a.input, 'rb')
+        dst = os.fdopen(out_fd, 'wb') if out_fd is not None else open(a.output, 'wb')
+        try:
+            nw, nf = vr.run_stream(src, dst)
+        finally:
+            dst.close()
+            if src is not sys.stdin.buffer:
+                src.close()
+    torch.cuda.synchronize()
+    dt = D.max_over_ranks(time.perf_counter() - t0, dev)
+    tw, tf = (D.sum_over_ranks([float(nw), float(nf)], dev).tolist() if world > 1 else (nw, nf))
+    if rank == 0:
+        if tw == 0:
+            print('demfi_amd.video: fewer than 4 input frames: no window, only the header was written', file=sys.stderr)
+        print(json.dumps({'windows': int(tw), 'frames_written': int(tf), 'seconds': round(dt, 2), 'ranks': world,
+                          'St_frames_per_s': round(tw * (a.mfi - 1) / dt, 2) if dt > 0 else None,
+                          'frames_per_s': round(tf / dt, 2) if dt > 0 else None,
+                          'weights': os.path.basename(a.checkpoint) if a.checkpoint else 'synthetic_state_dict(0) (random init: no checkpoint given)',
+                          'out': a.output}), file=sys.stderr)
+    D.finalize()
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,422 @@
+"""YUV4MPEG2 (Y4M) stream I/O and the definition of the YUV 4:2:0 <-> BGR conversion of the video edge (demfi_amd/video.py).
+
+Y4M is what video tools pass through pipes (``ffmpeg -f yuv4mpegpipe``, x264 / x265 / SVT-AV1 ``--input-y4m``, mpv): one text
+header line, then per frame ``FRAME[ params]\\n`` and the raw payload -- for 8-bit 4:2:0 the Y plane [h,w] followed by the Cb
+and Cr planes [ceil(h/2), ceil(w/2)], 1.5 bytes per pixel.
+
+``yuv420_to_bgr_np`` / ``bgr_to_yuv420_np`` DEFINE the colour conversion; the HIP kernels ``demfi_yuv420_to_bgr`` /
+``demfi_bgr_to_yuv420`` (csrc/yuv.hip) match them bit for bit.  Integer arithmetic only:
+  * Q16 matrix coefficients rounded (half up) from the float64 BT.601 / BT.709 matrices, limited (Y 16-235, C 16-240) or
+    full range folded in; int32 accumulators, ONE round-half-up, clamp to [0, 255];
+  * upsampling keeps chroma in 1/16 units into the matrix: 420jpeg (centred) 9/3/3/1 over 16, 420mpeg2 (co-sited
+    horizontally, centred vertically) 1/2 + 1/2 at odd columns and 3/4 + 1/4 vertically; neighbours clamp to the edge;
+  * downsampling (output is always 420jpeg) is a 2x2 box over the full-resolution Q16 Cb / Cr, rounded once; at an odd
+    edge the clamped neighbour repeats the pixel that exists, i.e. the 2 or 1 pixels there are averaged.
+Frames are uint8 [h,w,3] in B, G, R order, the frame order of the whole pipeline (cv2's).
+"""
+import io
+import math
+import os
+import re
+from fractions import Fraction
+
+import numpy as np
+
+MAGIC = b'YUV4MPEG2'
+FRAME = b'FRAME'
+MAX_SIDE = 16384
+FIX = "convert the input with ffmpeg's -pix_fmt yuv420p (progressive 8-bit 4:2:0), e.g. ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe -"
+MATRICES = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}       # (Kr, Kb)
+SITINGS = ('420jpeg', '420mpeg2')
+_CHROMA = {None: '420jpeg', '420jpeg': '420jpeg', '420': '420jpeg', '420mpeg2': '420mpeg2'}
+_MAX_LINE = 4096
+
+
+class Y4MError(ValueError):
+    pass
+
+
+# ---- the conversion definition ---------------------------------------------------------------------------------------------
+def _fix16(c):
+    return int(math.floor(c * 65536.0 + 0.5))
+
+
+def _kr_kb(matrix):
+    if matrix not in MATRICES:
+        raise ValueError('matrix must be one of %s, got %r' % (sorted(MATRICES), matrix))
+    return MATRICES[matrix]
+
+
+def to_bgr_coefs(matrix, full_range):
+    """Q16 (cy, r_cr, g_cb, g_cr, b_cb), Y offset: R = cy*Y' + r_cr*Cr', G = cy*Y' + g_cb*Cb' + g_cr*Cr', B = cy*Y' + b_cb*Cb'."""
+    kr, kb = _kr_kb(matrix)
+    kg = 1.0 - kr - kb
+    ys, cs = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    return (_fix16(ys), _fix16(cs * 2.0 * (1.0 - kr)), _fix16(-(cs * 2.0 * kb * (1.0 - kb) / kg)),
+            _fix16(-(cs * 2.0 * kr * (1.0 - kr) / kg)), _fix16(cs * 2.0 * (1.0 - kb))), (0 if full_range else 16)
+
+
+def to_yuv_coefs(matrix, full_range):
+    """Q16 rows (Y, Cb, Cr) x (R, G, B), Y offset (the chroma offset is 128)."""
+    kr, kb = _kr_kb(matrix)
+    kg = 1.0 - kr - kb
+    ys, cs = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
+    return ((_fix16(ys * kr), _fix16(ys * kg), _fix16(ys * kb)),
+            (_fix16(-(cs * kr / (2.0 * (1.0 - kb)))), _fix16(-(cs * kg / (2.0 * (1.0 - kb)))), _fix16(cs * 0.5)),
+            (_fix16(cs * 0.5), _fix16(-(cs * kg / (2.0 * (1.0 - kr)))), _fix16(-(cs * kb / (2.0 * (1.0 - kr)))))), (0 if full_range else 16)
+
+
+def payload_size(h, w):
+    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+
+
+def split_planes(payload, h, w):
+    """Y4M payload (bytes-like, 1-D uint8) -> (Y [h,w], Cb, Cr [ceil(h/2), ceil(w/2)]) views."""
+    a = np.frombuffer(payload, np.uint8) if not isinstance(payload, np.ndarray) else payload.reshape(-1)
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    if a.size != payload_size(h, w):
+        raise ValueError('payload of %d bytes for a %dx%d 4:2:0 frame (%d expected)' % (a.size, h, w, payload_size(h, w)))
+    return a[:h * w].reshape(h, w), a[h * w:h * w + ch * cw].reshape(ch, cw), a[h * w + ch * cw:].reshape(ch, cw)
+
+
+def _upsample16(c, h, w, siting):
+    """chroma [ch,cw] -> int32 [h,w] in 1/16 units (weights sum to 16)."""
+    ch, cw = c.shape
+    c = c.astype(np.int32)
+    ys = np.arange(h)
+    cy0 = ys >> 1
+    cy1 = np.where(ys & 1, np.minimum(cy0 + 1, ch - 1), np.maximum(cy0 - 1, 0))
+    v = 3 * c[cy0] + c[cy1]                                   # vertical 3/4 + 1/4, weight 4
+    xs = np.arange(w)
+    cx0 = xs >> 1
+    if siting == '420jpeg':
+        cx1 = np.where(xs & 1, np.minimum(cx0 + 1, cw - 1), np.maximum(cx0 - 1, 0))
+        return 3 * v[:, cx0] + v[:, cx1]
+    if siting == '420mpeg2':
+        cx1 = np.where(xs & 1, np.minimum(cx0 + 1, cw - 1), cx0)
+        return 2 * (v[:, cx0] + v[:, cx1])
+    raise ValueError('chroma siting must be one of %s, got %r' % (SITINGS, siting))
+
+
+def yuv420_to_bgr_np(payload, h, w, matrix='bt601', full_range=False, siting='420jpeg'):
+    """One 8-bit 4:2:0 Y4M payload -> uint8 BGR [h,w,3] (the definition the HIP kernel matches)."""
+    y, cb, cr = split_planes(payload, h, w)
+    (cy, r_cr, g_cb, g_cr, b_cb), yoff = to_bgr_coefs(matrix, full_range)
+    yy = (y.astype(np.int32) - yoff) * 16
+    cbv = _upsample16(cb, h, w, siting) - 128 * 16
+    crv = _upsample16(cr, h, w, siting) - 128 * 16
+    rnd = np.int32(1 << 19)
+    r = (cy * yy + r_cr * crv + rnd) >> 20
+    g = (cy * yy + g_cb * cbv + g_cr * crv + rnd) >> 20
+    b = (cy * yy + b_cb * cbv + rnd) >> 20
+    return np.clip(np.stack([b, g, r], -1), 0, 255).astype(np.uint8)
+
+
+def bgr_to_yuv420_np(bgr, matrix='bt601', full_range=False):
+    """uint8 BGR [h,w,3] -> one 8-bit 4:2:0 (420jpeg) Y4M payload, 1-D uint8 (the definition the HIP kernel matches)."""
+    bgr = np.asarray(bgr)
+    if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise ValueError('uint8 [h,w,3] expected, got %s %s' % (bgr.dtype, bgr.shape))
+    h, w = bgr.shape[:2]
+    if h < 2 or w < 2:
+        raise ValueError('frame of %dx%d: 2x2 at least' % (h, w))
+    (ky, kcb, kcr), yoff = to_yuv_coefs(matrix, full_range)
+    b, g, r = (bgr[:, :, i].astype(np.int32) for i in range(3))
+    y = np.clip((ky[0] * r + ky[1] * g + ky[2] * b + (yoff << 16) + (1 << 15)) >> 16, 0, 255)
+    r0 = np.arange(0, h, 2)
+    r1 = np.minimum(r0 + 1, h - 1)
+    c0 = np.arange(0, w, 2)
+    c1 = np.minimum(c0 + 1, w - 1)
+
+    def down(k):
+        f = k[0] * r + k[1] * g + k[2] * b                   # full-resolution Q16 chroma, centred on 0
+        s = f[r0][:, c0] + f[r0][:, c1] + f[r1][:, c0] + f[r1][:, c1]
+        return np.clip((s + (128 << 18) + (1 << 17)) >> 18, 0, 255)
+    return np.concatenate([y.reshape(-1), down(kcb).reshape(-1), down(kcr).reshape(-1)]).astype(np.uint8)
+
+
+def auto_matrix(h):
+    """--matrix auto: BT.709 for HD (H >= 720), BT.601 below (what encoders assume for untagged video)."""
+    return 'bt709' if h >= 720 else 'bt601'
+
+
+# ---- header ----------------------------------------------------------------------------------------------------------------
+class Header:
+    """Parsed stream header.  ``chroma``: '420jpeg' | '420mpeg2' (C420 / missing C = 420jpeg); ``full_range`` from
+    XCOLORRANGE (default limited); ``fps`` a Fraction; ``aspect`` / ``color_range`` the raw A / XCOLORRANGE values or None;
+    ``xtags`` the other X parameters in order."""
+
+    def __init__(self, w, h, fps, interlace='p', aspect=None, chroma='420jpeg', color_range=None, xtags=(), ctag=None):
+        self.w, self.h, self.fps = int(w), int(h), Fraction(fps)
+        self.interlace, self.aspect, self.chroma = interlace, aspect, chroma
+        self.color_range = color_range
+        self.xtags = list(xtags)
+        self.ctag = ctag
+
+    @property
+    def full_range(self):
+        return self.color_range == 'FULL'
+
+    @property
+    def payload(self):
+        return payload_size(self.h, self.w)
+
+    @property
+    def frame_bytes(self):
+        """bytes of one frame written by this module: 'FRAME\\n' + payload"""
+        return len(FRAME) + 1 + self.payload
+
+    def encode(self):
+        p = [MAGIC, b'W%d' % self.w, b'H%d' % self.h, b'F%d:%d' % (self.fps.numerator, self.fps.denominator),
+             b'I' + self.interlace.encode()]
+        if self.aspect is not None:
+            p.append(b'A' + self.aspect.encode())
+        if self.ctag is not None:
+            p.append(b'C' + self.ctag.encode())
+        p += [b'X' + x.encode() for x in self.xtags]
+        if self.color_range is not None:
+            p.append(b'XCOLORRANGE=' + self.color_range.encode())
+        return b' '.join(p) + b'\n'
+
+    def __repr__(self):
+        return 'Header(%r)' % self.encode()
+
+
+def _reject(what):
+    raise Y4MError('Y4M: %s is not supported: %s' % (what, FIX))
+
+
+def parse_header(line):
+    """One header line (bytes, with or without the trailing newline) -> Header.  Raises Y4MError."""
+    if isinstance(line, str):
+        line = line.encode()
+    line = line.rstrip(b'\n')
+    toks = line.split(b' ')
+    if toks[0] != MAGIC:
+        raise Y4MError('not a YUV4MPEG2 stream (bad magic %r): %s' % (bytes(line[:16]), FIX))
+    w = h = fps = None
+    inter, aspect, ctag, crange, xt = 'p', None, None, None, []
+    for t in toks[1:]:
+        if not t:
+            continue
+        tag, val = chr(t[0]), t[1:].decode('ascii', 'replace')
+        if tag in 'WH':
+            if not re.fullmatch(r'\d{1,9}', val):
+                raise Y4MError('Y4M: bad %s%s' % (tag, val))
+            if tag == 'W':
+                w = int(val)
+            else:
+                h = int(val)
+        elif tag == 'F':
+            m = re.fullmatch(r'(\d{1,9}):(\d{1,9})', val)
+            if not m or int(m.group(1)) == 0 or int(m.group(2)) == 0:
+                raise Y4MError('Y4M: bad frame rate F%s' % val)
+            fps = Fraction(int(m.group(1)), int(m.group(2)))
+        elif tag == 'I':
+            if val not in ('p', '?'):
+                _reject('interlaced video (I%s)' % val)
+            inter = val
+        elif tag == 'A':
+            aspect = val
+        elif tag == 'C':
+            if val not in _CHROMA:
+                _reject('colour space C%s (8-bit 4:2:0 only)' % val)
+            ctag = val
+        elif tag == 'X':
+            if val.startswith('COLORRANGE='):
+                crange = val.split('=', 1)[1]
+                if crange not in ('FULL', 'LIMITED'):
+                    raise Y4MError('Y4M: bad XCOLORRANGE=%s (FULL or LIMITED)' % crange)
+            else:
+                xt.append(val)
+        # other tags: ignored, as the format says
+    if w is None or h is None:
+        raise Y4MError('Y4M: header lacks W / H')
+    if fps is None:
+        raise Y4MError('Y4M: header lacks the frame rate F')
+    for nm, v in (('width', w), ('height', h)):
+        if not 2 <= v <= MAX_SIDE:
+            raise Y4MError('Y4M: %s %d outside 2..%d' % (nm, v, MAX_SIDE))
+    return Header(w, h, fps, inter, aspect, _CHROMA[ctag], crange, xt, ctag)
+
+
+def output_header(hdr, mfi):
+    """Header of the x M stream: the input's W H, F x M (reduced), progressive, A copied, C420jpeg, the input's XCOLORRANGE."""
+    return Header(hdr.w, hdr.h, hdr.fps * mfi, 'p', hdr.aspect, '420jpeg', hdr.color_range, (), '420jpeg')
+
+
+# ---- stream order of the x M output ----------------------------------------------------------------------------------------
+def n_output_frames(n_in, mfi):
+    """(n-3)*M + 1: per window S0 and the M-1 St, then the last window's S1; the first and last input frames have no output."""
+    return (n_in - 3) * mfi + 1 if n_in >= 4 else 0
+
+
+def output_index(k, j, mfi):
+    """Stream position of frame j of window k: j = 0 is S0 (deblurred B0), j = 1 .. M-1 is St at t = j/M, j = M is S1 (only
+    written for the last window)."""
+    return k * mfi + j
+
+
+def frame_offset(hdr_len, i, payload):
+    """Byte offset of output frame i in a file written by this module ('FRAME\\n' before every payload)."""
+    return hdr_len + i * (len(FRAME) + 1 + payload)
+
+
+# ---- reading -------------------------------------------------------------------------------------------------------------
+def _readline(f, what):
+    line = f.readline(_MAX_LINE)
+    if line and not line.endswith(b'\n'):
+        raise Y4MError('Y4M: %s line longer than %d bytes or cut off' % (what, _MAX_LINE))
+    return line
+
+
+def _readinto_full(f, mv):
+    """readinto until mv is full (a pipe returns short reads); returns the bytes read."""
+    got = 0
+    while got < len(mv):
+        k = f.readinto(mv[got:])
+        if not k:
+            break
+        got += k
+    return got
+
+
+def _frame_line(line, index):
+    if not (line == FRAME + b'\n' or line.startswith(FRAME + b' ')):
+        raise Y4MError('Y4M: frame %d does not start with FRAME (got %r)' % (index, bytes(line[:16])))
+
+
+class Reader:
+    """Sequential reader of a binary stream (a file, or stdin: nothing is seeked).  ``read_into(buf)`` fills one payload."""
+
+    def __init__(self, f):
+        self.f = f
+        line = _readline(f, 'header')
+        if not line:
+            raise Y4MError('Y4M: empty input: %s' % FIX)
+        self.header = parse_header(line)
+        self.header_bytes = len(line)
+        self.index = 0                                  # frames read so far
+
+    def read_into(self, buf):
+        """Next frame's payload into ``buf`` (writable, payload bytes).  False at a clean end of stream; a truncated frame raises."""
+        line = _readline(self.f, 'FRAME')
+        if not line:
+            return False
+        _frame_line(line, self.index)
+        mv = memoryview(buf).cast('B')
+        if len(mv) != self.header.payload:
+            raise ValueError('buffer of %d bytes for a payload of %d' % (len(mv), self.header.payload))
+        got = _readinto_full(self.f, mv)
+        if got != len(mv):
+            raise Y4MError('Y4M: truncated frame %d (%d of %d bytes)' % (self.index, got, len(mv)))
+        self.index += 1
+        return True
+
+
+def scan(f):
+    """One pass over the frame headers of a seekable file: (Header, header bytes, [file offset of every payload]).  The
+    payloads are skipped, not read; a truncated last frame raises."""
+    f.seek(0)
+    rd = Reader(f)
+    size = os.fstat(f.fileno()).st_size if hasattr(f, 'fileno') else None
+    p = rd.header.payload
+    offs = []
+    while True:
+        line = _readline(f, 'FRAME')
+        if not line:
+            break
+        _frame_line(line, len(offs))
+        off = f.tell()
+        end = size if size is not None else f.seek(0, io.SEEK_END)
+        if off + p > end:
+            raise Y4MError('Y4M: truncated frame %d (%d of %d bytes)' % (len(offs), end - off, p))
+        offs.append(off)
+        f.seek(off + p)
+    return rd.header, rd.header_bytes, offs
+
+
+class Frames:
+    """``host_frames`` of ``WindowRunner.run_clip_u8`` over a Y4M input: frame i is its payload (1-D uint8 tensor, pinned when a
+    GPU is present), read with ``readinto`` when first needed and dropped once the windows have moved past it (windows come in
+    increasing order and read frames k .. k+3).  ``peak`` = frames held at once: bounded by the runner's batch + 5, whatever
+    the input's length.
+
+    Frames(reader): the frames of a stream, read in order (stdin: nothing is seeked).
+    Frames.from_file(f, offsets, first, stop): frames first .. stop-1 of a scanned file (``scan``), by seek + readinto."""
+
+    def __init__(self, reader=None, payload=None, fetch=None, first=0, stop=None, pinned=None):
+        import torch
+        self.payload = reader.header.payload if reader is not None else payload
+        self._fetch = fetch or (lambda i, buf: reader.read_into(buf))
+        self.next, self.stop = first, stop
+        self.pinned = torch.cuda.is_available() if pinned is None else pinned
+        self.buf = {}
+        self.n = None                                   # index one past the last frame, once the end was seen
+        self.peak = 0
+
+    @classmethod
+    def from_file(cls, f, offsets, first, stop, payload, pinned=None):
+        def fetch(i, buf):
+            f.seek(offsets[i])
+            mv = memoryview(buf).cast('B')
+            if _readinto_full(f, mv) != len(mv):
+                raise Y4MError('Y4M: truncated frame %d' % i)
+            return True
+        return cls(payload=payload, fetch=fetch, first=first, stop=min(stop, len(offsets)), pinned=pinned)
+
+    def has(self, i):
+        """Reads through frame i; False when the input ends before it."""
+        import torch
+        while self.next <= i and self.n is None:
+            t = torch.empty(self.payload, dtype=torch.uint8, pin_memory=self.pinned)
+            if (self.stop is not None and self.next >= self.stop) or not self._fetch(self.next, t.numpy()):
+                self.n = self.next
+                break
+            self.buf[self.next] = t
+            self.next += 1
+            self.peak = max(self.peak, len(self.buf))
+        return i < self.next
+
+    def __getitem__(self, i):
+        if not self.has(i):
+            raise IndexError('Y4M frame %d: the input has %d frames' % (i, self.n))
+        for j in [j for j in self.buf if j < i - 3]:
+            del self.buf[j]
+        if i not in self.buf:
+            raise IndexError('Y4M frame %d was already dropped (frames are read in window order)' % i)
+        return self.buf[i]
+
+    def windows(self, first=0):
+        """(B0, B1, B-1, B2) of window k = first, first+1, ... while the input has frame k+3; frame k+4 is read ahead, so
+        ``is_last(k)`` is known when window k is handed out."""
+        k = first
+        while self.has(k + 3):
+            self.has(k + 4)
+            yield (k + 1, k + 2, k, k + 3)
+            k += 1
+
+    def is_last(self, k):
+        return self.n is not None and self.n == k + 4
+
+
+class Writer:
+    """Writes the header (unless ``at`` is given: then the frames go at byte offset ``at`` of a file another rank sized),
+    then frames ('FRAME\\n' + payload) in stream order."""
+
+    def __init__(self, f, header, at=None):
+        self.f = f
+        self.header = header
+        self.header_bytes = header.encode()
+        if at is None:
+            f.write(self.header_bytes)
+        else:
+            f.seek(at)
+        self.frames = 0
+
+    def write(self, payloads):
+        """payloads: uint8 [n, payload] (numpy array / CPU tensor) in stream order."""
+        for p in payloads:
+            self.f.write(FRAME + b'\n')
+            self.f.write(memoryview(p.numpy() if hasattr(p, 'numpy') else np.asarray(p)).cast('B'))
+            self.frames += 1

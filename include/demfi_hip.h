@@ -38,6 +38,10 @@ enum demfi_status {
     DEMFI_ERR_NODEV = -3     /* no gfx950 device visible */
 };
 
+/* Colour conversion of the Y4M stream edge (demfi_yuv420_to_bgr / demfi_bgr_to_yuv420 below). */
+enum demfi_yuv_matrix { DEMFI_BT601 = 0, DEMFI_BT709 = 1 };
+enum demfi_chroma_siting { DEMFI_420JPEG = 0, DEMFI_420MPEG2 = 1 };   /* chroma centred / co-sited horizontally, centred vertically */
+
 enum demfi_act { DEMFI_ACT_NONE = 0, DEMFI_ACT_RELU = 1, DEMFI_ACT_TANH = 2, DEMFI_ACT_SIGMOID = 3 };
 
 /* Output modes of a convolution segment (v = conv + bias):
@@ -345,6 +349,18 @@ int demfi_u8_ingest(const uint8_t* const* frames, int h, int w, float* x, void* 
 /* one BGR uint8 [h,w,3] frame -> planar fp32 [3,h,w] with the same arithmetic (ground-truth frames of the evaluation) */
 int demfi_u8_to_planar(const uint8_t* frame, int h, int w, float* out, void* stream);
 int demfi_frame_to_u8(const float* frame, uint8_t* out, int h, int w, int H, int W, void* stream);
+/* YUV 4:2:0 <-> BGR uint8 (the Y4M stream edge, demfi_amd/video.py), integer arithmetic that matches demfi_amd/y4m.py
+ * (yuv420_to_bgr_np / bgr_to_yuv420_np) bit for bit.  A 4:2:0 frame is the Y4M payload: Y [h,w], then Cb and Cr
+ * [ceil(h/2), ceil(w/2)]; any h, w in 2..16384.  matrix: DEMFI_BT601 / DEMFI_BT709; full_range: 0 = limited (Y 16-235,
+ * C 16-240), 1 = full.  Device buffers; one launch converts n frames.
+ * yuv420_to_bgr: frame i read at src + i*src_stride, written at dst + i*dst_stride; siting = the input's chroma siting.
+ * bgr_to_yuv420: output chroma is 420jpeg (centred).  Frame i is read at src + (i / group)*group_stride + (i % group)*src_stride
+ * (group <= 0: one group of n frames) and written at dst + i*dst_stride, so that frames kept per window in the sink's buffers
+ * land in stream order in one launch. */
+int demfi_yuv420_to_bgr(const uint8_t* src, int64_t src_stride, uint8_t* dst, int64_t dst_stride, int n, int h, int w, int matrix,
+                        int full_range, int siting, void* stream);
+int demfi_bgr_to_yuv420(const uint8_t* src, int64_t src_stride, int group, int64_t group_stride, uint8_t* dst, int64_t dst_stride,
+                        int n, int h, int w, int matrix, int full_range, void* stream);
 
 /* ---- on-GPU evaluation ------------------------------------------------------------
  * psnr (utils.py:652-660) and MATLAB-style 11x11 Gaussian ssim (utils.py:663-705) of one predicted frame against its
