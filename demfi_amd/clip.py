@@ -162,14 +162,17 @@ class _StreamedFrames:
 class ClipRunner:
     """x M interpolation of whole clips on this rank's GPU: frames in (host uint8 BGR), frames out (sink or files)."""
 
-    def __init__(self, model, height, width, n_tst=3, mfi=8, batch=4, world=1, rank=0, final_only=True, n_ctx=None, n_trunk=None, auto=False):
+    def __init__(self, model, height, width, n_tst=3, mfi=8, batch=4, world=1, rank=0, final_only=True, n_ctx=None, n_trunk=None, auto=False,
+                 retime=None):
         from .runner import WindowRunner
         # the clip pipeline delivers the LAST recursion's frames only (like test_custom, utils.py:1430-1434), so the decoder
-        # passes that only produce the earlier recursions' frames need not run: same delivered bytes (WindowRunner.final_only)
-        self.runner = WindowRunner(model, height, width, n_tst, mfi, final_only=final_only, n_ctx=n_ctx, n_trunk=n_trunk, auto=auto)
+        # passes that only produce the earlier recursions' frames need not run: same delivered bytes (WindowRunner.final_only).
+        # retime: the frame rate ratio of the Y4M edge (demfi_amd.video --fps), see WindowRunner
+        self.runner = WindowRunner(model, height, width, n_tst, mfi, final_only=final_only, n_ctx=n_ctx, n_trunk=n_trunk, auto=auto,
+                                   retime=retime)
         self.h, self.w, self.mfi, self.batch = height, width, mfi, batch
         self.world, self.rank = world, rank
-        self.ts = t_schedule(mfi)
+        self.ts = t_schedule(mfi) if retime is None else None
 
     def my_windows(self, n_frames):
         wins = window_list(n_frames)

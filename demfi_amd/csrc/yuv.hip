@@ -200,7 +200,51 @@ __global__ __launch_bounds__(NT) void yuv420_to_bgr_kernel(const uint8_t* __rest
     }
 }
 
-// one lane: luma rows 2cy, 2cy+1 (the second clamped to h-1 at an odd bottom edge) x columns x0 .. x0+7 -> 16 Y, 4 Cb, 4 Cr
+// one lane of one frame: BGR frame S -> 4:2:0 payload Y, luma rows 2cy, 2cy+1 (the second clamped to h-1 at an odd bottom edge) x
+// columns x0 .. x0+7 -> 16 Y, 4 Cb, 4 Cr.  Shared by the strided and the gathered conversion as a statement macro, not as an
+// inline function: the inlined call changed the register allocation of bgr_to_yuv420_kernel, the macro keeps its
+// instruction stream as it was.  Uses cy, x0, c0, h, w, cw, ch, k of the enclosing kernel.
+#define DEMFI_BGR_TO_YUV420_STRIP(S_, Y_)                                                                \
+    do {                                                                                                 \
+    const uint8_t* Sp = (S_);                                                                               \
+    uint8_t* Yp = (Y_);                                                                                     \
+    int cbs[4] = {0, 0, 0, 0}, crs[4] = {0, 0, 0, 0};                                                    \
+    for (int r = 0; r < 2; ++r) {                                                                        \
+        const int y = min(2 * cy + r, h - 1);                                                            \
+        uint64_t q[3];                                                                                   \
+        load_bgr8(Sp + (int64_t)y * w * 3, x0, w, q);                                                     \
+        uint64_t yo = 0;                                                                                 \
+_Pragma("unroll")                                                                                          \
+        for (int px = 0; px < SX; ++px) {                                                                \
+            const int B = byte_of(q, 3 * px), G = byte_of(q, 3 * px + 1), R = byte_of(q, 3 * px + 2);    \
+            const int yv = sat_shr<16>(k.y_r * R + k.y_g * G + k.y_b * B + (k.yoff << 16) + (1 << 15));  \
+            yo |= (uint64_t)yv << (8 * px);                                                              \
+            cbs[px >> 1] += k.cb_r * R + k.cb_g * G + k.cb_b * B;                                        \
+            crs[px >> 1] += k.cr_r * R + k.cr_g * G + k.cr_b * B;                                        \
+        }                                                                                                \
+        if (2 * cy + r < h) store8(Yp + (int64_t)y * w + x0, yo, w - x0);                                 \
+    }                                                                                                    \
+    uint32_t cbo = 0, cro = 0;                                                                           \
+    for (int i = 0; i < 4; ++i) {                                                                        \
+        cbo |= (uint32_t)sat_shr<18>(cbs[i] + (128 << 18) + (1 << 17)) << (8 * i);                       \
+        cro |= (uint32_t)sat_shr<18>(crs[i] + (128 << 18) + (1 << 17)) << (8 * i);                       \
+    }                                                                                                    \
+    uint8_t* pcb = Yp + (int64_t)h * w + (int64_t)cy * cw + c0;                                           \
+    uint8_t* pcr = pcb + (int64_t)ch * cw;                                                               \
+    if (c0 + 4 <= cw && ((uintptr_t)pcb & 3) == 0 && ((uintptr_t)pcr & 3) == 0) {                        \
+        *gp<uint32_t>(pcb) = cbo;                                                                        \
+        *gp<uint32_t>(pcr) = cro;                                                                        \
+    } else {                                                                                             \
+_Pragma("unroll")                                                                                          \
+        for (int i = 0; i < 4; ++i) {                                                                    \
+            if (i < cw - c0) {                                                                           \
+                gp<uint8_t>(pcb)[i] = (uint8_t)(cbo >> (8 * i));                                         \
+                gp<uint8_t>(pcr)[i] = (uint8_t)(cro >> (8 * i));                                         \
+            }                                                                                            \
+        }                                                                                                \
+    }                                                                                                    \
+    } while (0)
+
 __global__ __launch_bounds__(NT) void bgr_to_yuv420_kernel(const uint8_t* __restrict__ src, int64_t src_stride, int group,
                                                           int64_t group_stride, uint8_t* __restrict__ dst, int64_t dst_stride, int n,
                                                           int h, int w, ToYuv k)
@@ -212,43 +256,21 @@ __global__ __launch_bounds__(NT) void bgr_to_yuv420_kernel(const uint8_t* __rest
     for (int f = blockIdx.y; f < n; f += gridDim.y) {
         const int g = f / group;
         const uint8_t* S = src + (int64_t)g * group_stride + (int64_t)(f - g * group) * src_stride;
-        uint8_t* Y = dst + (int64_t)f * dst_stride;
-        int cbs[4] = {0, 0, 0, 0}, crs[4] = {0, 0, 0, 0};
-        for (int r = 0; r < 2; ++r) {
-            const int y = min(2 * cy + r, h - 1);
-            uint64_t q[3];
-            load_bgr8(S + (int64_t)y * w * 3, x0, w, q);
-            uint64_t yo = 0;
-#pragma unroll
-            for (int px = 0; px < SX; ++px) {
-                const int B = byte_of(q, 3 * px), G = byte_of(q, 3 * px + 1), R = byte_of(q, 3 * px + 2);
-                const int yv = sat_shr<16>(k.y_r * R + k.y_g * G + k.y_b * B + (k.yoff << 16) + (1 << 15));
-                yo |= (uint64_t)yv << (8 * px);
-                cbs[px >> 1] += k.cb_r * R + k.cb_g * G + k.cb_b * B;
-                crs[px >> 1] += k.cr_r * R + k.cr_g * G + k.cr_b * B;
-            }
-            if (2 * cy + r < h) store8(Y + (int64_t)y * w + x0, yo, w - x0);
-        }
-        uint32_t cbo = 0, cro = 0;
-        for (int i = 0; i < 4; ++i) {
-            cbo |= (uint32_t)sat_shr<18>(cbs[i] + (128 << 18) + (1 << 17)) << (8 * i);
-            cro |= (uint32_t)sat_shr<18>(crs[i] + (128 << 18) + (1 << 17)) << (8 * i);
-        }
-        uint8_t* pcb = Y + (int64_t)h * w + (int64_t)cy * cw + c0;
-        uint8_t* pcr = pcb + (int64_t)ch * cw;
-        if (c0 + 4 <= cw && ((uintptr_t)pcb & 3) == 0 && ((uintptr_t)pcr & 3) == 0) {
-            *gp<uint32_t>(pcb) = cbo;
-            *gp<uint32_t>(pcr) = cro;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (i < cw - c0) {
-                    gp<uint8_t>(pcb)[i] = (uint8_t)(cbo >> (8 * i));
-                    gp<uint8_t>(pcr)[i] = (uint8_t)(cro >> (8 * i));
-                }
-            }
-        }
+        DEMFI_BGR_TO_YUV420_STRIP(S, dst + (int64_t)f * dst_stride);
     }
+}
+
+// frame f read at base + offs[f]: one (wave-uniform) offset load per frame, the rest as bgr_to_yuv420_kernel
+__global__ __launch_bounds__(NT) void bgr_to_yuv420_gather_kernel(const uint8_t* __restrict__ base, const int64_t* __restrict__ offs,
+                                                                 uint8_t* __restrict__ dst, int64_t dst_stride, int n, int h, int w,
+                                                                 ToYuv k)
+{
+    const int cw = (w + 1) >> 1, ch = (h + 1) >> 1, ns = (w + SX - 1) / SX;
+    const int id = blockIdx.x * NT + threadIdx.x;
+    if (id >= ch * ns) return;
+    const int cy = id / ns, x0 = (id - cy * ns) * SX, c0 = x0 >> 1;
+    for (int f = blockIdx.y; f < n; f += gridDim.y)
+        DEMFI_BGR_TO_YUV420_STRIP(base + offs[f], dst + (int64_t)f * dst_stride);
 }
 
 int check_common(const char* fn, const void* src, const void* dst, int n, int h, int w, int matrix, int full_range)
@@ -302,6 +324,24 @@ extern "C" int demfi_bgr_to_yuv420(const uint8_t* src, int64_t src_stride, int g
     if (n == 0) return DEMFI_OK;
     hipLaunchKernelGGL(bgr_to_yuv420_kernel, grid_for(n, h, w), dim3(NT), 0, (hipStream_t)stream, src, src_stride, group, group_stride,
                        dst, dst_stride, n, h, w, to_yuv_coefs(matrix, full_range));
+    DEMFI_HIP_CHECK(hipGetLastError());
+    return DEMFI_OK;
+}
+
+extern "C" int demfi_bgr_to_yuv420_gather(const uint8_t* base, const int64_t* src_offsets, uint8_t* dst, int64_t dst_stride, int n,
+                                          int h, int w, int matrix, int full_range, void* stream)
+{
+    int st = check_common("demfi_bgr_to_yuv420_gather", base, dst, n, h, w, matrix, full_range);
+    if (st < 0) return st;
+    if (!src_offsets)
+        return demfi_set_error(DEMFI_ERR_ARG, "demfi_bgr_to_yuv420_gather: NULL src_offsets");
+    const int64_t payload = (int64_t)h * w + 2 * (int64_t)((h + 1) / 2) * ((w + 1) / 2);
+    if (n > 1 && dst_stride < payload)
+        return demfi_set_error(DEMFI_ERR_ARG, "demfi_bgr_to_yuv420_gather: dst_stride %lld below the payload %lld",
+                               (long long)dst_stride, (long long)payload);
+    if (n == 0) return DEMFI_OK;
+    hipLaunchKernelGGL(bgr_to_yuv420_gather_kernel, grid_for(n, h, w), dim3(NT), 0, (hipStream_t)stream, base, src_offsets, dst, dst_stride,
+                       n, h, w, to_yuv_coefs(matrix, full_range));
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }

@@ -55,16 +55,22 @@ def module_window_u8(model, frames_u8, num_update, mfi):
     frames_u8: 4 uint8 [h,w,3] tensors (B0, B1, B-1, B2; host or GPU).  Returns (St uint8 [M-1,h,w,3], S0S1 uint8 [2,h,w,3]) on
     the GPU -- what ``bench.py`` and the 720p test compare the scheduler's sunk bytes against, byte for byte (S0 / S1 from the
     first time instant, like main.py:1165-1172)."""
+    return module_window_ts_u8(model, frames_u8, num_update, t_schedule(mfi))
+
+
+def module_window_ts_u8(model, frames_u8, num_update, ts):
+    """``module_window_u8`` at the time instants ``ts`` (float32 values) instead of the x M schedule: (St uint8 [len(ts),h,w,3],
+    S0S1 uint8 [2,h,w,3] of the first instant)."""
     from .metrics import u8_frame_to_tensor
     dev = model.device
     fr = [f.to(dev) for f in frames_u8]
     h, w = fr[0].shape[:2]
     x = torch.stack([u8_frame_to_tensor(f) for f in fr], 1).unsqueeze(0)          # [1,3,4,h,w]
     lib = L.load()
-    st = torch.zeros((mfi - 1, h, w, 3), dtype=torch.uint8, device=dev)
+    st = torch.zeros((len(ts), h, w, 3), dtype=torch.uint8, device=dev)
     s01 = torch.zeros((2, h, w, 3), dtype=torch.uint8, device=dev)
     sh = torch.cuda.current_stream(dev).cuda_stream
-    for j, t in enumerate(t_schedule(mfi)):
+    for j, t in enumerate(ts):
         fin = pad_forward_crop(model, x, torch.tensor([[float(t)]], device=dev), num_update)[1][num_update - 1]
         planes = [f[0].contiguous() for f in fin]                                  # S0, S1, St: [3,h,w] fp32
         L.check(lib.demfi_frame_to_u8(planes[2].data_ptr(), st[j].data_ptr(), h, w, h, w, sh), 'to_u8')

@@ -18,13 +18,17 @@ import os
 
 import torch
 
+from fractions import Fraction
+
 from . import _lib as L
+from . import retime as R
 from .harness import t_schedule
 from .y4m import payload_size
 
 
 class WindowRunner:
-    def __init__(self, model, height, width, n_tst=3, mfi=8, use_graph=True, final_only=False, n_ctx=None, n_trunk=None, auto=False):
+    def __init__(self, model, height, width, n_tst=3, mfi=8, use_graph=True, final_only=False, n_ctx=None, n_trunk=None, auto=False,
+                 retime=None):
         """final_only: produce the frames of the LAST recursion only (what test / test_custom consume, utils.py:1430-1434):
         the warp + D2 tail of the earlier recursions feeds nothing else and is skipped (batched plan only); the delivered
         frames are bit-identical.
@@ -33,7 +37,11 @@ class WindowRunner:
         fails loudly).  None = default: env DEMFI_NCTX / DEMFI_NTRUNK, else the configuration of an engine the model
         already holds for this frame size, else FIXED values that depend on the arguments only (7 / 3 at 720p x8 fp16, 7 / 2 at
         720p fp32 N_tst=5, 5 / 3 at 1080p x16); ``auto=True`` (or env DEMFI_AUTO=1) opts into a probe of the free memory instead.  The chosen values and
-        how they were chosen are exposed as ``self.n_ctx`` / ``self.n_trunk`` / ``self.config`` and printed by bench.py."""
+        how they were chosen are exposed as ``self.n_ctx`` / ``self.n_trunk`` / ``self.config`` and printed by bench.py.
+        retime: output / input frame rate ratio r >= 1 (a Fraction) of the Y4M edge of ``run_clip_u8`` in place of x M: window k
+        runs the instants of ``retime.window_plan`` (``mfi`` is not used).  An explicit n_ctx is taken as given; the default is
+        ``retime.default_n_ctx`` over the sizes whose workspace fits the GPU.  ``instants_run`` / ``instants_padded`` count the
+        time instants run and the padded per-t slots of short batched chunks."""
         auto = bool(auto or os.environ.get('DEMFI_AUTO') == '1')
         self.final_only = bool(final_only)
         self.h, self.w = height, width
@@ -43,10 +51,18 @@ class WindowRunner:
         env_ctx = os.environ.get('DEMFI_NCTX')
         # batched mode (default): the time instants of a window run as ONE launch sequence whose convolutions are batched
         # over n_ctx per-t contexts (demfi_forward_tb).  DEMFI_TB=0: one graph per time instant on n_ctx streams (round-2a).
-        self.tb = bool(use_graph and mfi > 2 and os.environ.get('DEMFI_TB', '1') != '0')
+        if retime is not None and not isinstance(retime, (int, Fraction)):
+            raise TypeError('WindowRunner: retime must be an int or a Fraction, got %r' % (retime,))
+        self.retime = Fraction(retime) if retime is not None else None
+        if self.retime is not None and not 1 <= self.retime <= R.MAX_RATIO:
+            raise ValueError('WindowRunner: retime ratio %s outside 1 .. %d' % (self.retime, R.MAX_RATIO))
+        if self.retime is not None:
+            self.tb = bool(use_graph and os.environ.get('DEMFI_TB', '1') != '0')
+        else:
+            self.tb = bool(use_graph and mfi > 2 and os.environ.get('DEMFI_TB', '1') != '0')
         # a runner built earlier on this model for the same frame size fixed the engine's shape: take it over (batched mode) instead
         # of probing the memory again -- a second runner (bench.py's final_only one) must not force a second multi-GB engine
-        cached = getattr(model, '_engines', {}).get((H, W, model.path_dtype)) if self.tb else None     # the plain slot only: never forward()'s batch engine
+        cached = getattr(model, '_engines', {}).get((H, W, model.path_dtype)) if (self.tb and self.retime is None) else None     # the plain slot only: never forward()'s batch engine
         if cached is not None and cached.n_ctx <= 1:     # a plain forward()'s engine says nothing about a runner's configuration
             cached = None
         how = 'explicit' if (n_ctx is not None or n_trunk is not None) else None
@@ -59,6 +75,13 @@ class WindowRunner:
         if self.tb:
             if n_ctx is None and env_ctx:
                 n_ctx, how = int(env_ctx), 'env'
+            if n_ctx is None and self.retime is not None:
+                # fewest padded per-t slots over one period of the schedule, among the sizes whose workspace fits the GPU
+                how = how or 'retime schedule'
+                total = torch.cuda.get_device_properties(model.device).total_memory if torch.cuda.is_available() else 288 * 10 ** 9
+                n_ctx = R.default_n_ctx(self.retime, lambda d: 0 < lib.demfi_workspace_bytes(H, W, max(n_tst, 3), dt, n_trunk or 2, d) <= total)
+                if n_trunk is None and n_ctx > 1:    # n_ctx = 1 falls back to the non-batched plan and its two trunk sets
+                    n_trunk = 3 if 0 < lib.demfi_workspace_bytes(H, W, max(n_tst, 3), dt, 3, n_ctx) <= total // 2 else 2
             if n_ctx is None and cached is not None and (mfi - 1) % cached.n_ctx == 0:
                 n_ctx, how = cached.n_ctx, 'cached engine'
             if n_ctx is None and auto:
@@ -84,7 +107,7 @@ class WindowRunner:
                     # half of THIS device's memory (144 GB on an MI355X): a function of the arguments and the part, not of co-tenants
                     half = (torch.cuda.get_device_properties(model.device).total_memory // 2) if torch.cuda.is_available() else 144 * 10 ** 9
                     n_trunk = 3 if 0 < lib.demfi_workspace_bytes(H, W, max(n_tst, 3), dt, 3, n_ctx) <= half else 2
-            elif n_ctx > 1 and (mfi - 1) % n_ctx:
+            elif n_ctx > 1 and (mfi - 1) % n_ctx and self.retime is None:
                 raise ValueError('WindowRunner: n_ctx=%d must divide M-1=%d for the batched per-t plan' % (n_ctx, mfi - 1))
             self.n_ctx = int(n_ctx)
             self.tb = self.n_ctx > 1
@@ -92,7 +115,10 @@ class WindowRunner:
         if not self.tb:
             if n_ctx is None:
                 how = 'env' if env_ctx else (how or 'fixed default')
-            self.n_ctx = (int(n_ctx) if n_ctx else min(int(env_ctx or 5), max(1, mfi - 1))) if (use_graph and mfi > 2) else 1
+            if self.retime is not None:
+                self.n_ctx = (int(n_ctx) if n_ctx else min(int(env_ctx or 5), R.max_instants(self.retime))) if use_graph else 1
+            else:
+                self.n_ctx = (int(n_ctx) if n_ctx else min(int(env_ctx or 5), max(1, mfi - 1))) if (use_graph and mfi > 2) else 1
             self.final_only = False                  # a mode of the batched plan
         how = how or 'fixed default'
         need = lib.demfi_workspace_bytes(H, W, max(n_tst, 3), dt, self.n_trunk, self.n_ctx)
@@ -105,13 +131,16 @@ class WindowRunner:
         self.engine = model.engine(H, W, n_tst, n_ctx=self.n_ctx, n_trunk=self.n_trunk, exact_ctx=self.tb)
         self._weights_version = model._weights_version
         self.n_tst, self.mfi = n_tst, mfi
-        self.ts = [float(t) for t in t_schedule(mfi)]
         dev = self.engine.device
         self.stream = torch.cuda.Stream(dev)                                   # trunk stream
         self.t_streams = [torch.cuda.Stream(dev) for _ in range(self.n_ctx)]   # one per per-t context
-        self.out = torch.zeros((mfi - 1, 3, height, width), dtype=torch.float32, device=dev)   # St per t (run_window)
-        self.s01 = torch.zeros((2, 3, height, width), dtype=torch.float32, device=dev)          # S0, S1 (first t)
-        self.t_all = torch.tensor(self.ts, dtype=torch.float32, device=dev)
+        if self.retime is None:
+            self.ts = [float(t) for t in t_schedule(mfi)]
+            self.out = torch.zeros((mfi - 1, 3, height, width), dtype=torch.float32, device=dev)   # St per t (run_window)
+            self.s01 = torch.zeros((2, 3, height, width), dtype=torch.float32, device=dev)          # S0, S1 (first t)
+            self.t_all = torch.tensor(self.ts, dtype=torch.float32, device=dev)
+        else:                                        # a retimed runner serves run_clip_u8's Y4M edge only: no x M buffers
+            self.ts = self.out = self.s01 = self.t_all = None
         self.lib = L.load()
         self.use_graph = use_graph
         self._g_trunk = None
@@ -119,6 +148,8 @@ class WindowRunner:
         self._next_ctx = 0
         self._next_trunk = 0
         self._t_done = [None] * self.n_trunk        # events: the per-t work that last read trunk context k
+        self.instants_run = 0                        # time instants run (padded slots not counted)
+        self.instants_padded = 0                     # per-t slots of short batched chunks that ran a repeated t and wrote nothing
 
     # ---------------------------------------------------------------------------------------------------------
     def _check_device(self, t, what):
@@ -151,6 +182,12 @@ class WindowRunner:
         if self._g_trunk is not None or not self.use_graph:
             return
         h = self.stream.cuda_stream
+        # the engine may come from the model's cache, used before by another runner whose uint8 sink records still point at
+        # that runner's (possibly freed) output buffers: the warm-up below must write nothing, so every record is disabled first
+        with torch.cuda.stream(self.stream):
+            for row in e._ctxs:
+                for ctx in row:
+                    ctx['sink'].zero_()
         for k in range(self.n_trunk):                # warm every context (module load, attributes) before capture
             e.use_ctx(0, trunk=k)
             e.run_trunk(h)
@@ -178,12 +215,20 @@ class WindowRunner:
             s.synchronize()
         e.use_ctx(0, trunk=0)
 
-    def _window(self, load, emit, body_only=False, pre=None, emit_ctx=False):
+    def _window(self, load, emit, body_only=False, pre=None, emit_ctx=False, t_dev=None, nt=None):
         """One window: load(engine, stream_handle) fills the bound trunk context's input on the trunk stream;
         emit(j, finals, stream_handle) copies the outputs of time instant j out of a per-t context on that context's stream.
         body_only: load() already did the trunk's prologue (fused uint8 ingest).  pre(j, ctx): runs on the per-t stream before
-        the per-t segment of time instant j (sets the uint8 sink record)."""
+        the per-t segment of time instant j (sets the uint8 sink record).
+        t_dev / nt: the window's own nt instants (device fp32, padded to a multiple of n_ctx with the last t) in place of the
+        x M schedule.  A short last batched chunk runs its padded slots with an all-zero (disabled) sink record: they compute
+        and write nothing, and neither pre nor emit is called for them."""
         e = self.engine
+        if t_dev is None:
+            if self.retime is not None:
+                raise ValueError('WindowRunner: a retimed runner runs the Y4M edge of run_clip_u8 only, not the x M entry points')
+            t_dev, nt = self.t_all, self.mfi - 1
+        self.instants_run += nt
         k = self._next_trunk
         self._next_trunk = (k + 1) % self.n_trunk
         if self._t_done[k] is not None:              # the time instants that last read trunk context k must be done
@@ -208,15 +253,19 @@ class WindowRunner:
             st = self.t_streams[k % len(self.t_streams)]
             st.wait_event(ev_trunk)
             with torch.cuda.stream(st):
-                for j0 in range(0, self.mfi - 1, self.n_ctx):
-                    e._tb[k]['t_col'].copy_(self.t_all[j0:j0 + self.n_ctx], non_blocking=True)
+                for j0 in range(0, nt, self.n_ctx):
+                    cnt = min(self.n_ctx, nt - j0)
+                    self.instants_padded += self.n_ctx - cnt
+                    e._tb[k]['t_col'].copy_(t_dev[j0:j0 + self.n_ctx], non_blocking=True)
                     if pre is not None:
-                        for c in range(self.n_ctx):
+                        for c in range(cnt):
                             pre(j0 + c, e._ctxs[k][c])
+                        if cnt < self.n_ctx:
+                            e._tb[k]['sink_all'][cnt:].zero_()
                     else:
                         e._tb[k]['sink_all'].zero_()  # float path: a sink left by an earlier uint8 run must not fire
                     L.check(self.lib.demfi_graph_launch(self._g_tb[k], st.cuda_stream), 'graph_launch')
-                    for c in range(self.n_ctx):
+                    for c in range(cnt):
                         if emit_ctx:
                             emit(j0 + c, e._ctxs[k][c]['finals'][self.n_tst - 1], st.cuda_stream, e._ctxs[k][c])
                         else:
@@ -226,7 +275,7 @@ class WindowRunner:
             self._t_done[k] = [ev]
             return
         used = set()
-        for j in range(self.mfi - 1):
+        for j in range(nt):
             c = self._next_ctx
             self._next_ctx = (c + 1) % self.n_ctx
             st = self.t_streams[c]
@@ -235,7 +284,7 @@ class WindowRunner:
                 st.wait_event(ev_trunk)
                 used.add(c)
             with torch.cuda.stream(st):
-                ctx['t_dev'].copy_(self.t_all[j:j + 1], non_blocking=True)
+                ctx['t_dev'].copy_(t_dev[j:j + 1], non_blocking=True)
                 if pre is not None:
                     pre(j, ctx)
                 else:
@@ -457,7 +506,11 @@ class WindowRunner:
         consecutive slots, so each frame is converted once.  After the sink's buffers of a batch are written, one
         ``demfi_bgr_to_yuv420`` launch puts its frames in stream order (per window S0, then St for t = 1/M .. (M-1)/M; plus
         S1 when ``with_s1(k)`` says window k is the clip's last) into a device buffer that is copied to pinned memory, and
-        sink(k, payloads) gets uint8 [M or M+1, payload] per window.  Returns the number of windows run."""
+        sink(k, payloads) gets uint8 [M or M+1, payload] per window.
+        With ``retime`` (constructor) the Y4M edge follows ``retime.window_plan`` instead: window k (its global index is B-1 of
+        its 4-tuple) runs its own instants, its frames sit in [S0, St x ceil(r), S1] slots, and ONE
+        ``demfi_bgr_to_yuv420_gather`` launch per batch puts its outputs in stream order; sink(k, payloads) gets as many
+        payloads as window k owns.  Returns the number of windows run."""
         dev = self.engine.device
         it = iter(windows)
         wins = list(itertools.islice(it, batch))
@@ -465,6 +518,8 @@ class WindowRunner:
             return 0
         M1 = self.mfi - 1
         mode = 'yuv' if yuv is not None else 'bgr'
+        if self.retime is not None and yuv is None:
+            raise ValueError('WindowRunner.run_clip_u8: a retimed runner needs the Y4M edge (yuv=...)')
         if getattr(self, '_clip', None) is None or self._clip['batch'] != batch or self._clip['mode'] != mode:
             self._clip = None
             nslot = 4 * batch + 4 if not reuse_frames else 2 * batch + 8
@@ -476,6 +531,20 @@ class WindowRunner:
                     's01': [torch.empty((batch, 2, self.h, self.w, 3), dtype=torch.uint8, device=dev) for _ in range(2)],
                     'h_out': [torch.empty((batch, M1, self.h, self.w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)],
                     'h_s01': [torch.empty((batch, 2, self.h, self.w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)],
+                })
+            elif self.retime is not None:
+                # per window [S0, St x J, S1] with J = ceil(r) >= |T_k|; the outputs of a batch are gathered into stream order
+                P = payload_size(self.h, self.w)
+                J = R.max_instants(self.retime)
+                nJ = -(-J // self.n_ctx) * self.n_ctx if self.tb else J      # instants incl. the padding of a short chunk
+                comb = [torch.empty((batch, J + 2, self.h, self.w, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
+                cl.update({
+                    'J': J, 'comb': comb, 'yuv_in': torch.empty((cl['slots'].shape[0], P), dtype=torch.uint8, device=dev),
+                    't': [torch.empty((batch, nJ), dtype=torch.float32, device=dev) for _ in range(2)],
+                    'sinks': [torch.empty((batch, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)],
+                    'offs': [torch.empty(batch * J + 1, dtype=torch.int64, device=dev) for _ in range(2)],
+                    'yuv_out': [torch.empty((batch * J + 1, P), dtype=torch.uint8, device=dev) for _ in range(2)],
+                    'h_yuv': [torch.empty((batch * J + 1, P), dtype=torch.uint8).pin_memory() for _ in range(2)],
                 })
             else:
                 # per window [S0, St x (M-1), S1]: the frames of a batch in stream order are M per window at a fixed stride
@@ -541,8 +610,13 @@ class WindowRunner:
             cur.wait_event(ev_up)
             if ev_d2h[i] is not None:
                 cur.wait_event(ev_d2h[i])                     # the D2H of batch b-2 has read this output buffer
-            self.run_windows_u8(dev_wins, out=cl['out'][i][:len(wins)], s01=cl['s01'][i][:len(wins)])
-            nf = self._yuv_egress(i, n, len(wins), yuv, cur) if yuv is not None else None
+            if self.retime is not None:
+                plans = [R.window_plan(win[2], self.retime, yuv.with_s1(n + wi)) for wi, win in enumerate(wins)]
+                self._run_windows_rt(i, dev_wins, plans)
+                nf = self._yuv_egress_rt(i, plans, yuv, cur)
+            else:
+                self.run_windows_u8(dev_wins, out=cl['out'][i][:len(wins)], s01=cl['s01'][i][:len(wins)])
+                nf = self._yuv_egress(i, n, len(wins), yuv, cur) if yuv is not None else None
             ev = torch.cuda.Event()
             ev.record(cur)
             ev_done[i] = ev
@@ -556,7 +630,8 @@ class WindowRunner:
             with torch.cuda.stream(cl['d2h']):
                 cl['d2h'].wait_event(ev)
                 if yuv is not None:
-                    cl['h_yuv'][i][:nf].copy_(cl['yuv_out'][i][:nf], non_blocking=True)
+                    nt = sum(nf) if isinstance(nf, list) else nf
+                    cl['h_yuv'][i][:nt].copy_(cl['yuv_out'][i][:nt], non_blocking=True)
                 else:
                     cl['h_out'][i][:len(wins)].copy_(cl['out'][i][:len(wins)], non_blocking=True)
                     cl['h_s01'][i][:len(wins)].copy_(cl['s01'][i][:len(wins)], non_blocking=True)
@@ -574,6 +649,12 @@ class WindowRunner:
         k0, cnt, i, nf = pending
         ev_d2h[i].synchronize()
         if sink is None:
+            return
+        if isinstance(nf, list):                         # retimed Y4M: nf[j] payloads of window k0 + j, in stream order
+            hy, pos = self._clip['h_yuv'][i], 0
+            for j, c in enumerate(nf):
+                sink(k0 + j, hy[pos:pos + c])
+                pos += c
             return
         if nf is not None:                               # Y4M: M payloads per window, the last one's S1 after them
             hy = self._clip['h_yuv'][i]
@@ -613,6 +694,62 @@ class WindowRunner:
                                                  self.w, yuv.matrix, int(yuv.full_range), cur.cuda_stream), 'bgr_to_yuv420')
             nf += 1
         return nf
+
+    def _run_windows_rt(self, i, dev_wins, plans):
+        """Retimed batch: window w of ``dev_wins`` runs the instants of plans[w] = ``retime.window_plan``; its frames go to
+        comb[i][w] = [S0, St x J, S1].  The t values and the uint8 sink records (one per (window, instant); S0 / S1 only in the
+        row of the window's first instant and only when that frame is an output) are uploaded on the current stream."""
+        import numpy as np
+        cl = self._clip
+        comb, J = cl['comb'][i], cl['J']
+        nw, nJ = len(plans), cl['t'][i].shape[1]
+        tt = np.empty((nw, nJ), np.float32)
+        for w, (ts, _) in enumerate(plans):
+            tt[w, :len(ts)] = ts
+            tt[w, len(ts):] = ts[-1]                     # padded slots repeat the last t
+        t_dev = cl['t'][i][:nw]
+        t_dev.copy_(torch.from_numpy(tt).pin_memory(), non_blocking=True)
+        rows = None
+        if self.engine.supports_u8_sink:
+            a = np.zeros((nw, nJ, 32), np.int64)         # rows past a window's instants stay zero (disabled)
+            base, (c0, c1) = comb.data_ptr(), comb.stride()[:2]      # uint8: element strides are bytes
+            for w, (ts, outs) in enumerate(plans):
+                kinds = {kind for _, kind, _ in outs}
+                for j in range(len(ts)):
+                    a[w, j, 2] = base + w * c0 + (1 + j) * c1                          # frame[2] = St
+                    a[w, j, 8] = self.h | (self.w << 32)                                # int32 h, w
+                    a[w, j, 9] = self.n_tst - 1                                         # int32 iter, pad
+                if R.S0 in kinds:
+                    a[w, 0, 0] = base + w * c0                                          # frame[0] = S0
+                if R.S1 in kinds:
+                    a[w, 0, 1] = base + w * c0 + (J + 1) * c1                           # frame[1] = S1
+            rows = cl['sinks'][i][:nw]
+            rows.copy_(torch.from_numpy(a).pin_memory(), non_blocking=True)
+        io = [self._u8_io(fr, comb[w, 1:J + 1], comb[w, 0::J + 1], None if rows is None else rows[w]) for w, fr in enumerate(dev_wins)]
+        cur = self._begin()
+        for w, (load, emit, pre) in enumerate(io):
+            self._window(load, emit, body_only=True, pre=pre, t_dev=t_dev[w], nt=len(plans[w][0]))
+        self._end(cur)
+
+    def _yuv_egress_rt(self, i, plans, yuv, cur):
+        """Outputs of a retimed batch (comb[i]) -> yuv_out[i] in stream order: ONE gather launch on the compute stream.
+        Returns the number of payloads per window."""
+        cl = self._clip
+        comb, dst, J = cl['comb'][i], cl['yuv_out'][i], cl['J']
+        c0, c1 = comb.stride()[:2]
+        offs, counts = [], []
+        for w, (_, outs) in enumerate(plans):
+            for _, kind, j in outs:
+                offs.append(w * c0 + (0 if kind == R.S0 else J + 1 if kind == R.S1 else 1 + j) * c1)
+            counts.append(len(outs))
+        nf = len(offs)
+        if nf > dst.shape[0]:
+            raise RuntimeError('retime: %d outputs for %d payload slots' % (nf, dst.shape[0]))
+        od = cl['offs'][i][:nf]
+        od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
+        L.check(self.lib.demfi_bgr_to_yuv420_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), dst.shape[1], nf, self.h, self.w,
+                                                    yuv.matrix, int(yuv.full_range), cur.cuda_stream), 'bgr_to_yuv420_gather')
+        return counts
 
     def __del__(self):
         try:

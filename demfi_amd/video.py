@@ -1,11 +1,14 @@
-"""Video streams in, video streams out: x M interpolation of a YUV4MPEG2 (Y4M) stream.
+"""Video streams in, video streams out: x M interpolation of a YUV4MPEG2 (Y4M) stream, or retiming to any higher frame rate.
 
     ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe - | python -m demfi_amd.video - - --mfi 8 | ffmpeg -f yuv4mpegpipe -i - out.mp4
+    ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe - | python -m demfi_amd.video - - --fps 60000/1001 | ffmpeg -f yuv4mpegpipe -i - out.mp4
 
 The frames are those of the folder path (``python -m demfi_amd.clip``) for the same pixels, in the order of the reference's
 ``test_custom`` folder sorted by name (``clip.output_names`` / ``clip.deblurred_writes``): per window k, S0 (deblurred B0) and
 then St for t = 1/M .. (M-1)/M; after the last window its S1.  n input frames give (n-3)*M + 1 output frames: the first and
-the last input frame have no output of their own, as in the reference.
+the last input frame have no output of their own, as in the reference.  ``--fps F_out`` (an exact fraction, F_out >= F_in) puts
+output frame i at input time 1 + i * F_in / F_out instead and runs only the time instants those frames need
+(``demfi_amd.retime``); ``--fps M*F_in`` gives the bytes of ``--mfi M``.
 
 The colour conversion runs on the GPU next to the uint8 ingest / sink (csrc/yuv.hip, defined by ``y4m.yuv420_to_bgr_np`` /
 ``y4m.bgr_to_yuv420_np``): 4:2:0 payloads go host -> HBM (half the bytes of BGR), are converted once per frame into the
@@ -16,11 +19,13 @@ frames at their byte offsets of the output file (no collective on the data path)
 """
 import os
 import sys
+from fractions import Fraction
 
 import torch
 
 from . import _lib as L
 from . import dist as D
+from . import retime as R
 from . import y4m
 from .clip import ClipRunner
 
@@ -37,24 +42,63 @@ class YuvEdge:
 
 
 class VideoRunner:
-    """x M interpolation of Y4M input on this rank's GPU.  ``matrix``: 'auto' (BT.709 when H >= 720, else BT.601), 'bt601'
-    or 'bt709'; the output uses the input's matrix and range, so an ffmpeg round trip keeps the colours."""
+    """x M interpolation (``mfi``, default 8) or retiming to the output frame rate ``fps`` (a Fraction >= the input's rate) of
+    Y4M input on this rank's GPU; give one of the two.  ``matrix``: 'auto' (BT.709 when H >= 720, else BT.601), 'bt601'
+    or 'bt709'; the output uses the input's matrix and range, so an ffmpeg round trip keeps the colours.  After a run,
+    ``last_instants`` = (time instants run, padded per-t slots) and ``last_st_frames`` = St frames written, of this rank."""
 
-    def __init__(self, model, n_tst=3, mfi=8, batch=4, matrix='auto', **runner_kw):
+    def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, **runner_kw):
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
+        if mfi is not None and fps is not None:
+            raise ValueError('VideoRunner: give mfi or fps, not both')
+        if fps is not None and not isinstance(fps, (str, int, Fraction)) or isinstance(fps, bool):
+            raise TypeError('VideoRunner: fps must be a Fraction, an int or an "N/D" string (a float is not exact: 59.94 is not '
+                            '60000/1001), got %r' % (fps,))
+        self.fps = R.parse_fps(fps) if isinstance(fps, str) else (Fraction(fps) if fps is not None else None)
+        if self.fps is not None and self.fps <= 0:
+            raise ValueError('VideoRunner: fps must be > 0, got %s' % self.fps)
+        mfi = 8 if mfi is None and fps is None else mfi
         self.model, self.n_tst, self.mfi, self.batch, self.matrix = model, n_tst, mfi, batch, matrix
         self.runner_kw = runner_kw
         self._runners = {}
         self.last_decode_peak = 0
+        self.last_instants = (0, 0)
+        self.last_st_frames = 0
+        self.last_fps_out = None
+
+    def _ratio(self, hdr):
+        """None (x M) or the retime ratio F_out / F_in of this input."""
+        return None if self.fps is None else R.ratio(hdr.fps, self.fps)
+
+    def _out_header(self, hdr):
+        ohdr = y4m.output_header(hdr, self.mfi) if self.fps is None else R.output_header(hdr, self.fps)
+        self.last_fps_out = ohdr.fps
+        return ohdr
+
+    def _n_out(self, n_in, hdr):
+        return y4m.n_output_frames(n_in, self.mfi) if self.fps is None else R.n_output_frames(n_in, self._ratio(hdr))
 
     def _clip_runner(self, hdr, world, rank):
-        key = (hdr.h, hdr.w, world, rank)
+        r = self._ratio(hdr)
+        key = (hdr.h, hdr.w, world, rank, r)
         cr = self._runners.get(key)
         if cr is None:
-            cr = self._runners[key] = ClipRunner(self.model, hdr.h, hdr.w, self.n_tst, self.mfi, batch=self.batch, world=world,
-                                                 rank=rank, **self.runner_kw)
+            kw = dict(self.runner_kw, retime=r) if r is not None else self.runner_kw
+            cr = self._runners[key] = ClipRunner(self.model, hdr.h, hdr.w, self.n_tst, self.mfi or 8, batch=self.batch, world=world,
+                                                 rank=rank, **kw)
         return cr
+
+    def _run(self, cr, hdr, lo, fn):
+        """fn() runs windows lo, lo+1, ... of the input on cr; returns its window count and sets the per-run counters."""
+        rn = cr.runner
+        i0, p0 = rn.instants_run, rn.instants_padded
+        n = fn()
+        self.last_instants = (rn.instants_run - i0, rn.instants_padded - p0)
+        r = self._ratio(hdr)
+        self.last_st_frames = (n * (self.mfi - 1) if r is None else
+                               sum(kind == R.ST for k in range(lo, lo + n) for _, kind, _ in R.window_outputs(k, r)))
+        return n
 
     def _edge(self, hdr, with_s1):
         return YuvEdge(y4m.auto_matrix(hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1)
@@ -64,14 +108,15 @@ class VideoRunner:
         windows and every batch is written (and flushed) as it drains.  Returns (windows, frames written)."""
         rd = y4m.Reader(src)
         hdr = rd.header
-        wr = y4m.Writer(dst, y4m.output_header(hdr, self.mfi))
+        cr = self._clip_runner(hdr, 1, 0)
+        wr = y4m.Writer(dst, self._out_header(hdr))
         frames = y4m.Frames(rd)
 
         def sink(k, payloads):
             wr.write(payloads)
             dst.flush()
-        cr = self._clip_runner(hdr, 1, 0)
-        n = cr.runner.run_clip_u8(frames, frames.windows(), sink, batch=self.batch, yuv=self._edge(hdr, frames.is_last))
+        n = self._run(cr, hdr, 0, lambda: cr.runner.run_clip_u8(frames, frames.windows(), sink, batch=self.batch,
+                                                                  yuv=self._edge(hdr, frames.is_last)))
         dst.flush()
         self.last_decode_peak = frames.peak
         return n, wr.frames
@@ -83,9 +128,9 @@ class VideoRunner:
         with open(in_path, 'rb') as f:
             hdr, _, offs = y4m.scan(f)
             n_in = len(offs)
-            ohdr = y4m.output_header(hdr, self.mfi)
+            ohdr = self._out_header(hdr)
             hb = ohdr.encode()
-            total = y4m.n_output_frames(n_in, self.mfi)
+            total = self._n_out(n_in, hdr)
             if rank == 0:
                 with open(out_path, 'wb') as o:
                     o.write(hb)
@@ -94,13 +139,17 @@ class VideoRunner:
             cr = self._clip_runner(hdr, world, rank)
             lo, wins = cr.my_windows(n_in)
             if not wins:
+                self.last_instants, self.last_st_frames = (0, 0), 0
                 return 0, 0
             n_windows = n_in - 3
             frames = y4m.Frames.from_file(f, offs, lo, lo + len(wins) + 3, hdr.payload)
+            r = self._ratio(hdr)
+            at = (y4m.frame_offset(len(hb), y4m.output_index(lo, 0, self.mfi), hdr.payload) if r is None else
+                  R.block_offset(len(hb), lo, r, hdr.payload))
             with open(out_path, 'r+b') as o:
-                wr = y4m.Writer(o, ohdr, at=y4m.frame_offset(len(hb), y4m.output_index(lo, 0, self.mfi), hdr.payload))
-                n = cr.runner.run_clip_u8(frames, wins, lambda k, p: wr.write(p), batch=self.batch,
-                                          yuv=self._edge(hdr, lambda k: lo + k == n_windows - 1))
+                wr = y4m.Writer(o, ohdr, at=at)
+                n = self._run(cr, hdr, lo, lambda: cr.runner.run_clip_u8(frames, wins, lambda k, p: wr.write(p), batch=self.batch,
+                                                                         yuv=self._edge(hdr, lambda k: lo + k == n_windows - 1)))
             self.last_decode_peak = frames.peak
             return n, wr.frames
 
@@ -109,9 +158,18 @@ def _is_regular(path):
     return path != '-' and (not os.path.exists(path) or os.path.isfile(path))
 
 
+def _fps_arg(text):
+    try:
+        return R.parse_fps(text)
+    except ValueError as e:
+        import argparse
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def main(argv=None):
-    """``python -m demfi_amd.video IN OUT`` -- x M interpolation of a Y4M stream; ``-`` is stdin / stdout.  The first and the last
-    input frame have no output (as in the reference's test_custom): n frames in, (n-3)*M + 1 out, at M times the frame rate."""
+    """``python -m demfi_amd.video IN OUT`` -- x M interpolation of a Y4M stream, or retiming to ``--fps``; ``-`` is stdin / stdout.
+    The first and the last input frame have no output (as in the reference's test_custom): n frames in, (n-3)*M + 1 out, at M
+    times the frame rate; with --fps, floor((n-3)*F_out/F_in) + 1 out at F_out."""
     import argparse
     import json
     import time
@@ -122,7 +180,11 @@ def main(argv=None):
                                         'input frame have no output, as in the reference.  All logging goes to stderr.')
     ap.add_argument('input', help="Y4M file, or - for stdin")
     ap.add_argument('output', help="Y4M file, or - for stdout")
-    ap.add_argument('--mfi', type=int, default=8, help='multiple_MFI: output frame rate = M x input (main.py:98)')
+    rate = ap.add_mutually_exclusive_group()
+    rate.add_argument('--mfi', type=int, default=None, help='multiple_MFI: output frame rate = M x input (main.py:98); default 8')
+    rate.add_argument('--fps', type=_fps_arg, default=None,
+                      help='output frame rate N, N/D or N:D (exact: 60000/1001, not 59.94), at least the input rate; output frame '
+                           'i is at input time 1 + i*F_in/F_out')
     ap.add_argument('--n-tst', type=int, default=3, help='N_tst recursive boosts (main.py:101)')
     ap.add_argument('--dtype', default='fp16', choices=['fp16', 'fp32'])
     ap.add_argument('--checkpoint', default='', help="reference checkpoint (.pt holding 'state_dict_Model')")
@@ -130,6 +192,8 @@ def main(argv=None):
                     help='YCbCr matrix of the input (and output); auto: BT.709 when H >= 720, else BT.601')
     ap.add_argument('--batch', type=int, default=4, help='windows per batch (the input frames held are bounded by it)')
     a = ap.parse_args(argv)
+    if a.fps is None and a.mfi is None:
+        a.mfi = 8
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     if world > 1 and not (_is_regular(a.input) and os.path.isfile(a.input) and _is_regular(a.output)):
         raise SystemExit('demfi_amd.video: with %d ranks IN and OUT must be regular files (ranks write at byte offsets)' % world)
@@ -151,7 +215,7 @@ def main(argv=None):
         model.load_state_dict(load_checkpoint(a.checkpoint) if a.checkpoint else synthetic_state_dict(0))
     model = model.to(dev).eval()
     D.broadcast_state_dict(model, world, device=dev)
-    vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix)
+    vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps)
     t0 = time.perf_counter()
     if world > 1:
         nw, nf = vr.run_file(a.input, a.output, world, rank)
@@ -166,13 +230,16 @@ def main(argv=None):
                 src.close()
     torch.cuda.synchronize()
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
-    tw, tf = (D.sum_over_ranks([float(nw), float(nf)], dev).tolist() if world > 1 else (nw, nf))
+    counts = [float(nw), float(nf), float(vr.last_st_frames), float(vr.last_instants[0]), float(vr.last_instants[1])]
+    tw, tf, tst, ti, tp = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
     if rank == 0:
         if tw == 0:
             print('demfi_amd.video: fewer than 4 input frames: no window, only the header was written', file=sys.stderr)
         print(json.dumps({'windows': int(tw), 'frames_written': int(tf), 'seconds': round(dt, 2), 'ranks': world,
-                          'St_frames_per_s': round(tw * (a.mfi - 1) / dt, 2) if dt > 0 else None,
+                          'St_frames_per_s': round((tw * (a.mfi - 1) if a.fps is None else tst) / dt, 2) if dt > 0 else None,
                           'frames_per_s': round(tf / dt, 2) if dt > 0 else None,
+                          'fps_out': str(vr.last_fps_out) if vr.last_fps_out is not None else None,
+                          'instants_run': int(ti), 'instants_padded': int(tp),
                           'weights': os.path.basename(a.checkpoint) if a.checkpoint else 'synthetic_state_dict(0) (random init: no checkpoint given)',
                           'out': a.output}), file=sys.stderr)
     D.finalize()

@@ -356,11 +356,16 @@ int demfi_frame_to_u8(const float* frame, uint8_t* out, int h, int w, int H, int
  * yuv420_to_bgr: frame i read at src + i*src_stride, written at dst + i*dst_stride; siting = the input's chroma siting.
  * bgr_to_yuv420: output chroma is 420jpeg (centred).  Frame i is read at src + (i / group)*group_stride + (i % group)*src_stride
  * (group <= 0: one group of n frames) and written at dst + i*dst_stride, so that frames kept per window in the sink's buffers
- * land in stream order in one launch. */
+ * land in stream order in one launch.
+ * bgr_to_yuv420_gather: as bgr_to_yuv420, but frame i is read at base + src_offsets[i] (src_offsets: n int64 byte offsets in
+ * DEVICE memory, any order, repeats allowed) and written at dst + i*dst_stride: the egress of a retimed stream, whose windows
+ * give a varying number of frames. */
 int demfi_yuv420_to_bgr(const uint8_t* src, int64_t src_stride, uint8_t* dst, int64_t dst_stride, int n, int h, int w, int matrix,
                         int full_range, int siting, void* stream);
 int demfi_bgr_to_yuv420(const uint8_t* src, int64_t src_stride, int group, int64_t group_stride, uint8_t* dst, int64_t dst_stride,
                         int n, int h, int w, int matrix, int full_range, void* stream);
+int demfi_bgr_to_yuv420_gather(const uint8_t* base, const int64_t* src_offsets, uint8_t* dst, int64_t dst_stride, int n, int h, int w,
+                               int matrix, int full_range, void* stream);
 
 /* ---- on-GPU evaluation ------------------------------------------------------------
  * psnr (utils.py:652-660) and MATLAB-style 11x11 Gaussian ssim (utils.py:663-705) of one predicted frame against its
