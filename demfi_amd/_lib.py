@@ -139,6 +139,7 @@ _SIGS = {
                                       C.c_int, C.c_int, C.c_void_p]),
     'demfi_bgr_to_yuv420_gather': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_int, C.c_void_p]),
+    'demfi_yuv420_sad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     'demfi_eval_workspace_bytes': (C.c_int64, [C.c_int, C.c_int]),
     'demfi_eval_frame': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),

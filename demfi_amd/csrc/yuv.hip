@@ -273,6 +273,54 @@ __global__ __launch_bounds__(NT) void bgr_to_yuv420_gather_kernel(const uint8_t*
         DEMFI_BGR_TO_YUV420_STRIP(base + offs[f], dst + (int64_t)f * dst_stride);
 }
 
+// SAD of frame pair f: |a - b| summed over the payload, a = base + a_offs[f], b = base + b_offs[f], any byte alignment of either.
+// The bytes before a's first 16-byte boundary (head) and after its last one (tail) go to the first 16 lanes of block x = 0, one
+// byte each; the body is 16-byte loads, aligned for a (b's loads may be unaligned, which global memory serves) and four v_sad_u8
+// per load pair.  A lane's partial stays below 2^32 (at most ceil(payload / 16 / NT) * 16 * 255 < 2^32 for payloads up to
+// 16384 x 16384 4:2:0); the wave and block sums are 64-bit, and each block adds its sum with ONE 64-bit atomic (integer adds are
+// exact in any order).
+__global__ __launch_bounds__(NT) void yuv420_sad_kernel(const uint8_t* __restrict__ base, const int64_t* __restrict__ a_offs,
+                                                       const int64_t* __restrict__ b_offs, int n, int64_t payload,
+                                                       unsigned long long* __restrict__ sad)
+{
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    typedef u4 u4_unaligned __attribute__((aligned(1)));
+    __shared__ unsigned long long part[NT / 64];
+    const int tid = threadIdx.x;
+    for (int f = blockIdx.y; f < n; f += gridDim.y) {
+        const uint8_t* a = base + a_offs[f];
+        const uint8_t* b = base + b_offs[f];
+        const int64_t head = min((int64_t)((16 - ((uintptr_t)a & 15)) & 15), payload);
+        const int64_t nvec = (payload - head) >> 4;
+        const int64_t tail = head + (nvec << 4);              // payload - tail < 16
+        uint32_t acc = 0;
+        if (blockIdx.x == 0 && tid < 16) {
+            if (tid < head) acc = __builtin_amdgcn_sad_u8(gcp<uint8_t>(a)[tid], gcp<uint8_t>(b)[tid], acc);
+            if (tail + tid < payload) acc = __builtin_amdgcn_sad_u8(gcp<uint8_t>(a)[tail + tid], gcp<uint8_t>(b)[tail + tid], acc);
+        }
+        for (int64_t v = (int64_t)blockIdx.x * NT + tid; v < nvec; v += (int64_t)gridDim.x * NT) {
+            const u4 x = *(const DEMFI_GLOBAL u4*)(a + head + 16 * v);
+            const u4 y = *(const DEMFI_GLOBAL u4_unaligned*)(b + head + 16 * v);
+            acc = __builtin_amdgcn_sad_u8(x.x, y.x, acc);
+            acc = __builtin_amdgcn_sad_u8(x.y, y.y, acc);
+            acc = __builtin_amdgcn_sad_u8(x.z, y.z, acc);
+            acc = __builtin_amdgcn_sad_u8(x.w, y.w, acc);
+        }
+        unsigned long long s = acc;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if ((tid & 63) == 0) part[tid >> 6] = s;
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long t = 0;
+#pragma unroll
+            for (int i = 0; i < NT / 64; ++i) t += part[i];
+            if (t) atomicAdd(sad + f, t);
+        }
+        __syncthreads();                                      // part[] is reused by the next pair
+    }
+}
+
 int check_common(const char* fn, const void* src, const void* dst, int n, int h, int w, int matrix, int full_range)
 {
     if (!src || !dst || n < 0)
@@ -342,6 +390,21 @@ extern "C" int demfi_bgr_to_yuv420_gather(const uint8_t* base, const int64_t* sr
     if (n == 0) return DEMFI_OK;
     hipLaunchKernelGGL(bgr_to_yuv420_gather_kernel, grid_for(n, h, w), dim3(NT), 0, (hipStream_t)stream, base, src_offsets, dst, dst_stride,
                        n, h, w, to_yuv_coefs(matrix, full_range));
+    DEMFI_HIP_CHECK(hipGetLastError());
+    return DEMFI_OK;
+}
+
+extern "C" int demfi_yuv420_sad(const uint8_t* base, const int64_t* a_offsets, const int64_t* b_offsets, int n, int64_t payload,
+                                uint64_t* sad, void* stream)
+{
+    if (!base || !a_offsets || !b_offsets || !sad || n < 0 || payload <= 0)
+        return demfi_set_error(DEMFI_ERR_ARG, "demfi_yuv420_sad: NULL buffer, n=%d or payload=%lld", n, (long long)payload);
+    if (n == 0) return DEMFI_OK;
+    DEMFI_HIP_CHECK(hipMemsetAsync(sad, 0, (size_t)n * sizeof(uint64_t), (hipStream_t)stream));
+    const int64_t blocks = ((payload >> 4) + NT - 1) / NT;
+    const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks > 1024 ? 1024 : blocks), (unsigned)(n < 65535 ? n : 65535));
+    hipLaunchKernelGGL(yuv420_sad_kernel, grid, dim3(NT), 0, (hipStream_t)stream, base, a_offsets, b_offsets, n, payload,
+                       (unsigned long long*)sad);
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }

@@ -22,6 +22,7 @@ from fractions import Fraction
 
 from . import _lib as L
 from . import retime as R
+from . import scene as S
 from .harness import t_schedule
 from .y4m import payload_size
 
@@ -150,6 +151,8 @@ class WindowRunner:
         self._t_done = [None] * self.n_trunk        # events: the per-t work that last read trunk context k
         self.instants_run = 0                        # time instants run (padded slots not counted)
         self.instants_padded = 0                     # per-t slots of short batched chunks that ran a repeated t and wrote nothing
+        self.cut_windows = 0                         # windows run as scene-cut windows (two runs, no interpolation)
+        self.last_cuts = []                          # frames that start a scene, as the last run_clip_u8 with scene cuts found them
 
     # ---------------------------------------------------------------------------------------------------------
     def _check_device(self, t, what):
@@ -510,16 +513,25 @@ class WindowRunner:
         With ``retime`` (constructor) the Y4M edge follows ``retime.window_plan`` instead: window k (its global index is B-1 of
         its 4-tuple) runs its own instants, its frames sit in [S0, St x ceil(r), S1] slots, and ONE
         ``demfi_bgr_to_yuv420_gather`` launch per batch puts its outputs in stream order; sink(k, payloads) gets as many
-        payloads as window k owns.  Returns the number of windows run."""
+        payloads as window k owns.
+        ``yuv.scene_cut`` = T (retimed runners only; ``--mfi M`` is r = M): scene cuts (``demfi_amd.scene``).  ``windows`` must
+        then be the consecutive unclamped tuples, and host_frames must also hold frame k0 - 1 when the first window k0 >= 1.
+        Each batch's new payloads are scored by ONE ``demfi_yuv420_sad`` launch on the h2d stream, read back with one event wait,
+        before its windows are planned: window k runs ``scene.window_runs``, a cut window as two runs.  The cuts found are in
+        ``last_cuts``; ``cut_windows`` counts the cut windows.  Returns the number of windows run."""
         dev = self.engine.device
         it = iter(windows)
         wins = list(itertools.islice(it, batch))
         if not wins:
             return 0
         M1 = self.mfi - 1
-        mode = 'yuv' if yuv is not None else 'bgr'
+        threshold = getattr(yuv, 'scene_cut', None)
+        mode = 'bgr' if yuv is None else 'yuv' if threshold is None else 'yuv+cuts'
         if self.retime is not None and yuv is None:
             raise ValueError('WindowRunner.run_clip_u8: a retimed runner needs the Y4M edge (yuv=...)')
+        if threshold is not None and (self.retime is None or not reuse_frames):
+            raise ValueError('WindowRunner.run_clip_u8: scene cuts need a retimed runner (r = M for x M) and reuse_frames')
+        runs_max = 2 * batch if threshold is not None else batch        # a cut window is two runs
         if getattr(self, '_clip', None) is None or self._clip['batch'] != batch or self._clip['mode'] != mode:
             self._clip = None
             nslot = 4 * batch + 4 if not reuse_frames else 2 * batch + 8
@@ -537,15 +549,20 @@ class WindowRunner:
                 P = payload_size(self.h, self.w)
                 J = R.max_instants(self.retime)
                 nJ = -(-J // self.n_ctx) * self.n_ctx if self.tb else J      # instants incl. the padding of a short chunk
-                comb = [torch.empty((batch, J + 2, self.h, self.w, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
+                nsl = cl['slots'].shape[0]
+                comb = [torch.empty((runs_max, J + 2, self.h, self.w, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
                 cl.update({
-                    'J': J, 'comb': comb, 'yuv_in': torch.empty((cl['slots'].shape[0], P), dtype=torch.uint8, device=dev),
-                    't': [torch.empty((batch, nJ), dtype=torch.float32, device=dev) for _ in range(2)],
-                    'sinks': [torch.empty((batch, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)],
+                    'J': J, 'comb': comb, 'yuv_in': torch.empty((nsl, P), dtype=torch.uint8, device=dev),
+                    't': [torch.empty((runs_max, nJ), dtype=torch.float32, device=dev) for _ in range(2)],
+                    'sinks': [torch.empty((runs_max, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)],
                     'offs': [torch.empty(batch * J + 1, dtype=torch.int64, device=dev) for _ in range(2)],
                     'yuv_out': [torch.empty((batch * J + 1, P), dtype=torch.uint8, device=dev) for _ in range(2)],
                     'h_yuv': [torch.empty((batch * J + 1, P), dtype=torch.uint8).pin_memory() for _ in range(2)],
                 })
+                if threshold is not None:                # SADs of a batch's new frames (at most nsl) against their predecessors
+                    cl.update({'sad': torch.empty(nsl, dtype=torch.int64, device=dev),
+                               'sad_offs': torch.empty(2 * nsl, dtype=torch.int64, device=dev),
+                               'h_sad': torch.empty(nsl, dtype=torch.int64).pin_memory()})
             else:
                 # per window [S0, St x (M-1), S1]: the frames of a batch in stream order are M per window at a fixed stride
                 P = payload_size(self.h, self.w)
@@ -569,13 +586,20 @@ class WindowRunner:
         pending = None                    # (first window, count, buffer[, frames per window]) whose D2H is in flight
         n = 0
         b = 0
+        det = None
+        if threshold is not None:
+            det = S.Detector(cl['yuv_in'].shape[1], threshold, first=S.first_frame(wins[0][2]))
+            self.last_cuts = det.cuts
         while wins:
             i = b & 1
             # ---- H2D of the frames this batch needs (copy stream) -------------------------------------------------
             dev_wins = []
             new_slots = []
+            new_frames = []
             with torch.cuda.stream(cl['h2d']):
-                for wi, win in enumerate(wins):
+                # scene cuts: the block's first window k0 >= 1 also needs frame k0 - 1, the predecessor SAD_k0 is taken against
+                first = [(-1, [det.next - 1])] if det is not None and b == 0 and det.next - 1 < wins[0][2] else []
+                for wi, win in first + list(enumerate(wins)):
                     fr = []
                     for idx in win:
                         key = idx if reuse_frames else (b, wi, idx)
@@ -588,6 +612,7 @@ class WindowRunner:
                                     del slot_of[k_old]
                             if slot_busy[sl] is not None:
                                 cl['h2d'].wait_event(slot_busy[sl])
+                            new_frames.append(idx)
                             f = host_frames[idx]
                             if yuv is not None:
                                 if tuple(f.shape) != tuple(cl['yuv_in'].shape[1:]) or f.dtype != torch.uint8:
@@ -601,9 +626,12 @@ class WindowRunner:
                                 slots[sl].copy_(f, non_blocking=True)
                             slot_of[key] = sl
                         fr.append(slots[sl])
-                    dev_wins.append(fr)
+                    if wi >= 0:
+                        dev_wins.append(fr)
                 if yuv is not None:
                     self._yuv_ingest(new_slots, yuv)
+                if det is not None:
+                    self._scene_sads(det, new_frames, slot_of)
                 ev_up = torch.cuda.Event()
                 ev_up.record(cl['h2d'])
             # ---- compute (pipelined windows) ---------------------------------------------------------------------
@@ -611,9 +639,22 @@ class WindowRunner:
             if ev_d2h[i] is not None:
                 cur.wait_event(ev_d2h[i])                     # the D2H of batch b-2 has read this output buffer
             if self.retime is not None:
-                plans = [R.window_plan(win[2], self.retime, yuv.with_s1(n + wi)) for wi, win in enumerate(wins)]
-                self._run_windows_rt(i, dev_wins, plans)
-                nf = self._yuv_egress_rt(i, plans, yuv, cur)
+                runs, outs = [], []                      # runs: (frames, instants, kinds kept); outs[w]: (run, kind, instant index)
+                for wi, win in enumerate(wins):
+                    k = win[2]                           # window k's unclamped tuple is (k+1, k+2, k, k+3)
+                    if det is None:
+                        ts, o = R.window_plan(k, self.retime, yuv.with_s1(n + wi))
+                        wr, o = [(dev_wins[wi], ts)], [(0, kind, j) for _, kind, j in o]
+                    else:
+                        sr, so = S.window_runs(k, self.retime, yuv.with_s1(n + wi), det.is_cut)
+                        wr = [([slots[slot_of[x]] for x in S.runner_order(tup)], ts) for tup, ts in sr]
+                        o = [(run, kind, j) for _, run, kind, j in so]
+                        self.cut_windows += len(sr) - 1
+                    outs.append([(len(runs) + run, kind, j) for run, kind, j in o])
+                    runs += [(fr, ts, {kind for run, kind, _ in o if run == ri}) for ri, (fr, ts) in enumerate(wr)]
+                self._run_windows_rt(i, runs)
+                nf = self._yuv_egress_rt(i, outs, yuv, cur)
+                dev_wins = [fr for fr, _, _ in runs]     # the frames the compute reads (slot_busy below)
             else:
                 self.run_windows_u8(dev_wins, out=cl['out'][i][:len(wins)], s01=cl['s01'][i][:len(wins)])
                 nf = self._yuv_egress(i, n, len(wins), yuv, cur) if yuv is not None else None
@@ -695,16 +736,17 @@ class WindowRunner:
             nf += 1
         return nf
 
-    def _run_windows_rt(self, i, dev_wins, plans):
-        """Retimed batch: window w of ``dev_wins`` runs the instants of plans[w] = ``retime.window_plan``; its frames go to
-        comb[i][w] = [S0, St x J, S1].  The t values and the uint8 sink records (one per (window, instant); S0 / S1 only in the
-        row of the window's first instant and only when that frame is an output) are uploaded on the current stream."""
+    def _run_windows_rt(self, i, runs):
+        """Retimed batch: run w = (4 frames, instants, kinds) runs its instants (``retime.window_plan``, or a run of a scene-cut
+        window); its frames go to comb[i][w] = [S0, St x J, S1].  The t values and the uint8 sink records (one per (run, instant);
+        S0 / S1 only in the row of the run's first instant and only when ``kinds`` holds that frame) are uploaded on the current
+        stream."""
         import numpy as np
         cl = self._clip
         comb, J = cl['comb'][i], cl['J']
-        nw, nJ = len(plans), cl['t'][i].shape[1]
+        nw, nJ = len(runs), cl['t'][i].shape[1]
         tt = np.empty((nw, nJ), np.float32)
-        for w, (ts, _) in enumerate(plans):
+        for w, (_, ts, _) in enumerate(runs):
             tt[w, :len(ts)] = ts
             tt[w, len(ts):] = ts[-1]                     # padded slots repeat the last t
         t_dev = cl['t'][i][:nw]
@@ -713,8 +755,7 @@ class WindowRunner:
         if self.engine.supports_u8_sink:
             a = np.zeros((nw, nJ, 32), np.int64)         # rows past a window's instants stay zero (disabled)
             base, (c0, c1) = comb.data_ptr(), comb.stride()[:2]      # uint8: element strides are bytes
-            for w, (ts, outs) in enumerate(plans):
-                kinds = {kind for _, kind, _ in outs}
+            for w, (_, ts, kinds) in enumerate(runs):
                 for j in range(len(ts)):
                     a[w, j, 2] = base + w * c0 + (1 + j) * c1                          # frame[2] = St
                     a[w, j, 8] = self.h | (self.w << 32)                                # int32 h, w
@@ -725,23 +766,23 @@ class WindowRunner:
                     a[w, 0, 1] = base + w * c0 + (J + 1) * c1                           # frame[1] = S1
             rows = cl['sinks'][i][:nw]
             rows.copy_(torch.from_numpy(a).pin_memory(), non_blocking=True)
-        io = [self._u8_io(fr, comb[w, 1:J + 1], comb[w, 0::J + 1], None if rows is None else rows[w]) for w, fr in enumerate(dev_wins)]
+        io = [self._u8_io(fr, comb[w, 1:J + 1], comb[w, 0::J + 1], None if rows is None else rows[w]) for w, (fr, _, _) in enumerate(runs)]
         cur = self._begin()
         for w, (load, emit, pre) in enumerate(io):
-            self._window(load, emit, body_only=True, pre=pre, t_dev=t_dev[w], nt=len(plans[w][0]))
+            self._window(load, emit, body_only=True, pre=pre, t_dev=t_dev[w], nt=len(runs[w][1]))
         self._end(cur)
 
-    def _yuv_egress_rt(self, i, plans, yuv, cur):
+    def _yuv_egress_rt(self, i, outs, yuv, cur):
         """Outputs of a retimed batch (comb[i]) -> yuv_out[i] in stream order: ONE gather launch on the compute stream.
-        Returns the number of payloads per window."""
+        outs[w]: window w's outputs as (run, kind, instant index).  Returns the number of payloads per window."""
         cl = self._clip
         comb, dst, J = cl['comb'][i], cl['yuv_out'][i], cl['J']
         c0, c1 = comb.stride()[:2]
         offs, counts = [], []
-        for w, (_, outs) in enumerate(plans):
-            for _, kind, j in outs:
-                offs.append(w * c0 + (0 if kind == R.S0 else J + 1 if kind == R.S1 else 1 + j) * c1)
-            counts.append(len(outs))
+        for o in outs:
+            for run, kind, j in o:
+                offs.append(run * c0 + (0 if kind == R.S0 else J + 1 if kind == R.S1 else 1 + j) * c1)
+            counts.append(len(o))
         nf = len(offs)
         if nf > dst.shape[0]:
             raise RuntimeError('retime: %d outputs for %d payload slots' % (nf, dst.shape[0]))
@@ -750,6 +791,34 @@ class WindowRunner:
         L.check(self.lib.demfi_bgr_to_yuv420_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), dst.shape[1], nf, self.h, self.w,
                                                     yuv.matrix, int(yuv.full_range), cur.cuda_stream), 'bgr_to_yuv420_gather')
         return counts
+
+    def _scene_sads(self, det, new_frames, slot_of):
+        """SAD_j of every frame j just uploaded against frame j-1 (``demfi_yuv420_sad``, ONE launch on the h2d stream after the
+        copies), read back with one event wait and handed to ``det`` in frame order.  Call under the h2d stream.
+        Frame j-1 is resident: it was uploaded in this batch or in the previous one (windows are consecutive), and a slot is
+        reused only after all nslot >= 2 * batch + 8 slots have been.  The wait does not wait on the compute stream: the
+        ``slot_busy`` waits queued on h2d before this batch's copies are on the compute of the batch that last read a reused
+        slot, and that batch is at least two back (batch b-1 reads frames k .. k + batch + 2 of its first window k, batch b
+        uploads frames up to k + 2 * batch + 2 only), so the host already waited for it when it drained that batch's D2H."""
+        cl = self._clip
+        P = cl['yuv_in'].shape[1]
+        js = sorted(j for j in new_frames if j >= det.next)
+        if not js:
+            return
+        if any(j - 1 not in slot_of for j in js):
+            raise RuntimeError('scene cuts: the predecessor of frame %d is not resident' % min(j for j in js if j - 1 not in slot_of))
+        m = len(js)
+        offs = [slot_of[j - 1] * P for j in js] + [slot_of[j] * P for j in js]
+        od = cl['sad_offs'][:2 * m]
+        od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
+        L.check(self.lib.demfi_yuv420_sad(cl['yuv_in'].data_ptr(), od.data_ptr(), od[m:].data_ptr(), m, P, cl['sad'].data_ptr(),
+                                          cl['h2d'].cuda_stream), 'yuv420_sad')
+        cl['h_sad'][:m].copy_(cl['sad'][:m], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(cl['h2d'])
+        ev.synchronize()
+        for j, sad in zip(js, cl['h_sad'][:m].tolist()):
+            det.push(j, sad)
 
     def __del__(self):
         try:

@@ -1,0 +1,149 @@
+"""Scene cuts of the Y4M video path (``python -m demfi_amd.video --scene-cut [T]``): where they are, and what a window next to one
+runs.  Pure Python; the one module that knows the policy.
+
+Input frames are numbered 0 .. n-1 and window k reads frames k .. k+3, interpolating between B0 = k+1 and B1 = k+2 (``retime``).
+p_j is the raw 4:2:0 payload of frame j (all Y, Cb, Cr bytes; P of them).  For j = 1 .. n-1
+  SAD_j   = sum |p_j - p_{j-1}| over the P bytes (an exact integer; the GPU computes it, ``sad_np`` defines it),
+  mafd_j  = 100 * SAD_j / (255 * P) in float64, mafd_0 = 0,
+  score_j = min(mafd_j, |mafd_j - mafd_{j-1}|),
+and a cut lies before frame j iff score_j >= T.  This has the shape of ffmpeg's ``scdet`` filter (the mean absolute frame
+difference and how much it changed), so T is picked the same way; numeric equality with it is not claimed.
+
+scene(i) = number of cuts before frames 1 .. i.  Window k is
+  * an inner window when scene(k+1) == scene(k+2): it runs its usual instants and outputs on the clamped tuple
+    B-1 = k if scene(k) == scene(k+1) else k+1,  B2 = k+3 if scene(k+3) == scene(k+2) else k+2
+    (a window that touches no cut runs exactly what it runs without cuts);
+  * a cut window when scene(k+1) != scene(k+2), b = k+1: nothing is interpolated.  Two runs at the single instant t = 1/2,
+    written (B-1, B0, B1, B2): left = (L, b, b, b) with L = b-1 if scene(b-1) == scene(b) else b, and right = (b+1, b+1, b+1, R)
+    with R = b+2 if scene(b+2) == scene(b+1) else b+1.  Of the window's own outputs (``retime.window_outputs``), S0 and every
+    St whose exact in-window fraction is below 1/2 are left's S0; every St at 1/2 or later, and S1 of the last window, are
+    right's S1 (nearest-frame hold).
+The output timing (header, frame count, the position of every frame) is that of the run without cuts.
+"""
+from fractions import Fraction
+
+import numpy as np
+
+from . import retime as R
+
+DEFAULT_THRESHOLD = 10.0
+HALF = Fraction(1, 2)
+
+
+def check_threshold(t):
+    """T as a float in (0, 100]; ValueError otherwise."""
+    t = float(t)
+    if not 0.0 < t <= 100.0:
+        raise ValueError('scene-cut threshold %r outside (0, 100]' % t)
+    return t
+
+
+def sad_np(a, b):
+    """SAD of two payloads (uint8 arrays of the same length): sum |a - b| as a Python int."""
+    a, b = np.asarray(a, np.uint8).reshape(-1), np.asarray(b, np.uint8).reshape(-1)
+    if a.shape != b.shape:
+        raise ValueError('sad_np: payloads of %d and %d bytes' % (a.size, b.size))
+    return int(np.abs(a.astype(np.int16) - b.astype(np.int16)).sum(dtype=np.int64))
+
+
+def mafd(sad, payload):
+    return 100.0 * int(sad) / (255 * int(payload))
+
+
+def scores(sads, payload):
+    """score_1 .. score_{n-1} from SAD_1 .. SAD_{n-1} of a whole stream."""
+    out, prev = [], 0.0
+    for s in sads:
+        m = mafd(s, payload)
+        out.append(min(m, abs(m - prev)))
+        prev = m
+    return out
+
+
+def cuts_of(sads, payload, threshold):
+    """Frame indices j that start a scene (a cut before j), from SAD_1 .. SAD_{n-1} of a whole stream."""
+    return [j for j, s in enumerate(scores(sads, payload), 1) if s >= threshold]
+
+
+class Detector:
+    """The cuts of a stream as its SADs arrive in frame order: ``push(j, SAD_j)`` for consecutive j.  ``first`` is the first frame
+    read: mafd_0 = 0 is known when it is 0; otherwise the first SAD pushed (SAD_{first+1}) only supplies mafd_{first+1}, and cuts
+    are decided from frame first + 2 on -- a rank whose block starts at window lo >= 1 reads from frame lo - 1, which decides every
+    cut its windows look at (j >= lo + 1) as one rank over the whole stream would."""
+
+    def __init__(self, payload, threshold, first=0):
+        self.payload, self.threshold = int(payload), check_threshold(threshold)
+        self.next = first + 1
+        self.prev = 0.0 if first == 0 else None
+        self.cuts = []
+        self._cut = set()
+
+    def push(self, j, sad):
+        if j != self.next:
+            raise RuntimeError('scene.Detector: SAD of frame %d pushed where frame %d was due' % (j, self.next))
+        m = mafd(sad, self.payload)
+        if self.prev is not None and min(m, abs(m - self.prev)) >= self.threshold:
+            self.cuts.append(j)
+            self._cut.add(j)
+        self.prev = m
+        self.next = j + 1
+
+    def is_cut(self, j):
+        """Is there a cut before frame j (j must have been pushed)?"""
+        if j >= self.next:
+            raise RuntimeError('scene.Detector: frame %d is not scored yet' % j)
+        return j in self._cut
+
+
+def first_frame(lo):
+    """First input frame a block of windows starting at window lo must read: lo - 1 when lo >= 1 (score_{lo+1} needs mafd_lo)."""
+    return max(lo - 1, 0)
+
+
+def _same(is_cut, i, j):
+    """scene(i) == scene(j) for i < j: no cut before any of the frames i+1 .. j."""
+    return not any(is_cut(x) for x in range(i + 1, j + 1))
+
+
+def is_cut_window(k, is_cut):
+    return is_cut(k + 2)
+
+
+def inner_tuple(k, is_cut):
+    """(B-1, B0, B1, B2) of inner window k, clamped at the cuts next to it."""
+    bm1 = k if _same(is_cut, k, k + 1) else k + 1
+    b2 = k + 3 if _same(is_cut, k + 2, k + 3) else k + 2
+    return (bm1, k + 1, k + 2, b2)
+
+
+def cut_runs(k, is_cut):
+    """(left, right) runs of cut window k, each (B-1, B0, B1, B2)."""
+    b = k + 1
+    left = (b - 1 if _same(is_cut, b - 1, b) else b, b, b, b)
+    right = (b + 1, b + 1, b + 1, b + 2 if _same(is_cut, b + 1, b + 2) else b + 1)
+    return left, right
+
+
+def window_runs(k, r, last, is_cut):
+    """What window k runs for ratio r (``--mfi M`` is r = M): (runs, outs).  runs = [((B-1, B0, B1, B2), instants)];
+    outs = [(output index, run, kind, instant index)] in stream order -- kind S0 / St / S1 of that run, as in
+    ``retime.window_plan``.  The outputs are those of ``retime.window_outputs(k, r, last)``."""
+    if not is_cut_window(k, is_cut):
+        ts, outs = R.window_plan(k, r, last)
+        return [(inner_tuple(k, is_cut), ts)], [(i, 0, kind, j) for i, kind, j in outs]
+    r = Fraction(r)
+    left, right = cut_runs(k, is_cut)
+    outs = []
+    for i, kind, _ in R.window_outputs(k, r, last):
+        # exact in-window fraction of output i: tau_i - (k+1) = i / r - k; S0 is 0, S1 is 1
+        if kind == R.S0 or (kind == R.ST and Fraction(i) / r - k < HALF):
+            outs.append((i, 0, R.S0, 0))
+        else:
+            outs.append((i, 1, R.S1, 0))
+    return [(left, [0.5]), (right, [0.5])], outs
+
+
+def runner_order(tup):
+    """(B-1, B0, B1, B2) -> the runner's (B0, B1, B-1, B2)."""
+    bm1, b0, b1, b2 = tup
+    return (b0, b1, bm1, b2)

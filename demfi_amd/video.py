@@ -26,28 +26,34 @@ import torch
 from . import _lib as L
 from . import dist as D
 from . import retime as R
+from . import scene as S
 from . import y4m
 from .clip import ClipRunner
 
 
 class YuvEdge:
-    """Y4M edge of ``WindowRunner.run_clip_u8``: conversion parameters of the stream (library codes) and ``with_s1(k)``: does
-    window k (index in the runner's window sequence) close the stream, i.e. is its S1 written?"""
+    """Y4M edge of ``WindowRunner.run_clip_u8``: conversion parameters of the stream (library codes), ``with_s1(k)``: does
+    window k (index in the runner's window sequence) close the stream, i.e. is its S1 written?  ``scene_cut``: None, or the
+    threshold T of scene-cut detection (``demfi_amd.scene``)."""
 
-    def __init__(self, matrix, full_range, siting, with_s1):
+    def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None):
         self.matrix = {'bt601': L.BT601, 'bt709': L.BT709}[matrix]
         self.full_range = bool(full_range)
         self.siting = {'420jpeg': L.SITING_420JPEG, '420mpeg2': L.SITING_420MPEG2}[siting]
         self.with_s1 = with_s1
+        self.scene_cut = scene_cut
 
 
 class VideoRunner:
     """x M interpolation (``mfi``, default 8) or retiming to the output frame rate ``fps`` (a Fraction >= the input's rate) of
     Y4M input on this rank's GPU; give one of the two.  ``matrix``: 'auto' (BT.709 when H >= 720, else BT.601), 'bt601'
-    or 'bt709'; the output uses the input's matrix and range, so an ffmpeg round trip keeps the colours.  After a run,
-    ``last_instants`` = (time instants run, padded per-t slots) and ``last_st_frames`` = St frames written, of this rank."""
+    or 'bt709'; the output uses the input's matrix and range, so an ffmpeg round trip keeps the colours.  ``scene_cut``: None
+    (default) or the threshold T in (0, 100] of scene-cut detection: no window interpolates across a cut (``demfi_amd.scene``);
+    the output's timing is unchanged.  After a run, ``last_instants`` = (time instants run, padded per-t slots),
+    ``last_st_frames`` = St frames written, ``last_cuts`` = the frames j that start a scene and ``last_cut_windows`` = the
+    windows run as cut windows, of this rank."""
 
-    def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, **runner_kw):
+    def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, **runner_kw):
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
         if mfi is not None and fps is not None:
@@ -60,16 +66,22 @@ class VideoRunner:
             raise ValueError('VideoRunner: fps must be > 0, got %s' % self.fps)
         mfi = 8 if mfi is None and fps is None else mfi
         self.model, self.n_tst, self.mfi, self.batch, self.matrix = model, n_tst, mfi, batch, matrix
+        self.scene_cut = S.check_threshold(scene_cut) if scene_cut is not None else None
         self.runner_kw = runner_kw
         self._runners = {}
         self.last_decode_peak = 0
         self.last_instants = (0, 0)
         self.last_st_frames = 0
         self.last_fps_out = None
+        self.last_cuts = []
+        self.last_cut_windows = 0
 
     def _ratio(self, hdr):
-        """None (x M) or the retime ratio F_out / F_in of this input."""
-        return None if self.fps is None else R.ratio(hdr.fps, self.fps)
+        """None (x M) or the retime ratio F_out / F_in of this input.  With scene cuts x M runs as r = M, whose bytes are
+        those of x M: the per-window plans of the retimed path carry the cut windows."""
+        if self.fps is None:
+            return Fraction(self.mfi) if self.scene_cut is not None else None
+        return R.ratio(hdr.fps, self.fps)
 
     def _out_header(self, hdr):
         ohdr = y4m.output_header(hdr, self.mfi) if self.fps is None else R.output_header(hdr, self.fps)
@@ -92,16 +104,19 @@ class VideoRunner:
     def _run(self, cr, hdr, lo, fn):
         """fn() runs windows lo, lo+1, ... of the input on cr; returns its window count and sets the per-run counters."""
         rn = cr.runner
-        i0, p0 = rn.instants_run, rn.instants_padded
+        i0, p0, c0 = rn.instants_run, rn.instants_padded, rn.cut_windows
         n = fn()
         self.last_instants = (rn.instants_run - i0, rn.instants_padded - p0)
+        self.last_cuts = list(rn.last_cuts) if self.scene_cut is not None else []
+        self.last_cut_windows = rn.cut_windows - c0
         r = self._ratio(hdr)
         self.last_st_frames = (n * (self.mfi - 1) if r is None else
                                sum(kind == R.ST for k in range(lo, lo + n) for _, kind, _ in R.window_outputs(k, r)))
         return n
 
     def _edge(self, hdr, with_s1):
-        return YuvEdge(y4m.auto_matrix(hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1)
+        return YuvEdge(y4m.auto_matrix(hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
+                       self.scene_cut)
 
     def run_stream(self, src, dst):
         """One rank, sequential binary streams (stdin / stdout work): nothing is seeked, the input is read in batches of
@@ -139,10 +154,12 @@ class VideoRunner:
             cr = self._clip_runner(hdr, world, rank)
             lo, wins = cr.my_windows(n_in)
             if not wins:
-                self.last_instants, self.last_st_frames = (0, 0), 0
+                self.last_instants, self.last_st_frames, self.last_cuts, self.last_cut_windows = (0, 0), 0, [], 0
                 return 0, 0
             n_windows = n_in - 3
-            frames = y4m.Frames.from_file(f, offs, lo, lo + len(wins) + 3, hdr.payload)
+            # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
+            first = S.first_frame(lo) if self.scene_cut is not None else lo
+            frames = y4m.Frames.from_file(f, offs, first, lo + len(wins) + 3, hdr.payload)
             r = self._ratio(hdr)
             at = (y4m.frame_offset(len(hb), y4m.output_index(lo, 0, self.mfi), hdr.payload) if r is None else
                   R.block_offset(len(hb), lo, r, hdr.payload))
@@ -158,6 +175,14 @@ def _is_regular(path):
     return path != '-' and (not os.path.exists(path) or os.path.isfile(path))
 
 
+def _scene_cut_arg(text):
+    try:
+        return S.check_threshold(text)
+    except ValueError as e:
+        import argparse
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def _fps_arg(text):
     try:
         return R.parse_fps(text)
@@ -166,13 +191,9 @@ def _fps_arg(text):
         raise argparse.ArgumentTypeError(str(e))
 
 
-def main(argv=None):
-    """``python -m demfi_amd.video IN OUT`` -- x M interpolation of a Y4M stream, or retiming to ``--fps``; ``-`` is stdin / stdout.
-    The first and the last input frame have no output (as in the reference's test_custom): n frames in, (n-3)*M + 1 out, at M
-    times the frame rate; with --fps, floor((n-3)*F_out/F_in) + 1 out at F_out."""
+def parser():
+    """The command line of ``main``."""
     import argparse
-    import json
-    import time
     ap = argparse.ArgumentParser(prog='python -m demfi_amd.video', description=main.__doc__.split('\n\n')[0],
                                  epilog='Input: 8-bit 4:2:0 progressive Y4M (C420jpeg, C420, C420mpeg2; XCOLORRANGE=FULL|LIMITED), '
                                         'e.g. ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe -.  Output: C420jpeg, the input\'s '
@@ -191,7 +212,20 @@ def main(argv=None):
     ap.add_argument('--matrix', default='auto', choices=['auto', 'bt601', 'bt709'],
                     help='YCbCr matrix of the input (and output); auto: BT.709 when H >= 720, else BT.601')
     ap.add_argument('--batch', type=int, default=4, help='windows per batch (the input frames held are bounded by it)')
-    a = ap.parse_args(argv)
+    ap.add_argument('--scene-cut', nargs='?', type=_scene_cut_arg, const=S.DEFAULT_THRESHOLD, default=None, metavar='T',
+                    help='detect scene cuts (score = min(mafd, |mafd - previous mafd|) of the 4:2:0 bytes, in percent; a cut where '
+                         'score >= T, T in (0, 100], default %g) and never interpolate across one: the frames next to a cut '
+                         'hold the nearest input frame.  Off unless given' % S.DEFAULT_THRESHOLD)
+    return ap
+
+
+def main(argv=None):
+    """``python -m demfi_amd.video IN OUT`` -- x M interpolation of a Y4M stream, or retiming to ``--fps``; ``-`` is stdin / stdout.
+    The first and the last input frame have no output (as in the reference's test_custom): n frames in, (n-3)*M + 1 out, at M
+    times the frame rate; with --fps, floor((n-3)*F_out/F_in) + 1 out at F_out."""
+    import json
+    import time
+    a = parser().parse_args(argv)
     if a.fps is None and a.mfi is None:
         a.mfi = 8
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
@@ -215,7 +249,7 @@ def main(argv=None):
         model.load_state_dict(load_checkpoint(a.checkpoint) if a.checkpoint else synthetic_state_dict(0))
     model = model.to(dev).eval()
     D.broadcast_state_dict(model, world, device=dev)
-    vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps)
+    vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut)
     t0 = time.perf_counter()
     if world > 1:
         nw, nf = vr.run_file(a.input, a.output, world, rank)
@@ -230,8 +264,9 @@ def main(argv=None):
                 src.close()
     torch.cuda.synchronize()
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
-    counts = [float(nw), float(nf), float(vr.last_st_frames), float(vr.last_instants[0]), float(vr.last_instants[1])]
-    tw, tf, tst, ti, tp = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
+    counts = [float(nw), float(nf), float(vr.last_st_frames), float(vr.last_instants[0]), float(vr.last_instants[1]),
+              float(vr.last_cut_windows)]
+    tw, tf, tst, ti, tp, tc = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
     if rank == 0:
         if tw == 0:
             print('demfi_amd.video: fewer than 4 input frames: no window, only the header was written', file=sys.stderr)
@@ -239,7 +274,7 @@ def main(argv=None):
                           'St_frames_per_s': round((tw * (a.mfi - 1) if a.fps is None else tst) / dt, 2) if dt > 0 else None,
                           'frames_per_s': round(tf / dt, 2) if dt > 0 else None,
                           'fps_out': str(vr.last_fps_out) if vr.last_fps_out is not None else None,
-                          'instants_run': int(ti), 'instants_padded': int(tp),
+                          'instants_run': int(ti), 'instants_padded': int(tp), 'cut_windows': int(tc),
                           'weights': os.path.basename(a.checkpoint) if a.checkpoint else 'synthetic_state_dict(0) (random init: no checkpoint given)',
                           'out': a.output}), file=sys.stderr)
     D.finalize()

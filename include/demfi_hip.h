@@ -359,13 +359,18 @@ int demfi_frame_to_u8(const float* frame, uint8_t* out, int h, int w, int H, int
  * land in stream order in one launch.
  * bgr_to_yuv420_gather: as bgr_to_yuv420, but frame i is read at base + src_offsets[i] (src_offsets: n int64 byte offsets in
  * DEVICE memory, any order, repeats allowed) and written at dst + i*dst_stride: the egress of a retimed stream, whose windows
- * give a varying number of frames. */
+ * give a varying number of frames.
+ * yuv420_sad: sad[i] = sum over the payload bytes of |a - b| for a at base + a_offsets[i], b at base + b_offsets[i] (n int64 byte
+ * offsets each, in DEVICE memory; any alignment, any order, repeats allowed), exact in uint64; payload = the frame's byte
+ * count (any length > 0).  sad is zeroed on the stream first.  Scores the scene cuts of demfi_amd/scene.py (sad_np). */
 int demfi_yuv420_to_bgr(const uint8_t* src, int64_t src_stride, uint8_t* dst, int64_t dst_stride, int n, int h, int w, int matrix,
                         int full_range, int siting, void* stream);
 int demfi_bgr_to_yuv420(const uint8_t* src, int64_t src_stride, int group, int64_t group_stride, uint8_t* dst, int64_t dst_stride,
                         int n, int h, int w, int matrix, int full_range, void* stream);
 int demfi_bgr_to_yuv420_gather(const uint8_t* base, const int64_t* src_offsets, uint8_t* dst, int64_t dst_stride, int n, int h, int w,
                                int matrix, int full_range, void* stream);
+int demfi_yuv420_sad(const uint8_t* base, const int64_t* a_offsets, const int64_t* b_offsets, int n, int64_t payload, uint64_t* sad,
+                     void* stream);
 
 /* ---- on-GPU evaluation ------------------------------------------------------------
  * psnr (utils.py:652-660) and MATLAB-style 11x11 Gaussian ssim (utils.py:663-705) of one predicted frame against its
