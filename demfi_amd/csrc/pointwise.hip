@@ -577,7 +577,7 @@ __global__ __launch_bounds__(WARP_ROWS * 64, 1) void warp_blend_fat_kernel(demfi
     };
     uint4 ra0[4], rb0[4], ra1[4], rb1[4];
     issue(0, ra0, rb0);
-    for (int it = 0; it < lpp; it += 2) {                         // lpp is 8 (fp16) or 16 (fp32): always even
+    for (int it = 0; it < lpp; it += 2) {                         // lpp = 1 (8 fp16 channels) runs a spare it = 1, whose pixels >= 64 finish() skips
         issue(it + 1, ra1, rb1);
         finish(it, ra0, rb0);
         if (it + 2 < lpp) issue(it + 2, ra0, rb0);
@@ -978,6 +978,8 @@ static int warp_blend_impl(const demfi_view* A, const float* fa, const demfi_vie
         int f32 = 0;
         const int sh = fat_lpp_shift(A, C, "demfi_warp_blend", &f32);
         if (sh < 0) return sh;
+        // phase 2 walks ppi = 64 >> lpp_shift pixels per iteration: a pixel of more than 64 lanes (1 KiB) would give ppi = 0
+        if (sh > 6) return demfi_set_error(DEMFI_ERR_ARG, "demfi_warp_blend: C=%d spans more than 64 x 16 bytes per pixel", C);
         // the kernel keeps the corner byte offsets of A / B as 32-bit ints (WarpRec): refuse images they cannot address
         const int64_t elt = f32 ? 4 : 2;
         if (((int64_t)(H - 1) * A->sy + (int64_t)(W - 1) * A->sx + C) * elt >= ((int64_t)1 << 31) ||

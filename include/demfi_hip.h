@@ -252,7 +252,8 @@ int demfi_cfr_flow_align(const float* flow01, const float* flow10, const float* 
 /* Eq.(2): two backward warps (bwarp, DeMFInet.py:732-766) blended with the occlusion map
  * (DeMFInet.py:66-71, 90-93, 146-149):
  *   o0 = sigmoid(logit); out = ((1-t) o0 bwarp(A,fa) + t (1-o0) bwarp(B,fb)) / ((1-t) o0 + t (1-o0)).
- * A, B, out: views with C channels (fat NHWC of the path dtype, or thin planar fp32); fa, fb: planar
+ * A, B, out: views with C channels (fat NHWC of the path dtype, or thin planar fp32); a fat view whose pixel is
+ * not a power-of-two number of 16-byte lanes, or more than 64 of them (1 KiB), is refused; fa, fb: planar
  * fp32 [2,H,W]; logit: planar fp32 [H,W]; t: device fp32.  occ_out (optional): sigmoid(logit) [H,W].
  * dbg_maps (optional): int32 [2 warps][3][H*W] = floor x index, floor y index, bit0-3 in-bounds of
  * (nw,ne,sw,se) | bit4 validity mask -- the integer maps of grid_sample for the index-parity tests. */
