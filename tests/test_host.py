@@ -392,6 +392,24 @@ def test_bench_dump_outputs_is_bounded_and_repeatable(tmp_path, monkeypatch):
         b.parse()
 
 
+def test_bench_side_figures_only_under_full(monkeypatch):
+    """A plain ``bench.py`` run measures the headline alone; the checks and side figures run with ``--full``, and ``--profile-ops``
+    (the per-launch table those figures measure) is refused without it."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(root, 'bench.py'))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '4', '--warmup', '1'])
+    assert b.parse().full is False
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--profile-ops', 'ops.txt'])
+    a = b.parse()
+    assert a.full and a.profile_ops == 'ops.txt'
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--profile-ops', 'ops.txt'])
+    with pytest.raises(SystemExit):
+        b.parse()
+
+
 def test_rank_affinity_slices_a_numa_node_between_its_ranks():
     """tools/run_node.sh: ranks whose GPUs share a NUMA node get disjoint slices of that node's cores, the node comes
     from the PCI address of HIP device LOCAL_RANK; without NUMA information the cores are split evenly by rank."""

@@ -10,7 +10,7 @@ for r in $(seq 1 "$rounds"); do
 i=0
 for v in "$@"; do
   tag=$(echo "r${r}v$i $v" | tr ' =/' '___')
-  env $v python bench.py --steps ${DEMFI_AB_STEPS:-6} --warmup 2 --no-cpu-baseline --profile-ops "$out/ops_$tag.txt" > "$out/bench_$tag.json" 2> "$out/err_$tag.txt"
+  env $v python bench.py --steps ${DEMFI_AB_STEPS:-6} --warmup 2 --full --no-cpu-baseline --profile-ops "$out/ops_$tag.txt" > "$out/bench_$tag.json" 2> "$out/err_$tag.txt"
   python - "$out/ops_$tag.txt" "$out/bench_$tag.json" "$v" <<'PY'
 import sys, json, collections
 ops, bench, tag = sys.argv[1:4]

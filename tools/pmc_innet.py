@@ -34,7 +34,7 @@ def main():
         d = os.path.join(outdir, 'innet', name)
         os.makedirs(d, exist_ok=True)
         cmd = ['rocprofv3', '--pmc'] + ctrs.split() + ['--kernel-trace', '--output-format', 'csv', '-d', d, '-o', 'r', '--', sys.executable,
-                                                        os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-verify']
+                                                        os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-verify']
         subprocess.run(cmd, cwd='/tmp', env=dict(os.environ, DEMFI_NTRUNK='1', TMPDIR='/tmp'), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=False)
         for f in glob.glob(d + '/**/*counter_collection.csv', recursive=True):
             for r in csv.DictReader(open(f)):

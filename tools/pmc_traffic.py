@@ -62,7 +62,7 @@ def run_bench_pmc(outdir):
         os.makedirs(d, exist_ok=True)
         cmd = ['rocprofv3', '--pmc'] + PASSES[tag].split() + ['--kernel-trace', '--output-format', 'csv', '-d', d, '-o', 'r', '--',
                                                                sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1',
-                                                               '--no-cpu-baseline']
+                                                               '--full', '--no-cpu-baseline']
         e = dict(os.environ, DEMFI_NCTX='1', DEMFI_NTRUNK='1')
         subprocess.run(cmd, cwd='/tmp', env=e, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=False)
         for f in glob.glob(d + '/**/*counter_collection.csv', recursive=True):
