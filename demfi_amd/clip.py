@@ -174,7 +174,16 @@ class ClipRunner:
         self.world, self.rank = world, rank
         self.ts = t_schedule(mfi) if retime is None else None
 
-    def my_windows(self, n_frames):
+    def my_windows(self, n_frames, full_length=False):
+        """(global index of this rank's first window, its (B0, B1, B-1, B2) tuples).  ``full_length``: the windows of the
+        full-length timeline of the Y4M path (``retime``), from -1 on, on their tuples clamped at the clip's ends."""
+        if full_length:
+            from . import retime as R
+            from . import scene as S
+            k0 = R.first_window(n_frames, True)
+            lo, hi = D.shard_windows(R.n_windows(n_frames, True), self.world, self.rank)
+            ends = S.with_sentinels(lambda j: False, n_frames)
+            return k0 + lo, [S.runner_order(S.clip_tuple(k, ends)) for k in range(k0 + lo, k0 + hi)]
         wins = window_list(n_frames)
         lo, hi = D.shard_windows(len(wins), self.world, self.rank)
         return lo, wins[lo:hi]

@@ -14,6 +14,14 @@ single instant t = 1/2 when it has none (its only output is S0 or S1).  S0 and S
 For r = M this is exactly the x M stream of ``y4m``: ``n_output_frames`` / ``output_index`` / ``output_header`` and the t
 values of ``harness.t_schedule(M)``.  Everything about window k follows from k and r alone, so a stream is scheduled as it
 arrives; whether a window is the last one is the reader's business (``y4m.Frames.is_last``).
+
+Full-length timeline (``full_length=True``, ``python -m demfi_amd.video --full-length``): the output covers the input's whole
+timeline.  Output frame i sits at tau_i = i / r, so output 0 is input frame 0, and N_out = ceil(n r) (n M for x M).  Windows
+are k = -1 .. n-3; window k interpolates between B0 = k+1 and B1 = k+2 and owns the outputs with tau in [k+1, k+2), i.e. the
+indices ceil((k+1) r) .. ceil((k+2) r) - 1.  Output i is S0 when tau_i = k+1, else St at t = float32((i q - (k+1) p) / p).
+The last window (k = n-3) also owns tau in [n-2, n): tau = n-1 is its S1 and every tau in (n-1, n) holds that S1.  A one-frame
+clip has the single window k = n-3 = -2 (tuple (0, 0, 0, 0), t = 1/2): it owns [0, 1), all of it the S1 hold.  The tuples are
+clamped at the clip's ends as if there were a scene cut before frame 0 and after frame n-1 (``scene.with_sentinels``).
 """
 import math
 import re
@@ -75,41 +83,62 @@ def float32_of(x):
     return v
 
 
-def n_output_frames(n_in, r):
-    """floor((n-3) r) + 1 for n >= 4 input frames, else 0."""
+def n_output_frames(n_in, r, full_length=False):
+    """floor((n-3) r) + 1 for n >= 4 input frames, else 0.  ``full_length``: ceil(n r) for n >= 1."""
+    if full_length:
+        return math.ceil(n_in * Fraction(r)) if n_in >= 1 else 0
     return math.floor((n_in - 3) * Fraction(r)) + 1 if n_in >= 4 else 0
 
 
-def first_output(k, r):
-    """Stream index of the first output frame owned by window k: ceil(k r)."""
+def first_window(n_in, full_length=False):
+    """Index of the first window of an n-frame clip: 0; ``full_length``: -1, or -2 = n-3 for a one-frame clip."""
+    return min(-1, n_in - 3) if full_length else 0
+
+
+def n_windows(n_in, full_length=False):
+    """Windows of an n-frame clip: n-3 (none below 4 frames); ``full_length``: n-1 for n >= 2, one for n = 1."""
+    if full_length:
+        return max(n_in - 1, 1) if n_in >= 1 else 0
+    return max(n_in - 3, 0)
+
+
+def first_output(k, r, full_length=False):
+    """Stream index of the first output frame owned by window k: ceil(k r); ``full_length``: ceil((k+1) r), 0 for k = -2."""
+    if full_length:
+        return max(math.ceil((k + 1) * Fraction(r)), 0)
     return math.ceil(k * Fraction(r))
 
 
-def window_outputs(k, r, last=False):
+def window_outputs(k, r, last=False, full_length=False):
     """[(output index i, kind, t)] of window k in stream order: kind S0 / St / S1, t the float32 value (a Python float) for St
-    and None for S0 / S1.  ``last``: window k is the clip's last one (its S1 is written when (k+1) r is an integer)."""
+    and None for S0 / S1.  ``last``: window k is the clip's last one (its S1 is written when (k+1) r is an integer; in
+    ``full_length`` mode it also owns tau in [k+2, k+3): S1 and its hold)."""
     r = Fraction(r)
     p, q = r.numerator, r.denominator
+    sh = 1 if full_length else 0                                   # full-length: tau_i is one input frame earlier
     out = []
-    for i in range(first_output(k, r), first_output(k + 1, r)):
-        num = i * q - k * p                                        # tau_i - (k+1) = num / p, 0 <= num < p
+    for i in range(first_output(k, r, full_length), first_output(k + 1, r, full_length)):
+        num = i * q - (k + sh) * p                                 # tau_i - (k+1) = num / p, 0 <= num < p
         out.append((i, S0, None) if num == 0 else (i, ST, float32_of(Fraction(num, p))))
-    if last and (k + 1) * r == first_output(k + 1, r):
+    if full_length:
+        if last:
+            out += [(i, S1, None) for i in range(first_output(k + 1, r, True), first_output(k + 2, r, True))]
+    elif last and (k + 1) * r == first_output(k + 1, r):
         out.append((first_output(k + 1, r), S1, None))
     return out
 
 
-def instants(k, r):
+def instants(k, r, full_length=False):
     """T_k: the float32 t values window k runs, in increasing order (t = 1/2 alone when it has no St output)."""
-    ts = sorted({t for _, kind, t in window_outputs(k, r) if kind == ST})
+    ts = sorted({t for _, kind, t in window_outputs(k, r, full_length=full_length) if kind == ST})
     return ts or [0.5]
 
 
-def window_plan(k, r, last=False):
+def window_plan(k, r, last=False, full_length=False):
     """(T_k, [(output index, kind, instant index)]): window k's instants and, per output in stream order, which instant's St
     it is (S0 / S1: instant 0, the window's first)."""
-    outs = window_outputs(k, r, last)
-    ts = instants(k, r)
+    outs = window_outputs(k, r, last, full_length)
+    ts = instants(k, r, full_length)
     pos = {t: j for j, t in enumerate(ts)}
     return ts, [(i, kind, pos[t] if kind == ST else 0) for i, kind, t in outs]
 
@@ -125,9 +154,9 @@ def output_header(hdr, fps_out):
     return y4m.Header(hdr.w, hdr.h, Fraction(fps_out), 'p', hdr.aspect, '420jpeg', hdr.color_range, (), '420jpeg')
 
 
-def block_offset(hdr_len, first_window, r, payload):
+def block_offset(hdr_len, first_window, r, payload, full_length=False):
     """Byte offset in the output file of the first frame of the block of windows starting at ``first_window``."""
-    return y4m.frame_offset(hdr_len, first_output(first_window, r), payload)
+    return y4m.frame_offset(hdr_len, first_output(first_window, r, full_length), payload)
 
 
 SCAN_WINDOWS = 1000

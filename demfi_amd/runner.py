@@ -492,7 +492,7 @@ class WindowRunner:
         return out, s01
 
     # ---------------------------------------------------------------------------------------------------------
-    def run_clip_u8(self, host_frames, windows, sink=None, batch=4, reuse_frames=True, yuv=None):
+    def run_clip_u8(self, host_frames, windows, sink=None, batch=4, reuse_frames=True, yuv=None, window_index=None):
         """Host-to-host run of a list of windows: the counterpart of the test_custom loop (/root/reference/main.py:
         1121-1178) between cv2.imread and cv2.imwrite.
 
@@ -510,10 +510,12 @@ class WindowRunner:
         ``demfi_bgr_to_yuv420`` launch puts its frames in stream order (per window S0, then St for t = 1/M .. (M-1)/M; plus
         S1 when ``with_s1(k)`` says window k is the clip's last) into a device buffer that is copied to pinned memory, and
         sink(k, payloads) gets uint8 [M or M+1, payload] per window.
-        With ``retime`` (constructor) the Y4M edge follows ``retime.window_plan`` instead: window k (its global index is B-1 of
-        its 4-tuple) runs its own instants, its frames sit in [S0, St x ceil(r), S1] slots, and ONE
-        ``demfi_bgr_to_yuv420_gather`` launch per batch puts its outputs in stream order; sink(k, payloads) gets as many
-        payloads as window k owns.
+        With ``retime`` (constructor) the Y4M edge follows ``retime.window_plan`` instead: window k (its global index is
+        ``window_index(j)`` for the j-th window of ``windows`` when given, else B-1 of its 4-tuple) runs its own instants, its
+        frames sit in [S0, St x ceil(r), S1] slots, and ONE ``demfi_bgr_to_yuv420_gather`` launch per batch puts its outputs in
+        stream order; sink(k, payloads) gets as many payloads as window k owns.
+        ``yuv.full_length`` (retimed runners only, with ``window_index``): the full-length timeline of ``retime``; ``windows``
+        are then the tuples clamped at the clip's ends, and the last window's S1 hold repeats its S1 slot in the gather.
         ``yuv.scene_cut`` = T (retimed runners only; ``--mfi M`` is r = M): scene cuts (``demfi_amd.scene``).  ``windows`` must
         then be the consecutive unclamped tuples, and host_frames must also hold frame k0 - 1 when the first window k0 >= 1.
         Each batch's new payloads are scored by ONE ``demfi_yuv420_sad`` launch on the h2d stream, read back with one event wait,
@@ -526,11 +528,14 @@ class WindowRunner:
             return 0
         M1 = self.mfi - 1
         threshold = getattr(yuv, 'scene_cut', None)
-        mode = 'bgr' if yuv is None else 'yuv' if threshold is None else 'yuv+cuts'
+        full = bool(getattr(yuv, 'full_length', False))
+        mode = ('bgr' if yuv is None else 'yuv' if threshold is None else 'yuv+cuts') + ('+full' if full else '')
         if self.retime is not None and yuv is None:
             raise ValueError('WindowRunner.run_clip_u8: a retimed runner needs the Y4M edge (yuv=...)')
         if threshold is not None and (self.retime is None or not reuse_frames):
             raise ValueError('WindowRunner.run_clip_u8: scene cuts need a retimed runner (r = M for x M) and reuse_frames')
+        if full and (self.retime is None or window_index is None):
+            raise ValueError('WindowRunner.run_clip_u8: the full-length timeline needs a retimed runner and window_index')
         runs_max = 2 * batch if threshold is not None else batch        # a cut window is two runs
         if getattr(self, '_clip', None) is None or self._clip['batch'] != batch or self._clip['mode'] != mode:
             self._clip = None
@@ -550,14 +555,16 @@ class WindowRunner:
                 J = R.max_instants(self.retime)
                 nJ = -(-J // self.n_ctx) * self.n_ctx if self.tb else J      # instants incl. the padding of a short chunk
                 nsl = cl['slots'].shape[0]
+                # payloads of a batch: at most J per window, plus the last window's S1 (full-length: its [n-2, n) span, 2 J)
+                nout = (batch + 1) * J if full else batch * J + 1
                 comb = [torch.empty((runs_max, J + 2, self.h, self.w, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
                 cl.update({
                     'J': J, 'comb': comb, 'yuv_in': torch.empty((nsl, P), dtype=torch.uint8, device=dev),
                     't': [torch.empty((runs_max, nJ), dtype=torch.float32, device=dev) for _ in range(2)],
                     'sinks': [torch.empty((runs_max, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)],
-                    'offs': [torch.empty(batch * J + 1, dtype=torch.int64, device=dev) for _ in range(2)],
-                    'yuv_out': [torch.empty((batch * J + 1, P), dtype=torch.uint8, device=dev) for _ in range(2)],
-                    'h_yuv': [torch.empty((batch * J + 1, P), dtype=torch.uint8).pin_memory() for _ in range(2)],
+                    'offs': [torch.empty(nout, dtype=torch.int64, device=dev) for _ in range(2)],
+                    'yuv_out': [torch.empty((nout, P), dtype=torch.uint8, device=dev) for _ in range(2)],
+                    'h_yuv': [torch.empty((nout, P), dtype=torch.uint8).pin_memory() for _ in range(2)],
                 })
                 if threshold is not None:                # SADs of a batch's new frames (at most nsl) against their predecessors
                     cl.update({'sad': torch.empty(nsl, dtype=torch.int64, device=dev),
@@ -588,7 +595,8 @@ class WindowRunner:
         b = 0
         det = None
         if threshold is not None:
-            det = S.Detector(cl['yuv_in'].shape[1], threshold, first=S.first_frame(wins[0][2]))
+            det = S.Detector(cl['yuv_in'].shape[1], threshold,
+                             first=S.first_frame(window_index(0) if window_index is not None else wins[0][2]))
             self.last_cuts = det.cuts
         while wins:
             i = b & 1
@@ -641,12 +649,15 @@ class WindowRunner:
             if self.retime is not None:
                 runs, outs = [], []                      # runs: (frames, instants, kinds kept); outs[w]: (run, kind, instant index)
                 for wi, win in enumerate(wins):
-                    k = win[2]                           # window k's unclamped tuple is (k+1, k+2, k, k+3)
+                    # window k's unclamped tuple is (k+1, k+2, k, k+3); clamped tuples come with their index
+                    k = window_index(n + wi) if window_index is not None else win[2]
+                    last = yuv.with_s1(n + wi)
                     if det is None:
-                        ts, o = R.window_plan(k, self.retime, yuv.with_s1(n + wi))
+                        ts, o = R.window_plan(k, self.retime, last, full)
                         wr, o = [(dev_wins[wi], ts)], [(0, kind, j) for _, kind, j in o]
                     else:
-                        sr, so = S.window_runs(k, self.retime, yuv.with_s1(n + wi), det.is_cut)
+                        is_cut = S.with_sentinels(det.is_cut, k + 3 if last else None) if full else det.is_cut
+                        sr, so = S.window_runs(k, self.retime, last, is_cut, full)
                         wr = [([slots[slot_of[x]] for x in S.runner_order(tup)], ts) for tup, ts in sr]
                         o = [(run, kind, j) for _, run, kind, j in so]
                         self.cut_windows += len(sr) - 1

@@ -19,6 +19,11 @@ scene(i) = number of cuts before frames 1 .. i.  Window k is
     St whose exact in-window fraction is below 1/2 are left's S0; every St at 1/2 or later, and S1 of the last window, are
     right's S1 (nearest-frame hold).
 The output timing (header, frame count, the position of every frame) is that of the run without cuts.
+
+On the full-length timeline (``retime``, ``full_length``) the clip's ends are cuts by another name: ``with_sentinels`` adds a
+cut before frame 0 and one before frame n (frames -1 and n are scenes of their own), so the rules above clamp window -1 to
+B-1 = 0 and the last window to B2 = n-1, and a real cut before frame 1 or n-1 makes window -1 or n-3 a cut window.  The one
+window of a one-frame clip (k = -2) runs (0, 0, 0, 0).
 """
 from fractions import Fraction
 
@@ -96,8 +101,21 @@ class Detector:
 
 
 def first_frame(lo):
-    """First input frame a block of windows starting at window lo must read: lo - 1 when lo >= 1 (score_{lo+1} needs mafd_lo)."""
+    """First input frame a block of windows starting at window lo must read: lo - 1 when lo >= 1 (score_{lo+1} needs mafd_lo),
+    else frame 0 (full-length blocks start at window -1, or -2 for a one-frame clip)."""
     return max(lo - 1, 0)
+
+
+def with_sentinels(is_cut, n=None):
+    """``is_cut`` with the clip's ends as cuts (full-length timeline): a cut before frame 0 and, when the clip's length n is
+    known, before frame n.  A reader that does not know n yet has read past every frame it asks about."""
+    return lambda j: j <= 0 or (n is not None and j >= n) or is_cut(j)
+
+
+def clip_tuple(k, is_cut):
+    """(B-1, B0, B1, B2) of window k of the full-length timeline that is not a cut window under ``is_cut`` (with sentinels):
+    its inner tuple, or (0, 0, 0, 0) for the one window (k = -2) of a one-frame clip."""
+    return (0, 0, 0, 0) if k < -1 else inner_tuple(k, is_cut)
 
 
 def _same(is_cut, i, j):
@@ -124,19 +142,21 @@ def cut_runs(k, is_cut):
     return left, right
 
 
-def window_runs(k, r, last, is_cut):
+def window_runs(k, r, last, is_cut, full_length=False):
     """What window k runs for ratio r (``--mfi M`` is r = M): (runs, outs).  runs = [((B-1, B0, B1, B2), instants)];
     outs = [(output index, run, kind, instant index)] in stream order -- kind S0 / St / S1 of that run, as in
-    ``retime.window_plan``.  The outputs are those of ``retime.window_outputs(k, r, last)``."""
-    if not is_cut_window(k, is_cut):
-        ts, outs = R.window_plan(k, r, last)
-        return [(inner_tuple(k, is_cut), ts)], [(i, 0, kind, j) for i, kind, j in outs]
+    ``retime.window_plan``.  The outputs are those of ``retime.window_outputs(k, r, last, full_length)``; on the full-length
+    timeline ``is_cut`` must hold the sentinels (``with_sentinels``)."""
+    if k < -1 or not is_cut_window(k, is_cut):
+        ts, outs = R.window_plan(k, r, last, full_length)
+        return [(clip_tuple(k, is_cut), ts)], [(i, 0, kind, j) for i, kind, j in outs]
     r = Fraction(r)
     left, right = cut_runs(k, is_cut)
+    sh = 1 if full_length else 0
     outs = []
-    for i, kind, _ in R.window_outputs(k, r, last):
-        # exact in-window fraction of output i: tau_i - (k+1) = i / r - k; S0 is 0, S1 is 1
-        if kind == R.S0 or (kind == R.ST and Fraction(i) / r - k < HALF):
+    for i, kind, _ in R.window_outputs(k, r, last, full_length):
+        # exact in-window fraction of output i: tau_i - (k+1) = i / r - k (- 1 full-length); S0 is 0, S1 is 1
+        if kind == R.S0 or (kind == R.ST and Fraction(i) / r - k - sh < HALF):
             outs.append((i, 0, R.S0, 0))
         else:
             outs.append((i, 1, R.S1, 0))

@@ -8,7 +8,10 @@ The frames are those of the folder path (``python -m demfi_amd.clip``) for the s
 then St for t = 1/M .. (M-1)/M; after the last window its S1.  n input frames give (n-3)*M + 1 output frames: the first and
 the last input frame have no output of their own, as in the reference.  ``--fps F_out`` (an exact fraction, F_out >= F_in) puts
 output frame i at input time 1 + i * F_in / F_out instead and runs only the time instants those frames need
-(``demfi_amd.retime``); ``--fps M*F_in`` gives the bytes of ``--mfi M``.
+(``demfi_amd.retime``); ``--fps M*F_in`` gives the bytes of ``--mfi M``.  ``--full-length`` covers the input's whole timeline
+instead: output frame i sits at input time i * F_in / F_out, so n frames give n*M (ceil(n * F_out / F_in)) output frames that
+stay aligned with the input's audio; the clip's ends clamp the windows next to them like scene cuts and the last input frame
+is held to the end.
 
 The colour conversion runs on the GPU next to the uint8 ingest / sink (csrc/yuv.hip, defined by ``y4m.yuv420_to_bgr_np`` /
 ``y4m.bgr_to_yuv420_np``): 4:2:0 payloads go host -> HBM (half the bytes of BGR), are converted once per frame into the
@@ -34,14 +37,15 @@ from .clip import ClipRunner
 class YuvEdge:
     """Y4M edge of ``WindowRunner.run_clip_u8``: conversion parameters of the stream (library codes), ``with_s1(k)``: does
     window k (index in the runner's window sequence) close the stream, i.e. is its S1 written?  ``scene_cut``: None, or the
-    threshold T of scene-cut detection (``demfi_amd.scene``)."""
+    threshold T of scene-cut detection (``demfi_amd.scene``).  ``full_length``: the full-length timeline (``retime``)."""
 
-    def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None):
+    def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False):
         self.matrix = {'bt601': L.BT601, 'bt709': L.BT709}[matrix]
         self.full_range = bool(full_range)
         self.siting = {'420jpeg': L.SITING_420JPEG, '420mpeg2': L.SITING_420MPEG2}[siting]
         self.with_s1 = with_s1
         self.scene_cut = scene_cut
+        self.full_length = full_length
 
 
 class VideoRunner:
@@ -49,11 +53,13 @@ class VideoRunner:
     Y4M input on this rank's GPU; give one of the two.  ``matrix``: 'auto' (BT.709 when H >= 720, else BT.601), 'bt601'
     or 'bt709'; the output uses the input's matrix and range, so an ffmpeg round trip keeps the colours.  ``scene_cut``: None
     (default) or the threshold T in (0, 100] of scene-cut detection: no window interpolates across a cut (``demfi_amd.scene``);
-    the output's timing is unchanged.  After a run, ``last_instants`` = (time instants run, padded per-t slots),
-    ``last_st_frames`` = St frames written, ``last_cuts`` = the frames j that start a scene and ``last_cut_windows`` = the
-    windows run as cut windows, of this rank."""
+    the output's timing is unchanged.  ``full_length``: the output covers the input's whole timeline (``retime``): output
+    frame 0 is input frame 0, n frames give ceil(n r) (n M for x M), the clip's ends clamp the tuples like cuts and the last
+    frame is held to the end; it runs on the retimed path.  After a run, ``last_instants`` = (time instants run, padded per-t
+    slots), ``last_st_frames`` = St frames written, ``last_cuts`` = the frames j that start a scene and ``last_cut_windows`` =
+    the windows run as cut windows, of this rank."""
 
-    def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, **runner_kw):
+    def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, **runner_kw):
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
         if mfi is not None and fps is not None:
@@ -67,6 +73,7 @@ class VideoRunner:
         mfi = 8 if mfi is None and fps is None else mfi
         self.model, self.n_tst, self.mfi, self.batch, self.matrix = model, n_tst, mfi, batch, matrix
         self.scene_cut = S.check_threshold(scene_cut) if scene_cut is not None else None
+        self.full_length = bool(full_length)
         self.runner_kw = runner_kw
         self._runners = {}
         self.last_decode_peak = 0
@@ -77,10 +84,10 @@ class VideoRunner:
         self.last_cut_windows = 0
 
     def _ratio(self, hdr):
-        """None (x M) or the retime ratio F_out / F_in of this input.  With scene cuts x M runs as r = M, whose bytes are
-        those of x M: the per-window plans of the retimed path carry the cut windows."""
+        """None (x M) or the retime ratio F_out / F_in of this input.  With scene cuts or full length x M runs as r = M, whose
+        bytes are those of x M: the per-window plans of the retimed path carry the cut windows and the clip's ends."""
         if self.fps is None:
-            return Fraction(self.mfi) if self.scene_cut is not None else None
+            return Fraction(self.mfi) if self.scene_cut is not None or self.full_length else None
         return R.ratio(hdr.fps, self.fps)
 
     def _out_header(self, hdr):
@@ -89,7 +96,9 @@ class VideoRunner:
         return ohdr
 
     def _n_out(self, n_in, hdr):
-        return y4m.n_output_frames(n_in, self.mfi) if self.fps is None else R.n_output_frames(n_in, self._ratio(hdr))
+        if self.fps is None and not self.full_length:
+            return y4m.n_output_frames(n_in, self.mfi)
+        return R.n_output_frames(n_in, self._ratio(hdr), self.full_length)
 
     def _clip_runner(self, hdr, world, rank):
         r = self._ratio(hdr)
@@ -101,22 +110,25 @@ class VideoRunner:
                                                  rank=rank, **kw)
         return cr
 
-    def _run(self, cr, hdr, lo, fn):
-        """fn() runs windows lo, lo+1, ... of the input on cr; returns its window count and sets the per-run counters."""
+    def _run(self, cr, hdr, first, fn):
+        """fn() runs windows lo, lo+1, ... of the input on cr, lo = first() once it has run; returns its window count and sets
+        the per-run counters."""
         rn = cr.runner
         i0, p0, c0 = rn.instants_run, rn.instants_padded, rn.cut_windows
         n = fn()
+        lo = first()
         self.last_instants = (rn.instants_run - i0, rn.instants_padded - p0)
         self.last_cuts = list(rn.last_cuts) if self.scene_cut is not None else []
         self.last_cut_windows = rn.cut_windows - c0
         r = self._ratio(hdr)
         self.last_st_frames = (n * (self.mfi - 1) if r is None else
-                               sum(kind == R.ST for k in range(lo, lo + n) for _, kind, _ in R.window_outputs(k, r)))
+                               sum(kind == R.ST for k in range(lo, lo + n)
+                                   for _, kind, _ in R.window_outputs(k, r, full_length=self.full_length)))
         return n
 
     def _edge(self, hdr, with_s1):
         return YuvEdge(y4m.auto_matrix(hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
-                       self.scene_cut)
+                       self.scene_cut, self.full_length)
 
     def run_stream(self, src, dst):
         """One rank, sequential binary streams (stdin / stdout work): nothing is seeked, the input is read in batches of
@@ -125,13 +137,19 @@ class VideoRunner:
         hdr = rd.header
         cr = self._clip_runner(hdr, 1, 0)
         wr = y4m.Writer(dst, self._out_header(hdr))
-        frames = y4m.Frames(rd)
+        frames = y4m.Frames(rd, full_length=self.full_length)
 
         def sink(k, payloads):
             wr.write(payloads)
             dst.flush()
-        n = self._run(cr, hdr, 0, lambda: cr.runner.run_clip_u8(frames, frames.windows(), sink, batch=self.batch,
-                                                                  yuv=self._edge(hdr, frames.is_last)))
+        if self.full_length:                             # window j of the sequence is window first_window + j
+            def index(j):
+                return frames.first_window + j
+            edge, kw = self._edge(hdr, lambda j: frames.is_last(index(j))), {'window_index': index}
+        else:
+            edge, kw = self._edge(hdr, frames.is_last), {}
+        n = self._run(cr, hdr, lambda: frames.first_window or 0,
+                      lambda: cr.runner.run_clip_u8(frames, frames.windows(), sink, batch=self.batch, yuv=edge, **kw))
         dst.flush()
         self.last_decode_peak = frames.peak
         return n, wr.frames
@@ -152,21 +170,23 @@ class VideoRunner:
                     o.truncate(y4m.frame_offset(len(hb), total, hdr.payload))
             D.barrier()
             cr = self._clip_runner(hdr, world, rank)
-            lo, wins = cr.my_windows(n_in)
+            full = self.full_length
+            lo, wins = cr.my_windows(n_in, full)
             if not wins:
                 self.last_instants, self.last_st_frames, self.last_cuts, self.last_cut_windows = (0, 0), 0, [], 0
                 return 0, 0
-            n_windows = n_in - 3
+            last = R.first_window(n_in, full) + R.n_windows(n_in, full) - 1
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
-            first = S.first_frame(lo) if self.scene_cut is not None else lo
+            first = S.first_frame(lo) if self.scene_cut is not None else max(lo, 0)
             frames = y4m.Frames.from_file(f, offs, first, lo + len(wins) + 3, hdr.payload)
             r = self._ratio(hdr)
             at = (y4m.frame_offset(len(hb), y4m.output_index(lo, 0, self.mfi), hdr.payload) if r is None else
-                  R.block_offset(len(hb), lo, r, hdr.payload))
+                  R.block_offset(len(hb), lo, r, hdr.payload, full))
+            kw = {'window_index': lambda j: lo + j} if full else {}
             with open(out_path, 'r+b') as o:
                 wr = y4m.Writer(o, ohdr, at=at)
-                n = self._run(cr, hdr, lo, lambda: cr.runner.run_clip_u8(frames, wins, lambda k, p: wr.write(p), batch=self.batch,
-                                                                         yuv=self._edge(hdr, lambda k: lo + k == n_windows - 1)))
+                n = self._run(cr, hdr, lambda: lo, lambda: cr.runner.run_clip_u8(frames, wins, lambda k, p: wr.write(p), batch=self.batch,
+                                                                                 yuv=self._edge(hdr, lambda k: lo + k == last), **kw))
             self.last_decode_peak = frames.peak
             return n, wr.frames
 
@@ -198,7 +218,8 @@ def parser():
                                  epilog='Input: 8-bit 4:2:0 progressive Y4M (C420jpeg, C420, C420mpeg2; XCOLORRANGE=FULL|LIMITED), '
                                         'e.g. ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe -.  Output: C420jpeg, the input\'s '
                                         'matrix and range.  n input frames give (n-3)*M + 1 output frames: the first and the last '
-                                        'input frame have no output, as in the reference.  All logging goes to stderr.')
+                                        'input frame have no output, as in the reference (--full-length: n*M frames from input '
+                                        'frame 0 on).  All logging goes to stderr.')
     ap.add_argument('input', help="Y4M file, or - for stdin")
     ap.add_argument('output', help="Y4M file, or - for stdout")
     rate = ap.add_mutually_exclusive_group()
@@ -216,13 +237,18 @@ def parser():
                     help='detect scene cuts (score = min(mafd, |mafd - previous mafd|) of the 4:2:0 bytes, in percent; a cut where '
                          'score >= T, T in (0, 100], default %g) and never interpolate across one: the frames next to a cut '
                          'hold the nearest input frame.  Off unless given' % S.DEFAULT_THRESHOLD)
+    ap.add_argument('--full-length', action='store_true',
+                    help='cover the input\'s whole timeline: output frame 0 is input frame 0 and n input frames give ceil(n*F_out/F_in) '
+                         'output frames (n*M with --mfi), the last input frame held to the end, so the video stays aligned with its '
+                         'audio.  Off by default (the reference\'s timeline)')
     return ap
 
 
 def main(argv=None):
     """``python -m demfi_amd.video IN OUT`` -- x M interpolation of a Y4M stream, or retiming to ``--fps``; ``-`` is stdin / stdout.
     The first and the last input frame have no output (as in the reference's test_custom): n frames in, (n-3)*M + 1 out, at M
-    times the frame rate; with --fps, floor((n-3)*F_out/F_in) + 1 out at F_out."""
+    times the frame rate; with --fps, floor((n-3)*F_out/F_in) + 1 out at F_out.  --full-length: n*M (ceil(n*F_out/F_in)) out,
+    output frame 0 at input frame 0."""
     import json
     import time
     a = parser().parse_args(argv)
@@ -249,7 +275,7 @@ def main(argv=None):
         model.load_state_dict(load_checkpoint(a.checkpoint) if a.checkpoint else synthetic_state_dict(0))
     model = model.to(dev).eval()
     D.broadcast_state_dict(model, world, device=dev)
-    vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut)
+    vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut, full_length=a.full_length)
     t0 = time.perf_counter()
     if world > 1:
         nw, nf = vr.run_file(a.input, a.output, world, rank)
@@ -269,9 +295,11 @@ def main(argv=None):
     tw, tf, tst, ti, tp, tc = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
     if rank == 0:
         if tw == 0:
-            print('demfi_amd.video: fewer than 4 input frames: no window, only the header was written', file=sys.stderr)
+            print('demfi_amd.video: %s: no window, only the header was written' %
+                  ('no input frame' if a.full_length else 'fewer than 4 input frames'), file=sys.stderr)
+        st = tw * (a.mfi - 1) if a.fps is None and not a.full_length else tst
         print(json.dumps({'windows': int(tw), 'frames_written': int(tf), 'seconds': round(dt, 2), 'ranks': world,
-                          'St_frames_per_s': round((tw * (a.mfi - 1) if a.fps is None else tst) / dt, 2) if dt > 0 else None,
+                          'St_frames_per_s': round(st / dt, 2) if dt > 0 else None,
                           'frames_per_s': round(tf / dt, 2) if dt > 0 else None,
                           'fps_out': str(vr.last_fps_out) if vr.last_fps_out is not None else None,
                           'instants_run': int(ti), 'instants_padded': int(tp), 'cut_windows': int(tc),

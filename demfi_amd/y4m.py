@@ -13,6 +13,10 @@ and Cr planes [ceil(h/2), ceil(w/2)], 1.5 bytes per pixel.
   * downsampling (output is always 420jpeg) is a 2x2 box over the full-resolution Q16 Cb / Cr, rounded once; at an odd
     edge the clamped neighbour repeats the pixel that exists, i.e. the 2 or 1 pixels there are averaged.
 Frames are uint8 [h,w,3] in B, G, R order, the frame order of the whole pipeline (cv2's).
+
+Two timelines: by default n input frames give (n-3)*M + 1 output frames and the first and last input frames have no output
+(``n_output_frames``); on the full-length timeline (``Frames(full_length=True)``, ``retime``) output frame 0 is input frame 0
+and n frames give n*M, windows running from k = -1 on tuples clamped at the clip's ends.
 """
 import io
 import math
@@ -343,16 +347,19 @@ class Frames:
     the input's length.
 
     Frames(reader): the frames of a stream, read in order (stdin: nothing is seeked).
-    Frames.from_file(f, offsets, first, stop): frames first .. stop-1 of a scanned file (``scan``), by seek + readinto."""
+    Frames.from_file(f, offsets, first, stop): frames first .. stop-1 of a scanned file (``scan``), by seek + readinto.
+    ``full_length``: ``windows`` / ``is_last`` follow the full-length timeline (``retime``)."""
 
-    def __init__(self, reader=None, payload=None, fetch=None, first=0, stop=None, pinned=None):
+    def __init__(self, reader=None, payload=None, fetch=None, first=0, stop=None, pinned=None, full_length=False):
         import torch
         self.payload = reader.header.payload if reader is not None else payload
         self._fetch = fetch or (lambda i, buf: reader.read_into(buf))
         self.next, self.stop = first, stop
         self.pinned = torch.cuda.is_available() if pinned is None else pinned
+        self.full_length = full_length
         self.buf = {}
         self.n = None                                   # index one past the last frame, once the end was seen
+        self.first_window = None                        # global index of the first window handed out by ``windows``
         self.peak = 0
 
     @classmethod
@@ -389,15 +396,30 @@ class Frames:
 
     def windows(self, first=0):
         """(B0, B1, B-1, B2) of window k = first, first+1, ... while the input has frame k+3; frame k+4 is read ahead, so
-        ``is_last(k)`` is known when window k is handed out."""
-        k = first
-        while self.has(k + 3):
-            self.has(k + 4)
-            yield (k + 1, k + 2, k, k + 3)
+        ``is_last(k)`` is known when window k is handed out.
+        ``full_length``: window k = -1, 0, ... while the input has frame k+2, on its tuple clamped at the clip's ends
+        (``scene.clip_tuple``); frame k+3 is read ahead, and its absence makes window k the last.  A one-frame input has the
+        single window -2 on frame 0.  ``first_window`` is set before the first window is handed out."""
+        if not self.full_length:
+            self.first_window = k = first
+            while self.has(k + 3):
+                self.has(k + 4)
+                yield (k + 1, k + 2, k, k + 3)
+                k += 1
+            return
+        from . import scene as S
+        if not self.has(0):
+            return
+        self.first_window = k = -1 if self.has(1) else -2
+        while k == -2 or self.has(k + 2):
+            self.has(k + 3)
+            yield S.runner_order(S.clip_tuple(k, S.with_sentinels(lambda j: False, self.n)))
+            if k == -2:
+                return
             k += 1
 
     def is_last(self, k):
-        return self.n is not None and self.n == k + 4
+        return self.n is not None and self.n == k + (3 if self.full_length else 4)
 
 
 class Writer:
