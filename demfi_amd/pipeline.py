@@ -1,0 +1,336 @@
+"""Host-to-host clip pipeline behind ``WindowRunner.run_clip_u8``: a ring of device frame slots (``FrameSlots``), one edge object
+per output format (``BgrEdge``: BGR frames in and out; ``Y4mEdge``: 4:2:0 payloads in and out, every window on its own plan)
+and the double-buffered batch loop that drives them (``ClipPipeline``).  An edge has the same few methods whatever its format:
+``upload`` one frame into a slot and ``uploaded`` after a batch's copies (h2d stream), ``run`` a batch (compute stream), ``d2h``
+its outputs to pinned memory (d2h stream) and ``drain`` them to the sink; what ``run`` returns is handed back to ``d2h`` / ``drain``."""
+import ctypes as C
+import itertools
+import weakref
+from fractions import Fraction
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import retime as R
+from . import scene as S
+from .y4m import payload_size
+
+# int64 word positions in a demfi_u8_sink record (256 bytes: the context's "sink" buffer)
+_FRAME, _HW, _ITER = L.U8Sink.frame.offset // 8, L.U8Sink.h.offset // 8, L.U8Sink.iter.offset // 8
+assert (L.U8Sink.h.offset, L.U8Sink.w.offset, L.U8Sink.iter.offset) == (8 * _HW, 8 * _HW + 4, 8 * _ITER) and C.sizeof(L.U8Sink) <= 256
+
+
+def fill_sink_records(a, st, s0, s1, h, w, n_tst):
+    """demfi_u8_sink records into the int64 array a [..., 32]: segments 0 / 1 / 2 of the last layer = S0 / S1 / St are written to
+    the device pointers s0 / s1 / st (int64 arrays that broadcast to a.shape[:-1]; 0 = not written).  A record without St
+    stays all zero: disabled, its time instant writes nothing."""
+    live = np.broadcast_to(st, a.shape[:-1]) != 0
+    a[...] = 0
+    a[..., _FRAME], a[..., _FRAME + 1], a[..., _FRAME + 2] = s0, s1, st
+    a[..., _HW] = np.where(live, h | (w << 32), 0)           # int32 h, w
+    a[..., _ITER] = np.where(live, n_tst - 1, 0)              # int32 iter, pad
+    return a
+
+
+class FrameSlots:
+    """Device ring of input frame slots ``frames`` [n,h,w,3] uint8.  ``slot_of``: frame key -> slot; ``busy[s]``: event of the
+    compute of the batch that last read slot s."""
+
+    def __init__(self, n, h, w, dev):
+        self.frames = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+        self.reset()
+
+    def reset(self):
+        self.slot_of, self.key_of, self.busy, self.next = {}, [None] * len(self.frames), [None] * len(self.frames), 0
+
+    def acquire(self, key, stream):
+        """(slot of frame ``key``, must it be uploaded).  A new frame takes the ring's next slot: the frame held there is
+        forgotten, and ``stream`` (the one that uploads) waits for the compute that last read it."""
+        sl = self.slot_of.get(key)
+        if sl is not None:
+            return sl, False
+        sl = self.next
+        self.next = (sl + 1) % len(self.busy)
+        if self.key_of[sl] is not None:
+            del self.slot_of[self.key_of[sl]]
+        if self.busy[sl] is not None:
+            stream.wait_event(self.busy[sl])
+        self.slot_of[key], self.key_of[sl] = sl, key
+        return sl, True
+
+    def mark_busy(self, read, ev):
+        """The slots a batch read (lists of slots) stay busy until ``ev``."""
+        for fr in read:
+            for sl in fr:
+                self.busy[sl] = ev
+
+
+class BgrEdge:
+    """uint8 BGR [h,w,3] frames in; sink(k, St [M-1,h,w,3], S0S1 [2,h,w,3]) out (views of pinned staging buffers)."""
+
+    def __init__(self, runner, batch, slots):
+        self.rn, self.slots = runner, slots
+        dev, shape = runner.engine.device, (runner.h, runner.w, 3)
+        self.out = [torch.empty((batch, runner.mfi - 1) + shape, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.s01 = [torch.empty((batch, 2) + shape, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.h_out = [torch.empty((batch, runner.mfi - 1) + shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.h_s01 = [torch.empty((batch, 2) + shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+
+    def begin(self, yuv, window_index, first_win):
+        return ()
+
+    def upload(self, sl, idx, f):
+        if tuple(f.shape) != (self.rn.h, self.rn.w, 3) or f.dtype != torch.uint8:
+            raise ValueError('frame %d: expected uint8 [%d,%d,3], got %s %s' % (idx, self.rn.h, self.rn.w, f.dtype, tuple(f.shape)))
+        self.slots.frames[sl].copy_(f, non_blocking=True)
+
+    def uploaded(self, new, h2d):
+        pass
+
+    def run(self, i, n, wins, frames, cur):
+        cnt = len(wins)
+        self.rn.run_windows_u8([[self.slots.frames[sl] for sl in fr] for fr in frames], out=self.out[i][:cnt], s01=self.s01[i][:cnt])
+        return cnt, frames
+
+    def d2h(self, i, cnt):
+        self.h_out[i][:cnt].copy_(self.out[i][:cnt], non_blocking=True)
+        self.h_s01[i][:cnt].copy_(self.s01[i][:cnt], non_blocking=True)
+
+    def drain(self, i, k0, cnt, sink):
+        for j in range(cnt):
+            sink(k0 + j, self.h_out[i][j], self.h_s01[i][j])
+
+
+class Y4mEdge:
+    """4:2:0 payloads in; sink(k, payloads [c, P]) out, the c output frames window k owns in stream order.  Window k runs the
+    instants of ``retime.window_plan`` for the runner's ratio (x M is r = M), with ``cuts`` those of ``scene.window_runs`` (a
+    cut window is two runs); run w of a batch writes its frames to comb[i][w] = [S0, St x J, S1], J = ceil(r), and one gather
+    launch per batch puts the outputs in stream order.  ``full``: the full-length timeline of ``retime``."""
+
+    def __init__(self, runner, batch, slots, cuts, full):
+        self.rn, self.slots, self.cuts, self.full = runner, slots, cuts, full
+        self.r = runner.retime if runner.retime is not None else Fraction(runner.mfi)
+        dev, h, w, nsl = runner.engine.device, runner.h, runner.w, len(slots.frames)
+        P, J = self.P, self.J = payload_size(h, w), R.max_instants(self.r)
+        nJ = -(-J // runner.n_ctx) * runner.n_ctx if runner.tb else J    # instants incl. the padding of a short chunk
+        runs_max = 2 * batch if cuts else batch                          # a cut window is two runs
+        # payloads of a batch: at most J per window, plus the last window's S1 (full-length: its [n-2, n) span, 2 J)
+        nout = (batch + 1) * J if full else batch * J + 1
+        self.yuv_in = torch.empty((nsl, P), dtype=torch.uint8, device=dev)
+        self.comb = [torch.empty((runs_max, J + 2, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.t = [torch.empty((runs_max, nJ), dtype=torch.float32, device=dev) for _ in range(2)]
+        self.sinks = [torch.empty((runs_max, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)]
+        self.offs = [torch.empty(nout, dtype=torch.int64, device=dev) for _ in range(2)]
+        self.yuv_out = [torch.empty((nout, P), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.h_yuv = [torch.empty((nout, P), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        if cuts:                                     # SADs of a batch's new frames (at most nsl) against their predecessors
+            self.sad = torch.empty(nsl, dtype=torch.int64, device=dev)
+            self.sad_offs = torch.empty(2 * nsl, dtype=torch.int64, device=dev)
+            self.h_sad = torch.empty(nsl, dtype=torch.int64).pin_memory()
+        self.yuv = self.window_index = self.det = None
+
+    def begin(self, yuv, window_index, first_win):
+        """A run starts; returns the frames to make resident before its first batch.  Scene cuts: the block's first window
+        k0 >= 1 also needs frame k0 - 1, the predecessor SAD_k0 is taken against."""
+        self.yuv, self.window_index, self.det = yuv, window_index, None
+        if not self.cuts:
+            return ()
+        det = self.det = S.Detector(self.P, yuv.scene_cut, first=S.first_frame(window_index(0) if window_index is not None else first_win[2]))
+        self.rn.last_cuts = det.cuts
+        return (det.next - 1,) if det.next - 1 < first_win[2] else ()
+
+    def upload(self, sl, idx, f):
+        if tuple(f.shape) != (self.P,) or f.dtype != torch.uint8:
+            raise ValueError('frame %d: expected a uint8 [%d] 4:2:0 payload, got %s %s' % (idx, self.P, f.dtype, tuple(f.shape)))
+        self.yuv_in[sl].copy_(f, non_blocking=True)
+
+    def uploaded(self, new, h2d):
+        """Payloads copied to yuv_in[slot] -> BGR frame slots, one launch per run of consecutive slots; then the SADs."""
+        rn, yuv, sls = self.rn, self.yuv, [sl for _, sl in new]
+        r = 0
+        while r < len(sls):
+            e = r + 1
+            while e < len(sls) and sls[e] == sls[e - 1] + 1:
+                e += 1
+            L.check(rn.lib.demfi_yuv420_to_bgr(self.yuv_in[sls[r]].data_ptr(), self.P, self.slots.frames[sls[r]].data_ptr(), rn.h * rn.w * 3,
+                                               e - r, rn.h, rn.w, yuv.matrix, int(yuv.full_range), yuv.siting, h2d.cuda_stream), 'yuv420_to_bgr')
+            r = e
+        if self.det is not None:
+            self._scene_sads([idx for idx, _ in new], h2d)
+
+    def _scene_sads(self, new_frames, h2d):
+        """SAD_j of every frame j just uploaded against frame j-1 (``demfi_yuv420_sad``, ONE launch on the h2d stream after the
+        copies), read back with one event wait and handed to the detector in frame order.  Call under the h2d stream.
+        Frame j-1 is resident: it was uploaded in this batch or in the previous one (windows are consecutive), and a slot is
+        reused only after all nslot >= 2 * batch + 8 slots have been.  The wait does not wait on the compute stream: the
+        ``busy`` waits queued on h2d before this batch's copies are on the compute of the batch that last read a reused
+        slot, and that batch is at least two back (batch b-1 reads frames k .. k + batch + 2 of its first window k, batch b
+        uploads frames up to k + 2 * batch + 2 only), so the host already waited for it when it drained that batch's D2H."""
+        det, slot_of, P = self.det, self.slots.slot_of, self.P
+        js = sorted(j for j in new_frames if j >= det.next)
+        if not js:
+            return
+        if any(j - 1 not in slot_of for j in js):
+            raise RuntimeError('scene cuts: the predecessor of frame %d is not resident' % min(j for j in js if j - 1 not in slot_of))
+        m = len(js)
+        offs = [slot_of[j - 1] * P for j in js] + [slot_of[j] * P for j in js]
+        od = self.sad_offs[:2 * m]
+        od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
+        L.check(self.rn.lib.demfi_yuv420_sad(self.yuv_in.data_ptr(), od.data_ptr(), od[m:].data_ptr(), m, P, self.sad.data_ptr(),
+                                             h2d.cuda_stream), 'yuv420_sad')
+        self.h_sad[:m].copy_(self.sad[:m], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(h2d)
+        ev.synchronize()
+        for j, sad in zip(js, self.h_sad[:m].tolist()):
+            det.push(j, sad)
+
+    def run(self, i, n, wins, frames, cur):
+        """Plans the batch's windows (window n + wi of the sequence is window ``window_index(n + wi)``, else B-1 of its unclamped
+        tuple), runs them and gathers their outputs into yuv_out[i].  Returns (payloads per window, slots read)."""
+        rn, yuv, det, slot_of = self.rn, self.yuv, self.det, self.slots.slot_of
+        runs, outs = [], []                          # runs: (slots, instants, kinds kept); outs[w]: (run, kind, instant index)
+        for wi, win in enumerate(wins):
+            k = self.window_index(n + wi) if self.window_index is not None else win[2]
+            last = yuv.with_s1(n + wi)
+            if det is None:
+                ts, o = R.window_plan(k, self.r, last, self.full)
+                wr, o = [(frames[wi], ts)], [(0, kind, j) for _, kind, j in o]
+            else:
+                is_cut = S.with_sentinels(det.is_cut, k + 3 if last else None) if self.full else det.is_cut
+                sr, so = S.window_runs(k, self.r, last, is_cut, self.full)
+                wr = [([slot_of[x] for x in S.runner_order(tup)], ts) for tup, ts in sr]
+                o = [(run, kind, j) for _, run, kind, j in so]
+                rn.cut_windows += len(sr) - 1
+            outs.append([(len(runs) + run, kind, j) for run, kind, j in o])
+            runs += [(fr, ts, {kind for run, kind, _ in o if run == ri}) for ri, (fr, ts) in enumerate(wr)]
+        self._run_windows(i, runs)
+        return self._gather(i, outs, cur), [fr for fr, _, _ in runs]
+
+    def _run_windows(self, i, runs):
+        """Run w = (4 slots, instants, kinds) runs its instants into comb[i][w].  The t values (padded slots repeat the last t)
+        and the uint8 sink records (one per (run, instant); S0 / S1 only in the row of the run's first instant and only when
+        ``kinds`` holds that frame; rows past a run's instants disabled) are uploaded on the current stream."""
+        rn, comb, J = self.rn, self.comb[i], self.J
+        nw, nJ = len(runs), self.t[i].shape[1]
+        tt = np.empty((nw, nJ), np.float32)
+        st = np.zeros((nw, nJ), np.int64)
+        s01 = np.zeros((2, nw, nJ), np.int64)
+        base, (c0, c1) = comb.data_ptr(), comb.stride()[:2]              # uint8: element strides are bytes
+        for w, (_, ts, kinds) in enumerate(runs):
+            tt[w, :len(ts)] = ts
+            tt[w, len(ts):] = ts[-1]
+            st[w, :len(ts)] = base + w * c0 + c1 * np.arange(1, len(ts) + 1)
+            s01[0, w, 0] = base + w * c0 if R.S0 in kinds else 0
+            s01[1, w, 0] = base + w * c0 + (J + 1) * c1 if R.S1 in kinds else 0
+        t_dev = self.t[i][:nw]
+        t_dev.copy_(torch.from_numpy(tt).pin_memory(), non_blocking=True)
+        rows = None
+        if rn.engine.supports_u8_sink:
+            a = fill_sink_records(np.empty((nw, nJ, 32), np.int64), st, s01[0], s01[1], rn.h, rn.w, rn.n_tst)
+            rows = self.sinks[i][:nw]
+            rows.copy_(torch.from_numpy(a).pin_memory(), non_blocking=True)
+        io = [rn._u8_io([self.slots.frames[sl] for sl in fr], comb[w, 1:J + 1], comb[w, 0::J + 1], None if rows is None else rows[w])
+              for w, (fr, _, _) in enumerate(runs)]
+        cur = rn._begin()
+        for w, (load, emit, pre) in enumerate(io):
+            rn._window(load, emit, body_only=True, pre=pre, t_dev=t_dev[w], nt=len(runs[w][1]))
+        rn._end(cur)
+
+    def _gather(self, i, outs, cur):
+        """Outputs of a batch (comb[i]) -> yuv_out[i] in stream order: ONE gather launch on the compute stream.  outs[w]:
+        window w's outputs as (run, kind, instant index).  Returns the number of payloads per window."""
+        rn, yuv, comb, dst, J = self.rn, self.yuv, self.comb[i], self.yuv_out[i], self.J
+        c0, c1 = comb.stride()[:2]
+        offs = [run * c0 + (0 if kind == R.S0 else J + 1 if kind == R.S1 else 1 + j) * c1 for o in outs for run, kind, j in o]
+        nf = len(offs)
+        if nf > dst.shape[0]:
+            raise RuntimeError('retime: %d outputs for %d payload slots' % (nf, dst.shape[0]))
+        od = self.offs[i][:nf]
+        od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
+        L.check(rn.lib.demfi_bgr_to_yuv420_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), dst.shape[1], nf, rn.h, rn.w,
+                                                  yuv.matrix, int(yuv.full_range), cur.cuda_stream), 'bgr_to_yuv420_gather')
+        return [len(o) for o in outs]
+
+    def d2h(self, i, counts):
+        nf = sum(counts)
+        self.h_yuv[i][:nf].copy_(self.yuv_out[i][:nf], non_blocking=True)
+
+    def drain(self, i, k0, counts, sink):
+        pos = 0
+        for j, c in enumerate(counts):
+            sink(k0 + j, self.h_yuv[i][pos:pos + c])
+            pos += c
+
+
+class ClipPipeline:
+    """The batch loop of ``WindowRunner.run_clip_u8`` for one batch size and one edge (BGR, or Y4M with or without scene
+    cuts / the full-length timeline, which size its buffers): H2D of a batch's new frames, its compute, the drain of the
+    previous batch and its D2H, on three streams over two sets of output buffers."""
+
+    def __init__(self, runner, batch, y4m, cuts, full):
+        dev = self.dev = runner.engine.device
+        runner = weakref.proxy(runner)               # the runner owns this pipeline: no reference cycle keeps its buffers alive
+        self.batch, self.key = batch, (batch, y4m, cuts, full)          # what a cached pipeline can be reused for
+        self.h2d, self.d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+        self.slots = FrameSlots(max(2 * batch + 8, 8 * batch), runner.h, runner.w, dev)
+        self.edge = Y4mEdge(runner, batch, self.slots, cuts, full) if y4m else BgrEdge(runner, batch, self.slots)
+
+    def run(self, host_frames, windows, sink, reuse_frames, yuv, window_index):
+        it = iter(windows)
+        wins = list(itertools.islice(it, self.batch))
+        if not wins:
+            return 0
+        edge, slots, h2d, cur = self.edge, self.slots, self.h2d, torch.cuda.current_stream(self.dev)
+        slots.reset()
+        extra = edge.begin(yuv, window_index, wins[0])
+        ev_d2h = [None, None]             # D2H of the batch that last wrote output buffer i
+        pending = None                    # (buffer, first window, what edge.run returned) of the batch whose D2H is in flight
+        n = b = 0
+        while wins:
+            i = b & 1
+            # ---- H2D of the frames this batch needs (copy stream) -------------------------------------------------
+            new = []                      # (frame, slot) uploaded for this batch
+
+            def resident(idx, key):
+                sl, fresh = slots.acquire(key, h2d)
+                if fresh:
+                    edge.upload(sl, idx, host_frames[idx])
+                    new.append((idx, sl))
+                return sl
+            with torch.cuda.stream(h2d):
+                for idx in extra:
+                    resident(idx, idx)
+                frames = [[resident(idx, idx if reuse_frames else (b, wi, idx)) for idx in win] for wi, win in enumerate(wins)]
+                edge.uploaded(new, h2d)
+                ev_up = torch.cuda.Event()
+                ev_up.record(h2d)
+            # ---- compute (pipelined windows) ---------------------------------------------------------------------
+            cur.wait_event(ev_up)
+            if ev_d2h[i] is not None:
+                cur.wait_event(ev_d2h[i])                     # the D2H of batch b-2 has read this output buffer
+            res, read = edge.run(i, n, wins, frames, cur)
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            slots.mark_busy(read, ev)
+            # ---- hand the previous batch to the sink while this one computes ------------------------------------------
+            if pending is not None:
+                self._drain(pending, ev_d2h, sink)
+            # ---- D2H of this batch (copy stream), into pinned staging ------------------------------------------------
+            with torch.cuda.stream(self.d2h):
+                self.d2h.wait_event(ev)
+                edge.d2h(i, res)
+                ev_d2h[i] = torch.cuda.Event()
+                ev_d2h[i].record(self.d2h)
+            pending = (i, n, res)
+            n, b, extra = n + len(wins), b + 1, ()
+            wins = list(itertools.islice(it, self.batch))
+        self._drain(pending, ev_d2h, sink)
+        return n
+
+    def _drain(self, pending, ev_d2h, sink):
+        i, k0, res = pending
+        ev_d2h[i].synchronize()
+        if sink is not None:
+            self.edge.drain(i, k0, res, sink)

@@ -15,8 +15,9 @@ is held to the end.
 
 The colour conversion runs on the GPU next to the uint8 ingest / sink (csrc/yuv.hip, defined by ``y4m.yuv420_to_bgr_np`` /
 ``y4m.bgr_to_yuv420_np``): 4:2:0 payloads go host -> HBM (half the bytes of BGR), are converted once per frame into the
-runner's BGR frame slots, and every computed batch is converted back into a stream-order device buffer in one launch
-(``WindowRunner.run_clip_u8(yuv=...)``).  One rank reads a stream (stdin included) in bounded batches and writes each batch
+runner's BGR frame slots, and every computed batch is gathered back into a stream-order device buffer in one launch
+(``WindowRunner.run_clip_u8(yuv=...)``).  There is one path for all rates: every window runs the plan ``demfi_amd.retime`` gives
+it for r = F_out / F_in, and ``--mfi M`` is r = M.  One rank reads a stream (stdin included) in bounded batches and writes each batch
 as it drains; under ``torch.distributed.run`` every rank takes ``dist.shard_windows``' block of a regular file and writes its
 frames at their byte offsets of the output file (no collective on the data path).
 """
@@ -55,7 +56,7 @@ class VideoRunner:
     (default) or the threshold T in (0, 100] of scene-cut detection: no window interpolates across a cut (``demfi_amd.scene``);
     the output's timing is unchanged.  ``full_length``: the output covers the input's whole timeline (``retime``): output
     frame 0 is input frame 0, n frames give ceil(n r) (n M for x M), the clip's ends clamp the tuples like cuts and the last
-    frame is held to the end; it runs on the retimed path.  After a run, ``last_instants`` = (time instants run, padded per-t
+    frame is held to the end.  After a run, ``last_instants`` = (time instants run, padded per-t
     slots), ``last_st_frames`` = St frames written, ``last_cuts`` = the frames j that start a scene and ``last_cut_windows`` =
     the windows run as cut windows, of this rank."""
 
@@ -84,20 +85,15 @@ class VideoRunner:
         self.last_cut_windows = 0
 
     def _ratio(self, hdr):
-        """None (x M) or the retime ratio F_out / F_in of this input.  With scene cuts or full length x M runs as r = M, whose
-        bytes are those of x M: the per-window plans of the retimed path carry the cut windows and the clip's ends."""
-        if self.fps is None:
-            return Fraction(self.mfi) if self.scene_cut is not None or self.full_length else None
-        return R.ratio(hdr.fps, self.fps)
+        """The ratio r = F_out / F_in of this input: M for x M, whose per-window plans (``retime``) give exactly the x M stream."""
+        return Fraction(self.mfi) if self.mfi is not None else R.ratio(hdr.fps, self.fps)
 
     def _out_header(self, hdr):
-        ohdr = y4m.output_header(hdr, self.mfi) if self.fps is None else R.output_header(hdr, self.fps)
+        ohdr = R.output_header(hdr, hdr.fps * self._ratio(hdr))
         self.last_fps_out = ohdr.fps
         return ohdr
 
     def _n_out(self, n_in, hdr):
-        if self.fps is None and not self.full_length:
-            return y4m.n_output_frames(n_in, self.mfi)
         return R.n_output_frames(n_in, self._ratio(hdr), self.full_length)
 
     def _clip_runner(self, hdr, world, rank):
@@ -105,9 +101,8 @@ class VideoRunner:
         key = (hdr.h, hdr.w, world, rank, r)
         cr = self._runners.get(key)
         if cr is None:
-            kw = dict(self.runner_kw, retime=r) if r is not None else self.runner_kw
             cr = self._runners[key] = ClipRunner(self.model, hdr.h, hdr.w, self.n_tst, self.mfi or 8, batch=self.batch, world=world,
-                                                 rank=rank, **kw)
+                                                 rank=rank, **dict(self.runner_kw, retime=r))
         return cr
 
     def _run(self, cr, hdr, first, fn):
@@ -121,9 +116,7 @@ class VideoRunner:
         self.last_cuts = list(rn.last_cuts) if self.scene_cut is not None else []
         self.last_cut_windows = rn.cut_windows - c0
         r = self._ratio(hdr)
-        self.last_st_frames = (n * (self.mfi - 1) if r is None else
-                               sum(kind == R.ST for k in range(lo, lo + n)
-                                   for _, kind, _ in R.window_outputs(k, r, full_length=self.full_length)))
+        self.last_st_frames = sum(kind == R.ST for k in range(lo, lo + n) for _, kind, _ in R.window_outputs(k, r, full_length=self.full_length))
         return n
 
     def _edge(self, hdr, with_s1):
@@ -179,9 +172,7 @@ class VideoRunner:
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
             first = S.first_frame(lo) if self.scene_cut is not None else max(lo, 0)
             frames = y4m.Frames.from_file(f, offs, first, lo + len(wins) + 3, hdr.payload)
-            r = self._ratio(hdr)
-            at = (y4m.frame_offset(len(hb), y4m.output_index(lo, 0, self.mfi), hdr.payload) if r is None else
-                  R.block_offset(len(hb), lo, r, hdr.payload, full))
+            at = R.block_offset(len(hb), lo, self._ratio(hdr), hdr.payload, full)
             kw = {'window_index': lambda j: lo + j} if full else {}
             with open(out_path, 'r+b') as o:
                 wr = y4m.Writer(o, ohdr, at=at)
@@ -297,9 +288,8 @@ def main(argv=None):
         if tw == 0:
             print('demfi_amd.video: %s: no window, only the header was written' %
                   ('no input frame' if a.full_length else 'fewer than 4 input frames'), file=sys.stderr)
-        st = tw * (a.mfi - 1) if a.fps is None and not a.full_length else tst
         print(json.dumps({'windows': int(tw), 'frames_written': int(tf), 'seconds': round(dt, 2), 'ranks': world,
-                          'St_frames_per_s': round(st / dt, 2) if dt > 0 else None,
+                          'St_frames_per_s': round(tst / dt, 2) if dt > 0 else None,
                           'frames_per_s': round(tf / dt, 2) if dt > 0 else None,
                           'fps_out': str(vr.last_fps_out) if vr.last_fps_out is not None else None,
                           'instants_run': int(ti), 'instants_padded': int(tp), 'cut_windows': int(tc),

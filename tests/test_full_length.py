@@ -210,7 +210,7 @@ def test_video_runner_full_length_counts():
     vr = video.VideoRunner(None, 1, fps=Fraction(60), full_length=True)
     assert vr._n_out(9, hdr) == 23 and vr._n_out(0, hdr) == 0
     dflt = video.VideoRunner(None, 1, 4)
-    assert not dflt.full_length and dflt._ratio(hdr) is None and dflt._n_out(9, hdr) == 25
+    assert not dflt.full_length and dflt._ratio(hdr) == 4 and dflt._n_out(9, hdr) == 25      # x M is r = M on every path
 
 
 @pytest.mark.parametrize('argv', [['--mfi', '4'], ['--fps', '60000/1001'], ['--scene-cut'], ['--fps', '60', '--scene-cut', '20'], []])

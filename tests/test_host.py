@@ -4,6 +4,7 @@ import ctypes as C
 import os
 import re
 import sys
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -556,3 +557,85 @@ def test_workspace_arena_shrinks_the_workspace_and_changes_no_result():
     assert on['ws_small'] < 0.7 * off['ws_small']
     assert on['ws_720p'] <= 45e9 < 80e9 < off['ws_720p']
     assert on['ws_1080p'] <= 144e9 * 0.5 < off['ws_1080p']
+
+
+# ---- WindowRunner's configuration rule (runner.choose_config): pure, so it is pinned without a device -------------------------
+def _config(h, w, n_tst, mfi, dtype=L.F16, n_ctx=None, n_trunk=None, retime=None, env=None, cached=None, final_only=False,
+            workspace_bytes=None, total_memory=288 * 10 ** 9, free_memory=None, auto=False):
+    from demfi_amd.runner import choose_config
+    return choose_config((h + 31) // 32 * 32, (w + 31) // 32 * 32, n_tst, mfi, dtype, True, n_ctx, n_trunk, auto, retime, env=env or {},
+                         cached=cached, total_memory=total_memory, free_memory=free_memory, final_only=final_only,
+                         workspace_bytes=workspace_bytes or L.load().demfi_workspace_bytes)
+
+
+def test_choose_config_fixed_defaults():
+    """The configurations bench.py measures, on a 288 GB part: three trunk sets while their workspace is below half of it."""
+    ws = L.load().demfi_workspace_bytes
+    assert 0 < ws(736, 1280, 3, L.F16, 3, 7) <= 144 * 10 ** 9 and 0 < ws(1088, 1920, 3, L.F16, 3, 5) <= 144 * 10 ** 9
+    assert _config(720, 1280, 3, 8) == {'n_ctx': 7, 'n_trunk': 3, 'batched': True, 'final_only': False, 'chosen_by': 'fixed default'}
+    assert _config(1080, 1920, 3, 16) == {'n_ctx': 5, 'n_trunk': 3, 'batched': True, 'final_only': False, 'chosen_by': 'fixed default'}
+    # 720p fp32 N_tst=5: 7 / 3, as WindowRunner(model32, 720, 1280, n_tst=5, mfi=8).config reads on an MI355X
+    assert 0 < ws(736, 1280, 5, L.F32, 3, 7) <= 144 * 10 ** 9
+    assert _config(720, 1280, 5, 8, L.F32) == {'n_ctx': 7, 'n_trunk': 3, 'batched': True, 'final_only': False, 'chosen_by': 'fixed default'}
+    assert _config(720, 1280, 3, 8, final_only=True)['final_only'] is True
+    # a part where three trunk sets pass half of the memory gets two; one where nothing fits fails loudly
+    assert _config(720, 1280, 3, 8, total_memory=2 * ws(736, 1280, 3, L.F16, 3, 7) - 2)['n_trunk'] == 2
+    with pytest.raises(RuntimeError, match='exceeds the GPU memory'):
+        _config(720, 1280, 3, 8, total_memory=10 ** 9)
+    assert _config(64, 96, 1, 2) == {'n_ctx': 1, 'n_trunk': 2, 'batched': False, 'final_only': False, 'chosen_by': 'fixed default'}
+
+
+def test_choose_config_environment_and_explicit_values():
+    c = _config(720, 1280, 3, 8, env={'DEMFI_NCTX': '1', 'DEMFI_NTRUNK': '2'})
+    assert (c['n_ctx'], c['n_trunk'], c['batched'], c['chosen_by']) == (1, 2, False, 'env')
+    c = _config(720, 1280, 3, 8, env={'DEMFI_NTRUNK': '2'})
+    assert (c['n_ctx'], c['n_trunk'], c['chosen_by']) == (7, 2, 'env')
+    c = _config(720, 1280, 3, 8, env={'DEMFI_NCTX': '7', 'DEMFI_NTRUNK': '1'}, cached=(1, 3))
+    assert (c['n_ctx'], c['n_trunk'], c['chosen_by']) == (7, 1, 'env')
+    # DEMFI_TB=0: one graph per time instant over min(5, M-1) streams, and final_only is a mode of the batched plan
+    c = _config(720, 1280, 3, 8, env={'DEMFI_TB': '0'}, final_only=True)
+    assert c == {'n_ctx': 5, 'n_trunk': 2, 'batched': False, 'final_only': False, 'chosen_by': 'fixed default'}
+    assert _config(720, 1280, 3, 4, env={'DEMFI_TB': '0'})['n_ctx'] == 3
+    assert _config(720, 1280, 3, 8, n_ctx=1, n_trunk=1) == {'n_ctx': 1, 'n_trunk': 1, 'batched': False, 'final_only': False, 'chosen_by': 'explicit'}
+    # an explicit n_ctx must divide M-1 for the batched x M plan; the per-window plans pad a short chunk instead
+    with pytest.raises(ValueError, match='must divide'):
+        _config(720, 1280, 3, 8, n_ctx=3)
+    c = _config(720, 1280, 3, 8, n_ctx=3, retime=Fraction(8))
+    assert (c['n_ctx'], c['batched'], c['chosen_by']) == (3, True, 'explicit')
+
+
+def test_choose_config_cached_engine():
+    """An engine the model already holds fixes the shape only when it is a runner's (n_ctx > 1) and fits this M."""
+    assert _config(720, 1280, 3, 8, cached=(7, 2)) == {'n_ctx': 7, 'n_trunk': 2, 'batched': True, 'final_only': False, 'chosen_by': 'cached engine'}
+    assert _config(720, 1280, 3, 8, cached=(1, 1))['chosen_by'] == 'fixed default'       # a plain forward()'s engine
+    c = _config(720, 1280, 3, 8, cached=(5, 2))                                           # 5 does not divide 7: only its trunk sets
+    assert (c['n_ctx'], c['n_trunk'], c['chosen_by']) == (7, 2, 'cached engine')
+    c = _config(720, 1280, 3, 8, cached=(7, 2), retime=Fraction(8))                       # never for the per-window plans
+    assert (c['n_ctx'], c['n_trunk'], c['chosen_by']) == (7, 3, 'retime schedule')
+    assert _config(720, 1280, 3, 8, cached=(7, 2), env={'DEMFI_TB': '0'})['chosen_by'] == 'fixed default'
+
+
+def test_choose_config_retimed_defaults_follow_the_schedule():
+    from demfi_amd import retime as R
+    for r, n_ctx in ((Fraction(8), 7), (Fraction(5, 2), 2), (Fraction(2), 1)):
+        c = _config(720, 1280, 3, 8, retime=r)
+        assert c['n_ctx'] == n_ctx == R.default_n_ctx(r, lambda d: True) and c['chosen_by'] == 'retime schedule'
+        assert c['batched'] == (n_ctx > 1) and c['n_trunk'] == (3 if n_ctx > 1 else 2)
+    # x M through the plans is the x M default wherever both fit
+    assert {k: v for k, v in _config(720, 1280, 3, 8, retime=Fraction(8)).items() if k != 'chosen_by'} == \
+           {k: v for k, v in _config(720, 1280, 3, 8).items() if k != 'chosen_by'}
+    # sizes whose workspace does not fit are left out: with room for 4 contexts only, 2 .. 4 would all pad the 7 instants of
+    # r = 8, so it runs them one by one (the non-batched plan) where the x M rule would have failed
+    ws = L.load().demfi_workspace_bytes
+    c = _config(720, 1280, 3, 8, retime=Fraction(8), total_memory=ws(736, 1280, 3, L.F16, 2, 4))
+    assert c['n_ctx'] == R.default_n_ctx(Fraction(8), lambda d: d <= 4) == 1 and (c['batched'], c['n_trunk']) == (False, 2)
+    with pytest.raises(RuntimeError, match='exceeds the GPU memory'):
+        _config(720, 1280, 3, 8, total_memory=ws(736, 1280, 3, L.F16, 2, 4))
+
+
+def test_choose_config_memory_probe():
+    ws = L.load().demfi_workspace_bytes
+    c = _config(720, 1280, 3, 8, auto=True, free_memory=lambda: 10 * ws(736, 1280, 3, L.F16, 3, 7))
+    assert (c['n_ctx'], c['n_trunk'], c['chosen_by']) == (7, 3, 'memory probe')
+    c = _config(720, 1280, 3, 8, env={'DEMFI_AUTO': '1'}, free_memory=lambda: ws(736, 1280, 3, L.F16, 2, 7))
+    assert (c['n_ctx'], c['n_trunk'], c['batched'], c['chosen_by']) == (1, 2, False, 'memory probe')
