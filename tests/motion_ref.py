@@ -133,7 +133,8 @@ def warp_blend(A, fa, B, fb, logit, t, rows=None):
     a, aa = bwarp(A, fa, r)
     b, ba = bwarp(B, fb, r)
     t = f64(f32(t))
-    o0 = 1.0 / (1.0 + np.exp(-logit[r].astype(f64)))
+    with np.errstate(over='ignore'):                                         # logits below -709: exp -> inf, o0 = 0, as intended
+        o0 = 1.0 / (1.0 + np.exp(-logit[r].astype(f64)))
     ka = ((1.0 - t) * o0)[..., None]
     kb = (t * (1.0 - o0))[..., None]
     den = ka + kb

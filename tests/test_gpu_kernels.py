@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 from demfi_amd import _lib as L                      # noqa: E402
 from demfi_amd.engine import Plan, _Dst              # noqa: E402
 from oracle import demfi_oracle as O                 # noqa: E402
+from tests import epilogue_ref as E                  # noqa: E402
 
 DEV = 'cuda:0'
 
@@ -674,23 +675,23 @@ def test_sep_gru_persistent_kernel(kh, kw, H, W, batch):
         pl.launch_conv(0, _stream())
         pl.launch_conv(1, _stream())
     torch.cuda.synchronize()
-    F = torch.nn.functional
-    nchw = lambda t: t.permute(0, 3, 1, 2).float().cpu()
-    q16 = lambda z: z.half().float()
+    # float64 references and the per-element bound of tests/epilogue_ref.py (storage + accumulation + evaluation); the q launch reads
+    # r*h and z as stored, so they are operands of its reference
+    nchw = lambda t: t.permute(0, 3, 1, 2).double().cpu()
+    T16 = torch.float16
     pad = (kh // 2, kw // 2)
-    zr = F.conv2d(torch.cat([nchw(h), nchw(xx)], 1), q16(wzr), bzr, padding=pad)
-    z, r = torch.sigmoid(zr[:, :64]), torch.sigmoid(zr[:, 64:])
-    assert (nchw(zb) - z).abs().max() < 1e-2
-    assert (nchw(rh) - r * nchw(h)).abs().max() < 1e-2
-    qv = torch.tanh(F.conv2d(torch.cat([nchw(rh), nchw(xx)], 1), q16(wq), bq, padding=pad))
-    assert (nchw(hn) - ((1 - nchw(zb)) * nchw(h) + nchw(zb) * qv)).abs().max() < 1e-2
+    vzr, Szr = E.preact(torch.cat([nchw(h), nchw(xx)], 1), wzr.half(), bzr, pad)
+    E.assert_inside(nchw(zb), E.ref_store(vzr[:, :64], Szr[:, :64], E.ACT_SIGMOID, T16), T16, 'z')
+    E.assert_inside(nchw(rh), E.ref_mul(vzr[:, 64:], Szr[:, 64:], nchw(h), T16), T16, 'r*h')
+    vq, Sq = E.preact(torch.cat([nchw(rh), nchw(xx)], 1), wq.half(), bq, pad)
+    E.assert_inside(nchw(hn), E.ref_gru(vq, Sq, nchw(h), nchw(zb), T16), T16, "h'")
 
 
 @pytest.mark.parametrize('kh,kw', [(1, 5), (5, 1)])
 @pytest.mark.parametrize('H,W,batch', [(8, 32, 1), (37, 75, 2), (64, 96, 1), (100, 45, 1), (33, 8, 3), (16, 160, 1), (96, 64, 2)])
 def test_gru_half_step_r_then_zq(kh, kw, H, W, batch):
     """Round 6 (gru.hip): a SepConvGRU half-step (DeMFInet.py:844-849 / 851-856) as  r*h  (demfi_gru_r) and  z + q + blend  in one launch
-    (demfi_gru_zq; z stays on chip).  Checked against fp32 torch on the same fp16 operands and against the round-5 path (the same three
+    (demfi_gru_zq; z stays on chip).  Checked against float64 on the same fp16 operands under the bound of tests/epilogue_ref.py and against the round-5 path (the same three
     layers through demfi_conv2d: equal up to the summation order of the fp32 accumulators).  Ragged tiles in both directions, batch > 1,
     tiles that straddle the image along the filter axis (lines) and across it (pixels)."""
     torch.manual_seed(23 + kh)
@@ -724,16 +725,17 @@ def test_gru_half_step_r_then_zq(kh, kw, H, W, batch):
         pl.launch_gru_zq(1, 2, _stream())
     torch.cuda.synchronize()
     assert float(zb.min()) == 7.0                           # the fused launch never touches the z buffer
-    F = torch.nn.functional
-    nchw = lambda t: t.permute(0, 3, 1, 2).float().cpu()
-    q16 = lambda z: z.half().float()
+    # float64 references and the per-element bound of tests/epilogue_ref.py.  demfi_gru_zq keeps z in fp32 on chip (it is never rounded
+    # to fp16), so the reference does not round it either (epilogue_ref.ref_zq); r*h is read as demfi_gru_r stored it
+    nchw = lambda t: t.permute(0, 3, 1, 2).double().cpu()
+    T16 = torch.float16
     pad = (kh // 2, kw // 2)
     hx = torch.cat([nchw(h), nchw(xx)], 1)
-    r = torch.sigmoid(F.conv2d(hx, q16(wr), br, padding=pad))
-    assert (nchw(rh) - r * nchw(h)).abs().max() < 4e-3
-    z = q16(torch.sigmoid(F.conv2d(hx, q16(wz), bz, padding=pad)))                       # z is handed over as fp16
-    qv = torch.tanh(F.conv2d(torch.cat([nchw(rh), nchw(xx)], 1), q16(wq), bq, padding=pad))
-    assert (nchw(hn) - ((1 - z) * nchw(h) + z * qv)).abs().max() < 4e-3
+    vr, Sr = E.preact(hx, wr.half(), br, pad)
+    E.assert_inside(nchw(rh), E.ref_mul(vr, Sr, nchw(h), T16), T16, 'r*h')
+    vz, Sz = E.preact(hx, wz.half(), bz, pad)
+    vq, Sq = E.preact(torch.cat([nchw(rh), nchw(xx)], 1), wq.half(), bq, pad)
+    E.assert_inside(nchw(hn), E.ref_zq(vz, Sz, vq, Sq, nchw(h), T16), T16, "h'")
     # against the round-5 launches on the same operands
     pl.launch_conv(1, _stream())                            # z -> zb
     pl.launch_conv(3, _stream())                            # r*h -> rh2
