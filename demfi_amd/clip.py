@@ -14,6 +14,7 @@ the same file (both are named after frame k+2), so what survives is: S0 of the w
 S1 of the clip's LAST window.  ``deblurred_writes`` states exactly that, which makes the output independent of the
 order in which encoder threads or ranks finish (round 2 submitted both and kept whichever finished last).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -21,6 +22,8 @@ import torch
 
 from . import clipio
 from . import dist as D
+from . import tiling as T
+from ._lib import DemfiError
 from .harness import t_schedule
 
 
@@ -163,16 +166,40 @@ class ClipRunner:
     """x M interpolation of whole clips on this rank's GPU: frames in (host uint8 BGR), frames out (sink or files)."""
 
     def __init__(self, model, height, width, n_tst=3, mfi=8, batch=4, world=1, rank=0, final_only=True, n_ctx=None, n_trunk=None, auto=False,
-                 retime=None):
+                 retime=None, tile=None, tile_margin=T.DEFAULT_MARGIN):
         from .runner import WindowRunner
+        # tile: None (the whole frame in one forward), 'auto' or (th, tw): frames run as the overlapping tiles of
+        # tiling.plan_tiles, ``tile_margin`` pixels next to every cut thrown away.  A plan of one tile is the untiled path.
+        plan = T.plan_tiles(height, width, tile, tile_margin) if tile is not None else None
+        self.plan = plan if plan is not None and plan.n_tiles > 1 else None
+        self.h, self.w = height, width
+        rh, rw = self.plan.tile if self.plan is not None else (height, width)
         # the clip pipeline delivers the LAST recursion's frames only (like test_custom, utils.py:1430-1434), so the decoder
         # passes that only produce the earlier recursions' frames need not run: same delivered bytes (WindowRunner.final_only).
         # retime: the frame rate ratio of the Y4M edge (demfi_amd.video --fps), see WindowRunner
-        self.runner = WindowRunner(model, height, width, n_tst, mfi, final_only=final_only, n_ctx=n_ctx, n_trunk=n_trunk, auto=auto,
-                                   retime=retime)
-        self.h, self.w, self.mfi, self.batch = height, width, mfi, batch
+        with self.oversize_hint():
+            self.runner = WindowRunner(model, rh, rw, n_tst, mfi, final_only=final_only, n_ctx=n_ctx, n_trunk=n_trunk, auto=auto,
+                                       retime=retime, tiles=self.plan)
+        self.mfi, self.batch = mfi, batch
         self.world, self.rank = world, rank
         self.ts = t_schedule(mfi) if retime is None else None
+
+    @property
+    def n_tiles(self):
+        return self.plan.n_tiles if self.plan is not None else 1
+
+    @contextlib.contextmanager
+    def oversize_hint(self):
+        """What the engine or the runner raises for an untiled frame above the largest size that is tested untiled reaches the
+        user with the way out appended."""
+        try:
+            yield
+        except RuntimeError as e:
+            if self.plan is not None or (self.h <= T.MAX_TILE_H and self.w <= T.MAX_TILE_W):
+                raise
+            msg = ('%s\n%dx%d is above %dx%d, the largest frame that is run in one forward: run it as tiles with --tile auto '
+                   "(tile='auto')" % (e, self.h, self.w, T.MAX_TILE_H, T.MAX_TILE_W))
+            raise (type(e) if type(e) in (RuntimeError, DemfiError) else RuntimeError)(msg) from e
 
     def my_windows(self, n_frames, full_length=False):
         """(global index of this rank's first window, its (B0, B1, B-1, B2) tuples).  ``full_length``: the windows of the
@@ -201,7 +228,8 @@ class ClipRunner:
                 t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
                 return t if t.is_pinned() else t.pin_memory()
         shifted = (lambda k, st, s01: sink(lo + k, st, s01)) if sink is not None else None
-        return self.runner.run_clip_u8(_Pinned(), wins, shifted, batch=self.batch)
+        with self.oversize_hint():
+            return self.runner.run_clip_u8(_Pinned(), wins, shifted, batch=self.batch)
 
     def run_folder(self, scene_dir, out_dir=None, pool=None, ext='.png', ahead=None):
         """One scene folder of PNG frames -> ``out_dir`` (default: the reference's ``<scene>_sharply_interpolated_xM``).
@@ -231,7 +259,8 @@ class ClipRunner:
             if w1:
                 pool.submit_write(os.path.join(out_dir, s1n), s01[1].numpy())
             written[0] += len(st_names) + int(w0) + int(w1)
-        n = self.runner.run_clip_u8(frames, wins, sink, batch=self.batch)
+        with self.oversize_hint():
+            n = self.runner.run_clip_u8(frames, wins, sink, batch=self.batch)
         pool.wait()
         self.last_decode_peak = frames.peak              # frames held by the streamed decoder at its fullest (tests)
         if own:
@@ -247,6 +276,8 @@ class ClipRunner:
         reference's bookkeeping (``deblur_time_indices``): S0 of every window at t = 0.5 (x8; the only t at x2), S1 of the scene's
         LAST window at the last t.  Reduce over ranks with ``EvalTable.all_reduce``.  Returns (tables, windows evaluated)."""
         from .metrics import FrameEvaluator, u8_frame_to_tensor
+        if self.plan is not None:
+            raise ValueError('ClipRunner.evaluate: the fp32 evaluation path is not tiled (tile=...)')
         names = sorted(os.path.join(blur_dir, f) for f in os.listdir(blur_dir) if f.endswith(ext))
         if len(names) < 4:
             raise RuntimeError('Found %d frames in %s: a clip needs at least 4' % (len(names), blur_dir))
@@ -298,17 +329,9 @@ class ClipRunner:
         return D.sum_over_ranks([float(windows), float(frames)], device).tolist()
 
 
-def main(argv=None):
-    """``python -m demfi_amd.clip <custom_path> [<out_root>] [--checkpoint PATH] ...`` -- the folder-in / folder-out command
-    of ``main.py --phase test_custom`` (/root/reference/main.py:1108-1196): ``custom_path`` holds one folder of PNG frames per
-    scene (make_2D_dataset_Custom_Test, utils.py:554-580); every scene is interpolated x M and written to
-    ``<out_root or custom_path>/<scene>_sharply_interpolated_x<M>`` under the reference's file names.  ``--checkpoint`` loads the
-    reference's ``.pt`` (``checkpoint['state_dict_Model']``, main.py:316, 351); without it the deterministic random-init weights
-    are used (and said so).  Launched under ``torch.distributed.run`` the windows of every scene are sharded over the ranks
-    (one GPU each, RCCL broadcast of the state_dict from rank 0, no data-path collective)."""
+def parser():
+    """The command line of ``main``."""
     import argparse
-    import json
-    import time
     ap = argparse.ArgumentParser(prog='python -m demfi_amd.clip', description=main.__doc__.split('\n\n')[0])
     ap.add_argument('custom_path', help='folder with one sub-folder of frames per scene (or a single scene folder of frames)')
     ap.add_argument('out_root', nargs='?', default=None, help='where the <scene>_sharply_interpolated_xM folders go (default: custom_path)')
@@ -322,7 +345,22 @@ def main(argv=None):
     ap.add_argument('--n-ctx', type=int, default=None, help='per-t contexts per launch sequence (default: fixed rule, 7 at x8); must divide M-1')
     ap.add_argument('--n-trunk', type=int, default=None, help='trunk buffer sets = windows in flight (default: 3 if they fit half of the GPU memory, else 2)')
     ap.add_argument('--auto', action='store_true', help='size n_ctx / n_trunk from the FREE memory of the GPU (shared or smaller GPUs)')
-    a = ap.parse_args(argv)
+    T.add_arguments(ap)
+    return ap
+
+
+def main(argv=None):
+    """``python -m demfi_amd.clip <custom_path> [<out_root>] [--checkpoint PATH] ...`` -- the folder-in / folder-out command
+    of ``main.py --phase test_custom`` (/root/reference/main.py:1108-1196): ``custom_path`` holds one folder of PNG frames per
+    scene (make_2D_dataset_Custom_Test, utils.py:554-580); every scene is interpolated x M and written to
+    ``<out_root or custom_path>/<scene>_sharply_interpolated_x<M>`` under the reference's file names.  ``--checkpoint`` loads the
+    reference's ``.pt`` (``checkpoint['state_dict_Model']``, main.py:316, 351); without it the deterministic random-init weights
+    are used (and said so).  Launched under ``torch.distributed.run`` the windows of every scene are sharded over the ranks
+    (one GPU each, RCCL broadcast of the state_dict from rank 0, no data-path collective).  ``--tile auto|THxTW`` runs large
+    frames as overlapping tiles (``demfi_amd.tiling``)."""
+    import json
+    import time
+    a = parser().parse_args(argv)
     from . import DeMFInet, HyperParams, synthetic_state_dict
     from .weights import load_checkpoint
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
@@ -357,7 +395,8 @@ def main(argv=None):
         cr = runners.get((h, w))
         if cr is None:
             cr = runners[(h, w)] = ClipRunner(model, h, w, a.n_tst, a.mfi, batch=a.batch, world=world, rank=rank,
-                                              final_only=not a.all_recursions, n_ctx=a.n_ctx, n_trunk=a.n_trunk, auto=a.auto)
+                                              final_only=not a.all_recursions, n_ctx=a.n_ctx, n_trunk=a.n_trunk, auto=a.auto,
+                                              tile=a.tile, tile_margin=a.tile_margin)
         nw, nf = cr.run_folder(path, os.path.join(out_root, scene + '_sharply_interpolated_x' + str(a.mfi)), pool=pool, ext=a.ext)
         tot_w += nw
         tot_f += nf
@@ -368,6 +407,8 @@ def main(argv=None):
     if rank == 0:
         print(json.dumps({'scenes': len(jobs), 'windows': int(tw), 'png_written': int(tf), 'seconds': round(dt, 2), 'ranks': world,
                           'St_frames_per_s': round(tw * (a.mfi - 1) / dt, 2) if dt > 0 else None,
+                          'tiles': max([cr.n_tiles for cr in runners.values()] or [1]),
+                          'tile': next((cr.plan.label() for cr in runners.values() if cr.plan is not None), None),
                           'weights': os.path.basename(a.checkpoint) if a.checkpoint else 'synthetic_state_dict(0) (random init: no checkpoint given)',
                           'out_root': out_root}))
     D.finalize()

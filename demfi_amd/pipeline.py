@@ -2,7 +2,11 @@
 per output format (``BgrEdge``: BGR frames in and out; ``Y4mEdge``: 4:2:0 payloads in and out, every window on its own plan)
 and the double-buffered batch loop that drives them (``ClipPipeline``).  An edge has the same few methods whatever its format:
 ``upload`` one frame into a slot and ``uploaded`` after a batch's copies (h2d stream), ``run`` a batch (compute stream), ``d2h``
-its outputs to pinned memory (d2h stream) and ``drain`` them to the sink; what ``run`` returns is handed back to ``d2h`` / ``drain``."""
+its outputs to pinned memory (d2h stream) and ``drain`` them to the sink; what ``run`` returns is handed back to ``d2h`` / ``drain``.
+
+A runner of tiles (``WindowRunner(tiles=plan)``, ``demfi_amd.tiling``) has the tile's size while the slots, the outputs and
+everything after them keep the frame's: ``Tiler`` crops every uploaded frame into its tiles once, each (run, tile) pair is one run
+of the runner, and one stitch launch per batch pastes the kept rectangles into the full-size output buffers."""
 import ctypes as C
 import itertools
 import weakref
@@ -66,14 +70,69 @@ class FrameSlots:
                 self.busy[sl] = ev
 
 
-class BgrEdge:
-    """uint8 BGR [h,w,3] frames in; sink(k, St [M-1,h,w,3], S0S1 [2,h,w,3]) out (views of pinned staging buffers)."""
+def consecutive(sls):
+    """(first, count) of every run of consecutive slots in the list ``sls``."""
+    r = 0
+    while r < len(sls):
+        e = r + 1
+        while e < len(sls) and sls[e] == sls[e - 1] + 1:
+            e += 1
+        yield sls[r], e - r
+        r = e
 
-    def __init__(self, runner, batch, slots):
-        self.rn, self.slots = runner, slots
-        dev, shape = runner.engine.device, (runner.h, runner.w, 3)
-        self.out = [torch.empty((batch, runner.mfi - 1) + shape, dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.s01 = [torch.empty((batch, 2) + shape, dtype=torch.uint8, device=dev) for _ in range(2)]
+
+class Tiler:
+    """Device side of a multi-tile plan (``demfi_amd.tiling``).  ``tin`` [nslot, n_tiles, th, tw, 3]: the tiles of every frame
+    slot, cropped when the frame is uploaded (``crop``: one ``demfi_u8_tile_crop`` launch per run of consecutive new slots, on the
+    upload stream), so a frame is cropped once however many windows read it, and a slot's ``busy`` event covers its tiles too.
+    ``stitch``: ONE ``demfi_u8_tile_stitch`` launch pastes the tile outputs of a batch into full frames."""
+
+    def __init__(self, plan, slots, lib, dev, max_frames):
+        self.plan, self.nt, self.lib, self.slots = plan, plan.n_tiles, lib, slots
+        (self.h, self.w), (self.th, self.tw) = (plan.h, plan.w), plan.tile
+        self.rects = np.ascontiguousarray(plan.rects(), dtype=np.int32)
+        self.rects_dev = torch.from_numpy(self.rects).to(dev)
+        self.tin = torch.empty((len(slots.frames), self.nt, self.th, self.tw, 3), dtype=torch.uint8, device=dev)
+        self.offs = torch.empty(max_frames * (self.nt + 1), dtype=torch.int64, device=dev)    # reused in stream order
+
+    def crop(self, sls, stream):
+        fr = self.slots.frames
+        for s0, cnt in consecutive(sls):
+            L.check(self.lib.demfi_u8_tile_crop(fr[s0].data_ptr(), fr.stride(0), self.tin[s0].data_ptr(), cnt, self.h, self.w, self.th,
+                                                self.tw, self.nt, self.rects.ctypes.data, self.rects_dev.data_ptr(), stream.cuda_stream),
+                    'u8_tile_crop')
+
+    def stitch(self, src, src_offs, dst, dst_offs, stream):
+        """Frame f = the tiles at src + src_offs[f, j] -> the frame at dst + dst_offs[f] (numpy int64 byte offsets)."""
+        n = len(dst_offs)
+        if n == 0:
+            return
+        od = self.offs[:n * (self.nt + 1)]
+        od.copy_(torch.from_numpy(np.concatenate([np.asarray(src_offs, np.int64).reshape(-1), np.asarray(dst_offs, np.int64)])).pin_memory(),
+                 non_blocking=True)
+        L.check(self.lib.demfi_u8_tile_stitch(src.data_ptr(), od.data_ptr(), dst.data_ptr(), od[n * self.nt:].data_ptr(), n, self.h, self.w,
+                                              self.th, self.tw, self.nt, self.rects.ctypes.data, self.rects_dev.data_ptr(),
+                                              stream.cuda_stream), 'u8_tile_stitch')
+
+
+class BgrEdge:
+    """uint8 BGR [h,w,3] frames in; sink(k, St [M-1,h,w,3], S0S1 [2,h,w,3]) out (views of pinned staging buffers).  Tiled: window w
+    is the n_tiles runs w * n_tiles + j into ``tout`` / ``ts01``; out and s01 are then halves of one buffer (one stitch launch)."""
+
+    def __init__(self, runner, batch, slots, tiler=None):
+        self.rn, self.slots, self.tiler = runner, slots, tiler
+        self.fh, self.fw = (tiler.h, tiler.w) if tiler else (runner.h, runner.w)
+        dev, shape, m1 = runner.engine.device, (self.fh, self.fw, 3), runner.mfi - 1
+        if tiler:
+            def halves(n, sh):                       # [n, M-1] + sh and [n, 2] + sh in one allocation
+                buf, cut = torch.empty((n * (m1 + 2),) + sh, dtype=torch.uint8, device=dev), n * m1
+                return buf, buf[:cut].view((n, m1) + sh), buf[cut:].view((n, 2) + sh)
+            self.buf, self.out, self.s01 = zip(*[halves(batch, shape) for _ in range(2)])
+            self.tbuf, self.tout, self.ts01 = halves(batch * tiler.nt, (tiler.th, tiler.tw, 3))
+            self._stitch_offs = {}
+        else:
+            self.out = [torch.empty((batch, m1) + shape, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self.s01 = [torch.empty((batch, 2) + shape, dtype=torch.uint8, device=dev) for _ in range(2)]
         self.h_out = [torch.empty((batch, runner.mfi - 1) + shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.h_s01 = [torch.empty((batch, 2) + shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
 
@@ -81,16 +140,33 @@ class BgrEdge:
         return ()
 
     def upload(self, sl, idx, f):
-        if tuple(f.shape) != (self.rn.h, self.rn.w, 3) or f.dtype != torch.uint8:
-            raise ValueError('frame %d: expected uint8 [%d,%d,3], got %s %s' % (idx, self.rn.h, self.rn.w, f.dtype, tuple(f.shape)))
+        if tuple(f.shape) != (self.fh, self.fw, 3) or f.dtype != torch.uint8:
+            raise ValueError('frame %d: expected uint8 [%d,%d,3], got %s %s' % (idx, self.fh, self.fw, f.dtype, tuple(f.shape)))
         self.slots.frames[sl].copy_(f, non_blocking=True)
 
     def uploaded(self, new, h2d):
-        pass
+        if self.tiler:
+            self.tiler.crop([sl for _, sl in new], h2d)
 
     def run(self, i, n, wins, frames, cur):
-        cnt = len(wins)
-        self.rn.run_windows_u8([[self.slots.frames[sl] for sl in fr] for fr in frames], out=self.out[i][:cnt], s01=self.s01[i][:cnt])
+        cnt, tl = len(wins), self.tiler
+        if not tl:
+            self.rn.run_windows_u8([[self.slots.frames[sl] for sl in fr] for fr in frames], out=self.out[i][:cnt], s01=self.s01[i][:cnt])
+            return cnt, frames
+        nt = tl.nt
+        self.rn.run_windows_u8([[tl.tin[sl, j] for sl in fr] for fr in frames for j in range(nt)], out=self.tout[:cnt * nt],
+                               s01=self.ts01[:cnt * nt])
+        offs = self._stitch_offs.get(cnt)
+        if offs is None:                             # frame (w, p) of out, then of s01: its tiles are rows w * nt + j of tout / ts01
+            m1, fsz, tsz = self.rn.mfi - 1, self.out[i][0, 0].numel(), self.tout[0, 0].numel()
+            w, j = np.arange(cnt, dtype=np.int64)[:, None, None], np.arange(nt, dtype=np.int64)[None, None, :]
+            src, dst = [], []
+            for k, d0, s0 in ((m1, 0, 0), (2, self.out[i].numel(), self.tout.numel())):
+                p = np.arange(k, dtype=np.int64)[None, :, None]
+                src.append((s0 + ((w * nt + j) * k + p) * tsz).reshape(-1, nt))
+                dst.append((d0 + (w * k + p) * fsz)[:, :, 0].reshape(-1))
+            offs = self._stitch_offs[cnt] = (np.concatenate(src), np.concatenate(dst))
+        tl.stitch(self.tbuf, offs[0], self.buf[i], offs[1], cur)
         return cnt, frames
 
     def d2h(self, i, cnt):
@@ -108,10 +184,11 @@ class Y4mEdge:
     cut window is two runs); run w of a batch writes its frames to comb[i][w] = [S0, St x J, S1], J = ceil(r), and one gather
     launch per batch puts the outputs in stream order.  ``full``: the full-length timeline of ``retime``."""
 
-    def __init__(self, runner, batch, slots, cuts, full):
-        self.rn, self.slots, self.cuts, self.full = runner, slots, cuts, full
+    def __init__(self, runner, batch, slots, cuts, full, tiler=None):
+        self.rn, self.slots, self.cuts, self.full, self.tiler = runner, slots, cuts, full, tiler
         self.r = runner.retime if runner.retime is not None else Fraction(runner.mfi)
-        dev, h, w, nsl = runner.engine.device, runner.h, runner.w, len(slots.frames)
+        h, w = self.fh, self.fw = (tiler.h, tiler.w) if tiler else (runner.h, runner.w)
+        dev, nsl = runner.engine.device, len(slots.frames)
         P, J = self.P, self.J = payload_size(h, w), R.max_instants(self.r)
         nJ = -(-J // runner.n_ctx) * runner.n_ctx if runner.tb else J    # instants incl. the padding of a short chunk
         runs_max = 2 * batch if cuts else batch                          # a cut window is two runs
@@ -119,8 +196,11 @@ class Y4mEdge:
         nout = (batch + 1) * J if full else batch * J + 1
         self.yuv_in = torch.empty((nsl, P), dtype=torch.uint8, device=dev)
         self.comb = [torch.empty((runs_max, J + 2, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.t = [torch.empty((runs_max, nJ), dtype=torch.float32, device=dev) for _ in range(2)]
-        self.sinks = [torch.empty((runs_max, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)]
+        nt = tiler.nt if tiler else 1                                    # tiled: run w is the runs w * nt + j of the tile runner
+        if tiler:        # their frames; one buffer serves both sets: the stitch has read it before the next batch's runs start
+            self.tcomb = torch.empty((runs_max * nt, J + 2, tiler.th, tiler.tw, 3), dtype=torch.uint8, device=dev)
+        self.t = [torch.empty((runs_max * nt, nJ), dtype=torch.float32, device=dev) for _ in range(2)]
+        self.sinks = [torch.empty((runs_max * nt, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)]
         self.offs = [torch.empty(nout, dtype=torch.int64, device=dev) for _ in range(2)]
         self.yuv_out = [torch.empty((nout, P), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.h_yuv = [torch.empty((nout, P), dtype=torch.uint8).pin_memory() for _ in range(2)]
@@ -148,14 +228,11 @@ class Y4mEdge:
     def uploaded(self, new, h2d):
         """Payloads copied to yuv_in[slot] -> BGR frame slots, one launch per run of consecutive slots; then the SADs."""
         rn, yuv, sls = self.rn, self.yuv, [sl for _, sl in new]
-        r = 0
-        while r < len(sls):
-            e = r + 1
-            while e < len(sls) and sls[e] == sls[e - 1] + 1:
-                e += 1
-            L.check(rn.lib.demfi_yuv420_to_bgr(self.yuv_in[sls[r]].data_ptr(), self.P, self.slots.frames[sls[r]].data_ptr(), rn.h * rn.w * 3,
-                                               e - r, rn.h, rn.w, yuv.matrix, int(yuv.full_range), yuv.siting, h2d.cuda_stream), 'yuv420_to_bgr')
-            r = e
+        for s0, cnt in consecutive(sls):
+            L.check(rn.lib.demfi_yuv420_to_bgr(self.yuv_in[s0].data_ptr(), self.P, self.slots.frames[s0].data_ptr(), self.fh * self.fw * 3,
+                                               cnt, self.fh, self.fw, yuv.matrix, int(yuv.full_range), yuv.siting, h2d.cuda_stream), 'yuv420_to_bgr')
+        if self.tiler:
+            self.tiler.crop(sls, h2d)
         if self.det is not None:
             self._scene_sads([idx for idx, _ in new], h2d)
 
@@ -211,8 +288,15 @@ class Y4mEdge:
     def _run_windows(self, i, runs):
         """Run w = (4 slots, instants, kinds) runs its instants into comb[i][w].  The t values (padded slots repeat the last t)
         and the uint8 sink records (one per (run, instant); S0 / S1 only in the row of the run's first instant and only when
-        ``kinds`` holds that frame; rows past a run's instants disabled) are uploaded on the current stream."""
-        rn, comb, J = self.rn, self.comb[i], self.J
+        ``kinds`` holds that frame; rows past a run's instants disabled) are uploaded on the current stream.
+        Tiled: every run is one run per tile, on that tile of its slots into tcomb, and the frames written are then stitched
+        into comb[i] in one launch."""
+        rn, J, tl = self.rn, self.J, self.tiler
+        if tl:
+            full, comb = runs, self.tcomb
+            runs = [([tl.tin[sl, j] for sl in fr], ts, kinds) for fr, ts, kinds in full for j in range(tl.nt)]
+        else:
+            comb, runs = self.comb[i], [([self.slots.frames[sl] for sl in fr], ts, kinds) for fr, ts, kinds in runs]
         nw, nJ = len(runs), self.t[i].shape[1]
         tt = np.empty((nw, nJ), np.float32)
         st = np.zeros((nw, nJ), np.int64)
@@ -231,12 +315,16 @@ class Y4mEdge:
             a = fill_sink_records(np.empty((nw, nJ, 32), np.int64), st, s01[0], s01[1], rn.h, rn.w, rn.n_tst)
             rows = self.sinks[i][:nw]
             rows.copy_(torch.from_numpy(a).pin_memory(), non_blocking=True)
-        io = [rn._u8_io([self.slots.frames[sl] for sl in fr], comb[w, 1:J + 1], comb[w, 0::J + 1], None if rows is None else rows[w])
-              for w, (fr, _, _) in enumerate(runs)]
+        io = [rn._u8_io(fr, comb[w, 1:J + 1], comb[w, 0::J + 1], None if rows is None else rows[w]) for w, (fr, _, _) in enumerate(runs)]
         cur = rn._begin()
         for w, (load, emit, pre) in enumerate(io):
             rn._window(load, emit, body_only=True, pre=pre, t_dev=t_dev[w], nt=len(runs[w][1]))
         rn._end(cur)
+        if tl:
+            (c0, c1), (t0, t1), j = self.comb[i].stride()[:2], comb.stride()[:2], np.arange(tl.nt, dtype=np.int64)
+            pos = [(w, p) for w, (_, ts, kinds) in enumerate(full)
+                   for p in ([0] if R.S0 in kinds else []) + list(range(1, len(ts) + 1)) + ([J + 1] if R.S1 in kinds else [])]
+            tl.stitch(comb, [(w * tl.nt + j) * t0 + p * t1 for w, p in pos], self.comb[i], [w * c0 + p * c1 for w, p in pos], cur)
 
     def _gather(self, i, outs, cur):
         """Outputs of a batch (comb[i]) -> yuv_out[i] in stream order: ONE gather launch on the compute stream.  outs[w]:
@@ -249,7 +337,7 @@ class Y4mEdge:
             raise RuntimeError('retime: %d outputs for %d payload slots' % (nf, dst.shape[0]))
         od = self.offs[i][:nf]
         od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
-        L.check(rn.lib.demfi_bgr_to_yuv420_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), dst.shape[1], nf, rn.h, rn.w,
+        L.check(rn.lib.demfi_bgr_to_yuv420_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), dst.shape[1], nf, self.fh, self.fw,
                                                   yuv.matrix, int(yuv.full_range), cur.cuda_stream), 'bgr_to_yuv420_gather')
         return [len(o) for o in outs]
 
@@ -274,8 +362,14 @@ class ClipPipeline:
         runner = weakref.proxy(runner)               # the runner owns this pipeline: no reference cycle keeps its buffers alive
         self.batch, self.key = batch, (batch, y4m, cuts, full)          # what a cached pipeline can be reused for
         self.h2d, self.d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-        self.slots = FrameSlots(max(2 * batch + 8, 8 * batch), runner.h, runner.w, dev)
-        self.edge = Y4mEdge(runner, batch, self.slots, cuts, full) if y4m else BgrEdge(runner, batch, self.slots)
+        plan = runner.tiles
+        fh, fw = (plan.h, plan.w) if plan is not None else (runner.h, runner.w)
+        self.slots = FrameSlots(max(2 * batch + 8, 8 * batch), fh, fw, dev)
+        tiler = None
+        if plan is not None:                         # frames stitched per batch: a run's J + 2 (a cut window is two runs), or M + 1
+            J2 = (R.max_instants(runner.retime if runner.retime is not None else Fraction(runner.mfi)) + 2) if y4m else runner.mfi + 1
+            tiler = Tiler(plan, self.slots, runner.lib, dev, (2 * batch if cuts else batch) * J2)
+        self.edge = Y4mEdge(runner, batch, self.slots, cuts, full, tiler) if y4m else BgrEdge(runner, batch, self.slots, tiler)
 
     def run(self, host_frames, windows, sink, reuse_frames, yuv, window_index):
         it = iter(windows)

@@ -103,7 +103,7 @@ def choose_config(H, W, n_tst, mfi, dtype_code, use_graph, n_ctx, n_trunk, auto,
 
 class WindowRunner:
     def __init__(self, model, height, width, n_tst=3, mfi=8, use_graph=True, final_only=False, n_ctx=None, n_trunk=None, auto=False,
-                 retime=None):
+                 retime=None, tiles=None):
         """final_only: produce the frames of the LAST recursion only (what test / test_custom consume, utils.py:1430-1434):
         the warp + D2 tail of the earlier recursions feeds nothing else and is skipped (batched plan only); the delivered
         frames are bit-identical.
@@ -114,7 +114,13 @@ class WindowRunner:
         retime: output / input frame rate ratio r >= 1 (a Fraction) of the Y4M edge of ``run_clip_u8`` in place of x M: window k
         runs the instants of ``retime.window_plan`` (``mfi`` is not used).  An explicit n_ctx is taken as given; the default is
         ``retime.default_n_ctx`` over the sizes whose workspace fits the GPU.  ``instants_run`` / ``instants_padded`` count the
-        time instants run and the padded per-t slots of short batched chunks."""
+        time instants run and the padded per-t slots of short batched chunks.
+        tiles: a multi-tile ``tiling.Plan`` whose tile size is height x width: ``run_clip_u8`` then takes and gives frames of the
+        plan's size and runs every window once per tile (``demfi_amd.pipeline``); every other entry point stays at the tile's size."""
+        if tiles is not None and (tiles.n_tiles < 2 or tuple(tiles.tile) != (height, width)):
+            raise ValueError('WindowRunner: tiles must be a plan of several %dx%d tiles, got %d of %dx%d' %
+                             ((height, width, tiles.n_tiles) + tuple(tiles.tile)))
+        self.tiles = tiles
         self._g_trunk = self._g_t = self._g_body = self._g_tb = None
         self._out_u8 = self._s01_u8 = self.out_d1 = self.s01_d1 = self._pipeline = None
         self._sink_tabs = {}                         # every attribute exists from here on, for __del__ and the lazy allocations
@@ -508,7 +514,9 @@ class WindowRunner:
         then be the consecutive unclamped tuples, and host_frames must also hold frame k0 - 1 when the first window k0 >= 1.
         Each batch's new payloads are scored by ONE ``demfi_yuv420_sad`` launch before its windows are planned: window k runs
         ``scene.window_runs``, a cut window as two runs.  The cuts found are in ``last_cuts``; ``cut_windows`` counts the cut
-        windows.  Returns the number of windows run."""
+        windows.
+        A runner of ``tiles``: the frames (and payloads) have the plan's size, every run is one run per tile, and
+        ``instants_run`` / ``instants_padded`` count those.  Returns the number of windows run."""
         cuts, full = getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False))
         if self.retime is not None and yuv is None:
             raise ValueError('WindowRunner.run_clip_u8: a retimed runner needs the Y4M edge (yuv=...)')

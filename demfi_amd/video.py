@@ -31,6 +31,7 @@ from . import _lib as L
 from . import dist as D
 from . import retime as R
 from . import scene as S
+from . import tiling as T
 from . import y4m
 from .clip import ClipRunner
 
@@ -58,9 +59,12 @@ class VideoRunner:
     frame 0 is input frame 0, n frames give ceil(n r) (n M for x M), the clip's ends clamp the tuples like cuts and the last
     frame is held to the end.  After a run, ``last_instants`` = (time instants run, padded per-t
     slots), ``last_st_frames`` = St frames written, ``last_cuts`` = the frames j that start a scene and ``last_cut_windows`` =
-    the windows run as cut windows, of this rank."""
+    the windows run as cut windows, of this rank.  ``tile``: None, 'auto' or (th, tw): frames run as overlapping tiles
+    (``demfi_amd.tiling``, ``tile_margin`` pixels thrown away next to every cut); ``last_plan`` is the plan of the last input, None
+    when it ran untiled, and ``last_instants`` then counts per tile."""
 
-    def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, **runner_kw):
+    def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
+                 tile_margin=T.DEFAULT_MARGIN, **runner_kw):
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
         if mfi is not None and fps is not None:
@@ -75,7 +79,10 @@ class VideoRunner:
         self.model, self.n_tst, self.mfi, self.batch, self.matrix = model, n_tst, mfi, batch, matrix
         self.scene_cut = S.check_threshold(scene_cut) if scene_cut is not None else None
         self.full_length = bool(full_length)
-        self.runner_kw = runner_kw
+        if tile is not None:
+            T.plan_tiles(64, 64, tile, tile_margin)      # a bad tile or margin fails here, not at the first frame
+        self.runner_kw = dict(runner_kw, tile=tile, tile_margin=tile_margin)
+        self.last_plan = None
         self._runners = {}
         self.last_decode_peak = 0
         self.last_instants = (0, 0)
@@ -103,6 +110,7 @@ class VideoRunner:
         if cr is None:
             cr = self._runners[key] = ClipRunner(self.model, hdr.h, hdr.w, self.n_tst, self.mfi or 8, batch=self.batch, world=world,
                                                  rank=rank, **dict(self.runner_kw, retime=r))
+        self.last_plan = cr.plan
         return cr
 
     def _run(self, cr, hdr, first, fn):
@@ -110,7 +118,8 @@ class VideoRunner:
         the per-run counters."""
         rn = cr.runner
         i0, p0, c0 = rn.instants_run, rn.instants_padded, rn.cut_windows
-        n = fn()
+        with cr.oversize_hint():
+            n = fn()
         lo = first()
         self.last_instants = (rn.instants_run - i0, rn.instants_padded - p0)
         self.last_cuts = list(rn.last_cuts) if self.scene_cut is not None else []
@@ -232,6 +241,7 @@ def parser():
                     help='cover the input\'s whole timeline: output frame 0 is input frame 0 and n input frames give ceil(n*F_out/F_in) '
                          'output frames (n*M with --mfi), the last input frame held to the end, so the video stays aligned with its '
                          'audio.  Off by default (the reference\'s timeline)')
+    T.add_arguments(ap)
     return ap
 
 
@@ -266,7 +276,8 @@ def main(argv=None):
         model.load_state_dict(load_checkpoint(a.checkpoint) if a.checkpoint else synthetic_state_dict(0))
     model = model.to(dev).eval()
     D.broadcast_state_dict(model, world, device=dev)
-    vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut, full_length=a.full_length)
+    vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut, full_length=a.full_length,
+                     tile=a.tile, tile_margin=a.tile_margin)
     t0 = time.perf_counter()
     if world > 1:
         nw, nf = vr.run_file(a.input, a.output, world, rank)
@@ -293,6 +304,8 @@ def main(argv=None):
                           'frames_per_s': round(tf / dt, 2) if dt > 0 else None,
                           'fps_out': str(vr.last_fps_out) if vr.last_fps_out is not None else None,
                           'instants_run': int(ti), 'instants_padded': int(tp), 'cut_windows': int(tc),
+                          'tiles': vr.last_plan.n_tiles if vr.last_plan is not None else 1,
+                          'tile': vr.last_plan.label() if vr.last_plan is not None else None,
                           'weights': os.path.basename(a.checkpoint) if a.checkpoint else 'synthetic_state_dict(0) (random init: no checkpoint given)',
                           'out': a.output}), file=sys.stderr)
     D.finalize()

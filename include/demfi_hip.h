@@ -373,6 +373,22 @@ int demfi_bgr_to_yuv420_gather(const uint8_t* base, const int64_t* src_offsets, 
 int demfi_yuv420_sad(const uint8_t* base, const int64_t* a_offsets, const int64_t* b_offsets, int n, int64_t payload, uint64_t* sad,
                      void* stream);
 
+/* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
+ * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
+ * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
+ * coordinates: the tile's source origin y0, x0, then its kept rectangle y0, x0, y1, x1 (exclusive ends), which lies inside the
+ * tile.  The plan is passed twice with the same content: rects in HOST memory, checked here before anything is launched (a
+ * tile that leaves the frame or keeps pixels outside itself is DEMFI_ERR_ARG), and rects_dev in DEVICE memory, read by the
+ * kernels, which skip a tile that fails the same check.  One launch each, n frames per launch.
+ * u8_tile_crop: frame i read at src + i*src_stride -> all its tiles, dst [n, n_tiles, th, tw, 3].
+ * u8_tile_stitch: tile j of frame i is read at base + src_offsets[i*n_tiles + j] ([th,tw,3]) and its kept rectangle written into
+ * the frame at dst + dst_offsets[i] (int64 byte offsets in DEVICE memory, any order; source repeats allowed).  The kept
+ * rectangles of a plan partition the frame, so every byte of a frame is written once and nothing outside the frames is. */
+int demfi_u8_tile_crop(const uint8_t* src, int64_t src_stride, uint8_t* dst, int n, int h, int w, int th, int tw, int n_tiles,
+                       const int32_t* rects, const int32_t* rects_dev, void* stream);
+int demfi_u8_tile_stitch(const uint8_t* base, const int64_t* src_offsets, uint8_t* dst, const int64_t* dst_offsets, int n, int h, int w,
+                         int th, int tw, int n_tiles, const int32_t* rects, const int32_t* rects_dev, void* stream);
+
 /* ---- on-GPU evaluation ------------------------------------------------------------
  * psnr (utils.py:652-660) and MATLAB-style 11x11 Gaussian ssim (utils.py:663-705) of one predicted frame against its
  * target as test() computes them (main.py:762-770): pred is rounded after denorm255_np, the target is not (round_gt = 0)
