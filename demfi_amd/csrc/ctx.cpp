@@ -1942,6 +1942,15 @@ extern "C" int demfi_ingest_u8(demfi_ctx* c, int trunk, const uint8_t* const* fr
                            c->dtype, c->H, c->W, stream);
 }
 
+extern "C" int demfi_ingest_u16(demfi_ctx* c, int trunk, const uint16_t* const* frames, int h, int w, int depth, void* stream)
+{
+    if (!c || !c->bound || c->on_host || trunk < 0 || trunk >= c->n_trunk)
+        return demfi_set_error(DEMFI_ERR_ARG, "demfi_ingest_u16: context not bound to device memory / bad trunk index");
+    BufSet& B = c->tr_bufs[trunk];
+    return demfi_u16_ingest(frames, h, w, depth, (float*)(c->base + B["x"].off), c->base + B["s2d"].off,
+                            (float*)(c->base + B["overlay"].off), c->dtype, c->H, c->W, stream);
+}
+
 extern "C" int demfi_forward_trunk_body(demfi_ctx* c, int trunk, void* stream)
 {
     if (!c || !c->bound || c->on_host || trunk < 0 || trunk >= c->n_trunk)

@@ -355,6 +355,10 @@ class Engine:
         """4 BGR uint8 [h,w,3] device frames (ctypes array of 4 pointers) -> x, s2d, overlay of the bound trunk context."""
         L.check(self.lib.demfi_ingest_u8(self._ctx, self.trunk, frame_ptrs, h, w, stream), 'ingest_u8')
 
+    def ingest_u16(self, frame_ptrs, h, w, depth, stream):
+        """``ingest_u8`` for 4 BGR uint16 [h,w,3] device frames holding 0 .. 2^depth - 1."""
+        L.check(self.lib.demfi_ingest_u16(self._ctx, self.trunk, frame_ptrs, h, w, depth, stream), 'ingest_u16')
+
     def run_trunk_body(self, stream):
         """The trunk without its s2d / overlay prologue (what follows ingest_u8)."""
         L.check(self.lib.demfi_forward_trunk_body(self._ctx, self.trunk, stream), 'forward_trunk_body')

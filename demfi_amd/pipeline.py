@@ -38,11 +38,11 @@ def fill_sink_records(a, st, s0, s1, h, w, n_tst):
 
 
 class FrameSlots:
-    """Device ring of input frame slots ``frames`` [n,h,w,3] uint8.  ``slot_of``: frame key -> slot; ``busy[s]``: event of the
-    compute of the batch that last read slot s."""
+    """Device ring of input frame slots ``frames`` [n,h,w,3] uint8 (``dtype`` int16: the 16-bit frames of a high-depth Y4M
+    stream).  ``slot_of``: frame key -> slot; ``busy[s]``: event of the compute of the batch that last read slot s."""
 
-    def __init__(self, n, h, w, dev):
-        self.frames = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    def __init__(self, n, h, w, dev, dtype=torch.uint8):
+        self.frames = torch.empty((n, h, w, 3), dtype=dtype, device=dev)
         self.reset()
 
     def reset(self):
@@ -182,10 +182,17 @@ class Y4mEdge:
     """4:2:0 payloads in; sink(k, payloads [c, P]) out, the c output frames window k owns in stream order.  Window k runs the
     instants of ``retime.window_plan`` for the runner's ratio (x M is r = M), with ``cuts`` those of ``scene.window_runs`` (a
     cut window is two runs); run w of a batch writes its frames to comb[i][w] = [S0, St x J, S1], J = ceil(r), and one gather
-    launch per batch puts the outputs in stream order.  ``full``: the full-length timeline of ``retime``."""
+    launch per batch puts the outputs in stream order.  ``full``: the full-length timeline of ``retime``.
+    ``depth`` > 8: payloads of 16-bit samples at that bit depth.  The payload buffers stay uint8 tensors sized in bytes (what the
+    host hands over and gets back); the frame slots and ``comb`` are int16 storage of the uint16 frames, the three launches
+    are those of csrc/yuv16.hip (strides and offsets in samples), the egress is the emit path and the SADs count samples."""
 
-    def __init__(self, runner, batch, slots, cuts, full, tiler=None):
+    def __init__(self, runner, batch, slots, cuts, full, tiler=None, depth=8):
         self.rn, self.slots, self.cuts, self.full, self.tiler = runner, slots, cuts, full, tiler
+        self.depth, self.hi = depth, depth > 8
+        if self.hi and tiler is not None:
+            raise ValueError('Y4mEdge: tiles move 8-bit pixels; a %d-bit stream cannot run tiled' % depth)
+        es, fdt = (2, torch.int16) if self.hi else (1, torch.uint8)      # bytes per sample; storage of a frame value
         self.r = runner.retime if runner.retime is not None else Fraction(runner.mfi)
         h, w = self.fh, self.fw = (tiler.h, tiler.w) if tiler else (runner.h, runner.w)
         dev, nsl = runner.engine.device, len(slots.frames)
@@ -194,16 +201,17 @@ class Y4mEdge:
         runs_max = 2 * batch if cuts else batch                          # a cut window is two runs
         # payloads of a batch: at most J per window, plus the last window's S1 (full-length: its [n-2, n) span, 2 J)
         nout = (batch + 1) * J if full else batch * J + 1
-        self.yuv_in = torch.empty((nsl, P), dtype=torch.uint8, device=dev)
-        self.comb = [torch.empty((runs_max, J + 2, h, w, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
+        Pb = self.Pb = P * es                                            # bytes of a payload of P samples
+        self.yuv_in = torch.empty((nsl, Pb), dtype=torch.uint8, device=dev)
+        self.comb = [torch.empty((runs_max, J + 2, h, w, 3), dtype=fdt, device=dev) for _ in range(2)]
         nt = tiler.nt if tiler else 1                                    # tiled: run w is the runs w * nt + j of the tile runner
         if tiler:        # their frames; one buffer serves both sets: the stitch has read it before the next batch's runs start
             self.tcomb = torch.empty((runs_max * nt, J + 2, tiler.th, tiler.tw, 3), dtype=torch.uint8, device=dev)
         self.t = [torch.empty((runs_max * nt, nJ), dtype=torch.float32, device=dev) for _ in range(2)]
         self.sinks = [torch.empty((runs_max * nt, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)]
         self.offs = [torch.empty(nout, dtype=torch.int64, device=dev) for _ in range(2)]
-        self.yuv_out = [torch.empty((nout, P), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.h_yuv = [torch.empty((nout, P), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.yuv_out = [torch.empty((nout, Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.h_yuv = [torch.empty((nout, Pb), dtype=torch.uint8).pin_memory() for _ in range(2)]
         if cuts:                                     # SADs of a batch's new frames (at most nsl) against their predecessors
             self.sad = torch.empty(nsl, dtype=torch.int64, device=dev)
             self.sad_offs = torch.empty(2 * nsl, dtype=torch.int64, device=dev)
@@ -216,19 +224,25 @@ class Y4mEdge:
         self.yuv, self.window_index, self.det = yuv, window_index, None
         if not self.cuts:
             return ()
-        det = self.det = S.Detector(self.P, yuv.scene_cut, first=S.first_frame(window_index(0) if window_index is not None else first_win[2]))
+        det = self.det = S.Detector(self.P, yuv.scene_cut, first=S.first_frame(window_index(0) if window_index is not None else first_win[2]),
+                                    peak=(1 << self.depth) - 1)
         self.rn.last_cuts = det.cuts
         return (det.next - 1,) if det.next - 1 < first_win[2] else ()
 
     def upload(self, sl, idx, f):
-        if tuple(f.shape) != (self.P,) or f.dtype != torch.uint8:
-            raise ValueError('frame %d: expected a uint8 [%d] 4:2:0 payload, got %s %s' % (idx, self.P, f.dtype, tuple(f.shape)))
+        if tuple(f.shape) != (self.Pb,) or f.dtype != torch.uint8:
+            raise ValueError('frame %d: expected a uint8 [%d] 4:2:0 payload, got %s %s' % (idx, self.Pb, f.dtype, tuple(f.shape)))
         self.yuv_in[sl].copy_(f, non_blocking=True)
 
     def uploaded(self, new, h2d):
         """Payloads copied to yuv_in[slot] -> BGR frame slots, one launch per run of consecutive slots; then the SADs."""
         rn, yuv, sls = self.rn, self.yuv, [sl for _, sl in new]
         for s0, cnt in consecutive(sls):
+            if self.hi:                              # strides in samples
+                L.check(rn.lib.demfi_yuv420p16_to_bgr16(self.yuv_in[s0].data_ptr(), self.P, self.slots.frames[s0].data_ptr(),
+                                                        self.fh * self.fw * 3, cnt, self.fh, self.fw, self.depth, yuv.matrix,
+                                                        int(yuv.full_range), yuv.siting, h2d.cuda_stream), 'yuv420p16_to_bgr16')
+                continue
             L.check(rn.lib.demfi_yuv420_to_bgr(self.yuv_in[s0].data_ptr(), self.P, self.slots.frames[s0].data_ptr(), self.fh * self.fw * 3,
                                                cnt, self.fh, self.fw, yuv.matrix, int(yuv.full_range), yuv.siting, h2d.cuda_stream), 'yuv420_to_bgr')
         if self.tiler:
@@ -254,8 +268,8 @@ class Y4mEdge:
         offs = [slot_of[j - 1] * P for j in js] + [slot_of[j] * P for j in js]
         od = self.sad_offs[:2 * m]
         od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
-        L.check(self.rn.lib.demfi_yuv420_sad(self.yuv_in.data_ptr(), od.data_ptr(), od[m:].data_ptr(), m, P, self.sad.data_ptr(),
-                                             h2d.cuda_stream), 'yuv420_sad')
+        sad = self.rn.lib.demfi_yuv420p16_sad if self.hi else self.rn.lib.demfi_yuv420_sad      # offsets and P: samples / bytes
+        L.check(sad(self.yuv_in.data_ptr(), od.data_ptr(), od[m:].data_ptr(), m, P, self.sad.data_ptr(), h2d.cuda_stream), 'yuv420_sad')
         self.h_sad[:m].copy_(self.sad[:m], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(h2d)
@@ -311,11 +325,14 @@ class Y4mEdge:
         t_dev = self.t[i][:nw]
         t_dev.copy_(torch.from_numpy(tt).pin_memory(), non_blocking=True)
         rows = None
-        if rn.engine.supports_u8_sink:
+        if rn.engine.supports_u8_sink and not self.hi:
             a = fill_sink_records(np.empty((nw, nJ, 32), np.int64), st, s01[0], s01[1], rn.h, rn.w, rn.n_tst)
             rows = self.sinks[i][:nw]
             rows.copy_(torch.from_numpy(a).pin_memory(), non_blocking=True)
-        io = [rn._u8_io(fr, comb[w, 1:J + 1], comb[w, 0::J + 1], None if rows is None else rows[w]) for w, (fr, _, _) in enumerate(runs)]
+        if self.hi:
+            io = [rn._u16_io(fr, comb[w, 1:J + 1], comb[w, 0::J + 1], self.depth) for w, (fr, _, _) in enumerate(runs)]
+        else:
+            io = [rn._u8_io(fr, comb[w, 1:J + 1], comb[w, 0::J + 1], None if rows is None else rows[w]) for w, (fr, _, _) in enumerate(runs)]
         cur = rn._begin()
         for w, (load, emit, pre) in enumerate(io):
             rn._window(load, emit, body_only=True, pre=pre, t_dev=t_dev[w], nt=len(runs[w][1]))
@@ -337,6 +354,11 @@ class Y4mEdge:
             raise RuntimeError('retime: %d outputs for %d payload slots' % (nf, dst.shape[0]))
         od = self.offs[i][:nf]
         od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
+        if self.hi:                                  # comb's element strides are samples; so is the payload stride
+            L.check(rn.lib.demfi_bgr16_to_yuv420p16_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), self.P, nf, self.fh, self.fw,
+                                                           self.depth, yuv.matrix, int(yuv.full_range), cur.cuda_stream),
+                    'bgr16_to_yuv420p16_gather')
+            return [len(o) for o in outs]
         L.check(rn.lib.demfi_bgr_to_yuv420_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), dst.shape[1], nf, self.fh, self.fw,
                                                   yuv.matrix, int(yuv.full_range), cur.cuda_stream), 'bgr_to_yuv420_gather')
         return [len(o) for o in outs]
@@ -357,19 +379,21 @@ class ClipPipeline:
     cuts / the full-length timeline, which size its buffers): H2D of a batch's new frames, its compute, the drain of the
     previous batch and its D2H, on three streams over two sets of output buffers."""
 
-    def __init__(self, runner, batch, y4m, cuts, full):
+    def __init__(self, runner, batch, y4m, cuts, full, depth=8):
         dev = self.dev = runner.engine.device
         runner = weakref.proxy(runner)               # the runner owns this pipeline: no reference cycle keeps its buffers alive
-        self.batch, self.key = batch, (batch, y4m, cuts, full)          # what a cached pipeline can be reused for
+        self.batch, self.key = batch, (batch, y4m, cuts, full, depth)   # what a cached pipeline can be reused for
+        if depth > 8 and not y4m:
+            raise ValueError('ClipPipeline: 16-bit frames are those of the Y4M edge only')
         self.h2d, self.d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
         plan = runner.tiles
         fh, fw = (plan.h, plan.w) if plan is not None else (runner.h, runner.w)
-        self.slots = FrameSlots(max(2 * batch + 8, 8 * batch), fh, fw, dev)
+        self.slots = FrameSlots(max(2 * batch + 8, 8 * batch), fh, fw, dev, torch.int16 if depth > 8 else torch.uint8)
         tiler = None
         if plan is not None:                         # frames stitched per batch: a run's J + 2 (a cut window is two runs), or M + 1
             J2 = (R.max_instants(runner.retime if runner.retime is not None else Fraction(runner.mfi)) + 2) if y4m else runner.mfi + 1
             tiler = Tiler(plan, self.slots, runner.lib, dev, (2 * batch if cuts else batch) * J2)
-        self.edge = Y4mEdge(runner, batch, self.slots, cuts, full, tiler) if y4m else BgrEdge(runner, batch, self.slots, tiler)
+        self.edge = Y4mEdge(runner, batch, self.slots, cuts, full, tiler, depth) if y4m else BgrEdge(runner, batch, self.slots, tiler)
 
     def run(self, host_frames, windows, sink, reuse_frames, yuv, window_index):
         it = iter(windows)

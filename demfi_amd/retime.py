@@ -149,13 +149,15 @@ def max_instants(r):
 
 
 def output_header(hdr, fps_out):
-    """Header of the retimed stream: the input's W H, F = F_out (reduced), progressive, A copied, C420jpeg, the input's
-    XCOLORRANGE -- the fields of ``y4m.output_header``."""
-    return y4m.Header(hdr.w, hdr.h, Fraction(fps_out), 'p', hdr.aspect, '420jpeg', hdr.color_range, (), '420jpeg')
+    """Header of the retimed stream: the input's W H, F = F_out (reduced), progressive, A copied, C420jpeg (C420pNN at the input's
+    depth above 8 bits), the input's XCOLORRANGE -- the fields of ``y4m.output_header``."""
+    return y4m.Header(hdr.w, hdr.h, Fraction(fps_out), 'p', hdr.aspect, '420jpeg', hdr.color_range, (), y4m.output_ctag(hdr.depth),
+                      hdr.depth)
 
 
 def block_offset(hdr_len, first_window, r, payload, full_length=False):
-    """Byte offset in the output file of the first frame of the block of windows starting at ``first_window``."""
+    """Byte offset in the output file of the first frame of the block of windows starting at ``first_window``; ``payload``:
+    the bytes of one payload (``Header.payload``)."""
     return y4m.frame_offset(hdr_len, first_output(first_window, r, full_length), payload)
 
 

@@ -26,6 +26,8 @@ from . import retime as R
 from .harness import t_schedule
 from .pipeline import ClipPipeline, fill_sink_records
 
+U16_DTYPES = tuple(d for d in (torch.int16, getattr(torch, 'uint16', None)) if d is not None)   # plain storage of 16-bit frames
+
 
 def choose_config(H, W, n_tst, mfi, dtype_code, use_graph, n_ctx, n_trunk, auto, retime, env, cached, total_memory, free_memory,
                   workspace_bytes, final_only=False):
@@ -488,6 +490,76 @@ class WindowRunner:
         self._end(cur)
         return out, s01
 
+    # ---- 16-bit frames (bit depth 10 .. 16 of the Y4M edge; 8 to compare with the uint8 path) -------------------------------
+    def _check_u16_frames(self, frames_u16, depth):
+        if depth not in (8, 10, 12, 14, 16):
+            raise ValueError('bit depth must be 8, 10, 12, 14 or 16, got %r' % (depth,))
+        if len(frames_u16) != 4:
+            raise ValueError('expected 4 16-bit frames (B0,B1,B-1,B2), got %d' % len(frames_u16))
+        for f in frames_u16:
+            self._check_device(f, '16-bit frame')
+            if f.dtype not in U16_DTYPES or tuple(f.shape) != (self.h, self.w, 3) or not f.is_contiguous():
+                raise ValueError('16-bit frames must be contiguous [%d,%d,3] int16 / uint16 tensors (the bits of uint16 values), got %s %s' %
+                                 (self.h, self.w, f.dtype, tuple(f.shape)))
+
+    def _u16_io(self, frames_u16, out_u16, s01_u16, depth):
+        """(load, emit, pre) of one 16-bit window, the counterpart of ``_u8_io``: 4 BGR [h,w,3] GPU frames of 16-bit storage
+        (``torch.int16`` holding the bits of uint16 values 0 .. 2^depth - 1; only pointers reach the library) in ->
+        out_u16 [J,h,w,3], s01_u16 [2,h,w,3] of the same storage.  Ingest: ONE kernel (``demfi_u16_ingest``).  Egress: always
+        the emit path, one ``demfi_frame_to_u16`` per frame (the fused sink of the fp16 engine writes uint8 only)."""
+        e = self.engine
+        self._check_u16_frames(frames_u16, depth)
+        ptrs = (C.c_void_p * 4)(*[f.data_ptr() for f in frames_u16])
+
+        def load(eng, h):
+            eng.ingest_u16(ptrs, self.h, self.w, depth, h)
+
+        def emit(j, ctx, sh):
+            fin = ctx['finals'][self.n_tst - 1]
+            L.check(self.lib.demfi_frame_to_u16(fin[2].data_ptr(), out_u16[j].data_ptr(), self.h, self.w, e.H, e.W, depth, sh), 'to_u16')
+            if j == 0:
+                for i in range(2):
+                    L.check(self.lib.demfi_frame_to_u16(fin[i].data_ptr(), s01_u16[i].data_ptr(), self.h, self.w, e.H, e.W, depth, sh),
+                            'to_u16')
+        return load, emit, None                      # no pre: _window then disables every uint8 sink record
+
+    def run_windows_u16(self, windows_u16, depth, out=None, s01=None, ts=None):
+        """``run_windows_u8`` for 16-bit frames at bit depth ``depth`` (list of 4-tuples of BGR [h,w,3] ``torch.int16`` GPU
+        frames, ready on the current stream), with the same scheduling.  Returns (St [n,M-1,h,w,3], S0S1 [n,2,h,w,3]) as
+        ``torch.int16`` storage of uint16 values (``.cpu().numpy().view(numpy.uint16)``).
+        ts: per window, the float32 instants it runs in place of the x M schedule (what a retimed runner needs: the instants
+        of ``retime.window_plan``); St is then [n, max len(ts), h, w, 3] and the rows past a window's instants are not written."""
+        n = len(windows_u16)
+        dev = self.engine.device
+        if ts is not None and len(ts) != n:
+            raise ValueError('run_windows_u16: %d lists of instants for %d windows' % (len(ts), n))
+        nj = self.mfi - 1 if ts is None else max([len(t) for t in ts] or [0])
+        if out is None:
+            out = torch.empty((n, nj, self.h, self.w, 3), dtype=torch.int16, device=dev)
+        if s01 is None:
+            s01 = torch.empty((n, 2, self.h, self.w, 3), dtype=torch.int16, device=dev)
+        for t in (out, s01):
+            self._check_device(t, 'output buffer')
+            if t.dtype not in U16_DTYPES:
+                raise ValueError('run_windows_u16: the output buffers hold 16-bit values (torch.int16), got %s' % t.dtype)
+        io = [self._u16_io(windows_u16[i], out[i], s01[i], depth) for i in range(n)]
+        t_dev = None
+        if ts is not None:                           # padded to whole chunks of n_ctx with the window's last t, as the Y4M edge does
+            njp = -(-nj // self.n_ctx) * self.n_ctx if self.tb else nj
+            tt = np.empty((n, max(njp, 1)), np.float32)
+            for w, t in enumerate(ts):
+                tt[w, :len(t)] = t
+                tt[w, len(t):] = t[-1]
+            t_dev = torch.from_numpy(tt).to(dev)
+        cur = self._begin()
+        for w, (load, emit, pre) in enumerate(io):
+            if t_dev is None:
+                self._window(load, emit, body_only=True, pre=pre)
+            else:
+                self._window(load, emit, body_only=True, pre=pre, t_dev=t_dev[w], nt=len(ts[w]))
+        self._end(cur)
+        return out, s01
+
     # ---------------------------------------------------------------------------------------------------------
     def run_clip_u8(self, host_frames, windows, sink=None, batch=4, reuse_frames=True, yuv=None, window_index=None):
         """Host-to-host run of a list of windows: the counterpart of the test_custom loop (/root/reference/main.py:
@@ -516,17 +588,23 @@ class WindowRunner:
         ``scene.window_runs``, a cut window as two runs.  The cuts found are in ``last_cuts``; ``cut_windows`` counts the cut
         windows.
         A runner of ``tiles``: the frames (and payloads) have the plan's size, every run is one run per tile, and
-        ``instants_run`` / ``instants_padded`` count those.  Returns the number of windows run."""
+        ``instants_run`` / ``instants_padded`` count those.
+        ``yuv.depth`` > 8 (10, 12, 14, 16): the payloads hold 16-bit little-endian samples (host_frames[i] is still a 1-D
+        uint8 tensor, of twice the bytes, and so are the payloads the sink gets); the frame slots and everything between the
+        two conversions are 16-bit (csrc/yuv16.hip, ``_u16_io``).  Not with ``tiles``.  Returns the number of windows run."""
         cuts, full = getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False))
+        depth = int(getattr(yuv, 'depth', 8))
+        if depth > 8 and self.tiles is not None:
+            raise ValueError('WindowRunner.run_clip_u8: tiles move 8-bit pixels; a %d-bit stream cannot run tiled' % depth)
         if self.retime is not None and yuv is None:
             raise ValueError('WindowRunner.run_clip_u8: a retimed runner needs the Y4M edge (yuv=...)')
         if cuts and (self.retime is None or not reuse_frames):
             raise ValueError('WindowRunner.run_clip_u8: scene cuts need a retimed runner (r = M for x M) and reuse_frames')
         if full and (self.retime is None or window_index is None):
             raise ValueError('WindowRunner.run_clip_u8: the full-length timeline needs a retimed runner and window_index')
-        if self._pipeline is None or self._pipeline.key != (batch, yuv is not None, cuts, full):
+        if self._pipeline is None or self._pipeline.key != (batch, yuv is not None, cuts, full, depth):
             self._pipeline = None                        # release the old buffers before the new ones are allocated
-            self._pipeline = ClipPipeline(self, batch, yuv is not None, cuts, full)
+            self._pipeline = ClipPipeline(self, batch, yuv is not None, cuts, full, depth)
         return self._pipeline.run(host_frames, windows, sink, reuse_frames, yuv, window_index)
 
     def __del__(self):

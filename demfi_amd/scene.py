@@ -8,6 +8,8 @@ p_j is the raw 4:2:0 payload of frame j (all Y, Cb, Cr bytes; P of them).  For j
   score_j = min(mafd_j, |mafd_j - mafd_{j-1}|),
 and a cut lies before frame j iff score_j >= T.  This has the shape of ffmpeg's ``scdet`` filter (the mean absolute frame
 difference and how much it changed), so T is picked the same way; numeric equality with it is not claimed.
+At bit depth d > 8 (``y4m``: 16-bit samples) everything counts samples, not bytes: SAD_j sums over the P samples and
+mafd_j = 100 * SAD_j / (peak * P) with peak = 2^d - 1, so a threshold T means the same picture change at every depth.
 
 scene(i) = number of cuts before frames 1 .. i.  Window k is
   * an inner window when scene(k+1) == scene(k+2): it runs its usual instants and outputs on the clamped tuple
@@ -44,40 +46,44 @@ def check_threshold(t):
 
 
 def sad_np(a, b):
-    """SAD of two payloads (uint8 arrays of the same length): sum |a - b| as a Python int."""
-    a, b = np.asarray(a, np.uint8).reshape(-1), np.asarray(b, np.uint8).reshape(-1)
+    """SAD of two payloads (uint8 arrays of the same length, or uint16 arrays of samples): sum |a - b| as a Python int."""
+    if all(isinstance(x, np.ndarray) and x.dtype == np.uint16 for x in (a, b)):
+        a, b, wide = a.reshape(-1), b.reshape(-1), np.int32
+    else:
+        a, b, wide = np.asarray(a, np.uint8).reshape(-1), np.asarray(b, np.uint8).reshape(-1), np.int16
     if a.shape != b.shape:
-        raise ValueError('sad_np: payloads of %d and %d bytes' % (a.size, b.size))
-    return int(np.abs(a.astype(np.int16) - b.astype(np.int16)).sum(dtype=np.int64))
+        raise ValueError('sad_np: payloads of %d and %d samples' % (a.size, b.size))
+    return int(np.abs(a.astype(wide) - b.astype(wide)).sum(dtype=np.int64))
 
 
-def mafd(sad, payload):
-    return 100.0 * int(sad) / (255 * int(payload))
+def mafd(sad, payload, peak=255):
+    """100 * SAD / (peak * payload): ``payload`` counts samples, ``peak`` is the largest sample value (2^d - 1)."""
+    return 100.0 * int(sad) / (int(peak) * int(payload))
 
 
-def scores(sads, payload):
+def scores(sads, payload, peak=255):
     """score_1 .. score_{n-1} from SAD_1 .. SAD_{n-1} of a whole stream."""
     out, prev = [], 0.0
     for s in sads:
-        m = mafd(s, payload)
+        m = mafd(s, payload, peak)
         out.append(min(m, abs(m - prev)))
         prev = m
     return out
 
 
-def cuts_of(sads, payload, threshold):
+def cuts_of(sads, payload, threshold, peak=255):
     """Frame indices j that start a scene (a cut before j), from SAD_1 .. SAD_{n-1} of a whole stream."""
-    return [j for j, s in enumerate(scores(sads, payload), 1) if s >= threshold]
+    return [j for j, s in enumerate(scores(sads, payload, peak), 1) if s >= threshold]
 
 
 class Detector:
     """The cuts of a stream as its SADs arrive in frame order: ``push(j, SAD_j)`` for consecutive j.  ``first`` is the first frame
     read: mafd_0 = 0 is known when it is 0; otherwise the first SAD pushed (SAD_{first+1}) only supplies mafd_{first+1}, and cuts
     are decided from frame first + 2 on -- a rank whose block starts at window lo >= 1 reads from frame lo - 1, which decides every
-    cut its windows look at (j >= lo + 1) as one rank over the whole stream would."""
+    cut its windows look at (j >= lo + 1) as one rank over the whole stream would.  ``payload`` / ``peak``: as ``mafd``."""
 
-    def __init__(self, payload, threshold, first=0):
-        self.payload, self.threshold = int(payload), check_threshold(threshold)
+    def __init__(self, payload, threshold, first=0, peak=255):
+        self.payload, self.threshold, self.peak = int(payload), check_threshold(threshold), int(peak)
         self.next = first + 1
         self.prev = 0.0 if first == 0 else None
         self.cuts = []
@@ -86,7 +92,7 @@ class Detector:
     def push(self, j, sad):
         if j != self.next:
             raise RuntimeError('scene.Detector: SAD of frame %d pushed where frame %d was due' % (j, self.next))
-        m = mafd(sad, self.payload)
+        m = mafd(sad, self.payload, self.peak)
         if self.prev is not None and min(m, abs(m - self.prev)) >= self.threshold:
             self.cuts.append(j)
             self._cut.add(j)

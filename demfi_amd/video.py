@@ -20,6 +20,13 @@ runner's BGR frame slots, and every computed batch is gathered back into a strea
 it for r = F_out / F_in, and ``--mfi M`` is r = M.  One rank reads a stream (stdin included) in bounded batches and writes each batch
 as it drains; under ``torch.distributed.run`` every rank takes ``dist.shard_windows``' block of a regular file and writes its
 frames at their byte offsets of the output file (no collective on the data path).
+
+``--high-depth`` also takes 10-, 12-, 14- and 16-bit 4:2:0 (C420p10 .. C420p16: 16-bit little-endian samples, what
+``ffmpeg -pix_fmt yuv420p10le -strict -1 -f yuv4mpegpipe`` writes) and gives the output at the input's depth: the same path on
+16-bit frames (csrc/yuv16.hip, ``y4m.yuv420_to_bgr16_np`` / ``y4m.bgr16_to_yuv420_np``) from the payload to the network's input and
+from its fp32 output frames back; only the fused uint8 store of the fp16 engine is replaced by one egress kernel per frame.
+With ``--dtype fp16`` the network's input record and features are fp16, which resolves 10-bit video fully and about 12 bits at
+best near the ends of the range; ``--dtype fp32`` carries all 16 bits.
 """
 import os
 import sys
@@ -39,9 +46,11 @@ from .clip import ClipRunner
 class YuvEdge:
     """Y4M edge of ``WindowRunner.run_clip_u8``: conversion parameters of the stream (library codes), ``with_s1(k)``: does
     window k (index in the runner's window sequence) close the stream, i.e. is its S1 written?  ``scene_cut``: None, or the
-    threshold T of scene-cut detection (``demfi_amd.scene``).  ``full_length``: the full-length timeline (``retime``)."""
+    threshold T of scene-cut detection (``demfi_amd.scene``).  ``full_length``: the full-length timeline (``retime``).
+    ``depth``: bits per sample, 8, or 10 / 12 / 14 / 16 for payloads of 16-bit samples."""
 
-    def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False):
+    def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8):
+        self.depth = y4m.check_depth(depth)
         self.matrix = {'bt601': L.BT601, 'bt709': L.BT709}[matrix]
         self.full_range = bool(full_range)
         self.siting = {'420jpeg': L.SITING_420JPEG, '420mpeg2': L.SITING_420MPEG2}[siting]
@@ -61,10 +70,12 @@ class VideoRunner:
     slots), ``last_st_frames`` = St frames written, ``last_cuts`` = the frames j that start a scene and ``last_cut_windows`` =
     the windows run as cut windows, of this rank.  ``tile``: None, 'auto' or (th, tw): frames run as overlapping tiles
     (``demfi_amd.tiling``, ``tile_margin`` pixels thrown away next to every cut); ``last_plan`` is the plan of the last input, None
-    when it ran untiled, and ``last_instants`` then counts per tile."""
+    when it ran untiled, and ``last_instants`` then counts per tile.  ``high_depth``: also take 10- to 16-bit 4:2:0 input
+    (C420p10 / C420p12 / C420p14 / C420p16) and give the output at the input's depth (``last_depth``); off by default, and an
+    8-bit stream gives the same bytes either way.  Not together with ``tile`` (tiles move 8-bit pixels)."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
-                 tile_margin=T.DEFAULT_MARGIN, **runner_kw):
+                 tile_margin=T.DEFAULT_MARGIN, high_depth=False, **runner_kw):
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
         if mfi is not None and fps is not None:
@@ -79,6 +90,10 @@ class VideoRunner:
         self.model, self.n_tst, self.mfi, self.batch, self.matrix = model, n_tst, mfi, batch, matrix
         self.scene_cut = S.check_threshold(scene_cut) if scene_cut is not None else None
         self.full_length = bool(full_length)
+        self.high_depth = bool(high_depth)
+        self.depths = y4m.DEPTHS if self.high_depth else (8,)
+        self.tile = tile
+        self.last_depth = 8
         if tile is not None:
             T.plan_tiles(64, 64, tile, tile_margin)      # a bad tile or margin fails here, not at the first frame
         self.runner_kw = dict(runner_kw, tile=tile, tile_margin=tile_margin)
@@ -102,6 +117,13 @@ class VideoRunner:
 
     def _n_out(self, n_in, hdr):
         return R.n_output_frames(n_in, self._ratio(hdr), self.full_length)
+
+    def _check_depth(self, hdr):
+        """Before anything is allocated for this input: a stream above 8 bits cannot run as tiles."""
+        if hdr.depth > 8 and self.tile is not None:
+            raise ValueError('VideoRunner: tile=%r with a %d-bit stream (C%s): tiles move 8-bit pixels, so --tile and high bit '
+                             'depth do not go together yet; run it untiled, or convert the input to 8 bits' % (self.tile, hdr.depth, hdr.ctag))
+        self.last_depth = hdr.depth
 
     def _clip_runner(self, hdr, world, rank):
         r = self._ratio(hdr)
@@ -130,13 +152,14 @@ class VideoRunner:
 
     def _edge(self, hdr, with_s1):
         return YuvEdge(y4m.auto_matrix(hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
-                       self.scene_cut, self.full_length)
+                       self.scene_cut, self.full_length, hdr.depth)
 
     def run_stream(self, src, dst):
         """One rank, sequential binary streams (stdin / stdout work): nothing is seeked, the input is read in batches of
         windows and every batch is written (and flushed) as it drains.  Returns (windows, frames written)."""
-        rd = y4m.Reader(src)
+        rd = y4m.Reader(src, self.depths)
         hdr = rd.header
+        self._check_depth(hdr)
         cr = self._clip_runner(hdr, 1, 0)
         wr = y4m.Writer(dst, self._out_header(hdr))
         frames = y4m.Frames(rd, full_length=self.full_length)
@@ -161,7 +184,8 @@ class VideoRunner:
         (``dist.shard_windows``), its frames written at ``header + i*(6 + payload)``.  Rank 0 writes the header and sizes the
         output file; all ranks meet at a barrier before writing.  Returns (windows, frames written) of this rank."""
         with open(in_path, 'rb') as f:
-            hdr, _, offs = y4m.scan(f)
+            hdr, _, offs = y4m.scan(f, self.depths)
+            self._check_depth(hdr)
             n_in = len(offs)
             ohdr = self._out_header(hdr)
             hb = ohdr.encode()
@@ -216,7 +240,9 @@ def parser():
     import argparse
     ap = argparse.ArgumentParser(prog='python -m demfi_amd.video', description=main.__doc__.split('\n\n')[0],
                                  epilog='Input: 8-bit 4:2:0 progressive Y4M (C420jpeg, C420, C420mpeg2; XCOLORRANGE=FULL|LIMITED), '
-                                        'e.g. ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe -.  Output: C420jpeg, the input\'s '
+                                        'e.g. ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe -; with --high-depth also 10- to 16-bit '
+                                        '4:2:0 (C420p10, C420p12, C420p14, C420p16), e.g. ffmpeg -i in.mkv -pix_fmt yuv420p10le -strict -1 '
+                                        '-f yuv4mpegpipe -.  Output: C420jpeg (C420pNN at the input\'s depth), the input\'s '
                                         'matrix and range.  n input frames give (n-3)*M + 1 output frames: the first and the last '
                                         'input frame have no output, as in the reference (--full-length: n*M frames from input '
                                         'frame 0 on).  All logging goes to stderr.')
@@ -241,6 +267,10 @@ def parser():
                     help='cover the input\'s whole timeline: output frame 0 is input frame 0 and n input frames give ceil(n*F_out/F_in) '
                          'output frames (n*M with --mfi), the last input frame held to the end, so the video stays aligned with its '
                          'audio.  Off by default (the reference\'s timeline)')
+    ap.add_argument('--high-depth', action='store_true',
+                    help='also take 10-, 12-, 14- and 16-bit 4:2:0 (C420p10 .. C420p16, 16-bit little-endian samples) and write the '
+                         'output at the input\'s depth, through a 16-bit frame path; --dtype fp16 resolves 10 bits fully and about 12 at '
+                         'best, --dtype fp32 all 16.  Not with --tile.  Off by default (8-bit input only)')
     T.add_arguments(ap)
     return ap
 
@@ -277,7 +307,7 @@ def main(argv=None):
     model = model.to(dev).eval()
     D.broadcast_state_dict(model, world, device=dev)
     vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut, full_length=a.full_length,
-                     tile=a.tile, tile_margin=a.tile_margin)
+                     tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth)
     t0 = time.perf_counter()
     if world > 1:
         nw, nf = vr.run_file(a.input, a.output, world, rank)
@@ -305,7 +335,7 @@ def main(argv=None):
                           'fps_out': str(vr.last_fps_out) if vr.last_fps_out is not None else None,
                           'instants_run': int(ti), 'instants_padded': int(tp), 'cut_windows': int(tc),
                           'tiles': vr.last_plan.n_tiles if vr.last_plan is not None else 1,
-                          'tile': vr.last_plan.label() if vr.last_plan is not None else None,
+                          'tile': vr.last_plan.label() if vr.last_plan is not None else None, 'depth': vr.last_depth,
                           'weights': os.path.basename(a.checkpoint) if a.checkpoint else 'synthetic_state_dict(0) (random init: no checkpoint given)',
                           'out': a.output}), file=sys.stderr)
     D.finalize()

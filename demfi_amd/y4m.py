@@ -14,6 +14,14 @@ and Cr planes [ceil(h/2), ceil(w/2)], 1.5 bytes per pixel.
     edge the clamped neighbour repeats the pixel that exists, i.e. the 2 or 1 pixels there are averaged.
 Frames are uint8 [h,w,3] in B, G, R order, the frame order of the whole pipeline (cv2's).
 
+High bit depth (opt-in: ``depths=DEPTHS``, ``python -m demfi_amd.video --high-depth``): the tags C420p10 / C420p12 / C420p14 /
+C420p16 carry unsigned 16-bit little-endian samples holding 0 .. 2^d - 1 = peak, so a payload has twice the bytes;
+``Header.payload`` counts bytes.  ``yuv420_to_bgr16_np`` / ``bgr16_to_yuv420_np`` define the conversion at depth d (the HIP kernels
+of csrc/yuv16.hip match them bit for bit) as the 8-bit pair generalised: with s = 2^(d-8), limited range is Y 16s .. 235s and
+C 16s .. 240s, the Y offset 16s, the chroma centre 2^(d-1), the scale factors peak / (219 s) and peak / (224 s) (and their
+inverses); coefficients are rounded half up to Q(8+d), accumulators are 64-bit, results clamp to [0, peak].  d = 8 is the
+8-bit pair exactly.  Frames are then uint16 [h,w,3] B, G, R with values 0 .. peak.
+
 Two timelines: by default n input frames give (n-3)*M + 1 output frames and the first and last input frames have no output
 (``n_output_frames``); on the full-length timeline (``Frames(full_length=True)``, ``retime``) output frame 0 is input frame 0
 and n frames give n*M, windows running from k = -1 on tuples clamped at the clip's ends.
@@ -32,6 +40,8 @@ MAX_SIDE = 16384
 FIX = "convert the input with ffmpeg's -pix_fmt yuv420p (progressive 8-bit 4:2:0), e.g. ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe -"
 MATRICES = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}       # (Kr, Kb)
 SITINGS = ('420jpeg', '420mpeg2')
+DEPTHS = (8, 10, 12, 14, 16)                                          # what ``depths=DEPTHS`` (--high-depth) accepts
+HIGH_DEPTH_HINT = '; or keep the bit depth: --high-depth accepts 10- to 16-bit 4:2:0 (C420p10, C420p12, C420p14, C420p16)'
 _CHROMA = {None: '420jpeg', '420jpeg': '420jpeg', '420': '420jpeg', '420mpeg2': '420mpeg2'}
 _MAX_LINE = 4096
 
@@ -139,6 +149,108 @@ def bgr_to_yuv420_np(bgr, matrix='bt601', full_range=False):
     return np.concatenate([y.reshape(-1), down(kcb).reshape(-1), down(kcr).reshape(-1)]).astype(np.uint8)
 
 
+# ---- the conversion at depth d: 16-bit samples -------------------------------------------------------------------------------
+def check_depth(depth):
+    if depth not in DEPTHS:
+        raise ValueError('bit depth must be one of %s, got %r' % (DEPTHS, depth))
+    return depth
+
+
+def _fixq(c, q):
+    return int(math.floor(c * float(1 << q) + 0.5))
+
+
+def to_bgr_coefs_depth(matrix, full_range, depth):
+    """``to_bgr_coefs`` at depth d: Q(8+d) coefficients, Y offset 16 s (s = 2^(d-8)); d = 8 gives ``to_bgr_coefs``."""
+    kr, kb = _kr_kb(matrix)
+    kg = 1.0 - kr - kb
+    q, s, peak = 8 + depth, 1 << (depth - 8), (1 << depth) - 1
+    ys, cs = (1.0, 1.0) if full_range else (peak / (219.0 * s), peak / (224.0 * s))
+    return (_fixq(ys, q), _fixq(cs * 2.0 * (1.0 - kr), q), _fixq(-(cs * 2.0 * kb * (1.0 - kb) / kg), q),
+            _fixq(-(cs * 2.0 * kr * (1.0 - kr) / kg), q), _fixq(cs * 2.0 * (1.0 - kb), q)), (0 if full_range else 16 * s)
+
+
+def to_yuv_coefs_depth(matrix, full_range, depth):
+    """``to_yuv_coefs`` at depth d: Q(8+d) rows (Y, Cb, Cr) x (R, G, B), Y offset 16 s (the chroma offset is 2^(d-1))."""
+    kr, kb = _kr_kb(matrix)
+    kg = 1.0 - kr - kb
+    q, s, peak = 8 + depth, 1 << (depth - 8), (1 << depth) - 1
+    ys, cs = (1.0, 1.0) if full_range else (219.0 * s / peak, 224.0 * s / peak)
+    return ((_fixq(ys * kr, q), _fixq(ys * kg, q), _fixq(ys * kb, q)),
+            (_fixq(-(cs * kr / (2.0 * (1.0 - kb))), q), _fixq(-(cs * kg / (2.0 * (1.0 - kb))), q), _fixq(cs * 0.5, q)),
+            (_fixq(cs * 0.5, q), _fixq(-(cs * kg / (2.0 * (1.0 - kr))), q), _fixq(-(cs * kb / (2.0 * (1.0 - kr))), q))), \
+        (0 if full_range else 16 * s)
+
+
+def payload_bytes(h, w, depth=8):
+    """Bytes of one 4:2:0 payload: ``payload_size`` samples of one byte at depth 8, of two above."""
+    return payload_size(h, w) * (2 if depth > 8 else 1)
+
+
+def as_samples16(payload):
+    """A payload of 16-bit little-endian samples (bytes-like, a uint8 array or a uint16 array) -> 1-D uint16 view."""
+    if isinstance(payload, np.ndarray) and payload.dtype == np.uint16:
+        return payload.reshape(-1)
+    a = np.frombuffer(payload, np.uint8) if not isinstance(payload, np.ndarray) else payload.reshape(-1)
+    if a.dtype != np.uint8 or a.size % 2:
+        raise ValueError('a payload of 16-bit samples is an even number of bytes (uint8) or a uint16 array, got %s x %d' % (a.dtype, a.size))
+    return a.view('<u2')
+
+
+def split_planes16(payload, h, w):
+    """16-bit Y4M payload -> (Y [h,w], Cb, Cr [ceil(h/2), ceil(w/2)]) uint16 views."""
+    a = as_samples16(payload)
+    ch, cw = (h + 1) // 2, (w + 1) // 2
+    if a.size != payload_size(h, w):
+        raise ValueError('payload of %d samples for a %dx%d 4:2:0 frame (%d expected)' % (a.size, h, w, payload_size(h, w)))
+    return a[:h * w].reshape(h, w), a[h * w:h * w + ch * cw].reshape(ch, cw), a[h * w + ch * cw:].reshape(ch, cw)
+
+
+def yuv420_to_bgr16_np(payload, h, w, depth, matrix='bt601', full_range=False, siting='420jpeg'):
+    """One 4:2:0 payload of 16-bit samples at depth d -> uint16 BGR [h,w,3], values 0 .. peak (the definition the HIP kernel
+    matches); ``depth`` = 8 (samples 0 .. 255 in the 16-bit container) gives the values of ``yuv420_to_bgr_np``."""
+    check_depth(depth)
+    y, cb, cr = split_planes16(payload, h, w)
+    (cy, r_cr, g_cb, g_cr, b_cb), yoff = to_bgr_coefs_depth(matrix, full_range, depth)
+    mid = (1 << (depth - 1)) * 16
+    yy = (y.astype(np.int64) - yoff) * 16
+    cbv = _upsample16(cb, h, w, siting).astype(np.int64) - mid
+    crv = _upsample16(cr, h, w, siting).astype(np.int64) - mid
+    sh = 8 + depth + 4
+    rnd = np.int64(1 << (sh - 1))
+    r = (cy * yy + r_cr * crv + rnd) >> sh
+    g = (cy * yy + g_cb * cbv + g_cr * crv + rnd) >> sh
+    b = (cy * yy + b_cb * cbv + rnd) >> sh
+    return np.clip(np.stack([b, g, r], -1), 0, (1 << depth) - 1).astype(np.uint16)
+
+
+def bgr16_to_yuv420_np(bgr16, depth, matrix='bt601', full_range=False):
+    """uint16 BGR [h,w,3] at depth d -> one 4:2:0 (420jpeg) payload of 16-bit samples, 1-D uint16 (the definition the HIP
+    kernel matches); ``.view(np.uint8)`` / ``.tobytes()`` of it are the little-endian bytes of the stream."""
+    check_depth(depth)
+    bgr = np.asarray(bgr16)
+    if bgr.dtype != np.uint16 or bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise ValueError('uint16 [h,w,3] expected, got %s %s' % (bgr.dtype, bgr.shape))
+    h, w = bgr.shape[:2]
+    if h < 2 or w < 2:
+        raise ValueError('frame of %dx%d: 2x2 at least' % (h, w))
+    (ky, kcb, kcr), yoff = to_yuv_coefs_depth(matrix, full_range, depth)
+    q, peak, mid = 8 + depth, (1 << depth) - 1, 1 << (depth - 1)
+    b, g, r = (bgr[:, :, i].astype(np.int64) for i in range(3))
+    y = np.clip((ky[0] * r + ky[1] * g + ky[2] * b + (yoff << q) + (1 << (q - 1))) >> q, 0, peak)
+    r0 = np.arange(0, h, 2)
+    r1 = np.minimum(r0 + 1, h - 1)
+    c0 = np.arange(0, w, 2)
+    c1 = np.minimum(c0 + 1, w - 1)
+
+    def down(k):
+        f = k[0] * r + k[1] * g + k[2] * b                   # full-resolution Q(8+d) chroma, centred on 0
+        s = f[r0][:, c0] + f[r0][:, c1] + f[r1][:, c0] + f[r1][:, c1]
+        return np.clip((s + (mid << (q + 2)) + (1 << (q + 1))) >> (q + 2), 0, peak)
+    out = np.concatenate([y.reshape(-1), down(kcb).reshape(-1), down(kcr).reshape(-1)]).astype(np.uint16)
+    return out.astype('<u2', copy=False)
+
+
 def auto_matrix(h):
     """--matrix auto: BT.709 for HD (H >= 720), BT.601 below (what encoders assume for untagged video)."""
     return 'bt709' if h >= 720 else 'bt601'
@@ -148,14 +260,16 @@ def auto_matrix(h):
 class Header:
     """Parsed stream header.  ``chroma``: '420jpeg' | '420mpeg2' (C420 / missing C = 420jpeg); ``full_range`` from
     XCOLORRANGE (default limited); ``fps`` a Fraction; ``aspect`` / ``color_range`` the raw A / XCOLORRANGE values or None;
-    ``xtags`` the other X parameters in order."""
+    ``xtags`` the other X parameters in order.  ``depth``: bits per sample, 8 or (C420pNN) 10 / 12 / 14 / 16, the latter as
+    16-bit little-endian samples; ``payload`` / ``frame_bytes`` are bytes."""
 
-    def __init__(self, w, h, fps, interlace='p', aspect=None, chroma='420jpeg', color_range=None, xtags=(), ctag=None):
+    def __init__(self, w, h, fps, interlace='p', aspect=None, chroma='420jpeg', color_range=None, xtags=(), ctag=None, depth=8):
         self.w, self.h, self.fps = int(w), int(h), Fraction(fps)
         self.interlace, self.aspect, self.chroma = interlace, aspect, chroma
         self.color_range = color_range
         self.xtags = list(xtags)
         self.ctag = ctag
+        self.depth = check_depth(depth)
 
     @property
     def full_range(self):
@@ -163,7 +277,11 @@ class Header:
 
     @property
     def payload(self):
-        return payload_size(self.h, self.w)
+        return payload_bytes(self.h, self.w, self.depth)
+
+    @property
+    def peak(self):
+        return (1 << self.depth) - 1
 
     @property
     def frame_bytes(self):
@@ -186,12 +304,16 @@ class Header:
         return 'Header(%r)' % self.encode()
 
 
-def _reject(what):
-    raise Y4MError('Y4M: %s is not supported: %s' % (what, FIX))
+def _reject(what, hint=''):
+    raise Y4MError('Y4M: %s is not supported: %s%s' % (what, FIX, hint))
 
 
-def parse_header(line):
-    """One header line (bytes, with or without the trailing newline) -> Header.  Raises Y4MError."""
+_DEEP = {'420p%d' % d: d for d in DEPTHS if d > 8}                    # 4:2:0 tags of 16-bit samples (420jpeg siting)
+
+
+def parse_header(line, depths=(8,)):
+    """One header line (bytes, with or without the trailing newline) -> Header.  Raises Y4MError.  ``depths``: the bit depths
+    taken; the default is 8-bit only, ``DEPTHS`` also takes C420p10 / C420p12 / C420p14 / C420p16."""
     if isinstance(line, str):
         line = line.encode()
     line = line.rstrip(b'\n')
@@ -199,7 +321,7 @@ def parse_header(line):
     if toks[0] != MAGIC:
         raise Y4MError('not a YUV4MPEG2 stream (bad magic %r): %s' % (bytes(line[:16]), FIX))
     w = h = fps = None
-    inter, aspect, ctag, crange, xt = 'p', None, None, None, []
+    inter, aspect, ctag, crange, xt, depth = 'p', None, None, None, [], 8
     for t in toks[1:]:
         if not t:
             continue
@@ -223,8 +345,15 @@ def parse_header(line):
         elif tag == 'A':
             aspect = val
         elif tag == 'C':
-            if val not in _CHROMA:
-                _reject('colour space C%s (8-bit 4:2:0 only)' % val)
+            if val in _DEEP:
+                if _DEEP[val] not in depths:
+                    _reject('colour space C%s (8-bit 4:2:0 only)' % val, HIGH_DEPTH_HINT)
+                depth = _DEEP[val]
+            elif val not in _CHROMA:
+                _reject('colour space C%s (%s)' % (val, '8-bit 4:2:0 only' if tuple(depths) == (8,) else
+                                                   '4:2:0 only, %s bits' % ', '.join(str(d) for d in depths)))
+            else:
+                depth = 8
             ctag = val
         elif tag == 'X':
             if val.startswith('COLORRANGE='):
@@ -241,12 +370,18 @@ def parse_header(line):
     for nm, v in (('width', w), ('height', h)):
         if not 2 <= v <= MAX_SIDE:
             raise Y4MError('Y4M: %s %d outside 2..%d' % (nm, v, MAX_SIDE))
-    return Header(w, h, fps, inter, aspect, _CHROMA[ctag], crange, xt, ctag)
+    return Header(w, h, fps, inter, aspect, _CHROMA.get(ctag, '420jpeg'), crange, xt, ctag, depth)
+
+
+def output_ctag(depth):
+    """C tag of an output stream: 420jpeg, or the input's 420pNN (420jpeg siting) above 8 bits."""
+    return '420jpeg' if depth == 8 else '420p%d' % depth
 
 
 def output_header(hdr, mfi):
-    """Header of the x M stream: the input's W H, F x M (reduced), progressive, A copied, C420jpeg, the input's XCOLORRANGE."""
-    return Header(hdr.w, hdr.h, hdr.fps * mfi, 'p', hdr.aspect, '420jpeg', hdr.color_range, (), '420jpeg')
+    """Header of the x M stream: the input's W H, F x M (reduced), progressive, A copied, C420jpeg (C420pNN at the input's depth
+    above 8 bits), the input's XCOLORRANGE."""
+    return Header(hdr.w, hdr.h, hdr.fps * mfi, 'p', hdr.aspect, '420jpeg', hdr.color_range, (), output_ctag(hdr.depth), hdr.depth)
 
 
 # ---- stream order of the x M output ----------------------------------------------------------------------------------------
@@ -262,7 +397,7 @@ def output_index(k, j, mfi):
 
 
 def frame_offset(hdr_len, i, payload):
-    """Byte offset of output frame i in a file written by this module ('FRAME\\n' before every payload)."""
+    """Byte offset of output frame i in a file written by this module ('FRAME\\n' before every payload of ``payload`` bytes)."""
     return hdr_len + i * (len(FRAME) + 1 + payload)
 
 
@@ -293,12 +428,12 @@ def _frame_line(line, index):
 class Reader:
     """Sequential reader of a binary stream (a file, or stdin: nothing is seeked).  ``read_into(buf)`` fills one payload."""
 
-    def __init__(self, f):
+    def __init__(self, f, depths=(8,)):
         self.f = f
         line = _readline(f, 'header')
         if not line:
             raise Y4MError('Y4M: empty input: %s' % FIX)
-        self.header = parse_header(line)
+        self.header = parse_header(line, depths)
         self.header_bytes = len(line)
         self.index = 0                                  # frames read so far
 
@@ -318,11 +453,11 @@ class Reader:
         return True
 
 
-def scan(f):
+def scan(f, depths=(8,)):
     """One pass over the frame headers of a seekable file: (Header, header bytes, [file offset of every payload]).  The
-    payloads are skipped, not read; a truncated last frame raises."""
+    payloads are skipped, not read; a truncated last frame raises.  ``depths``: as ``parse_header``."""
     f.seek(0)
-    rd = Reader(f)
+    rd = Reader(f, depths)
     size = os.fstat(f.fileno()).st_size if hasattr(f, 'fileno') else None
     p = rd.header.payload
     offs = []
@@ -341,8 +476,8 @@ def scan(f):
 
 
 class Frames:
-    """``host_frames`` of ``WindowRunner.run_clip_u8`` over a Y4M input: frame i is its payload (1-D uint8 tensor, pinned when a
-    GPU is present), read with ``readinto`` when first needed and dropped once the windows have moved past it (windows come in
+    """``host_frames`` of ``WindowRunner.run_clip_u8`` over a Y4M input: frame i is its payload (1-D uint8 tensor of the payload's bytes,
+    pinned when a GPU is present), read with ``readinto`` when first needed and dropped once the windows have moved past it (windows come in
     increasing order and read frames k .. k+3).  ``peak`` = frames held at once: bounded by the runner's batch + 5, whatever
     the input's length.
 
@@ -437,7 +572,8 @@ class Writer:
         self.frames = 0
 
     def write(self, payloads):
-        """payloads: uint8 [n, payload] (numpy array / CPU tensor) in stream order."""
+        """payloads: uint8 [n, payload bytes] (numpy array / CPU tensor; uint16 rows are written as they lie in memory) in
+        stream order."""
         for p in payloads:
             self.f.write(FRAME + b'\n')
             self.f.write(memoryview(p.numpy() if hasattr(p, 'numpy') else np.asarray(p)).cast('B'))

@@ -373,6 +373,31 @@ int demfi_bgr_to_yuv420_gather(const uint8_t* base, const int64_t* src_offsets, 
 int demfi_yuv420_sad(const uint8_t* base, const int64_t* a_offsets, const int64_t* b_offsets, int n, int64_t payload, uint64_t* sad,
                      void* stream);
 
+/* ---- the 16-bit frame path of the Y4M edge (csrc/yuv16.hip; demfi_amd/video.py --high-depth) ---------------------------------
+ * The functions above at bit depth d = `depth`, 8 <= d <= 16 (the Y4M tags C420p10 .. C420p16; 8 is accepted so that this path can
+ * be compared with the 8-bit one value for value): samples and B, G, R values are unsigned 16-bit holding 0 .. peak = 2^d - 1,
+ * buffers are 2-byte aligned, and EVERY stride and offset counts 16-bit samples, not bytes.  Integer arithmetic that matches
+ * demfi_amd/y4m.py (yuv420_to_bgr16_np / bgr16_to_yuv420_np) bit for bit: the 8-bit definition with s = 2^(d-8) -- limited range
+ * Y 16s-235s, C 16s-240s, chroma centre 2^(d-1), Q(8+d) coefficients, 64-bit accumulators, one rounding, clamp to [0, peak].
+ * Any h, w in 2..16384; device buffers; one launch for n frames.
+ * yuv420p16_to_bgr16: frame i read at src + i*src_stride ([payload] samples), written at dst + i*dst_stride ([h,w,3]).
+ * bgr16_to_yuv420p16_gather: frame i read at base + src_offsets[i] (n int64 sample offsets in DEVICE memory, any order, repeats
+ * allowed), written at dst + i*dst_stride; output chroma is 420jpeg.
+ * yuv420p16_sad: sad[i] = sum over `samples` samples of |a - b|, a at base + a_offsets[i], b at base + b_offsets[i] (sample
+ * offsets in DEVICE memory), exact in uint64; sad is zeroed on the stream first (demfi_amd/scene.py: sad_np on uint16 arrays).
+ * u16_ingest: demfi_u8_ingest for 4 BGR uint16 [h,w,3] frames: v = p / peak, v -= 0.5, v *= 2 in fp32, the same reflect padding
+ * and the same three outputs.  frame_to_u16: demfi_frame_to_u8 with peak in place of 255: float64 clip((x + 1) / 2, 0, 1) * peak,
+ * truncated. */
+int demfi_yuv420p16_to_bgr16(const uint16_t* src, int64_t src_stride, uint16_t* dst, int64_t dst_stride, int n, int h, int w, int depth,
+                             int matrix, int full_range, int siting, void* stream);
+int demfi_bgr16_to_yuv420p16_gather(const uint16_t* base, const int64_t* src_offsets, uint16_t* dst, int64_t dst_stride, int n, int h,
+                                    int w, int depth, int matrix, int full_range, void* stream);
+int demfi_yuv420p16_sad(const uint16_t* base, const int64_t* a_offsets, const int64_t* b_offsets, int n, int64_t samples, uint64_t* sad,
+                        void* stream);
+int demfi_u16_ingest(const uint16_t* const* frames, int h, int w, int depth, float* x, void* s2d, float* overlay, int dtype, int H,
+                     int W, void* stream);
+int demfi_frame_to_u16(const float* frame, uint16_t* out, int h, int w, int H, int W, int depth, void* stream);
+
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
  * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
@@ -522,6 +547,8 @@ int     demfi_ctx_buffer(const demfi_ctx* ctx, int trunk, int c, const char* nam
  * reshuffle in one kernel); follow it with demfi_forward_trunk_body.  The per-t context's buffer "sink" is a
  * demfi_u8_sink record: fill it (device memory) before demfi_forward_t and the last layer writes uint8 frames directly. */
 int     demfi_ingest_u8(demfi_ctx* ctx, int trunk, const uint8_t* const* frames, int h, int w, void* stream);
+/* the same for 4 BGR uint16 [h,w,3] frames at bit depth `depth` (demfi_u16_ingest) */
+int     demfi_ingest_u16(demfi_ctx* ctx, int trunk, const uint16_t* const* frames, int h, int w, int depth, void* stream);
 int     demfi_forward_trunk_body(demfi_ctx* ctx, int trunk, void* stream);
 /* t-independent segment (FF_RDB + FAC-FB, DeMFInet.py:59, 74) of trunk context `trunk`; x: device fp32 [3,4,H,W]
  * copied into the context's input buffer first, or NULL when the caller already filled buffer "x". */
