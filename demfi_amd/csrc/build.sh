@@ -18,6 +18,7 @@ SRCS_CPP="abi.cpp"
 [ -f viz.hip ] && SRCS_HIP="$SRCS_HIP viz.hip"
 [ -f yuv.hip ] && SRCS_HIP="$SRCS_HIP yuv.hip"
 [ -f yuv16.hip ] && SRCS_HIP="$SRCS_HIP yuv16.hip"
+[ -f yuv_layouts.hip ] && SRCS_HIP="$SRCS_HIP yuv_layouts.hip"
 [ -f tile.hip ] && SRCS_HIP="$SRCS_HIP tile.hip"
 [ -f wsconv.hip ] && SRCS_HIP="$SRCS_HIP wsconv.hip"
 [ -f ctx.cpp ] && SRCS_CPP="$SRCS_CPP ctx.cpp"

@@ -1,5 +1,5 @@
 """Host-to-host clip pipeline behind ``WindowRunner.run_clip_u8``: a ring of device frame slots (``FrameSlots``), one edge object
-per output format (``BgrEdge``: BGR frames in and out; ``Y4mEdge``: 4:2:0 payloads in and out, every window on its own plan)
+per output format (``BgrEdge``: BGR frames in and out; ``Y4mEdge``: Y4M payloads in and out, every window on its own plan)
 and the double-buffered batch loop that drives them (``ClipPipeline``).  An edge has the same few methods whatever its format:
 ``upload`` one frame into a slot and ``uploaded`` after a batch's copies (h2d stream), ``run`` a batch (compute stream), ``d2h``
 its outputs to pinned memory (d2h stream) and ``drain`` them to the sink; what ``run`` returns is handed back to ``d2h`` / ``drain``.
@@ -179,24 +179,27 @@ class BgrEdge:
 
 
 class Y4mEdge:
-    """4:2:0 payloads in; sink(k, payloads [c, P]) out, the c output frames window k owns in stream order.  Window k runs the
+    """Y4M payloads in; sink(k, payloads [c, P]) out, the c output frames window k owns in stream order.  Window k runs the
     instants of ``retime.window_plan`` for the runner's ratio (x M is r = M), with ``cuts`` those of ``scene.window_runs`` (a
     cut window is two runs); run w of a batch writes its frames to comb[i][w] = [S0, St x J, S1], J = ceil(r), and one gather
     launch per batch puts the outputs in stream order.  ``full``: the full-length timeline of ``retime``.
     ``depth`` > 8: payloads of 16-bit samples at that bit depth.  The payload buffers stay uint8 tensors sized in bytes (what the
     host hands over and gets back); the frame slots and ``comb`` are int16 storage of the uint16 frames, the three launches
-    are those of csrc/yuv16.hip (strides and offsets in samples), the egress is the emit path and the SADs count samples."""
+    are those of csrc/yuv16.hip (strides and offsets in samples), the egress is the emit path and the SADs count samples.
+    ``layout``: the payloads' chroma layout (``y4m.LAYOUTS``): it sets P, and for 4:2:2, 4:4:4 and mono the two conversion
+    launches are those of csrc/yuv_layouts.hip; everything between them sees BGR frames."""
 
-    def __init__(self, runner, batch, slots, cuts, full, tiler=None, depth=8):
+    def __init__(self, runner, batch, slots, cuts, full, tiler=None, depth=8, layout='420'):
         self.rn, self.slots, self.cuts, self.full, self.tiler = runner, slots, cuts, full, tiler
         self.depth, self.hi = depth, depth > 8
+        self.layout, self.lcode = layout, L.YUV_LAYOUT[layout]
         if self.hi and tiler is not None:
             raise ValueError('Y4mEdge: tiles move 8-bit pixels; a %d-bit stream cannot run tiled' % depth)
         es, fdt = (2, torch.int16) if self.hi else (1, torch.uint8)      # bytes per sample; storage of a frame value
         self.r = runner.retime if runner.retime is not None else Fraction(runner.mfi)
         h, w = self.fh, self.fw = (tiler.h, tiler.w) if tiler else (runner.h, runner.w)
         dev, nsl = runner.engine.device, len(slots.frames)
-        P, J = self.P, self.J = payload_size(h, w), R.max_instants(self.r)
+        P, J = self.P, self.J = payload_size(h, w, layout), R.max_instants(self.r)
         nJ = -(-J // runner.n_ctx) * runner.n_ctx if runner.tb else J    # instants incl. the padding of a short chunk
         runs_max = 2 * batch if cuts else batch                          # a cut window is two runs
         # payloads of a batch: at most J per window, plus the last window's S1 (full-length: its [n-2, n) span, 2 J)
@@ -231,13 +234,22 @@ class Y4mEdge:
 
     def upload(self, sl, idx, f):
         if tuple(f.shape) != (self.Pb,) or f.dtype != torch.uint8:
-            raise ValueError('frame %d: expected a uint8 [%d] 4:2:0 payload, got %s %s' % (idx, self.Pb, f.dtype, tuple(f.shape)))
+            raise ValueError('frame %d: expected a uint8 [%d] %s payload, got %s %s' % (idx, self.Pb, self.layout, f.dtype, tuple(f.shape)))
         self.yuv_in[sl].copy_(f, non_blocking=True)
 
     def uploaded(self, new, h2d):
         """Payloads copied to yuv_in[slot] -> BGR frame slots, one launch per run of consecutive slots; then the SADs."""
         rn, yuv, sls = self.rn, self.yuv, [sl for _, sl in new]
         for s0, cnt in consecutive(sls):
+            if self.lcode:                           # 4:2:2, 4:4:4, mono: strides in samples (16-bit) / bytes
+                src, dst, F = self.yuv_in[s0].data_ptr(), self.slots.frames[s0].data_ptr(), self.fh * self.fw * 3
+                if self.hi:
+                    L.check(rn.lib.demfi_yuvl16_to_bgr16(src, self.P, dst, F, cnt, self.fh, self.fw, self.depth, self.lcode, yuv.matrix,
+                                                         int(yuv.full_range), h2d.cuda_stream), 'yuvl16_to_bgr16')
+                else:
+                    L.check(rn.lib.demfi_yuvl_to_bgr(src, self.P, dst, F, cnt, self.fh, self.fw, self.lcode, yuv.matrix,
+                                                     int(yuv.full_range), h2d.cuda_stream), 'yuvl_to_bgr')
+                continue
             if self.hi:                              # strides in samples
                 L.check(rn.lib.demfi_yuv420p16_to_bgr16(self.yuv_in[s0].data_ptr(), self.P, self.slots.frames[s0].data_ptr(),
                                                         self.fh * self.fw * 3, cnt, self.fh, self.fw, self.depth, yuv.matrix,
@@ -354,6 +366,15 @@ class Y4mEdge:
             raise RuntimeError('retime: %d outputs for %d payload slots' % (nf, dst.shape[0]))
         od = self.offs[i][:nf]
         od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
+        if self.lcode:                               # 4:2:2, 4:4:4, mono; the payload stride P counts samples (16-bit) / bytes
+            if self.hi:
+                L.check(rn.lib.demfi_bgr16_to_yuvl16_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), self.P, nf, self.fh, self.fw,
+                                                            self.depth, self.lcode, yuv.matrix, int(yuv.full_range), cur.cuda_stream),
+                        'bgr16_to_yuvl16_gather')
+            else:
+                L.check(rn.lib.demfi_bgr_to_yuvl_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), self.P, nf, self.fh, self.fw,
+                                                        self.lcode, yuv.matrix, int(yuv.full_range), cur.cuda_stream), 'bgr_to_yuvl_gather')
+            return [len(o) for o in outs]
         if self.hi:                                  # comb's element strides are samples; so is the payload stride
             L.check(rn.lib.demfi_bgr16_to_yuv420p16_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), self.P, nf, self.fh, self.fw,
                                                            self.depth, yuv.matrix, int(yuv.full_range), cur.cuda_stream),
@@ -379,10 +400,10 @@ class ClipPipeline:
     cuts / the full-length timeline, which size its buffers): H2D of a batch's new frames, its compute, the drain of the
     previous batch and its D2H, on three streams over two sets of output buffers."""
 
-    def __init__(self, runner, batch, y4m, cuts, full, depth=8):
+    def __init__(self, runner, batch, y4m, cuts, full, depth=8, layout='420'):
         dev = self.dev = runner.engine.device
         runner = weakref.proxy(runner)               # the runner owns this pipeline: no reference cycle keeps its buffers alive
-        self.batch, self.key = batch, (batch, y4m, cuts, full, depth)   # what a cached pipeline can be reused for
+        self.batch, self.key = batch, (batch, y4m, cuts, full, depth, layout)   # what a cached pipeline can be reused for
         if depth > 8 and not y4m:
             raise ValueError('ClipPipeline: 16-bit frames are those of the Y4M edge only')
         self.h2d, self.d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
@@ -393,7 +414,7 @@ class ClipPipeline:
         if plan is not None:                         # frames stitched per batch: a run's J + 2 (a cut window is two runs), or M + 1
             J2 = (R.max_instants(runner.retime if runner.retime is not None else Fraction(runner.mfi)) + 2) if y4m else runner.mfi + 1
             tiler = Tiler(plan, self.slots, runner.lib, dev, (2 * batch if cuts else batch) * J2)
-        self.edge = Y4mEdge(runner, batch, self.slots, cuts, full, tiler, depth) if y4m else BgrEdge(runner, batch, self.slots, tiler)
+        self.edge = Y4mEdge(runner, batch, self.slots, cuts, full, tiler, depth, layout) if y4m else BgrEdge(runner, batch, self.slots, tiler)
 
     def run(self, host_frames, windows, sink, reuse_frames, yuv, window_index):
         it = iter(windows)

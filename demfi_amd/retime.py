@@ -150,9 +150,10 @@ def max_instants(r):
 
 def output_header(hdr, fps_out):
     """Header of the retimed stream: the input's W H, F = F_out (reduced), progressive, A copied, C420jpeg (C420pNN at the input's
-    depth above 8 bits), the input's XCOLORRANGE -- the fields of ``y4m.output_header``."""
-    return y4m.Header(hdr.w, hdr.h, Fraction(fps_out), 'p', hdr.aspect, '420jpeg', hdr.color_range, (), y4m.output_ctag(hdr.depth),
-                      hdr.depth)
+    depth above 8 bits; the input's layout and depth for 4:2:2, 4:4:4 and mono), the input's XCOLORRANGE -- the fields of
+    ``y4m.output_header``."""
+    return y4m.Header(hdr.w, hdr.h, Fraction(fps_out), 'p', hdr.aspect, '420jpeg', hdr.color_range, (),
+                      y4m.output_ctag(hdr.depth, hdr.layout), hdr.depth, hdr.layout)
 
 
 def block_offset(hdr_len, first_window, r, payload, full_length=False):

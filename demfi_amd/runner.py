@@ -591,9 +591,11 @@ class WindowRunner:
         ``instants_run`` / ``instants_padded`` count those.
         ``yuv.depth`` > 8 (10, 12, 14, 16): the payloads hold 16-bit little-endian samples (host_frames[i] is still a 1-D
         uint8 tensor, of twice the bytes, and so are the payloads the sink gets); the frame slots and everything between the
-        two conversions are 16-bit (csrc/yuv16.hip, ``_u16_io``).  Not with ``tiles``.  Returns the number of windows run."""
+        two conversions are 16-bit (csrc/yuv16.hip, ``_u16_io``).  Not with ``tiles``.
+        ``yuv.layout`` ('420' when absent; ``y4m.LAYOUTS``): the payloads' chroma layout; 4:2:2, 4:4:4 and mono payloads are
+        converted by csrc/yuv_layouts.hip and the outputs keep the layout.  Returns the number of windows run."""
         cuts, full = getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False))
-        depth = int(getattr(yuv, 'depth', 8))
+        depth, layout = int(getattr(yuv, 'depth', 8)), getattr(yuv, 'layout', '420')
         if depth > 8 and self.tiles is not None:
             raise ValueError('WindowRunner.run_clip_u8: tiles move 8-bit pixels; a %d-bit stream cannot run tiled' % depth)
         if self.retime is not None and yuv is None:
@@ -602,9 +604,9 @@ class WindowRunner:
             raise ValueError('WindowRunner.run_clip_u8: scene cuts need a retimed runner (r = M for x M) and reuse_frames')
         if full and (self.retime is None or window_index is None):
             raise ValueError('WindowRunner.run_clip_u8: the full-length timeline needs a retimed runner and window_index')
-        if self._pipeline is None or self._pipeline.key != (batch, yuv is not None, cuts, full, depth):
+        if self._pipeline is None or self._pipeline.key != (batch, yuv is not None, cuts, full, depth, layout):
             self._pipeline = None                        # release the old buffers before the new ones are allocated
-            self._pipeline = ClipPipeline(self, batch, yuv is not None, cuts, full, depth)
+            self._pipeline = ClipPipeline(self, batch, yuv is not None, cuts, full, depth, layout)
         return self._pipeline.run(host_frames, windows, sink, reuse_frames, yuv, window_index)
 
     def __del__(self):

@@ -2,8 +2,9 @@
 runs.  Pure Python; the one module that knows the policy.
 
 Input frames are numbered 0 .. n-1 and window k reads frames k .. k+3, interpolating between B0 = k+1 and B1 = k+2 (``retime``).
-p_j is the raw 4:2:0 payload of frame j (all Y, Cb, Cr bytes; P of them).  For j = 1 .. n-1
-  SAD_j   = sum |p_j - p_{j-1}| over the P bytes (an exact integer; the GPU computes it, ``sad_np`` defines it),
+p_j is the raw payload of frame j (all its payload samples: Y, Cb, Cr of a 4:2:0, 4:2:2 or 4:4:4 stream, Y of a mono one; P of
+them, bytes at 8 bits).  For j = 1 .. n-1
+  SAD_j   = sum |p_j - p_{j-1}| over the P payload samples (an exact integer; the GPU computes it, ``sad_np`` defines it),
   mafd_j  = 100 * SAD_j / (255 * P) in float64, mafd_0 = 0,
   score_j = min(mafd_j, |mafd_j - mafd_{j-1}|),
 and a cut lies before frame j iff score_j >= T.  This has the shape of ffmpeg's ``scdet`` filter (the mean absolute frame

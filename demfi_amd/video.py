@@ -27,6 +27,12 @@ frames at their byte offsets of the output file (no collective on the data path)
 from its fp32 output frames back; only the fused uint8 store of the fp16 engine is replaced by one egress kernel per frame.
 With ``--dtype fp16`` the network's input record and features are fp16, which resolves 10-bit video fully and about 12 bits at
 best near the ends of the range; ``--dtype fp32`` carries all 16 bits.
+
+``--any-layout`` also takes 4:2:2, 4:4:4 and grey streams (C422, C444, Cmono, what ``ffmpeg -pix_fmt yuv422p / yuv444p / gray -f
+yuv4mpegpipe`` writes; together with ``--high-depth`` their 10- to 16-bit forms C422pNN, C444pNN, CmonoNN) and gives the output in
+the input's layout and depth.  Only the two conversions at the edge know the layout (csrc/yuv_layouts.hip, ``y4m.yuv_to_bgr_np`` /
+``y4m.bgr_to_yuv_np`` and their 16-bit forms): the payload of P samples becomes the same BGR frame slots, and retiming, scene cuts
+(scored over the payload's P samples), the full-length timeline, tiles (8-bit layouts) and rank sharding run as they do for 4:2:0.
 """
 import os
 import sys
@@ -47,10 +53,12 @@ class YuvEdge:
     """Y4M edge of ``WindowRunner.run_clip_u8``: conversion parameters of the stream (library codes), ``with_s1(k)``: does
     window k (index in the runner's window sequence) close the stream, i.e. is its S1 written?  ``scene_cut``: None, or the
     threshold T of scene-cut detection (``demfi_amd.scene``).  ``full_length``: the full-length timeline (``retime``).
-    ``depth``: bits per sample, 8, or 10 / 12 / 14 / 16 for payloads of 16-bit samples."""
+    ``depth``: bits per sample, 8, or 10 / 12 / 14 / 16 for payloads of 16-bit samples.  ``layout``: the payloads' chroma
+    layout, one of ``y4m.LAYOUTS`` (``siting`` only matters to '420')."""
 
-    def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8):
+    def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420'):
         self.depth = y4m.check_depth(depth)
+        self.layout = y4m.check_layout(layout)
         self.matrix = {'bt601': L.BT601, 'bt709': L.BT709}[matrix]
         self.full_range = bool(full_range)
         self.siting = {'420jpeg': L.SITING_420JPEG, '420mpeg2': L.SITING_420MPEG2}[siting]
@@ -72,10 +80,13 @@ class VideoRunner:
     (``demfi_amd.tiling``, ``tile_margin`` pixels thrown away next to every cut); ``last_plan`` is the plan of the last input, None
     when it ran untiled, and ``last_instants`` then counts per tile.  ``high_depth``: also take 10- to 16-bit 4:2:0 input
     (C420p10 / C420p12 / C420p14 / C420p16) and give the output at the input's depth (``last_depth``); off by default, and an
-    8-bit stream gives the same bytes either way.  Not together with ``tile`` (tiles move 8-bit pixels)."""
+    8-bit stream gives the same bytes either way.  Not together with ``tile`` (tiles move 8-bit pixels).  ``layouts``: also take
+    4:2:2, 4:4:4 and mono input (C422, C444, Cmono; with ``high_depth`` their deep forms C422pNN / C444pNN / CmonoNN) and give the
+    output in the input's layout (``last_layout``); off by default, and a 4:2:0 stream gives the same bytes either way.  The 8-bit
+    layouts run with ``tile``, since tiles cut BGR frames."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
-                 tile_margin=T.DEFAULT_MARGIN, high_depth=False, **runner_kw):
+                 tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, **runner_kw):
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
         if mfi is not None and fps is not None:
@@ -92,8 +103,9 @@ class VideoRunner:
         self.full_length = bool(full_length)
         self.high_depth = bool(high_depth)
         self.depths = y4m.DEPTHS if self.high_depth else (8,)
+        self.layouts = y4m.LAYOUTS if layouts else ('420',)
         self.tile = tile
-        self.last_depth = 8
+        self.last_depth, self.last_layout = 8, '420'
         if tile is not None:
             T.plan_tiles(64, 64, tile, tile_margin)      # a bad tile or margin fails here, not at the first frame
         self.runner_kw = dict(runner_kw, tile=tile, tile_margin=tile_margin)
@@ -123,7 +135,7 @@ class VideoRunner:
         if hdr.depth > 8 and self.tile is not None:
             raise ValueError('VideoRunner: tile=%r with a %d-bit stream (C%s): tiles move 8-bit pixels, so --tile and high bit '
                              'depth do not go together yet; run it untiled, or convert the input to 8 bits' % (self.tile, hdr.depth, hdr.ctag))
-        self.last_depth = hdr.depth
+        self.last_depth, self.last_layout = hdr.depth, hdr.layout
 
     def _clip_runner(self, hdr, world, rank):
         r = self._ratio(hdr)
@@ -152,12 +164,12 @@ class VideoRunner:
 
     def _edge(self, hdr, with_s1):
         return YuvEdge(y4m.auto_matrix(hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
-                       self.scene_cut, self.full_length, hdr.depth)
+                       self.scene_cut, self.full_length, hdr.depth, hdr.layout)
 
     def run_stream(self, src, dst):
         """One rank, sequential binary streams (stdin / stdout work): nothing is seeked, the input is read in batches of
         windows and every batch is written (and flushed) as it drains.  Returns (windows, frames written)."""
-        rd = y4m.Reader(src, self.depths)
+        rd = y4m.Reader(src, self.depths, self.layouts)
         hdr = rd.header
         self._check_depth(hdr)
         cr = self._clip_runner(hdr, 1, 0)
@@ -184,7 +196,7 @@ class VideoRunner:
         (``dist.shard_windows``), its frames written at ``header + i*(6 + payload)``.  Rank 0 writes the header and sizes the
         output file; all ranks meet at a barrier before writing.  Returns (windows, frames written) of this rank."""
         with open(in_path, 'rb') as f:
-            hdr, _, offs = y4m.scan(f, self.depths)
+            hdr, _, offs = y4m.scan(f, self.depths, self.layouts)
             self._check_depth(hdr)
             n_in = len(offs)
             ohdr = self._out_header(hdr)
@@ -242,7 +254,10 @@ def parser():
                                  epilog='Input: 8-bit 4:2:0 progressive Y4M (C420jpeg, C420, C420mpeg2; XCOLORRANGE=FULL|LIMITED), '
                                         'e.g. ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe -; with --high-depth also 10- to 16-bit '
                                         '4:2:0 (C420p10, C420p12, C420p14, C420p16), e.g. ffmpeg -i in.mkv -pix_fmt yuv420p10le -strict -1 '
-                                        '-f yuv4mpegpipe -.  Output: C420jpeg (C420pNN at the input\'s depth), the input\'s '
+                                        '-f yuv4mpegpipe -; with --any-layout also 4:2:2, 4:4:4 and grey (C422, C444, Cmono and, with '
+                                        '--high-depth, C422pNN, C444pNN, CmonoNN), e.g. ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 '
+                                        '-f yuv4mpegpipe -.  Output: C420jpeg (C420pNN at the input\'s depth; the input\'s layout and '
+                                        'depth for the other layouts), the input\'s '
                                         'matrix and range.  n input frames give (n-3)*M + 1 output frames: the first and the last '
                                         'input frame have no output, as in the reference (--full-length: n*M frames from input '
                                         'frame 0 on).  All logging goes to stderr.')
@@ -260,7 +275,7 @@ def parser():
                     help='YCbCr matrix of the input (and output); auto: BT.709 when H >= 720, else BT.601')
     ap.add_argument('--batch', type=int, default=4, help='windows per batch (the input frames held are bounded by it)')
     ap.add_argument('--scene-cut', nargs='?', type=_scene_cut_arg, const=S.DEFAULT_THRESHOLD, default=None, metavar='T',
-                    help='detect scene cuts (score = min(mafd, |mafd - previous mafd|) of the 4:2:0 bytes, in percent; a cut where '
+                    help='detect scene cuts (score = min(mafd, |mafd - previous mafd|) of the payload samples, in percent; a cut where '
                          'score >= T, T in (0, 100], default %g) and never interpolate across one: the frames next to a cut '
                          'hold the nearest input frame.  Off unless given' % S.DEFAULT_THRESHOLD)
     ap.add_argument('--full-length', action='store_true',
@@ -271,6 +286,10 @@ def parser():
                     help='also take 10-, 12-, 14- and 16-bit 4:2:0 (C420p10 .. C420p16, 16-bit little-endian samples) and write the '
                          'output at the input\'s depth, through a 16-bit frame path; --dtype fp16 resolves 10 bits fully and about 12 at '
                          'best, --dtype fp32 all 16.  Not with --tile.  Off by default (8-bit input only)')
+    ap.add_argument('--any-layout', action='store_true',
+                    help='also take 4:2:2, 4:4:4 and grey input (C422, C444, Cmono; together with --high-depth their 10- to 16-bit forms '
+                         'C422pNN, C444pNN, CmonoNN) and write the output in the input\'s layout: nothing is resampled to 4:2:0 and back.  '
+                         'Off by default (4:2:0 input only)')
     T.add_arguments(ap)
     return ap
 
@@ -307,7 +326,7 @@ def main(argv=None):
     model = model.to(dev).eval()
     D.broadcast_state_dict(model, world, device=dev)
     vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut, full_length=a.full_length,
-                     tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth)
+                     tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth, layouts=a.any_layout)
     t0 = time.perf_counter()
     if world > 1:
         nw, nf = vr.run_file(a.input, a.output, world, rank)
@@ -335,7 +354,7 @@ def main(argv=None):
                           'fps_out': str(vr.last_fps_out) if vr.last_fps_out is not None else None,
                           'instants_run': int(ti), 'instants_padded': int(tp), 'cut_windows': int(tc),
                           'tiles': vr.last_plan.n_tiles if vr.last_plan is not None else 1,
-                          'tile': vr.last_plan.label() if vr.last_plan is not None else None, 'depth': vr.last_depth,
+                          'tile': vr.last_plan.label() if vr.last_plan is not None else None, 'depth': vr.last_depth, 'layout': vr.last_layout,
                           'weights': os.path.basename(a.checkpoint) if a.checkpoint else 'synthetic_state_dict(0) (random init: no checkpoint given)',
                           'out': a.output}), file=sys.stderr)
     D.finalize()

@@ -22,6 +22,14 @@ C 16s .. 240s, the Y offset 16s, the chroma centre 2^(d-1), the scale factors pe
 inverses); coefficients are rounded half up to Q(8+d), accumulators are 64-bit, results clamp to [0, peak].  d = 8 is the
 8-bit pair exactly.  Frames are then uint16 [h,w,3] B, G, R with values 0 .. peak.
 
+Other chroma layouts (opt-in: ``layouts=LAYOUTS``, ``python -m demfi_amd.video --any-layout``): C422 (Cb, Cr [h, ceil(w/2)],
+co-sited horizontally), C444 (three [h,w] planes) and Cmono (Y only), and with ``depths=DEPTHS`` their deep forms C422pNN /
+C444pNN / CmonoNN.  ``yuv_to_bgr_np`` / ``bgr_to_yuv_np`` (8-bit) and ``yuv_to_bgr16_np`` / ``bgr16_to_yuv_np`` (depth d) define
+their conversion (the HIP kernels of csrc/yuv_layouts.hip match them bit for bit): the matrix step above, unchanged, behind the
+layout's upsampler -- 4:4:4 the sample itself, 4:2:2 the horizontal rule of 420mpeg2 with no vertical filter, mono no chroma
+(B = G = R); downsampling rounds the full-resolution chroma once (4:4:4) or the co-sited [1,2,1]/4 of it with clamped edges
+(4:2:2).  The output keeps the input's layout and depth.
+
 Two timelines: by default n input frames give (n-3)*M + 1 output frames and the first and last input frames have no output
 (``n_output_frames``); on the full-length timeline (``Frames(full_length=True)``, ``retime``) output frame 0 is input frame 0
 and n frames give n*M, windows running from k = -1 on tuples clamped at the clip's ends.
@@ -42,6 +50,9 @@ MATRICES = {'bt601': (0.299, 0.114), 'bt709': (0.2126, 0.0722)}       # (Kr, Kb)
 SITINGS = ('420jpeg', '420mpeg2')
 DEPTHS = (8, 10, 12, 14, 16)                                          # what ``depths=DEPTHS`` (--high-depth) accepts
 HIGH_DEPTH_HINT = '; or keep the bit depth: --high-depth accepts 10- to 16-bit 4:2:0 (C420p10, C420p12, C420p14, C420p16)'
+LAYOUTS = ('420', '422', '444', 'mono')                               # what ``layouts=LAYOUTS`` (--any-layout) accepts
+ANY_LAYOUT_HINT = ('; or keep the chroma layout: --any-layout accepts 4:2:2, 4:4:4 and grey (C422, C444, Cmono; together with '
+                   '--high-depth also C422pNN, C444pNN, CmonoNN for NN in 10, 12, 14, 16)')
 _CHROMA = {None: '420jpeg', '420jpeg': '420jpeg', '420': '420jpeg', '420mpeg2': '420mpeg2'}
 _MAX_LINE = 4096
 
@@ -80,8 +91,22 @@ def to_yuv_coefs(matrix, full_range):
             (_fix16(cs * 0.5), _fix16(-(cs * kg / (2.0 * (1.0 - kr)))), _fix16(-(cs * kb / (2.0 * (1.0 - kr)))))), (0 if full_range else 16)
 
 
-def payload_size(h, w):
-    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+def check_layout(layout):
+    if layout not in LAYOUTS:
+        raise ValueError('chroma layout must be one of %s, got %r' % (LAYOUTS, layout))
+    return layout
+
+
+def chroma_shape(h, w, layout='420'):
+    """(rows, columns) of one chroma plane of an h x w frame; (0, 0) for mono."""
+    check_layout(layout)
+    return {'420': ((h + 1) // 2, (w + 1) // 2), '422': (h, (w + 1) // 2), '444': (h, w), 'mono': (0, 0)}[layout]
+
+
+def payload_size(h, w, layout='420'):
+    """Samples of one payload: Y [h,w], then Cb and Cr of ``chroma_shape`` (4:2:0 unless ``layout`` says otherwise)."""
+    ch, cw = chroma_shape(h, w, layout)
+    return h * w + 2 * ch * cw
 
 
 def split_planes(payload, h, w):
@@ -182,9 +207,9 @@ def to_yuv_coefs_depth(matrix, full_range, depth):
         (0 if full_range else 16 * s)
 
 
-def payload_bytes(h, w, depth=8):
-    """Bytes of one 4:2:0 payload: ``payload_size`` samples of one byte at depth 8, of two above."""
-    return payload_size(h, w) * (2 if depth > 8 else 1)
+def payload_bytes(h, w, depth=8, layout='420'):
+    """Bytes of one payload: ``payload_size`` samples of one byte at depth 8, of two above."""
+    return payload_size(h, w, layout) * (2 if depth > 8 else 1)
 
 
 def as_samples16(payload):
@@ -251,6 +276,109 @@ def bgr16_to_yuv420_np(bgr16, depth, matrix='bt601', full_range=False):
     return out.astype('<u2', copy=False)
 
 
+# ---- the other chroma layouts: 4:2:2, 4:4:4, mono ---------------------------------------------------------------------------
+def split_planes_layout(payload, h, w, layout):
+    """Payload of samples (a 1-D uint8 or uint16 array) -> (Y [h,w], Cb, Cr of ``chroma_shape``) views; mono: Cb = Cr = None."""
+    a = payload.reshape(-1)
+    ch, cw = chroma_shape(h, w, layout)
+    if a.size != payload_size(h, w, layout):
+        raise ValueError('payload of %d samples for a %dx%d %s frame (%d expected)' % (a.size, h, w, layout, payload_size(h, w, layout)))
+    if layout == 'mono':
+        return a.reshape(h, w), None, None
+    return a[:h * w].reshape(h, w), a[h * w:h * w + ch * cw].reshape(ch, cw), a[h * w + ch * cw:].reshape(ch, cw)
+
+
+def _upsample16_layout(c, h, w, layout):
+    """chroma plane of a 4:2:2 / 4:4:4 frame -> int32 [h,w] in 1/16 units.  4:4:4: the sample.  4:2:2 (co-sited horizontally, no
+    vertical filter): the sample at even x, 1/2 + 1/2 of it and its right neighbour (clamped to the edge) at odd x -- the
+    horizontal rule of 420mpeg2."""
+    c = c.astype(np.int32)
+    if layout == '444':
+        return 16 * c
+    if layout == '422':
+        xs = np.arange(w)
+        cx0 = xs >> 1
+        cx1 = np.where(xs & 1, np.minimum(cx0 + 1, c.shape[1] - 1), cx0)
+        return 8 * (c[:, cx0] + c[:, cx1])
+    raise ValueError('no chroma upsampling for layout %r' % (layout,))
+
+
+def yuv_to_bgr16_np(payload, h, w, depth, layout, matrix='bt601', full_range=False, siting='420jpeg'):
+    """One payload of 16-bit samples at depth d in any of ``LAYOUTS`` -> uint16 BGR [h,w,3], values 0 .. peak: the matrix step of
+    ``yuv420_to_bgr16_np`` (same coefficients, chroma in 1/16 units, ONE round-half-up, clamp) behind the layout's upsampler;
+    mono has no chroma term, so B = G = R.  ``siting`` only matters to '420', which is ``yuv420_to_bgr16_np``.  The definition
+    the HIP kernels of csrc/yuv_layouts.hip match."""
+    check_depth(depth)
+    if check_layout(layout) == '420':
+        return yuv420_to_bgr16_np(payload, h, w, depth, matrix, full_range, siting)
+    y, cb, cr = split_planes_layout(as_samples16(payload), h, w, layout)
+    (cy, r_cr, g_cb, g_cr, b_cb), yoff = to_bgr_coefs_depth(matrix, full_range, depth)
+    mid = (1 << (depth - 1)) * 16
+    yy = (y.astype(np.int64) - yoff) * 16
+    if layout == 'mono':
+        cbv = crv = np.zeros((h, w), np.int64)
+    else:
+        cbv = _upsample16_layout(cb, h, w, layout).astype(np.int64) - mid
+        crv = _upsample16_layout(cr, h, w, layout).astype(np.int64) - mid
+    sh = 8 + depth + 4
+    rnd = np.int64(1 << (sh - 1))
+    r = (cy * yy + r_cr * crv + rnd) >> sh
+    g = (cy * yy + g_cb * cbv + g_cr * crv + rnd) >> sh
+    b = (cy * yy + b_cb * cbv + rnd) >> sh
+    return np.clip(np.stack([b, g, r], -1), 0, (1 << depth) - 1).astype(np.uint16)
+
+
+def bgr16_to_yuv_np(bgr16, depth, layout, matrix='bt601', full_range=False):
+    """uint16 BGR [h,w,3] at depth d -> one payload of 16-bit samples in any of ``LAYOUTS``, 1-D uint16.  Y as in
+    ``bgr16_to_yuv420_np``; with f the full-resolution Q(8+d) chroma centred on 0: 4:4:4 rounds f once; 4:2:2 is the co-sited
+    [1,2,1]/4 over f[y, 2i-1], f[y, 2i], f[y, 2i+1] (clamped to the edge), rounded once; mono is Y only.  '420' is
+    ``bgr16_to_yuv420_np``.  The definition the HIP kernels of csrc/yuv_layouts.hip match."""
+    check_depth(depth)
+    if check_layout(layout) == '420':
+        return bgr16_to_yuv420_np(bgr16, depth, matrix, full_range)
+    bgr = np.asarray(bgr16)
+    if bgr.dtype != np.uint16 or bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise ValueError('uint16 [h,w,3] expected, got %s %s' % (bgr.dtype, bgr.shape))
+    h, w = bgr.shape[:2]
+    if h < 2 or w < 2:
+        raise ValueError('frame of %dx%d: 2x2 at least' % (h, w))
+    (ky, kcb, kcr), yoff = to_yuv_coefs_depth(matrix, full_range, depth)
+    q, peak, mid = 8 + depth, (1 << depth) - 1, 1 << (depth - 1)
+    b, g, r = (bgr[:, :, i].astype(np.int64) for i in range(3))
+    y = np.clip((ky[0] * r + ky[1] * g + ky[2] * b + (yoff << q) + (1 << (q - 1))) >> q, 0, peak)
+    ci = np.arange(0, w, 2)                                   # the luma column chroma column i is co-sited with
+
+    def down(k):
+        f = k[0] * r + k[1] * g + k[2] * b                   # full-resolution Q(8+d) chroma, centred on 0
+        if layout == '444':
+            return np.clip((f + (mid << q) + (1 << (q - 1))) >> q, 0, peak)
+        s = f[:, np.maximum(ci - 1, 0)] + 2 * f[:, ci] + f[:, np.minimum(ci + 1, w - 1)]
+        return np.clip((s + (mid << (q + 2)) + (1 << (q + 1))) >> (q + 2), 0, peak)
+    planes = [y] if layout == 'mono' else [y, down(kcb), down(kcr)]
+    return np.concatenate([p.reshape(-1) for p in planes]).astype(np.uint16).astype('<u2', copy=False)
+
+
+def yuv_to_bgr_np(payload, h, w, layout, matrix='bt601', full_range=False, siting='420jpeg'):
+    """One 8-bit payload in any of ``LAYOUTS`` -> uint8 BGR [h,w,3]: the d = 8 instance of ``yuv_to_bgr16_np`` (whose
+    intermediates then fit int32, as the kernels compute them); '420' is ``yuv420_to_bgr_np``."""
+    a = np.frombuffer(payload, np.uint8) if not isinstance(payload, np.ndarray) else payload.reshape(-1)
+    if a.dtype != np.uint8:
+        raise ValueError('a payload of 8-bit samples is a uint8 array, got %s' % a.dtype)
+    if check_layout(layout) == '420':
+        return yuv420_to_bgr_np(a, h, w, matrix, full_range, siting)
+    return yuv_to_bgr16_np(a.astype(np.uint16), h, w, 8, layout, matrix, full_range).astype(np.uint8)
+
+
+def bgr_to_yuv_np(bgr, layout, matrix='bt601', full_range=False):
+    """uint8 BGR [h,w,3] -> one 8-bit payload in any of ``LAYOUTS``, 1-D uint8: the d = 8 instance of ``bgr16_to_yuv_np``."""
+    bgr = np.asarray(bgr)
+    if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise ValueError('uint8 [h,w,3] expected, got %s %s' % (bgr.dtype, bgr.shape))
+    if check_layout(layout) == '420':
+        return bgr_to_yuv420_np(bgr, matrix, full_range)
+    return bgr16_to_yuv_np(bgr.astype(np.uint16), 8, layout, matrix, full_range).astype(np.uint8)
+
+
 def auto_matrix(h):
     """--matrix auto: BT.709 for HD (H >= 720), BT.601 below (what encoders assume for untagged video)."""
     return 'bt709' if h >= 720 else 'bt601'
@@ -261,15 +389,18 @@ class Header:
     """Parsed stream header.  ``chroma``: '420jpeg' | '420mpeg2' (C420 / missing C = 420jpeg); ``full_range`` from
     XCOLORRANGE (default limited); ``fps`` a Fraction; ``aspect`` / ``color_range`` the raw A / XCOLORRANGE values or None;
     ``xtags`` the other X parameters in order.  ``depth``: bits per sample, 8 or (C420pNN) 10 / 12 / 14 / 16, the latter as
-    16-bit little-endian samples; ``payload`` / ``frame_bytes`` are bytes."""
+    16-bit little-endian samples; ``payload`` / ``frame_bytes`` are bytes.  ``layout``: one of ``LAYOUTS``; ``chroma`` is the
+    siting of a 4:2:0 stream and stays '420jpeg' for the other layouts, which have one siting each."""
 
-    def __init__(self, w, h, fps, interlace='p', aspect=None, chroma='420jpeg', color_range=None, xtags=(), ctag=None, depth=8):
+    def __init__(self, w, h, fps, interlace='p', aspect=None, chroma='420jpeg', color_range=None, xtags=(), ctag=None, depth=8,
+                 layout='420'):
         self.w, self.h, self.fps = int(w), int(h), Fraction(fps)
         self.interlace, self.aspect, self.chroma = interlace, aspect, chroma
         self.color_range = color_range
         self.xtags = list(xtags)
         self.ctag = ctag
         self.depth = check_depth(depth)
+        self.layout = check_layout(layout)
 
     @property
     def full_range(self):
@@ -277,7 +408,12 @@ class Header:
 
     @property
     def payload(self):
-        return payload_bytes(self.h, self.w, self.depth)
+        return payload_bytes(self.h, self.w, self.depth, self.layout)
+
+    @property
+    def samples(self):
+        """samples of one payload (what the scene-cut scores count)"""
+        return payload_size(self.h, self.w, self.layout)
 
     @property
     def peak(self):
@@ -309,11 +445,17 @@ def _reject(what, hint=''):
 
 
 _DEEP = {'420p%d' % d: d for d in DEPTHS if d > 8}                    # 4:2:0 tags of 16-bit samples (420jpeg siting)
+# tags of the other layouts -> (layout, depth): C422 / C444 / Cmono, and C422pNN / C444pNN / CmonoNN of 16-bit samples
+_LAYOUT_TAGS = dict([(lay, (lay, 8)) for lay in LAYOUTS[1:]] +
+                    [(('mono%d' if lay == 'mono' else lay + 'p%d') % d, (lay, d)) for lay in LAYOUTS[1:] for d in DEPTHS if d > 8])
+_LAYOUT_NAMES = {'420': '4:2:0', '422': '4:2:2', '444': '4:4:4', 'mono': 'mono'}
 
 
-def parse_header(line, depths=(8,)):
+def parse_header(line, depths=(8,), layouts=('420',)):
     """One header line (bytes, with or without the trailing newline) -> Header.  Raises Y4MError.  ``depths``: the bit depths
-    taken; the default is 8-bit only, ``DEPTHS`` also takes C420p10 / C420p12 / C420p14 / C420p16."""
+    taken; the default is 8-bit only, ``DEPTHS`` also takes C420p10 / C420p12 / C420p14 / C420p16.  ``layouts``: the chroma
+    layouts taken; the default is 4:2:0 only, ``LAYOUTS`` also takes C422 / C444 / Cmono and, with ``depths=DEPTHS``, their deep
+    forms C422pNN / C444pNN / CmonoNN."""
     if isinstance(line, str):
         line = line.encode()
     line = line.rstrip(b'\n')
@@ -321,7 +463,7 @@ def parse_header(line, depths=(8,)):
     if toks[0] != MAGIC:
         raise Y4MError('not a YUV4MPEG2 stream (bad magic %r): %s' % (bytes(line[:16]), FIX))
     w = h = fps = None
-    inter, aspect, ctag, crange, xt, depth = 'p', None, None, None, [], 8
+    inter, aspect, ctag, crange, xt, depth, layout = 'p', None, None, None, [], 8, '420'
     for t in toks[1:]:
         if not t:
             continue
@@ -345,15 +487,24 @@ def parse_header(line, depths=(8,)):
         elif tag == 'A':
             aspect = val
         elif tag == 'C':
+            names = ', '.join(_LAYOUT_NAMES[x] for x in layouts)
+            only = '8-bit %s only' % names if tuple(depths) == (8,) else '%s only, %s bits' % (names, ', '.join(str(d) for d in depths))
             if val in _DEEP:
                 if _DEEP[val] not in depths:
                     _reject('colour space C%s (8-bit 4:2:0 only)' % val, HIGH_DEPTH_HINT)
-                depth = _DEEP[val]
+                depth, layout = _DEEP[val], '420'
+            elif val in _LAYOUT_TAGS:
+                lay, d = _LAYOUT_TAGS[val]
+                if lay not in layouts:
+                    _reject('colour space C%s (%s)' % (val, only), ANY_LAYOUT_HINT)
+                if d not in depths:
+                    _reject('colour space C%s (8-bit %s only)' % (val, names),
+                            '; or keep the bit depth: --high-depth accepts 10- to 16-bit samples (C%s)' % val)
+                depth, layout = d, lay
             elif val not in _CHROMA:
-                _reject('colour space C%s (%s)' % (val, '8-bit 4:2:0 only' if tuple(depths) == (8,) else
-                                                   '4:2:0 only, %s bits' % ', '.join(str(d) for d in depths)))
+                _reject('colour space C%s (%s)' % (val, only))
             else:
-                depth = 8
+                depth, layout = 8, '420'
             ctag = val
         elif tag == 'X':
             if val.startswith('COLORRANGE='):
@@ -370,18 +521,22 @@ def parse_header(line, depths=(8,)):
     for nm, v in (('width', w), ('height', h)):
         if not 2 <= v <= MAX_SIDE:
             raise Y4MError('Y4M: %s %d outside 2..%d' % (nm, v, MAX_SIDE))
-    return Header(w, h, fps, inter, aspect, _CHROMA.get(ctag, '420jpeg'), crange, xt, ctag, depth)
+    return Header(w, h, fps, inter, aspect, _CHROMA.get(ctag, '420jpeg'), crange, xt, ctag, depth, layout)
 
 
-def output_ctag(depth):
-    """C tag of an output stream: 420jpeg, or the input's 420pNN (420jpeg siting) above 8 bits."""
-    return '420jpeg' if depth == 8 else '420p%d' % depth
+def output_ctag(depth, layout='420'):
+    """C tag of an output stream: 420jpeg, or the input's 420pNN (420jpeg siting) above 8 bits; for the other layouts the
+    input's own tag: 422 / 444 / mono, 422pNN / 444pNN / monoNN above 8 bits."""
+    if check_layout(layout) == '420':
+        return '420jpeg' if depth == 8 else '420p%d' % depth
+    return layout if depth == 8 else ('mono%d' if layout == 'mono' else layout + 'p%d') % depth
 
 
 def output_header(hdr, mfi):
     """Header of the x M stream: the input's W H, F x M (reduced), progressive, A copied, C420jpeg (C420pNN at the input's depth
-    above 8 bits), the input's XCOLORRANGE."""
-    return Header(hdr.w, hdr.h, hdr.fps * mfi, 'p', hdr.aspect, '420jpeg', hdr.color_range, (), output_ctag(hdr.depth), hdr.depth)
+    above 8 bits; the input's layout and depth for 4:2:2, 4:4:4 and mono), the input's XCOLORRANGE."""
+    return Header(hdr.w, hdr.h, hdr.fps * mfi, 'p', hdr.aspect, '420jpeg', hdr.color_range, (), output_ctag(hdr.depth, hdr.layout),
+                  hdr.depth, hdr.layout)
 
 
 # ---- stream order of the x M output ----------------------------------------------------------------------------------------
@@ -428,12 +583,12 @@ def _frame_line(line, index):
 class Reader:
     """Sequential reader of a binary stream (a file, or stdin: nothing is seeked).  ``read_into(buf)`` fills one payload."""
 
-    def __init__(self, f, depths=(8,)):
+    def __init__(self, f, depths=(8,), layouts=('420',)):
         self.f = f
         line = _readline(f, 'header')
         if not line:
             raise Y4MError('Y4M: empty input: %s' % FIX)
-        self.header = parse_header(line, depths)
+        self.header = parse_header(line, depths, layouts)
         self.header_bytes = len(line)
         self.index = 0                                  # frames read so far
 
@@ -453,11 +608,11 @@ class Reader:
         return True
 
 
-def scan(f, depths=(8,)):
+def scan(f, depths=(8,), layouts=('420',)):
     """One pass over the frame headers of a seekable file: (Header, header bytes, [file offset of every payload]).  The
-    payloads are skipped, not read; a truncated last frame raises.  ``depths``: as ``parse_header``."""
+    payloads are skipped, not read; a truncated last frame raises.  ``depths``, ``layouts``: as ``parse_header``."""
     f.seek(0)
-    rd = Reader(f, depths)
+    rd = Reader(f, depths, layouts)
     size = os.fstat(f.fileno()).st_size if hasattr(f, 'fileno') else None
     p = rd.header.payload
     offs = []

@@ -41,6 +41,8 @@ enum demfi_status {
 /* Colour conversion of the Y4M stream edge (demfi_yuv420_to_bgr / demfi_bgr_to_yuv420 below). */
 enum demfi_yuv_matrix { DEMFI_BT601 = 0, DEMFI_BT709 = 1 };
 enum demfi_chroma_siting { DEMFI_420JPEG = 0, DEMFI_420MPEG2 = 1 };   /* chroma centred / co-sited horizontally, centred vertically */
+/* Chroma layouts of demfi_yuvl_to_bgr and its kin below (4:2:0 = 0 is served by the demfi_yuv420 functions). */
+enum demfi_yuv_layout { DEMFI_YUV_420 = 0, DEMFI_YUV_422 = 1, DEMFI_YUV_444 = 2, DEMFI_YUV_MONO = 3 };
 
 enum demfi_act { DEMFI_ACT_NONE = 0, DEMFI_ACT_RELU = 1, DEMFI_ACT_TANH = 2, DEMFI_ACT_SIGMOID = 3 };
 
@@ -397,6 +399,23 @@ int demfi_yuv420p16_sad(const uint16_t* base, const int64_t* a_offsets, const in
 int demfi_u16_ingest(const uint16_t* const* frames, int h, int w, int depth, float* x, void* s2d, float* overlay, int dtype, int H,
                      int W, void* stream);
 int demfi_frame_to_u16(const float* frame, uint16_t* out, int h, int w, int H, int W, int depth, void* stream);
+
+/* ---- the other chroma layouts of the Y4M edge (csrc/yuv_layouts.hip; demfi_amd/video.py --any-layout) ------------------------
+ * demfi_yuv420_to_bgr / demfi_bgr_to_yuv420_gather and their 16-bit forms for layout = DEMFI_YUV_422 (Y [h,w]; Cb, Cr
+ * [h, ceil(w/2)], co-sited horizontally), DEMFI_YUV_444 (three [h,w] planes) and DEMFI_YUV_MONO (Y only; B = G = R), with the
+ * same argument conventions: byte strides and offsets for the uint8 pair, sample strides and offsets (and 2-byte aligned
+ * buffers, depth 8..16) for the uint16 pair; any h, w in 2..16384; device buffers; one launch for n frames; the output keeps the
+ * layout.  Integer arithmetic that matches demfi_amd/y4m.py (yuv_to_bgr_np / bgr_to_yuv_np, yuv_to_bgr16_np / bgr16_to_yuv_np) bit
+ * for bit: the matrix step of the 4:2:0 functions; 4:2:2 upsamples by the horizontal rule of 420mpeg2 and downsamples by the
+ * co-sited [1,2,1]/4 with clamped edges, 4:4:4 does neither.  DEMFI_YUV_420 is an argument error here. */
+int demfi_yuvl_to_bgr(const uint8_t* src, int64_t src_stride, uint8_t* dst, int64_t dst_stride, int n, int h, int w, int layout,
+                      int matrix, int full_range, void* stream);
+int demfi_bgr_to_yuvl_gather(const uint8_t* base, const int64_t* src_offsets, uint8_t* dst, int64_t dst_stride, int n, int h, int w,
+                             int layout, int matrix, int full_range, void* stream);
+int demfi_yuvl16_to_bgr16(const uint16_t* src, int64_t src_stride, uint16_t* dst, int64_t dst_stride, int n, int h, int w, int depth,
+                          int layout, int matrix, int full_range, void* stream);
+int demfi_bgr16_to_yuvl16_gather(const uint16_t* base, const int64_t* src_offsets, uint16_t* dst, int64_t dst_stride, int n, int h,
+                                 int w, int depth, int layout, int matrix, int full_range, void* stream);
 
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
