@@ -20,6 +20,7 @@ SRCS_CPP="abi.cpp"
 [ -f yuv16.hip ] && SRCS_HIP="$SRCS_HIP yuv16.hip"
 [ -f yuv_layouts.hip ] && SRCS_HIP="$SRCS_HIP yuv_layouts.hip"
 [ -f tile.hip ] && SRCS_HIP="$SRCS_HIP tile.hip"
+[ -f dedup.hip ] && SRCS_HIP="$SRCS_HIP dedup.hip"
 [ -f wsconv.hip ] && SRCS_HIP="$SRCS_HIP wsconv.hip"
 [ -f ctx.cpp ] && SRCS_CPP="$SRCS_CPP ctx.cpp"
 [ -f png_codec.cpp ] && SRCS_CPP="$SRCS_CPP png_codec.cpp"

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import cadence as K
 from . import retime as R
 from . import scene as S
 from .y4m import payload_size
@@ -62,6 +63,13 @@ class FrameSlots:
             stream.wait_event(self.busy[sl])
         self.slot_of[key], self.key_of[sl] = sl, key
         return sl, True
+
+    def release(self, key):
+        """Give back the slot of frame ``key``, the one acquired last: the ring's next frame takes it."""
+        sl = self.slot_of.pop(key)
+        if (sl + 1) % len(self.busy) != self.next:
+            raise RuntimeError('FrameSlots.release: frame %r was not the last one acquired' % (key,))
+        self.key_of[sl], self.next = None, sl
 
     def mark_busy(self, read, ev):
         """The slots a batch read (lists of slots) stay busy until ``ev``."""
@@ -189,8 +197,9 @@ class Y4mEdge:
     ``layout``: the payloads' chroma layout (``y4m.LAYOUTS``): it sets P, and for 4:2:2, 4:4:4 and mono the two conversion
     launches are those of csrc/yuv_layouts.hip; everything between them sees BGR frames."""
 
-    def __init__(self, runner, batch, slots, cuts, full, tiler=None, depth=8, layout='420'):
+    def __init__(self, runner, batch, slots, cuts, full, tiler=None, depth=8, layout='420', dedup=None, h2d=None):
         self.rn, self.slots, self.cuts, self.full, self.tiler = runner, slots, cuts, full, tiler
+        self.dedup, self.h2d, self.kept, self._pending = dedup, h2d, None, []
         self.depth, self.hi = depth, depth > 8
         self.layout, self.lcode = layout, L.YUV_LAYOUT[layout]
         if self.hi and tiler is not None:
@@ -201,9 +210,11 @@ class Y4mEdge:
         dev, nsl = runner.engine.device, len(slots.frames)
         P, J = self.P, self.J = payload_size(h, w, layout), R.max_instants(self.r)
         nJ = -(-J // runner.n_ctx) * runner.n_ctx if runner.tb else J    # instants incl. the padding of a short chunk
-        runs_max = 2 * batch if cuts else batch                          # a cut window is two runs
+        runs_max = batch * max_runs(self.r, cuts, dedup)                 # a cut window is two runs
         # payloads of a batch: at most J per window, plus the last window's S1 (full-length: its [n-2, n) span, 2 J)
         nout = (batch + 1) * J if full else batch * J + 1
+        if dedup is not None:                        # a window spans up to max_hold + 1 input frames, and so does the last one's hold
+            nout = (batch + 1) * K.max_window_instants(self.r, dedup[3]) + 1
         Pb = self.Pb = P * es                                            # bytes of a payload of P samples
         self.yuv_in = torch.empty((nsl, Pb), dtype=torch.uint8, device=dev)
         self.comb = [torch.empty((runs_max, J + 2, h, w, 3), dtype=fdt, device=dev) for _ in range(2)]
@@ -219,7 +230,51 @@ class Y4mEdge:
             self.sad = torch.empty(nsl, dtype=torch.int64, device=dev)
             self.sad_offs = torch.empty(2 * nsl, dtype=torch.int64, device=dev)
             self.h_sad = torch.empty(nsl, dtype=torch.int64).pin_memory()
+        if dedup is not None:                        # block counts of one (frame, last kept frame) pair; pinned buffers are reused:
+            self.cnt = torch.empty(2, dtype=torch.int32, device=dev)         # every probe ends with a wait for its answer
+            self.cnt_offs = torch.empty(2, dtype=torch.int64, device=dev)
+            self.h_cnt = torch.empty(2, dtype=torch.int32).pin_memory()
+            self.h_cnt_offs = torch.empty(2, dtype=torch.int64).pin_memory()
         self.yuv = self.window_index = self.det = None
+
+    # ---- repeated frames (``cadence``): the windows generator (``KeptFrames``) stages, scores and keeps frames through these ----
+    def attach(self, kept):
+        """A --dedup run starts, before its first window is asked for: ``kept`` (``KeptFrames``) will stage frames here."""
+        self.kept, self._pending = kept, []
+        kept.edge = self
+
+    def stage(self, key, idx, f):
+        """Input frame idx, the candidate for kept index ``key``, is copied into the ring's next slot (upload stream)."""
+        with torch.cuda.stream(self.h2d):
+            sl, _ = self.slots.acquire(key, self.h2d)
+            self.upload(sl, idx, f)
+        return sl
+
+    def block_counts(self, sl, ref):
+        """(hot, warm) of the payload in slot sl against the one in slot ref: ONE ``demfi_luma_block_counts`` launch on the
+        upload stream behind the copy, read back with one event wait (the next frame is compared with whichever of the two
+        is kept, so frames are scored one by one)."""
+        hi, lo = self.dedup[0] << (self.depth - 8), self.dedup[1] << (self.depth - 8)
+        with torch.cuda.stream(self.h2d):
+            self.h_cnt_offs[0], self.h_cnt_offs[1] = sl * self.Pb, ref * self.Pb
+            self.cnt_offs.copy_(self.h_cnt_offs, non_blocking=True)
+            L.check(self.rn.lib.demfi_luma_block_counts(self.yuv_in.data_ptr(), self.cnt_offs.data_ptr(), self.cnt_offs[1:].data_ptr(), 1,
+                                                        self.fh, self.fw, 2 if self.hi else 1, hi, lo, self.cnt.data_ptr(),
+                                                        self.h2d.cuda_stream), 'luma_block_counts')
+            self.h_cnt.copy_(self.cnt, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.h2d)
+        ev.synchronize()
+        hot, warm = self.h_cnt.tolist()
+        return hot, warm
+
+    def keep(self, key, sl):
+        """The staged frame is kept: it is converted with the next batch's uploads."""
+        self._pending.append((key, sl))
+
+    def discard(self, key):
+        """The staged frame repeats the last kept one: its slot is recycled at once."""
+        self.slots.release(key)
 
     def begin(self, yuv, window_index, first_win):
         """A run starts; returns the frames to make resident before its first batch.  Scene cuts: the block's first window
@@ -239,6 +294,8 @@ class Y4mEdge:
 
     def uploaded(self, new, h2d):
         """Payloads copied to yuv_in[slot] -> BGR frame slots, one launch per run of consecutive slots; then the SADs."""
+        if self._pending:                            # --dedup: the kept frames staged since the last batch
+            new, self._pending = self._pending + list(new), []
         rn, yuv, sls = self.rn, self.yuv, [sl for _, sl in new]
         for s0, cnt in consecutive(sls):
             if self.lcode:                           # 4:2:2, 4:4:4, mono: strides in samples (16-bit) / bytes
@@ -297,7 +354,14 @@ class Y4mEdge:
         for wi, win in enumerate(wins):
             k = self.window_index(n + wi) if self.window_index is not None else win[2]
             last = yuv.with_s1(n + wi)
-            if det is None:
+            if self.kept is not None:                # --dedup: the plans of ``cadence`` over the kept frames; slots by kept index
+                kf = self.kept
+                sr, so = K.window_runs(k, self.r, kf.s, kf.n, det.is_cut if det is not None else None, self.full)
+                wr = [([slot_of[x] for x in S.runner_order(tup)], ts) for tup, ts in sr]
+                o = [(run, kind, j) for _, run, kind, j in so]
+                rn.cut_windows += int(K.is_cut_window(k, det.is_cut if det is not None else None))
+                kf.st_frames += sum(kind == R.ST for _, kind, _ in o)
+            elif det is None:
                 ts, o = R.window_plan(k, self.r, last, self.full)
                 wr, o = [(frames[wi], ts)], [(0, kind, j) for _, kind, j in o]
             else:
@@ -395,17 +459,98 @@ class Y4mEdge:
             pos += c
 
 
+def max_runs(r, cuts, dedup):
+    """Upper bound of the runs of one window of the Y4M edge: a cut window is two; with ``dedup`` = (hi, lo, frac, max_hold) a
+    window that spans several input frames is split into runs of at most ``retime.max_instants(r)`` instants."""
+    return max(2 if cuts else 1, K.max_window_runs(r, dedup[3]) if dedup is not None else 1)
+
+
+def pipeline_key(batch, y4m, cuts, full, depth=8, layout='420', dedup=None):
+    """What a cached ``ClipPipeline`` can be reused for."""
+    return (batch, y4m, cuts, full, depth, layout) + ((tuple(dedup),) if dedup is not None else ())
+
+
+class KeptFrames:
+    """``host_frames`` and ``windows`` of a --dedup run: the kept frames of an input (``y4m.Frames`` ``raw``), indexed by kept
+    index.  Pulling ``windows()`` reads the input: every frame is staged in a device slot and scored there against the last
+    kept frame (``Y4mEdge.stage`` / ``block_counts``), a repeat's slot is recycled at once, and window k is handed out when
+    ``cadence.ready`` says it can be planned -- B2 or the end of the input is known.  So the pipeline finds every frame a
+    window names already resident, and only kept frames occupy slots.  ``det``: the ``cadence.Detector``; ``s`` its kept
+    times, ``n`` the input's length once its end was seen, ``first_window`` the first window handed out, ``st_frames`` the St
+    frames planned."""
+
+    def __init__(self, raw, det, r, full_length=False):
+        self.raw, self.det, self.r, self.full = raw, det, Fraction(r), bool(full_length)
+        self.s, self.n, self.first_window, self.edge, self.ref, self.st_frames = det.kept, None, None, None, None, 0
+
+    def __getitem__(self, j):
+        raise IndexError('kept frame %d is not resident: --dedup stages every frame before a window names it' % j)
+
+    def index(self, j):
+        """Window index of the j-th window handed out."""
+        return self.first_window + j
+
+    def _probe(self):
+        """Examines the next input frame; False at the end of the input."""
+        det, i = self.det, self.det.next
+        if not self.raw.has(i):
+            self.n = i
+            return False
+        key = len(det.kept)
+        sl = self.edge.stage(key, i, self.raw[i])
+        if det.push(i, None if det.forced() else self.edge.block_counts(sl, self.ref)):
+            self.ref = sl
+            self.edge.keep(key, sl)
+        else:
+            self.edge.discard(key)
+        return True
+
+    def _know(self, k):
+        """Reads on until window k can be planned."""
+        while self.n is None:
+            if len(self.s) > k + 2 and not self.full:
+                self.raw.has(self.s[k + 2] + 2)      # read ahead only: is tau = s_{k+2} the last output?
+            if K.ready(k, self.s, self.raw.next, None, self.full) or not self._probe():
+                return
+
+    def windows(self):
+        """(B0, B1, B-1, B2), kept indices clamped at the ends of the kept sequence, of every window in order."""
+        while self.n is None and len(self.s) < 2:
+            self._probe()
+        if not self.s:
+            return
+        if len(self.s) == 1:                         # the end was seen: one kept frame, held
+            if R.n_output_frames(self.n, self.r, self.full) > 0:
+                self.first_window = -2
+                yield (0, 0, 0, 0)
+            return
+        k = -1
+        while True:
+            self._know(k)
+            if self.n is not None and k + 2 > len(self.s) - 1:
+                return
+            if K.window_outputs(k, self.r, self.s, self.n, self.full):
+                if self.first_window is None:
+                    self.first_window = k
+                yield S.runner_order(K.window_tuple(k, self.s, self.n))
+            elif self.first_window is not None:
+                return                               # past the last output
+            k += 1
+
+
 class ClipPipeline:
     """The batch loop of ``WindowRunner.run_clip_u8`` for one batch size and one edge (BGR, or Y4M with or without scene
     cuts / the full-length timeline, which size its buffers): H2D of a batch's new frames, its compute, the drain of the
     previous batch and its D2H, on three streams over two sets of output buffers."""
 
-    def __init__(self, runner, batch, y4m, cuts, full, depth=8, layout='420'):
+    def __init__(self, runner, batch, y4m, cuts, full, depth=8, layout='420', dedup=None):
         dev = self.dev = runner.engine.device
         runner = weakref.proxy(runner)               # the runner owns this pipeline: no reference cycle keeps its buffers alive
-        self.batch, self.key = batch, (batch, y4m, cuts, full, depth, layout)   # what a cached pipeline can be reused for
+        self.batch, self.key = batch, pipeline_key(batch, y4m, cuts, full, depth, layout, dedup)
         if depth > 8 and not y4m:
             raise ValueError('ClipPipeline: 16-bit frames are those of the Y4M edge only')
+        if dedup is not None and not y4m:
+            raise ValueError('ClipPipeline: repeated frames are found by the Y4M edge only')
         self.h2d, self.d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
         plan = runner.tiles
         fh, fw = (plan.h, plan.w) if plan is not None else (runner.h, runner.w)
@@ -413,16 +558,20 @@ class ClipPipeline:
         tiler = None
         if plan is not None:                         # frames stitched per batch: a run's J + 2 (a cut window is two runs), or M + 1
             J2 = (R.max_instants(runner.retime if runner.retime is not None else Fraction(runner.mfi)) + 2) if y4m else runner.mfi + 1
-            tiler = Tiler(plan, self.slots, runner.lib, dev, (2 * batch if cuts else batch) * J2)
-        self.edge = Y4mEdge(runner, batch, self.slots, cuts, full, tiler, depth, layout) if y4m else BgrEdge(runner, batch, self.slots, tiler)
+            rr = (runner.retime if runner.retime is not None else Fraction(runner.mfi)) if y4m else None
+            tiler = Tiler(plan, self.slots, runner.lib, dev, batch * (max_runs(rr, cuts, dedup) if y4m else 1) * J2)
+        self.edge = (Y4mEdge(runner, batch, self.slots, cuts, full, tiler, depth, layout, dedup, self.h2d) if y4m
+                     else BgrEdge(runner, batch, self.slots, tiler))
 
     def run(self, host_frames, windows, sink, reuse_frames, yuv, window_index):
+        edge, slots, h2d, cur = self.edge, self.slots, self.h2d, torch.cuda.current_stream(self.dev)
+        slots.reset()
+        if getattr(edge, 'dedup', None) is not None:  # --dedup: ``windows`` stages and scores frames as it is pulled
+            edge.attach(host_frames)
         it = iter(windows)
         wins = list(itertools.islice(it, self.batch))
         if not wins:
             return 0
-        edge, slots, h2d, cur = self.edge, self.slots, self.h2d, torch.cuda.current_stream(self.dev)
-        slots.reset()
         extra = edge.begin(yuv, window_index, wins[0])
         ev_d2h = [None, None]             # D2H of the batch that last wrote output buffer i
         pending = None                    # (buffer, first window, what edge.run returned) of the batch whose D2H is in flight

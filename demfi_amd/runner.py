@@ -24,7 +24,7 @@ import torch
 from . import _lib as L
 from . import retime as R
 from .harness import t_schedule
-from .pipeline import ClipPipeline, fill_sink_records
+from .pipeline import ClipPipeline, fill_sink_records, pipeline_key
 
 U16_DTYPES = tuple(d for d in (torch.int16, getattr(torch, 'uint16', None)) if d is not None)   # plain storage of 16-bit frames
 
@@ -593,9 +593,17 @@ class WindowRunner:
         uint8 tensor, of twice the bytes, and so are the payloads the sink gets); the frame slots and everything between the
         two conversions are 16-bit (csrc/yuv16.hip, ``_u16_io``).  Not with ``tiles``.
         ``yuv.layout`` ('420' when absent; ``y4m.LAYOUTS``): the payloads' chroma layout; 4:2:2, 4:4:4 and mono payloads are
-        converted by csrc/yuv_layouts.hip and the outputs keep the layout.  Returns the number of windows run."""
+        converted by csrc/yuv_layouts.hip and the outputs keep the layout.
+        ``yuv.dedup`` = (hi, lo, frac, max_hold) (None when absent; retimed runners only, with ``window_index``): repeated
+        frames are left out (``demfi_amd.cadence``).  host_frames is then a ``pipeline.KeptFrames`` over the input and ``windows``
+        its ``windows()``: frames and windows are named by kept index, every input frame is scored on the GPU as it is
+        uploaded (ONE ``demfi_luma_block_counts`` launch each), and window k runs ``cadence.window_runs``.
+        Returns the number of windows run."""
         cuts, full = getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False))
         depth, layout = int(getattr(yuv, 'depth', 8)), getattr(yuv, 'layout', '420')
+        dedup = getattr(yuv, 'dedup', None)
+        if dedup is not None and (self.retime is None or window_index is None or not reuse_frames):
+            raise ValueError('WindowRunner.run_clip_u8: repeated frames need a retimed runner (r = M for x M), window_index and reuse_frames')
         if depth > 8 and self.tiles is not None:
             raise ValueError('WindowRunner.run_clip_u8: tiles move 8-bit pixels; a %d-bit stream cannot run tiled' % depth)
         if self.retime is not None and yuv is None:
@@ -604,9 +612,9 @@ class WindowRunner:
             raise ValueError('WindowRunner.run_clip_u8: scene cuts need a retimed runner (r = M for x M) and reuse_frames')
         if full and (self.retime is None or window_index is None):
             raise ValueError('WindowRunner.run_clip_u8: the full-length timeline needs a retimed runner and window_index')
-        if self._pipeline is None or self._pipeline.key != (batch, yuv is not None, cuts, full, depth, layout):
+        if self._pipeline is None or self._pipeline.key != pipeline_key(batch, yuv is not None, cuts, full, depth, layout, dedup):
             self._pipeline = None                        # release the old buffers before the new ones are allocated
-            self._pipeline = ClipPipeline(self, batch, yuv is not None, cuts, full, depth, layout)
+            self._pipeline = ClipPipeline(self, batch, yuv is not None, cuts, full, depth, layout, dedup)
         return self._pipeline.run(host_frames, windows, sink, reuse_frames, yuv, window_index)
 
     def __del__(self):

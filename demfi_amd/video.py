@@ -41,12 +41,14 @@ from fractions import Fraction
 import torch
 
 from . import _lib as L
+from . import cadence as K
 from . import dist as D
 from . import retime as R
 from . import scene as S
 from . import tiling as T
 from . import y4m
 from .clip import ClipRunner
+from .pipeline import KeptFrames
 
 
 class YuvEdge:
@@ -54,9 +56,11 @@ class YuvEdge:
     window k (index in the runner's window sequence) close the stream, i.e. is its S1 written?  ``scene_cut``: None, or the
     threshold T of scene-cut detection (``demfi_amd.scene``).  ``full_length``: the full-length timeline (``retime``).
     ``depth``: bits per sample, 8, or 10 / 12 / 14 / 16 for payloads of 16-bit samples.  ``layout``: the payloads' chroma
-    layout, one of ``y4m.LAYOUTS`` (``siting`` only matters to '420')."""
+    layout, one of ``y4m.LAYOUTS`` (``siting`` only matters to '420').  ``dedup``: None, or (hi, lo, frac, max_hold) of
+    repeated-frame detection (``demfi_amd.cadence``)."""
 
-    def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420'):
+    def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None):
+        self.dedup = dedup
         self.depth = y4m.check_depth(depth)
         self.layout = y4m.check_layout(layout)
         self.matrix = {'bt601': L.BT601, 'bt709': L.BT709}[matrix]
@@ -83,10 +87,14 @@ class VideoRunner:
     8-bit stream gives the same bytes either way.  Not together with ``tile`` (tiles move 8-bit pixels).  ``layouts``: also take
     4:2:2, 4:4:4 and mono input (C422, C444, Cmono; with ``high_depth`` their deep forms C422pNN / C444pNN / CmonoNN) and give the
     output in the input's layout (``last_layout``); off by default, and a 4:2:0 stream gives the same bytes either way.  The 8-bit
-    layouts run with ``tile``, since tiles cut BGR frames."""
+    layouts run with ``tile``, since tiles cut BGR frames.  ``dedup``: None (default), True or (hi, lo, frac): input frames that
+    repeat the last kept frame (``demfi_amd.cadence``: no 8x8 luma block differs by more than hi, at most frac of them by more
+    than lo; True takes the defaults of ffmpeg's mpdecimate) are left out and the windows interpolate over the gap, at most
+    ``dedup_max_hold`` repeats in a row; the output's length and timing are unchanged.  ``last_dups`` lists the input frames
+    dropped.  One rank only: which frames are kept depends on the whole prefix of the input."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
-                 tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, **runner_kw):
+                 tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD, **runner_kw):
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
         if mfi is not None and fps is not None:
@@ -117,6 +125,12 @@ class VideoRunner:
         self.last_fps_out = None
         self.last_cuts = []
         self.last_cut_windows = 0
+        if dedup is None or dedup is False:
+            self.dedup = None
+            K.check_params(max_hold=dedup_max_hold)
+        else:
+            self.dedup = K.check_params(*(K.DEFAULTS if dedup is True else tuple(dedup)), max_hold=dedup_max_hold)
+        self.last_dups = []
 
     def _ratio(self, hdr):
         """The ratio r = F_out / F_in of this input: M for x M, whose per-window plans (``retime``) give exactly the x M stream."""
@@ -164,7 +178,18 @@ class VideoRunner:
 
     def _edge(self, hdr, with_s1):
         return YuvEdge(y4m.auto_matrix(hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
-                       self.scene_cut, self.full_length, hdr.depth, hdr.layout)
+                       self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup)
+
+    def _run_dedup(self, cr, hdr, frames, sink):
+        """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
+        det = K.Detector(hdr.h, hdr.w, *self.dedup)
+        kf = KeptFrames(frames, det, self._ratio(hdr), self.full_length)
+        n = self._run(cr, hdr, lambda: 0, lambda: cr.runner.run_clip_u8(kf, kf.windows(), sink, batch=self.batch,
+                                                                       yuv=self._edge(hdr, lambda j: False), window_index=kf.index))
+        self.last_st_frames, self.last_dups = kf.st_frames, list(det.dups)
+        self.last_cuts = [det.kept[j] for j in self.last_cuts]      # scored over the kept sequence: back to input frames
+        self.last_decode_peak = frames.peak
+        return n
 
     def run_stream(self, src, dst):
         """One rank, sequential binary streams (stdin / stdout work): nothing is seeked, the input is read in batches of
@@ -175,10 +200,15 @@ class VideoRunner:
         cr = self._clip_runner(hdr, 1, 0)
         wr = y4m.Writer(dst, self._out_header(hdr))
         frames = y4m.Frames(rd, full_length=self.full_length)
+        self.last_dups = []
 
         def sink(k, payloads):
             wr.write(payloads)
             dst.flush()
+        if self.dedup is not None:
+            n = self._run_dedup(cr, hdr, frames, sink)
+            dst.flush()
+            return n, wr.frames
         if self.full_length:                             # window j of the sequence is window first_window + j
             def index(j):
                 return frames.first_window + j
@@ -195,6 +225,10 @@ class VideoRunner:
         """Rank ``rank`` of ``world`` on regular files: one scan of the input's frame headers, this rank's block of windows
         (``dist.shard_windows``), its frames written at ``header + i*(6 + payload)``.  Rank 0 writes the header and sizes the
         output file; all ranks meet at a barrier before writing.  Returns (windows, frames written) of this rank."""
+        if self.dedup is not None and world > 1:
+            raise ValueError('VideoRunner: dedup with %d ranks: which frames are kept depends on the whole prefix of the input, so a rank '
+                             'cannot place its block of windows from k and r alone; run --dedup on one rank' % world)
+        self.last_dups = []
         with open(in_path, 'rb') as f:
             hdr, _, offs = y4m.scan(f, self.depths, self.layouts)
             self._check_depth(hdr)
@@ -209,6 +243,11 @@ class VideoRunner:
             D.barrier()
             cr = self._clip_runner(hdr, world, rank)
             full = self.full_length
+            if self.dedup is not None:
+                with open(out_path, 'r+b') as o:
+                    wr = y4m.Writer(o, ohdr, at=len(hb))
+                    n = self._run_dedup(cr, hdr, y4m.Frames.from_file(f, offs, 0, n_in, hdr.payload), lambda k, p: wr.write(p))
+                return n, wr.frames
             lo, wins = cr.my_windows(n_in, full)
             if not wins:
                 self.last_instants, self.last_st_frames, self.last_cuts, self.last_cut_windows = (0, 0), 0, [], 0
@@ -290,6 +329,15 @@ def parser():
                     help='also take 4:2:2, 4:4:4 and grey input (C422, C444, Cmono; together with --high-depth their 10- to 16-bit forms '
                          'C422pNN, C444pNN, CmonoNN) and write the output in the input\'s layout: nothing is resampled to 4:2:0 and back.  '
                          'Off by default (4:2:0 input only)')
+    ap.add_argument('--dedup', action='store_true',
+                    help='detect input frames that repeat the one before them (animation on twos and threes, 24p in a 30p or 60p '
+                         'container, captures with dropped frames) and interpolate over them: a frame is a repeat when no 8x8 luma '
+                         'block differs from the last kept frame by more than %d and at most %s of them by more than %d (the '
+                         'defaults of ffmpeg\'s mpdecimate).  The output keeps its length and timing.  One rank only.  Off by '
+                         'default' % (K.DEFAULT_HI, K.DEFAULT_FRAC, K.DEFAULT_LO))
+    ap.add_argument('--dedup-max-hold', type=int, default=K.DEFAULT_MAX_HOLD, metavar='N',
+                    help='with --dedup: after N repeats in a row the next frame is kept whatever it shows (default %d), so a still '
+                         'scene stays a sequence of frames N + 1 apart' % K.DEFAULT_MAX_HOLD)
     T.add_arguments(ap)
     return ap
 
@@ -305,6 +353,8 @@ def main(argv=None):
     if a.fps is None and a.mfi is None:
         a.mfi = 8
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
+    if world > 1 and a.dedup:
+        raise SystemExit('demfi_amd.video: --dedup runs on one rank (which frames are kept depends on the whole prefix of the input)')
     if world > 1 and not (_is_regular(a.input) and os.path.isfile(a.input) and _is_regular(a.output)):
         raise SystemExit('demfi_amd.video: with %d ranks IN and OUT must be regular files (ranks write at byte offsets)' % world)
     out_fd = None
@@ -326,7 +376,8 @@ def main(argv=None):
     model = model.to(dev).eval()
     D.broadcast_state_dict(model, world, device=dev)
     vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut, full_length=a.full_length,
-                     tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth, layouts=a.any_layout)
+                     tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth, layouts=a.any_layout, dedup=a.dedup or None,
+                     dedup_max_hold=a.dedup_max_hold)
     t0 = time.perf_counter()
     if world > 1:
         nw, nf = vr.run_file(a.input, a.output, world, rank)
@@ -352,7 +403,7 @@ def main(argv=None):
                           'St_frames_per_s': round(tst / dt, 2) if dt > 0 else None,
                           'frames_per_s': round(tf / dt, 2) if dt > 0 else None,
                           'fps_out': str(vr.last_fps_out) if vr.last_fps_out is not None else None,
-                          'instants_run': int(ti), 'instants_padded': int(tp), 'cut_windows': int(tc),
+                          'instants_run': int(ti), 'instants_padded': int(tp), 'cut_windows': int(tc), 'dups': len(vr.last_dups),
                           'tiles': vr.last_plan.n_tiles if vr.last_plan is not None else 1,
                           'tile': vr.last_plan.label() if vr.last_plan is not None else None, 'depth': vr.last_depth, 'layout': vr.last_layout,
                           'weights': os.path.basename(a.checkpoint) if a.checkpoint else 'synthetic_state_dict(0) (random init: no checkpoint given)',

@@ -417,6 +417,17 @@ int demfi_yuvl16_to_bgr16(const uint16_t* src, int64_t src_stride, uint16_t* dst
 int demfi_bgr16_to_yuvl16_gather(const uint16_t* base, const int64_t* src_offsets, uint16_t* dst, int64_t dst_stride, int n, int h,
                                  int w, int depth, int layout, int matrix, int full_range, void* stream);
 
+/* ---- repeated frames of the Y4M edge (csrc/dedup.hip; demfi_amd/video.py --dedup) ---------------------------------------------
+ * luma_block_counts: for pair i, frame a at base + a_offsets[i] against frame b at base + b_offsets[i] (n int64 BYTE offsets in
+ * DEVICE memory; even ones for 16-bit samples), over the luma plane = the first h*w samples of a payload, sample_bytes = 1
+ * (bytes) or 2 (16-bit little-endian samples).  The plane is cut into 8x8 blocks from the top-left corner (edge blocks are
+ * partial, area a < 64); with SAD = sum |a - b| over a block, the block is hot when 64*SAD > hi_s*a and warm when
+ * 64*SAD > lo_s*a, hi_s / lo_s = the thresholds times 2^(depth-8), 0 .. 2^40.  counts[2i] = hot blocks, counts[2i+1] = warm
+ * blocks of pair i (device memory, 2n uint32, zeroed on the stream first); exact integers, the numpy definition is
+ * demfi_amd/cadence.py block_counts_np.  Any h, w in 2..16384; one launch for n pairs; each frame of a pair is read once. */
+int demfi_luma_block_counts(const uint8_t* base, const int64_t* a_offsets, const int64_t* b_offsets, int n, int h, int w,
+                            int sample_bytes, int64_t hi_s, int64_t lo_s, uint32_t* counts, void* stream);
+
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
  * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
