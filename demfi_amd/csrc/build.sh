@@ -17,8 +17,8 @@ SRCS_CPP="abi.cpp"
 [ -f gru.hip ] && SRCS_HIP="$SRCS_HIP gru.hip"
 [ -f viz.hip ] && SRCS_HIP="$SRCS_HIP viz.hip"
 [ -f yuv.hip ] && SRCS_HIP="$SRCS_HIP yuv.hip"
-[ -f yuv16.hip ] && SRCS_HIP="$SRCS_HIP yuv16.hip"
-[ -f yuv_layouts.hip ] && SRCS_HIP="$SRCS_HIP yuv_layouts.hip"
+[ -f frames16.hip ] && SRCS_HIP="$SRCS_HIP frames16.hip"
+[ -f yuv_family.hip ] && SRCS_HIP="$SRCS_HIP yuv_family.hip"
 [ -f tile.hip ] && SRCS_HIP="$SRCS_HIP tile.hip"
 [ -f dedup.hip ] && SRCS_HIP="$SRCS_HIP dedup.hip"
 [ -f wsconv.hip ] && SRCS_HIP="$SRCS_HIP wsconv.hip"

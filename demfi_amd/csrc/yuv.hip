@@ -1,8 +1,9 @@
-// YUV 4:2:0 <-> BGR uint8 colour conversion of the Y4M stream edge (demfi_amd/video.py).
+// YUV 4:2:0 <-> BGR uint8 colour conversion of the Y4M stream edge (demfi_amd/video.py), the default path, and the SAD of its
+// scene-cut detection over either sample type.
 //
 // The definition is the numpy pair yuv420_to_bgr_np / bgr_to_yuv420_np in demfi_amd/y4m.py; these kernels match it bit for
-// bit.  Integer arithmetic only: Q16 matrix coefficients rounded from the float64 matrices (computed here by the same float64
-// expressions as in y4m.py, built with -ffp-contract=off), int32 accumulators, ONE round-half-up, clamp to [0, 255].
+// bit.  Integer arithmetic only: the d = 8 coefficients of yuv_common.h (Q16), int32 accumulators, ONE round-half-up, clamp to
+// [0, 255].
 //   upsampling (YUV -> BGR): chroma kept in 1/16 units -- 420jpeg: 9/3/3/1 over the 2x2 nearest chroma samples; 420mpeg2:
 //     co-sited horizontally (even x: the sample, odd x: 1/2 + 1/2), centred vertically (3/4 + 1/4); neighbours clamp to the edge;
 //   downsampling (BGR -> YUV, always 420jpeg): a 2x2 box over the full-resolution Q16 Cb / Cr, rounded once; at an odd edge the
@@ -11,70 +12,39 @@
 // Memory-bound on bytes: a lane owns a strip of 8 luma pixels x 2 rows (one chroma row): Y as one 8-byte access per row, the
 // 24 bytes of BGR per row as three 8-byte accesses, 4 bytes per chroma plane.  Strips that are cut by the right edge or whose
 // rows are not 8-byte aligned (widths that are not a multiple of 8) take the byte path; the data are the same.
-#include "common.h"
-#include <math.h>
+//
+// These kernels were shaped by hand around packed 64-bit words of bytes (see sat_shr and the strip macro below), so they keep byte
+// helpers of their own -- load8 / store8 / load_c6 and the uint64_t overloads of load_bgr8 / store_bgr8 -- beside the int-array
+// accessors of yuv_common.h that every other kernel of the edge uses (yuv_family.hip).
+#include "yuv_common.h"
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int SX = 8;                 // luma pixels per lane strip
-
-struct ToBgr {                        // Q16; chroma arrives in 1/16 units -> one shift by 20
+// What the 8-bit 4:2:0 kernels take: the d = 8 coefficients (Q16; chroma arrives in 1/16 units -> one shift by 20) without the
+// fields that are constants at 8 bits, so that the kernels' argument lists are what they were shaped around.
+struct ToBgr8 {
     int cy, r_cr, g_cb, g_cr, b_cb, yoff;
 };
-struct ToYuv {                        // Q16 over 8-bit B, G, R
+struct ToYuv8 {                       // Q16 over 8-bit B, G, R
     int y_r, y_g, y_b, cb_r, cb_g, cb_b, cr_r, cr_g, cr_b, yoff;
 };
 
-inline int fix16(double c) { return (int)floor(c * 65536.0 + 0.5); }
-
-inline void kr_kb(int matrix, double* kr, double* kb)
+ToBgr8 to_bgr_coefs8(int matrix, int full)
 {
-    if (matrix == DEMFI_BT709) { *kr = 0.2126; *kb = 0.0722; }
-    else { *kr = 0.299; *kb = 0.114; }
+    const ToBgr c = to_bgr_coefs(matrix, full, 8);
+    return ToBgr8{c.cy, c.r_cr, c.g_cb, c.g_cr, c.b_cb, c.yoff};
 }
 
-// y4m.py: to_bgr_coefs
-ToBgr to_bgr_coefs(int matrix, int full)
+ToYuv8 to_yuv_coefs8(int matrix, int full)
 {
-    double kr, kb;
-    kr_kb(matrix, &kr, &kb);
-    const double kg = 1.0 - kr - kb;
-    const double ys = full ? 1.0 : 255.0 / 219.0, cs = full ? 1.0 : 255.0 / 224.0;
-    ToBgr c;
-    c.cy = fix16(ys);
-    c.r_cr = fix16(cs * 2.0 * (1.0 - kr));
-    c.g_cb = fix16(-(cs * 2.0 * kb * (1.0 - kb) / kg));
-    c.g_cr = fix16(-(cs * 2.0 * kr * (1.0 - kr) / kg));
-    c.b_cb = fix16(cs * 2.0 * (1.0 - kb));
-    c.yoff = full ? 0 : 16;
-    return c;
-}
-
-// y4m.py: to_yuv_coefs
-ToYuv to_yuv_coefs(int matrix, int full)
-{
-    double kr, kb;
-    kr_kb(matrix, &kr, &kb);
-    const double kg = 1.0 - kr - kb;
-    const double ys = full ? 1.0 : 219.0 / 255.0, cs = full ? 1.0 : 224.0 / 255.0;
-    ToYuv c;
-    c.y_r = fix16(ys * kr);
-    c.y_g = fix16(ys * kg);
-    c.y_b = fix16(ys * kb);
-    c.cb_r = fix16(-(cs * kr / (2.0 * (1.0 - kb))));
-    c.cb_g = fix16(-(cs * kg / (2.0 * (1.0 - kb))));
-    c.cb_b = fix16(cs * 0.5);
-    c.cr_r = fix16(cs * 0.5);
-    c.cr_g = fix16(-(cs * kg / (2.0 * (1.0 - kr))));
-    c.cr_b = fix16(-(cs * kb / (2.0 * (1.0 - kr))));
-    c.yoff = full ? 0 : 16;
-    return c;
+    const ToYuv c = to_yuv_coefs(matrix, full, 8);
+    return ToYuv8{c.y_r, c.y_g, c.y_b, c.cb_r, c.cb_g, c.cb_b, c.cr_r, c.cr_g, c.cr_b, c.yoff};
 }
 
 // clamp255(acc >> S), written as a clamp of the accumulator and then the shift: the shift-then-saturate form is matched to
 // v_ashr_pk_u8_i32 on gfx950, which packs two results into the low half of a register and -- as the code came out -- left the
 // upper half's old bits in place, to be OR-ed into the neighbouring bytes of the packed word.  Same value for every acc.
+// (sat_shr<S>(acc), S a constant shift, is this one; sat_shr<A>(acc, sh, lim), A an accumulator type, is yuv_common.h's.)
 template <int S> __device__ __forceinline__ int sat_shr(int acc) { return min(max(acc, 0), (256 << S) - 1) >> S; }
 
 // 8 bytes row[x0 .. x0+7]; indices past the right edge repeat row[w-1]
@@ -150,7 +120,7 @@ __device__ __forceinline__ int byte_of(const uint64_t* q, int b) { return (int)(
 
 // one lane: chroma row cy (luma rows 2cy, 2cy+1) x luma columns x0 .. x0+7 of one frame
 __global__ __launch_bounds__(NT) void yuv420_to_bgr_kernel(const uint8_t* __restrict__ src, int64_t src_stride, uint8_t* __restrict__ dst,
-                                                          int64_t dst_stride, int n, int h, int w, int mpeg2, ToBgr k)
+                                                          int64_t dst_stride, int n, int h, int w, int mpeg2, ToBgr8 k)
 {
     const int cw = (w + 1) >> 1, ch = (h + 1) >> 1, ns = (w + SX - 1) / SX;
     const int id = blockIdx.x * NT + threadIdx.x;
@@ -247,7 +217,7 @@ _Pragma("unroll")                                                               
 
 __global__ __launch_bounds__(NT) void bgr_to_yuv420_kernel(const uint8_t* __restrict__ src, int64_t src_stride, int group,
                                                           int64_t group_stride, uint8_t* __restrict__ dst, int64_t dst_stride, int n,
-                                                          int h, int w, ToYuv k)
+                                                          int h, int w, ToYuv8 k)
 {
     const int cw = (w + 1) >> 1, ch = (h + 1) >> 1, ns = (w + SX - 1) / SX;
     const int id = blockIdx.x * NT + threadIdx.x;
@@ -263,7 +233,7 @@ __global__ __launch_bounds__(NT) void bgr_to_yuv420_kernel(const uint8_t* __rest
 // frame f read at base + offs[f]: one (wave-uniform) offset load per frame, the rest as bgr_to_yuv420_kernel
 __global__ __launch_bounds__(NT) void bgr_to_yuv420_gather_kernel(const uint8_t* __restrict__ base, const int64_t* __restrict__ offs,
                                                                  uint8_t* __restrict__ dst, int64_t dst_stride, int n, int h, int w,
-                                                                 ToYuv k)
+                                                                 ToYuv8 k)
 {
     const int cw = (w + 1) >> 1, ch = (h + 1) >> 1, ns = (w + SX - 1) / SX;
     const int id = blockIdx.x * NT + threadIdx.x;
@@ -273,39 +243,60 @@ __global__ __launch_bounds__(NT) void bgr_to_yuv420_gather_kernel(const uint8_t*
         DEMFI_BGR_TO_YUV420_STRIP(base + offs[f], dst + (int64_t)f * dst_stride);
 }
 
-// SAD of frame pair f: |a - b| summed over the payload, a = base + a_offs[f], b = base + b_offs[f], any byte alignment of either.
-// The bytes before a's first 16-byte boundary (head) and after its last one (tail) go to the first 16 lanes of block x = 0, one
-// byte each; the body is 16-byte loads, aligned for a (b's loads may be unaligned, which global memory serves) and four v_sad_u8
-// per load pair.  A lane's partial stays below 2^32 (at most ceil(payload / 16 / NT) * 16 * 255 < 2^32 for payloads up to
-// 16384 x 16384 4:2:0); the wave and block sums are 64-bit, and each block adds its sum with ONE 64-bit atomic (integer adds are
-// exact in any order).
-__global__ __launch_bounds__(NT) void yuv420_sad_kernel(const uint8_t* __restrict__ base, const int64_t* __restrict__ a_offs,
-                                                       const int64_t* __restrict__ b_offs, int n, int64_t payload,
-                                                       unsigned long long* __restrict__ sad)
+// ---- the SAD of scene-cut detection, over either sample type ------------------------------------------------------------------
+typedef u4_t u4_align1 __attribute__((aligned(1)));
+typedef u4_t u4_align2 __attribute__((aligned(2)));
+
+__device__ __forceinline__ uint32_t sad_one(uint8_t x, uint8_t y, uint32_t acc) { return __builtin_amdgcn_sad_u8(x, y, acc); }
+__device__ __forceinline__ uint32_t sad_one(uint16_t x, uint16_t y, uint32_t acc) { return __builtin_amdgcn_sad_u16(x, y, acc); }
+
+// 16 bytes at a (16-byte aligned) against 16 at b (sample-aligned, which global memory serves): four v_sad_u8 / v_sad_u16
+__device__ __forceinline__ uint32_t sad_vec(const uint8_t* a, const uint8_t* b, uint32_t acc)
 {
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    typedef u4 u4_unaligned __attribute__((aligned(1)));
+    const u4_t x = *(const DEMFI_GLOBAL u4_t*)a, y = *(const DEMFI_GLOBAL u4_align1*)b;
+    acc = __builtin_amdgcn_sad_u8(x.x, y.x, acc);
+    acc = __builtin_amdgcn_sad_u8(x.y, y.y, acc);
+    acc = __builtin_amdgcn_sad_u8(x.z, y.z, acc);
+    return __builtin_amdgcn_sad_u8(x.w, y.w, acc);
+}
+
+__device__ __forceinline__ uint32_t sad_vec(const uint16_t* a, const uint16_t* b, uint32_t acc)
+{
+    const u4_t x = *(const DEMFI_GLOBAL u4_t*)a, y = *(const DEMFI_GLOBAL u4_align2*)b;
+    acc = __builtin_amdgcn_sad_u16(x.x, y.x, acc);
+    acc = __builtin_amdgcn_sad_u16(x.y, y.y, acc);
+    acc = __builtin_amdgcn_sad_u16(x.z, y.z, acc);
+    return __builtin_amdgcn_sad_u16(x.w, y.w, acc);
+}
+
+// SAD of frame pair f: |a - b| summed over `samples` samples of T, a = base + a_offs[f], b = base + b_offs[f] (offsets in samples:
+// any sample alignment of either).  VS = 16 / sizeof(T) samples make one 16-byte vector.  The samples before a's first 16-byte
+// boundary (head) and after its last one (tail) go to the first VS lanes of block x = 0, one sample each; the body is one vector
+// per lane and step (sad_vec).  A lane's partial stays below 2^32: up to 1024 blocks a lane takes one vector, and where the grid is
+// cut at 1024 blocks it takes at most ceil(samples / VS / (1024 NT)) vectors of at most VS * (2^(8 sizeof(T)) - 1) each, which
+// is below 2^20 (uint8) and 2^28 (uint16) for any payload up to 2^29 samples (16384 x 16384 4:2:0 has 1.5 * 2^28).  The wave and
+// block sums are 64-bit, and each block adds its sum with ONE 64-bit atomic (integer adds are exact in any order).
+template <typename T>
+__global__ __launch_bounds__(NT) void yuv_sad_kernel(const T* __restrict__ base, const int64_t* __restrict__ a_offs,
+                                                    const int64_t* __restrict__ b_offs, int n, int64_t samples,
+                                                    unsigned long long* __restrict__ sad)
+{
+    constexpr int LB = sizeof(T) == 2 ? 1 : 0, LV = 4 - LB, VS = 1 << LV;      // log2 of bytes per sample, of samples per vector
     __shared__ unsigned long long part[NT / 64];
     const int tid = threadIdx.x;
     for (int f = blockIdx.y; f < n; f += gridDim.y) {
-        const uint8_t* a = base + a_offs[f];
-        const uint8_t* b = base + b_offs[f];
-        const int64_t head = min((int64_t)((16 - ((uintptr_t)a & 15)) & 15), payload);
-        const int64_t nvec = (payload - head) >> 4;
-        const int64_t tail = head + (nvec << 4);              // payload - tail < 16
+        const T* a = base + a_offs[f];
+        const T* b = base + b_offs[f];
+        const int64_t head = min((int64_t)(((16 - ((uintptr_t)a & 15)) & 15) >> LB), samples);
+        const int64_t nvec = (samples - head) >> LV;
+        const int64_t tail = head + (nvec << LV);             // samples - tail < VS
         uint32_t acc = 0;
-        if (blockIdx.x == 0 && tid < 16) {
-            if (tid < head) acc = __builtin_amdgcn_sad_u8(gcp<uint8_t>(a)[tid], gcp<uint8_t>(b)[tid], acc);
-            if (tail + tid < payload) acc = __builtin_amdgcn_sad_u8(gcp<uint8_t>(a)[tail + tid], gcp<uint8_t>(b)[tail + tid], acc);
+        if (blockIdx.x == 0 && tid < VS) {
+            if (tid < head) acc = sad_one(gcp<T>(a)[tid], gcp<T>(b)[tid], acc);
+            if (tail + tid < samples) acc = sad_one(gcp<T>(a)[tail + tid], gcp<T>(b)[tail + tid], acc);
         }
-        for (int64_t v = (int64_t)blockIdx.x * NT + tid; v < nvec; v += (int64_t)gridDim.x * NT) {
-            const u4 x = *(const DEMFI_GLOBAL u4*)(a + head + 16 * v);
-            const u4 y = *(const DEMFI_GLOBAL u4_unaligned*)(b + head + 16 * v);
-            acc = __builtin_amdgcn_sad_u8(x.x, y.x, acc);
-            acc = __builtin_amdgcn_sad_u8(x.y, y.y, acc);
-            acc = __builtin_amdgcn_sad_u8(x.z, y.z, acc);
-            acc = __builtin_amdgcn_sad_u8(x.w, y.w, acc);
-        }
+        for (int64_t v = (int64_t)blockIdx.x * NT + tid; v < nvec; v += (int64_t)gridDim.x * NT)
+            acc = sad_vec(a + head + VS * v, b + head + VS * v, acc);
         unsigned long long s = acc;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
@@ -321,21 +312,21 @@ __global__ __launch_bounds__(NT) void yuv420_sad_kernel(const uint8_t* __restric
     }
 }
 
-int check_common(const char* fn, const void* src, const void* dst, int n, int h, int w, int matrix, int full_range)
+template <typename T>
+int yuv_sad(const char* fn, const T* base, const int64_t* a_offsets, const int64_t* b_offsets, int n, int64_t samples, uint64_t* sad,
+            void* stream)
 {
-    if (!src || !dst || n < 0)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer or n=%d", fn, n);
-    if (h < 2 || w < 2 || h > 16384 || w > 16384)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: frame size %dx%d outside 2..16384", fn, h, w);
-    if ((matrix != DEMFI_BT601 && matrix != DEMFI_BT709) || (full_range != 0 && full_range != 1))
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: matrix %d / full_range %d", fn, matrix, full_range);
+    if (!base || !a_offsets || !b_offsets || !sad || n < 0 || samples <= 0 || ((uintptr_t)base & (sizeof(T) - 1)))
+        return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL%s buffer, n=%d or %s=%lld", fn, sizeof(T) == 2 ? " or odd" : "", n,
+                               sizeof(T) == 2 ? "samples" : "payload", (long long)samples);
+    if (n == 0) return DEMFI_OK;
+    DEMFI_HIP_CHECK(hipMemsetAsync(sad, 0, (size_t)n * sizeof(uint64_t), (hipStream_t)stream));
+    const int64_t blocks = (samples * (int64_t)sizeof(T) / 16 + NT - 1) / NT;
+    const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks > 1024 ? 1024 : blocks), (unsigned)(n < 65535 ? n : 65535));
+    hipLaunchKernelGGL(yuv_sad_kernel<T>, grid, dim3(NT), 0, (hipStream_t)stream, base, a_offsets, b_offsets, n, samples,
+                       (unsigned long long*)sad);
+    DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
-}
-
-dim3 grid_for(int n, int h, int w)
-{
-    const int64_t lanes = (int64_t)((h + 1) / 2) * ((w + SX - 1) / SX);
-    return dim3((unsigned)((lanes + NT - 1) / NT), (unsigned)min(n, 65535));
 }
 
 }  // namespace
@@ -343,17 +334,17 @@ dim3 grid_for(int n, int h, int w)
 extern "C" int demfi_yuv420_to_bgr(const uint8_t* src, int64_t src_stride, uint8_t* dst, int64_t dst_stride, int n, int h, int w,
                                    int matrix, int full_range, int siting, void* stream)
 {
-    int st = check_common("demfi_yuv420_to_bgr", src, dst, n, h, w, matrix, full_range);
+    int st = check_args("demfi_yuv420_to_bgr", src, dst, n, h, w, 8, matrix, full_range, 1);
     if (st < 0) return st;
-    const int64_t payload = (int64_t)h * w + 2 * (int64_t)((h + 1) / 2) * ((w + 1) / 2);
+    const int64_t payload = payload_of(DEMFI_YUV_420, h, w);
     if (siting != DEMFI_420JPEG && siting != DEMFI_420MPEG2)
         return demfi_set_error(DEMFI_ERR_ARG, "demfi_yuv420_to_bgr: chroma siting %d", siting);
     if (n > 1 && (src_stride < payload || dst_stride < (int64_t)h * w * 3))
         return demfi_set_error(DEMFI_ERR_ARG, "demfi_yuv420_to_bgr: strides %lld / %lld below the frame sizes %lld / %lld",
                                (long long)src_stride, (long long)dst_stride, (long long)payload, (long long)h * w * 3);
     if (n == 0) return DEMFI_OK;
-    hipLaunchKernelGGL(yuv420_to_bgr_kernel, grid_for(n, h, w), dim3(NT), 0, (hipStream_t)stream, src, src_stride, dst, dst_stride, n, h,
-                       w, siting == DEMFI_420MPEG2 ? 1 : 0, to_bgr_coefs(matrix, full_range));
+    hipLaunchKernelGGL(yuv420_to_bgr_kernel, grid_for(n, (h + 1) / 2, w), dim3(NT), 0, (hipStream_t)stream, src, src_stride, dst,
+                       dst_stride, n, h, w, siting == DEMFI_420MPEG2 ? 1 : 0, to_bgr_coefs8(matrix, full_range));
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }
@@ -361,17 +352,17 @@ extern "C" int demfi_yuv420_to_bgr(const uint8_t* src, int64_t src_stride, uint8
 extern "C" int demfi_bgr_to_yuv420(const uint8_t* src, int64_t src_stride, int group, int64_t group_stride, uint8_t* dst,
                                    int64_t dst_stride, int n, int h, int w, int matrix, int full_range, void* stream)
 {
-    int st = check_common("demfi_bgr_to_yuv420", src, dst, n, h, w, matrix, full_range);
+    int st = check_args("demfi_bgr_to_yuv420", src, dst, n, h, w, 8, matrix, full_range, 1);
     if (st < 0) return st;
-    const int64_t payload = (int64_t)h * w + 2 * (int64_t)((h + 1) / 2) * ((w + 1) / 2);
+    const int64_t payload = payload_of(DEMFI_YUV_420, h, w);
     if (group <= 0) group = n > 0 ? n : 1;
     if (n > 1 && (dst_stride < payload || (group > 1 && src_stride < (int64_t)h * w * 3) ||
                   (n > group && group_stride < (int64_t)(group - 1) * src_stride + (int64_t)h * w * 3)))
         return demfi_set_error(DEMFI_ERR_ARG, "demfi_bgr_to_yuv420: strides %lld / %lld (group %d) / %lld below the frame sizes",
                                (long long)src_stride, (long long)group_stride, group, (long long)dst_stride);
     if (n == 0) return DEMFI_OK;
-    hipLaunchKernelGGL(bgr_to_yuv420_kernel, grid_for(n, h, w), dim3(NT), 0, (hipStream_t)stream, src, src_stride, group, group_stride,
-                       dst, dst_stride, n, h, w, to_yuv_coefs(matrix, full_range));
+    hipLaunchKernelGGL(bgr_to_yuv420_kernel, grid_for(n, (h + 1) / 2, w), dim3(NT), 0, (hipStream_t)stream, src, src_stride, group,
+                       group_stride, dst, dst_stride, n, h, w, to_yuv_coefs8(matrix, full_range));
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }
@@ -379,17 +370,17 @@ extern "C" int demfi_bgr_to_yuv420(const uint8_t* src, int64_t src_stride, int g
 extern "C" int demfi_bgr_to_yuv420_gather(const uint8_t* base, const int64_t* src_offsets, uint8_t* dst, int64_t dst_stride, int n,
                                           int h, int w, int matrix, int full_range, void* stream)
 {
-    int st = check_common("demfi_bgr_to_yuv420_gather", base, dst, n, h, w, matrix, full_range);
+    int st = check_args("demfi_bgr_to_yuv420_gather", base, dst, n, h, w, 8, matrix, full_range, 1);
     if (st < 0) return st;
     if (!src_offsets)
         return demfi_set_error(DEMFI_ERR_ARG, "demfi_bgr_to_yuv420_gather: NULL src_offsets");
-    const int64_t payload = (int64_t)h * w + 2 * (int64_t)((h + 1) / 2) * ((w + 1) / 2);
+    const int64_t payload = payload_of(DEMFI_YUV_420, h, w);
     if (n > 1 && dst_stride < payload)
         return demfi_set_error(DEMFI_ERR_ARG, "demfi_bgr_to_yuv420_gather: dst_stride %lld below the payload %lld",
                                (long long)dst_stride, (long long)payload);
     if (n == 0) return DEMFI_OK;
-    hipLaunchKernelGGL(bgr_to_yuv420_gather_kernel, grid_for(n, h, w), dim3(NT), 0, (hipStream_t)stream, base, src_offsets, dst, dst_stride,
-                       n, h, w, to_yuv_coefs(matrix, full_range));
+    hipLaunchKernelGGL(bgr_to_yuv420_gather_kernel, grid_for(n, (h + 1) / 2, w), dim3(NT), 0, (hipStream_t)stream, base, src_offsets, dst,
+                       dst_stride, n, h, w, to_yuv_coefs8(matrix, full_range));
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }
@@ -397,14 +388,11 @@ extern "C" int demfi_bgr_to_yuv420_gather(const uint8_t* base, const int64_t* sr
 extern "C" int demfi_yuv420_sad(const uint8_t* base, const int64_t* a_offsets, const int64_t* b_offsets, int n, int64_t payload,
                                 uint64_t* sad, void* stream)
 {
-    if (!base || !a_offsets || !b_offsets || !sad || n < 0 || payload <= 0)
-        return demfi_set_error(DEMFI_ERR_ARG, "demfi_yuv420_sad: NULL buffer, n=%d or payload=%lld", n, (long long)payload);
-    if (n == 0) return DEMFI_OK;
-    DEMFI_HIP_CHECK(hipMemsetAsync(sad, 0, (size_t)n * sizeof(uint64_t), (hipStream_t)stream));
-    const int64_t blocks = ((payload >> 4) + NT - 1) / NT;
-    const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks > 1024 ? 1024 : blocks), (unsigned)(n < 65535 ? n : 65535));
-    hipLaunchKernelGGL(yuv420_sad_kernel, grid, dim3(NT), 0, (hipStream_t)stream, base, a_offsets, b_offsets, n, payload,
-                       (unsigned long long*)sad);
-    DEMFI_HIP_CHECK(hipGetLastError());
-    return DEMFI_OK;
+    return yuv_sad<uint8_t>("demfi_yuv420_sad", base, a_offsets, b_offsets, n, payload, sad, stream);
+}
+
+extern "C" int demfi_yuv420p16_sad(const uint16_t* base, const int64_t* a_offsets, const int64_t* b_offsets, int n, int64_t samples,
+                                   uint64_t* sad, void* stream)
+{
+    return yuv_sad<uint16_t>("demfi_yuv420p16_sad", base, a_offsets, b_offsets, n, samples, sad, stream);
 }

@@ -193,15 +193,15 @@ class Y4mEdge:
     launch per batch puts the outputs in stream order.  ``full``: the full-length timeline of ``retime``.
     ``depth`` > 8: payloads of 16-bit samples at that bit depth.  The payload buffers stay uint8 tensors sized in bytes (what the
     host hands over and gets back); the frame slots and ``comb`` are int16 storage of the uint16 frames, the three launches
-    are those of csrc/yuv16.hip (strides and offsets in samples), the egress is the emit path and the SADs count samples.
+    are the 16-bit ones (strides and offsets in samples), the egress is the emit path and the SADs count samples.
     ``layout``: the payloads' chroma layout (``y4m.LAYOUTS``): it sets P, and for 4:2:2, 4:4:4 and mono the two conversion
-    launches are those of csrc/yuv_layouts.hip; everything between them sees BGR frames."""
+    launches are those of the layouts family; everything between them sees BGR frames.  ``yuv_calls`` picks the launches."""
 
     def __init__(self, runner, batch, slots, cuts, full, tiler=None, depth=8, layout='420', dedup=None, h2d=None):
         self.rn, self.slots, self.cuts, self.full, self.tiler = runner, slots, cuts, full, tiler
         self.dedup, self.h2d, self.kept, self._pending = dedup, h2d, None, []
         self.depth, self.hi = depth, depth > 8
-        self.layout, self.lcode = layout, L.YUV_LAYOUT[layout]
+        self.layout = layout
         if self.hi and tiler is not None:
             raise ValueError('Y4mEdge: tiles move 8-bit pixels; a %d-bit stream cannot run tiled' % depth)
         es, fdt = (2, torch.int16) if self.hi else (1, torch.uint8)      # bytes per sample; storage of a frame value
@@ -227,7 +227,7 @@ class Y4mEdge:
         self.yuv_out = [torch.empty((nout, Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.h_yuv = [torch.empty((nout, Pb), dtype=torch.uint8).pin_memory() for _ in range(2)]
         if cuts:                                     # SADs of a batch's new frames (at most nsl) against their predecessors
-            self.sad = torch.empty(nsl, dtype=torch.int64, device=dev)
+            self.d_sad = torch.empty(nsl, dtype=torch.int64, device=dev)
             self.sad_offs = torch.empty(2 * nsl, dtype=torch.int64, device=dev)
             self.h_sad = torch.empty(nsl, dtype=torch.int64).pin_memory()
         if dedup is not None:                        # block counts of one (frame, last kept frame) pair; pinned buffers are reused:
@@ -235,7 +235,7 @@ class Y4mEdge:
             self.cnt_offs = torch.empty(2, dtype=torch.int64, device=dev)
             self.h_cnt = torch.empty(2, dtype=torch.int32).pin_memory()
             self.h_cnt_offs = torch.empty(2, dtype=torch.int64).pin_memory()
-        self.yuv = self.window_index = self.det = None
+        self.yuv = self.window_index = self.det = self.to_bgr = self.gather = self.sad = None
 
     # ---- repeated frames (``cadence``): the windows generator (``KeptFrames``) stages, scores and keeps frames through these ----
     def attach(self, kept):
@@ -280,6 +280,7 @@ class Y4mEdge:
         """A run starts; returns the frames to make resident before its first batch.  Scene cuts: the block's first window
         k0 >= 1 also needs frame k0 - 1, the predecessor SAD_k0 is taken against."""
         self.yuv, self.window_index, self.det = yuv, window_index, None
+        self.to_bgr, self.gather, self.sad = yuv_calls(self.rn.lib, self.depth, self.layout, self.fh, self.fw, yuv)
         if not self.cuts:
             return ()
         det = self.det = S.Detector(self.P, yuv.scene_cut, first=S.first_frame(window_index(0) if window_index is not None else first_win[2]),
@@ -296,24 +297,9 @@ class Y4mEdge:
         """Payloads copied to yuv_in[slot] -> BGR frame slots, one launch per run of consecutive slots; then the SADs."""
         if self._pending:                            # --dedup: the kept frames staged since the last batch
             new, self._pending = self._pending + list(new), []
-        rn, yuv, sls = self.rn, self.yuv, [sl for _, sl in new]
+        sls = [sl for _, sl in new]
         for s0, cnt in consecutive(sls):
-            if self.lcode:                           # 4:2:2, 4:4:4, mono: strides in samples (16-bit) / bytes
-                src, dst, F = self.yuv_in[s0].data_ptr(), self.slots.frames[s0].data_ptr(), self.fh * self.fw * 3
-                if self.hi:
-                    L.check(rn.lib.demfi_yuvl16_to_bgr16(src, self.P, dst, F, cnt, self.fh, self.fw, self.depth, self.lcode, yuv.matrix,
-                                                         int(yuv.full_range), h2d.cuda_stream), 'yuvl16_to_bgr16')
-                else:
-                    L.check(rn.lib.demfi_yuvl_to_bgr(src, self.P, dst, F, cnt, self.fh, self.fw, self.lcode, yuv.matrix,
-                                                     int(yuv.full_range), h2d.cuda_stream), 'yuvl_to_bgr')
-                continue
-            if self.hi:                              # strides in samples
-                L.check(rn.lib.demfi_yuv420p16_to_bgr16(self.yuv_in[s0].data_ptr(), self.P, self.slots.frames[s0].data_ptr(),
-                                                        self.fh * self.fw * 3, cnt, self.fh, self.fw, self.depth, yuv.matrix,
-                                                        int(yuv.full_range), yuv.siting, h2d.cuda_stream), 'yuv420p16_to_bgr16')
-                continue
-            L.check(rn.lib.demfi_yuv420_to_bgr(self.yuv_in[s0].data_ptr(), self.P, self.slots.frames[s0].data_ptr(), self.fh * self.fw * 3,
-                                               cnt, self.fh, self.fw, yuv.matrix, int(yuv.full_range), yuv.siting, h2d.cuda_stream), 'yuv420_to_bgr')
+            self.to_bgr(self.yuv_in[s0].data_ptr(), self.slots.frames[s0].data_ptr(), cnt, h2d.cuda_stream)
         if self.tiler:
             self.tiler.crop(sls, h2d)
         if self.det is not None:
@@ -337,9 +323,8 @@ class Y4mEdge:
         offs = [slot_of[j - 1] * P for j in js] + [slot_of[j] * P for j in js]
         od = self.sad_offs[:2 * m]
         od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
-        sad = self.rn.lib.demfi_yuv420p16_sad if self.hi else self.rn.lib.demfi_yuv420_sad      # offsets and P: samples / bytes
-        L.check(sad(self.yuv_in.data_ptr(), od.data_ptr(), od[m:].data_ptr(), m, P, self.sad.data_ptr(), h2d.cuda_stream), 'yuv420_sad')
-        self.h_sad[:m].copy_(self.sad[:m], non_blocking=True)
+        self.sad(self.yuv_in.data_ptr(), od.data_ptr(), od[m:].data_ptr(), m, self.d_sad.data_ptr(), h2d.cuda_stream)
+        self.h_sad[:m].copy_(self.d_sad[:m], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(h2d)
         ev.synchronize()
@@ -422,7 +407,7 @@ class Y4mEdge:
     def _gather(self, i, outs, cur):
         """Outputs of a batch (comb[i]) -> yuv_out[i] in stream order: ONE gather launch on the compute stream.  outs[w]:
         window w's outputs as (run, kind, instant index).  Returns the number of payloads per window."""
-        rn, yuv, comb, dst, J = self.rn, self.yuv, self.comb[i], self.yuv_out[i], self.J
+        comb, dst, J = self.comb[i], self.yuv_out[i], self.J
         c0, c1 = comb.stride()[:2]
         offs = [run * c0 + (0 if kind == R.S0 else J + 1 if kind == R.S1 else 1 + j) * c1 for o in outs for run, kind, j in o]
         nf = len(offs)
@@ -430,22 +415,7 @@ class Y4mEdge:
             raise RuntimeError('retime: %d outputs for %d payload slots' % (nf, dst.shape[0]))
         od = self.offs[i][:nf]
         od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
-        if self.lcode:                               # 4:2:2, 4:4:4, mono; the payload stride P counts samples (16-bit) / bytes
-            if self.hi:
-                L.check(rn.lib.demfi_bgr16_to_yuvl16_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), self.P, nf, self.fh, self.fw,
-                                                            self.depth, self.lcode, yuv.matrix, int(yuv.full_range), cur.cuda_stream),
-                        'bgr16_to_yuvl16_gather')
-            else:
-                L.check(rn.lib.demfi_bgr_to_yuvl_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), self.P, nf, self.fh, self.fw,
-                                                        self.lcode, yuv.matrix, int(yuv.full_range), cur.cuda_stream), 'bgr_to_yuvl_gather')
-            return [len(o) for o in outs]
-        if self.hi:                                  # comb's element strides are samples; so is the payload stride
-            L.check(rn.lib.demfi_bgr16_to_yuv420p16_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), self.P, nf, self.fh, self.fw,
-                                                           self.depth, yuv.matrix, int(yuv.full_range), cur.cuda_stream),
-                    'bgr16_to_yuv420p16_gather')
-            return [len(o) for o in outs]
-        L.check(rn.lib.demfi_bgr_to_yuv420_gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), dst.shape[1], nf, self.fh, self.fw,
-                                                  yuv.matrix, int(yuv.full_range), cur.cuda_stream), 'bgr_to_yuv420_gather')
+        self.gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), nf, cur.cuda_stream)
         return [len(o) for o in outs]
 
     def d2h(self, i, counts):
@@ -457,6 +427,34 @@ class Y4mEdge:
         for j, c in enumerate(counts):
             sink(k0 + j, self.h_yuv[i][pos:pos + c])
             pos += c
+
+
+def yuv_calls(lib, depth, layout, h, w, yuv):
+    """The three launches of the Y4M edge for h x w frames of (depth, layout), bound to the stream's matrix, range and siting
+    (``yuv``): to_bgr(src, dst, cnt, stream) converts cnt consecutive payloads to BGR frames, gather(base, offs, dst, n, stream)
+    converts the n frames at base + offs[] to consecutive payloads, sad(base, a, b, m, out, stream) scores m payload pairs.
+    Pointers are addresses; every stride and offset counts samples, which are bytes at depth 8.  4:2:0 has C functions of its own
+    (8-bit: csrc/yuv.hip), 4:2:2, 4:4:4 and mono those of the layouts family, which take the layout code; the 16-bit functions
+    take the depth; only 4:2:0 has a siting."""
+    hi, lc, P, F = depth > 8, L.YUV_LAYOUT[layout], payload_size(h, w, layout), h * w * 3
+    if lc:
+        names = ('yuvl16_to_bgr16', 'bgr16_to_yuvl16_gather') if hi else ('yuvl_to_bgr', 'bgr_to_yuvl_gather')
+    else:
+        names = ('yuv420p16_to_bgr16', 'bgr16_to_yuv420p16_gather') if hi else ('yuv420_to_bgr', 'bgr_to_yuv420_gather')
+    names += ('yuv420p16_sad' if hi else 'yuv420_sad',)
+    c_bgr, c_gather, c_sad = (getattr(lib, 'demfi_' + nm) for nm in names)
+    fmt = ((depth,) if hi else ()) + ((lc,) if lc else ()) + (yuv.matrix, int(yuv.full_range))
+    site = () if lc else (yuv.siting,)
+
+    def to_bgr(src, dst, cnt, stream):
+        L.check(c_bgr(src, P, dst, F, cnt, h, w, *fmt, *site, stream), names[0])
+
+    def gather(base, offs, dst, n, stream):
+        L.check(c_gather(base, offs, dst, P, n, h, w, *fmt, stream), names[1])
+
+    def sad(base, a, b, m, out, stream):
+        L.check(c_sad(base, a, b, m, P, out, stream), names[2])
+    return to_bgr, gather, sad
 
 
 def max_runs(r, cuts, dedup):

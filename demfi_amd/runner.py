@@ -591,9 +591,9 @@ class WindowRunner:
         ``instants_run`` / ``instants_padded`` count those.
         ``yuv.depth`` > 8 (10, 12, 14, 16): the payloads hold 16-bit little-endian samples (host_frames[i] is still a 1-D
         uint8 tensor, of twice the bytes, and so are the payloads the sink gets); the frame slots and everything between the
-        two conversions are 16-bit (csrc/yuv16.hip, ``_u16_io``).  Not with ``tiles``.
+        two conversions are 16-bit (csrc/yuv_family.hip, ``_u16_io``).  Not with ``tiles``.
         ``yuv.layout`` ('420' when absent; ``y4m.LAYOUTS``): the payloads' chroma layout; 4:2:2, 4:4:4 and mono payloads are
-        converted by csrc/yuv_layouts.hip and the outputs keep the layout.
+        converted by csrc/yuv_family.hip and the outputs keep the layout.
         ``yuv.dedup`` = (hi, lo, frac, max_hold) (None when absent; retimed runners only, with ``window_index``): repeated
         frames are left out (``demfi_amd.cadence``).  host_frames is then a ``pipeline.KeptFrames`` over the input and ``windows``
         its ``windows()``: frames and windows are named by kept index, every input frame is scored on the GPU as it is

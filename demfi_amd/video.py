@@ -23,14 +23,14 @@ frames at their byte offsets of the output file (no collective on the data path)
 
 ``--high-depth`` also takes 10-, 12-, 14- and 16-bit 4:2:0 (C420p10 .. C420p16: 16-bit little-endian samples, what
 ``ffmpeg -pix_fmt yuv420p10le -strict -1 -f yuv4mpegpipe`` writes) and gives the output at the input's depth: the same path on
-16-bit frames (csrc/yuv16.hip, ``y4m.yuv420_to_bgr16_np`` / ``y4m.bgr16_to_yuv420_np``) from the payload to the network's input and
+16-bit frames (csrc/yuv_family.hip, ``y4m.yuv420_to_bgr16_np`` / ``y4m.bgr16_to_yuv420_np``) from the payload to the network's input and
 from its fp32 output frames back; only the fused uint8 store of the fp16 engine is replaced by one egress kernel per frame.
 With ``--dtype fp16`` the network's input record and features are fp16, which resolves 10-bit video fully and about 12 bits at
 best near the ends of the range; ``--dtype fp32`` carries all 16 bits.
 
 ``--any-layout`` also takes 4:2:2, 4:4:4 and grey streams (C422, C444, Cmono, what ``ffmpeg -pix_fmt yuv422p / yuv444p / gray -f
 yuv4mpegpipe`` writes; together with ``--high-depth`` their 10- to 16-bit forms C422pNN, C444pNN, CmonoNN) and gives the output in
-the input's layout and depth.  Only the two conversions at the edge know the layout (csrc/yuv_layouts.hip, ``y4m.yuv_to_bgr_np`` /
+the input's layout and depth.  Only the two conversions at the edge know the layout (csrc/yuv_family.hip, ``y4m.yuv_to_bgr_np`` /
 ``y4m.bgr_to_yuv_np`` and their 16-bit forms): the payload of P samples becomes the same BGR frame slots, and retiming, scene cuts
 (scored over the payload's P samples), the full-length timeline, tiles (8-bit layouts) and rank sharding run as they do for 4:2:0.
 """

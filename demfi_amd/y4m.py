@@ -1,34 +1,32 @@
-"""YUV4MPEG2 (Y4M) stream I/O and the definition of the YUV 4:2:0 <-> BGR conversion of the video edge (demfi_amd/video.py).
+"""YUV4MPEG2 (Y4M) stream I/O and the definition of the YUV <-> BGR conversion of the video edge (demfi_amd/video.py).
 
 Y4M is what video tools pass through pipes (``ffmpeg -f yuv4mpegpipe``, x264 / x265 / SVT-AV1 ``--input-y4m``, mpv): one text
-header line, then per frame ``FRAME[ params]\\n`` and the raw payload -- for 8-bit 4:2:0 the Y plane [h,w] followed by the Cb
-and Cr planes [ceil(h/2), ceil(w/2)], 1.5 bytes per pixel.
+header line, then per frame ``FRAME[ params]\\n`` and the raw payload.
 
-``yuv420_to_bgr_np`` / ``bgr_to_yuv420_np`` DEFINE the colour conversion; the HIP kernels ``demfi_yuv420_to_bgr`` /
-``demfi_bgr_to_yuv420`` (csrc/yuv.hip) match them bit for bit.  Integer arithmetic only:
-  * Q16 matrix coefficients rounded (half up) from the float64 BT.601 / BT.709 matrices, limited (Y 16-235, C 16-240) or
-    full range folded in; int32 accumulators, ONE round-half-up, clamp to [0, 255];
-  * upsampling keeps chroma in 1/16 units into the matrix: 420jpeg (centred) 9/3/3/1 over 16, 420mpeg2 (co-sited
-    horizontally, centred vertically) 1/2 + 1/2 at odd columns and 3/4 + 1/4 vertically; neighbours clamp to the edge;
-  * downsampling (output is always 420jpeg) is a 2x2 box over the full-resolution Q16 Cb / Cr, rounded once; at an odd
-    edge the clamped neighbour repeats the pixel that exists, i.e. the 2 or 1 pixels there are averaged.
-Frames are uint8 [h,w,3] in B, G, R order, the frame order of the whole pipeline (cv2's).
+``yuv_to_bgr16_np`` / ``bgr16_to_yuv_np`` DEFINE the colour conversion, for every chroma layout of ``LAYOUTS`` and every bit
+depth d of ``DEPTHS``; the HIP kernels (csrc/yuv.hip: 8-bit 4:2:0; csrc/yuv_family.hip: the rest; csrc/yuv_common.h: what they
+share) match them bit for bit.  Samples and frame values hold 0 .. peak = 2^d - 1.  Integer arithmetic only; with s = 2^(d-8):
+  * Q(8+d) matrix coefficients rounded (half up) from the float64 BT.601 / BT.709 matrices, with limited (Y 16s .. 235s,
+    C 16s .. 240s; scale factors peak / (219 s), peak / (224 s) and their inverses) or full range folded in; the Y offset is
+    16s, the chroma centre 2^(d-1); int64 accumulators (at d = 8 every sum fits int32, which is what the 8-bit kernels use), ONE
+    round-half-up, clamp to [0, peak];
+  * upsampling keeps chroma in 1/16 units into the matrix.  4:2:0: 420jpeg (centred) 9/3/3/1 over 16, 420mpeg2 (co-sited
+    horizontally, centred vertically) 1/2 + 1/2 at odd columns and 3/4 + 1/4 vertically; neighbours clamp to the edge.  4:2:2
+    (co-sited horizontally): the horizontal rule of 420mpeg2 with no vertical filter.  4:4:4: the sample itself.  Mono: no chroma
+    term, so B = G = R;
+  * downsampling rounds once, from the full-resolution Q(8+d) Cb / Cr.  4:2:0 (output is always 420jpeg): a 2x2 box; at an odd
+    edge the clamped neighbour repeats the pixel that exists, i.e. the 2 or 1 pixels there are averaged.  4:2:2: the co-sited
+    [1,2,1]/4 with clamped edges.  4:4:4: the value itself.  Mono: Y only.
+Frames are [h,w,3] in B, G, R order, the frame order of the whole pipeline (cv2's).  The other public conversions are instances:
+``yuv_to_bgr_np`` / ``bgr_to_yuv_np`` are d = 8 on uint8 payloads and frames, and ``yuv420_to_bgr_np`` / ``bgr_to_yuv420_np`` /
+``yuv420_to_bgr16_np`` / ``bgr16_to_yuv420_np`` are the '420' layout of the two pairs.
 
-High bit depth (opt-in: ``depths=DEPTHS``, ``python -m demfi_amd.video --high-depth``): the tags C420p10 / C420p12 / C420p14 /
-C420p16 carry unsigned 16-bit little-endian samples holding 0 .. 2^d - 1 = peak, so a payload has twice the bytes;
-``Header.payload`` counts bytes.  ``yuv420_to_bgr16_np`` / ``bgr16_to_yuv420_np`` define the conversion at depth d (the HIP kernels
-of csrc/yuv16.hip match them bit for bit) as the 8-bit pair generalised: with s = 2^(d-8), limited range is Y 16s .. 235s and
-C 16s .. 240s, the Y offset 16s, the chroma centre 2^(d-1), the scale factors peak / (219 s) and peak / (224 s) (and their
-inverses); coefficients are rounded half up to Q(8+d), accumulators are 64-bit, results clamp to [0, peak].  d = 8 is the
-8-bit pair exactly.  Frames are then uint16 [h,w,3] B, G, R with values 0 .. peak.
-
-Other chroma layouts (opt-in: ``layouts=LAYOUTS``, ``python -m demfi_amd.video --any-layout``): C422 (Cb, Cr [h, ceil(w/2)],
-co-sited horizontally), C444 (three [h,w] planes) and Cmono (Y only), and with ``depths=DEPTHS`` their deep forms C422pNN /
-C444pNN / CmonoNN.  ``yuv_to_bgr_np`` / ``bgr_to_yuv_np`` (8-bit) and ``yuv_to_bgr16_np`` / ``bgr16_to_yuv_np`` (depth d) define
-their conversion (the HIP kernels of csrc/yuv_layouts.hip match them bit for bit): the matrix step above, unchanged, behind the
-layout's upsampler -- 4:4:4 the sample itself, 4:2:2 the horizontal rule of 420mpeg2 with no vertical filter, mono no chroma
-(B = G = R); downsampling rounds the full-resolution chroma once (4:4:4) or the co-sited [1,2,1]/4 of it with clamped edges
-(4:2:2).  The output keeps the input's layout and depth.
+What a stream may carry: 8-bit 4:2:0 by default -- the Y plane [h,w] followed by the Cb and Cr planes [ceil(h/2), ceil(w/2)],
+1.5 bytes per pixel.  High bit depth is opt-in (``depths=DEPTHS``, ``python -m demfi_amd.video --high-depth``): the tags C420p10 /
+C420p12 / C420p14 / C420p16 carry unsigned 16-bit little-endian samples, so a payload has twice the bytes (``Header.payload``
+counts bytes) and frames are uint16.  Other chroma layouts are opt-in too (``layouts=LAYOUTS``, ``--any-layout``): C422 (Cb, Cr
+[h, ceil(w/2)]), C444 (three [h,w] planes) and Cmono (Y only), and with ``depths=DEPTHS`` their deep forms C422pNN / C444pNN /
+CmonoNN.  The output keeps the input's layout and depth.
 
 Two timelines: by default n input frames give (n-3)*M + 1 output frames and the first and last input frames have no output
 (``n_output_frames``); on the full-length timeline (``Frames(full_length=True)``, ``retime``) output frame 0 is input frame 0
@@ -62,39 +60,59 @@ class Y4MError(ValueError):
 
 
 # ---- the conversion definition ---------------------------------------------------------------------------------------------
-def _fix16(c):
-    return int(math.floor(c * 65536.0 + 0.5))
-
-
 def _kr_kb(matrix):
     if matrix not in MATRICES:
         raise ValueError('matrix must be one of %s, got %r' % (sorted(MATRICES), matrix))
     return MATRICES[matrix]
 
 
-def to_bgr_coefs(matrix, full_range):
-    """Q16 (cy, r_cr, g_cb, g_cr, b_cb), Y offset: R = cy*Y' + r_cr*Cr', G = cy*Y' + g_cb*Cb' + g_cr*Cr', B = cy*Y' + b_cb*Cb'."""
-    kr, kb = _kr_kb(matrix)
-    kg = 1.0 - kr - kb
-    ys, cs = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
-    return (_fix16(ys), _fix16(cs * 2.0 * (1.0 - kr)), _fix16(-(cs * 2.0 * kb * (1.0 - kb) / kg)),
-            _fix16(-(cs * 2.0 * kr * (1.0 - kr) / kg)), _fix16(cs * 2.0 * (1.0 - kb))), (0 if full_range else 16)
-
-
-def to_yuv_coefs(matrix, full_range):
-    """Q16 rows (Y, Cb, Cr) x (R, G, B), Y offset (the chroma offset is 128)."""
-    kr, kb = _kr_kb(matrix)
-    kg = 1.0 - kr - kb
-    ys, cs = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
-    return ((_fix16(ys * kr), _fix16(ys * kg), _fix16(ys * kb)),
-            (_fix16(-(cs * kr / (2.0 * (1.0 - kb)))), _fix16(-(cs * kg / (2.0 * (1.0 - kb)))), _fix16(cs * 0.5)),
-            (_fix16(cs * 0.5), _fix16(-(cs * kg / (2.0 * (1.0 - kr)))), _fix16(-(cs * kb / (2.0 * (1.0 - kr)))))), (0 if full_range else 16)
+def check_depth(depth):
+    if depth not in DEPTHS:
+        raise ValueError('bit depth must be one of %s, got %r' % (DEPTHS, depth))
+    return depth
 
 
 def check_layout(layout):
     if layout not in LAYOUTS:
         raise ValueError('chroma layout must be one of %s, got %r' % (LAYOUTS, layout))
     return layout
+
+
+def _fixq(c, q):
+    return int(math.floor(c * float(1 << q) + 0.5))
+
+
+def to_bgr_coefs_depth(matrix, full_range, depth):
+    """Q(8+d) (cy, r_cr, g_cb, g_cr, b_cb), Y offset 16 s (s = 2^(d-8)): R = cy*Y' + r_cr*Cr', G = cy*Y' + g_cb*Cb' + g_cr*Cr',
+    B = cy*Y' + b_cb*Cb'."""
+    kr, kb = _kr_kb(matrix)
+    kg = 1.0 - kr - kb
+    q, s, peak = 8 + depth, 1 << (depth - 8), (1 << depth) - 1
+    ys, cs = (1.0, 1.0) if full_range else (peak / (219.0 * s), peak / (224.0 * s))
+    return (_fixq(ys, q), _fixq(cs * 2.0 * (1.0 - kr), q), _fixq(-(cs * 2.0 * kb * (1.0 - kb) / kg), q),
+            _fixq(-(cs * 2.0 * kr * (1.0 - kr) / kg), q), _fixq(cs * 2.0 * (1.0 - kb), q)), (0 if full_range else 16 * s)
+
+
+def to_yuv_coefs_depth(matrix, full_range, depth):
+    """Q(8+d) rows (Y, Cb, Cr) x (R, G, B), Y offset 16 s (the chroma offset is 2^(d-1))."""
+    kr, kb = _kr_kb(matrix)
+    kg = 1.0 - kr - kb
+    q, s, peak = 8 + depth, 1 << (depth - 8), (1 << depth) - 1
+    ys, cs = (1.0, 1.0) if full_range else (219.0 * s / peak, 224.0 * s / peak)
+    return ((_fixq(ys * kr, q), _fixq(ys * kg, q), _fixq(ys * kb, q)),
+            (_fixq(-(cs * kr / (2.0 * (1.0 - kb))), q), _fixq(-(cs * kg / (2.0 * (1.0 - kb))), q), _fixq(cs * 0.5, q)),
+            (_fixq(cs * 0.5, q), _fixq(-(cs * kg / (2.0 * (1.0 - kr))), q), _fixq(-(cs * kb / (2.0 * (1.0 - kr))), q))), \
+        (0 if full_range else 16 * s)
+
+
+def to_bgr_coefs(matrix, full_range):
+    """The 8-bit coefficients: ``to_bgr_coefs_depth`` at d = 8 (Q16, Y offset 16)."""
+    return to_bgr_coefs_depth(matrix, full_range, 8)
+
+
+def to_yuv_coefs(matrix, full_range):
+    """The 8-bit coefficients: ``to_yuv_coefs_depth`` at d = 8 (Q16, Y offset 16, chroma offset 128)."""
+    return to_yuv_coefs_depth(matrix, full_range, 8)
 
 
 def chroma_shape(h, w, layout='420'):
@@ -107,104 +125,6 @@ def payload_size(h, w, layout='420'):
     """Samples of one payload: Y [h,w], then Cb and Cr of ``chroma_shape`` (4:2:0 unless ``layout`` says otherwise)."""
     ch, cw = chroma_shape(h, w, layout)
     return h * w + 2 * ch * cw
-
-
-def split_planes(payload, h, w):
-    """Y4M payload (bytes-like, 1-D uint8) -> (Y [h,w], Cb, Cr [ceil(h/2), ceil(w/2)]) views."""
-    a = np.frombuffer(payload, np.uint8) if not isinstance(payload, np.ndarray) else payload.reshape(-1)
-    ch, cw = (h + 1) // 2, (w + 1) // 2
-    if a.size != payload_size(h, w):
-        raise ValueError('payload of %d bytes for a %dx%d 4:2:0 frame (%d expected)' % (a.size, h, w, payload_size(h, w)))
-    return a[:h * w].reshape(h, w), a[h * w:h * w + ch * cw].reshape(ch, cw), a[h * w + ch * cw:].reshape(ch, cw)
-
-
-def _upsample16(c, h, w, siting):
-    """chroma [ch,cw] -> int32 [h,w] in 1/16 units (weights sum to 16)."""
-    ch, cw = c.shape
-    c = c.astype(np.int32)
-    ys = np.arange(h)
-    cy0 = ys >> 1
-    cy1 = np.where(ys & 1, np.minimum(cy0 + 1, ch - 1), np.maximum(cy0 - 1, 0))
-    v = 3 * c[cy0] + c[cy1]                                   # vertical 3/4 + 1/4, weight 4
-    xs = np.arange(w)
-    cx0 = xs >> 1
-    if siting == '420jpeg':
-        cx1 = np.where(xs & 1, np.minimum(cx0 + 1, cw - 1), np.maximum(cx0 - 1, 0))
-        return 3 * v[:, cx0] + v[:, cx1]
-    if siting == '420mpeg2':
-        cx1 = np.where(xs & 1, np.minimum(cx0 + 1, cw - 1), cx0)
-        return 2 * (v[:, cx0] + v[:, cx1])
-    raise ValueError('chroma siting must be one of %s, got %r' % (SITINGS, siting))
-
-
-def yuv420_to_bgr_np(payload, h, w, matrix='bt601', full_range=False, siting='420jpeg'):
-    """One 8-bit 4:2:0 Y4M payload -> uint8 BGR [h,w,3] (the definition the HIP kernel matches)."""
-    y, cb, cr = split_planes(payload, h, w)
-    (cy, r_cr, g_cb, g_cr, b_cb), yoff = to_bgr_coefs(matrix, full_range)
-    yy = (y.astype(np.int32) - yoff) * 16
-    cbv = _upsample16(cb, h, w, siting) - 128 * 16
-    crv = _upsample16(cr, h, w, siting) - 128 * 16
-    rnd = np.int32(1 << 19)
-    r = (cy * yy + r_cr * crv + rnd) >> 20
-    g = (cy * yy + g_cb * cbv + g_cr * crv + rnd) >> 20
-    b = (cy * yy + b_cb * cbv + rnd) >> 20
-    return np.clip(np.stack([b, g, r], -1), 0, 255).astype(np.uint8)
-
-
-def bgr_to_yuv420_np(bgr, matrix='bt601', full_range=False):
-    """uint8 BGR [h,w,3] -> one 8-bit 4:2:0 (420jpeg) Y4M payload, 1-D uint8 (the definition the HIP kernel matches)."""
-    bgr = np.asarray(bgr)
-    if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3:
-        raise ValueError('uint8 [h,w,3] expected, got %s %s' % (bgr.dtype, bgr.shape))
-    h, w = bgr.shape[:2]
-    if h < 2 or w < 2:
-        raise ValueError('frame of %dx%d: 2x2 at least' % (h, w))
-    (ky, kcb, kcr), yoff = to_yuv_coefs(matrix, full_range)
-    b, g, r = (bgr[:, :, i].astype(np.int32) for i in range(3))
-    y = np.clip((ky[0] * r + ky[1] * g + ky[2] * b + (yoff << 16) + (1 << 15)) >> 16, 0, 255)
-    r0 = np.arange(0, h, 2)
-    r1 = np.minimum(r0 + 1, h - 1)
-    c0 = np.arange(0, w, 2)
-    c1 = np.minimum(c0 + 1, w - 1)
-
-    def down(k):
-        f = k[0] * r + k[1] * g + k[2] * b                   # full-resolution Q16 chroma, centred on 0
-        s = f[r0][:, c0] + f[r0][:, c1] + f[r1][:, c0] + f[r1][:, c1]
-        return np.clip((s + (128 << 18) + (1 << 17)) >> 18, 0, 255)
-    return np.concatenate([y.reshape(-1), down(kcb).reshape(-1), down(kcr).reshape(-1)]).astype(np.uint8)
-
-
-# ---- the conversion at depth d: 16-bit samples -------------------------------------------------------------------------------
-def check_depth(depth):
-    if depth not in DEPTHS:
-        raise ValueError('bit depth must be one of %s, got %r' % (DEPTHS, depth))
-    return depth
-
-
-def _fixq(c, q):
-    return int(math.floor(c * float(1 << q) + 0.5))
-
-
-def to_bgr_coefs_depth(matrix, full_range, depth):
-    """``to_bgr_coefs`` at depth d: Q(8+d) coefficients, Y offset 16 s (s = 2^(d-8)); d = 8 gives ``to_bgr_coefs``."""
-    kr, kb = _kr_kb(matrix)
-    kg = 1.0 - kr - kb
-    q, s, peak = 8 + depth, 1 << (depth - 8), (1 << depth) - 1
-    ys, cs = (1.0, 1.0) if full_range else (peak / (219.0 * s), peak / (224.0 * s))
-    return (_fixq(ys, q), _fixq(cs * 2.0 * (1.0 - kr), q), _fixq(-(cs * 2.0 * kb * (1.0 - kb) / kg), q),
-            _fixq(-(cs * 2.0 * kr * (1.0 - kr) / kg), q), _fixq(cs * 2.0 * (1.0 - kb), q)), (0 if full_range else 16 * s)
-
-
-def to_yuv_coefs_depth(matrix, full_range, depth):
-    """``to_yuv_coefs`` at depth d: Q(8+d) rows (Y, Cb, Cr) x (R, G, B), Y offset 16 s (the chroma offset is 2^(d-1))."""
-    kr, kb = _kr_kb(matrix)
-    kg = 1.0 - kr - kb
-    q, s, peak = 8 + depth, 1 << (depth - 8), (1 << depth) - 1
-    ys, cs = (1.0, 1.0) if full_range else (219.0 * s / peak, 224.0 * s / peak)
-    return ((_fixq(ys * kr, q), _fixq(ys * kg, q), _fixq(ys * kb, q)),
-            (_fixq(-(cs * kr / (2.0 * (1.0 - kb))), q), _fixq(-(cs * kg / (2.0 * (1.0 - kb))), q), _fixq(cs * 0.5, q)),
-            (_fixq(cs * 0.5, q), _fixq(-(cs * kg / (2.0 * (1.0 - kr))), q), _fixq(-(cs * kb / (2.0 * (1.0 - kr))), q))), \
-        (0 if full_range else 16 * s)
 
 
 def payload_bytes(h, w, depth=8, layout='420'):
@@ -222,70 +142,48 @@ def as_samples16(payload):
     return a.view('<u2')
 
 
-def split_planes16(payload, h, w):
-    """16-bit Y4M payload -> (Y [h,w], Cb, Cr [ceil(h/2), ceil(w/2)]) uint16 views."""
-    a = as_samples16(payload)
-    ch, cw = (h + 1) // 2, (w + 1) // 2
-    if a.size != payload_size(h, w):
-        raise ValueError('payload of %d samples for a %dx%d 4:2:0 frame (%d expected)' % (a.size, h, w, payload_size(h, w)))
-    return a[:h * w].reshape(h, w), a[h * w:h * w + ch * cw].reshape(ch, cw), a[h * w + ch * cw:].reshape(ch, cw)
-
-
-def yuv420_to_bgr16_np(payload, h, w, depth, matrix='bt601', full_range=False, siting='420jpeg'):
-    """One 4:2:0 payload of 16-bit samples at depth d -> uint16 BGR [h,w,3], values 0 .. peak (the definition the HIP kernel
-    matches); ``depth`` = 8 (samples 0 .. 255 in the 16-bit container) gives the values of ``yuv420_to_bgr_np``."""
-    check_depth(depth)
-    y, cb, cr = split_planes16(payload, h, w)
-    (cy, r_cr, g_cb, g_cr, b_cb), yoff = to_bgr_coefs_depth(matrix, full_range, depth)
-    mid = (1 << (depth - 1)) * 16
-    yy = (y.astype(np.int64) - yoff) * 16
-    cbv = _upsample16(cb, h, w, siting).astype(np.int64) - mid
-    crv = _upsample16(cr, h, w, siting).astype(np.int64) - mid
-    sh = 8 + depth + 4
-    rnd = np.int64(1 << (sh - 1))
-    r = (cy * yy + r_cr * crv + rnd) >> sh
-    g = (cy * yy + g_cb * cbv + g_cr * crv + rnd) >> sh
-    b = (cy * yy + b_cb * cbv + rnd) >> sh
-    return np.clip(np.stack([b, g, r], -1), 0, (1 << depth) - 1).astype(np.uint16)
-
-
-def bgr16_to_yuv420_np(bgr16, depth, matrix='bt601', full_range=False):
-    """uint16 BGR [h,w,3] at depth d -> one 4:2:0 (420jpeg) payload of 16-bit samples, 1-D uint16 (the definition the HIP
-    kernel matches); ``.view(np.uint8)`` / ``.tobytes()`` of it are the little-endian bytes of the stream."""
-    check_depth(depth)
-    bgr = np.asarray(bgr16)
-    if bgr.dtype != np.uint16 or bgr.ndim != 3 or bgr.shape[2] != 3:
-        raise ValueError('uint16 [h,w,3] expected, got %s %s' % (bgr.dtype, bgr.shape))
-    h, w = bgr.shape[:2]
-    if h < 2 or w < 2:
-        raise ValueError('frame of %dx%d: 2x2 at least' % (h, w))
-    (ky, kcb, kcr), yoff = to_yuv_coefs_depth(matrix, full_range, depth)
-    q, peak, mid = 8 + depth, (1 << depth) - 1, 1 << (depth - 1)
-    b, g, r = (bgr[:, :, i].astype(np.int64) for i in range(3))
-    y = np.clip((ky[0] * r + ky[1] * g + ky[2] * b + (yoff << q) + (1 << (q - 1))) >> q, 0, peak)
-    r0 = np.arange(0, h, 2)
-    r1 = np.minimum(r0 + 1, h - 1)
-    c0 = np.arange(0, w, 2)
-    c1 = np.minimum(c0 + 1, w - 1)
-
-    def down(k):
-        f = k[0] * r + k[1] * g + k[2] * b                   # full-resolution Q(8+d) chroma, centred on 0
-        s = f[r0][:, c0] + f[r0][:, c1] + f[r1][:, c0] + f[r1][:, c1]
-        return np.clip((s + (mid << (q + 2)) + (1 << (q + 1))) >> (q + 2), 0, peak)
-    out = np.concatenate([y.reshape(-1), down(kcb).reshape(-1), down(kcr).reshape(-1)]).astype(np.uint16)
-    return out.astype('<u2', copy=False)
-
-
-# ---- the other chroma layouts: 4:2:2, 4:4:4, mono ---------------------------------------------------------------------------
-def split_planes_layout(payload, h, w, layout):
-    """Payload of samples (a 1-D uint8 or uint16 array) -> (Y [h,w], Cb, Cr of ``chroma_shape``) views; mono: Cb = Cr = None."""
-    a = payload.reshape(-1)
+def _split(a, h, w, layout, unit, name):
     ch, cw = chroma_shape(h, w, layout)
     if a.size != payload_size(h, w, layout):
-        raise ValueError('payload of %d samples for a %dx%d %s frame (%d expected)' % (a.size, h, w, layout, payload_size(h, w, layout)))
+        raise ValueError('payload of %d %s for a %dx%d %s frame (%d expected)' % (a.size, unit, h, w, name, payload_size(h, w, layout)))
     if layout == 'mono':
         return a.reshape(h, w), None, None
     return a[:h * w].reshape(h, w), a[h * w:h * w + ch * cw].reshape(ch, cw), a[h * w + ch * cw:].reshape(ch, cw)
+
+
+def split_planes_layout(payload, h, w, layout):
+    """Payload of samples (a 1-D uint8 or uint16 array) -> (Y [h,w], Cb, Cr of ``chroma_shape``) views; mono: Cb = Cr = None."""
+    return _split(payload.reshape(-1), h, w, layout, 'samples', layout)
+
+
+def split_planes(payload, h, w):
+    """8-bit 4:2:0 Y4M payload (bytes-like, 1-D uint8) -> (Y [h,w], Cb, Cr [ceil(h/2), ceil(w/2)]) views."""
+    a = np.frombuffer(payload, np.uint8) if not isinstance(payload, np.ndarray) else payload.reshape(-1)
+    return _split(a, h, w, '420', 'bytes', '4:2:0')
+
+
+def split_planes16(payload, h, w):
+    """16-bit 4:2:0 Y4M payload -> (Y [h,w], Cb, Cr [ceil(h/2), ceil(w/2)]) uint16 views."""
+    return _split(as_samples16(payload), h, w, '420', 'samples', '4:2:0')
+
+
+def _upsample16(c, h, w, siting):
+    """4:2:0 chroma [ch,cw] -> int32 [h,w] in 1/16 units (weights sum to 16)."""
+    ch, cw = c.shape
+    c = c.astype(np.int32)
+    ys = np.arange(h)
+    cy0 = ys >> 1
+    cy1 = np.where(ys & 1, np.minimum(cy0 + 1, ch - 1), np.maximum(cy0 - 1, 0))
+    v = 3 * c[cy0] + c[cy1]                                   # vertical 3/4 + 1/4, weight 4
+    xs = np.arange(w)
+    cx0 = xs >> 1
+    if siting == '420jpeg':
+        cx1 = np.where(xs & 1, np.minimum(cx0 + 1, cw - 1), np.maximum(cx0 - 1, 0))
+        return 3 * v[:, cx0] + v[:, cx1]
+    if siting == '420mpeg2':
+        cx1 = np.where(xs & 1, np.minimum(cx0 + 1, cw - 1), cx0)
+        return 2 * (v[:, cx0] + v[:, cx1])
+    raise ValueError('chroma siting must be one of %s, got %r' % (SITINGS, siting))
 
 
 def _upsample16_layout(c, h, w, layout):
@@ -303,80 +201,122 @@ def _upsample16_layout(c, h, w, layout):
     raise ValueError('no chroma upsampling for layout %r' % (layout,))
 
 
-def yuv_to_bgr16_np(payload, h, w, depth, layout, matrix='bt601', full_range=False, siting='420jpeg'):
-    """One payload of 16-bit samples at depth d in any of ``LAYOUTS`` -> uint16 BGR [h,w,3], values 0 .. peak: the matrix step of
-    ``yuv420_to_bgr16_np`` (same coefficients, chroma in 1/16 units, ONE round-half-up, clamp) behind the layout's upsampler;
-    mono has no chroma term, so B = G = R.  ``siting`` only matters to '420', which is ``yuv420_to_bgr16_np``.  The definition
-    the HIP kernels of csrc/yuv_layouts.hip match."""
-    check_depth(depth)
-    if check_layout(layout) == '420':
-        return yuv420_to_bgr16_np(payload, h, w, depth, matrix, full_range, siting)
-    y, cb, cr = split_planes_layout(as_samples16(payload), h, w, layout)
-    (cy, r_cr, g_cb, g_cr, b_cb), yoff = to_bgr_coefs_depth(matrix, full_range, depth)
-    mid = (1 << (depth - 1)) * 16
-    yy = (y.astype(np.int64) - yoff) * 16
-    if layout == 'mono':
-        cbv = crv = np.zeros((h, w), np.int64)
-    else:
-        cbv = _upsample16_layout(cb, h, w, layout).astype(np.int64) - mid
-        crv = _upsample16_layout(cr, h, w, layout).astype(np.int64) - mid
+def _matrix_to_bgr(yy, cbv, crv, depth, coefs):
+    """The matrix step: int64 [h,w] luma and chroma in 1/16 units, offsets removed -> int64 B, G, R [h,w,3] in 0 .. peak."""
+    cy, r_cr, g_cb, g_cr, b_cb = coefs
     sh = 8 + depth + 4
     rnd = np.int64(1 << (sh - 1))
     r = (cy * yy + r_cr * crv + rnd) >> sh
     g = (cy * yy + g_cb * cbv + g_cr * crv + rnd) >> sh
     b = (cy * yy + b_cb * cbv + rnd) >> sh
-    return np.clip(np.stack([b, g, r], -1), 0, (1 << depth) - 1).astype(np.uint16)
+    return np.clip(np.stack([b, g, r], -1), 0, (1 << depth) - 1)
 
 
-def bgr16_to_yuv_np(bgr16, depth, layout, matrix='bt601', full_range=False):
-    """uint16 BGR [h,w,3] at depth d -> one payload of 16-bit samples in any of ``LAYOUTS``, 1-D uint16.  Y as in
-    ``bgr16_to_yuv420_np``; with f the full-resolution Q(8+d) chroma centred on 0: 4:4:4 rounds f once; 4:2:2 is the co-sited
-    [1,2,1]/4 over f[y, 2i-1], f[y, 2i], f[y, 2i+1] (clamped to the edge), rounded once; mono is Y only.  '420' is
-    ``bgr16_to_yuv420_np``.  The definition the HIP kernels of csrc/yuv_layouts.hip match."""
-    check_depth(depth)
-    if check_layout(layout) == '420':
-        return bgr16_to_yuv420_np(bgr16, depth, matrix, full_range)
-    bgr = np.asarray(bgr16)
-    if bgr.dtype != np.uint16 or bgr.ndim != 3 or bgr.shape[2] != 3:
-        raise ValueError('uint16 [h,w,3] expected, got %s %s' % (bgr.dtype, bgr.shape))
+def _to_bgr(planes, h, w, depth, layout, matrix, full_range, siting):
+    """(Y, Cb, Cr) sample planes of any of ``LAYOUTS`` at depth d -> int64 B, G, R [h,w,3] in 0 .. peak: the layout's upsampler,
+    then the matrix step."""
+    y, cb, cr = planes
+    coefs, yoff = to_bgr_coefs_depth(matrix, full_range, depth)
+    mid = (1 << (depth - 1)) * 16
+    yy = (y.astype(np.int64) - yoff) * 16
+    if layout == 'mono':
+        cbv = crv = np.zeros((h, w), np.int64)
+    else:
+        up = (lambda c: _upsample16(c, h, w, siting)) if layout == '420' else (lambda c: _upsample16_layout(c, h, w, layout))
+        cbv, crv = up(cb).astype(np.int64) - mid, up(cr).astype(np.int64) - mid
+    return _matrix_to_bgr(yy, cbv, crv, depth, coefs)
+
+
+def _luma_and_chroma(bgr, depth, coefs):
+    """B, G, R [h,w,3] at depth d -> (Y [h,w] in 0 .. peak, (Cb, Cr) the full-resolution Q(8+d) chroma centred on 0), int64."""
+    (ky, kcb, kcr), yoff = coefs
+    q = 8 + depth
+    b, g, r = (bgr[:, :, i].astype(np.int64) for i in range(3))
+    y = np.clip((ky[0] * r + ky[1] * g + ky[2] * b + (yoff << q) + (1 << (q - 1))) >> q, 0, (1 << depth) - 1)
+    return y, [k[0] * r + k[1] * g + k[2] * b for k in (kcb, kcr)]
+
+
+def _to_yuv(bgr, dtype, depth, layout, matrix, full_range):
+    """B, G, R [h,w,3] of ``dtype`` at depth d -> the samples of one payload in any of ``LAYOUTS``, 1-D int64."""
+    bgr = np.asarray(bgr)
+    if bgr.dtype != dtype or bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise ValueError('%s [h,w,3] expected, got %s %s' % (np.dtype(dtype).name, bgr.dtype, bgr.shape))
     h, w = bgr.shape[:2]
     if h < 2 or w < 2:
         raise ValueError('frame of %dx%d: 2x2 at least' % (h, w))
-    (ky, kcb, kcr), yoff = to_yuv_coefs_depth(matrix, full_range, depth)
+    y, fs = _luma_and_chroma(bgr, depth, to_yuv_coefs_depth(matrix, full_range, depth))
     q, peak, mid = 8 + depth, (1 << depth) - 1, 1 << (depth - 1)
-    b, g, r = (bgr[:, :, i].astype(np.int64) for i in range(3))
-    y = np.clip((ky[0] * r + ky[1] * g + ky[2] * b + (yoff << q) + (1 << (q - 1))) >> q, 0, peak)
-    ci = np.arange(0, w, 2)                                   # the luma column chroma column i is co-sited with
 
-    def down(k):
-        f = k[0] * r + k[1] * g + k[2] * b                   # full-resolution Q(8+d) chroma, centred on 0
+    def rounded(s, sh):                                       # a sum of weight 2^(sh-q) over f -> samples, rounded once
+        return np.clip((s + (mid << sh) + (1 << (sh - 1))) >> sh, 0, peak)
+
+    def down(f):
         if layout == '444':
-            return np.clip((f + (mid << q) + (1 << (q - 1))) >> q, 0, peak)
-        s = f[:, np.maximum(ci - 1, 0)] + 2 * f[:, ci] + f[:, np.minimum(ci + 1, w - 1)]
-        return np.clip((s + (mid << (q + 2)) + (1 << (q + 1))) >> (q + 2), 0, peak)
-    planes = [y] if layout == 'mono' else [y, down(kcb), down(kcr)]
-    return np.concatenate([p.reshape(-1) for p in planes]).astype(np.uint16).astype('<u2', copy=False)
+            return rounded(f, q)
+        if layout == '422':                                   # chroma column i is co-sited with luma column 2i: [1,2,1]/4
+            ci = np.arange(0, w, 2)
+            return rounded(f[:, np.maximum(ci - 1, 0)] + 2 * f[:, ci] + f[:, np.minimum(ci + 1, w - 1)], q + 2)
+        r0, c0 = np.arange(0, h, 2), np.arange(0, w, 2)       # 4:2:0: the 2x2 box; at an odd edge the pixel that exists repeats
+        r1, c1 = np.minimum(r0 + 1, h - 1), np.minimum(c0 + 1, w - 1)
+        return rounded(f[r0][:, c0] + f[r0][:, c1] + f[r1][:, c0] + f[r1][:, c1], q + 2)
+    planes = [y] if layout == 'mono' else [y, down(fs[0]), down(fs[1])]
+    return np.concatenate([p.reshape(-1) for p in planes])
 
 
-def yuv_to_bgr_np(payload, h, w, layout, matrix='bt601', full_range=False, siting='420jpeg'):
-    """One 8-bit payload in any of ``LAYOUTS`` -> uint8 BGR [h,w,3]: the d = 8 instance of ``yuv_to_bgr16_np`` (whose
-    intermediates then fit int32, as the kernels compute them); '420' is ``yuv420_to_bgr_np``."""
+def _as_u8(payload):
     a = np.frombuffer(payload, np.uint8) if not isinstance(payload, np.ndarray) else payload.reshape(-1)
     if a.dtype != np.uint8:
         raise ValueError('a payload of 8-bit samples is a uint8 array, got %s' % a.dtype)
-    if check_layout(layout) == '420':
-        return yuv420_to_bgr_np(a, h, w, matrix, full_range, siting)
-    return yuv_to_bgr16_np(a.astype(np.uint16), h, w, 8, layout, matrix, full_range).astype(np.uint8)
+    return a
+
+
+def yuv_to_bgr16_np(payload, h, w, depth, layout, matrix='bt601', full_range=False, siting='420jpeg'):
+    """One payload of 16-bit samples at depth d in any of ``LAYOUTS`` -> uint16 BGR [h,w,3], values 0 .. peak (the definition
+    the HIP kernels match); ``siting`` only matters to '420'.  ``depth`` = 8 (samples 0 .. 255 in the 16-bit container) gives the
+    values of ``yuv_to_bgr_np``."""
+    check_depth(depth)
+    planes = split_planes_layout(as_samples16(payload), h, w, check_layout(layout))
+    return _to_bgr(planes, h, w, depth, layout, matrix, full_range, siting).astype(np.uint16)
+
+
+def yuv_to_bgr_np(payload, h, w, layout, matrix='bt601', full_range=False, siting='420jpeg'):
+    """One 8-bit payload in any of ``LAYOUTS`` -> uint8 BGR [h,w,3]: the d = 8 instance (whose intermediates fit int32, as the
+    8-bit kernels compute them)."""
+    planes = split_planes_layout(_as_u8(payload), h, w, check_layout(layout))
+    return _to_bgr(planes, h, w, 8, layout, matrix, full_range, siting).astype(np.uint8)
+
+
+def yuv420_to_bgr16_np(payload, h, w, depth, matrix='bt601', full_range=False, siting='420jpeg'):
+    """``yuv_to_bgr16_np`` of a 4:2:0 payload."""
+    check_depth(depth)
+    return _to_bgr(split_planes16(payload, h, w), h, w, depth, '420', matrix, full_range, siting).astype(np.uint16)
+
+
+def yuv420_to_bgr_np(payload, h, w, matrix='bt601', full_range=False, siting='420jpeg'):
+    """``yuv_to_bgr_np`` of a 4:2:0 payload: one 8-bit 4:2:0 Y4M payload -> uint8 BGR [h,w,3]."""
+    return _to_bgr(split_planes(payload, h, w), h, w, 8, '420', matrix, full_range, siting).astype(np.uint8)
+
+
+def bgr16_to_yuv_np(bgr16, depth, layout, matrix='bt601', full_range=False):
+    """uint16 BGR [h,w,3] at depth d -> one payload of 16-bit samples in any of ``LAYOUTS``, 1-D uint16 (the definition the HIP
+    kernels match); ``.view(np.uint8)`` / ``.tobytes()`` of it are the little-endian bytes of the stream."""
+    check_depth(depth)
+    return _to_yuv(bgr16, np.uint16, depth, check_layout(layout), matrix, full_range).astype(np.uint16).astype('<u2', copy=False)
 
 
 def bgr_to_yuv_np(bgr, layout, matrix='bt601', full_range=False):
-    """uint8 BGR [h,w,3] -> one 8-bit payload in any of ``LAYOUTS``, 1-D uint8: the d = 8 instance of ``bgr16_to_yuv_np``."""
-    bgr = np.asarray(bgr)
-    if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3:
-        raise ValueError('uint8 [h,w,3] expected, got %s %s' % (bgr.dtype, bgr.shape))
-    if check_layout(layout) == '420':
-        return bgr_to_yuv420_np(bgr, matrix, full_range)
-    return bgr16_to_yuv_np(bgr.astype(np.uint16), 8, layout, matrix, full_range).astype(np.uint8)
+    """uint8 BGR [h,w,3] -> one 8-bit payload in any of ``LAYOUTS``, 1-D uint8: the d = 8 instance."""
+    return _to_yuv(bgr, np.uint8, 8, check_layout(layout), matrix, full_range).astype(np.uint8)
+
+
+def bgr16_to_yuv420_np(bgr16, depth, matrix='bt601', full_range=False):
+    """``bgr16_to_yuv_np`` to a 4:2:0 (420jpeg) payload."""
+    return bgr16_to_yuv_np(bgr16, depth, '420', matrix, full_range)
+
+
+def bgr_to_yuv420_np(bgr, matrix='bt601', full_range=False):
+    """``bgr_to_yuv_np`` to a 4:2:0 (420jpeg) payload."""
+    return bgr_to_yuv_np(bgr, '420', matrix, full_range)
 
 
 def auto_matrix(h):

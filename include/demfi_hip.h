@@ -375,7 +375,7 @@ int demfi_bgr_to_yuv420_gather(const uint8_t* base, const int64_t* src_offsets, 
 int demfi_yuv420_sad(const uint8_t* base, const int64_t* a_offsets, const int64_t* b_offsets, int n, int64_t payload, uint64_t* sad,
                      void* stream);
 
-/* ---- the 16-bit frame path of the Y4M edge (csrc/yuv16.hip; demfi_amd/video.py --high-depth) ---------------------------------
+/* ---- the 16-bit frame path of the Y4M edge (csrc/yuv_family.hip, yuv.hip, frames16.hip; video.py --high-depth) ------------
  * The functions above at bit depth d = `depth`, 8 <= d <= 16 (the Y4M tags C420p10 .. C420p16; 8 is accepted so that this path can
  * be compared with the 8-bit one value for value): samples and B, G, R values are unsigned 16-bit holding 0 .. peak = 2^d - 1,
  * buffers are 2-byte aligned, and EVERY stride and offset counts 16-bit samples, not bytes.  Integer arithmetic that matches
@@ -400,7 +400,7 @@ int demfi_u16_ingest(const uint16_t* const* frames, int h, int w, int depth, flo
                      int W, void* stream);
 int demfi_frame_to_u16(const float* frame, uint16_t* out, int h, int w, int H, int W, int depth, void* stream);
 
-/* ---- the other chroma layouts of the Y4M edge (csrc/yuv_layouts.hip; demfi_amd/video.py --any-layout) ------------------------
+/* ---- the other chroma layouts of the Y4M edge (csrc/yuv_family.hip; demfi_amd/video.py --any-layout) ------------------------
  * demfi_yuv420_to_bgr / demfi_bgr_to_yuv420_gather and their 16-bit forms for layout = DEMFI_YUV_422 (Y [h,w]; Cb, Cr
  * [h, ceil(w/2)], co-sited horizontally), DEMFI_YUV_444 (three [h,w] planes) and DEMFI_YUV_MONO (Y only; B = G = R), with the
  * same argument conventions: byte strides and offsets for the uint8 pair, sample strides and offsets (and 2-byte aligned

@@ -1,5 +1,5 @@
-"""The 16-bit frame path of the Y4M edge (``--high-depth``: C420p10 .. C420p16) on a real MI355X: the kernels of csrc/yuv16.hip
-bit-exact against their numpy definitions, the uint16 ingest / egress against the uint8 kernels (depth 8) and against numpy, the
+"""The 16-bit frame path of the Y4M edge (``--high-depth``: C420p10 .. C420p16) on a real MI355X: its kernels (csrc/yuv_family.hip,
+csrc/yuv.hip, csrc/frames16.hip) bit-exact against their numpy definitions, the uint16 ingest / egress against the uint8 kernels (depth 8) and against numpy, the
 whole 16-bit container path anchored to the 8-bit emit path value for value, and ``VideoRunner(high_depth=True)`` byte-identical
 to the expectation composed from the numpy definitions and ``WindowRunner.run_windows_u16``."""
 import ctypes as C
@@ -77,7 +77,7 @@ def _gather_gpu(frames, order, d, matrix, full, src_pad=0, dst_pad=0, lead=0):
     return out[:, :P]
 
 
-SIZES = [(2, 2), (3, 5), (5, 3), (37, 53), (70, 98), (64, 128), (720, 1280)]          # those of tests/test_gpu_y4m.py
+SIZES = [(2, 2), (3, 5), (5, 3), (6, 9), (37, 53), (70, 98), (64, 128), (720, 1280)]  # those of tests/test_gpu_y4m.py, and a width of 8k + 1
 DEPTHS = [8, 10, 12, 16]
 
 
@@ -118,7 +118,7 @@ def test_depth_8_equals_the_8_bit_kernels(h, w):
     assert np.array_equal(got, pay8.cpu().numpy().astype(np.uint16))
 
 
-@pytest.mark.parametrize('h,w', [(37, 53), (64, 128), (70, 98)])
+@pytest.mark.parametrize('h,w', [(6, 9), (37, 53), (64, 128), (70, 98)])
 @pytest.mark.parametrize('pad', [0, 8, 13])
 @pytest.mark.parametrize('d', [10, 16])
 def test_strided_batches_and_gather_order(h, w, pad, d):

@@ -1,4 +1,4 @@
-"""4:2:2, 4:4:4 and mono Y4M (``--any-layout``) on a real MI355X: the kernels of csrc/yuv_layouts.hip bit-exact against their numpy
+"""4:2:2, 4:4:4 and mono Y4M (``--any-layout``) on a real MI355X: the kernels of csrc/yuv_family.hip bit-exact against their numpy
 definitions (byte samples and 16-bit samples, padded strides, shuffled gathers, argument errors), and ``VideoRunner(layouts=True)``
 byte-identical to the expectation composed from the numpy definitions around the BGR window path: the module path of
 tests/test_gpu_scene.py / test_gpu_tiling.py for 8-bit streams, ``WindowRunner.run_windows_u16`` as in tests/test_gpu_y4m_depth.py
