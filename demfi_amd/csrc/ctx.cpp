@@ -1951,6 +1951,16 @@ extern "C" int demfi_ingest_u16(demfi_ctx* c, int trunk, const uint16_t* const* 
                             (float*)(c->base + B["overlay"].off), c->dtype, c->H, c->W, stream);
 }
 
+extern "C" int demfi_ingest_u16_rect(demfi_ctx* c, int trunk, const uint16_t* const* frames, int fh, int fw, int y0, int x0, int h, int w,
+                                     int depth, void* stream)
+{
+    if (!c || !c->bound || c->on_host || trunk < 0 || trunk >= c->n_trunk)
+        return demfi_set_error(DEMFI_ERR_ARG, "demfi_ingest_u16_rect: context not bound to device memory / bad trunk index");
+    BufSet& B = c->tr_bufs[trunk];
+    return demfi_u16_ingest_rect(frames, fh, fw, y0, x0, h, w, depth, (float*)(c->base + B["x"].off), c->base + B["s2d"].off,
+                                 (float*)(c->base + B["overlay"].off), c->dtype, c->H, c->W, stream);
+}
+
 extern "C" int demfi_forward_trunk_body(demfi_ctx* c, int trunk, void* stream)
 {
     if (!c || !c->bound || c->on_host || trunk < 0 || trunk >= c->n_trunk)

@@ -359,6 +359,10 @@ class Engine:
         """``ingest_u8`` for 4 BGR uint16 [h,w,3] device frames holding 0 .. 2^depth - 1."""
         L.check(self.lib.demfi_ingest_u16(self._ctx, self.trunk, frame_ptrs, h, w, depth, stream), 'ingest_u16')
 
+    def ingest_u16_rect(self, frame_ptrs, fh, fw, y0, x0, h, w, depth, stream):
+        """``ingest_u16`` for the h x w rectangle at (y0, x0) of 4 BGR uint16 [fh,fw,3] device frames: a tile read in place."""
+        L.check(self.lib.demfi_ingest_u16_rect(self._ctx, self.trunk, frame_ptrs, fh, fw, y0, x0, h, w, depth, stream), 'ingest_u16_rect')
+
     def run_trunk_body(self, stream):
         """The trunk without its s2d / overlay prologue (what follows ingest_u8)."""
         L.check(self.lib.demfi_forward_trunk_body(self._ctx, self.trunk, stream), 'forward_trunk_body')

@@ -6,7 +6,9 @@ its outputs to pinned memory (d2h stream) and ``drain`` them to the sink; what `
 
 A runner of tiles (``WindowRunner(tiles=plan)``, ``demfi_amd.tiling``) has the tile's size while the slots, the outputs and
 everything after them keep the frame's: ``Tiler`` crops every uploaded frame into its tiles once, each (run, tile) pair is one run
-of the runner, and one stitch launch per batch pastes the kept rectangles into the full-size output buffers."""
+of the runner, and one stitch launch per batch pastes the kept rectangles into the full-size output buffers.  The 16-bit frames
+of a high-depth Y4M stream are not cropped or stitched (``TileGrid``): the 16-bit ingest and egress kernels address a tile inside
+the full frames, so every (run, tile) pair reads the frame slots and writes the output frames directly."""
 import ctypes as C
 import itertools
 import weakref
@@ -123,6 +125,16 @@ class Tiler:
                                               stream.cuda_stream), 'u8_tile_stitch')
 
 
+class TileGrid:
+    """A multi-tile plan for the 16-bit frames of the Y4M edge: the sizes ``Tiler`` gives, and no device side.  The ingest of a
+    (run, tile) pair reads its source rectangle out of the full frame slots and its egress writes its kept rectangle into the full
+    output frames (``WindowRunner._u16_tile_io``), so there is nothing to crop into and nothing to stitch from."""
+
+    def __init__(self, plan):
+        self.plan, self.nt = plan, plan.n_tiles
+        (self.h, self.w), (self.th, self.tw) = (plan.h, plan.w), plan.tile
+
+
 class BgrEdge:
     """uint8 BGR [h,w,3] frames in; sink(k, St [M-1,h,w,3], S0S1 [2,h,w,3]) out (views of pinned staging buffers).  Tiled: window w
     is the n_tiles runs w * n_tiles + j into ``tout`` / ``ts01``; out and s01 are then halves of one buffer (one stitch launch)."""
@@ -195,15 +207,18 @@ class Y4mEdge:
     host hands over and gets back); the frame slots and ``comb`` are int16 storage of the uint16 frames, the three launches
     are the 16-bit ones (strides and offsets in samples), the egress is the emit path and the SADs count samples.
     ``layout``: the payloads' chroma layout (``y4m.LAYOUTS``): it sets P, and for 4:2:2, 4:4:4 and mono the two conversion
-    launches are those of the layouts family; everything between them sees BGR frames.  ``yuv_calls`` picks the launches."""
+    launches are those of the layouts family; everything between them sees BGR frames.  ``yuv_calls`` picks the launches.
+    ``tiler``: a ``Tiler`` (8-bit frames: crop, run into ``tcomb``, stitch) or a ``TileGrid`` (16-bit frames: every tile run reads
+    the slots and writes comb[i] in place)."""
 
     def __init__(self, runner, batch, slots, cuts, full, tiler=None, depth=8, layout='420', dedup=None, h2d=None):
         self.rn, self.slots, self.cuts, self.full, self.tiler = runner, slots, cuts, full, tiler
         self.dedup, self.h2d, self.kept, self._pending = dedup, h2d, None, []
         self.depth, self.hi = depth, depth > 8
         self.layout = layout
-        if self.hi and tiler is not None:
-            raise ValueError('Y4mEdge: tiles move 8-bit pixels; a %d-bit stream cannot run tiled' % depth)
+        if tiler is not None and self.hi != isinstance(tiler, TileGrid):
+            raise ValueError('Y4mEdge: %d-bit frames with a %s' % (depth, type(tiler).__name__))
+        self.in_place = self.hi and tiler is not None                    # tiles addressed inside the full frames
         es, fdt = (2, torch.int16) if self.hi else (1, torch.uint8)      # bytes per sample; storage of a frame value
         self.r = runner.retime if runner.retime is not None else Fraction(runner.mfi)
         h, w = self.fh, self.fw = (tiler.h, tiler.w) if tiler else (runner.h, runner.w)
@@ -219,7 +234,7 @@ class Y4mEdge:
         self.yuv_in = torch.empty((nsl, Pb), dtype=torch.uint8, device=dev)
         self.comb = [torch.empty((runs_max, J + 2, h, w, 3), dtype=fdt, device=dev) for _ in range(2)]
         nt = tiler.nt if tiler else 1                                    # tiled: run w is the runs w * nt + j of the tile runner
-        if tiler:        # their frames; one buffer serves both sets: the stitch has read it before the next batch's runs start
+        if tiler and not self.in_place:   # their frames; one buffer serves both sets: the stitch has read it before the next batch's runs start
             self.tcomb = torch.empty((runs_max * nt, J + 2, tiler.th, tiler.tw, 3), dtype=torch.uint8, device=dev)
         self.t = [torch.empty((runs_max * nt, nJ), dtype=torch.float32, device=dev) for _ in range(2)]
         self.sinks = [torch.empty((runs_max * nt, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)]
@@ -300,7 +315,7 @@ class Y4mEdge:
         sls = [sl for _, sl in new]
         for s0, cnt in consecutive(sls):
             self.to_bgr(self.yuv_in[s0].data_ptr(), self.slots.frames[s0].data_ptr(), cnt, h2d.cuda_stream)
-        if self.tiler:
+        if self.tiler and not self.in_place:
             self.tiler.crop(sls, h2d)
         if self.det is not None:
             self._scene_sads([idx for idx, _ in new], h2d)
@@ -365,9 +380,13 @@ class Y4mEdge:
         and the uint8 sink records (one per (run, instant); S0 / S1 only in the row of the run's first instant and only when
         ``kinds`` holds that frame; rows past a run's instants disabled) are uploaded on the current stream.
         Tiled: every run is one run per tile, on that tile of its slots into tcomb, and the frames written are then stitched
-        into comb[i] in one launch."""
+        into comb[i] in one launch.  Tiled 16-bit frames: run w is the tile runs w * nt + j, each from the full slots into its
+        kept rectangle of comb[i][w]; the rectangles of a frame are disjoint, so the runs need no order among themselves."""
         rn, J, tl = self.rn, self.J, self.tiler
-        if tl:
+        if self.in_place:
+            comb = self.comb[i]
+            runs = [([self.slots.frames[sl] for sl in fr], ts, kinds) for fr, ts, kinds in runs for _ in range(tl.nt)]
+        elif tl:
             full, comb = runs, self.tcomb
             runs = [([tl.tin[sl, j] for sl in fr], ts, kinds) for fr, ts, kinds in full for j in range(tl.nt)]
         else:
@@ -380,6 +399,8 @@ class Y4mEdge:
         for w, (_, ts, kinds) in enumerate(runs):
             tt[w, :len(ts)] = ts
             tt[w, len(ts):] = ts[-1]
+            if self.hi:                              # no sink records: every 16-bit frame leaves through the emit path
+                continue
             st[w, :len(ts)] = base + w * c0 + c1 * np.arange(1, len(ts) + 1)
             s01[0, w, 0] = base + w * c0 if R.S0 in kinds else 0
             s01[1, w, 0] = base + w * c0 + (J + 1) * c1 if R.S1 in kinds else 0
@@ -390,7 +411,10 @@ class Y4mEdge:
             a = fill_sink_records(np.empty((nw, nJ, 32), np.int64), st, s01[0], s01[1], rn.h, rn.w, rn.n_tst)
             rows = self.sinks[i][:nw]
             rows.copy_(torch.from_numpy(a).pin_memory(), non_blocking=True)
-        if self.hi:
+        if self.in_place:
+            nt, tiles = tl.nt, tl.plan.tiles
+            io = [rn._u16_tile_io(fr, tiles[w % nt], comb[w // nt, 1:J + 1], comb[w // nt, 0::J + 1], self.depth) for w, (fr, _, _) in enumerate(runs)]
+        elif self.hi:
             io = [rn._u16_io(fr, comb[w, 1:J + 1], comb[w, 0::J + 1], self.depth) for w, (fr, _, _) in enumerate(runs)]
         else:
             io = [rn._u8_io(fr, comb[w, 1:J + 1], comb[w, 0::J + 1], None if rows is None else rows[w]) for w, (fr, _, _) in enumerate(runs)]
@@ -398,7 +422,7 @@ class Y4mEdge:
         for w, (load, emit, pre) in enumerate(io):
             rn._window(load, emit, body_only=True, pre=pre, t_dev=t_dev[w], nt=len(runs[w][1]))
         rn._end(cur)
-        if tl:
+        if tl and not self.in_place:
             (c0, c1), (t0, t1), j = self.comb[i].stride()[:2], comb.stride()[:2], np.arange(tl.nt, dtype=np.int64)
             pos = [(w, p) for w, (_, ts, kinds) in enumerate(full)
                    for p in ([0] if R.S0 in kinds else []) + list(range(1, len(ts) + 1)) + ([J + 1] if R.S1 in kinds else [])]
@@ -554,7 +578,9 @@ class ClipPipeline:
         fh, fw = (plan.h, plan.w) if plan is not None else (runner.h, runner.w)
         self.slots = FrameSlots(max(2 * batch + 8, 8 * batch), fh, fw, dev, torch.int16 if depth > 8 else torch.uint8)
         tiler = None
-        if plan is not None:                         # frames stitched per batch: a run's J + 2 (a cut window is two runs), or M + 1
+        if plan is not None and depth > 8:           # 16-bit frames: tiles are read and written inside the full frames
+            tiler = TileGrid(plan)
+        elif plan is not None:                       # frames stitched per batch: a run's J + 2 (a cut window is two runs), or M + 1
             J2 = (R.max_instants(runner.retime if runner.retime is not None else Fraction(runner.mfi)) + 2) if y4m else runner.mfi + 1
             rr = (runner.retime if runner.retime is not None else Fraction(runner.mfi)) if y4m else None
             tiler = Tiler(plan, self.slots, runner.lib, dev, batch * (max_runs(rr, cuts, dedup) if y4m else 1) * J2)

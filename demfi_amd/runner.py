@@ -523,6 +523,43 @@ class WindowRunner:
                             'to_u16')
         return load, emit, None                      # no pre: _window then disables every uint8 sink record
 
+    def _u16_tile_io(self, slots4, tile, out_full, s01_full, depth):
+        """(load, emit, pre) of one (run, tile) pair of a runner of ``tiles``, the counterpart of ``_u16_io``: ``slots4`` are 4 BGR
+        frames of the PLAN's size [fh,fw,3] (16-bit storage), ``tile`` one ``tiling.Tile`` of the plan; out_full [J,fh,fw,3] and
+        s01_full [2,fh,fw,3] are full output frames.  Ingest: ONE kernel reads the tile's source rectangle in place
+        (``demfi_u16_ingest_rect``).  Egress: one ``demfi_frame_to_u16_rect`` per frame writes the tile's kept rectangle only; the
+        kept rectangles of a plan partition the frame, so its tiles fill a frame between them in any order."""
+        e, plan = self.engine, self.tiles
+        if plan is None or tile not in plan.tiles:
+            raise ValueError('_u16_tile_io: a runner of tiles and one tile of its plan')
+        if depth not in (8, 10, 12, 14, 16):
+            raise ValueError('bit depth must be 8, 10, 12, 14 or 16, got %r' % (depth,))
+        fh, fw = plan.h, plan.w
+        if len(slots4) != 4:
+            raise ValueError('expected 4 16-bit frames (B0,B1,B-1,B2), got %d' % len(slots4))
+        for f in list(slots4) + list(out_full) + list(s01_full):
+            self._check_device(f, '16-bit frame')
+            if f.dtype not in U16_DTYPES or tuple(f.shape) != (fh, fw, 3) or not f.is_contiguous():
+                raise ValueError('16-bit frames of a tiled run must be contiguous [%d,%d,3] int16 / uint16 tensors, got %s %s' %
+                                 (fh, fw, f.dtype, tuple(f.shape)))
+        ptrs = (C.c_void_p * 4)(*[f.data_ptr() for f in slots4])
+        (y0, x0, _, _), k = tile.src, tile.keep
+
+        def load(eng, h):
+            eng.ingest_u16_rect(ptrs, fh, fw, y0, x0, self.h, self.w, depth, h)
+
+        def put(frame, dst, sh):
+            L.check(self.lib.demfi_frame_to_u16_rect(frame.data_ptr(), dst.data_ptr(), fh, fw, y0, x0, k.y0, k.x0, k.y1, k.x1, e.H, e.W,
+                                                     depth, sh), 'to_u16_rect')
+
+        def emit(j, ctx, sh):
+            fin = ctx['finals'][self.n_tst - 1]
+            put(fin[2], out_full[j], sh)
+            if j == 0:
+                for i in range(2):
+                    put(fin[i], s01_full[i], sh)
+        return load, emit, None
+
     def run_windows_u16(self, windows_u16, depth, out=None, s01=None, ts=None):
         """``run_windows_u8`` for 16-bit frames at bit depth ``depth`` (list of 4-tuples of BGR [h,w,3] ``torch.int16`` GPU
         frames, ready on the current stream), with the same scheduling.  Returns (St [n,M-1,h,w,3], S0S1 [n,2,h,w,3]) as
@@ -591,7 +628,9 @@ class WindowRunner:
         ``instants_run`` / ``instants_padded`` count those.
         ``yuv.depth`` > 8 (10, 12, 14, 16): the payloads hold 16-bit little-endian samples (host_frames[i] is still a 1-D
         uint8 tensor, of twice the bytes, and so are the payloads the sink gets); the frame slots and everything between the
-        two conversions are 16-bit (csrc/yuv_family.hip, ``_u16_io``).  Not with ``tiles``.
+        two conversions are 16-bit (csrc/yuv_family.hip, ``_u16_io``).  On a runner of ``tiles`` every (run, tile) pair reads its
+        tile out of the full 16-bit frame slots and writes its kept rectangle into the full output frames (``_u16_tile_io``):
+        nothing is cropped or stitched.
         ``yuv.layout`` ('420' when absent; ``y4m.LAYOUTS``): the payloads' chroma layout; 4:2:2, 4:4:4 and mono payloads are
         converted by csrc/yuv_family.hip and the outputs keep the layout.
         ``yuv.dedup`` = (hi, lo, frac, max_hold) (None when absent; retimed runners only, with ``window_index``): repeated
@@ -604,8 +643,6 @@ class WindowRunner:
         dedup = getattr(yuv, 'dedup', None)
         if dedup is not None and (self.retime is None or window_index is None or not reuse_frames):
             raise ValueError('WindowRunner.run_clip_u8: repeated frames need a retimed runner (r = M for x M), window_index and reuse_frames')
-        if depth > 8 and self.tiles is not None:
-            raise ValueError('WindowRunner.run_clip_u8: tiles move 8-bit pixels; a %d-bit stream cannot run tiled' % depth)
         if self.retime is not None and yuv is None:
             raise ValueError('WindowRunner.run_clip_u8: a retimed runner needs the Y4M edge (yuv=...)')
         if cuts and (self.retime is None or not reuse_frames):

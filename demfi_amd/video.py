@@ -26,13 +26,16 @@ frames at their byte offsets of the output file (no collective on the data path)
 16-bit frames (csrc/yuv_family.hip, ``y4m.yuv420_to_bgr16_np`` / ``y4m.bgr16_to_yuv420_np``) from the payload to the network's input and
 from its fp32 output frames back; only the fused uint8 store of the fp16 engine is replaced by one egress kernel per frame.
 With ``--dtype fp16`` the network's input record and features are fp16, which resolves 10-bit video fully and about 12 bits at
-best near the ends of the range; ``--dtype fp32`` carries all 16 bits.
+best near the ends of the range; ``--dtype fp32`` carries all 16 bits.  ``--tile-high-depth`` lets such a stream run as tiles
+(``--tile``): the 16-bit ingest and egress kernels address every tile inside the full frames (csrc/frames16.hip), so no tile is
+copied out of a frame or pasted back into one.
 
 ``--any-layout`` also takes 4:2:2, 4:4:4 and grey streams (C422, C444, Cmono, what ``ffmpeg -pix_fmt yuv422p / yuv444p / gray -f
 yuv4mpegpipe`` writes; together with ``--high-depth`` their 10- to 16-bit forms C422pNN, C444pNN, CmonoNN) and gives the output in
 the input's layout and depth.  Only the two conversions at the edge know the layout (csrc/yuv_family.hip, ``y4m.yuv_to_bgr_np`` /
 ``y4m.bgr_to_yuv_np`` and their 16-bit forms): the payload of P samples becomes the same BGR frame slots, and retiming, scene cuts
-(scored over the payload's P samples), the full-length timeline, tiles (8-bit layouts) and rank sharding run as they do for 4:2:0.
+(scored over the payload's P samples), the full-length timeline, tiles (deep layouts with ``--tile-high-depth``) and rank sharding run
+as they do for 4:2:0.
 """
 import os
 import sys
@@ -84,17 +87,20 @@ class VideoRunner:
     (``demfi_amd.tiling``, ``tile_margin`` pixels thrown away next to every cut); ``last_plan`` is the plan of the last input, None
     when it ran untiled, and ``last_instants`` then counts per tile.  ``high_depth``: also take 10- to 16-bit 4:2:0 input
     (C420p10 / C420p12 / C420p14 / C420p16) and give the output at the input's depth (``last_depth``); off by default, and an
-    8-bit stream gives the same bytes either way.  Not together with ``tile`` (tiles move 8-bit pixels).  ``layouts``: also take
+    8-bit stream gives the same bytes either way.  Together with ``tile`` only when ``tile_high_depth`` is set (off by default: a
+    stream above 8 bits is then refused before anything is allocated); every tile is then read out of and written into the full
+    16-bit frames in place, and the switch changes nothing for an 8-bit stream or an untiled run.  ``layouts``: also take
     4:2:2, 4:4:4 and mono input (C422, C444, Cmono; with ``high_depth`` their deep forms C422pNN / C444pNN / CmonoNN) and give the
-    output in the input's layout (``last_layout``); off by default, and a 4:2:0 stream gives the same bytes either way.  The 8-bit
-    layouts run with ``tile``, since tiles cut BGR frames.  ``dedup``: None (default), True or (hi, lo, frac): input frames that
-    repeat the last kept frame (``demfi_amd.cadence``: no 8x8 luma block differs by more than hi, at most frac of them by more
+    output in the input's layout (``last_layout``); off by default, and a 4:2:0 stream gives the same bytes either way.  Every
+    layout runs with ``tile``, since tiles cut BGR frames (the deep ones with ``tile_high_depth``).  ``dedup``: None (default),
+    True or (hi, lo, frac): input frames that repeat the last kept frame (``demfi_amd.cadence``: no 8x8 luma block differs by more than hi, at most frac of them by more
     than lo; True takes the defaults of ffmpeg's mpdecimate) are left out and the windows interpolate over the gap, at most
     ``dedup_max_hold`` repeats in a row; the output's length and timing are unchanged.  ``last_dups`` lists the input frames
     dropped.  One rank only: which frames are kept depends on the whole prefix of the input."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
-                 tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD, **runner_kw):
+                 tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
+                 tile_high_depth=False, **runner_kw):
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
         if mfi is not None and fps is not None:
@@ -110,6 +116,7 @@ class VideoRunner:
         self.scene_cut = S.check_threshold(scene_cut) if scene_cut is not None else None
         self.full_length = bool(full_length)
         self.high_depth = bool(high_depth)
+        self.tile_high_depth = bool(tile_high_depth)
         self.depths = y4m.DEPTHS if self.high_depth else (8,)
         self.layouts = y4m.LAYOUTS if layouts else ('420',)
         self.tile = tile
@@ -145,10 +152,11 @@ class VideoRunner:
         return R.n_output_frames(n_in, self._ratio(hdr), self.full_length)
 
     def _check_depth(self, hdr):
-        """Before anything is allocated for this input: a stream above 8 bits cannot run as tiles."""
-        if hdr.depth > 8 and self.tile is not None:
+        """Before anything is allocated for this input: a stream above 8 bits runs as tiles only with ``tile_high_depth``."""
+        if hdr.depth > 8 and self.tile is not None and not self.tile_high_depth:
             raise ValueError('VideoRunner: tile=%r with a %d-bit stream (C%s): tiles move 8-bit pixels, so --tile and high bit '
-                             'depth do not go together yet; run it untiled, or convert the input to 8 bits' % (self.tile, hdr.depth, hdr.ctag))
+                             'depth do not go together unless asked for; run it untiled, convert the input to 8 bits, or pass '
+                             '--tile-high-depth (tile_high_depth=True)' % (self.tile, hdr.depth, hdr.ctag))
         self.last_depth, self.last_layout = hdr.depth, hdr.layout
 
     def _clip_runner(self, hdr, world, rank):
@@ -324,7 +332,11 @@ def parser():
     ap.add_argument('--high-depth', action='store_true',
                     help='also take 10-, 12-, 14- and 16-bit 4:2:0 (C420p10 .. C420p16, 16-bit little-endian samples) and write the '
                          'output at the input\'s depth, through a 16-bit frame path; --dtype fp16 resolves 10 bits fully and about 12 at '
-                         'best, --dtype fp32 all 16.  Not with --tile.  Off by default (8-bit input only)')
+                         'best, --dtype fp32 all 16.  With --tile only together with --tile-high-depth.  Off by default (8-bit input only)')
+    ap.add_argument('--tile-high-depth', action='store_true',
+                    help='let a 10- to 16-bit stream (--high-depth) run as tiles (--tile): every tile is read out of the full 16-bit '
+                         'frames and its kept part written into the full output frames in place.  Changes nothing without both '
+                         '--tile and --high-depth.  Off by default (such a stream is refused)')
     ap.add_argument('--any-layout', action='store_true',
                     help='also take 4:2:2, 4:4:4 and grey input (C422, C444, Cmono; together with --high-depth their 10- to 16-bit forms '
                          'C422pNN, C444pNN, CmonoNN) and write the output in the input\'s layout: nothing is resampled to 4:2:0 and back.  '
@@ -377,7 +389,7 @@ def main(argv=None):
     D.broadcast_state_dict(model, world, device=dev)
     vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut, full_length=a.full_length,
                      tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth, layouts=a.any_layout, dedup=a.dedup or None,
-                     dedup_max_hold=a.dedup_max_hold)
+                     dedup_max_hold=a.dedup_max_hold, tile_high_depth=a.tile_high_depth)
     t0 = time.perf_counter()
     if world > 1:
         nw, nf = vr.run_file(a.input, a.output, world, rank)

@@ -389,7 +389,12 @@ int demfi_yuv420_sad(const uint8_t* base, const int64_t* a_offsets, const int64_
  * offsets in DEVICE memory), exact in uint64; sad is zeroed on the stream first (demfi_amd/scene.py: sad_np on uint16 arrays).
  * u16_ingest: demfi_u8_ingest for 4 BGR uint16 [h,w,3] frames: v = p / peak, v -= 0.5, v *= 2 in fp32, the same reflect padding
  * and the same three outputs.  frame_to_u16: demfi_frame_to_u8 with peak in place of 255: float64 clip((x + 1) / 2, 0, 1) * peak,
- * truncated. */
+ * truncated.
+ * u16_ingest_rect: u16_ingest for the h x w rectangle at (y0, x0) of four [fh,fw,3] frames: tile pixel (sy, sx) is frame pixel
+ * (y0 + sy, x0 + sx), the reflect padding is in tile coordinates, so the outputs are those of u16_ingest on the contiguous crop.
+ * frame_to_u16_rect: `frame` [3,H,W] is the output of a tile whose pixel (0, 0) is pixel (y0, x0) of the [fh,fw,3] frame `out`; the
+ * pixels of the kept rectangle rows ky0 .. ky1-1, columns kx0 .. kx1-1 (frame coordinates, inside the tile and the frame) are written
+ * to out[(y*fw + x)*3 + c] by the rule of frame_to_u16, and nothing else is.  Both refuse a rectangle that leaves the frame. */
 int demfi_yuv420p16_to_bgr16(const uint16_t* src, int64_t src_stride, uint16_t* dst, int64_t dst_stride, int n, int h, int w, int depth,
                              int matrix, int full_range, int siting, void* stream);
 int demfi_bgr16_to_yuv420p16_gather(const uint16_t* base, const int64_t* src_offsets, uint16_t* dst, int64_t dst_stride, int n, int h,
@@ -399,6 +404,10 @@ int demfi_yuv420p16_sad(const uint16_t* base, const int64_t* a_offsets, const in
 int demfi_u16_ingest(const uint16_t* const* frames, int h, int w, int depth, float* x, void* s2d, float* overlay, int dtype, int H,
                      int W, void* stream);
 int demfi_frame_to_u16(const float* frame, uint16_t* out, int h, int w, int H, int W, int depth, void* stream);
+int demfi_u16_ingest_rect(const uint16_t* const* frames, int fh, int fw, int y0, int x0, int h, int w, int depth, float* x, void* s2d,
+                          float* overlay, int dtype, int H, int W, void* stream);
+int demfi_frame_to_u16_rect(const float* frame, uint16_t* out, int fh, int fw, int y0, int x0, int ky0, int kx0, int ky1, int kx1, int H,
+                            int W, int depth, void* stream);
 
 /* ---- the other chroma layouts of the Y4M edge (csrc/yuv_family.hip; demfi_amd/video.py --any-layout) ------------------------
  * demfi_yuv420_to_bgr / demfi_bgr_to_yuv420_gather and their 16-bit forms for layout = DEMFI_YUV_422 (Y [h,w]; Cb, Cr
@@ -579,6 +588,9 @@ int     demfi_ctx_buffer(const demfi_ctx* ctx, int trunk, int c, const char* nam
 int     demfi_ingest_u8(demfi_ctx* ctx, int trunk, const uint8_t* const* frames, int h, int w, void* stream);
 /* the same for 4 BGR uint16 [h,w,3] frames at bit depth `depth` (demfi_u16_ingest) */
 int     demfi_ingest_u16(demfi_ctx* ctx, int trunk, const uint16_t* const* frames, int h, int w, int depth, void* stream);
+/* the same for the h x w rectangle at (y0, x0) of 4 BGR uint16 [fh,fw,3] frames (demfi_u16_ingest_rect): a tile read in place */
+int     demfi_ingest_u16_rect(demfi_ctx* ctx, int trunk, const uint16_t* const* frames, int fh, int fw, int y0, int x0, int h, int w,
+                              int depth, void* stream);
 int     demfi_forward_trunk_body(demfi_ctx* ctx, int trunk, void* stream);
 /* t-independent segment (FF_RDB + FAC-FB, DeMFInet.py:59, 74) of trunk context `trunk`; x: device fp32 [3,4,H,W]
  * copied into the context's input buffer first, or NULL when the caller already filled buffer "x". */
