@@ -21,6 +21,7 @@ SRCS_CPP="abi.cpp"
 [ -f yuv_family.hip ] && SRCS_HIP="$SRCS_HIP yuv_family.hip"
 [ -f tile.hip ] && SRCS_HIP="$SRCS_HIP tile.hip"
 [ -f dedup.hip ] && SRCS_HIP="$SRCS_HIP dedup.hip"
+[ -f deint.hip ] && SRCS_HIP="$SRCS_HIP deint.hip"
 [ -f wsconv.hip ] && SRCS_HIP="$SRCS_HIP wsconv.hip"
 [ -f ctx.cpp ] && SRCS_CPP="$SRCS_CPP ctx.cpp"
 [ -f png_codec.cpp ] && SRCS_CPP="$SRCS_CPP png_codec.cpp"

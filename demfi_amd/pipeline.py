@@ -19,6 +19,7 @@ import torch
 
 from . import _lib as L
 from . import cadence as K
+from . import deint as I
 from . import retime as R
 from . import scene as S
 from .y4m import payload_size
@@ -209,10 +210,17 @@ class Y4mEdge:
     ``layout``: the payloads' chroma layout (``y4m.LAYOUTS``): it sets P, and for 4:2:2, 4:4:4 and mono the two conversion
     launches are those of the layouts family; everything between them sees BGR frames.  ``yuv_calls`` picks the launches.
     ``tiler``: a ``Tiler`` (8-bit frames: crop, run into ``tcomb``, stitch) or a ``TileGrid`` (16-bit frames: every tile run reads
-    the slots and writes comb[i] in place)."""
+    the slots and writes comb[i] in place).
+    ``fields``: None, or the field order 't' / 'b' of an interlaced input (``demfi_amd.deint``): frame index f is then field f, its
+    payload is uploaded as it is, and ONE ``demfi_yuv_bob`` launch per run of consecutive slots rebuilds the rows of the other field
+    in place (upload stream) before anything reads yuv_in: the conversion, the scene SADs and the block counts see progressive
+    payloads."""
 
-    def __init__(self, runner, batch, slots, cuts, full, tiler=None, depth=8, layout='420', dedup=None, h2d=None):
+    def __init__(self, runner, batch, slots, cuts, full, tiler=None, depth=8, layout='420', dedup=None, h2d=None, fields=None):
         self.rn, self.slots, self.cuts, self.full, self.tiler = runner, slots, cuts, full, tiler
+        if fields not in (None, 't', 'b'):
+            raise ValueError("Y4mEdge: fields must be None, 't' or 'b', got %r" % (fields,))
+        self.fields = fields
         self.dedup, self.h2d, self.kept, self._pending = dedup, h2d, None, []
         self.depth, self.hi = depth, depth > 8
         self.layout = layout
@@ -220,6 +228,7 @@ class Y4mEdge:
             raise ValueError('Y4mEdge: %d-bit frames with a %s' % (depth, type(tiler).__name__))
         self.in_place = self.hi and tiler is not None                    # tiles addressed inside the full frames
         es, fdt = (2, torch.int16) if self.hi else (1, torch.uint8)      # bytes per sample; storage of a frame value
+        self.es = es
         self.r = runner.retime if runner.retime is not None else Fraction(runner.mfi)
         h, w = self.fh, self.fw = (tiler.h, tiler.w) if tiler else (runner.h, runner.w)
         dev, nsl = runner.engine.device, len(slots.frames)
@@ -263,6 +272,7 @@ class Y4mEdge:
         with torch.cuda.stream(self.h2d):
             sl, _ = self.slots.acquire(key, self.h2d)
             self.upload(sl, idx, f)
+            self._bob([(idx, sl)], self.h2d)
         return sl
 
     def block_counts(self, sl, ref):
@@ -308,8 +318,22 @@ class Y4mEdge:
             raise ValueError('frame %d: expected a uint8 [%d] %s payload, got %s %s' % (idx, self.Pb, self.layout, f.dtype, tuple(f.shape)))
         self.yuv_in[sl].copy_(f, non_blocking=True)
 
+    def _bob(self, new, stream):
+        """Interlaced input: the payloads just copied to yuv_in[slot] for the (field index, slot) pairs ``new`` become progressive
+        frames in place, one ``demfi_yuv_bob`` launch per run of consecutive slots (at most 64 payloads each) on ``stream``."""
+        if self.fields is None or not new:
+            return
+        q = {sl: I.field_parity(self.fields, idx) for idx, sl in new}
+        for s0, cnt in consecutive([sl for _, sl in new]):
+            for c0 in range(s0, s0 + cnt, 64):
+                c = min(64, s0 + cnt - c0)
+                L.check(self.rn.lib.demfi_yuv_bob(self.yuv_in[c0].data_ptr(), self.Pb, c, self.fh, self.fw, L.YUV_LAYOUT[self.layout], self.es,
+                                                  sum(q[c0 + j] << j for j in range(c)), stream.cuda_stream), 'yuv_bob')
+
     def uploaded(self, new, h2d):
-        """Payloads copied to yuv_in[slot] -> BGR frame slots, one launch per run of consecutive slots; then the SADs."""
+        """Payloads copied to yuv_in[slot] (interlaced input: bobbed there first) -> BGR frame slots, one launch per run of
+        consecutive slots; then the SADs."""
+        self._bob(new, h2d)                          # the frames staged by --dedup were bobbed when they were staged
         if self._pending:                            # --dedup: the kept frames staged since the last batch
             new, self._pending = self._pending + list(new), []
         sls = [sl for _, sl in new]
@@ -487,9 +511,9 @@ def max_runs(r, cuts, dedup):
     return max(2 if cuts else 1, K.max_window_runs(r, dedup[3]) if dedup is not None else 1)
 
 
-def pipeline_key(batch, y4m, cuts, full, depth=8, layout='420', dedup=None):
+def pipeline_key(batch, y4m, cuts, full, depth=8, layout='420', dedup=None, fields=None):
     """What a cached ``ClipPipeline`` can be reused for."""
-    return (batch, y4m, cuts, full, depth, layout) + ((tuple(dedup),) if dedup is not None else ())
+    return (batch, y4m, cuts, full, depth, layout) + ((tuple(dedup),) if dedup is not None else ()) + (('fields', fields) if fields else ())
 
 
 class KeptFrames:
@@ -565,14 +589,16 @@ class ClipPipeline:
     cuts / the full-length timeline, which size its buffers): H2D of a batch's new frames, its compute, the drain of the
     previous batch and its D2H, on three streams over two sets of output buffers."""
 
-    def __init__(self, runner, batch, y4m, cuts, full, depth=8, layout='420', dedup=None):
+    def __init__(self, runner, batch, y4m, cuts, full, depth=8, layout='420', dedup=None, fields=None):
         dev = self.dev = runner.engine.device
         runner = weakref.proxy(runner)               # the runner owns this pipeline: no reference cycle keeps its buffers alive
-        self.batch, self.key = batch, pipeline_key(batch, y4m, cuts, full, depth, layout, dedup)
+        self.batch, self.key = batch, pipeline_key(batch, y4m, cuts, full, depth, layout, dedup, fields)
         if depth > 8 and not y4m:
             raise ValueError('ClipPipeline: 16-bit frames are those of the Y4M edge only')
         if dedup is not None and not y4m:
             raise ValueError('ClipPipeline: repeated frames are found by the Y4M edge only')
+        if fields is not None and not y4m:
+            raise ValueError('ClipPipeline: fields are bobbed by the Y4M edge only')
         self.h2d, self.d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
         plan = runner.tiles
         fh, fw = (plan.h, plan.w) if plan is not None else (runner.h, runner.w)
@@ -584,7 +610,7 @@ class ClipPipeline:
             J2 = (R.max_instants(runner.retime if runner.retime is not None else Fraction(runner.mfi)) + 2) if y4m else runner.mfi + 1
             rr = (runner.retime if runner.retime is not None else Fraction(runner.mfi)) if y4m else None
             tiler = Tiler(plan, self.slots, runner.lib, dev, batch * (max_runs(rr, cuts, dedup) if y4m else 1) * J2)
-        self.edge = (Y4mEdge(runner, batch, self.slots, cuts, full, tiler, depth, layout, dedup, self.h2d) if y4m
+        self.edge = (Y4mEdge(runner, batch, self.slots, cuts, full, tiler, depth, layout, dedup, self.h2d, fields) if y4m
                      else BgrEdge(runner, batch, self.slots, tiler))
 
     def run(self, host_frames, windows, sink, reuse_frames, yuv, window_index):

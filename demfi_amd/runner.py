@@ -637,10 +637,14 @@ class WindowRunner:
         frames are left out (``demfi_amd.cadence``).  host_frames is then a ``pipeline.KeptFrames`` over the input and ``windows``
         its ``windows()``: frames and windows are named by kept index, every input frame is scored on the GPU as it is
         uploaded (ONE ``demfi_luma_block_counts`` launch each), and window k runs ``cadence.window_runs``.
+        ``yuv.fields`` = 't' / 'b' (None when absent): the input is interlaced with that field order (``demfi_amd.deint``).
+        host_frames[f] is then the payload that holds FIELD f (``y4m.Frames(fields=2)``); every uploaded payload is bobbed in place
+        on the GPU (``demfi_yuv_bob``) before it is converted or scored, and everything else runs as on the progressive stream of
+        those frames.
         Returns the number of windows run."""
         cuts, full = getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False))
         depth, layout = int(getattr(yuv, 'depth', 8)), getattr(yuv, 'layout', '420')
-        dedup = getattr(yuv, 'dedup', None)
+        dedup, fields = getattr(yuv, 'dedup', None), getattr(yuv, 'fields', None)
         if dedup is not None and (self.retime is None or window_index is None or not reuse_frames):
             raise ValueError('WindowRunner.run_clip_u8: repeated frames need a retimed runner (r = M for x M), window_index and reuse_frames')
         if self.retime is not None and yuv is None:
@@ -649,9 +653,9 @@ class WindowRunner:
             raise ValueError('WindowRunner.run_clip_u8: scene cuts need a retimed runner (r = M for x M) and reuse_frames')
         if full and (self.retime is None or window_index is None):
             raise ValueError('WindowRunner.run_clip_u8: the full-length timeline needs a retimed runner and window_index')
-        if self._pipeline is None or self._pipeline.key != pipeline_key(batch, yuv is not None, cuts, full, depth, layout, dedup):
+        if self._pipeline is None or self._pipeline.key != pipeline_key(batch, yuv is not None, cuts, full, depth, layout, dedup, fields):
             self._pipeline = None                        # release the old buffers before the new ones are allocated
-            self._pipeline = ClipPipeline(self, batch, yuv is not None, cuts, full, depth, layout, dedup)
+            self._pipeline = ClipPipeline(self, batch, yuv is not None, cuts, full, depth, layout, dedup, fields)
         return self._pipeline.run(host_frames, windows, sink, reuse_frames, yuv, window_index)
 
     def __del__(self):

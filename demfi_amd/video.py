@@ -36,6 +36,16 @@ the input's layout and depth.  Only the two conversions at the edge know the lay
 ``y4m.bgr_to_yuv_np`` and their 16-bit forms): the payload of P samples becomes the same BGR frame slots, and retiming, scene cuts
 (scored over the payload's P samples), the full-length timeline, tiles (deep layouts with ``--tile-high-depth``) and rank sharding run
 as they do for 4:2:0.
+
+``--deinterlace`` also takes interlaced streams (``It``: top field first, ``Ib``: bottom field first; what ``ffmpeg -f yuv4mpegpipe``
+writes for 1080i, 576i, 480i and DV material) and bobs them: every payload gives two progressive frames, one per field in field
+order, each at its own time instant, so n payloads at F are a progressive stream of 2n frames at 2F ("50i in, 100p out" with
+``--mfi 2``).  The payload is uploaded as it is and one launch rebuilds the other field's rows in place by an edge-directed line
+average (csrc/deint.hip, defined by ``deint.bob_plane_np``) before it is converted; everything behind that -- rates, scene cuts,
+repeated frames, the full-length timeline, tiles, depths, layouts, rank sharding -- runs on the progressive stream unchanged.
+``--fps`` and ``--mfi`` count from the field rate 2F.  The output is always progressive.  Not offered: motion-adaptive or
+temporal deinterlacing, inverse telecine, mixed-mode streams (``Im``) and interlaced output; the quarter-row chroma offset of
+interlaced 4:2:0 fields is not modelled; a payload is uploaded once per field.
 """
 import os
 import sys
@@ -45,6 +55,7 @@ import torch
 
 from . import _lib as L
 from . import cadence as K
+from . import deint as I
 from . import dist as D
 from . import retime as R
 from . import scene as S
@@ -60,10 +71,13 @@ class YuvEdge:
     threshold T of scene-cut detection (``demfi_amd.scene``).  ``full_length``: the full-length timeline (``retime``).
     ``depth``: bits per sample, 8, or 10 / 12 / 14 / 16 for payloads of 16-bit samples.  ``layout``: the payloads' chroma
     layout, one of ``y4m.LAYOUTS`` (``siting`` only matters to '420').  ``dedup``: None, or (hi, lo, frac, max_hold) of
-    repeated-frame detection (``demfi_amd.cadence``)."""
+    repeated-frame detection (``demfi_amd.cadence``).  ``fields``: None, or the field order 't' / 'b' of an interlaced input whose
+    fields are the stream's frames (``demfi_amd.deint``)."""
 
-    def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None):
+    def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
+                 fields=None):
         self.dedup = dedup
+        self.fields = fields
         self.depth = y4m.check_depth(depth)
         self.layout = y4m.check_layout(layout)
         self.matrix = {'bt601': L.BT601, 'bt709': L.BT709}[matrix]
@@ -96,11 +110,16 @@ class VideoRunner:
     True or (hi, lo, frac): input frames that repeat the last kept frame (``demfi_amd.cadence``: no 8x8 luma block differs by more than hi, at most frac of them by more
     than lo; True takes the defaults of ffmpeg's mpdecimate) are left out and the windows interpolate over the gap, at most
     ``dedup_max_hold`` repeats in a row; the output's length and timing are unchanged.  ``last_dups`` lists the input frames
-    dropped.  One rank only: which frames are kept depends on the whole prefix of the input."""
+    dropped.  One rank only: which frames are kept depends on the whole prefix of the input.  ``deinterlace``: also take
+    interlaced input of a fixed field order (``It`` / ``Ib``) and bob it (``demfi_amd.deint``): field f = 2p + s of payload p is
+    progressive frame f, so the input counts as 2n frames at twice its rate -- ``mfi`` multiplies and ``fps`` is checked against
+    that field rate, and windows, ranks and output counts follow it; the output is progressive.  ``last_fields`` is None, 'tff'
+    or 'bff'.  Off by default (an interlaced stream is refused before anything is allocated); a progressive stream gives the same
+    bytes either way."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
-                 tile_high_depth=False, **runner_kw):
+                 tile_high_depth=False, deinterlace=False, **runner_kw):
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
         if mfi is not None and fps is not None:
@@ -117,6 +136,8 @@ class VideoRunner:
         self.full_length = bool(full_length)
         self.high_depth = bool(high_depth)
         self.tile_high_depth = bool(tile_high_depth)
+        self.deinterlace = bool(deinterlace)
+        self.last_fields = None
         self.depths = y4m.DEPTHS if self.high_depth else (8,)
         self.layouts = y4m.LAYOUTS if layouts else ('420',)
         self.tile = tile
@@ -151,6 +172,21 @@ class VideoRunner:
     def _n_out(self, n_in, hdr):
         return R.n_output_frames(n_in, self._ratio(hdr), self.full_length)
 
+    def _progressive(self, hdr):
+        """(the header everything downstream works on, field order or None, input frames per payload) of an input with header
+        ``hdr``: an interlaced stream counts as its fields, a progressive stream at twice the rate (``deint.progressive_header``).
+        Before anything is allocated: a requested output rate below the field rate is refused here."""
+        order = hdr.interlace if hdr.interlace in ('t', 'b') else None
+        self.last_fields = {'t': 'tff', 'b': 'bff', None: None}[order]
+        if order is None:
+            return hdr, None, 1
+        phdr = I.progressive_header(hdr)
+        if self.fps is not None and self.fps < phdr.fps:
+            raise ValueError('VideoRunner: output frame rate %s is below the field rate %s of the interlaced input (%s frames/s, two fields '
+                             'each): --deinterlace gives one frame per field, so F_out must be at least %s'
+                             % (self.fps, phdr.fps, hdr.fps, phdr.fps))
+        return phdr, order, 2
+
     def _check_depth(self, hdr):
         """Before anything is allocated for this input: a stream above 8 bits runs as tiles only with ``tile_high_depth``."""
         if hdr.depth > 8 and self.tile is not None and not self.tile_high_depth:
@@ -184,16 +220,16 @@ class VideoRunner:
         self.last_st_frames = sum(kind == R.ST for k in range(lo, lo + n) for _, kind, _ in R.window_outputs(k, r, full_length=self.full_length))
         return n
 
-    def _edge(self, hdr, with_s1):
+    def _edge(self, hdr, with_s1, order=None):
         return YuvEdge(y4m.auto_matrix(hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
-                       self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup)
+                       self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup, order)
 
-    def _run_dedup(self, cr, hdr, frames, sink):
+    def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
         det = K.Detector(hdr.h, hdr.w, *self.dedup)
         kf = KeptFrames(frames, det, self._ratio(hdr), self.full_length)
         n = self._run(cr, hdr, lambda: 0, lambda: cr.runner.run_clip_u8(kf, kf.windows(), sink, batch=self.batch,
-                                                                       yuv=self._edge(hdr, lambda j: False), window_index=kf.index))
+                                                                       yuv=self._edge(hdr, lambda j: False, order), window_index=kf.index))
         self.last_st_frames, self.last_dups = kf.st_frames, list(det.dups)
         self.last_cuts = [det.kept[j] for j in self.last_cuts]      # scored over the kept sequence: back to input frames
         self.last_decode_peak = frames.peak
@@ -202,27 +238,27 @@ class VideoRunner:
     def run_stream(self, src, dst):
         """One rank, sequential binary streams (stdin / stdout work): nothing is seeked, the input is read in batches of
         windows and every batch is written (and flushed) as it drains.  Returns (windows, frames written)."""
-        rd = y4m.Reader(src, self.depths, self.layouts)
-        hdr = rd.header
+        rd = y4m.Reader(src, self.depths, self.layouts, self.deinterlace)
+        hdr, order, per = self._progressive(rd.header)
         self._check_depth(hdr)
         cr = self._clip_runner(hdr, 1, 0)
         wr = y4m.Writer(dst, self._out_header(hdr))
-        frames = y4m.Frames(rd, full_length=self.full_length)
+        frames = y4m.Frames(rd, full_length=self.full_length, fields=per)
         self.last_dups = []
 
         def sink(k, payloads):
             wr.write(payloads)
             dst.flush()
         if self.dedup is not None:
-            n = self._run_dedup(cr, hdr, frames, sink)
+            n = self._run_dedup(cr, hdr, frames, sink, order)
             dst.flush()
             return n, wr.frames
         if self.full_length:                             # window j of the sequence is window first_window + j
             def index(j):
                 return frames.first_window + j
-            edge, kw = self._edge(hdr, lambda j: frames.is_last(index(j))), {'window_index': index}
+            edge, kw = self._edge(hdr, lambda j: frames.is_last(index(j)), order), {'window_index': index}
         else:
-            edge, kw = self._edge(hdr, frames.is_last), {}
+            edge, kw = self._edge(hdr, frames.is_last, order), {}
         n = self._run(cr, hdr, lambda: frames.first_window or 0,
                       lambda: cr.runner.run_clip_u8(frames, frames.windows(), sink, batch=self.batch, yuv=edge, **kw))
         dst.flush()
@@ -238,9 +274,10 @@ class VideoRunner:
                              'cannot place its block of windows from k and r alone; run --dedup on one rank' % world)
         self.last_dups = []
         with open(in_path, 'rb') as f:
-            hdr, _, offs = y4m.scan(f, self.depths, self.layouts)
+            hdr, _, offs = y4m.scan(f, self.depths, self.layouts, self.deinterlace)
+            hdr, order, per = self._progressive(hdr)
             self._check_depth(hdr)
-            n_in = len(offs)
+            n_in = per * len(offs)                       # an interlaced input counts as its fields
             ohdr = self._out_header(hdr)
             hb = ohdr.encode()
             total = self._n_out(n_in, hdr)
@@ -254,7 +291,8 @@ class VideoRunner:
             if self.dedup is not None:
                 with open(out_path, 'r+b') as o:
                     wr = y4m.Writer(o, ohdr, at=len(hb))
-                    n = self._run_dedup(cr, hdr, y4m.Frames.from_file(f, offs, 0, n_in, hdr.payload), lambda k, p: wr.write(p))
+                    n = self._run_dedup(cr, hdr, y4m.Frames.from_file(f, offs, 0, n_in, hdr.payload, fields=per), lambda k, p: wr.write(p),
+                                        order)
                 return n, wr.frames
             lo, wins = cr.my_windows(n_in, full)
             if not wins:
@@ -263,13 +301,13 @@ class VideoRunner:
             last = R.first_window(n_in, full) + R.n_windows(n_in, full) - 1
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
             first = S.first_frame(lo) if self.scene_cut is not None else max(lo, 0)
-            frames = y4m.Frames.from_file(f, offs, first, lo + len(wins) + 3, hdr.payload)
+            frames = y4m.Frames.from_file(f, offs, first, lo + len(wins) + 3, hdr.payload, fields=per)
             at = R.block_offset(len(hb), lo, self._ratio(hdr), hdr.payload, full)
             kw = {'window_index': lambda j: lo + j} if full else {}
             with open(out_path, 'r+b') as o:
                 wr = y4m.Writer(o, ohdr, at=at)
                 n = self._run(cr, hdr, lambda: lo, lambda: cr.runner.run_clip_u8(frames, wins, lambda k, p: wr.write(p), batch=self.batch,
-                                                                                 yuv=self._edge(hdr, lambda k: lo + k == last), **kw))
+                                                                                 yuv=self._edge(hdr, lambda k: lo + k == last, order), **kw))
             self.last_decode_peak = frames.peak
             return n, wr.frames
 
@@ -298,12 +336,13 @@ def parser():
     """The command line of ``main``."""
     import argparse
     ap = argparse.ArgumentParser(prog='python -m demfi_amd.video', description=main.__doc__.split('\n\n')[0],
-                                 epilog='Input: 8-bit 4:2:0 progressive Y4M (C420jpeg, C420, C420mpeg2; XCOLORRANGE=FULL|LIMITED), '
+                                 epilog='Input: 8-bit 4:2:0 progressive Y4M (Ip, I? or no I tag; C420jpeg, C420, C420mpeg2; XCOLORRANGE=FULL|LIMITED), '
                                         'e.g. ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe -; with --high-depth also 10- to 16-bit '
                                         '4:2:0 (C420p10, C420p12, C420p14, C420p16), e.g. ffmpeg -i in.mkv -pix_fmt yuv420p10le -strict -1 '
                                         '-f yuv4mpegpipe -; with --any-layout also 4:2:2, 4:4:4 and grey (C422, C444, Cmono and, with '
                                         '--high-depth, C422pNN, C444pNN, CmonoNN), e.g. ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 '
-                                        '-f yuv4mpegpipe -.  Output: C420jpeg (C420pNN at the input\'s depth; the input\'s layout and '
+                                        '-f yuv4mpegpipe -; with --deinterlace also interlaced streams of a fixed field order (It, Ib), every '
+                                        'field a frame at twice the rate.  Output: progressive, C420jpeg (C420pNN at the input\'s depth; the input\'s layout and '
                                         'depth for the other layouts), the input\'s '
                                         'matrix and range.  n input frames give (n-3)*M + 1 output frames: the first and the last '
                                         'input frame have no output, as in the reference (--full-length: n*M frames from input '
@@ -347,6 +386,12 @@ def parser():
                          'block differs from the last kept frame by more than %d and at most %s of them by more than %d (the '
                          'defaults of ffmpeg\'s mpdecimate).  The output keeps its length and timing.  One rank only.  Off by '
                          'default' % (K.DEFAULT_HI, K.DEFAULT_FRAC, K.DEFAULT_LO))
+    ap.add_argument('--deinterlace', action='store_true',
+                    help='also take interlaced input (It: top field first, Ib: bottom field first; 1080i, 576i, 480i, DV) and bob it on '
+                         'the GPU: every field becomes a progressive frame at its own time instant (the other field\'s rows are rebuilt '
+                         'by an edge-directed line average), so n payloads at F count as 2n frames at 2F: --mfi M gives 2*M*F, --fps '
+                         'must be at least 2F, and 50i --mfi 2 is 100p.  The output is progressive.  Mixed-mode streams (Im) stay '
+                         'refused.  Off by default (progressive input only); changes nothing for a progressive stream')
     ap.add_argument('--dedup-max-hold', type=int, default=K.DEFAULT_MAX_HOLD, metavar='N',
                     help='with --dedup: after N repeats in a row the next frame is kept whatever it shows (default %d), so a still '
                          'scene stays a sequence of frames N + 1 apart' % K.DEFAULT_MAX_HOLD)
@@ -389,7 +434,7 @@ def main(argv=None):
     D.broadcast_state_dict(model, world, device=dev)
     vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut, full_length=a.full_length,
                      tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth, layouts=a.any_layout, dedup=a.dedup or None,
-                     dedup_max_hold=a.dedup_max_hold, tile_high_depth=a.tile_high_depth)
+                     dedup_max_hold=a.dedup_max_hold, tile_high_depth=a.tile_high_depth, deinterlace=a.deinterlace)
     t0 = time.perf_counter()
     if world > 1:
         nw, nf = vr.run_file(a.input, a.output, world, rank)
@@ -418,6 +463,7 @@ def main(argv=None):
                           'instants_run': int(ti), 'instants_padded': int(tp), 'cut_windows': int(tc), 'dups': len(vr.last_dups),
                           'tiles': vr.last_plan.n_tiles if vr.last_plan is not None else 1,
                           'tile': vr.last_plan.label() if vr.last_plan is not None else None, 'depth': vr.last_depth, 'layout': vr.last_layout,
+                          'fields': vr.last_fields,
                           'weights': os.path.basename(a.checkpoint) if a.checkpoint else 'synthetic_state_dict(0) (random init: no checkpoint given)',
                           'out': a.output}), file=sys.stderr)
     D.finalize()

@@ -51,6 +51,10 @@ HIGH_DEPTH_HINT = '; or keep the bit depth: --high-depth accepts 10- to 16-bit 4
 LAYOUTS = ('420', '422', '444', 'mono')                               # what ``layouts=LAYOUTS`` (--any-layout) accepts
 ANY_LAYOUT_HINT = ('; or keep the chroma layout: --any-layout accepts 4:2:2, 4:4:4 and grey (C422, C444, Cmono; together with '
                    '--high-depth also C422pNN, C444pNN, CmonoNN for NN in 10, 12, 14, 16)')
+DEINTERLACE_HINT = ('; or pass --deinterlace, which bobs the fields of an It (top field first) or Ib (bottom field first) stream '
+                    'to progressive frames at twice the rate')
+MIXED_HINT = ('; --deinterlace takes It and Ib only: a mixed-mode stream (Im) changes its field order from frame to frame and needs '
+              'a field-order fix upstream (for example ffmpeg -vf fieldorder=tff)')
 _CHROMA = {None: '420jpeg', '420jpeg': '420jpeg', '420': '420jpeg', '420mpeg2': '420mpeg2'}
 _MAX_LINE = 4096
 
@@ -391,11 +395,12 @@ _LAYOUT_TAGS = dict([(lay, (lay, 8)) for lay in LAYOUTS[1:]] +
 _LAYOUT_NAMES = {'420': '4:2:0', '422': '4:2:2', '444': '4:4:4', 'mono': 'mono'}
 
 
-def parse_header(line, depths=(8,), layouts=('420',)):
+def parse_header(line, depths=(8,), layouts=('420',), fields=False):
     """One header line (bytes, with or without the trailing newline) -> Header.  Raises Y4MError.  ``depths``: the bit depths
     taken; the default is 8-bit only, ``DEPTHS`` also takes C420p10 / C420p12 / C420p14 / C420p16.  ``layouts``: the chroma
     layouts taken; the default is 4:2:0 only, ``LAYOUTS`` also takes C422 / C444 / Cmono and, with ``depths=DEPTHS``, their deep
-    forms C422pNN / C444pNN / CmonoNN."""
+    forms C422pNN / C444pNN / CmonoNN.  ``fields``: also take interlaced streams of a fixed field order, ``It`` and ``Ib``
+    (``Header.interlace`` is then 't' or 'b'; ``demfi_amd.deint`` makes frames of their fields); mixed-mode ``Im`` stays refused."""
     if isinstance(line, str):
         line = line.encode()
     line = line.rstrip(b'\n')
@@ -421,8 +426,10 @@ def parse_header(line, depths=(8,), layouts=('420',)):
                 raise Y4MError('Y4M: bad frame rate F%s' % val)
             fps = Fraction(int(m.group(1)), int(m.group(2)))
         elif tag == 'I':
-            if val not in ('p', '?'):
-                _reject('interlaced video (I%s)' % val)
+            if val == 'm':
+                _reject('mixed-mode interlaced video (Im)', MIXED_HINT)
+            if val not in ('p', '?') and not (fields and val in ('t', 'b')):
+                _reject('interlaced video (I%s)' % val, DEINTERLACE_HINT if val in ('t', 'b') else '')
             inter = val
         elif tag == 'A':
             aspect = val
@@ -523,12 +530,12 @@ def _frame_line(line, index):
 class Reader:
     """Sequential reader of a binary stream (a file, or stdin: nothing is seeked).  ``read_into(buf)`` fills one payload."""
 
-    def __init__(self, f, depths=(8,), layouts=('420',)):
+    def __init__(self, f, depths=(8,), layouts=('420',), fields=False):
         self.f = f
         line = _readline(f, 'header')
         if not line:
             raise Y4MError('Y4M: empty input: %s' % FIX)
-        self.header = parse_header(line, depths, layouts)
+        self.header = parse_header(line, depths, layouts, fields)
         self.header_bytes = len(line)
         self.index = 0                                  # frames read so far
 
@@ -548,11 +555,11 @@ class Reader:
         return True
 
 
-def scan(f, depths=(8,), layouts=('420',)):
+def scan(f, depths=(8,), layouts=('420',), fields=False):
     """One pass over the frame headers of a seekable file: (Header, header bytes, [file offset of every payload]).  The
-    payloads are skipped, not read; a truncated last frame raises.  ``depths``, ``layouts``: as ``parse_header``."""
+    payloads are skipped, not read; a truncated last frame raises.  ``depths``, ``layouts``, ``fields``: as ``parse_header``."""
     f.seek(0)
-    rd = Reader(f, depths, layouts)
+    rd = Reader(f, depths, layouts, fields)
     size = os.fstat(f.fileno()).st_size if hasattr(f, 'fileno') else None
     p = rd.header.payload
     offs = []
@@ -578,13 +585,19 @@ class Frames:
 
     Frames(reader): the frames of a stream, read in order (stdin: nothing is seeked).
     Frames.from_file(f, offsets, first, stop): frames first .. stop-1 of a scanned file (``scan``), by seek + readinto.
-    ``full_length``: ``windows`` / ``is_last`` follow the full-length timeline (``retime``)."""
+    ``full_length``: ``windows`` / ``is_last`` follow the full-length timeline (``retime``).
+    ``fields`` = 2 (an interlaced input, ``demfi_amd.deint``): index i is FIELD i, and both fields of payload i // 2 are the
+    same tensor: the payload is read once and never copied.  ``first`` / ``stop``, ``n``, ``is_last``, ``windows`` and the
+    dropping count fields; ``peak`` counts the payload tensors held."""
 
-    def __init__(self, reader=None, payload=None, fetch=None, first=0, stop=None, pinned=None, full_length=False):
+    def __init__(self, reader=None, payload=None, fetch=None, first=0, stop=None, pinned=None, full_length=False, fields=1):
         import torch
+        if fields not in (1, 2):
+            raise ValueError('Frames: fields must be 1 or 2, got %r' % (fields,))
         self.payload = reader.header.payload if reader is not None else payload
         self._fetch = fetch or (lambda i, buf: reader.read_into(buf))
-        self.next, self.stop = first, stop
+        self.fields = fields
+        self.next, self.stop = first - first % fields, stop
         self.pinned = torch.cuda.is_available() if pinned is None else pinned
         self.full_length = full_length
         self.buf = {}
@@ -593,26 +606,29 @@ class Frames:
         self.peak = 0
 
     @classmethod
-    def from_file(cls, f, offsets, first, stop, payload, pinned=None):
+    def from_file(cls, f, offsets, first, stop, payload, pinned=None, fields=1):
         def fetch(i, buf):
             f.seek(offsets[i])
             mv = memoryview(buf).cast('B')
             if _readinto_full(f, mv) != len(mv):
                 raise Y4MError('Y4M: truncated frame %d' % i)
             return True
-        return cls(payload=payload, fetch=fetch, first=first, stop=min(stop, len(offsets)), pinned=pinned)
+        return cls(payload=payload, fetch=fetch, first=first, stop=min(stop, fields * len(offsets)), pinned=pinned, fields=fields)
 
     def has(self, i):
         """Reads through frame i; False when the input ends before it."""
         import torch
         while self.next <= i and self.n is None:
             t = torch.empty(self.payload, dtype=torch.uint8, pin_memory=self.pinned)
-            if (self.stop is not None and self.next >= self.stop) or not self._fetch(self.next, t.numpy()):
+            if (self.stop is not None and self.next >= self.stop) or not self._fetch(self.next // self.fields, t.numpy()):
                 self.n = self.next
                 break
-            self.buf[self.next] = t
-            self.next += 1
-            self.peak = max(self.peak, len(self.buf))
+            for j in range(self.next, self.next + self.fields):          # the fields of a payload share its tensor
+                self.buf[j] = t
+            self.next += self.fields
+            if self.stop is not None:
+                self.next = min(self.next, self.stop)
+            self.peak = max(self.peak, len({j // self.fields for j in self.buf}))
         return i < self.next
 
     def __getitem__(self, i):

@@ -437,6 +437,17 @@ int demfi_bgr16_to_yuvl16_gather(const uint16_t* base, const int64_t* src_offset
 int demfi_luma_block_counts(const uint8_t* base, const int64_t* a_offsets, const int64_t* b_offsets, int n, int h, int w,
                             int sample_bytes, int64_t hi_s, int64_t lo_s, uint32_t* counts, void* stream);
 
+/* ---- interlaced input of the Y4M edge (csrc/deint.hip; demfi_amd/video.py --deinterlace) ------------------------------------------
+ * yuv_bob: the n (0..64) payloads at payloads + i*stride_bytes (Y [h,w], then Cb and Cr of `layout`; sample_bytes = 1, or 2 for
+ * 16-bit little-endian samples: even address and stride) become progressive frames IN PLACE: in every plane of payload i the rows
+ * of parity q_i = bit i of odd_mask (0: even rows, the top field; 1: odd rows) are kept and the other rows are rebuilt from
+ * them by the five-direction edge-directed line average of demfi_amd/deint.py (bob_plane_np), which this matches sample for
+ * sample; a missing row with one neighbour copies it, a one-row plane whose row is not kept stays.  Kept rows and everything
+ * between the payloads are not written.  Any h, w in 2..16384; stride_bytes >= the payload's bytes; one launch for all planes of
+ * all payloads; n = 0 does nothing. */
+int demfi_yuv_bob(void* payloads, int64_t stride_bytes, int n, int h, int w, int layout, int sample_bytes, uint64_t odd_mask,
+                  void* stream);
+
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
  * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
