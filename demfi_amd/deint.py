@@ -21,13 +21,44 @@ interlaced 4:2:0 the chroma rows alternate between the fields as the luma rows d
 taken to sit at the plane's own row positions; the quarter-row vertical offset that interlaced 4:2:0 chroma has per field is
 not modelled.
 
-Out of scope: motion-adaptive or temporal deinterlacing (it would need the neighbouring payloads resident at the bob), inverse
-telecine, mixed-mode streams (``Im``) and interlaced output.
+``adaptive_plane_np`` DEFINES the motion-adaptive mode (``--deinterlace-mode adaptive``; csrc/deint.hip,
+``demfi_yuv_deint_adaptive``): yadif's temporal rule (the ``filter_line`` of ffmpeg's filter with the spatial check on) around this
+module's own spatial predictor.  Field f of parity q keeps its rows; a missing row y with both neighbours inside the plane is
+rebuilt sample by sample from the fields around it in time, each read ONLY at rows of its own parity out of the payload that holds
+it: P1 = field f-1 and N1 = field f+1 (parity 1-q: rows y, y-2, y+2), P2 = field f-2 and N2 = field f+2 (parity q: rows y-1, y+1).
+With c = cur[y-1][x] and e = cur[y+1][x]:
+
+    d  = (P1[y][x] + N1[y][x]) >> 1
+    t0 = |P1[y][x] - N1[y][x]| >> 1
+    t1 = (|P2[y-1][x] - c| + |P2[y+1][x] - e|) >> 1
+    t2 = (|N2[y-1][x] - c| + |N2[y+1][x] - e|) >> 1
+    diff = max(t0, t1, t2)
+
+and, when y-2 >= 0 and y+2 < rows, the spatial check
+
+    b  = (P1[y-2][x] + N1[y-2][x]) >> 1        g  = (P1[y+2][x] + N1[y+2][x]) >> 1
+    mx = max(d-e, d-c, min(b-c, g-e))          mn = min(d-e, d-c, max(b-c, g-e))
+    diff = max(diff, mn, -mx)
+
+    out = clamp(sp, d - diff, d + diff),  sp = the bob's value at (y, x), exactly ``bob_plane_np``'s
+
+Integers throughout, no state between samples.  A missing row with one neighbour copies it and a plane without a kept row is
+returned as it is, as in the bob.  A field absent at an end of the stream is replaced by its partner on the other side in time (P1
+by N1 or N1 by P1, P2 by N2 or N2 by P2); every payload has two fields, so one of P1 and N1 always exists in a stream, and the
+function given neither returns the bob's value (the kernel does the same); with P2 and N2 both absent (a one-payload stream) t1 and
+t2 are dropped.  So a static scene comes back at full vertical resolution (diff = 0, out = d = the source row) and where the
+picture moves diff is large and out = sp, the bob.  Scene cuts need nothing special for the same reason: across a cut diff is large
+and the result falls back to the spatial value.  Output field f depends on payloads p-1, p and p+1 of the input only.
+
+Out of scope: ``--dedup`` together with the adaptive mode (repeated frames are staged and discarded one field at a time, the
+adaptive mode needs two fields of lookahead; ``--deinterlace-mode bob`` is the way out), inverse telecine, mixed-mode streams
+(``Im``) and interlaced output.
 """
 import numpy as np
 
 from . import y4m
 
+MODES = ('bob', 'adaptive')
 
 def field_parity(order, f):
     """Parity q of the rows field f keeps (0: even rows, the top field; 1: odd rows): ``order`` 't' starts with the top field,
@@ -55,11 +86,24 @@ def bob_plane_np(plane, q):
     for y in range(1 - q, rows, 2):                           # a missing row at an end of the plane has one neighbour
         if y == 0 or y == rows - 1:
             out[y] = p[y + 1] if y == 0 else p[y - 1]
-    ys = np.arange(1 - q, rows, 2)
-    ys = ys[(ys >= 1) & (ys + 1 < rows)]
+    ys = _interior_rows(rows, q)
     if ys.size == 0:
         return out
-    a, b = p[ys - 1].astype(np.int64), p[ys + 1].astype(np.int64)
+    out[ys] = edge_average_np(p[ys - 1], p[ys + 1]).astype(p.dtype)
+    return out
+
+
+def _interior_rows(rows, q):
+    """The missing rows (parity 1-q) of a plane of ``rows`` rows that have both neighbours inside it."""
+    ys = np.arange(1 - q, rows, 2)
+    return ys[(ys >= 1) & (ys + 1 < rows)]
+
+
+def edge_average_np(a, b):
+    """The bob's spatial value of the rows between rows ``a`` (above) and ``b`` (below), [m, cols] each -> int64 [m, cols]: the
+    five-direction edge-directed line average of the module's docstring.  ``bob_plane_np`` and ``adaptive_plane_np`` share it."""
+    a, b = np.asarray(a).astype(np.int64), np.asarray(b).astype(np.int64)
+    cols = a.shape[1]
     xs = np.arange(cols)
 
     def at(r, off):
@@ -77,7 +121,52 @@ def bob_plane_np(plane, q):
             s = score(j)
             taken = taken & (s < best)
             best, res = np.where(taken, s, best), np.where(taken, pred(j), res)
-    out[ys] = res.astype(p.dtype)
+    return res
+
+
+def adaptive_bounds_np(planes, q):
+    """(ys, d, diff) of ``adaptive_plane_np``: the interior missing rows and, int64 [len(ys), cols] each, the temporal average d and
+    the half-width diff of the interval [d - diff, d + diff] the spatial value is clamped to.  None when P1 and N1 are both absent."""
+    p2, p1, cur, n1, n2 = [None if p is None else np.asarray(p) for p in planes]
+    if cur is None or cur.ndim != 2 or q not in (0, 1) or any(p is not None and p.shape != cur.shape for p in (p2, p1, n1, n2)):
+        raise ValueError('adaptive_plane_np: (P2, P1, cur, N1, N2) planes of one [rows, cols] shape (None: absent) and q in (0, 1)')
+    if p1 is None and n1 is None:
+        return None
+    p1, n1 = (n1 if p1 is None else p1), (p1 if n1 is None else n1)
+    p2, n2 = (n2 if p2 is None else p2), (p2 if n2 is None else n2)
+    rows = cur.shape[0]
+    ys = _interior_rows(rows, q) if rows > q else np.arange(0)
+
+    def at(p, r):
+        return p[r].astype(np.int64)
+    c, e = at(cur, ys - 1), at(cur, ys + 1)
+    py, ny = at(p1, ys), at(n1, ys)
+    d = (py + ny) >> 1
+    diff = np.abs(py - ny) >> 1
+    if p2 is not None:
+        for t in (p2, n2):
+            diff = np.maximum(diff, (np.abs(at(t, ys - 1) - c) + np.abs(at(t, ys + 1) - e)) >> 1)
+    ok = (ys - 2 >= 0) & (ys + 2 < rows)                       # rows y-2 and y+2 exist: the spatial check
+    up, dn = np.where(ok, ys - 2, ys), np.where(ok, ys + 2, ys)
+    b, g = (at(p1, up) + at(n1, up)) >> 1, (at(p1, dn) + at(n1, dn)) >> 1
+    mx = np.maximum(np.maximum(d - e, d - c), np.minimum(b - c, g - e))
+    mn = np.minimum(np.minimum(d - e, d - c), np.maximum(b - c, g - e))
+    diff = np.where(ok[:, None], np.maximum(diff, np.maximum(mn, -mx)), diff)
+    return ys, d, diff
+
+
+def adaptive_plane_np(planes, q):
+    """``planes`` = (P2, P1, cur, N1, N2): the planes [rows, cols] that hold fields f-2 .. f+2 (None for a field the stream does not
+    have), field f of parity ``q`` kept in ``cur`` -> ``cur`` with its other rows rebuilt by the motion-adaptive rule (the module's
+    docstring); same dtype.  Of P1 and N1 only rows of parity 1-q are read, of P2 and N2 only rows of parity q, of ``cur`` only its
+    kept rows: what the other rows of any of them hold does not matter."""
+    cur = np.asarray(planes[2])
+    out = bob_plane_np(cur, q)
+    bounds = adaptive_bounds_np(planes, q)
+    if bounds is None or bounds[0].size == 0:
+        return out
+    ys, d, diff = bounds
+    out[ys] = np.clip(out[ys].astype(np.int64), d - diff, d + diff).astype(cur.dtype)
     return out
 
 
@@ -92,3 +181,36 @@ def bob_payload_np(payload, h, w, depth, layout, q):
         raise ValueError('a payload of 8-bit samples is a uint8 array, got %s' % a.dtype)
     planes = y4m.split_planes_layout(a, h, w, y4m.check_layout(layout))
     return np.concatenate([bob_plane_np(p, q).reshape(-1) for p in planes if p is not None])
+
+
+def _samples(payload, depth):
+    a = y4m.as_samples16(payload) if depth > 8 else (np.frombuffer(payload, np.uint8) if not isinstance(payload, np.ndarray)
+                                                    else payload.reshape(-1))
+    if depth == 8 and a.dtype != np.uint8:
+        raise ValueError('a payload of 8-bit samples is a uint8 array, got %s' % a.dtype)
+    return a
+
+
+def adaptive_payload_np(payloads, h, w, depth, layout, q):
+    """``payloads`` = the five payloads (as ``bob_payload_np`` takes one; None for an absent field) that hold fields f-2, f-1, f, f+1
+    and f+2 of an h x w stream in ``layout``, field f of parity ``q`` -> the progressive payload of field f, 1-D uint8 / uint16:
+    ``adaptive_plane_np`` of Y, Cb and Cr by their own shapes."""
+    y4m.check_depth(depth)
+    if len(payloads) != 5 or payloads[2] is None:
+        raise ValueError('adaptive_payload_np: five payloads (f-2 .. f+2), that of field f not None')
+    split = [None if p is None else y4m.split_planes_layout(_samples(p, depth), h, w, y4m.check_layout(layout)) for p in payloads]
+    return np.concatenate([adaptive_plane_np([None if s is None else s[i] for s in split], q).reshape(-1)
+                           for i in range(3) if split[2][i] is not None])
+
+
+def field_neighbours(f, n_fields):
+    """Fields f-2, f-1, f, f+1, f+2 of a stream of ``n_fields`` fields, None for one the stream does not have."""
+    return [g if 0 <= g < n_fields else None for g in range(f - 2, f + 3)]
+
+
+def adaptive_stream_np(payloads, h, w, depth, layout, order):
+    """The payloads of an interlaced stream of field order ``order`` -> the 2n progressive payloads of the adaptive mode: field
+    f = 2p + s from the payloads that hold fields f-2 .. f+2."""
+    n = 2 * len(payloads)
+    return [adaptive_payload_np([None if g is None else payloads[g // 2] for g in field_neighbours(f, n)], h, w, depth, layout,
+                                field_parity(order, f)) for f in range(n)]

@@ -214,13 +214,24 @@ class Y4mEdge:
     ``fields``: None, or the field order 't' / 'b' of an interlaced input (``demfi_amd.deint``): frame index f is then field f, its
     payload is uploaded as it is, and ONE ``demfi_yuv_bob`` launch per run of consecutive slots rebuilds the rows of the other field
     in place (upload stream) before anything reads yuv_in: the conversion, the scene SADs and the block counts see progressive
-    payloads."""
+    payloads.
+    ``deint_mode`` 'adaptive' (with ``fields``; 'bob' is the above): field f is rebuilt by ONE ``demfi_yuv_deint_adaptive`` launch per
+    batch (at most 64 fields each) that also reads the kept rows of fields f-2, f-1, f+1 and f+2 out of THEIR slots, so those
+    must have been uploaded (``around`` names them to the batch loop, which makes them resident: two fields of lookahead, and at
+    the start of a block the two fields before it) but need not have been rebuilt, nor stay raw: a launch reads only kept rows and
+    writes only missing ones (the hazard rule of csrc/deint.hip).  A field is rebuilt in the batch that first names it in a window
+    (or as the scene detector's predecessor frame); until then it is ``raw``, and the conversion, the scene SADs and the tile crops
+    are run for the fields just rebuilt, not for those just uploaded.  No payload is uploaded more often than by the bob: once per
+    field."""
 
-    def __init__(self, runner, batch, slots, cuts, full, tiler=None, depth=8, layout='420', dedup=None, h2d=None, fields=None):
+    def __init__(self, runner, batch, slots, cuts, full, tiler=None, depth=8, layout='420', dedup=None, h2d=None, fields=None,
+                 deint_mode='bob'):
         self.rn, self.slots, self.cuts, self.full, self.tiler = runner, slots, cuts, full, tiler
         if fields not in (None, 't', 'b'):
             raise ValueError("Y4mEdge: fields must be None, 't' or 'b', got %r" % (fields,))
-        self.fields = fields
+        if deint_mode not in I.MODES or (deint_mode != 'bob' and (fields is None or dedup is not None)):
+            raise ValueError('Y4mEdge: deint_mode %r with fields=%r, dedup=%r' % (deint_mode, fields, dedup))
+        self.fields, self.adaptive, self.raw = fields, deint_mode == 'adaptive', {}
         self.dedup, self.h2d, self.kept, self._pending = dedup, h2d, None, []
         self.depth, self.hi = depth, depth > 8
         self.layout = layout
@@ -250,6 +261,8 @@ class Y4mEdge:
         self.offs = [torch.empty(nout, dtype=torch.int64, device=dev) for _ in range(2)]
         self.yuv_out = [torch.empty((nout, Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.h_yuv = [torch.empty((nout, Pb), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        if self.adaptive:                            # five payload offsets per field rebuilt in a batch (at most nsl); reused in stream order
+            self.dei_offs = torch.empty(5 * nsl, dtype=torch.int64, device=dev)
         if cuts:                                     # SADs of a batch's new frames (at most nsl) against their predecessors
             self.d_sad = torch.empty(nsl, dtype=torch.int64, device=dev)
             self.sad_offs = torch.empty(2 * nsl, dtype=torch.int64, device=dev)
@@ -305,6 +318,7 @@ class Y4mEdge:
         """A run starts; returns the frames to make resident before its first batch.  Scene cuts: the block's first window
         k0 >= 1 also needs frame k0 - 1, the predecessor SAD_k0 is taken against."""
         self.yuv, self.window_index, self.det = yuv, window_index, None
+        self.raw = {}
         self.to_bgr, self.gather, self.sad = yuv_calls(self.rn.lib, self.depth, self.layout, self.fh, self.fw, yuv)
         if not self.cuts:
             return ()
@@ -330,10 +344,46 @@ class Y4mEdge:
                 L.check(self.rn.lib.demfi_yuv_bob(self.yuv_in[c0].data_ptr(), self.Pb, c, self.fh, self.fw, L.YUV_LAYOUT[self.layout], self.es,
                                                   sum(q[c0 + j] << j for j in range(c)), stream.cuda_stream), 'yuv_bob')
 
+    def around(self, needed, has):
+        """Adaptive mode: the fields a batch that names the fields ``needed`` must find uploaded besides them, in order: fields
+        f-2 .. f+2 of every field f of ``needed`` that is not rebuilt yet, as far as the input has them (``has``)."""
+        if not self.adaptive:
+            return []
+        self._needed, self._has = sorted(set(needed)), has
+        todo = [f for f in self._needed if f in self.raw or f not in self.slots.slot_of]
+        return sorted({g for f in todo for g in range(max(f - 2, 0), f + 3) if g not in needed and (g < f or has(g))})
+
+    def _adaptive(self, new, stream):
+        """The fields of this batch that are still raw become progressive frames in place; returns them as (field, slot) pairs."""
+        slot_of = self.slots.slot_of
+        self.raw.update(new)
+        self.raw = {f: sl for f, sl in self.raw.items() if slot_of.get(f) == sl}     # a slot the ring took back is forgotten
+        todo = [f for f in self._needed if f in self.raw]
+        done = 0
+        for c0 in range(0, len(todo), 64):
+            fs = todo[c0:c0 + 64]
+            for f in fs:                             # a field of the input that is not resident must not pass for an absent one
+                gone = [g for g in range(max(f - 2, 0), f + 3) if g not in slot_of and (g < f or self._has(g))]
+                if gone:
+                    raise RuntimeError('adaptive deinterlacing: field %d needs field %d, which is not resident' % (f, gone[0]))
+            offs = [slot_of[g] * self.Pb if g in slot_of else -1 for f in fs for g in range(f - 2, f + 3)]
+            host = torch.tensor(offs, dtype=torch.int64).pin_memory()
+            od = self.dei_offs[5 * done:5 * (done + len(fs))]
+            od.copy_(host, non_blocking=True)
+            L.check(self.rn.lib.demfi_yuv_deint_adaptive(self.yuv_in.data_ptr(), self.yuv_in.numel(), host.data_ptr(), od.data_ptr(), len(fs),
+                                                         self.fh, self.fw, L.YUV_LAYOUT[self.layout], self.es,
+                                                         sum(I.field_parity(self.fields, f) << j for j, f in enumerate(fs)),
+                                                         stream.cuda_stream), 'yuv_deint_adaptive')
+            done += len(fs)
+        return [(f, self.raw.pop(f)) for f in todo]
+
     def uploaded(self, new, h2d):
-        """Payloads copied to yuv_in[slot] (interlaced input: bobbed there first) -> BGR frame slots, one launch per run of
-        consecutive slots; then the SADs."""
-        self._bob(new, h2d)                          # the frames staged by --dedup were bobbed when they were staged
+        """Payloads copied to yuv_in[slot] (interlaced input: bobbed there first, or in adaptive mode the batch's fields rebuilt
+        there, which then take the place of ``new``) -> BGR frame slots, one launch per run of consecutive slots; then the SADs."""
+        if self.adaptive:
+            new = self._adaptive(new, h2d)
+        else:
+            self._bob(new, h2d)                      # the frames staged by --dedup were bobbed when they were staged
         if self._pending:                            # --dedup: the kept frames staged since the last batch
             new, self._pending = self._pending + list(new), []
         sls = [sl for _, sl in new]
@@ -348,7 +398,10 @@ class Y4mEdge:
         """SAD_j of every frame j just uploaded against frame j-1 (``demfi_yuv420_sad``, ONE launch on the h2d stream after the
         copies), read back with one event wait and handed to the detector in frame order.  Call under the h2d stream.
         Frame j-1 is resident: it was uploaded in this batch or in the previous one (windows are consecutive), and a slot is
-        reused only after all nslot >= 2 * batch + 8 slots have been.  The wait does not wait on the compute stream: the
+        reused only after all nslot >= 2 * batch + 8 slots have been (adaptive deinterlacing: nslot >= 2 * batch + 12, and batch b
+        uploads up to frame k + 2 * batch + 4, its two fields of lookahead included, so it takes back the slots of frames up to
+        k - 8 at most, while batch b-1 reads frames from k - 1 on and its rebuild launches, queued on h2d before, from k - 3 on).
+        The wait does not wait on the compute stream: the
         ``busy`` waits queued on h2d before this batch's copies are on the compute of the batch that last read a reused
         slot, and that batch is at least two back (batch b-1 reads frames k .. k + batch + 2 of its first window k, batch b
         uploads frames up to k + 2 * batch + 2 only), so the host already waited for it when it drained that batch's D2H."""
@@ -511,9 +564,10 @@ def max_runs(r, cuts, dedup):
     return max(2 if cuts else 1, K.max_window_runs(r, dedup[3]) if dedup is not None else 1)
 
 
-def pipeline_key(batch, y4m, cuts, full, depth=8, layout='420', dedup=None, fields=None):
+def pipeline_key(batch, y4m, cuts, full, depth=8, layout='420', dedup=None, fields=None, deint_mode='bob'):
     """What a cached ``ClipPipeline`` can be reused for."""
-    return (batch, y4m, cuts, full, depth, layout) + ((tuple(dedup),) if dedup is not None else ()) + (('fields', fields) if fields else ())
+    return ((batch, y4m, cuts, full, depth, layout) + ((tuple(dedup),) if dedup is not None else ()) + (('fields', fields) if fields else ())
+            + (('deint', deint_mode) if fields and deint_mode != 'bob' else ()))
 
 
 class KeptFrames:
@@ -589,10 +643,10 @@ class ClipPipeline:
     cuts / the full-length timeline, which size its buffers): H2D of a batch's new frames, its compute, the drain of the
     previous batch and its D2H, on three streams over two sets of output buffers."""
 
-    def __init__(self, runner, batch, y4m, cuts, full, depth=8, layout='420', dedup=None, fields=None):
+    def __init__(self, runner, batch, y4m, cuts, full, depth=8, layout='420', dedup=None, fields=None, deint_mode='bob'):
         dev = self.dev = runner.engine.device
         runner = weakref.proxy(runner)               # the runner owns this pipeline: no reference cycle keeps its buffers alive
-        self.batch, self.key = batch, pipeline_key(batch, y4m, cuts, full, depth, layout, dedup, fields)
+        self.batch, self.key = batch, pipeline_key(batch, y4m, cuts, full, depth, layout, dedup, fields, deint_mode)
         if depth > 8 and not y4m:
             raise ValueError('ClipPipeline: 16-bit frames are those of the Y4M edge only')
         if dedup is not None and not y4m:
@@ -602,7 +656,8 @@ class ClipPipeline:
         self.h2d, self.d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
         plan = runner.tiles
         fh, fw = (plan.h, plan.w) if plan is not None else (runner.h, runner.w)
-        self.slots = FrameSlots(max(2 * batch + 8, 8 * batch), fh, fw, dev, torch.int16 if depth > 8 else torch.uint8)
+        look = 4 if fields is not None and deint_mode == 'adaptive' else 0      # two fields behind a batch's frames and two ahead
+        self.slots = FrameSlots(max(2 * batch + 8 + look, 8 * batch), fh, fw, dev, torch.int16 if depth > 8 else torch.uint8)
         tiler = None
         if plan is not None and depth > 8:           # 16-bit frames: tiles are read and written inside the full frames
             tiler = TileGrid(plan)
@@ -610,7 +665,7 @@ class ClipPipeline:
             J2 = (R.max_instants(runner.retime if runner.retime is not None else Fraction(runner.mfi)) + 2) if y4m else runner.mfi + 1
             rr = (runner.retime if runner.retime is not None else Fraction(runner.mfi)) if y4m else None
             tiler = Tiler(plan, self.slots, runner.lib, dev, batch * (max_runs(rr, cuts, dedup) if y4m else 1) * J2)
-        self.edge = (Y4mEdge(runner, batch, self.slots, cuts, full, tiler, depth, layout, dedup, self.h2d, fields) if y4m
+        self.edge = (Y4mEdge(runner, batch, self.slots, cuts, full, tiler, depth, layout, dedup, self.h2d, fields, deint_mode) if y4m
                      else BgrEdge(runner, batch, self.slots, tiler))
 
     def run(self, host_frames, windows, sink, reuse_frames, yuv, window_index):
@@ -623,6 +678,10 @@ class ClipPipeline:
         if not wins:
             return 0
         extra = edge.begin(yuv, window_index, wins[0])
+        around = edge.around if getattr(edge, 'adaptive', False) else None
+        if around is not None and not reuse_frames:
+            raise ValueError('ClipPipeline: adaptive deinterlacing needs reuse_frames (slots are keyed by field)')
+        has = getattr(host_frames, 'has', lambda i: 0 <= i < len(host_frames))
         ev_d2h = [None, None]             # D2H of the batch that last wrote output buffer i
         pending = None                    # (buffer, first window, what edge.run returned) of the batch whose D2H is in flight
         n = b = 0
@@ -638,9 +697,19 @@ class ClipPipeline:
                     new.append((idx, sl))
                 return sl
             with torch.cuda.stream(h2d):
+                if around is not None:    # raw fields next to this batch's in time: those before them first (frames are read in order)
+                    named = set(extra).union(*wins)
+                    near = around(named, has)
+                    for idx in near:
+                        if idx < min(named):
+                            resident(idx, idx)
                 for idx in extra:
                     resident(idx, idx)
                 frames = [[resident(idx, idx if reuse_frames else (b, wi, idx)) for idx in win] for wi, win in enumerate(wins)]
+                if around is not None:
+                    for idx in near:
+                        if idx > min(named):
+                            resident(idx, idx)
                 edge.uploaded(new, h2d)
                 ev_up = torch.cuda.Event()
                 ev_up.record(h2d)

@@ -640,11 +640,16 @@ class WindowRunner:
         ``yuv.fields`` = 't' / 'b' (None when absent): the input is interlaced with that field order (``demfi_amd.deint``).
         host_frames[f] is then the payload that holds FIELD f (``y4m.Frames(fields=2)``); every uploaded payload is bobbed in place
         on the GPU (``demfi_yuv_bob``) before it is converted or scored, and everything else runs as on the progressive stream of
-        those frames.
+        those frames.  ``yuv.deint_mode`` = 'adaptive' ('bob' when absent): every field is rebuilt by the motion-adaptive rule instead
+        (``demfi_yuv_deint_adaptive``), which reads fields f-2 .. f+2: host_frames must then also hold the two fields before the first
+        one named and answer ``has(f)`` for the fields after the last (``y4m.Frames(behind=2)``); not together with ``yuv.dedup``.
         Returns the number of windows run."""
         cuts, full = getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False))
         depth, layout = int(getattr(yuv, 'depth', 8)), getattr(yuv, 'layout', '420')
         dedup, fields = getattr(yuv, 'dedup', None), getattr(yuv, 'fields', None)
+        mode = getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob'
+        if mode != 'bob' and (dedup is not None or not reuse_frames):
+            raise ValueError('WindowRunner.run_clip_u8: deint_mode %r needs reuse_frames and does not go with repeated frames' % (mode,))
         if dedup is not None and (self.retime is None or window_index is None or not reuse_frames):
             raise ValueError('WindowRunner.run_clip_u8: repeated frames need a retimed runner (r = M for x M), window_index and reuse_frames')
         if self.retime is not None and yuv is None:
@@ -653,9 +658,9 @@ class WindowRunner:
             raise ValueError('WindowRunner.run_clip_u8: scene cuts need a retimed runner (r = M for x M) and reuse_frames')
         if full and (self.retime is None or window_index is None):
             raise ValueError('WindowRunner.run_clip_u8: the full-length timeline needs a retimed runner and window_index')
-        if self._pipeline is None or self._pipeline.key != pipeline_key(batch, yuv is not None, cuts, full, depth, layout, dedup, fields):
+        if self._pipeline is None or self._pipeline.key != pipeline_key(batch, yuv is not None, cuts, full, depth, layout, dedup, fields, mode):
             self._pipeline = None                        # release the old buffers before the new ones are allocated
-            self._pipeline = ClipPipeline(self, batch, yuv is not None, cuts, full, depth, layout, dedup, fields)
+            self._pipeline = ClipPipeline(self, batch, yuv is not None, cuts, full, depth, layout, dedup, fields, mode)
         return self._pipeline.run(host_frames, windows, sink, reuse_frames, yuv, window_index)
 
     def __del__(self):

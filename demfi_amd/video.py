@@ -43,9 +43,19 @@ order, each at its own time instant, so n payloads at F are a progressive stream
 ``--mfi 2``).  The payload is uploaded as it is and one launch rebuilds the other field's rows in place by an edge-directed line
 average (csrc/deint.hip, defined by ``deint.bob_plane_np``) before it is converted; everything behind that -- rates, scene cuts,
 repeated frames, the full-length timeline, tiles, depths, layouts, rank sharding -- runs on the progressive stream unchanged.
-``--fps`` and ``--mfi`` count from the field rate 2F.  The output is always progressive.  Not offered: motion-adaptive or
-temporal deinterlacing, inverse telecine, mixed-mode streams (``Im``) and interlaced output; the quarter-row chroma offset of
-interlaced 4:2:0 fields is not modelled; a payload is uploaded once per field.
+``--fps`` and ``--mfi`` count from the field rate 2F.  The output is always progressive.  Not offered: inverse telecine,
+mixed-mode streams (``Im``) and interlaced output; the quarter-row chroma offset of interlaced 4:2:0 fields is not modelled; a
+payload is uploaded once per field.
+
+``--deinterlace-mode adaptive`` (with ``--deinterlace``; the default ``bob`` is the above) rebuilds the missing rows motion-adaptively
+instead: the bob's value is clamped to an interval around the average of the fields before and after, whose width is yadif's
+temporal difference over fields f-2 .. f+2 with its spatial check (csrc/deint.hip ``demfi_yuv_deint_adaptive``, defined by
+``deint.adaptive_plane_np``).  Static parts of the picture keep their full vertical resolution and stop flickering at the field
+rate, so the network is not shown motion that is not there; moving parts and scene cuts fall back to the bob's value.  Field f
+is rebuilt once fields f+1 and f+2 are uploaded (two fields of lookahead; a rank's block also reads the two fields before it and
+after it), in place and without uploading any payload more often; an output field depends on payloads p-1, p and p+1 of the
+input only, whatever the batch size and the rank count.  Works with every switch above except ``--dedup``, which stages and
+discards fields one at a time: the two together are refused, ``--deinterlace-mode bob`` is the way out.
 """
 import os
 import sys
@@ -72,12 +82,12 @@ class YuvEdge:
     ``depth``: bits per sample, 8, or 10 / 12 / 14 / 16 for payloads of 16-bit samples.  ``layout``: the payloads' chroma
     layout, one of ``y4m.LAYOUTS`` (``siting`` only matters to '420').  ``dedup``: None, or (hi, lo, frac, max_hold) of
     repeated-frame detection (``demfi_amd.cadence``).  ``fields``: None, or the field order 't' / 'b' of an interlaced input whose
-    fields are the stream's frames (``demfi_amd.deint``)."""
+    fields are the stream's frames (``demfi_amd.deint``), rebuilt by ``deint_mode`` 'bob' or 'adaptive'."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
-                 fields=None):
+                 fields=None, deint_mode='bob'):
         self.dedup = dedup
-        self.fields = fields
+        self.fields, self.deint_mode = fields, deint_mode
         self.depth = y4m.check_depth(depth)
         self.layout = y4m.check_layout(layout)
         self.matrix = {'bt601': L.BT601, 'bt709': L.BT709}[matrix]
@@ -86,6 +96,17 @@ class YuvEdge:
         self.with_s1 = with_s1
         self.scene_cut = scene_cut
         self.full_length = full_length
+
+
+def check_deinterlace_mode(deinterlace, mode, dedup):
+    """The rules of ``--deinterlace-mode``: 'bob' or 'adaptive'; 'adaptive' only with ``--deinterlace`` and not with ``--dedup``."""
+    if mode not in I.MODES:
+        raise ValueError('deinterlace_mode must be one of %s, got %r' % (', '.join(I.MODES), mode))
+    if mode != 'bob' and not deinterlace:
+        raise ValueError('--deinterlace-mode %s needs --deinterlace (deinterlace=True): the mode says how fields are rebuilt' % mode)
+    if mode != 'bob' and dedup not in (None, False):
+        raise ValueError('--deinterlace-mode %s does not go with --dedup: repeated frames are staged and discarded one field at a time, '
+                         'the %s mode needs two fields of lookahead; use --deinterlace-mode bob with --dedup' % (mode, mode))
 
 
 class VideoRunner:
@@ -115,11 +136,14 @@ class VideoRunner:
     progressive frame f, so the input counts as 2n frames at twice its rate -- ``mfi`` multiplies and ``fps`` is checked against
     that field rate, and windows, ranks and output counts follow it; the output is progressive.  ``last_fields`` is None, 'tff'
     or 'bff'.  Off by default (an interlaced stream is refused before anything is allocated); a progressive stream gives the same
-    bytes either way."""
+    bytes either way.  ``deinterlace_mode``: 'bob' (default) or 'adaptive', the motion-adaptive rule of ``demfi_amd.deint`` over fields
+    f-2 .. f+2; only with ``deinterlace``, and not with ``dedup`` (both are refused here, before anything is allocated)."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
-                 tile_high_depth=False, deinterlace=False, **runner_kw):
+                 tile_high_depth=False, deinterlace=False, deinterlace_mode='bob', **runner_kw):
+        check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.deinterlace_mode = deinterlace_mode
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
         if mfi is not None and fps is not None:
@@ -187,6 +211,10 @@ class VideoRunner:
                              % (self.fps, phdr.fps, hdr.fps, phdr.fps))
         return phdr, order, 2
 
+    def _behind(self, order):
+        """``y4m.Frames(behind=...)``: the adaptive mode reads two fields before and after every field it rebuilds."""
+        return 2 if order is not None and self.deinterlace_mode == 'adaptive' else 0
+
     def _check_depth(self, hdr):
         """Before anything is allocated for this input: a stream above 8 bits runs as tiles only with ``tile_high_depth``."""
         if hdr.depth > 8 and self.tile is not None and not self.tile_high_depth:
@@ -222,7 +250,7 @@ class VideoRunner:
 
     def _edge(self, hdr, with_s1, order=None):
         return YuvEdge(y4m.auto_matrix(hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
-                       self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup, order)
+                       self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup, order, self.deinterlace_mode)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
@@ -243,7 +271,7 @@ class VideoRunner:
         self._check_depth(hdr)
         cr = self._clip_runner(hdr, 1, 0)
         wr = y4m.Writer(dst, self._out_header(hdr))
-        frames = y4m.Frames(rd, full_length=self.full_length, fields=per)
+        frames = y4m.Frames(rd, full_length=self.full_length, fields=per, behind=self._behind(order))
         self.last_dups = []
 
         def sink(k, payloads):
@@ -301,7 +329,7 @@ class VideoRunner:
             last = R.first_window(n_in, full) + R.n_windows(n_in, full) - 1
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
             first = S.first_frame(lo) if self.scene_cut is not None else max(lo, 0)
-            frames = y4m.Frames.from_file(f, offs, first, lo + len(wins) + 3, hdr.payload, fields=per)
+            frames = y4m.Frames.from_file(f, offs, first, lo + len(wins) + 3, hdr.payload, fields=per, behind=self._behind(order))
             at = R.block_offset(len(hb), lo, self._ratio(hdr), hdr.payload, full)
             kw = {'window_index': lambda j: lo + j} if full else {}
             with open(out_path, 'r+b') as o:
@@ -392,6 +420,11 @@ def parser():
                          'by an edge-directed line average), so n payloads at F count as 2n frames at 2F: --mfi M gives 2*M*F, --fps '
                          'must be at least 2F, and 50i --mfi 2 is 100p.  The output is progressive.  Mixed-mode streams (Im) stay '
                          'refused.  Off by default (progressive input only); changes nothing for a progressive stream')
+    ap.add_argument('--deinterlace-mode', default='bob', choices=list(I.MODES),
+                    help='with --deinterlace: bob (default) rebuilds the other field\'s rows from the field alone; adaptive also looks at '
+                         'the two fields before and the two after (yadif\'s temporal rule around the bob\'s value): static parts keep '
+                         'their full vertical resolution and do not flicker, moving parts and scene cuts get the bob\'s value.  Costs '
+                         'two fields of lookahead.  An error without --deinterlace, and with --dedup (use bob there)')
     ap.add_argument('--dedup-max-hold', type=int, default=K.DEFAULT_MAX_HOLD, metavar='N',
                     help='with --dedup: after N repeats in a row the next frame is kept whatever it shows (default %d), so a still '
                          'scene stays a sequence of frames N + 1 apart' % K.DEFAULT_MAX_HOLD)
@@ -409,6 +442,10 @@ def main(argv=None):
     a = parser().parse_args(argv)
     if a.fps is None and a.mfi is None:
         a.mfi = 8
+    try:
+        check_deinterlace_mode(a.deinterlace, a.deinterlace_mode, a.dedup or None)
+    except ValueError as e:
+        parser().error(str(e))
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     if world > 1 and a.dedup:
         raise SystemExit('demfi_amd.video: --dedup runs on one rank (which frames are kept depends on the whole prefix of the input)')
@@ -434,7 +471,8 @@ def main(argv=None):
     D.broadcast_state_dict(model, world, device=dev)
     vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut, full_length=a.full_length,
                      tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth, layouts=a.any_layout, dedup=a.dedup or None,
-                     dedup_max_hold=a.dedup_max_hold, tile_high_depth=a.tile_high_depth, deinterlace=a.deinterlace)
+                     dedup_max_hold=a.dedup_max_hold, tile_high_depth=a.tile_high_depth, deinterlace=a.deinterlace,
+                     deinterlace_mode=a.deinterlace_mode)
     t0 = time.perf_counter()
     if world > 1:
         nw, nf = vr.run_file(a.input, a.output, world, rank)

@@ -584,19 +584,27 @@ class Frames:
     the input's length.
 
     Frames(reader): the frames of a stream, read in order (stdin: nothing is seeked).
-    Frames.from_file(f, offsets, first, stop): frames first .. stop-1 of a scanned file (``scan``), by seek + readinto.
+    Frames.from_file(f, offsets, first, stop): frames first .. stop-1 of a scanned file (``scan``), by seek + readinto (with
+    ``behind`` = b: frames first-b .. stop+b-1, as far as the file has them).
     ``full_length``: ``windows`` / ``is_last`` follow the full-length timeline (``retime``).
     ``fields`` = 2 (an interlaced input, ``demfi_amd.deint``): index i is FIELD i, and both fields of payload i // 2 are the
     same tensor: the payload is read once and never copied.  ``first`` / ``stop``, ``n``, ``is_last``, ``windows`` and the
-    dropping count fields; ``peak`` counts the payload tensors held."""
+    dropping count fields; ``peak`` counts the payload tensors held.
+    ``behind`` = b (default 0: nothing changes): for a consumer that also reads the b frames before every frame it names and the
+    frames after it (the motion-adaptive deinterlacer, b = 2 fields): the input starts b frames earlier (at frame 0 at the
+    earliest) and b more frames are kept behind, so ``peak`` grows by at most the payloads those b frames and the b frames read
+    ahead by ``has`` add."""
 
-    def __init__(self, reader=None, payload=None, fetch=None, first=0, stop=None, pinned=None, full_length=False, fields=1):
+    def __init__(self, reader=None, payload=None, fetch=None, first=0, stop=None, pinned=None, full_length=False, fields=1, behind=0):
         import torch
         if fields not in (1, 2):
             raise ValueError('Frames: fields must be 1 or 2, got %r' % (fields,))
         self.payload = reader.header.payload if reader is not None else payload
         self._fetch = fetch or (lambda i, buf: reader.read_into(buf))
-        self.fields = fields
+        if int(behind) != behind or behind < 0:
+            raise ValueError('Frames: behind must be an integer >= 0, got %r' % (behind,))
+        self.fields, self.behind = fields, int(behind)
+        first = max(first - self.behind, 0)
         self.next, self.stop = first - first % fields, stop
         self.pinned = torch.cuda.is_available() if pinned is None else pinned
         self.full_length = full_length
@@ -606,14 +614,15 @@ class Frames:
         self.peak = 0
 
     @classmethod
-    def from_file(cls, f, offsets, first, stop, payload, pinned=None, fields=1):
+    def from_file(cls, f, offsets, first, stop, payload, pinned=None, fields=1, behind=0):
         def fetch(i, buf):
             f.seek(offsets[i])
             mv = memoryview(buf).cast('B')
             if _readinto_full(f, mv) != len(mv):
                 raise Y4MError('Y4M: truncated frame %d' % i)
             return True
-        return cls(payload=payload, fetch=fetch, first=first, stop=min(stop, fields * len(offsets)), pinned=pinned, fields=fields)
+        return cls(payload=payload, fetch=fetch, first=first, stop=min(stop + behind, fields * len(offsets)), pinned=pinned,
+                   fields=fields, behind=behind)
 
     def has(self, i):
         """Reads through frame i; False when the input ends before it."""
@@ -634,7 +643,7 @@ class Frames:
     def __getitem__(self, i):
         if not self.has(i):
             raise IndexError('Y4M frame %d: the input has %d frames' % (i, self.n))
-        for j in [j for j in self.buf if j < i - 3]:
+        for j in [j for j in self.buf if j < i - 3 - self.behind]:
             del self.buf[j]
         if i not in self.buf:
             raise IndexError('Y4M frame %d was already dropped (frames are read in window order)' % i)

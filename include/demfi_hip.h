@@ -447,6 +447,19 @@ int demfi_luma_block_counts(const uint8_t* base, const int64_t* a_offsets, const
  * all payloads; n = 0 does nothing. */
 int demfi_yuv_bob(void* payloads, int64_t stride_bytes, int n, int h, int w, int layout, int sample_bytes, uint64_t odd_mask,
                   void* stream);
+/* yuv_deint_adaptive: the motion-adaptive mode (--deinterlace-mode adaptive; demfi_amd/deint.py adaptive_plane_np, matched sample
+ * for sample).  Field i (n = 0..64 per launch) has five int64 BYTE offsets from base, offsets[5i .. 5i+4]: the payloads that hold
+ * fields f-2, f-1, f, f+1, f+2 of the stream, -1 for a field the stream does not have (even offsets for 16-bit samples).  The
+ * payload of f, whose rows of parity q_i = bit i of odd_mask are kept, becomes a progressive frame IN PLACE: a missing row with
+ * both neighbours is the bob's value clamped to [d - diff, d + diff] (yadif's temporal rule with the spatial check), every other row
+ * as in yuv_bob.  Of the payloads of f-1 and f+1 only rows of parity 1 - q_i are read, of those of f-2 and f+2 only rows of parity
+ * q_i, i.e. kept rows of the fields they belong to: such a payload may be raw, already rebuilt, or rebuilt by the same launch.  The
+ * offsets are passed twice with the same content: offsets in HOST memory, checked here before anything is launched (every present
+ * payload inside base .. base + size_bytes, the payload of f present, f-1 or f+1 present, no payload rebuilt twice), and
+ * offsets_dev in DEVICE memory, read by the kernel, which leaves a field without its own payload alone and gives one without f-1
+ * and f+1 the bob's value.  One launch for all planes of all n fields; n = 0 does nothing. */
+int demfi_yuv_deint_adaptive(void* base, int64_t size_bytes, const int64_t* offsets, const int64_t* offsets_dev, int n, int h, int w,
+                             int layout, int sample_bytes, uint64_t odd_mask, void* stream);
 
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
