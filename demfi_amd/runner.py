@@ -24,7 +24,7 @@ import torch
 from . import _lib as L
 from . import retime as R
 from .harness import t_schedule
-from .pipeline import ClipPipeline, fill_sink_records, pipeline_key
+from .pipeline import ClipPipeline, EdgeSpec, fill_sink_records
 
 U16_DTYPES = tuple(d for d in (torch.int16, getattr(torch, 'uint16', None)) if d is not None)   # plain storage of 16-bit frames
 
@@ -147,6 +147,7 @@ class WindowRunner:
         self.engine = model.engine(H, W, n_tst, n_ctx=self.n_ctx, n_trunk=self.n_trunk, exact_ctx=self.tb)
         self._weights_version = model._weights_version
         self.n_tst, self.mfi = n_tst, mfi
+        self.ratio = self.retime if self.retime is not None else Fraction(mfi)     # r of the Y4M edge of run_clip_u8: x M is r = M
         dev = self.engine.device
         self.stream = torch.cuda.Stream(dev)                                   # trunk stream
         self.t_streams = [torch.cuda.Stream(dev) for _ in range(self.n_ctx)]   # one per per-t context
@@ -344,6 +345,23 @@ class WindowRunner:
             cur.wait_stream(s)
         self.engine.use_ctx(0, trunk=0)
 
+    def _emitter(self, put, out, s01, s0_at=0, s1_at=0, frames=None):
+        """emit(j, ctx, sh) of ``_window``: put(frame, dst, sh) writes St of instant j to out[j] and S0 / S1 of instants s0_at / s1_at to
+        s01[0] / s01[1].  frames(ctx): the per-t context's [S0, S1, St]; default: those of the last recursion."""
+        last = self.n_tst - 1
+
+        def emit(j, ctx, sh):
+            fin = ctx['finals'][last] if frames is None else frames(ctx)
+            put(fin[2], out[j], sh)
+            if j == s0_at:
+                put(fin[0], s01[0], sh)
+            if j == s1_at:
+                put(fin[1], s01[1], sh)
+        return emit
+
+    def _crop(self, frame, dst, sh):                 # ``put`` of the fp32 entry points: the padded [3,H,W] frame without its padding
+        dst.copy_(frame[:, :self.h, :self.w], non_blocking=True)
+
     def _loader(self, x):
         if tuple(x.shape) != (1, 3, 4, self.h, self.w):
             raise ValueError('expected a [1,3,4,%d,%d] window, got %s' % (self.h, self.w, tuple(x.shape)))
@@ -369,20 +387,10 @@ class WindowRunner:
             self.out_d1 = torch.zeros_like(self.out)
             self.s01_d1 = torch.zeros_like(self.s01)
 
-        def emit(j, ctx, sh):
-            fin = ctx['finals'][self.n_tst - 1]
-            self.out[j].copy_(fin[2, :, :self.h, :self.w], non_blocking=True)
-            if j == s0_at:
-                self.s01[0].copy_(fin[0, :, :self.h, :self.w], non_blocking=True)
-            if j == s1_at:
-                self.s01[1].copy_(fin[1, :, :self.h, :self.w], non_blocking=True)
-            if with_d1:
-                d1 = ctx['sharp1']                   # [9,H,W]: S0', S1', St'
-                self.out_d1[j].copy_(d1[6:9, :self.h, :self.w], non_blocking=True)
-                if j == s0_at:
-                    self.s01_d1[0].copy_(d1[0:3, :self.h, :self.w], non_blocking=True)
-                if j == s1_at:
-                    self.s01_d1[1].copy_(d1[3:6, :self.h, :self.w], non_blocking=True)
+        emit = self._emitter(self._crop, self.out, self.s01, s0_at, s1_at)
+        if with_d1:                                  # then Stage I's frames, sharp1 [9,H,W]: S0', S1', St'
+            both = emit, self._emitter(self._crop, self.out_d1, self.s01_d1, s0_at, s1_at, lambda ctx: ctx['sharp1'].unflatten(0, (3, 3)))
+            emit = lambda j, ctx, sh: [e(j, ctx, sh) for e in both]   # noqa: E731
         self._window(load, emit)
         self._end(cur)
         if with_d1:
@@ -401,13 +409,7 @@ class WindowRunner:
         loads = [self._loader(x) for x in xs]
         cur = self._begin()
         for w in range(n):
-            def emit(j, ctx, sh, w=w):
-                fin = ctx['finals'][self.n_tst - 1]
-                out[w, j].copy_(fin[2, :, :self.h, :self.w], non_blocking=True)
-                if j == 0:
-                    s01[w, 0].copy_(fin[0, :, :self.h, :self.w], non_blocking=True)
-                    s01[w, 1].copy_(fin[1, :, :self.h, :self.w], non_blocking=True)
-            self._window(loads[w], emit)
+            self._window(loads[w], self._emitter(self._crop, out[w], s01[w]))
         self._end(cur)
         return out, s01
 
@@ -448,14 +450,9 @@ class WindowRunner:
                 ctx['sink'][:32].copy_(sink_rows[j], non_blocking=True)
             return load, (lambda j, ctx, sh: None), pre
 
-        def emit(j, ctx, sh):
-            fin = ctx['finals'][self.n_tst - 1]
-            L.check(self.lib.demfi_frame_to_u8(fin[2].data_ptr(), out_u8[j].data_ptr(), self.h, self.w, e.H, e.W, sh), 'to_u8')
-            if j == 0:
-                for i in range(2):
-                    L.check(self.lib.demfi_frame_to_u8(fin[i].data_ptr(), s01_u8[i].data_ptr(), self.h, self.w, e.H, e.W, sh),
-                            'to_u8')
-        return load, emit, None
+        def put(frame, dst, sh):
+            L.check(self.lib.demfi_frame_to_u8(frame.data_ptr(), dst.data_ptr(), self.h, self.w, e.H, e.W, sh), 'to_u8')
+        return load, self._emitter(put, out_u8, s01_u8), None
 
     def run_window_u8(self, frames_u8):
         """uint8 in / uint8 out: frames_u8 = 4 BGR uint8 [h,w,3] GPU tensors in the order (B0,B1,B-1,B2).  Returns
@@ -491,16 +488,17 @@ class WindowRunner:
         return out, s01
 
     # ---- 16-bit frames (bit depth 10 .. 16 of the Y4M edge; 8 to compare with the uint8 path) -------------------------------
-    def _check_u16_frames(self, frames_u16, depth):
+    def _check_u16_frames(self, frames_u16, depth, shape, also=()):
+        # the 4 frames a 16-bit window reads, and the frames ``also`` it writes: device tensors of ``shape`` in 16-bit storage
         if depth not in (8, 10, 12, 14, 16):
             raise ValueError('bit depth must be 8, 10, 12, 14 or 16, got %r' % (depth,))
         if len(frames_u16) != 4:
             raise ValueError('expected 4 16-bit frames (B0,B1,B-1,B2), got %d' % len(frames_u16))
-        for f in frames_u16:
+        for f in list(frames_u16) + list(also):
             self._check_device(f, '16-bit frame')
-            if f.dtype not in U16_DTYPES or tuple(f.shape) != (self.h, self.w, 3) or not f.is_contiguous():
+            if f.dtype not in U16_DTYPES or tuple(f.shape) != shape or not f.is_contiguous():
                 raise ValueError('16-bit frames must be contiguous [%d,%d,3] int16 / uint16 tensors (the bits of uint16 values), got %s %s' %
-                                 (self.h, self.w, f.dtype, tuple(f.shape)))
+                                 (shape[0], shape[1], f.dtype, tuple(f.shape)))
 
     def _u16_io(self, frames_u16, out_u16, s01_u16, depth):
         """(load, emit, pre) of one 16-bit window, the counterpart of ``_u8_io``: 4 BGR [h,w,3] GPU frames of 16-bit storage
@@ -508,20 +506,15 @@ class WindowRunner:
         out_u16 [J,h,w,3], s01_u16 [2,h,w,3] of the same storage.  Ingest: ONE kernel (``demfi_u16_ingest``).  Egress: always
         the emit path, one ``demfi_frame_to_u16`` per frame (the fused sink of the fp16 engine writes uint8 only)."""
         e = self.engine
-        self._check_u16_frames(frames_u16, depth)
+        self._check_u16_frames(frames_u16, depth, (self.h, self.w, 3))
         ptrs = (C.c_void_p * 4)(*[f.data_ptr() for f in frames_u16])
 
         def load(eng, h):
             eng.ingest_u16(ptrs, self.h, self.w, depth, h)
 
-        def emit(j, ctx, sh):
-            fin = ctx['finals'][self.n_tst - 1]
-            L.check(self.lib.demfi_frame_to_u16(fin[2].data_ptr(), out_u16[j].data_ptr(), self.h, self.w, e.H, e.W, depth, sh), 'to_u16')
-            if j == 0:
-                for i in range(2):
-                    L.check(self.lib.demfi_frame_to_u16(fin[i].data_ptr(), s01_u16[i].data_ptr(), self.h, self.w, e.H, e.W, depth, sh),
-                            'to_u16')
-        return load, emit, None                      # no pre: _window then disables every uint8 sink record
+        def put(frame, dst, sh):
+            L.check(self.lib.demfi_frame_to_u16(frame.data_ptr(), dst.data_ptr(), self.h, self.w, e.H, e.W, depth, sh), 'to_u16')
+        return load, self._emitter(put, out_u16, s01_u16), None      # no pre: _window then disables every uint8 sink record
 
     def _u16_tile_io(self, slots4, tile, out_full, s01_full, depth):
         """(load, emit, pre) of one (run, tile) pair of a runner of ``tiles``, the counterpart of ``_u16_io``: ``slots4`` are 4 BGR
@@ -532,16 +525,8 @@ class WindowRunner:
         e, plan = self.engine, self.tiles
         if plan is None or tile not in plan.tiles:
             raise ValueError('_u16_tile_io: a runner of tiles and one tile of its plan')
-        if depth not in (8, 10, 12, 14, 16):
-            raise ValueError('bit depth must be 8, 10, 12, 14 or 16, got %r' % (depth,))
         fh, fw = plan.h, plan.w
-        if len(slots4) != 4:
-            raise ValueError('expected 4 16-bit frames (B0,B1,B-1,B2), got %d' % len(slots4))
-        for f in list(slots4) + list(out_full) + list(s01_full):
-            self._check_device(f, '16-bit frame')
-            if f.dtype not in U16_DTYPES or tuple(f.shape) != (fh, fw, 3) or not f.is_contiguous():
-                raise ValueError('16-bit frames of a tiled run must be contiguous [%d,%d,3] int16 / uint16 tensors, got %s %s' %
-                                 (fh, fw, f.dtype, tuple(f.shape)))
+        self._check_u16_frames(slots4, depth, (fh, fw, 3), also=list(out_full) + list(s01_full))
         ptrs = (C.c_void_p * 4)(*[f.data_ptr() for f in slots4])
         (y0, x0, _, _), k = tile.src, tile.keep
 
@@ -552,13 +537,7 @@ class WindowRunner:
             L.check(self.lib.demfi_frame_to_u16_rect(frame.data_ptr(), dst.data_ptr(), fh, fw, y0, x0, k.y0, k.x0, k.y1, k.x1, e.H, e.W,
                                                      depth, sh), 'to_u16_rect')
 
-        def emit(j, ctx, sh):
-            fin = ctx['finals'][self.n_tst - 1]
-            put(fin[2], out_full[j], sh)
-            if j == 0:
-                for i in range(2):
-                    put(fin[i], s01_full[i], sh)
-        return load, emit, None
+        return load, self._emitter(put, out_full, s01_full), None
 
     def run_windows_u16(self, windows_u16, depth, out=None, s01=None, ts=None):
         """``run_windows_u8`` for 16-bit frames at bit depth ``depth`` (list of 4-tuples of BGR [h,w,3] ``torch.int16`` GPU
@@ -644,23 +623,11 @@ class WindowRunner:
         (``demfi_yuv_deint_adaptive``), which reads fields f-2 .. f+2: host_frames must then also hold the two fields before the first
         one named and answer ``has(f)`` for the fields after the last (``y4m.Frames(behind=2)``); not together with ``yuv.dedup``.
         Returns the number of windows run."""
-        cuts, full = getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False))
-        depth, layout = int(getattr(yuv, 'depth', 8)), getattr(yuv, 'layout', '420')
-        dedup, fields = getattr(yuv, 'dedup', None), getattr(yuv, 'fields', None)
-        mode = getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob'
-        if mode != 'bob' and (dedup is not None or not reuse_frames):
-            raise ValueError('WindowRunner.run_clip_u8: deint_mode %r needs reuse_frames and does not go with repeated frames' % (mode,))
-        if dedup is not None and (self.retime is None or window_index is None or not reuse_frames):
-            raise ValueError('WindowRunner.run_clip_u8: repeated frames need a retimed runner (r = M for x M), window_index and reuse_frames')
-        if self.retime is not None and yuv is None:
-            raise ValueError('WindowRunner.run_clip_u8: a retimed runner needs the Y4M edge (yuv=...)')
-        if cuts and (self.retime is None or not reuse_frames):
-            raise ValueError('WindowRunner.run_clip_u8: scene cuts need a retimed runner (r = M for x M) and reuse_frames')
-        if full and (self.retime is None or window_index is None):
-            raise ValueError('WindowRunner.run_clip_u8: the full-length timeline needs a retimed runner and window_index')
-        if self._pipeline is None or self._pipeline.key != pipeline_key(batch, yuv is not None, cuts, full, depth, layout, dedup, fields, mode):
+        spec = EdgeSpec.of(yuv)
+        spec.check(self.retime is not None, window_index is not None, reuse_frames)
+        if self._pipeline is None or self._pipeline.key != (batch, spec):
             self._pipeline = None                        # release the old buffers before the new ones are allocated
-            self._pipeline = ClipPipeline(self, batch, yuv is not None, cuts, full, depth, layout, dedup, fields, mode)
+            self._pipeline = ClipPipeline(self, batch, spec)
         return self._pipeline.run(host_frames, windows, sink, reuse_frames, yuv, window_index)
 
     def __del__(self):

@@ -72,7 +72,7 @@ from . import scene as S
 from . import tiling as T
 from . import y4m
 from .clip import ClipRunner
-from .pipeline import KeptFrames
+from .pipeline import KeptFrames, deint_conflict
 
 
 class YuvEdge:
@@ -99,12 +99,13 @@ class YuvEdge:
 
 
 def check_deinterlace_mode(deinterlace, mode, dedup):
-    """The rules of ``--deinterlace-mode``: 'bob' or 'adaptive'; 'adaptive' only with ``--deinterlace`` and not with ``--dedup``."""
-    if mode not in I.MODES:
+    """``pipeline.deint_conflict`` in the words of the switches: 'adaptive' only with ``--deinterlace`` and not with ``--dedup``."""
+    why = deint_conflict(mode, deinterlace, dedup not in (None, False))
+    if why == 'mode':
         raise ValueError('deinterlace_mode must be one of %s, got %r' % (', '.join(I.MODES), mode))
-    if mode != 'bob' and not deinterlace:
+    if why == 'fields':
         raise ValueError('--deinterlace-mode %s needs --deinterlace (deinterlace=True): the mode says how fields are rebuilt' % mode)
-    if mode != 'bob' and dedup not in (None, False):
+    if why == 'dedup':
         raise ValueError('--deinterlace-mode %s does not go with --dedup: repeated frames are staged and discarded one field at a time, '
                          'the %s mode needs two fields of lookahead; use --deinterlace-mode bob with --dedup' % (mode, mode))
 

@@ -1,0 +1,444 @@
+"""The Y4M edge of the clip pipeline (``demfi_amd.pipeline``): Y4M payloads in and out, every window on its own plan, all options in
+one ``pipeline.EdgeSpec``.  One stage per job, each with its own buffers: ``Ingest``, ``SceneScores``, ``DedupProbe``, the pure function
+``plan_batch`` and a ``FrameIO`` chosen once; ``Y4mEdge`` keeps their order and the payloads' way out."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import cadence as K
+from . import deint as I
+from . import retime as R
+from . import scene as S
+from .y4m import payload_size
+
+# int64 word positions in a demfi_u8_sink record (256 bytes: the context's "sink" buffer)
+_FRAME, _HW, _ITER = L.U8Sink.frame.offset // 8, L.U8Sink.h.offset // 8, L.U8Sink.iter.offset // 8
+assert (L.U8Sink.h.offset, L.U8Sink.w.offset, L.U8Sink.iter.offset) == (8 * _HW, 8 * _HW + 4, 8 * _ITER) and C.sizeof(L.U8Sink) <= 256
+
+
+def fill_sink_records(a, st, s0, s1, h, w, n_tst):
+    """demfi_u8_sink records into the int64 array a [..., 32]: segments 0 / 1 / 2 of the last layer = S0 / S1 / St are written to
+    the device pointers s0 / s1 / st (int64 arrays that broadcast to a.shape[:-1]; 0 = not written).  A record without St
+    stays all zero: disabled, its time instant writes nothing."""
+    live = np.broadcast_to(st, a.shape[:-1]) != 0
+    a[...] = 0
+    a[..., _FRAME], a[..., _FRAME + 1], a[..., _FRAME + 2] = s0, s1, st
+    a[..., _HW] = np.where(live, h | (w << 32), 0)           # int32 h, w
+    a[..., _ITER] = np.where(live, n_tst - 1, 0)              # int32 iter, pad
+    return a
+
+
+def consecutive(sls):
+    """(first, count) of every run of consecutive slots in the list ``sls``."""
+    r = 0
+    while r < len(sls):
+        e = r + 1
+        while e < len(sls) and sls[e] == sls[e - 1] + 1:
+            e += 1
+        yield sls[r], e - r
+        r = e
+
+
+def yuv_calls(lib, spec, h, w, yuv):
+    """The three launches of the Y4M edge for h x w frames of ``spec``'s depth and layout, bound to the stream's matrix, range and siting (``yuv``):
+    to_bgr(src, dst, cnt, stream) converts cnt consecutive payloads to BGR frames, gather(base, offs, dst, n, stream) converts the n frames at base +
+    offs[] to consecutive payloads, sad(base, a, b, m, out, stream) scores m payload pairs. Pointers are addresses; every stride and offset counts
+    samples, which are bytes at depth 8.  4:2:0 has C functions of its own (8-bit: csrc/yuv.hip), 4:2:2, 4:4:4 and mono those of the layouts family,
+    which take the layout code; the 16-bit functions take the depth; only 4:2:0 has a siting."""
+    hi, lc, P, F = spec.hi, L.YUV_LAYOUT[spec.layout], payload_size(h, w, spec.layout), h * w * 3
+    if lc:
+        names = ('yuvl16_to_bgr16', 'bgr16_to_yuvl16_gather') if hi else ('yuvl_to_bgr', 'bgr_to_yuvl_gather')
+    else:
+        names = ('yuv420p16_to_bgr16', 'bgr16_to_yuv420p16_gather') if hi else ('yuv420_to_bgr', 'bgr_to_yuv420_gather')
+    names += ('yuv420p16_sad' if hi else 'yuv420_sad',)
+    c_bgr, c_gather, c_sad = (getattr(lib, 'demfi_' + nm) for nm in names)
+    fmt = ((spec.depth,) if hi else ()) + ((lc,) if lc else ()) + (yuv.matrix, int(yuv.full_range))
+    site = () if lc else (yuv.siting,)
+
+    def to_bgr(src, dst, cnt, stream):
+        L.check(c_bgr(src, P, dst, F, cnt, h, w, *fmt, *site, stream), names[0])
+
+    def gather(base, offs, dst, n, stream):
+        L.check(c_gather(base, offs, dst, P, n, h, w, *fmt, stream), names[1])
+
+    def sad(base, a, b, m, out, stream):
+        L.check(c_sad(base, a, b, m, P, out, stream), names[2])
+    return to_bgr, gather, sad
+
+
+def max_runs(r, cuts, dedup):
+    """Upper bound of the runs of one window of the Y4M edge: a cut window is two; with ``dedup`` = (hi, lo, frac, max_hold) a
+    window that spans several input frames is split into runs of at most ``retime.max_instants(r)`` instants."""
+    return max(2 if cuts else 1, K.max_window_runs(r, dedup[3]) if dedup is not None else 1)
+
+
+class Ingest:
+    """Payload copied -> BGR frame slot ready.  ``yuv_in`` [nslot, Pb]: the payload of every frame slot (uint8, sized in bytes: P samples of ``es``
+    bytes); ``to_frames`` converts new ones into their slots, one launch per run of consecutive slots, and crops them into their tiles (``tiler``: the
+    ``pipeline.Tiler`` of an 8-bit tiled run, else None).  Interlaced input (``fields`` 't' / 'b': frame f is field f, its payload uploaded as it is)
+    is first made progressive in place.  ``bob``: ONE ``demfi_yuv_bob`` launch per run of consecutive slots.  ``adaptive``: ONE
+    ``demfi_yuv_deint_adaptive`` launch per batch (at most 64 fields each) that also reads the kept rows of fields f-2, f-1, f+1 and f+2 out of THEIR
+    slots, so those must have been uploaded (``around`` names them to the batch loop) but need not have been rebuilt, nor stay raw: a launch reads
+    only kept rows and writes only missing ones (the hazard rule of csrc/deint.hip).  A field is rebuilt in the batch that first names it in a window
+    (or as the scene detector's predecessor frame); until then it is ``raw``.  No payload is uploaded more often than by the bob: once per field."""
+
+    def __init__(self, runner, slots, spec, h, w, tiler=None):
+        self.rn, self.slots, self.tiler, self.fh, self.fw = runner, slots, tiler, h, w
+        self.fields, self.raw, self.layout, self.to_bgr = spec.fields, {}, spec.layout, None
+        self.adaptive = spec.fields is not None and spec.deint_mode == 'adaptive'
+        self.es, self.P = 2 if spec.hi else 1, payload_size(h, w, spec.layout)       # bytes per sample; samples of a payload
+        self.Pb = self.P * self.es                                       # bytes of a payload
+        dev, nsl = runner.engine.device, len(slots.frames)
+        self.yuv_in = torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev)
+        if self.adaptive:                            # five payload offsets per field rebuilt in a batch (at most nsl); reused in stream order
+            self.dei_offs = torch.empty(5 * nsl, dtype=torch.int64, device=dev)
+
+    def upload(self, sl, idx, f):
+        if tuple(f.shape) != (self.Pb,) or f.dtype != torch.uint8:
+            raise ValueError('frame %d: expected a uint8 [%d] %s payload, got %s %s' % (idx, self.Pb, self.layout, f.dtype, tuple(f.shape)))
+        self.yuv_in[sl].copy_(f, non_blocking=True)
+
+    def bob(self, new, stream):
+        """The payloads just copied for the (field, slot) pairs ``new`` become progressive in place (at most 64 per launch)."""
+        if self.fields is None or not new:
+            return new
+        q = {sl: I.field_parity(self.fields, idx) for idx, sl in new}
+        for s0, cnt in consecutive([sl for _, sl in new]):
+            for c0 in range(s0, s0 + cnt, 64):
+                c = min(64, s0 + cnt - c0)
+                L.check(self.rn.lib.demfi_yuv_bob(self.yuv_in[c0].data_ptr(), self.Pb, c, self.fh, self.fw, L.YUV_LAYOUT[self.layout], self.es,
+                                                  sum(q[c0 + j] << j for j in range(c)), stream.cuda_stream), 'yuv_bob')
+        return new
+
+    def around(self, needed, has):
+        """Adaptive: the fields f-2 .. f+2 of every field f of ``needed`` not rebuilt yet, as far as the input has them (``has``)."""
+        if not self.adaptive:
+            return []
+        needed = set(needed)
+        self._needed, self._has = sorted(needed), has
+        todo = [f for f in self._needed if f in self.raw or f not in self.slots.slot_of]
+        return sorted({g for f in todo for g in range(max(f - 2, 0), f + 3) if g not in needed and (g < f or has(g))})
+
+    def _adaptive(self, new, stream):
+        """The fields of this batch that are still raw become progressive frames in place; returns them as (field, slot) pairs."""
+        slot_of = self.slots.slot_of
+        self.raw.update(new)
+        self.raw = {f: sl for f, sl in self.raw.items() if slot_of.get(f) == sl}     # a slot the ring took back is forgotten
+        todo = [f for f in self._needed if f in self.raw]
+        done = 0
+        for c0 in range(0, len(todo), 64):
+            fs = todo[c0:c0 + 64]
+            for f in fs:                             # a field of the input that is not resident must not pass for an absent one
+                gone = [g for g in range(max(f - 2, 0), f + 3) if g not in slot_of and (g < f or self._has(g))]
+                if gone:
+                    raise RuntimeError('adaptive deinterlacing: field %d needs field %d, which is not resident' % (f, gone[0]))
+            offs = [slot_of[g] * self.Pb if g in slot_of else -1 for f in fs for g in range(f - 2, f + 3)]
+            host = torch.tensor(offs, dtype=torch.int64).pin_memory()
+            od = self.dei_offs[5 * done:5 * (done + len(fs))]
+            od.copy_(host, non_blocking=True)
+            L.check(self.rn.lib.demfi_yuv_deint_adaptive(self.yuv_in.data_ptr(), self.yuv_in.numel(), host.data_ptr(), od.data_ptr(), len(fs),
+                                                         self.fh, self.fw, L.YUV_LAYOUT[self.layout], self.es,
+                                                         sum(I.field_parity(self.fields, f) << j for j, f in enumerate(fs)),
+                                                         stream.cuda_stream), 'yuv_deint_adaptive')
+            done += len(fs)
+        return [(f, self.raw.pop(f)) for f in todo]
+
+    def to_frames(self, new, stream):
+        """The progressive payloads of the (frame, slot) pairs ``new`` -> their BGR frame slots (and tiles)."""
+        sls = [sl for _, sl in new]
+        for s0, cnt in consecutive(sls):
+            self.to_bgr(self.yuv_in[s0].data_ptr(), self.slots.frames[s0].data_ptr(), cnt, stream.cuda_stream)
+        if self.tiler is not None:
+            self.tiler.crop(sls, stream)
+
+
+class SceneScores:
+    """SAD_j of every new frame j against frame j-1 over the payloads of ``ingest``, for the run's ``scene.Detector`` (``det``).
+    d_sad / sad_offs / h_sad: the SADs of a batch's new frames (at most nslot), their offset pairs, the pinned copy the host reads."""
+
+    def __init__(self, slots, ingest):
+        self.slots, self.ingest, self.det, self.sad = slots, ingest, None, None
+        dev, nsl = ingest.yuv_in.device, len(slots.frames)
+        self.d_sad, self.sad_offs = torch.empty(nsl, dtype=torch.int64, device=dev), torch.empty(2 * nsl, dtype=torch.int64, device=dev)
+        self.h_sad = torch.empty(nsl, dtype=torch.int64).pin_memory()
+
+    def score(self, new_frames, h2d):
+        """SAD_j of every frame j just uploaded against frame j-1 (``demfi_yuv420_sad``, ONE launch on the h2d stream after the
+        copies), read back with one event wait and handed to the detector in frame order.  Call under the h2d stream.
+        Frame j-1 is resident: it was uploaded in this batch or in the previous one (windows are consecutive), and a slot is
+        reused only after all nslot >= 2 * batch + 8 slots have been (adaptive deinterlacing: nslot >= 2 * batch + 12, and batch b
+        uploads up to frame k + 2 * batch + 4, its two fields of lookahead included, so it takes back the slots of frames up to
+        k - 8 at most, while batch b-1 reads frames from k - 1 on and its rebuild launches, queued on h2d before, from k - 3 on).
+        The wait does not wait on the compute stream: the
+        ``busy`` waits queued on h2d before this batch's copies are on the compute of the batch that last read a reused
+        slot, and that batch is at least two back (batch b-1 reads frames k .. k + batch + 2 of its first window k, batch b
+        uploads frames up to k + 2 * batch + 2 only), so the host already waited for it when it drained that batch's D2H."""
+        det, slot_of, P, yuv_in = self.det, self.slots.slot_of, self.ingest.P, self.ingest.yuv_in
+        js = sorted(j for j in new_frames if j >= det.next)
+        if not js:
+            return
+        if any(j - 1 not in slot_of for j in js):
+            raise RuntimeError('scene cuts: the predecessor of frame %d is not resident' % min(j for j in js if j - 1 not in slot_of))
+        m = len(js)
+        offs = [slot_of[j - 1] * P for j in js] + [slot_of[j] * P for j in js]
+        od = self.sad_offs[:2 * m]
+        od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
+        self.sad(yuv_in.data_ptr(), od.data_ptr(), od[m:].data_ptr(), m, self.d_sad.data_ptr(), h2d.cuda_stream)
+        self.h_sad[:m].copy_(self.d_sad[:m], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(h2d)
+        ev.synchronize()
+        for j, sad in zip(js, self.h_sad[:m].tolist()):
+            det.push(j, sad)
+
+
+class DedupProbe:
+    """Repeated frames (``cadence``): ``pipeline.KeptFrames`` stages, scores and keeps or discards input frames through this object, one
+    at a time, on the upload stream ``h2d``.  cnt / cnt_offs: the block counts of one (frame, last kept frame) pair and their offsets;
+    the pinned twins are reused: every probe ends with a wait for its answer.  ``thresholds``: (hi, lo) at the bit depth."""
+
+    def __init__(self, runner, slots, ingest, spec, h2d):
+        self.rn, self.slots, self.ingest, self.h2d, self.kept, self.pending = runner, slots, ingest, h2d, None, []
+        self.thresholds = spec.dedup[0] << (spec.depth - 8), spec.dedup[1] << (spec.depth - 8)
+        dev = ingest.yuv_in.device
+        self.cnt, self.cnt_offs = torch.empty(2, dtype=torch.int32, device=dev), torch.empty(2, dtype=torch.int64, device=dev)
+        self.h_cnt, self.h_cnt_offs = torch.empty(2, dtype=torch.int32).pin_memory(), torch.empty(2, dtype=torch.int64).pin_memory()
+
+    def attach(self, kept):
+        """A --dedup run starts, before its first window is asked for: ``kept`` (``KeptFrames``) will stage frames here."""
+        self.kept, self.pending, kept.edge = kept, [], self
+        return kept
+
+    def stage(self, key, idx, f):
+        """Input frame idx, the candidate for kept index ``key``, is copied into the ring's next slot and (a field) bobbed there."""
+        with torch.cuda.stream(self.h2d):
+            sl, _ = self.slots.acquire(key, self.h2d)
+            self.ingest.upload(sl, idx, f)
+            self.ingest.bob([(idx, sl)], self.h2d)
+        return sl
+
+    def block_counts(self, sl, ref):
+        """(hot, warm) of the payload in slot sl against the one in slot ref: ONE ``demfi_luma_block_counts`` launch on the upload stream behind the
+        copy, read back with one event wait (the next frame is compared with whichever of the two is kept, so frames are scored one by one)."""
+        ing, (hi, lo) = self.ingest, self.thresholds
+        with torch.cuda.stream(self.h2d):
+            self.h_cnt_offs[0], self.h_cnt_offs[1] = sl * ing.Pb, ref * ing.Pb
+            self.cnt_offs.copy_(self.h_cnt_offs, non_blocking=True)
+            L.check(self.rn.lib.demfi_luma_block_counts(ing.yuv_in.data_ptr(), self.cnt_offs.data_ptr(), self.cnt_offs[1:].data_ptr(), 1,
+                                                        ing.fh, ing.fw, ing.es, hi, lo, self.cnt.data_ptr(), self.h2d.cuda_stream),
+                    'luma_block_counts')
+            self.h_cnt.copy_(self.cnt, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.h2d)
+        ev.synchronize()
+        return tuple(self.h_cnt.tolist())
+
+    def keep(self, key, sl):
+        """The staged frame is kept: it is converted with the next batch's uploads."""
+        self.pending.append((key, sl))
+
+    def discard(self, key):
+        """The staged frame repeats the last kept one: its slot is recycled at once."""
+        self.slots.release(key)
+
+
+def plan_batch(spec, r, wins, n, window_index, with_s1, det, kept, frames, slot_of):
+    """The plan of a batch of windows n, n+1, ... of the sequence (window n + wi is window ``window_index(n + wi)``, else B-1 of its unclamped tuple)
+    at the ratio r; ``frames``: the slots of their tuples, ``slot_of``: those of all resident frames.  The planner is ``retime.window_plan``, with a
+    scene detector ``det`` ``scene.window_runs`` (a cut window is two runs), with the ``kept`` frames of a --dedup run ``cadence.window_runs`` over
+    kept indices.  Returns (runs as (slots, instants, kinds kept), outs[w] as (run of the batch, kind, instant index) in stream order, the cut windows
+    among them, the St frames planned over kept frames).  Pure."""
+    runs, outs, cut_windows, st_frames = [], [], 0, 0
+    for wi, win in enumerate(wins):
+        k = window_index(n + wi) if window_index is not None else win[2]
+        last = with_s1(n + wi)
+        if kept is not None:                         # the plans of ``cadence`` over the kept frames; slots by kept index
+            is_cut = det.is_cut if det is not None else None
+            sr, so = K.window_runs(k, r, kept.s, kept.n, is_cut, spec.full)
+            cut_windows += int(K.is_cut_window(k, is_cut))
+            st_frames += sum(kind == R.ST for _, _, kind, _ in so)
+        elif det is None:
+            ts, o = R.window_plan(k, r, last, spec.full)
+            sr, so = None, [(None, 0, kind, j) for _, kind, j in o]
+        else:
+            is_cut = S.with_sentinels(det.is_cut, k + 3 if last else None) if spec.full else det.is_cut
+            sr, so = S.window_runs(k, r, last, is_cut, spec.full)
+            cut_windows += len(sr) - 1
+        wr = [(frames[wi], ts)] if sr is None else [([slot_of[x] for x in S.runner_order(tup)], ts) for tup, ts in sr]
+        outs.append([(len(runs) + run, kind, j) for _, run, kind, j in so])
+        runs += [(fr, ts, {kind for _, run, kind, _ in so if run == ri}) for ri, (fr, ts) in enumerate(wr)]
+    return runs, outs, cut_windows, st_frames
+
+
+class TileGrid:
+    """A multi-tile plan for the 16-bit frames of the Y4M edge: the sizes ``pipeline.Tiler`` gives, and no device side.  The ingest of
+    a (run, tile) pair reads its source rectangle out of the full frame slots and its egress writes its kept rectangle into the full
+    output frames (``WindowRunner._u16_tile_io``), so there is nothing to crop into and nothing to stitch from."""
+
+    def __init__(self, plan):
+        self.plan, self.nt = plan, plan.n_tiles
+        (self.h, self.w), (self.th, self.tw) = (plan.h, plan.w), plan.tile
+
+
+class FrameIO:
+    """How the runs of a batch read and write frames, chosen once from (16-bit frames, tiled): each planned run is ``nt`` runner runs, ``reads(fr)``
+    gives the four tensors each reads, ``dst[i]`` the buffer they write, ``window(w, frames, buf, rows)`` the (load, emit, pre) of runner run w, and
+    ``after(i, runs, cur)`` follows the windows.  comb[i][w] = [S0, St x J, S1] of planned run w; 16-bit frames are int16 storage and leave through the
+    emit path (``sinks`` False: the fused sink writes uint8 only).  8-bit tiles (``crops``: the ``pipeline.Tiler`` that cropped the slots at upload)
+    run into ``tcomb`` and ONE stitch launch per batch pastes them into comb[i]; one tcomb serves both buffer sets: the stitch has read it before the
+    next batch's runs start.  16-bit tiles are ``in_place``: their kept rectangles of comb[i][w] are disjoint, so the runs need no order among
+    themselves."""
+
+    def __init__(self, runner, slots, tiler, runs_max, J, h, w, depth):
+        hi, tiled, dev, frames = depth > 8, tiler is not None, runner.engine.device, slots.frames
+        if tiled and hi != isinstance(tiler, TileGrid):
+            raise ValueError('Y4mEdge: %d-bit frames with a %s' % (depth, type(tiler).__name__))
+        nt = self.nt = tiler.nt if tiled else 1
+        self.J, self.tiler, self.sinks, self.in_place, self.crops = J, tiler, not hi, hi and tiled, None
+        self.comb = self.dst = [torch.empty((runs_max, J + 2, h, w, 3), dtype=torch.int16 if hi else torch.uint8, device=dev) for _ in range(2)]
+        self.reads, self.after = lambda fr: [[frames[sl] for sl in fr]] * nt, lambda i, runs, cur: None
+        out = lambda buf, w: (buf[w, 1:J + 1], buf[w, 0::J + 1])          # noqa: E731  (St x J, [S0, S1]) of run w
+        self.window = ((lambda w, fr, buf, rows: runner._u16_tile_io(fr, tiler.plan.tiles[w % nt], *out(buf, w // nt), depth)) if self.in_place
+                       else (lambda w, fr, buf, rows: runner._u16_io(fr, *out(buf, w), depth)) if hi
+                       else (lambda w, fr, buf, rows: runner._u8_io(fr, *out(buf, w), None if rows is None else rows[w])))
+        if tiled and not hi:
+            self.crops, self.after, self.reads = tiler, self._stitch, lambda fr: [[tiler.tin[sl, j] for sl in fr] for j in range(nt)]
+            self.tcomb = torch.empty((runs_max * nt, J + 2, tiler.th, tiler.tw, 3), dtype=torch.uint8, device=dev)
+            self.dst = [self.tcomb, self.tcomb]
+
+    def _stitch(self, i, runs, cur):
+        J, nt, comb, tcomb = self.J, self.nt, self.comb[i], self.tcomb
+        (c0, c1), (t0, t1), j = comb.stride()[:2], tcomb.stride()[:2], np.arange(nt, dtype=np.int64)
+        pos = [(w, p) for w, (_, ts, kinds) in enumerate(runs)
+               for p in ([0] if R.S0 in kinds else []) + list(range(1, len(ts) + 1)) + ([J + 1] if R.S1 in kinds else [])]
+        self.tiler.stitch(tcomb, [(w * nt + j) * t0 + p * t1 for w, p in pos], comb, [w * c0 + p * c1 for w, p in pos], cur)
+
+
+class Y4mEdge:
+    """Y4M payloads in; sink(k, payloads [c, P]) out, the c output frames window k owns in stream order.  ``spec``: the run's
+    ``pipeline.EdgeSpec``; ``tiler``: None, a ``pipeline.Tiler`` (8-bit frames) or a ``TileGrid`` (16-bit).  ONE gather launch per batch
+    converts the outputs in comb[i] into yuv_out[i] in stream order; the payload buffers are uint8 tensors sized in bytes."""
+
+    def __init__(self, runner, batch, slots, spec, tiler, h2d):
+        self.rn, self.slots, self.spec = runner, slots, spec
+        r = self.r = runner.ratio
+        h, w = (tiler.h, tiler.w) if tiler else (runner.h, runner.w)
+        dev, J = runner.engine.device, R.max_instants(r)
+        nJ = -(-J // runner.n_ctx) * runner.n_ctx if runner.tb else J    # instants incl. the padding of a short chunk
+        runs_max = batch * max_runs(r, spec.cuts, spec.dedup)            # a cut window is two runs
+        # payloads of a batch: at most J per window, plus the last window's S1 (full-length: its [n-2, n) span, 2 J)
+        nout = (batch + 1) * J if spec.full else batch * J + 1
+        if spec.dedup is not None:                   # a window spans up to max_hold + 1 input frames, and so does the last one's hold
+            nout = (batch + 1) * K.max_window_instants(r, spec.dedup[3]) + 1
+        io = self.io = FrameIO(runner, slots, tiler, runs_max, J, h, w, spec.depth)
+        ing = self.ingest = Ingest(runner, slots, spec, h, w, io.crops)
+        self.around = ing.around                     # the frames a batch must find uploaded besides those it names
+        self.scores = SceneScores(slots, ing) if spec.cuts else None
+        self.probe = DedupProbe(runner, slots, ing, spec, h2d) if spec.dedup is not None else None
+        self.t = [torch.empty((runs_max * io.nt, nJ), dtype=torch.float32, device=dev) for _ in range(2)]
+        self.sinks = [torch.empty((runs_max * io.nt, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)]
+        self.offs = [torch.empty(nout, dtype=torch.int64, device=dev) for _ in range(2)]
+        self.yuv_out = [torch.empty((nout, ing.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.h_yuv = [torch.empty((nout, ing.Pb), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.yuv = self.window_index = self.det = self.kept = self.gather = None
+
+    def __getattr__(self, name):                     # J, tiler, in_place and, on a crop-run-stitch edge only, tcomb: the frame IO's
+        return getattr(self.__dict__['io'], name)
+
+    def attach(self, host_frames):
+        """Before a run's first window is asked for.  --dedup: ``host_frames`` is the ``KeptFrames`` that stages frames through ``probe``."""
+        if self.probe is not None:
+            self.kept = self.probe.attach(host_frames)
+
+    def begin(self, yuv, window_index, first_win):
+        """A run starts; returns the frames to make resident first: with scene cuts, frame k0 - 1 of a first window k0 >= 1."""
+        ing, sc = self.ingest, self.scores
+        self.yuv, self.window_index, self.det, ing.raw = yuv, window_index, None, {}
+        ing.to_bgr, self.gather, sad = yuv_calls(self.rn.lib, self.spec, ing.fh, ing.fw, yuv)
+        if sc is None:
+            return ()
+        sc.sad, det = sad, S.Detector(ing.P, yuv.scene_cut, first=S.first_frame(window_index(0) if window_index is not None else first_win[2]),
+                                      peak=(1 << self.spec.depth) - 1)
+        sc.det = self.det = det
+        self.rn.last_cuts = det.cuts
+        return (det.next - 1,) if det.next - 1 < first_win[2] else ()
+
+    def upload(self, sl, idx, f):
+        self.ingest.upload(sl, idx, f)
+
+    def uploaded(self, new, h2d):
+        """After a batch's copies (h2d stream): its (frame, slot) pairs and the kept frames staged since become frame slots; then the SADs."""
+        ing, probe = self.ingest, self.probe
+        new = ing._adaptive(new, h2d) if ing.adaptive else ing.bob(new, h2d)      # adaptive: the fields just rebuilt, not those uploaded
+        if probe is not None:                        # the frames kept since the last batch were bobbed when they were staged
+            new, probe.pending = probe.pending + list(new), []
+        ing.to_frames(new, h2d)
+        if self.det is not None:
+            self.scores.score([idx for idx, _ in new], h2d)
+
+    def run(self, i, n, wins, frames, cur):
+        """Plans the batch's windows, runs them and gathers their outputs into yuv_out[i].  Returns (payloads per window, slots read)."""
+        runs, outs, cut_windows, st_frames = plan_batch(self.spec, self.r, wins, n, self.window_index, self.yuv.with_s1, self.det, self.kept,
+                                                        frames, self.slots.slot_of)
+        self.rn.cut_windows += cut_windows
+        if self.kept is not None:
+            self.kept.st_frames += st_frames
+        self._run_windows(i, runs)
+        return self._gather(i, outs, cur), [fr for fr, _, _ in runs]
+
+    def _run_windows(self, i, runs):
+        """Planned run w = (4 slots, instants, kinds) becomes the ``io.nt`` runner runs w * nt + j, which run its instants into ``io.dst[i]``;
+        ``io.after`` follows them.  The t values (padded slots repeat the last t) are uploaded on the current stream, and so are the uint8 sink records
+        of a frame IO of ``sinks``, the one mode switch left here: one per (run, instant), S0 / S1 only in the row of the run's first instant and only
+        when ``kinds`` holds that frame, rows past a run's instants disabled."""
+        rn, J, io, buf = self.rn, self.J, self.io, self.io.dst[i]
+        subs = [(frames, ts, kinds) for fr, ts, kinds in runs for frames in io.reads(fr)]
+        nw, nJ = len(subs), self.t[i].shape[1]
+        tt = np.empty((nw, nJ), np.float32)
+        for w, (_, ts, _) in enumerate(subs):
+            tt[w, :len(ts)] = ts
+            tt[w, len(ts):] = ts[-1]
+        t_dev = self.t[i][:nw]
+        t_dev.copy_(torch.from_numpy(tt).pin_memory(), non_blocking=True)
+        rows = None
+        if io.sinks and rn.engine.supports_u8_sink:
+            st = np.zeros((nw, nJ), np.int64)
+            s01 = np.zeros((2, nw, nJ), np.int64)
+            base, (c0, c1) = buf.data_ptr(), buf.stride()[:2]            # uint8: element strides are bytes
+            for w, (_, ts, kinds) in enumerate(subs):
+                st[w, :len(ts)] = base + w * c0 + c1 * np.arange(1, len(ts) + 1)
+                s01[0, w, 0] = base + w * c0 if R.S0 in kinds else 0
+                s01[1, w, 0] = base + w * c0 + (J + 1) * c1 if R.S1 in kinds else 0
+            a = fill_sink_records(np.empty((nw, nJ, 32), np.int64), st, s01[0], s01[1], rn.h, rn.w, rn.n_tst)
+            rows = self.sinks[i][:nw]
+            rows.copy_(torch.from_numpy(a).pin_memory(), non_blocking=True)
+        wio = [io.window(w, frames, buf, rows) for w, (frames, _, _) in enumerate(subs)]
+        cur = rn._begin()
+        for w, (load, emit, pre) in enumerate(wio):
+            rn._window(load, emit, body_only=True, pre=pre, t_dev=t_dev[w], nt=len(subs[w][1]))
+        rn._end(cur)
+        io.after(i, runs, cur)
+
+    def _gather(self, i, outs, cur):
+        """outs[w] = window w's outputs as (run, kind, instant index), from comb[i] -> yuv_out[i]; returns the payloads per window."""
+        comb, dst, J = self.io.comb[i], self.yuv_out[i], self.J
+        c0, c1 = comb.stride()[:2]
+        offs = [run * c0 + (0 if kind == R.S0 else J + 1 if kind == R.S1 else 1 + j) * c1 for o in outs for run, kind, j in o]
+        nf = len(offs)
+        if nf > dst.shape[0]:
+            raise RuntimeError('retime: %d outputs for %d payload slots' % (nf, dst.shape[0]))
+        od = self.offs[i][:nf]
+        od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
+        self.gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), nf, cur.cuda_stream)
+        return [len(o) for o in outs]
+
+    def d2h(self, i, counts):
+        self.h_yuv[i][:sum(counts)].copy_(self.yuv_out[i][:sum(counts)], non_blocking=True)
+
+    def drain(self, i, k0, counts, sink):
+        pos = 0
+        for j, c in enumerate(counts):
+            sink(k0 + j, self.h_yuv[i][pos:pos + c])
+            pos += c

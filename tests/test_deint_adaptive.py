@@ -10,6 +10,7 @@ import pytest
 from demfi_amd import deint as I
 from demfi_amd import pipeline as P
 from demfi_amd import video, y4m
+from demfi_amd.y4m_edge import Ingest
 
 
 # ---- hand-computed samples ------------------------------------------------------------------------------------------------------
@@ -304,8 +305,8 @@ def test_runner_arguments():
     assert video.VideoRunner(None, deinterlace=True, deinterlace_mode='bob', dedup=True).dedup is not None
     e = video.YuvEdge('bt601', False, '420jpeg', None, fields='t', deint_mode='adaptive')
     assert e.deint_mode == 'adaptive' and video.YuvEdge('bt601', False, '420jpeg', None).deint_mode == 'bob'
-    assert P.pipeline_key(4, True, False, False, fields='t') == P.pipeline_key(4, True, False, False, fields='t', deint_mode='bob')
-    assert P.pipeline_key(4, True, False, False, fields='t', deint_mode='adaptive') != P.pipeline_key(4, True, False, False, fields='t')
+    assert P.EdgeSpec(True, False, False, fields='t') == P.EdgeSpec(True, False, False, fields='t', deint_mode='bob')
+    assert P.EdgeSpec(True, False, False, fields='t', deint_mode='adaptive') != P.EdgeSpec(True, False, False, fields='t')
 
 
 def test_command_line(capsys):
@@ -336,7 +337,7 @@ def _fake_edge(nslot, order='t', pb=36):
 
     import torch
     slots = P.FrameSlots(nslot, 2, 2, 'cpu')
-    e = object.__new__(P.Y4mEdge)
+    e = object.__new__(Ingest)
     e.slots, e.adaptive, e.raw, e.fields, e.Pb, e.es, e.fh, e.fw, e.layout = slots, True, {}, order, pb, 1, 4, 6, '420'
     e.rn = types.SimpleNamespace(lib=_FakeLib())
     e.yuv_in = torch.empty((nslot, pb), dtype=torch.uint8)
@@ -367,8 +368,7 @@ def _drive(frames, windows, batch, n_fields, extra=(), order='t', monkeypatch=No
                 ups.append(idx)
                 new.append((idx, sl))
         named = set(extra).union(*wins)
-        near = e.around(named, frames.has)
-        for idx in [i for i in near if i < min(named)] + list(extra) + [i for w in wins for i in w] + [i for i in near if i > min(named)]:
+        for _, idx in P.residency_order(extra, wins, e.around(named, frames.has)):
             resident(idx)
         calls0 = len(e.rn.lib.calls)
         done = e._adaptive(new, stream)
