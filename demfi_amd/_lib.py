@@ -16,6 +16,8 @@ MODE_STORE, MODE_MUL, MODE_GRU = 0, 1, 2
 BT601, BT709 = 0, 1
 SITING_420JPEG, SITING_420MPEG2 = 0, 1
 YUV_LAYOUT = {'420': 0, '422': 1, '444': 2, 'mono': 3}              # enum demfi_yuv_layout
+OWNERS = ('sep', 'wstream7', 'ws2', 'wstream3', 'c64', 'narrow_nhwc', 'narrow_thin', 'general')     # enum demfi_owner
+OWNERS_COUT_PERM = frozenset(range(6))                              # every owner but narrow_thin and general packs with cout_perm
 MAX_PIECES, MAX_CHUNKS, MAX_SEGS, MAX_OCTS = 48, 40, 8, 32
 
 
@@ -207,6 +209,7 @@ _SIGS = {
     'demfi_ctx_get_op': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Op)]),
     'demfi_ctx_num_convs': (C.c_int, [C.c_void_p]),
     'demfi_ctx_conv_desc': (C.POINTER(Conv), [C.c_void_p, C.c_int]),
+    'demfi_conv_owner': (C.c_int, [C.POINTER(Conv)]),
     'demfi_run_op': (C.c_int, [C.c_void_p, C.POINTER(Op), C.c_void_p]),
     'demfi_graph_begin': (C.c_int, [C.c_void_p]),
     'demfi_graph_end': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),

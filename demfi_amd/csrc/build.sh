@@ -10,7 +10,10 @@ XFLAGS="$DEMFI_EXTRA_FLAGS"
 CONV_UNITS="conv conv_general conv_c64 conv_narrow conv_sep conv_wstream"
 SRCS_HIP="pointwise.hip"
 for u in $CONV_UNITS; do SRCS_HIP="$SRCS_HIP $u.hip"; done
-SRCS_CPP="abi.cpp"
+# the host units, ONE list: the product compile loop and the --asan branch below both run over it.  abi.cpp = ABI glue; ctx.cpp = context
+# life cycle + op interpreter; plan.cpp = launch plan; layout.cpp = workspace layout + arena; conv_build.cpp = descriptor builder;
+# png_codec.cpp parses untrusted bytes
+HOST_UNITS="abi ctx plan layout conv_build png_codec"
 [ -f metrics.hip ] && SRCS_HIP="$SRCS_HIP metrics.hip"
 [ -f fgac_window.hip ] && SRCS_HIP="$SRCS_HIP fgac_window.hip"
 [ -f resblock.hip ] && SRCS_HIP="$SRCS_HIP resblock.hip"
@@ -23,8 +26,6 @@ SRCS_CPP="abi.cpp"
 [ -f dedup.hip ] && SRCS_HIP="$SRCS_HIP dedup.hip"
 [ -f deint.hip ] && SRCS_HIP="$SRCS_HIP deint.hip"
 [ -f wsconv.hip ] && SRCS_HIP="$SRCS_HIP wsconv.hip"
-[ -f ctx.cpp ] && SRCS_CPP="$SRCS_CPP ctx.cpp"
-[ -f png_codec.cpp ] && SRCS_CPP="$SRCS_CPP png_codec.cpp"
 # stale objects must never be linked: a failed compile has to fail the build
 rm -f ./*.o libdemfi_hip.so
 pids=()
@@ -37,9 +38,9 @@ for s in $SRCS_HIP; do
   xf=""; case "$s" in conv*.hip|resblock.hip|gru.hip|wsconv.hip) xf="$CONV_FLAGS" ;; esac
   $HIPCC $FLAGS $xf -c "$s" -o "$o" & pids+=($!)
 done
-for s in $SRCS_CPP; do
-  o="${s%.cpp}.o"; objs+=("$o")
-  $HIPCC $FLAGS -x hip -c "$s" -o "$o" & pids+=($!)
+for u in $HOST_UNITS; do
+  objs+=("$u.o")
+  $HIPCC $FLAGS -x hip -c "$u.cpp" -o "$u.o" & pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done      # 'wait PID' returns that job's status: set -e stops on the first failure
 $HIPCC --offload-arch=gfx950 -shared -fPIC "${objs[@]}" -o libdemfi_hip.so -lz -lpthread
@@ -58,20 +59,19 @@ if [ "$1" = "--trace" ]; then
   $HIPCC --offload-arch=gfx950 -shared -fPIC "${trc[@]}" -o libdemfi_hip_trace.so -lz -lpthread
   echo "built $(pwd)/libdemfi_hip_trace.so"
 fi
-# --asan: host-side AddressSanitizer + UBSan build: the three host translation units -- the plan builder / arena
-# planner / op interpreter (ctx.cpp), the ABI glue (abi.cpp) and the PNG codec that parses untrusted bytes (png_codec.cpp) --
-# instrumented, linked with the ordinary kernel objects.  Run with tools/asan_check.sh (preloads the sanitizer runtime under python).
+# --asan: host-side AddressSanitizer + UBSan build: every host unit of HOST_UNITS instrumented, linked with the
+# ordinary kernel objects.  tools/asan_check.sh does NOT use this library: it builds its own, with ctx.cpp, abi.cpp and png_codec.cpp
+# instrumented only (plan.cpp, layout.cpp, conv_build.cpp plain); those three run under the sanitizers in tests/c/plan_walk_san.sh.
 if [ "$1" = "--asan" ]; then
   # pointer-overflow is off on purpose: the sizing pass of demfi_ctx_create lays the plan out on a NULL base (addresses == workspace offsets)
 SAN="-O1 -g -fsanitize=address,undefined -fno-sanitize=pointer-overflow -fno-gpu-sanitize -fno-omit-frame-pointer -shared-libsan -fno-sanitize-recover=undefined"
   aso=()
   for o in "${objs[@]}"; do
-    case "$o" in
-      ctx.o|abi.o|png_codec.o)
-        $HIPCC --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -I../../include -Wno-unused-result $SAN -x hip -c "${o%.o}.cpp" -o "${o%.o}_asan.o"
-        aso+=("${o%.o}_asan.o") ;;
-      *) aso+=("$o") ;;
-    esac
+    u="${o%.o}"
+    if [[ " $HOST_UNITS " == *" $u "* ]]; then
+      $HIPCC --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -I../../include -Wno-unused-result $SAN -x hip -c "$u.cpp" -o "${u}_asan.o"
+      aso+=("${u}_asan.o")
+    else aso+=("$o"); fi
   done
   $HIPCC --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -fno-gpu-sanitize -shared-libsan "${aso[@]}" -o libdemfi_hip_asan.so -lz -lpthread
   echo "built $(pwd)/libdemfi_hip_asan.so"

@@ -5,13 +5,10 @@
 //   conv_narrow.hip   3x3 / 7x7 over <= 64 channels in one chunk, NHWC or thin outputs      conv_sep.hip   SepConvGRU 1x5 / 5x1 (rounds 1-5; round 6: gru.hip)
 //   conv_wstream.hip  Ch_Reducer 7x7 with streamed weights (+ its 3x3 / 32-cout form)       wsconv.hip     32-channel units, helper-wave DMA (round 6)
 //   resblock.hip      fused residual block                                                  gru.hip        SepConvGRU half-step as r*h, then z + q + blend
-// Eligibility is decided from the descriptor alone; demfi_conv_build (ctx.cpp) shapes a layer for the kernel that owns it.
+// Which kernel owns a layer is decided from the descriptor alone, in ONE place (demfi_conv_owner); demfi_conv_build (conv_build.cpp) shapes a layer for it.
 #include "conv_common.h"
 
 namespace {
-
-bool sep_eligible(const demfi_conv* h) { return demfi_sep_eligible(h); }
-bool wstream_eligible(const demfi_conv* h, int ks = 7, int nch = 2) { return demfi_wstream_eligible(h, ks, nch); }
 
 // epilogue of the persistent 3x3 kernels: ONE NHWC fp16 destination holding all NCO*32 channels (optional residual)
 static bool persist_out_eligible(const demfi_conv* h, bool allow_tanh = false);
@@ -80,12 +77,26 @@ static bool persist_out_eligible(const demfi_conv* h, bool allow_tanh)
 }  // namespace
 
 
-// the descriptor belongs to one of the persistent kernels whose epilogue works on 8 consecutive channels per lane: the 64-channel
-// 3x3 kernel, the narrow kernel with an NHWC destination, the SepConvGRU kernel.  Their layers are packed with cout_perm.
+// The kernel that runs a descriptor: the first of this ladder whose shape it has.
+extern "C" int demfi_conv_owner(const demfi_conv* h)
+{
+    if (demfi_sep_eligible(h)) return DEMFI_OWNER_SEP;
+    if (demfi_wstream_eligible(h, 7, 2)) return DEMFI_OWNER_WSTREAM7;
+    const bool c64 = persist_eligible(h), narrow = narrow_eligible(h);
+    if (!c64 && !narrow && demfi_ws2_eligible(h)) return DEMFI_OWNER_WS2;
+    if (demfi_wstream_eligible(h, 3, 1)) return DEMFI_OWNER_WSTREAM3;
+    if (c64) return DEMFI_OWNER_C64;
+    if (narrow && persist_out_eligible(h)) return DEMFI_OWNER_NARROW_NHWC;
+    if (narrow && h->kh != 7) return DEMFI_OWNER_NARROW_THIN;    // the 7x7 narrow kernel has no thin epilogue
+    return DEMFI_OWNER_GENERAL;
+}
+
+// the descriptor belongs to one of the persistent kernels whose epilogue works on 8 consecutive channels per lane (every owner but the
+// thin-output narrow kernel and the general kernel).  Their layers are packed with cout_perm.
 bool demfi_persist_eligible(const demfi_conv* h)
 {
-    return sep_eligible(h) || wstream_eligible(h) || wstream_eligible(h, 3, 1) || persist_eligible(h) || (narrow_eligible(h) && persist_out_eligible(h)) ||
-           demfi_ws2_eligible(h);
+    const int o = demfi_conv_owner(h);
+    return o != DEMFI_OWNER_NARROW_THIN && o != DEMFI_OWNER_GENERAL;
 }
 
 extern "C" int64_t demfi_conv_lds_bytes(const demfi_conv* h)
@@ -149,26 +160,26 @@ extern "C" int demfi_conv2d(const demfi_conv* h, const demfi_conv* dev, void* st
         if (!ok) return demfi_set_error(DEMFI_ERR_ARG, "demfi_conv2d: subtile %d is not eligible for the staged epilogue", sb);
     }
     hipStream_t st = (hipStream_t)stream;
+    const int owner = demfi_conv_owner(h);
     if (h->pack.ptr != nullptr) {
         // the packed copy is an epilogue of the thin-output narrow kernel only: any other layer asking for it must fail loudly
-        bool ok = h->dtype == DEMFI_F16 && narrow_eligible(h) && thin_out_eligible(h) && !persist_out_eligible(h) && h->pack.sc == 1 && !h->pack.is_f32;
+        bool ok = owner == DEMFI_OWNER_NARROW_THIN && h->pack.sc == 1 && !h->pack.is_f32;
         for (int g = 0; g < 4; ++g) ok = ok && (h->pack_oct_ch[g] < 0 || (h->pack_oct_ch[g] % 4 == 0 && h->oct_n[g] > 0));
         if (!ok) return demfi_set_error(DEMFI_ERR_ARG, "demfi_conv2d: packed copy (demfi_conv.pack) on a layer that is not a thin-output fp16 narrow layer, or malformed");
     }
     if ((h->cout_perm != 0) != demfi_persist_eligible(h))
         return demfi_set_error(DEMFI_ERR_ARG, h->cout_perm ? "demfi_conv2d: descriptor packed for a persistent kernel (cout_perm) but not eligible for one (zero_page missing?)"
                                                            : "demfi_conv2d: persistent-kernel layer without cout_perm (build the descriptor with demfi_conv_build)");
-    if (sep_eligible(h)) return demfi_sep_launch(h, dev, st);
-    if (wstream_eligible(h)) return demfi_wstream_launch(h, dev, st);
-    if (!persist_eligible(h) && !narrow_eligible(h) && demfi_ws2_eligible(h)) return demfi_ws2_launch(h, dev, st);      // wsconv.hip (round 6)
-    if (wstream_eligible(h, 3, 1)) return demfi_wstream3_launch(h, dev, st);
-    if (persist_eligible(h)) return demfi_c64_launch(h, dev, st);
-    if (narrow_eligible(h)) {
-        bool handled = false;
-        const int rc = demfi_narrow_launch(h, dev, st, !persist_out_eligible(h), &handled);
-        if (handled) return rc;
+    switch (owner) {
+    case DEMFI_OWNER_SEP: return demfi_sep_launch(h, dev, st);
+    case DEMFI_OWNER_WSTREAM7: return demfi_wstream_launch(h, dev, st);
+    case DEMFI_OWNER_WS2: return demfi_ws2_launch(h, dev, st);      // wsconv.hip (round 6)
+    case DEMFI_OWNER_WSTREAM3: return demfi_wstream3_launch(h, dev, st);
+    case DEMFI_OWNER_C64: return demfi_c64_launch(h, dev, st);
+    case DEMFI_OWNER_NARROW_NHWC: return demfi_narrow_launch(h, dev, st, false);
+    case DEMFI_OWNER_NARROW_THIN: return demfi_narrow_launch(h, dev, st, true);
+    default: return demfi_conv_general_launch(h, dev, st, (size_t)lds);
     }
-    return demfi_conv_general_launch(h, dev, st, (size_t)lds);
 }
 
 #ifdef DEMFI_TRACE

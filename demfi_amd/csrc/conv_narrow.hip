@@ -739,9 +739,9 @@ int launch_narrow(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, bo
 
 DEMFI_TU_TRACE(demfi_narrow_trace_collect)
 
-int demfi_narrow_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, bool thin, bool* handled)
+// thin: the planar fp32 epilogue (conv.hip, demfi_conv_owner, sends here only the shapes instantiated below)
+int demfi_narrow_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, bool thin)
 {
-    *handled = true;
     if (h->kh == 7) {
         if (!thin) return launch_narrow<1, 32, 7>(h, dev, st, false);
     } else
@@ -753,6 +753,5 @@ int demfi_narrow_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t 
     case 4 * 2 + 1: return launch_narrow<1, 128>(h, dev, st, thin);
     case 4 * 2 + 2: return launch_narrow<2, 128>(h, dev, st, thin);
     }
-    *handled = false;
-    return DEMFI_OK;
+    return demfi_set_error(DEMFI_ERR_ARG, "demfi_narrow_launch: not a narrow layer (kh=%d nks=%d nco=%d thin=%d)", h->kh, h->chunks[0].nks, h->nco, (int)thin);
 }

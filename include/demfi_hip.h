@@ -640,6 +640,11 @@ int     demfi_ctx_num_ops(const demfi_ctx* ctx, int segment, int trunk, int c, i
 int     demfi_ctx_get_op(const demfi_ctx* ctx, int segment, int trunk, int c, int iter, int index, demfi_op* out);
 int     demfi_ctx_num_convs(const demfi_ctx* ctx);
 const demfi_conv* demfi_ctx_conv_desc(const demfi_ctx* ctx, int index);          /* host copy */
+/* The kernel demfi_conv2d runs a descriptor on (decided from the descriptor alone).  Every owner but NARROW_THIN and GENERAL wants its
+ * weights packed with cout_perm. */
+enum demfi_owner { DEMFI_OWNER_SEP = 0, DEMFI_OWNER_WSTREAM7 = 1, DEMFI_OWNER_WS2 = 2, DEMFI_OWNER_WSTREAM3 = 3, DEMFI_OWNER_C64 = 4,
+                   DEMFI_OWNER_NARROW_NHWC = 5, DEMFI_OWNER_NARROW_THIN = 6, DEMFI_OWNER_GENERAL = 7 };
+int     demfi_conv_owner(const demfi_conv* desc);
 int     demfi_run_op(demfi_ctx* ctx, const demfi_op* op, void* stream);
 
 /* ---- single-call operators behind the C ABI (ABI v7; SURVEY.md section 8b: demfi_gru_sep / demfi_fgac) -----------------------------

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "demfi_hip.h"
+#include "weights_bin.h"
 
 #define CHECK(call)                                                                         \
     do {                                                                                    \
@@ -90,25 +91,7 @@ int main(int argc, char** argv)
     /* ---- context: create, load the state_dict, size + allocate + bind the workspace ------------------------- */
     demfi_ctx* ctx = NULL;
     CHECK(demfi_ctx_create(H, W, N, DEMFI_F32, NULL, 1, 2, &ctx));     /* two per-t contexts: the batched plan is checked below */
-    FILE* fw = fopen(argv[1], "rb");
-    if (!fw) { perror(argv[1]); return 1; }
-    int32_t nt = 0;
-    if (fread(&nt, 4, 1, fw) != 1) return 1;
-    for (int i = 0; i < nt; ++i) {
-        int32_t nl = 0, nd = 0;
-        char key[256];
-        int64_t dims[5];
-        if (fread(&nl, 4, 1, fw) != 1 || nl <= 0 || nl >= (int)sizeof(key) || fread(key, 1, nl, fw) != (size_t)nl) return 1;
-        key[nl] = 0;
-        if (fread(&nd, 4, 1, fw) != 1 || nd < 1 || nd > 5 || fread(dims, 8, nd, fw) != (size_t)nd) return 1;
-        size_t n = 1;
-        for (int k = 0; k < nd; ++k) n *= (size_t)dims[k];
-        float* w = (float*)malloc(n * 4);
-        if (fread(w, 4, n, fw) != n) return 1;
-        CHECK(demfi_load_weight(ctx, key, w, dims, nd));
-        free(w);
-    }
-    fclose(fw);
+    if (load_weights_bin(ctx, argv[1]) != 0) return 1;
     const int64_t ws_bytes = demfi_ctx_workspace_bytes(ctx);
     if (ws_bytes != demfi_workspace_bytes(H, W, N, DEMFI_F32, 1, 2)) { fprintf(stderr, "workspace size mismatch\n"); return 1; }
     char* ws = NULL;

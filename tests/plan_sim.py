@@ -1,7 +1,7 @@
 """CPU interpreter of a launch plan  --  TEST INFRASTRUCTURE (not shipped, not a fallback).
 
 Builds nothing itself: it takes an ``Engine`` whose context was bound to HOST memory (``device='cpu'``: same descriptors,
-same packed weight blob the GPU would get, built by the C++ planner in demfi_amd/csrc/ctx.cpp) or a ``Plan`` on CPU
+same packed weight blob the GPU would get, built by the C++ planner in demfi_amd/csrc/plan.cpp) or a ``Plan`` on CPU
 tensors, and *interprets* every ``demfi_conv`` descriptor and pointwise op with torch CPU ops, following the semantics
 documented in include/demfi_hip.h.  Purpose: check the host logic (channel maps, chunking, weight repack, output
 routing, buffer wiring) against the oracle without a GPU, so that a mismatch on the GPU box isolates the HIP kernels.

@@ -14,10 +14,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, 'tests', 'c', 'forward_golden')
 
 
-def _write_inputs(tmp, golden_dir, name):
-    from demfi_amd import synthetic_state_dict, synthetic_window
+def _write_weights(wpath):
+    """weights.bin of synthetic_state_dict(0) in the layout tests/c/weights_bin.h reads."""
+    from demfi_amd import synthetic_state_dict
     sd = synthetic_state_dict(0)
-    wpath, cpath = os.path.join(tmp, 'weights.bin'), os.path.join(tmp, 'case.bin')
     with open(wpath, 'wb') as f:
         f.write(struct.pack('<i', len(sd)))
         for k, v in sd.items():
@@ -25,6 +25,12 @@ def _write_inputs(tmp, golden_dir, name):
             kb = k.encode()
             f.write(struct.pack('<i', len(kb)) + kb + struct.pack('<i', a.ndim) + struct.pack('<%dq' % a.ndim, *a.shape))
             f.write(a.tobytes())
+
+
+def _write_inputs(tmp, golden_dir, name):
+    from demfi_amd import synthetic_window
+    wpath, cpath = os.path.join(tmp, 'weights.bin'), os.path.join(tmp, 'case.bin')
+    _write_weights(wpath)
     g = np.load(os.path.join(golden_dir, name + '.npz'))
     H, W, N = int(g['H']), int(g['W']), int(g['N'])
     x = synthetic_window(H, W, int(g['seed']))[0].numpy()                    # [3,4,H,W]

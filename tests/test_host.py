@@ -486,7 +486,7 @@ def test_single_call_operator_plans_interpreted_on_the_cpu(synthetic_sd):
 def test_per_t_contexts_stay_independent_in_the_arena(synthetic_sd):
     """The per-t contexts of a trunk set may run CONCURRENTLY on different streams (demfi_forward_t; the runner's DEMFI_TB=0 mode).
     With buffers sharing memory that only holds if everything context q touches lies in memory no other context touches (the
-    slotted arena of ctx.cpp::plan_arena).  Interpreted on the CPU: the op lists of three contexts interleaved with a lag of
+    slotted arena of layout.cpp::plan_arena).  Interpreted on the CPU: the op lists of three contexts interleaved with a lag of
     11 ops between them leave exactly what each context leaves when it runs alone."""
     from demfi_amd.engine import SEG_HEAD, SEG_ITER, SEG_TRUNK
     H, W, N, NC = 32, 64, 2, 3
@@ -548,7 +548,7 @@ def _plan_digest(env):
 
 
 def test_workspace_arena_shrinks_the_workspace_and_changes_no_result():
-    """the per-t / trunk buffers are planned by liveness (ctx.cpp, plan_arena): the headline configuration needs
+    """the per-t / trunk buffers are planned by liveness (layout.cpp, plan_arena): the headline configuration needs
     <= 45 GB instead of 87.5 GB, config 5 (1080p x16) fits three trunk sets under the half-of-HBM rule, and the launch plan computes
     bit-identical results whether buffers share memory or not (batched per-t plan, fp16, two recursions, interpreted on the CPU --
     recycled memory holds the previous tenant's values there exactly as on the GPU)."""
