@@ -2,7 +2,11 @@
 
 Comparisons: the oracle (oracle/demfi_oracle.py) and the fixtures frozen from the upstream reference
 (tests/golden).  Integer maps (splat target indices, grid-sample floor indices / in-bounds bits / validity)
-must be BIT-IDENTICAL; floating-point values are compared with the tolerance written in each test."""
+must be BIT-IDENTICAL; floating-point values are compared with the tolerance written in each test.
+
+The body of every convolution test is a function of the plan class (``_xxx(plan_cls, ..., rec=None)``): the tests here run it on
+``engine.Plan``, tests/test_gpu_guarded.py runs the same body on ``GuardedPlan`` (poisoned guard bands, pitched rows).  ``_launch`` is
+``pl.launch_<kind>`` plus, on a guarded plan, that module's checks around it; ``_prefill`` is ``fill_`` on a plain plan."""
 import ctypes as C
 import os
 
@@ -16,6 +20,7 @@ from demfi_amd import _lib as L                      # noqa: E402
 from demfi_amd.engine import Plan, _Dst              # noqa: E402
 from oracle import demfi_oracle as O                 # noqa: E402
 from tests import epilogue_ref as E                  # noqa: E402
+from tests.guarded_plan import launch as _launch, prefill as _prefill      # noqa: E402
 
 DEV = 'cuda:0'
 
@@ -65,31 +70,37 @@ CONV_CASES = [
 @pytest.mark.parametrize('dtype', [torch.float32, torch.float16])
 @pytest.mark.parametrize('case', CONV_CASES)
 def test_conv_vs_torch(case, dtype):
+    _conv_vs_torch(Plan, case, dtype)
+
+
+def _conv_vs_torch(plan_cls, case, dtype, batch=1, rec=None):
     cin, cout, kh, kw, stride, H, W, act, with_res = case
     torch.manual_seed(cin * 1000 + cout + kh)
     inH, inW = H * stride, W * stride
-    pl = Plan(H, W, dtype, DEV)
-    x = pl._fat(inH, inW, cin)
+    pl = plan_cls(H, W, dtype, DEV)
+    x = pl._fat(inH, inW, cin, batch)
     x.copy_(torch.randn(x.shape, device=DEV))
-    out = pl._fat(H, W, cout)
-    res = pl._fat(H, W, cout)
+    out = pl._fat(H, W, cout, batch)
+    res = pl._fat(H, W, cout, batch)
     res.copy_(torch.randn(res.shape, device=DEV))
     wt = torch.randn(cout, cin, kh, kw) * (1.0 / (cin * kh * kw) ** 0.5)
     bs = torch.randn(cout) * 0.1
     seg = []
     pl.conv(seg, 'case', [pl.fsrc(x, 0)], [_Dst(pl.fview(out), range(cout), act, res=pl.fview(res) if with_res else None)],
-            H, W, stride=stride, weight=wt, bias=bs)
+            H, W, stride=stride, batch=batch, weight=wt, bias=bs)
     pl._upload()
-    pl.launch_conv(0, _stream())
+    _launch(pl, rec, 'conv', (0,), [out], _stream())
     torch.cuda.synchronize()
-    xin = x[0].permute(2, 0, 1).float().cpu()[None]
+    if rec is not None and rec.launch_only:
+        return
+    xin = x.permute(0, 3, 1, 2).float().cpu()
     wq = wt.half().float() if dtype == torch.float16 else wt
     pad = (1, 1) if stride == 2 else (kh // 2, kw // 2)
-    ref = torch.nn.functional.conv2d(xin.double(), wq.double(), bs.double(), stride=stride, padding=pad)[0]
+    ref = torch.nn.functional.conv2d(xin.double(), wq.double(), bs.double(), stride=stride, padding=pad)
     if with_res:
-        ref = ref + res[0].permute(2, 0, 1).double().cpu()
+        ref = ref + res.permute(0, 3, 1, 2).double().cpu()
     ref = {L.ACT_NONE: lambda z: z, L.ACT_RELU: torch.relu, L.ACT_TANH: torch.tanh, L.ACT_SIGMOID: torch.sigmoid}[act](ref)
-    got = out[0].permute(2, 0, 1).double().cpu()
+    got = out.permute(0, 3, 1, 2).double().cpu()
     # fp32 path: exact-fp32 MFMA, only summation order differs from the fp64 reference;
     # fp16 path: inputs/weights identical fp16 values, fp32 accumulate, fp16 rounding of the stored result.
     tol = 2e-5 if dtype == torch.float32 else 4e-3
@@ -115,10 +126,15 @@ def test_fused_resblock_vs_two_launches_and_torch(case):
     of the intermediate), conv2 accumulates onto bias + identity instead of adding the identity last, i.e. at most one fp16 ulp
     apart -- and (ii) an fp64 torch reference of the block that rounds the intermediate to fp16 like both forms do.  The scratch
     buffer of the two-launch form must stay untouched by the fused launch."""
+    _fused_resblock(Plan, case)
+
+
+def _fused_resblock(plan_cls, case, rec=None):
     H, W, B = case
     torch.manual_seed(H * 7 + W)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     x, t, y2, y1 = (pl._fat(H, W, 64, B) for _ in range(4))
+    t.zero_()                                                  # the scratch buffer of the two-launch form
     x.copy_(torch.randn(x.shape, device=DEV))
     w1 = torch.randn(64, 64, 3, 3) * (1.0 / 24.0)
     w2 = torch.randn(64, 64, 3, 3) * (1.0 / 24.0)
@@ -131,12 +147,15 @@ def test_fused_resblock_vs_two_launches_and_torch(case):
     pl._upload()
     assert pl.lib.demfi_resblock_eligible(C.byref(pl._descs[0]), C.byref(pl._descs[2])) == 1
     assert pl.lib.demfi_resblock_eligible(C.byref(pl._descs[1]), C.byref(pl._descs[2])) == 0      # not a block: no ReLU / wrong chaining
-    pl.launch_resblock(0, 2, _stream())
+    _launch(pl, rec, 'resblock', (0, 2), [y1], _stream())
     torch.cuda.synchronize()
     assert float(t.abs().max()) == 0.0                         # the intermediate never went to memory
-    pl.launch_conv(0, _stream())
-    pl.launch_conv(1, _stream())
+    _prefill(pl, t)
+    _launch(pl, rec, 'conv', (0,), [t], _stream())
+    _launch(pl, rec, 'conv', (1,), [y2], _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     got, two = y1.float().cpu(), y2.float().cpu()
     assert torch.isfinite(got).all()
     # (ii) fp64 reference with the fp16 intermediate
@@ -160,8 +179,12 @@ def test_rdb_growth_conv_streamed_weights(H, W, q):
     1152-channel GFF input, the growth buffer), ragged edges, several tiles per workgroup (133 x 530), against an fp64 convolution of the
     same fp16 operands.  Since round 6 these shapes run on wsconv.hip's 32-cout form (64-byte records, one 32-cout block per work item);
     the 3x3 / 32-cout instantiation of the streamed-weight kernel (conv_wstream.hip) only takes the shapes wsconv.hip declines."""
+    _rdb_growth_conv(Plan, H, W, q)
+
+
+def _rdb_growth_conv(plan_cls, H, W, q, rec=None):
     torch.manual_seed(H + W + q)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     cat = pl._fat(H, W, 1152)
     grow = pl._fat(H, W, 128)
     cat.copy_(torch.randn(cat.shape, device=DEV) * 0.5)
@@ -175,8 +198,11 @@ def test_rdb_growth_conv_streamed_weights(H, W, q):
     d = pl._descs[0]
     assert d.rec_bytes == 64 and d.cout_perm == 1 and d.n_chunks == 3 + q      # the shape the streamed-weight kernel owns
     pl._upload()
-    pl.launch_conv(0, _stream())
+    _prefill(pl, grow[..., 32 * q:32 * q + 32])                 # a guarded plan: poison in the channel range the launch writes, and only there
+    _launch(pl, rec, 'conv', (0,), [(grow, 32 * q, 32 * q + 32)], _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     xin = torch.cat([cat[0, :, :, 192:288], g0[0, :, :, :32 * q]], 2).permute(2, 0, 1).double().cpu()[None]
     ref = torch.relu(torch.nn.functional.conv2d(xin, wt.half().double(), bs.double(), padding=1))[0]
     got = grow[0, :, :, 32 * q:32 * q + 32].permute(2, 0, 1).double().cpu()
@@ -212,9 +238,13 @@ def test_persistent_conv_needs_its_cout_order():
 @pytest.mark.parametrize('dtype', [torch.float32, torch.float16])
 def test_conv_multi_piece_routing_upsample_shuffle(dtype):
     """Mixed fat/thin/upsampled inputs, PixelShuffle store, planar outputs with residual, GRU modes."""
+    _conv_multi_piece_routing(Plan, dtype)
+
+
+def _conv_multi_piece_routing(plan_cls, dtype, rec=None):
     torch.manual_seed(5)
     H, W = 16, 32
-    pl = Plan(H, W, dtype, DEV)
+    pl = plan_cls(H, W, dtype, DEV)
     a = pl._fat(H, W, 32)
     lo = pl._fat(H // 2, W // 2, 16)
     th = pl._thin(5)
@@ -253,9 +283,11 @@ def test_conv_multi_piece_routing_upsample_shuffle(dtype):
     pl.conv(seg, 'q', [pl.fsrc(rh, 0), pl.fsrc(xx, 64)],
             [_Dst(pl.fview(hn), range(64), mode=L.MODE_GRU, res=pl.fview(h), aux=pl.fview(zb))], H, W, weight=wq, bias=bq)
     pl._upload()
-    for i in range(4):
-        pl.launch_conv(i, _stream())
+    for i, written in enumerate(([o_fat, o_thin], [ps_out], [zb, rh], [hn])):
+        _launch(pl, rec, 'conv', (i,), written, _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     q = (lambda z: z.half().float()) if dtype == torch.float16 else (lambda z: z)
     tol = 1e-4 if dtype == torch.float32 else 1e-2
     F = torch.nn.functional
@@ -292,9 +324,13 @@ NARROW_CASES = [
 def test_narrow_persistent_conv(case, H, W, batch):
     """3x3 layers with <= 64 input channels (Mixer, DeMFInet.py:800-836) through the narrow persistent kernel:
     record sizes 32 / 64 / 128 B, two-piece records, zero-padded records, ragged tile edges, batch > 1."""
+    _narrow_persistent_conv(Plan, case, H, W, batch)
+
+
+def _narrow_persistent_conv(plan_cls, case, H, W, batch, rec=None):
     pieces, cout, res, act = case
     torch.manual_seed(3)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     srcs, xs, cin = [], [], 0
     for pc in pieces:
         if pc == 'p8':
@@ -320,9 +356,11 @@ def test_narrow_persistent_conv(case, H, W, batch):
             weight=wt, bias=bs)
     pl._upload()
     for rep in range(2):
-        out.zero_()
-        pl.launch_conv(0, _stream())
+        _prefill(pl, out, 0.0)
+        _launch(pl, rec, 'conv', (0,), [out], _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     F = torch.nn.functional
     nchw = lambda t: t.permute(0, 3, 1, 2).double().cpu()
     ref = F.conv2d(torch.cat([nchw(x) for x in xs], 1), wt.half().double(), bs.double(), padding=1)
@@ -340,8 +378,12 @@ def test_narrow_persistent_conv_7x7(H, W):
     resident weights, one 16-channel k-step per tap, 14x38-pixel tiles) instead of the general kernel's 49 per-tap barriers.  Round 6: the chunk
     [8-channel piece | 8 zero channels] of this test (and of the plan) takes the PAIRED-TAP mode -- the upper-half lanes of the B operand read the next
     column, one MFMA covers the taps (ky, 2j) and (ky, 2j + 1): 28 k-steps instead of 49, four DMA waves."""
+    _narrow_persistent_conv_7x7(Plan, H, W)
+
+
+def _narrow_persistent_conv_7x7(plan_cls, H, W, rec=None):
     torch.manual_seed(5)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     b = pl._fat(H, W, 8)
     b.copy_(torch.randn(b.shape, device=DEV))
     out = pl._fat(H, W, 32)
@@ -350,9 +392,11 @@ def test_narrow_persistent_conv_7x7(H, W):
     pl.conv([], 'delta1', [pl.fsrc_map(b, [0, 1, 2, 3, 4, -1, -1, -1])], [_Dst(pl.fview(out), range(32), L.ACT_RELU)], H, W, weight=wt, bias=bs)
     pl._upload()
     for rep in range(2):
-        out.zero_()
-        pl.launch_conv(0, _stream())
+        _prefill(pl, out, 0.0)
+        _launch(pl, rec, 'conv', (0,), [out], _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     nchw = lambda t: t.permute(0, 3, 1, 2).double().cpu()
     ref = torch.relu(torch.nn.functional.conv2d(nchw(b[..., :5]), wt.half().double(), bs.double(), padding=3))
     err = (nchw(out) - ref).abs().max().item()
@@ -367,8 +411,12 @@ def test_streamed_weight_conv_7x7_192_to_64(H, W, batch, act):
     A fragments straight from the packed weights in L2, 32-channel activation units through a double buffer) against torch on
     tiles that are interior, ragged at both edges, several per workgroup sequence, and with a batch stride.  The three pieces
     are channel slices of ONE 192-channel NHWC buffer, as in the plan."""
+    _streamed_weight_conv_7x7(Plan, H, W, batch, act)
+
+
+def _streamed_weight_conv_7x7(plan_cls, H, W, batch, act, rec=None):
     torch.manual_seed(11)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     b = pl._fat(H, W, 192, batch)
     b.copy_(torch.randn(b.shape, device=DEV))
     out = pl._fat(H, W, 64, batch)
@@ -379,9 +427,11 @@ def test_streamed_weight_conv_7x7_192_to_64(H, W, batch, act):
     assert pl._descs[0].cout_perm == 1, 'the layer must be packed for the streamed-weight kernel'
     pl._upload()
     for rep in range(2):
-        out.fill_(7.0)
-        pl.launch_conv(0, _stream())
+        _prefill(pl, out, 7.0)
+        _launch(pl, rec, 'conv', (0,), [out], _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     nchw = lambda t: t.permute(0, 3, 1, 2).double().cpu()
     big = H * W * batch > 50000                                  # the multi-tile case: fp32 reference on the GPU (a double conv on the CPU takes a minute)
     if big:
@@ -409,11 +459,15 @@ def test_stride2_4x4_conv_by_phases(case, H, W, batch):
     32-channel units -- every tap of every phase against torch's strided convolution (fp64 on the same fp16 operands): interior and
     ragged tiles, odd output sizes (the input is 2H x 2W), a 16-channel tail piece padded to a unit, several 64-cout blocks, a batch
     stride, the NHWC residual, more items than workgroups (184 x 320 x 2)."""
-    pieces, cout, with_res, act = case
-    if H * W * batch > 50000 and cout > 64:
+    if H * W * batch > 50000 and case[1] > 64:
         pytest.skip('the large grid is covered by the 64-cout cases')
+    _stride2_4x4_conv(Plan, case, H, W, batch)
+
+
+def _stride2_4x4_conv(plan_cls, case, H, W, batch, rec=None):
+    pieces, cout, with_res, act = case
     torch.manual_seed(H * 7 + W + cout)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     bufs, srcs, cin = [], [], 0
     for ct, take in pieces:
         b = pl._fat(2 * H, 2 * W, ct, batch)
@@ -437,9 +491,11 @@ def test_stride2_4x4_conv_by_phases(case, H, W, batch):
     assert d.rec_bytes == 64 and d.nco == 2 and d.cout_perm == 1 and d.n_chunks == sum((t + 31) // 32 for _, t in pieces)      # the shape wsconv.hip owns
     pl._upload()
     for rep in range(2):
-        out.fill_(7.0)
-        pl.launch_conv(0, _stream())
+        _prefill(pl, out, 7.0)
+        _launch(pl, rec, 'conv', (0,), [out], _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     xs = []
     for b, take in bufs:
         xs.append(b[..., :9] if take == 16 else b[..., :take])
@@ -474,11 +530,15 @@ def test_conv3x3_over_32_channel_units(case, H, W, batch):
     """Round 6 (wsconv.hip), the 3x3 form: K walked in 32-channel units from several NHWC pieces, some of them read through the x2
     nearest-neighbour upsample of the UNet decoder (DeMFInet.py:592-601: cat[up(d), skip]), 64-cout blocks, optional residual --
     against torch (upsample + conv2d, fp64 on the same fp16 operands) on interior / ragged tiles and more items than workgroups."""
-    pieces, cout, with_res, act = case
-    if H * W * batch > 50000 and cout > 64:
+    if H * W * batch > 50000 and case[1] > 64:
         pytest.skip('the large grid is covered by the 64-cout cases')
+    _conv3x3_over_units(Plan, case, H, W, batch)
+
+
+def _conv3x3_over_units(plan_cls, case, H, W, batch, rec=None):
+    pieces, cout, with_res, act = case
     torch.manual_seed(H * 5 + W + cout)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     srcs, xs, cin = [], [], 0
     for ch, up in pieces:
         b = pl._fat(H // 2, W // 2, ch, batch) if up else pl._fat(H, W, ch, batch)
@@ -497,9 +557,11 @@ def test_conv3x3_over_32_channel_units(case, H, W, batch):
     assert d.rec_bytes == 64 and d.nco == 2 and d.cout_perm == 1 and d.n_chunks == cin // 32
     pl._upload()
     for rep in range(2):
-        out.fill_(7.0)
-        pl.launch_conv(0, _stream())
+        _prefill(pl, out, 7.0)
+        _launch(pl, rec, 'conv', (0,), [out], _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     x = torch.cat(xs, 1)
     if H * W * batch > 50000:
         ref = torch.nn.functional.conv2d(x.float(), wt.half().float().to(DEV), bs.to(DEV), padding=1).double().cpu()
@@ -517,8 +579,12 @@ def test_conv3x3_units_with_a_two_piece_tail(H, W, batch):
     """The fused Dec_first_2 of the fp16 plan (DeMFInet.py:151-158, round 6): units [F_rec lo | F_rec hi | 16 channels of ref16 through a
     channel map + the 8-channel record of the recursion + zero padding], the window-constant partial sum as a residual WITHOUT batch
     stride (one image shared by all time instants), ReLU -- against torch on the same fp16 operands."""
+    _conv3x3_two_piece_tail(Plan, H, W, batch)
+
+
+def _conv3x3_two_piece_tail(plan_cls, H, W, batch, rec=None):
     torch.manual_seed(H + W)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     h = pl._fat(H, W, 64, batch)
     r16 = pl._fat(H, W, 16, batch)
     a8 = pl._fat(H, W, 8, batch)
@@ -539,9 +605,11 @@ def test_conv3x3_units_with_a_two_piece_tail(H, W, batch):
     assert d.rec_bytes == 64 and d.nco == 2 and d.cout_perm == 1 and d.n_chunks == 3 and d.chunks[2].n_pieces == 3
     pl._upload()
     for rep in range(2):
-        out.fill_(7.0)
-        pl.launch_conv(0, _stream())
+        _prefill(pl, out, 7.0)
+        _launch(pl, rec, 'conv', (0,), [out], _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     x = torch.zeros(batch, cin, H, W, dtype=torch.float16, device=DEV)
     x[:, :64] = h.permute(0, 3, 1, 2)
     for ch, ci in enumerate(m16):
@@ -569,15 +637,21 @@ THIN_CASES = [
 def test_narrow_persistent_conv_thin_outputs(case, H, W):
     """3x3 layers writing planar fp32 outputs (frames, flow/occlusion deltas, gates) through the THIN epilogue of the narrow
     persistent kernel: per-octet routing to several tensors, planar residuals, batch stride, ragged edges."""
+    _narrow_thin_outputs(Plan, case, H, W)
+
+
+def _narrow_thin_outputs(plan_cls, case, H, W, rec=None):
     cin, dsts, act, batch = case
     torch.manual_seed(17)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     x = pl._fat(H, W, cin, batch)
     x.copy_(torch.randn(x.shape, device=DEV))
     outs, ress, D, c0 = [], [], [], 0
     for n, has_res in dsts:
-        o = torch.zeros((batch * n, H, W), dtype=torch.float32, device=DEV)
-        r = torch.randn((batch * n, H, W), dtype=torch.float32, device=DEV) if has_res else None
+        o = pl._thin(batch * n, H, W)
+        r = pl._thin(batch * n, H, W) if has_res else None
+        if has_res:
+            r.copy_(torch.randn((batch * n, H, W), dtype=torch.float32, device=DEV))
         outs.append(o)
         ress.append(r)
         sb = n * H * W if batch > 1 else 0
@@ -590,9 +664,11 @@ def test_narrow_persistent_conv_thin_outputs(case, H, W):
     pl._upload()
     for rep in range(2):
         for o in outs:
-            o.fill_(-77.0)
-        pl.launch_conv(0, _stream())
+            _prefill(pl, o, -77.0)
+        _launch(pl, rec, 'conv', (0,), outs, _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     F = torch.nn.functional
     ref = F.conv2d(x.permute(0, 3, 1, 2).double().cpu(), wt.half().double(), bs.double(), padding=1)
     fn = {L.ACT_NONE: lambda z: z, L.ACT_TANH: torch.tanh, L.ACT_SIGMOID: torch.sigmoid}[act]
@@ -600,9 +676,9 @@ def test_narrow_persistent_conv_thin_outputs(case, H, W):
     for (n, has_res), o, r in zip(dsts, outs, ress):
         e = ref[:, c0:c0 + n]
         if has_res:
-            e = e + r.view(batch, n, H, W).double().cpu()
+            e = e + r.reshape(batch, n, H, W).double().cpu()
         e = fn(e)
-        got = o.view(batch, n, H, W).double().cpu()
+        got = o.reshape(batch, n, H, W).double().cpu()
         err = (got - e).abs().max().item()
         assert err < 4e-3 * max(1.0, e.abs().max().item()), (case, err)
         c0 += n
@@ -615,36 +691,52 @@ def test_thin_outputs_with_packed_copy(dsts, pack_ch, H, W, batch):
     demfi_pack_planes launch over the fp32 planes produces (the per-recursion pack of the flow / occlusion deltas,
     DeMFInet.py:130-137 -> Mixer.conv_delta1, is gone from the plan).  Shapes: flow_occ.conv2 (5 channels straddling the lane
     halves), dec3's plane launches (4 + 1 in two octets), an octet that is not packed; channels nobody writes keep their value."""
+    _thin_outputs_with_packed_copy(Plan, dsts, pack_ch, H, W, batch)
+
+
+def _thin_outputs_with_packed_copy(plan_cls, dsts, pack_ch, H, W, batch, rec=None):
     torch.manual_seed(23)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     x = pl._fat(H, W, 32, batch)
     x.copy_(torch.randn(x.shape, device=DEV))
-    rec = pl._fat(H, W, 16, batch)
+    pk = pl._fat(H, W, 16, batch)
     outs, ress, D, c0 = [], [], [], 0
     for n, has_res in dsts:
-        o = torch.zeros((batch * n, H, W), dtype=torch.float32, device=DEV)
-        r = torch.randn((batch * n, H, W), dtype=torch.float32, device=DEV) if has_res else None
+        o = pl._thin(batch * n, H, W)
+        r = pl._thin(batch * n, H, W) if has_res else None
+        if has_res:
+            r.copy_(torch.randn((batch * n, H, W), dtype=torch.float32, device=DEV))
         outs.append(o)
         ress.append(r)                                   # the descriptor holds a raw pointer: the residual must stay alive
         sb = n * H * W if batch > 1 else 0
         D.append(_Dst(pl.tview(o, 0, sb=sb), range(c0, c0 + n), L.ACT_NONE, res=pl.tview(r, 0, sb=sb) if has_res else None))
         c0 += n
     wt = torch.randn(c0, 32, 3, 3) * (1.0 / (32 * 9) ** 0.5)
-    pl.conv([], 'thinpack', [pl.fsrc(x, 0)], D, H, W, batch=batch, weight=wt, bias=torch.randn(c0) * 0.1, pack=(pl.fview(rec), pack_ch))
+    pl.conv([], 'thinpack', [pl.fsrc(x, 0)], D, H, W, batch=batch, weight=wt, bias=torch.randn(c0) * 0.1, pack=(pl.fview(pk), pack_ch))
     pl._upload()
+    packed = [(pk, chn, chn + (n + 3) // 4 * 4) for (n, _), chn in zip(dsts, pack_ch) if chn >= 0]
     for rep in range(2):
-        rec.fill_(-3.0)
-        pl.launch_conv(0, _stream())
+        _prefill(pl, pk, -3.0)
+        for o in outs:
+            _prefill(pl, o)
+        before = pk.cpu()
+        _launch(pl, rec, 'conv', (0,), outs + packed, _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     exp = torch.full((batch, H, W, 16), -3.0, dtype=torch.float16)
+    wrote = torch.zeros(16, dtype=torch.bool)
     for (n, _), o, chn in zip(dsts, outs, pack_ch):
         if chn < 0:
             continue
         n4 = (n + 3) // 4 * 4
         exp[..., chn:chn + n4] = 0.0
-        exp[..., chn:chn + n] = o.view(batch, n, H, W).permute(0, 2, 3, 1).half().cpu()    # the pack kernel's conversion of the stored planes
+        exp[..., chn:chn + n] = o.reshape(batch, n, H, W).permute(0, 2, 3, 1).half().cpu()    # the pack kernel's conversion of the stored planes
+        wrote[chn:chn + n4] = True
         assert torch.isfinite(o).all()
-    assert torch.equal(rec.cpu(), exp)
+    # channels nobody writes keep their value: -3.0 on a plain plan (so this is  rec == exp  there), the poison on a guarded one
+    assert torch.equal(pk.cpu()[..., wrote], exp[..., wrote])
+    assert torch.equal(pk.cpu()[..., ~wrote].view(torch.int16), before[..., ~wrote].view(torch.int16))
 
 
 @pytest.mark.parametrize('kh,kw', [(1, 5), (5, 1)])
@@ -652,8 +744,12 @@ def test_thin_outputs_with_packed_copy(dsts, pack_ch, H, W, batch):
 def test_sep_gru_persistent_kernel(kh, kw, H, W, batch):
     """SepConvGRU half-step (DeMFInet.py:844-849 / 851-856) through the persistent 1x5 / 5x1 kernel: fused z|r launch
     (sigmoid, sigmoid*h) and the q launch ((1-z)h + z tanh), ragged tile edges, batch > 1, both orientations."""
+    _sep_gru_persistent(Plan, kh, kw, H, W, batch)
+
+
+def _sep_gru_persistent(plan_cls, kh, kw, H, W, batch, rec=None):
     torch.manual_seed(11 + kh)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     h, xx = pl._fat(H, W, 64, batch), pl._fat(H, W, 64, batch)
     h.copy_(torch.tanh(torch.randn(h.shape, device=DEV)))
     xx.copy_(torch.randn(xx.shape, device=DEV))
@@ -671,10 +767,13 @@ def test_sep_gru_persistent_kernel(kh, kw, H, W, batch):
             weight=wq, bias=bq)
     pl._upload()
     for rep in range(2):                                   # twice: the launch leaves no state behind
-        zb.zero_(); rh.zero_(); hn.zero_()
-        pl.launch_conv(0, _stream())
-        pl.launch_conv(1, _stream())
+        for o in (zb, rh, hn):
+            _prefill(pl, o, 0.0)
+        _launch(pl, rec, 'conv', (0,), [zb, rh], _stream())
+        _launch(pl, rec, 'conv', (1,), [hn], _stream())
     torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     # float64 references and the per-element bound of tests/epilogue_ref.py (storage + accumulation + evaluation); the q launch reads
     # r*h and z as stored, so they are operands of its reference
     nchw = lambda t: t.permute(0, 3, 1, 2).double().cpu()
@@ -694,8 +793,12 @@ def test_gru_half_step_r_then_zq(kh, kw, H, W, batch):
     (demfi_gru_zq; z stays on chip).  Checked against float64 on the same fp16 operands under the bound of tests/epilogue_ref.py and against the round-5 path (the same three
     layers through demfi_conv2d: equal up to the summation order of the fp32 accumulators).  Ragged tiles in both directions, batch > 1,
     tiles that straddle the image along the filter axis (lines) and across it (pixels)."""
+    _gru_half_step(Plan, kh, kw, H, W, batch)
+
+
+def _gru_half_step(plan_cls, kh, kw, H, W, batch, rec=None):
     torch.manual_seed(23 + kh)
-    pl = Plan(H, W, torch.float16, DEV)
+    pl = plan_cls(H, W, torch.float16, DEV)
     h, xx = pl._fat(H, W, 64, batch), pl._fat(H, W, 64, batch)
     h.copy_(torch.tanh(torch.randn(h.shape, device=DEV)))
     xx.copy_(torch.randn(xx.shape, device=DEV))
@@ -720,11 +823,21 @@ def test_gru_half_step_r_then_zq(kh, kw, H, W, batch):
     assert pl.lib.demfi_gru_zq_eligible(C.byref(pl._descs[0]), C.byref(pl._descs[2])) == 0          # r is not an update gate
     assert pl.lib.demfi_gru_r_eligible(C.byref(pl._descs[1])) == 0
     for rep in range(2):                                   # twice: the launches leave no state behind
-        zb.fill_(7.0); rh.zero_(); hn.zero_()
-        pl.launch_gru_r(0, _stream())
-        pl.launch_gru_zq(1, 2, _stream())
+        zb.fill_(7.0)                                       # no destination of the fused launches: a bystander
+        _prefill(pl, rh, 0.0)
+        _prefill(pl, hn, 0.0)
+        _launch(pl, rec, 'gru_r', (0,), [rh], _stream())
+        _launch(pl, rec, 'gru_zq', (1, 2), [hn], _stream())
     torch.cuda.synchronize()
     assert float(zb.min()) == 7.0                           # the fused launch never touches the z buffer
+    # the round-5 launches on the same operands
+    _prefill(pl, zb)
+    _launch(pl, rec, 'conv', (1,), [zb], _stream())         # z -> zb
+    _launch(pl, rec, 'conv', (3,), [rh2], _stream())        # r*h -> rh2
+    _launch(pl, rec, 'conv', (4,), [hn2], _stream())        # -> hn2
+    torch.cuda.synchronize()
+    if rec is not None and rec.launch_only:
+        return
     # float64 references and the per-element bound of tests/epilogue_ref.py.  demfi_gru_zq keeps z in fp32 on chip (it is never rounded
     # to fp16), so the reference does not round it either (epilogue_ref.ref_zq); r*h is read as demfi_gru_r stored it
     nchw = lambda t: t.permute(0, 3, 1, 2).double().cpu()
@@ -736,11 +849,7 @@ def test_gru_half_step_r_then_zq(kh, kw, H, W, batch):
     vz, Sz = E.preact(hx, wz.half(), bz, pad)
     vq, Sq = E.preact(torch.cat([nchw(rh), nchw(xx)], 1), wq.half(), bq, pad)
     E.assert_inside(nchw(hn), E.ref_zq(vz, Sz, vq, Sq, nchw(h), T16), T16, "h'")
-    # against the round-5 launches on the same operands
-    pl.launch_conv(1, _stream())                            # z -> zb
-    pl.launch_conv(3, _stream())                            # r*h -> rh2
-    pl.launch_conv(4, _stream())                            # -> hn2
-    torch.cuda.synchronize()
+    # against the round-5 launches
     assert (rh.float() - rh2.float()).abs().max() < 2e-3
     assert (hn.float() - hn2.float()).abs().max() < 4e-3
 
