@@ -5,6 +5,8 @@
 //   conv_narrow.hip   3x3 / 7x7 over <= 64 channels in one chunk, NHWC or thin outputs      conv_sep.hip   SepConvGRU 1x5 / 5x1 (rounds 1-5; round 6: gru.hip)
 //   conv_wstream.hip  Ch_Reducer 7x7 with streamed weights (+ its 3x3 / 32-cout form)       wsconv.hip     32-channel units, helper-wave DMA (round 6)
 //   resblock.hip      fused residual block                                                  gru.hip        SepConvGRU half-step as r*h, then z + q + blend
+//   conv_common.h     tile constants + shared epilogue of the conv_* units                  kernel_kit.h   static_for, Mma<>, res_mix / sub_mix, the phase trace:
+//                                                                                                          shared by every unit above (resblock, gru, wsconv include it alone)
 // Which kernel owns a layer is decided from the descriptor alone, in ONE place (demfi_conv_owner); demfi_conv_build (conv_build.cpp) shapes a layer for it.
 #include "conv_common.h"
 
@@ -183,10 +185,10 @@ extern "C" int demfi_conv2d(const demfi_conv* h, const demfi_conv* dev, void* st
 }
 
 #ifdef DEMFI_TRACE
-// trace build only: copy the phase trace out (see TRACE_STAMP; one kernel family is traced at a time, the units' buffers are OR-ed) and clear it
+// trace build only: copy the phase trace out (kernel_kit.h: TRACE_STAMP; one kernel family is traced at a time, the units' buffers are OR-ed) and clear it
 extern "C" int demfi_trace_dump(unsigned long long* out, int64_t n)
 {
-    const int64_t have = (int64_t)TR_WGS * TR_WAVES * TR_TILES * TR_STAMPS;
+    const int64_t have = TR_N;
     if (!out || n < have) return demfi_set_error(DEMFI_ERR_ARG, "demfi_trace_dump: need room for %lld entries", (long long)have);
     DEMFI_HIP_CHECK(hipDeviceSynchronize());
     for (int64_t i = 0; i < have; ++i) out[i] = 0;

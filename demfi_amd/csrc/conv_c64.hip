@@ -50,20 +50,8 @@ __global__ __launch_bounds__(NT + 64 * P_NDMA, 1) void conv3x3_c64_persist_kerne
     char* const tbuf = smem + WBYTES;                           // 2 x tile buffer
 
     // tile sequence of this workgroup: XCD x = b & 7 owns the contiguous band [lo, hi) of tile indices
-    const int G = gridDim.x;
     int t_first, t_end, t_step;
-    if ((G & 7) == 0 && total >= G) {
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        const int q = total >> 3, r = total & 7;
-        const int lo = xcd * q + min(xcd, r);
-        t_first = lo + idx;
-        t_end = lo + q + (xcd < r ? 1 : 0);
-        t_step = G >> 3;
-    } else {
-        t_first = blockIdx.x;
-        t_end = total;
-        t_step = G;
-    }
+    XCD_TILE_STRIDE(total, t_first, t_end, t_step);
     if (t_first >= t_end) return;                               // uniform per workgroup
 
     auto tile_coords = [&](int t, int& bimg, int& oy0, int& ox0) {
@@ -356,20 +344,8 @@ __global__ __launch_bounds__(SG_NT, 1) void conv3x3_c64_stg_kernel(const demfi_c
     const int total = tiles_img * d->batch;
     char* const wlds = smem;
     char* const tbuf = smem + WBYTES;
-    const int G = gridDim.x;
     int t_first, t_end, t_step;
-    if ((G & 7) == 0 && total >= G) {
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        const int q = total >> 3, r = total & 7;
-        const int lo = xcd * q + min(xcd, r);
-        t_first = lo + idx;
-        t_end = lo + q + (xcd < r ? 1 : 0);
-        t_step = G >> 3;
-    } else {
-        t_first = blockIdx.x;
-        t_end = total;
-        t_step = G;
-    }
+    XCD_TILE_STRIDE(total, t_first, t_end, t_step);
     if (t_first >= t_end) return;
     auto tile_coords = [&](int t, int& bimg, int& oy0, int& ox0) {
         bimg = t / tiles_img;
@@ -688,7 +664,7 @@ static int launch_stg(const demfi_conv* h, const demfi_conv* dev, hipStream_t st
 
 }  // namespace
 
-DEMFI_TU_TRACE(demfi_c64_trace_collect)
+int demfi_c64_trace_collect(unsigned long long* acc) { return TRACE_DRAIN(acc, true); }
 
 int demfi_c64_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st)
 {

@@ -1,76 +1,22 @@
 // Shared device helpers of the convolution kernels (conv_general.hip, conv_c64.hip, conv_narrow.hip, conv_sep.hip, conv_wstream.hip):
-// tile constants, the MFMA wrappers, the epilogue the general and the 32-cout persistent kernel share, and -- trace build only -- the
-// per-translation-unit phase-trace buffer (each unit has its own copy; conv.hip collects them).
+// tile constants, 8-channel loads / stores, the epilogue the general and the 32-cout persistent kernel share, and -- trace build only --
+// the per-translation-unit phase-trace buffer (each unit has its own copy; conv.hip collects them).  The loop, MFMA, fp16-mix and trace
+// primitives themselves are kernel_kit.h's, which resblock.hip, gru.hip and wsconv.hip share.
 #pragma once
-#include "common.h"
+#include "kernel_kit.h"
 #include "conv_kernels.h"
-#include <type_traits>
 #include <stdlib.h>
 
 namespace {
 
-
-// In-kernel phase trace (libdemfi_hip_trace.so, build.sh --trace; never in the product): s_memtime stamps of the first
-// TR_TILES tiles of workgroups 0..TR_WGS-1, [wg][wave][tile][stamp].  MFMA waves: 0 = arrived at barrier A, 1 = released,
-// 2 = MFMA phase done, 3 = epilogue issued.  DMA waves: 0 = tile landed (vmcnt 0), 1 = released, 2 = next tile issued.
-#ifdef DEMFI_TRACE
-constexpr int TR_WGS = 32, TR_WAVES = 10, TR_TILES = 24, TR_STAMPS = 6;
-__device__ unsigned long long g_trace[TR_WGS * TR_WAVES * TR_TILES * TR_STAMPS];
-#define TRACE_STAMP(wave_, k_, i_)                                                                                  \
-    do {                                                                                                              \
-        if (blockIdx.x < TR_WGS && (k_) < TR_TILES && (threadIdx.x & 63) == 0)                                      \
-            g_trace[((blockIdx.x * TR_WAVES + (wave_)) * TR_TILES + (k_)) * TR_STAMPS + (i_)] = __builtin_readcyclecounter(); \
-    } while (0)
-#else
-#define TRACE_STAMP(wave_, k_, i_) do { } while (0)
-#endif
+// Phase trace of these units: the first 24 tiles of workgroups 0..31, [wg][wave][tile][stamp].  MFMA waves: 0 = arrived at barrier A,
+// 1 = released, 2 = MFMA phase done, 3 = epilogue issued.  DMA waves: 0 = tile landed (vmcnt 0), 1 = released, 2 = next tile issued.
+DEMFI_TRACE_BUFFER(32, 10, 24, 6)
 
 constexpr int TH = 8;
 constexpr int TW = 32;
 constexpr int NT = 256;
 constexpr int REC_PAD = 16;
-
-template <typename T> struct Mma;
-
-template <> struct Mma<half_t> {
-    static __device__ __forceinline__ void run(f16x_t& acc, const uint4& a, const uint4& b)
-    {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b),
-                                                     acc, 0, 0, 0);
-    }
-    // first MFMA of an accumulator with an explicit C operand (the bias rows: saves the epilogue's bias adds)
-    static __device__ __forceinline__ void initc(f16x_t& acc, const uint4& a, const uint4& b, const f16x_t& c)
-    {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), c, 0, 0, 0);
-    }
-    // first MFMA of an accumulator: C = inline constant 0 instead of 16 v_mov per accumulator before the loop
-    static __device__ __forceinline__ void init(f16x_t& acc, const uint4& a, const uint4& b)
-    {
-        const f16x_t z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), z, 0, 0, 0);
-    }
-};
-template <> struct Mma<float> {
-    static __device__ __forceinline__ void run(f16x_t& acc, const uint4& a, const uint4& b)
-    {
-        f4_t fa = __builtin_bit_cast(f4_t, a), fb = __builtin_bit_cast(f4_t, b);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[0], fb[0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[1], fb[1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[2], fb[2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[3], fb[3], acc, 0, 0, 0);
-    }
-};
-
-// Compile-time loop: the accumulator arrays must only ever be indexed by constants (runtime-indexed
-// ext_vector arrays go to scratch), and '#pragma unroll' is refused on the large epilogue body.
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 constexpr int STAGE_LD = 36;          // floats per staged pixel row: 32 couts + 4 pad (144 B, conflict-light b128)
 
@@ -295,57 +241,7 @@ __device__ __forceinline__ void conv_epilogue(const demfi_conv* __restrict__ d, 
 // second launch_bounds argument = minimum waves per SIMD: 2-3 resident workgroups per CU let one workgroup's
 // tile staging overlap another's MFMA phase.
 
-// (fp16 half of a packed pair) * 1.0 + c in one VALU op: the residual add of the epilogue
-__device__ __forceinline__ float res_mix_lo(unsigned a, float c)
-{
-    float d = 0.0f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
-#endif
-    return d;
-}
-__device__ __forceinline__ float res_mix_hi(unsigned a, float c)
-{
-    float d = 0.0f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
-#endif
-    return d;
-}
-// c - (fp16 half of a packed pair) in one VALU op (no v_cvt_f32_f16): the GRU update's tanh(.) - h
-__device__ __forceinline__ float sub_mix_lo(float c, unsigned a)
-{
-    float d = 0.0f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
-#endif
-    return d;
-}
-__device__ __forceinline__ float sub_mix_hi(float c, unsigned a)
-{
-    float d = 0.0f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
-#endif
-    return d;
-}
 // one k-step's fragments of the 64-channel kernels (conv_c64.hip, conv_sep.hip)
 template <int NCO> struct FragSet { uint4 a[2][NCO]; uint4 b[2][2]; };
 
 }  // namespace
-
-// trace build: this unit's trace buffer behind a function conv.hip can call (device globals are per translation unit)
-#ifdef DEMFI_TRACE
-#define DEMFI_TU_TRACE(fn)                                                                                  \
-    int fn(unsigned long long* acc)                                                                         \
-    {                                                                                                       \
-        constexpr int64_t have = (int64_t)TR_WGS * TR_WAVES * TR_TILES * TR_STAMPS;                         \
-        static unsigned long long tmp[have], zeros[have];                                                   \
-        DEMFI_HIP_CHECK(hipMemcpyFromSymbol(tmp, HIP_SYMBOL(g_trace), have * 8));                           \
-        for (int64_t i = 0; i < have; ++i) acc[i] |= tmp[i];                                                \
-        DEMFI_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_trace), zeros, have * 8));                           \
-        return 0;                                                                                           \
-    }
-#else
-#define DEMFI_TU_TRACE(fn) int fn(unsigned long long*) { return 0; }
-#endif

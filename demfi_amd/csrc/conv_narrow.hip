@@ -112,20 +112,8 @@ __global__ __launch_bounds__(NT + 64 * NDMA, 1) void conv3x3_narrow_persist_kern
     const int total = tiles_img * d->batch;
     char* const wlds = smem;
     char* const tbuf = smem + WBYTES;
-    const int G = gridDim.x;
     int t_first, t_end, t_step;
-    if ((G & 7) == 0 && total >= G) {
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        const int q = total >> 3, r = total & 7;
-        const int lo = xcd * q + min(xcd, r);
-        t_first = lo + idx;
-        t_end = lo + q + (xcd < r ? 1 : 0);
-        t_step = G >> 3;
-    } else {
-        t_first = blockIdx.x;
-        t_end = total;
-        t_step = G;
-    }
+    XCD_TILE_STRIDE(total, t_first, t_end, t_step);
     if (t_first >= t_end) return;                               // uniform per workgroup
     const int n_tiles = (t_end - t_first + t_step - 1) / t_step;
     auto tile_coords = [&](int t, int& bimg, int& oy0, int& ox0) {
@@ -737,7 +725,7 @@ int launch_narrow(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, bo
 
 }  // namespace
 
-DEMFI_TU_TRACE(demfi_narrow_trace_collect)
+int demfi_narrow_trace_collect(unsigned long long* acc) { return TRACE_DRAIN(acc, true); }
 
 // thin: the planar fp32 epilogue (conv.hip, demfi_conv_owner, sends here only the shapes instantiated below)
 int demfi_narrow_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, bool thin)

@@ -418,7 +418,7 @@ static int launch_sep(const demfi_conv* h, const demfi_conv* dev, hipStream_t st
 
 }  // namespace
 
-DEMFI_TU_TRACE(demfi_sep_trace_collect)
+int demfi_sep_trace_collect(unsigned long long* acc) { return TRACE_DRAIN(acc, true); }
 
 bool demfi_sep_eligible(const demfi_conv* h) { return sep_eligible(h); }
 

@@ -307,7 +307,7 @@ static int launch_wstream(const demfi_conv* h, const demfi_conv* dev, hipStream_
 
 }  // namespace
 
-DEMFI_TU_TRACE(demfi_wstream_trace_collect)
+int demfi_wstream_trace_collect(unsigned long long* acc) { return TRACE_DRAIN(acc, true); }
 
 bool demfi_wstream_eligible(const demfi_conv* h, int ks, int nch) { return wstream_eligible(h, ks, nch); }
 int demfi_wstream_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st) { return launch_wstream(h, dev, st); }

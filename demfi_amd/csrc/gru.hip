@@ -22,10 +22,8 @@
 // with h prefetched from global) stages h' as fp16 in the x piece (dead by then); the helper waves store it as whole 128-byte lines
 // (streaming) and issue the DMA.
 // R: tile = 32 pixels x 16 lines, wave = cout half x line half, pieces x | h of 20 lines (160 KiB), sigmoid * h from the h window.
-#include "common.h"
+#include "kernel_kit.h"
 #include <cstdlib>
-#include <type_traits>
-#include <vector>
 
 namespace {
 
@@ -47,51 +45,8 @@ constexpr int ZS_D = 8;                                          // ZQS: A ring 
 constexpr int ZS_NA = 80;                                        // ZQS: A fragments per tile and wave: 20 (z . h) + 20 (q . r*h) + 40 (z, q alternating . x)
 static_assert(ZS_NA % ZS_D == 0, "static ring indices");
 
-#ifdef DEMFI_TRACE
-constexpr int GT_WGS = 32, GT_WAVES = 8, GT_TILES = 24, GT_STAMPS = 10;
-__device__ unsigned long long g_gru_trace[GT_WGS * GT_WAVES * GT_TILES * GT_STAMPS];
-#define G_STAMP(wave_, k_, i_)                                                                                        \
-    do {                                                                                                              \
-        if (blockIdx.x < GT_WGS && (k_) < GT_TILES && (threadIdx.x & 63) == 0)                                        \
-            g_gru_trace[((blockIdx.x * GT_WAVES + (wave_)) * GT_TILES + (k_)) * GT_STAMPS + (i_)] = __builtin_readcyclecounter(); \
-    } while (0)
-#else
-#define G_STAMP(wave_, k_, i_) do { } while (0)
-#endif
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void g_for(F&& f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        g_for<I + 1, N>(f);
-    }
-}
-__device__ __forceinline__ void g_mma(f16x_t& acc, const uint4& a, const uint4& b)
-{
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), acc, 0, 0, 0);
-}
-__device__ __forceinline__ void g_mma_c(f16x_t& acc, const uint4& a, const uint4& b, const f16x_t& c)
-{
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), c, 0, 0, 0);
-}
-// c - (fp16 half of a packed pair) in one VALU op: tanh(.) - h
-__device__ __forceinline__ float g_sub_lo(float c, unsigned a)
-{
-    float d = 0.0f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
-#endif
-    return d;
-}
-__device__ __forceinline__ float g_sub_hi(float c, unsigned a)
-{
-    float d = 0.0f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
-#endif
-    return d;
-}
+// Phase trace (trace build only): the first 24 tiles of workgroups 0..31, [wg][wave][tile][stamp]; tools/gru_trace.py prints the phase means.
+DEMFI_TRACE_BUFFER(32, 8, 24, 10)
 
 // c - b * (fp16 half of a packed pair): (b - 1) - (b + 1) h
 __device__ __forceinline__ float g_nfma_lo(float b, unsigned h, float c)
@@ -166,22 +121,10 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int per_img = a.n_pt * a.n_ls;
     const int total = per_img * a.batch;
+    // contiguous run of items (image, tile across, step along -- along fastest) per workgroup; the workgroups of an XCD
+    // (blockIdx % 8) share a contiguous band, so the 4 halo lines two consecutive steps share meet in one L2
     int it0, it1;
-    {
-        // contiguous run of items (image, tile across, step along -- along fastest) per workgroup; the workgroups of an XCD
-        // (blockIdx % 8) share a contiguous band, so the 4 halo lines two consecutive steps share meet in one L2
-        const int G = gridDim.x;
-        if ((G & 7) == 0 && total >= G) {
-            const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, nw = G >> 3;
-            const int q = total >> 3, r = total & 7;
-            const int lo = xcd * q + min(xcd, r), n = q + (xcd < r ? 1 : 0);
-            it0 = lo + (int)(((int64_t)n * idx) / nw);
-            it1 = lo + (int)(((int64_t)n * (idx + 1)) / nw);
-        } else {
-            it0 = (int)(((int64_t)total * blockIdx.x) / G);
-            it1 = (int)(((int64_t)total * (blockIdx.x + 1)) / G);
-        }
-    }
+    XCD_ITEM_RUN(total, it0, it1);
     if (it0 >= it1) return;                                      // uniform per workgroup
     auto pos_of = [&](int it, int& img, int& P0, int& L0) {
         img = it / per_img;
@@ -286,13 +229,13 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
             };
             // loads and stores count together, in order
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NIW) : "memory");      // the first tile's h, r*h have landed (x may be in flight)
-            G_STAMP(wave, trk, 0);
+            TRACE_STAMP(wave, trk, 0);
             asm volatile("s_barrier" ::: "memory");             // A0
             for (;;) {
                 // the MFMA waves are in phase A of this tile; this tile's x was issued behind barrier E of the previous one
                 const bool more = it + 1 < it1;
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // x has landed (older: the stores of tile k - 2)
-                G_STAMP(wave, trk, 1);
+                TRACE_STAMP(wave, trk, 1);
                 asm volatile("s_barrier" ::: "memory");         // B: x has landed; every MFMA wave is done with h, r*h
                 int nimg = img, nP0 = P0, nL0 = L0;
                 bool carry = false;
@@ -301,16 +244,16 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
                     carry = nimg == img && nP0 == P0 && nL0 == L0 + TL;
                     issue_piece(a.h, S0, nimg, nP0, nL0, carry);
                 }
-                G_STAMP(wave, trk, 2);
+                TRACE_STAMP(wave, trk, 2);
                 asm volatile("s_barrier" ::: "memory");         // C: every MFMA wave is done with x
                 // ... r*h (8) under the sigmoid / tanh pass.  Both there (16) delay barrier D by ~1 400 cycles: measured, profiles/r06_notes.md
                 if (more) issue_piece(a.rh, S1, nimg, nP0, nL0, carry);
-                G_STAMP(wave, trk, 3);
+                TRACE_STAMP(wave, trk, 3);
                 bool exact = false;
                 if (have_prev) exact = do_stores(pimg, pP0, pL0);                          // the previous tile's outputs (8 stores) under the blend
                 if (exact) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TL) : "memory");      // the next tile's h, r*h (older than the stores) have landed:
                 else       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // E tells the MFMA waves
-                G_STAMP(wave, trk, 4);
+                TRACE_STAMP(wave, trk, 4);
                 asm volatile("s_barrier" ::: "memory");         // E: h' is staged
                 {
                     const char* sbp = S2 + dw * 1024 + lane * 16;
@@ -320,7 +263,7 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
                 }
                 // this helper's DMA instructions overwrite exactly the chunks it has just read
                 if (more) issue_piece(a.x, S2, nimg, nP0, nL0, carry);   // lines 8 .. 11 of the x piece survived the staging (lines 0 .. 7)
-                G_STAMP(wave, trk, 5);
+                TRACE_STAMP(wave, trk, 5);
                 ++trk;
                 have_prev = true; pimg = img; pP0 = P0; pL0 = L0;
                 if (!more) break;
@@ -336,10 +279,10 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
                 // outstanding, in order: x | h  ->  x has landed when only h's instructions are left
                 if (h_carried) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NIW - 4) : "memory");
                 else           asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NIW) : "memory");
-                G_STAMP(wave, trk, 0);
+                TRACE_STAMP(wave, trk, 0);
                 asm volatile("s_barrier" ::: "memory");         // A: x has landed
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                G_STAMP(wave, trk, 1);
+                TRACE_STAMP(wave, trk, 1);
                 asm volatile("s_barrier" ::: "memory");         // B: h has landed; every MFMA wave is done with x
                 int nimg = img, nP0 = P0, nL0 = L0;
                 bool carry = false;
@@ -348,11 +291,11 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
                     carry = nimg == img && nP0 == P0 && nL0 == L0 + TL;
                     issue_piece(a.x, S0, nimg, nP0, nL0, carry);
                 }
-                G_STAMP(wave, trk, 2);
+                TRACE_STAMP(wave, trk, 2);
                 asm volatile("s_barrier" ::: "memory");         // C: epilogues done, h is free
                 if (more) issue_piece(a.h, S1, nimg, nP0, nL0, carry);
                 h_carried = carry;
-                G_STAMP(wave, trk, 3);
+                TRACE_STAMP(wave, trk, 3);
                 ++trk;
                 if (!more) break;
                 ++it; img = nimg; P0 = nP0; L0 = nL0;
@@ -399,10 +342,10 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
         uint4 A[ZS_D];
         uint4 B[8];
         f16x_t accz[4], accq[4];
-        auto prime = [&]() { g_for<0, ZS_D>([&](auto T) { A[decltype(T)::value] = a_loadn(T); }); };
+        auto prime = [&]() { static_for<0, ZS_D>([&](auto T) { A[decltype(T)::value] = a_loadn(T); }); };
         auto b_init = [&](const char* tb) {
             const int o = boff(std::integral_constant<int, 0>{});
-            g_for<0, 4>([&](auto R) { B[decltype(R)::value] = *(const uint4*)(tb + decltype(R)::value * G_LS + o); });
+            static_for<0, 4>([&](auto R) { B[decltype(R)::value] = *(const uint4*)(tb + decltype(R)::value * G_LS + o); });
         };
         // one 64-channel window: 4 k-steps x 5 taps; WHICH = 0: z (4 MFMAs per step), 1: q, 2: both (8 MFMAs, two A fragments).  This wave's
         // B window = lines tb + 0 .. 7: step (ks, tap) multiplies output line p with line tap + p; line 4 + tap arrives during tap; during tap 4
@@ -411,7 +354,7 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
             constexpr int NB = decltype(NB_)::value, WHICH = decltype(WHICH_)::value;
             constexpr bool DUAL = WHICH == 2, HASNEXT = decltype(HASNEXT_)::value;
             constexpr int PER = DUAL ? 2 : 1;
-            g_for<0, G_NSTEP>([&](auto T_) {
+            static_for<0, G_NSTEP>([&](auto T_) {
                 constexpr int t = decltype(T_)::value;
                 constexpr int ks = t / 5, tap = t % 5;
                 constexpr int n0 = NB + t * PER, n1 = n0 + PER - 1;
@@ -423,15 +366,15 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
                 if constexpr (LA1) A[n1 % ZS_D] = a_loadn(std::integral_constant<int, LA1 ? n1 + ZS_D : 0>{});
                 constexpr bool NXT = tap == 4 && (ks < 3 || HASNEXT);
                 const f16x_t zero = {};
-                g_for<0, 4>([&](auto P) {
+                static_for<0, 4>([&](auto P) {
                     constexpr int p = decltype(P)::value;
                     if constexpr (WHICH != 1) {
-                        if constexpr (t == 0 && NB != 40) g_mma_c(accz[p], av0, B[tap + p], zero);
-                        else g_mma(accz[p], av0, B[tap + p]);
+                        if constexpr (t == 0 && NB != 40) Mma<half_t>::initc(accz[p], av0, B[tap + p], zero);
+                        else Mma<half_t>::run(accz[p], av0, B[tap + p]);
                     }
                     if constexpr (WHICH != 0) {
-                        if constexpr (t == 0 && NB != 40) g_mma_c(accq[p], av1, B[tap + p], zero);
-                        else g_mma(accq[p], av1, B[tap + p]);
+                        if constexpr (t == 0 && NB != 40) Mma<half_t>::initc(accq[p], av1, B[tap + p], zero);
+                        else Mma<half_t>::run(accq[p], av1, B[tap + p]);
                     }
                     if constexpr (NXT) B[p] = *(const uint4*)((ks < 3 ? tb : tbn) + p * G_LS + boff(std::integral_constant<int, (ks + 1) & 3>{}));
                 });
@@ -459,28 +402,28 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
         int it = it0;
         [[maybe_unused]] int trk = 0;
         prime();
-        G_STAMP(wave, trk, 0);
+        TRACE_STAMP(wave, trk, 0);
         asm volatile("s_barrier" ::: "memory");                 // A0: the first tile's h, r*h have landed; the bias is in LDS
         for (;;) {
             int img, P0, L0;
             pos_of(it, img, P0, L0);
-            G_STAMP(wave, trk, 1);
+            TRACE_STAMP(wave, trk, 1);
             b_init(tbH);
             __builtin_amdgcn_sched_barrier(0);
             phase(tbH, tbR, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::true_type{});
             phase(tbR, tbR, std::integral_constant<int, 20>{}, std::integral_constant<int, 1>{}, std::false_type{});
-            G_STAMP(wave, trk, 2);
+            TRACE_STAMP(wave, trk, 2);
             asm volatile("s_barrier" ::: "memory");             // B: x has landed; h, r*h are free
-            G_STAMP(wave, trk, 3);
+            TRACE_STAMP(wave, trk, 3);
             b_init(tbX);
             __builtin_amdgcn_sched_barrier(0);
             phase(tbX, tbX, std::integral_constant<int, 40>{}, std::integral_constant<int, 2>{}, std::false_type{});
 #if defined(__HIP_DEVICE_COMPILE__)
             asm volatile("" ::"v"(accz[0]), "v"(accz[1]), "v"(accz[2]), "v"(accz[3]), "v"(accq[0]), "v"(accq[1]), "v"(accq[2]), "v"(accq[3]));
 #endif
-            G_STAMP(wave, trk, 4);
+            TRACE_STAMP(wave, trk, 4);
             asm volatile("s_barrier" ::: "memory");             // C: the x piece is free (the staged h' goes there)
-            G_STAMP(wave, trk, 5);
+            TRACE_STAMP(wave, trk, 5);
             // h of this wave's outputs: clamped addresses, unconditional loads, all eight in flight under the first pass of transcendentals
             const char* hb = a.h.ptr + (int64_t)img * a.h.sb + (int64_t)min(P0 + lx, a.Plen - 1) * a.h.sp + (cs * 32 + hi * 8) * 2;
             u4_t hreg[4][2];
@@ -502,7 +445,7 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
                     bq[2 * g] = f2_t{vq[0], vq[1]} * KS_TANH; bq[2 * g + 1] = f2_t{vq[2], vq[3]} * KS_TANH;
                 }
                 // pass 1 (no h needed): a = e^-z', b = e^2q' (exponent clamped: b stays finite), den = (b + 1)(1 + a); r = 1 / den -> accz, b -> accq
-                g_for<0, 4>([&](auto P) {
+                static_for<0, 4>([&](auto P) {
                     constexpr int p = decltype(P)::value;
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
@@ -522,9 +465,9 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
                 asm volatile("" ::"v"(accz[0]), "v"(accz[1]), "v"(accz[2]), "v"(accz[3]), "v"(accq[0]), "v"(accq[1]), "v"(accq[2]), "v"(accq[3]));
 #endif
                 __builtin_amdgcn_sched_barrier(0);               // ALL of pass 1 first (interleaved with pass 2, the first h load's latency was exposed)
-                G_STAMP(wave, trk, 6);
+                TRACE_STAMP(wave, trk, 6);
                 // pass 2: h' = h + ((b - 1) - h (b + 1)) r, fp16, staged in the x piece (line lh 4 + p) for the helpers' whole-line stores
-                g_for<0, 4>([&](auto P) {
+                static_for<0, 4>([&](auto P) {
                     constexpr int p = decltype(P)::value;
 #pragma unroll
                     for (int m2 = 0; m2 < 2; ++m2) {
@@ -546,10 +489,10 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
                     }
                 });
             }
-            G_STAMP(wave, trk, 7);
+            TRACE_STAMP(wave, trk, 7);
             prime();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            G_STAMP(wave, trk, 8);
+            TRACE_STAMP(wave, trk, 8);
             asm volatile("s_barrier" ::: "memory");             // E: h' is staged; the next tile's h, r*h have landed
             ++trk;
             ++it;
@@ -585,7 +528,7 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
     };
     uint4 A[G_DEPTH];
     f16x_t acc[8];
-    g_for<0, G_DEPTH>([&](auto T) { A[decltype(T)::value] = a_load(wA, T); });
+    static_for<0, G_DEPTH>([&](auto T) { A[decltype(T)::value] = a_load(wA, T); });
 
     // one 64-channel piece: 4 k-steps x 5 taps of 8 MFMAs.  tb = first window line of this wave.  B window: step (ks, tap)
     // multiplies output line p with window line tap + p; line 8 + tap arrives during tap (for tap + 1); during tap 4 the next
@@ -594,10 +537,10 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
         uint4 B[12];
         {
             const int o = boff(std::integral_constant<int, 0>{});
-            g_for<0, 8>([&](auto R) { B[decltype(R)::value] = *(const uint4*)(tb + decltype(R)::value * G_LS + o); });
+            static_for<0, 8>([&](auto R) { B[decltype(R)::value] = *(const uint4*)(tb + decltype(R)::value * G_LS + o); });
         }
         __builtin_amdgcn_sched_barrier(0);
-        g_for<0, G_NSTEP>([&](auto T_) {
+        static_for<0, G_NSTEP>([&](auto T_) {
             constexpr int t = decltype(T_)::value;
             constexpr int ks = t / 5, tap = t % 5;
             const uint4 av = A[t % G_DEPTH];
@@ -606,10 +549,10 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
             if constexpr (t + G_DEPTH < G_NSTEP) A[t % G_DEPTH] = a_load(wcur, std::integral_constant<int, t + G_DEPTH>{});
             else if constexpr (!decltype(LAST)::value) A[t % G_DEPTH] = a_load(wnxt, std::integral_constant<int, t + G_DEPTH - G_NSTEP>{});
             if constexpr (tap < 4 || ks == 3) {
-                g_for<0, 8>([&](auto P) {
+                static_for<0, 8>([&](auto P) {
                     constexpr int p = decltype(P)::value;
-                    if constexpr (decltype(INITC)::value && t == 0) g_mma_c(acc[p], av, B[tap + p], cinit);
-                    else g_mma(acc[p], av, B[tap + p]);
+                    if constexpr (decltype(INITC)::value && t == 0) Mma<half_t>::initc(acc[p], av, B[tap + p], cinit);
+                    else Mma<half_t>::run(acc[p], av, B[tap + p]);
                 });
                 constexpr bool has_a = t + G_DEPTH < G_NSTEP || !decltype(LAST)::value;
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -620,12 +563,12 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
             } else {
                 uint4 Bn[8];
                 const int o = boff(std::integral_constant<int, (ks + 1) & 3>{});
-                g_for<0, 8>([&](auto P) {
+                static_for<0, 8>([&](auto P) {
                     constexpr int p = decltype(P)::value;
-                    g_mma(acc[p], av, B[4 + p]);
+                    Mma<half_t>::run(acc[p], av, B[4 + p]);
                     Bn[p] = *(const uint4*)(tb + p * G_LS + o);
                 });
-                g_for<0, 8>([&](auto P) { B[decltype(P)::value] = Bn[decltype(P)::value]; });
+                static_for<0, 8>([&](auto P) { B[decltype(P)::value] = Bn[decltype(P)::value]; });
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -662,13 +605,13 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
         // R: phase A contracts x (piece 0), phase B h (piece 1); r * h from the h window's centre lines
         const char* const t0 = S0 + role * 8 * G_LS;
         const char* const t1 = S1 + role * 8 * G_LS;
-        G_STAMP(wave, trk, 0);
+        TRACE_STAMP(wave, trk, 0);
         asm volatile("s_barrier" ::: "memory");             // A
-        G_STAMP(wave, trk, 1);
+        TRACE_STAMP(wave, trk, 1);
         conv_phase(t0, wA, wB, std::true_type{}, c1, std::false_type{});
-        G_STAMP(wave, trk, 2);
+        TRACE_STAMP(wave, trk, 2);
         asm volatile("s_barrier" ::: "memory");             // B
-        G_STAMP(wave, trk, 3);
+        TRACE_STAMP(wave, trk, 3);
         {
             const f16x_t none = {};
             conv_phase(t1, wB, wA, std::false_type{}, none, std::false_type{});
@@ -676,13 +619,13 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
 #if defined(DEMFI_TRACE) && defined(__HIP_DEVICE_COMPILE__)
         asm volatile("" ::"v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]));
 #endif
-        G_STAMP(wave, trk, 4);
+        TRACE_STAMP(wave, trk, 4);
         // r * h: h from the window's centre lines; barrier C (the h piece is free) AFTER the epilogue.  Measured alternative (round 6): h
         // into registers first and C before the epilogue, so that the helpers issue the next h under it -- the tile got 20 % SLOWER
         // (epilogue + stores 5 500 -> 11 200 cycles: the helpers' DMA and these 16 partial-line stores share the CU's memory pipe)
         char* const ob = a.dst + (int64_t)img * a.d_sb + (int64_t)(P0 + lx) * a.d_sp + (cs * 32 + hi * 8) * 2;
         const bool pok = P0 + lx < a.Plen;
-        g_for<0, 8>([&](auto P) {
+        static_for<0, 8>([&](auto P) {
             constexpr int p = decltype(P)::value;
             const int l = L0 + role * 8 + p;
             f2_t sg[8];
@@ -706,7 +649,7 @@ __global__ __launch_bounds__(G_NTHREADS, 1) void gru_sep5_kernel(const GArgs a)
                 if (pok && l < a.Llen) *gp<u4_t>(ob + (int64_t)l * a.d_sl + m2 * 32) = __builtin_bit_cast(u4_t, o);
             }
         });
-        G_STAMP(wave, trk, 5);
+        TRACE_STAMP(wave, trk, 5);
         asm volatile("s_barrier" ::: "memory");             // C: the h piece is free
         ++trk;
         ++it;
@@ -841,12 +784,8 @@ extern "C" int demfi_gru_zq(const demfi_conv* hz, const demfi_conv* hq, void* st
 #ifdef DEMFI_TRACE
 extern "C" int demfi_gru_trace_dump(unsigned long long* out, int64_t n)
 {
-    const int64_t have = (int64_t)GT_WGS * GT_WAVES * GT_TILES * GT_STAMPS;
-    if (n != have) return demfi_set_error(DEMFI_ERR_ARG, "demfi_gru_trace_dump: expected %lld entries", (long long)have);
+    if (n != TR_N) return demfi_set_error(DEMFI_ERR_ARG, "demfi_gru_trace_dump: expected %lld entries", (long long)TR_N);
     DEMFI_HIP_CHECK(hipDeviceSynchronize());
-    DEMFI_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gru_trace), have * 8));
-    static const std::vector<unsigned long long> zeros(have, 0ull);
-    DEMFI_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_gru_trace), zeros.data(), have * 8));
-    return DEMFI_OK;
+    return TRACE_DRAIN(out, false);
 }
 #endif

@@ -24,9 +24,7 @@
 // Roles by wave age as in the staged-store kernel: MFMA waves 0-3 (cout half x row half) touch global memory only for their A
 // fragments; helper waves 4-7 issue the window DMA (under conv2's MFMA phase), read the staged outputs back 8 lanes per pixel and store
 // whole 128-byte lines with the streaming hint (round 6: under conv1's epilogue, not its MFMA phase).  Four raw s_barriers per step of 2 x 288 MFMAs per wave (18 432 matrix-pipe cycles).
-#include "common.h"
-#include <type_traits>
-#include <vector>
+#include "kernel_kit.h"
 
 namespace {
 
@@ -53,54 +51,9 @@ constexpr int RB_NSTEP = 36;                                     // (kx, k-step)
 static_assert(RB_NSTEP % RB_DEPTH == 0, "static ring indices");
 static_assert(RB_LDS <= 160 * 1024, "LDS budget");
 
-// In-kernel phase trace (libdemfi_hip_trace.so only): s_memtime at the barriers of the first RB_TR_STEPS loop iterations of
-// workgroups 0..31, [wg][wave][iteration][stamp]; tools/rb_trace.py prints the phase means.
-#ifdef DEMFI_TRACE
-constexpr int RB_TR_WGS = 32, RB_TR_WAVES = 8, RB_TR_STEPS = 24, RB_TR_STAMPS = 10;
-__device__ unsigned long long g_rb_trace[RB_TR_WGS * RB_TR_WAVES * RB_TR_STEPS * RB_TR_STAMPS];
-#define RB_STAMP(wave_, k_, i_)                                                                                       \
-    do {                                                                                                              \
-        if (blockIdx.x < RB_TR_WGS && (k_) < RB_TR_STEPS && (threadIdx.x & 63) == 0)                                  \
-            g_rb_trace[((blockIdx.x * RB_TR_WAVES + (wave_)) * RB_TR_STEPS + (k_)) * RB_TR_STAMPS + (i_)] =           \
-                __builtin_readcyclecounter() | ((unsigned long long)(pro ? 1 : 0) << 63);                             \
-    } while (0)
-#else
-#define RB_STAMP(wave_, k_, i_) do { } while (0)
-#endif
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void rb_for(F&& f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        rb_for<I + 1, N>(f);
-    }
-}
-__device__ __forceinline__ void rb_mma(f16x_t& acc, const uint4& a, const uint4& b)
-{
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), acc, 0, 0, 0);
-}
-__device__ __forceinline__ void rb_mma_c(f16x_t& acc, const uint4& a, const uint4& b, const f16x_t& c)
-{
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), c, 0, 0, 0);
-}
-// (fp16 half of a packed pair) * 1.0 + c in one VALU op
-__device__ __forceinline__ float rb_mix_lo(unsigned a, float c)
-{
-    float d = 0.0f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
-#endif
-    return d;
-}
-__device__ __forceinline__ float rb_mix_hi(unsigned a, float c)
-{
-    float d = 0.0f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
-#endif
-    return d;
-}
+// In-kernel phase trace (libdemfi_hip_trace.so only): s_memtime at the barriers of the first 24 loop iterations of
+// workgroups 0..31, [wg][wave][iteration][stamp], bit 63 = opening step of a chain; tools/rb_trace.py prints the phase means.
+DEMFI_TRACE_BUFFER(32, 8, 24, 10)
 
 struct RbArgs {
     const char* src;  int64_t s_sx, s_sy, s_sb;                  // input x (bytes)
@@ -124,19 +77,7 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
     // contiguous run of items per workgroup; the workgroups of an XCD (blockIdx % 8) share a contiguous band, so neighbouring
     // strips (which share 4 of 34 input columns) meet in one L2
     int it0, it1;
-    {
-        const int G = gridDim.x;
-        if ((G & 7) == 0 && total >= G) {
-            const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, nw = G >> 3;
-            const int q = total >> 3, r = total & 7;
-            const int lo = xcd * q + min(xcd, r), n = q + (xcd < r ? 1 : 0);
-            it0 = lo + (int)(((int64_t)n * idx) / nw);
-            it1 = lo + (int)(((int64_t)n * (idx + 1)) / nw);
-        } else {
-            it0 = (int)(((int64_t)total * blockIdx.x) / G);
-            it1 = (int)(((int64_t)total * (blockIdx.x + 1)) / G);
-        }
-    }
+    XCD_ITEM_RUN(total, it0, it1);
     if (it0 >= it1) return;                                      // uniform per workgroup
     // (item, opening?) -> image, first output column, first input row of the window
     auto pos_of = [&](int it, bool pro, int& img, int& x0, int& row0) {
@@ -219,28 +160,28 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
         [[maybe_unused]] int trk = 0;
         for (;;) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the window has landed (and this wave's stores are out)
-            RB_STAMP(wave, trk, 0);
+            TRACE_STAMP(wave, trk, 0, pro);
             asm volatile("s_barrier" ::: "memory");             // A
-            RB_STAMP(wave, trk, 1);
+            TRACE_STAMP(wave, trk, 1, pro);
             // The 16 output stores go behind barrier B, under conv1's EPILOGUE, not here under its MFMA phase (round 5): the stores and the MFMA waves' A-fragment loads share the CU's one memory pipe, and
             // a matrix phase without the helpers' VMEM traffic runs at 0.93 of the pipe instead of 0.81 (conv1 phase 11 400 -> 9 950
             // cycles, step 28 900 -> 27 400, launch -3 %: profiles/r06_resblock_store_timing_ab.txt); the epilogue issues no VMEM itself
             if (have_prev) stage_read();
-            RB_STAMP(wave, trk, 2);
+            TRACE_STAMP(wave, trk, 2, pro);
             asm volatile("s_barrier" ::: "memory");             // B: the staged outputs are in registers -> the M lines are free
             if (have_prev) stage_store(p_img, p_x0, p_row0);
-            RB_STAMP(wave, trk, 3);
+            TRACE_STAMP(wave, trk, 3, pro);
             asm volatile("s_barrier" ::: "memory");             // C: every MFMA wave is done with the input window
-            RB_STAMP(wave, trk, 4);
+            TRACE_STAMP(wave, trk, 4, pro);
             int nit = it;
             bool npro = false, more = true;
             if (!pro) { nit = it + 1; more = nit < it1; npro = more && opens_chain(nit); }
             // (measured negative, round 6: the window DMA as a burst at s_setprio 3 -- issued in 3 300 instead of 8 300 cycles, conv2's MFMA
             // phase 11 900 -> 12 750 cycles: profiles/r06_resblock_store_timing_ab.txt)
             if (more) issue_window(nit, npro);
-            RB_STAMP(wave, trk, 5);
+            TRACE_STAMP(wave, trk, 5, pro);
             asm volatile("s_barrier" ::: "memory");             // D
-            RB_STAMP(wave, trk, 6);
+            TRACE_STAMP(wave, trk, 6, pro);
             ++trk;
             have_prev = !pro;
             if (have_prev) pos_of(it, false, p_img, p_x0, p_row0);
@@ -302,7 +243,7 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
     };
     uint4 A[RB_DEPTH];
     f16x_t acc[8];
-    rb_for<0, RB_DEPTH>([&](auto T) { A[decltype(T)::value] = a_load(w1, T); });
+    static_for<0, RB_DEPTH>([&](auto T) { A[decltype(T)::value] = a_load(w1, T); });
 
     // one convolution phase: 36 steps of 8 MFMAs.  line(L, o): address of window line L (0..9, relative to this wave's first
     // line) + fragment offset o.  The A ring runs through the phase boundary (wnxt = the next phase's weights).
@@ -313,10 +254,10 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
         uint4 B[10];
         {
             const int o = boff(std::integral_constant<int, 0>{});
-            rb_for<0, 8>([&](auto R) { B[decltype(R)::value] = *(const uint4*)line(R, o); });
+            static_for<0, 8>([&](auto R) { B[decltype(R)::value] = *(const uint4*)line(R, o); });
         }
         __builtin_amdgcn_sched_barrier(0);
-        rb_for<0, RB_NSTEP>([&](auto T_) {
+        static_for<0, RB_NSTEP>([&](auto T_) {
             constexpr int t = decltype(T_)::value;
             constexpr int g = t / 3, ky = t % 3;
             const uint4 av = A[t % RB_DEPTH];
@@ -324,10 +265,10 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
             if constexpr (t + RB_DEPTH < RB_NSTEP) A[t % RB_DEPTH] = a_load(wcur, std::integral_constant<int, t + RB_DEPTH>{});
             else                                   A[t % RB_DEPTH] = a_load(wnxt, std::integral_constant<int, t + RB_DEPTH - RB_NSTEP>{});
             if constexpr (ky < 2 || g + 1 == 12) {
-                rb_for<0, 8>([&](auto P) {
+                static_for<0, 8>([&](auto P) {
                     constexpr int p = decltype(P)::value;
-                    if constexpr (decltype(INITC)::value && t == 0) rb_mma_c(acc[p], av, B[ky + p], cinit);
-                    else rb_mma(acc[p], av, B[ky + p]);
+                    if constexpr (decltype(INITC)::value && t == 0) Mma<half_t>::initc(acc[p], av, B[ky + p], cinit);
+                    else Mma<half_t>::run(acc[p], av, B[ky + p]);
                 });
                 // 1 MFMA, the B line, 1 MFMA, the A fragment, the rest
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -338,12 +279,12 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
             } else {
                 uint4 Bn[8];
                 const int o = boff(std::integral_constant<int, (g + 1 < 12 ? g + 1 : 0)>{});
-                rb_for<0, 8>([&](auto P) {
+                static_for<0, 8>([&](auto P) {
                     constexpr int p = decltype(P)::value;
-                    rb_mma(acc[p], av, B[2 + p]);
+                    Mma<half_t>::run(acc[p], av, B[2 + p]);
                     Bn[p] = *(const uint4*)line(P, o);
                 });
-                rb_for<0, 8>([&](auto P) { B[decltype(P)::value] = Bn[decltype(P)::value]; });
+                static_for<0, 8>([&](auto P) { B[decltype(P)::value] = Bn[decltype(P)::value]; });
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -372,9 +313,9 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
         int img, x0, row0;
         pos_of(it, pro, img, x0, row0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the previous step's staged outputs (and the biases) are in LDS
-        RB_STAMP(wave, trk, 0);
+        TRACE_STAMP(wave, trk, 0, pro);
         asm volatile("s_barrier" ::: "memory");                 // A: the input window has landed
-        RB_STAMP(wave, trk, 1);
+        TRACE_STAMP(wave, trk, 1, pro);
         {
             f16x_t c1;
 #pragma unroll
@@ -392,21 +333,21 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
                 // with ONE accumulator: 36 x (A fragment + MFMA) instead of 36 x 8 MFMAs (18 700 -> ~7 000 cycles per chain)
                 const char* const tp = smem + (14 + rh) * RB_IN_LS;
                 uint4 Bc[3], Bn[3];
-                rb_for<0, 3>([&](auto L) { Bc[decltype(L)::value] = *(const uint4*)(tp + decltype(L)::value * RB_IN_LS + boff(std::integral_constant<int, 0>{})); });
-                rb_for<0, 12>([&](auto G) {
+                static_for<0, 3>([&](auto L) { Bc[decltype(L)::value] = *(const uint4*)(tp + decltype(L)::value * RB_IN_LS + boff(std::integral_constant<int, 0>{})); });
+                static_for<0, 12>([&](auto G) {
                     constexpr int g = decltype(G)::value;
                     if constexpr (g + 1 < 12) {
                         const int o = boff(std::integral_constant<int, g + 1>{});
-                        rb_for<0, 3>([&](auto L) { Bn[decltype(L)::value] = *(const uint4*)(tp + decltype(L)::value * RB_IN_LS + o); });
+                        static_for<0, 3>([&](auto L) { Bn[decltype(L)::value] = *(const uint4*)(tp + decltype(L)::value * RB_IN_LS + o); });
                     }
-                    rb_for<0, 3>([&](auto KY) {
+                    static_for<0, 3>([&](auto KY) {
                         constexpr int t = 3 * g + decltype(KY)::value;
                         const uint4 av = A[t % RB_DEPTH];
                         A[t % RB_DEPTH] = a_load(w1, std::integral_constant<int, (t + RB_DEPTH) % RB_NSTEP>{});
-                        if constexpr (t == 0) rb_mma_c(acc[0], av, Bc[0], c1);
-                        else rb_mma(acc[0], av, Bc[decltype(KY)::value]);
+                        if constexpr (t == 0) Mma<half_t>::initc(acc[0], av, Bc[0], c1);
+                        else Mma<half_t>::run(acc[0], av, Bc[decltype(KY)::value]);
                     });
-                    rb_for<0, 3>([&](auto L) { Bc[decltype(L)::value] = Bn[decltype(L)::value]; });
+                    static_for<0, 3>([&](auto L) { Bc[decltype(L)::value] = Bn[decltype(L)::value]; });
                     __builtin_amdgcn_sched_barrier(0);
                 });
             }
@@ -414,9 +355,9 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
 #if defined(DEMFI_TRACE) && defined(__HIP_DEVICE_COMPILE__)
         asm volatile("" ::"v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]));
 #endif
-        RB_STAMP(wave, trk, 2);
+        TRACE_STAMP(wave, trk, 2, pro);
         asm volatile("s_barrier" ::: "memory");                 // B: the helpers hold the previous outputs in registers
-        RB_STAMP(wave, trk, 3);
+        TRACE_STAMP(wave, trk, 3, pro);
         {
             // conv1 epilogue: ReLU, fp16 -> M lines (rows 14, 15 also to the carry slot the NEXT step reads); the accumulators then
             // restart at bias2 + identity (the row's identity is read from the input window before its conversions are issued).  A
@@ -453,7 +394,7 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
             }
             char* const mrow = smem + RB_M_OFF + rh * 8 * RB_ML;
             char* const crow = smem + RB_C_OFF + (cp ^ 1) * 2 * RB_ML;
-            rb_for<0, 8>([&](auto P) {
+            static_for<0, 8>([&](auto P) {
                 constexpr int p = decltype(P)::value;
                 if (pro) return;                                 // per row (see the note on basic blocks above the kernel's epilogue)
                 u4_t idr[2];
@@ -479,10 +420,10 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
                         const u4_t r = idr[m2];
 #pragma unroll
                         for (int q = 0; q < 2; ++q) {
-                            acc[p][(2 * m2) * 4 + 2 * q] = rb_mix_lo(r[q], c2[(2 * m2) * 4 + 2 * q]);
-                            acc[p][(2 * m2) * 4 + 2 * q + 1] = rb_mix_hi(r[q], c2[(2 * m2) * 4 + 2 * q + 1]);
-                            acc[p][(2 * m2 + 1) * 4 + 2 * q] = rb_mix_lo(r[2 + q], c2[(2 * m2 + 1) * 4 + 2 * q]);
-                            acc[p][(2 * m2 + 1) * 4 + 2 * q + 1] = rb_mix_hi(r[2 + q], c2[(2 * m2 + 1) * 4 + 2 * q + 1]);
+                            acc[p][(2 * m2) * 4 + 2 * q] = res_mix_lo(r[q], c2[(2 * m2) * 4 + 2 * q]);
+                            acc[p][(2 * m2) * 4 + 2 * q + 1] = res_mix_hi(r[q], c2[(2 * m2) * 4 + 2 * q + 1]);
+                            acc[p][(2 * m2 + 1) * 4 + 2 * q] = res_mix_lo(r[2 + q], c2[(2 * m2 + 1) * 4 + 2 * q]);
+                            acc[p][(2 * m2 + 1) * 4 + 2 * q + 1] = res_mix_hi(r[2 + q], c2[(2 * m2 + 1) * 4 + 2 * q + 1]);
                         }
                     }
                 }
@@ -491,7 +432,7 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
                 // LDS operations of one wave complete in order: these zeros land on top of the values this lane has just written
                 const bool col_out = !((unsigned)(x0 + col_x) < (unsigned)W);
                 const u4_t zz = {0u, 0u, 0u, 0u};
-                rb_for<0, 8>([&](auto P) {
+                static_for<0, 8>([&](auto P) {
                     constexpr int p = decltype(P)::value;
                     const bool row_out = !((unsigned)(row0 + 1 + rh * 8 + p) < (unsigned)H);
                     if (row_out || col_out) {
@@ -505,9 +446,9 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        RB_STAMP(wave, trk, 4);
+        TRACE_STAMP(wave, trk, 4, pro);
         asm volatile("s_barrier" ::: "memory");                 // C: M is complete, the input window is free
-        RB_STAMP(wave, trk, 5);
+        TRACE_STAMP(wave, trk, 5, pro);
         if (!pro) {
             const char* const t01 = rh == 0 ? smem + RB_C_OFF + cp * 2 * RB_ML : smem + RB_M_OFF + 6 * RB_ML;
             auto line_m = [&](auto L, int o) {
@@ -521,12 +462,12 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
 #if defined(DEMFI_TRACE) && defined(__HIP_DEVICE_COMPILE__)
         asm volatile("" ::"v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3]), "v"(acc[4]), "v"(acc[5]), "v"(acc[6]), "v"(acc[7]));
 #endif
-        RB_STAMP(wave, trk, 6);
+        TRACE_STAMP(wave, trk, 6, pro);
         asm volatile("s_barrier" ::: "memory");                 // D: nobody reads M any more -> its 16 lines take the staged outputs
-        RB_STAMP(wave, trk, 7);
+        TRACE_STAMP(wave, trk, 7, pro);
         if (!pro) {
             char* const srow = smem + RB_M_OFF + rh * 8 * RB_ML;
-            rb_for<0, 8>([&](auto P) {
+            static_for<0, 8>([&](auto P) {
                 constexpr int p = decltype(P)::value;
 #pragma unroll
                 for (int m2 = 0; m2 < 2; ++m2) {
@@ -540,7 +481,7 @@ __global__ __launch_bounds__(RB_NTHREADS, 1) void resblock3x3_c64_kernel(const R
                 }
             });
         }
-        RB_STAMP(wave, trk, 8);
+        TRACE_STAMP(wave, trk, 8, pro);
         ++trk;
         cp ^= 1;
         if (pro) pro = false;
@@ -626,12 +567,8 @@ extern "C" int demfi_resblock3x3_c64(const demfi_conv* h1, const demfi_conv* h2,
 // copies the trace to host memory and clears it (trace build only)
 extern "C" int demfi_rb_trace_dump(unsigned long long* out, int64_t n)
 {
-    const int64_t have = (int64_t)RB_TR_WGS * RB_TR_WAVES * RB_TR_STEPS * RB_TR_STAMPS;
-    if (n != have) return demfi_set_error(DEMFI_ERR_ARG, "demfi_rb_trace_dump: expected %lld entries", (long long)have);
+    if (n != TR_N) return demfi_set_error(DEMFI_ERR_ARG, "demfi_rb_trace_dump: expected %lld entries", (long long)TR_N);
     DEMFI_HIP_CHECK(hipDeviceSynchronize());
-    DEMFI_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rb_trace), have * 8));
-    static const std::vector<unsigned long long> zeros(have, 0ull);
-    DEMFI_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_rb_trace), zeros.data(), have * 8));
-    return DEMFI_OK;
+    return TRACE_DRAIN(out, false);
 }
 #endif

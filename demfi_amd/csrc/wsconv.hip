@@ -25,25 +25,11 @@
 // 2x2 and the 32-cout forms are bound by it, the 3x3 / 64-cout form is balanced); the item's end (64 KiB of the MFMA waves' own stores [+ loads]) is
 // serial with the matrix phases -- staged whole-line stores by the helpers, lane-swapped store layouts and a one-instruction DMA address path
 // were each built and measured neutral.
-#include "common.h"
-#include <type_traits>
+#include "kernel_kit.h"
 #include <stdlib.h>
 #include <string.h>
 
 namespace {
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void ws_for(F&& f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        ws_for<I + 1, N>(f);
-    }
-}
-__device__ __forceinline__ void ws_mma(f16x_t& acc, const uint4& a, const uint4& b)
-{
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), acc, 0, 0, 0);
-}
 
 template <bool S2, int NCH = 2> struct Ws2Cfg {                // NCH: 32-cout subtiles per work item (2: waves = cout half x row half; 1: four row groups)
     static constexpr int KSE = S2 ? 2 : 3;                       // taps per dimension a unit sees
@@ -111,24 +97,6 @@ struct WsArgs {
     WsChunk ch[WS_MAX_CHUNKS];
 };
 
-// (fp16 half of a packed pair) * 1.0 + c in one VALU op: bias + residual -> the accumulator's initial value
-__device__ __forceinline__ float ws_mix_lo(unsigned a, float c)
-{
-    float d = 0.0f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
-#endif
-    return d;
-}
-__device__ __forceinline__ float ws_mix_hi(unsigned a, float c)
-{
-    float d = 0.0f;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(a), "v"(c));
-#endif
-    return d;
-}
-
 constexpr int WS_NTHREADS = 512;                                 // 4 MFMA + 4 helper waves (== Ws2Cfg::NTHREADS: a macro argument cannot hold the template's comma)
 template <bool S2, int NCH>
 __global__ __launch_bounds__(WS_NTHREADS, 1) void conv_ws2_kernel(const WsArgs a)
@@ -146,19 +114,7 @@ __global__ __launch_bounds__(WS_NTHREADS, 1) void conv_ws2_kernel(const WsArgs a
     const int total = tiles_img * a.batch * nblk;
     // contiguous run of items per workgroup, the workgroups of an XCD (blockIdx % 8) share a contiguous band
     int it0, it1;
-    {
-        const int G = gridDim.x;
-        if ((G & 7) == 0 && total >= G) {
-            const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3, nw = G >> 3;
-            const int q = total >> 3, r = total & 7;
-            const int lo = xcd * q + min(xcd, r), n = q + (xcd < r ? 1 : 0);
-            it0 = lo + (int)(((int64_t)n * idx) / nw);
-            it1 = lo + (int)(((int64_t)n * (idx + 1)) / nw);
-        } else {
-            it0 = (int)(((int64_t)total * blockIdx.x) / G);
-            it1 = (int)(((int64_t)total * (blockIdx.x + 1)) / G);
-        }
-    }
+    XCD_ITEM_RUN(total, it0, it1);
     if (it0 >= it1) return;                                      // uniform per workgroup
     const int upi = a.n_chunks * (S2 ? 4 : 1);                   // units per item
     const int n_units = (it1 - it0) * upi;
@@ -335,10 +291,10 @@ __global__ __launch_bounds__(WS_NTHREADS, 1) void conv_ws2_kernel(const WsArgs a
                     const u4_t r = rr[p][m2];
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
-                        acc[p][(2 * m2) * 4 + 2 * q] = ws_mix_lo(r[q], bq[2 * m2][2 * q]);
-                        acc[p][(2 * m2) * 4 + 2 * q + 1] = ws_mix_hi(r[q], bq[2 * m2][2 * q + 1]);
-                        acc[p][(2 * m2 + 1) * 4 + 2 * q] = ws_mix_lo(r[2 + q], bq[2 * m2 + 1][2 * q]);
-                        acc[p][(2 * m2 + 1) * 4 + 2 * q + 1] = ws_mix_hi(r[2 + q], bq[2 * m2 + 1][2 * q + 1]);
+                        acc[p][(2 * m2) * 4 + 2 * q] = res_mix_lo(r[q], bq[2 * m2][2 * q]);
+                        acc[p][(2 * m2) * 4 + 2 * q + 1] = res_mix_hi(r[q], bq[2 * m2][2 * q + 1]);
+                        acc[p][(2 * m2 + 1) * 4 + 2 * q] = res_mix_lo(r[2 + q], bq[2 * m2 + 1][2 * q]);
+                        acc[p][(2 * m2 + 1) * 4 + 2 * q + 1] = res_mix_hi(r[2 + q], bq[2 * m2 + 1][2 * q + 1]);
                     }
                 }
             }
@@ -384,7 +340,7 @@ __global__ __launch_bounds__(WS_NTHREADS, 1) void conv_ws2_kernel(const WsArgs a
         acc_init(io, rr, std::true_type{});
     }
     WsUnit cur = unit_info(ccur);
-    ws_for<0, C::DEPTH>([&](auto T) { A[decltype(T)::value] = a_load(cur, T); });
+    static_for<0, C::DEPTH>([&](auto T) { A[decltype(T)::value] = a_load(cur, T); });
 
     for (int u = 0; u < n_units; ++u) {
         const bool last_of_item = ccur.cu == a.n_chunks - 1 && (!S2 || ccur.ph == 3);
@@ -395,9 +351,9 @@ __global__ __launch_bounds__(WS_NTHREADS, 1) void conv_ws2_kernel(const WsArgs a
         asm volatile("s_barrier" ::: "memory");                 // unit u has landed
         stamp(2);
         uint4 B[C::BL];
-        ws_for<0, RPW>([&](auto R) { B[decltype(R)::value] = *(const uint4*)(tb + boff[0] + decltype(R)::value * (C::LL * 64)); });
+        static_for<0, RPW>([&](auto R) { B[decltype(R)::value] = *(const uint4*)(tb + boff[0] + decltype(R)::value * (C::LL * 64)); });
         __builtin_amdgcn_sched_barrier(0);
-        ws_for<0, C::NSTEP>([&](auto T_) {
+        static_for<0, C::NSTEP>([&](auto T_) {
             constexpr int t = decltype(T_)::value;
             constexpr int g = t / KSE, ky = t % KSE;
             const uint4 av = A[t % C::DEPTH];
@@ -407,7 +363,7 @@ __global__ __launch_bounds__(WS_NTHREADS, 1) void conv_ws2_kernel(const WsArgs a
             if constexpr (t + C::DEPTH < C::NSTEP) A[t % C::DEPTH] = a_load(cur, std::integral_constant<int, t + C::DEPTH>{});
             else                                   A[t % C::DEPTH] = a_load(nxt, std::integral_constant<int, t + C::DEPTH - C::NSTEP>{});
             if constexpr (ky < KSE - 1 || g + 1 == C::NG) {
-                ws_for<0, RPW>([&](auto P) { ws_mma(acc[decltype(P)::value], av, B[ky + decltype(P)::value]); });
+                static_for<0, RPW>([&](auto P) { Mma<half_t>::run(acc[decltype(P)::value], av, B[ky + decltype(P)::value]); });
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 if constexpr (ky < KSE - 1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -415,12 +371,12 @@ __global__ __launch_bounds__(WS_NTHREADS, 1) void conv_ws2_kernel(const WsArgs a
                 __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
             } else {
                 uint4 Bn[RPW];
-                ws_for<0, RPW>([&](auto P) {
+                static_for<0, RPW>([&](auto P) {
                     constexpr int p = decltype(P)::value;
-                    ws_mma(acc[p], av, B[KSE - 1 + p]);
+                    Mma<half_t>::run(acc[p], av, B[KSE - 1 + p]);
                     Bn[p] = *(const uint4*)(tb + boff[g + 1 < C::NG ? g + 1 : 0] + p * (C::LL * 64));
                 });
-                ws_for<0, RPW>([&](auto P) { B[decltype(P)::value] = Bn[decltype(P)::value]; });
+                static_for<0, RPW>([&](auto P) { B[decltype(P)::value] = Bn[decltype(P)::value]; });
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
