@@ -43,8 +43,8 @@ order, each at its own time instant, so n payloads at F are a progressive stream
 ``--mfi 2``).  The payload is uploaded as it is and one launch rebuilds the other field's rows in place by an edge-directed line
 average (csrc/deint.hip, defined by ``deint.bob_plane_np``) before it is converted; everything behind that -- rates, scene cuts,
 repeated frames, the full-length timeline, tiles, depths, layouts, rank sharding -- runs on the progressive stream unchanged.
-``--fps`` and ``--mfi`` count from the field rate 2F.  The output is always progressive.  Not offered: inverse telecine,
-mixed-mode streams (``Im``) and interlaced output; the quarter-row chroma offset of interlaced 4:2:0 fields is not modelled; a
+``--fps`` and ``--mfi`` count from the field rate 2F.  The output is always progressive.  Not offered: mixed-mode streams (``Im``;
+film carried by pulldown goes through ``--ivtc`` below) and interlaced output; the quarter-row chroma offset of interlaced 4:2:0 fields is not modelled; a
 payload is uploaded once per field.
 
 ``--deinterlace-mode adaptive`` (with ``--deinterlace``; the default ``bob`` is the above) rebuilds the missing rows motion-adaptively
@@ -56,6 +56,19 @@ is rebuilt once fields f+1 and f+2 are uploaded (two fields of lookahead; a rank
 after it), in place and without uploading any payload more often; an output field depends on payloads p-1, p and p+1 of the
 input only, whatever the batch size and the rank count.  Works with every switch above except ``--dedup``, which stages and
 discards fields one at a time: the two together are refused, ``--deinterlace-mode bob`` is the way out.
+
+``--ivtc`` takes film carried by 3:2 pulldown (24p as 29.97 frames/s: NTSC DVDs, broadcast captures; flagged ``It``, ``Ib``, ``Im`` or,
+wrongly, ``Ip``) and undoes the pulldown in front of everything else, as ffmpeg's ``fieldmatch,decimate`` does
+(``demfi_amd.telecine``): every payload keeps its top field and takes the bottom field of itself, the payload before or the one
+after, whichever weaves to the least combed frame, and of every five matched frames the one that repeats its predecessor most
+closely is dropped.  n payloads at F are a progressive stream of n - floor(n/5) frames at 4F/5, so ``--ivtc --fps 60000/1001`` is
+the true 23.976 -> 59.94; ``--fps`` and ``--mfi`` count from the film rate.  The comb scores of the three candidates of five
+payloads are ONE launch and the decimation metrics another (csrc/ivtc.hip, defined by ``telecine.comb_counts_np`` /
+``woven_sad_np``) over a small device ring of luma planes on a stream of its own; the kept frames are woven on the host.  A matched
+frame that is still combed (more than ``--ivtc-combpel`` samples in a 16x16 block) is bobbed from its top field
+(``--ivtc-combed bob``, the default) or passed through (``keep``) and reported.  Not offered: hybrid film / video material (30i
+sections are decimated like the rest), other cadences, a scene-change guard for the decimator, interlaced output, more than one
+rank, and ``--ivtc`` together with ``--deinterlace``.
 """
 import os
 import sys
@@ -69,6 +82,7 @@ from . import deint as I
 from . import dist as D
 from . import retime as R
 from . import scene as S
+from . import telecine as TC
 from . import tiling as T
 from . import y4m
 from .clip import ClipRunner
@@ -96,6 +110,16 @@ class YuvEdge:
         self.with_s1 = with_s1
         self.scene_cut = scene_cut
         self.full_length = full_length
+
+
+def check_ivtc(ivtc, deinterlace, world=1):
+    """``--ivtc`` does not go with ``--deinterlace`` or with more than one rank."""
+    if ivtc and deinterlace:
+        raise ValueError('--ivtc does not go with --deinterlace: inverse telecine puts the fields of a film frame back together, the '
+                         'deinterlacer makes a frame of every field; choose one (film carried by 3:2 pulldown: --ivtc)')
+    if ivtc and world > 1:
+        raise ValueError('VideoRunner: ivtc with %d ranks: which frames are dropped depends on the whole prefix of the input, so a rank '
+                         'cannot place its block of windows from k and r alone; run --ivtc on one rank' % world)
 
 
 def check_deinterlace_mode(deinterlace, mode, dedup):
@@ -138,12 +162,24 @@ class VideoRunner:
     that field rate, and windows, ranks and output counts follow it; the output is progressive.  ``last_fields`` is None, 'tff'
     or 'bff'.  Off by default (an interlaced stream is refused before anything is allocated); a progressive stream gives the same
     bytes either way.  ``deinterlace_mode``: 'bob' (default) or 'adaptive', the motion-adaptive rule of ``demfi_amd.deint`` over fields
-    f-2 .. f+2; only with ``deinterlace``, and not with ``dedup`` (both are refused here, before anything is allocated)."""
+    f-2 .. f+2; only with ``deinterlace``, and not with ``dedup`` (both are refused here, before anything is allocated).  ``ivtc``: inverse
+    telecine (``demfi_amd.telecine``): the input, whatever its I tag, is field-matched and decimated to n - floor(n/5) progressive
+    frames at 4/5 of its rate before anything else sees it; ``mfi`` multiplies and ``fps`` is checked against that film rate.
+    ``ivtc_cthresh`` (0..255, default 9) is the comb threshold, ``ivtc_combpel`` (0..256, default 80) the combed samples of a 16x16
+    block above which a matched frame counts as combed, ``ivtc_combed`` what happens to such a frame: 'bob' (default) or 'keep'.
+    One rank only, and not with ``deinterlace`` (refused here).  After a run ``last_matches`` = {'c': , 'p': , 'n': } counts of the
+    payloads' matches, ``last_dropped`` = the input payloads dropped, ``last_combed`` = the film frames left combed.  Off by
+    default: nothing changes anywhere without it."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
-                 tile_high_depth=False, deinterlace=False, deinterlace_mode='bob', **runner_kw):
+                 tile_high_depth=False, deinterlace=False, deinterlace_mode='bob', ivtc=False, ivtc_cthresh=TC.DEFAULT_CTHRESH,
+                 ivtc_combpel=TC.DEFAULT_COMBPEL, ivtc_combed=TC.DEFAULT_COMBED, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.ivtc = bool(ivtc)
+        self.ivtc_params = TC.check_params(ivtc_cthresh, ivtc_combpel, ivtc_combed)
+        check_ivtc(self.ivtc, deinterlace)
+        self._film = None
         self.deinterlace_mode = deinterlace_mode
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
@@ -201,6 +237,14 @@ class VideoRunner:
         """(the header everything downstream works on, field order or None, input frames per payload) of an input with header
         ``hdr``: an interlaced stream counts as its fields, a progressive stream at twice the rate (``deint.progressive_header``).
         Before anything is allocated: a requested output rate below the field rate is refused here."""
+        if self.ivtc:
+            fhdr = TC.film_header(hdr)
+            self.last_fields = None
+            if self.fps is not None and self.fps < fhdr.fps:
+                raise ValueError('VideoRunner: output frame rate %s is below the film rate %s of the telecined input (%s frames/s, four '
+                                 'film frames in five): --ivtc gives the film frames, so F_out must be at least %s'
+                                 % (self.fps, fhdr.fps, hdr.fps, fhdr.fps))
+            return fhdr, None, 1
         order = hdr.interlace if hdr.interlace in ('t', 'b') else None
         self.last_fields = {'t': 'tff', 'b': 'bff', None: None}[order]
         if order is None:
@@ -211,6 +255,25 @@ class VideoRunner:
                              'each): --deinterlace gives one frame per field, so F_out must be at least %s'
                              % (self.fps, phdr.fps, hdr.fps, phdr.fps))
         return phdr, order, 2
+
+    @property
+    def last_matches(self):
+        return self._film.matches if self._film is not None else {c: 0 for c in TC.CANDIDATES}
+
+    @property
+    def last_dropped(self):
+        return self._film.dropped if self._film is not None else []
+
+    @property
+    def last_combed(self):
+        return list(self._film.combed) if self._film is not None else []
+
+    def _film_frames(self, read, hdr, device):
+        """``telecine.FilmFrames`` over the input payloads ``read`` gives (``hdr``: the input's header), scored on the GPU."""
+        from .y4m_edge import IvtcScorer
+        cthresh, combpel, combed = self.ivtc_params
+        self._film = TC.FilmFrames(read, hdr, IvtcScorer(L.load(), hdr.h, hdr.w, hdr.depth, cthresh, device), combpel, combed)
+        return self._film
 
     def _behind(self, order):
         """``y4m.Frames(behind=...)``: the adaptive mode reads two fields before and after every field it rebuilds."""
@@ -267,12 +330,17 @@ class VideoRunner:
     def run_stream(self, src, dst):
         """One rank, sequential binary streams (stdin / stdout work): nothing is seeked, the input is read in batches of
         windows and every batch is written (and flushed) as it drains.  Returns (windows, frames written)."""
-        rd = y4m.Reader(src, self.depths, self.layouts, self.deinterlace)
+        rd = y4m.Reader(src, self.depths, self.layouts, self.deinterlace, self.ivtc)
+        self._film = None
         hdr, order, per = self._progressive(rd.header)
         self._check_depth(hdr)
         cr = self._clip_runner(hdr, 1, 0)
         wr = y4m.Writer(dst, self._out_header(hdr))
-        frames = y4m.Frames(rd, full_length=self.full_length, fields=per, behind=self._behind(order))
+        if self.ivtc:                                    # downstream sees an ordinary progressive input at the film rate
+            film = self._film_frames(lambda i, buf: rd.read_into(buf), rd.header, cr.runner.engine.device)
+            frames = y4m.Frames(payload=hdr.payload, fetch=film, full_length=self.full_length)
+        else:
+            frames = y4m.Frames(rd, full_length=self.full_length, fields=per, behind=self._behind(order))
         self.last_dups = []
 
         def sink(k, payloads):
@@ -301,12 +369,13 @@ class VideoRunner:
         if self.dedup is not None and world > 1:
             raise ValueError('VideoRunner: dedup with %d ranks: which frames are kept depends on the whole prefix of the input, so a rank '
                              'cannot place its block of windows from k and r alone; run --dedup on one rank' % world)
-        self.last_dups = []
+        check_ivtc(self.ivtc, self.deinterlace, world)
+        self.last_dups, self._film = [], None
         with open(in_path, 'rb') as f:
-            hdr, _, offs = y4m.scan(f, self.depths, self.layouts, self.deinterlace)
-            hdr, order, per = self._progressive(hdr)
+            in_hdr, _, offs = y4m.scan(f, self.depths, self.layouts, self.deinterlace, self.ivtc)
+            hdr, order, per = self._progressive(in_hdr)
             self._check_depth(hdr)
-            n_in = per * len(offs)                       # an interlaced input counts as its fields
+            n_in = TC.n_film_frames(len(offs)) if self.ivtc else per * len(offs)     # an interlaced input counts as its fields
             ohdr = self._out_header(hdr)
             hb = ohdr.encode()
             total = self._n_out(n_in, hdr)
@@ -317,11 +386,20 @@ class VideoRunner:
             D.barrier()
             cr = self._clip_runner(hdr, world, rank)
             full = self.full_length
+
+            def file_frames(first, stop, **kw):
+                """Frames first .. stop-1 of the input: its payloads by seek, or (one rank, from frame 0) the film frames made of them."""
+                if not self.ivtc:
+                    return y4m.Frames.from_file(f, offs, first, stop, hdr.payload, **kw)
+                if first != 0:
+                    raise RuntimeError('ivtc: film frames are made in order from frame 0, not from frame %d' % first)
+                fetch = y4m.file_fetch(f, offs)
+                film = self._film_frames(lambda i, buf: i < len(offs) and fetch(i, buf), in_hdr, cr.runner.engine.device)
+                return y4m.Frames(payload=hdr.payload, fetch=film, stop=min(stop, n_in))
             if self.dedup is not None:
                 with open(out_path, 'r+b') as o:
                     wr = y4m.Writer(o, ohdr, at=len(hb))
-                    n = self._run_dedup(cr, hdr, y4m.Frames.from_file(f, offs, 0, n_in, hdr.payload, fields=per), lambda k, p: wr.write(p),
-                                        order)
+                    n = self._run_dedup(cr, hdr, file_frames(0, n_in, fields=per), lambda k, p: wr.write(p), order)
                 return n, wr.frames
             lo, wins = cr.my_windows(n_in, full)
             if not wins:
@@ -330,7 +408,7 @@ class VideoRunner:
             last = R.first_window(n_in, full) + R.n_windows(n_in, full) - 1
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
             first = S.first_frame(lo) if self.scene_cut is not None else max(lo, 0)
-            frames = y4m.Frames.from_file(f, offs, first, lo + len(wins) + 3, hdr.payload, fields=per, behind=self._behind(order))
+            frames = file_frames(first, lo + len(wins) + 3, fields=per, behind=self._behind(order))
             at = R.block_offset(len(hb), lo, self._ratio(hdr), hdr.payload, full)
             kw = {'window_index': lambda j: lo + j} if full else {}
             with open(out_path, 'r+b') as o:
@@ -420,7 +498,7 @@ def parser():
                          'the GPU: every field becomes a progressive frame at its own time instant (the other field\'s rows are rebuilt '
                          'by an edge-directed line average), so n payloads at F count as 2n frames at 2F: --mfi M gives 2*M*F, --fps '
                          'must be at least 2F, and 50i --mfi 2 is 100p.  The output is progressive.  Mixed-mode streams (Im) stay '
-                         'refused.  Off by default (progressive input only); changes nothing for a progressive stream')
+                         'refused (film carried by 3:2 pulldown: --ivtc).  Off by default (progressive input only); changes nothing for a progressive stream')
     ap.add_argument('--deinterlace-mode', default='bob', choices=list(I.MODES),
                     help='with --deinterlace: bob (default) rebuilds the other field\'s rows from the field alone; adaptive also looks at '
                          'the two fields before and the two after (yadif\'s temporal rule around the bob\'s value): static parts keep '
@@ -429,6 +507,23 @@ def parser():
     ap.add_argument('--dedup-max-hold', type=int, default=K.DEFAULT_MAX_HOLD, metavar='N',
                     help='with --dedup: after N repeats in a row the next frame is kept whatever it shows (default %d), so a still '
                          'scene stays a sequence of frames N + 1 apart' % K.DEFAULT_MAX_HOLD)
+    ap.add_argument('--ivtc', action='store_true',
+                    help='inverse telecine: take film carried by 3:2 pulldown (24p as 29.97 frames/s; It, Ib, Im or a wrongly flagged Ip) '
+                         'and put the film frames back together before anything else runs, as ffmpeg\'s fieldmatch,decimate does: every '
+                         'payload keeps its top field and takes the bottom field that weaves to the least combed frame, and one frame '
+                         'in five, the closest repeat, is dropped.  n payloads at F count as n - n//5 frames at 4F/5, so --fps must be at '
+                         'least 4F/5 and --ivtc --fps 60000/1001 is the true 23.976 -> 59.94.  One rank only; not with --deinterlace.  '
+                         'Off by default')
+    ap.add_argument('--ivtc-cthresh', type=int, default=TC.DEFAULT_CTHRESH, metavar='T',
+                    help='with --ivtc: the comb threshold in 8-bit steps, 0..255 (default %d, that of ffmpeg\'s fieldmatch): a sample is '
+                         'combed when it differs from both rows next to it, in the same direction, by more than T' % TC.DEFAULT_CTHRESH)
+    ap.add_argument('--ivtc-combpel', type=int, default=TC.DEFAULT_COMBPEL, metavar='N',
+                    help='with --ivtc: a matched frame with more than N combed samples in one 16x16 luma block counts as combed '
+                         '(default %d, ffmpeg\'s)' % TC.DEFAULT_COMBPEL)
+    ap.add_argument('--ivtc-combed', default=TC.DEFAULT_COMBED, choices=list(TC.COMBED_MODES),
+                    help='with --ivtc: what a matched frame that is still combed becomes (video inserts, bad edits, a stream that starts '
+                         'mid-cycle): bob (default) rebuilds it from its top field, keep passes it through.  Its index is reported '
+                         'either way')
     T.add_arguments(ap)
     return ap
 
@@ -445,11 +540,15 @@ def main(argv=None):
         a.mfi = 8
     try:
         check_deinterlace_mode(a.deinterlace, a.deinterlace_mode, a.dedup or None)
+        check_ivtc(a.ivtc, a.deinterlace)
+        TC.check_params(a.ivtc_cthresh, a.ivtc_combpel, a.ivtc_combed)
     except ValueError as e:
         parser().error(str(e))
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     if world > 1 and a.dedup:
         raise SystemExit('demfi_amd.video: --dedup runs on one rank (which frames are kept depends on the whole prefix of the input)')
+    if world > 1 and a.ivtc:
+        raise SystemExit('demfi_amd.video: --ivtc runs on one rank (which frames are dropped depends on the whole prefix of the input)')
     if world > 1 and not (_is_regular(a.input) and os.path.isfile(a.input) and _is_regular(a.output)):
         raise SystemExit('demfi_amd.video: with %d ranks IN and OUT must be regular files (ranks write at byte offsets)' % world)
     out_fd = None
@@ -473,7 +572,8 @@ def main(argv=None):
     vr = VideoRunner(model, a.n_tst, a.mfi, batch=a.batch, matrix=a.matrix, fps=a.fps, scene_cut=a.scene_cut, full_length=a.full_length,
                      tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth, layouts=a.any_layout, dedup=a.dedup or None,
                      dedup_max_hold=a.dedup_max_hold, tile_high_depth=a.tile_high_depth, deinterlace=a.deinterlace,
-                     deinterlace_mode=a.deinterlace_mode)
+                     deinterlace_mode=a.deinterlace_mode, ivtc=a.ivtc, ivtc_cthresh=a.ivtc_cthresh, ivtc_combpel=a.ivtc_combpel,
+                     ivtc_combed=a.ivtc_combed)
     t0 = time.perf_counter()
     if world > 1:
         nw, nf = vr.run_file(a.input, a.output, world, rank)
@@ -502,7 +602,8 @@ def main(argv=None):
                           'instants_run': int(ti), 'instants_padded': int(tp), 'cut_windows': int(tc), 'dups': len(vr.last_dups),
                           'tiles': vr.last_plan.n_tiles if vr.last_plan is not None else 1,
                           'tile': vr.last_plan.label() if vr.last_plan is not None else None, 'depth': vr.last_depth, 'layout': vr.last_layout,
-                          'fields': vr.last_fields,
+                          'fields': vr.last_fields, 'ivtc_matches': vr.last_matches if a.ivtc else None,
+                          'ivtc_dropped': vr.last_dropped if a.ivtc else None, 'ivtc_combed': vr.last_combed if a.ivtc else None,
                           'weights': os.path.basename(a.checkpoint) if a.checkpoint else 'synthetic_state_dict(0) (random init: no checkpoint given)',
                           'out': a.output}), file=sys.stderr)
     D.finalize()

@@ -54,7 +54,8 @@ ANY_LAYOUT_HINT = ('; or keep the chroma layout: --any-layout accepts 4:2:2, 4:4
 DEINTERLACE_HINT = ('; or pass --deinterlace, which bobs the fields of an It (top field first) or Ib (bottom field first) stream '
                     'to progressive frames at twice the rate')
 MIXED_HINT = ('; --deinterlace takes It and Ib only: a mixed-mode stream (Im) changes its field order from frame to frame and needs '
-              'a field-order fix upstream (for example ffmpeg -vf fieldorder=tff)')
+              'a field-order fix upstream (for example ffmpeg -vf fieldorder=tff); if it is film carried by 3:2 pulldown, --ivtc takes it '
+              'as it is and gives the film frames back')
 _CHROMA = {None: '420jpeg', '420jpeg': '420jpeg', '420': '420jpeg', '420mpeg2': '420mpeg2'}
 _MAX_LINE = 4096
 
@@ -395,12 +396,14 @@ _LAYOUT_TAGS = dict([(lay, (lay, 8)) for lay in LAYOUTS[1:]] +
 _LAYOUT_NAMES = {'420': '4:2:0', '422': '4:2:2', '444': '4:4:4', 'mono': 'mono'}
 
 
-def parse_header(line, depths=(8,), layouts=('420',), fields=False):
+def parse_header(line, depths=(8,), layouts=('420',), fields=False, telecine=False):
     """One header line (bytes, with or without the trailing newline) -> Header.  Raises Y4MError.  ``depths``: the bit depths
     taken; the default is 8-bit only, ``DEPTHS`` also takes C420p10 / C420p12 / C420p14 / C420p16.  ``layouts``: the chroma
     layouts taken; the default is 4:2:0 only, ``LAYOUTS`` also takes C422 / C444 / Cmono and, with ``depths=DEPTHS``, their deep
     forms C422pNN / C444pNN / CmonoNN.  ``fields``: also take interlaced streams of a fixed field order, ``It`` and ``Ib``
-    (``Header.interlace`` is then 't' or 'b'; ``demfi_amd.deint`` makes frames of their fields); mixed-mode ``Im`` stays refused."""
+    (``Header.interlace`` is then 't' or 'b'; ``demfi_amd.deint`` makes frames of their fields); mixed-mode ``Im`` stays refused.
+    ``telecine``: also take ``It``, ``Ib`` and ``Im`` (``Header.interlace`` 't', 'b' or 'm') for inverse telecine, which matches
+    fields whatever their flagged order (``demfi_amd.telecine``)."""
     if isinstance(line, str):
         line = line.encode()
     line = line.rstrip(b'\n')
@@ -426,9 +429,9 @@ def parse_header(line, depths=(8,), layouts=('420',), fields=False):
                 raise Y4MError('Y4M: bad frame rate F%s' % val)
             fps = Fraction(int(m.group(1)), int(m.group(2)))
         elif tag == 'I':
-            if val == 'm':
+            if val == 'm' and not telecine:
                 _reject('mixed-mode interlaced video (Im)', MIXED_HINT)
-            if val not in ('p', '?') and not (fields and val in ('t', 'b')):
+            if val not in ('p', '?') and not ((fields or telecine) and val in ('t', 'b')) and not (telecine and val == 'm'):
                 _reject('interlaced video (I%s)' % val, DEINTERLACE_HINT if val in ('t', 'b') else '')
             inter = val
         elif tag == 'A':
@@ -530,12 +533,12 @@ def _frame_line(line, index):
 class Reader:
     """Sequential reader of a binary stream (a file, or stdin: nothing is seeked).  ``read_into(buf)`` fills one payload."""
 
-    def __init__(self, f, depths=(8,), layouts=('420',), fields=False):
+    def __init__(self, f, depths=(8,), layouts=('420',), fields=False, telecine=False):
         self.f = f
         line = _readline(f, 'header')
         if not line:
             raise Y4MError('Y4M: empty input: %s' % FIX)
-        self.header = parse_header(line, depths, layouts, fields)
+        self.header = parse_header(line, depths, layouts, fields, telecine)
         self.header_bytes = len(line)
         self.index = 0                                  # frames read so far
 
@@ -555,11 +558,11 @@ class Reader:
         return True
 
 
-def scan(f, depths=(8,), layouts=('420',), fields=False):
+def scan(f, depths=(8,), layouts=('420',), fields=False, telecine=False):
     """One pass over the frame headers of a seekable file: (Header, header bytes, [file offset of every payload]).  The
-    payloads are skipped, not read; a truncated last frame raises.  ``depths``, ``layouts``, ``fields``: as ``parse_header``."""
+    payloads are skipped, not read; a truncated last frame raises.  ``depths``, ``layouts``, ``fields``, ``telecine``: as ``parse_header``."""
     f.seek(0)
-    rd = Reader(f, depths, layouts, fields)
+    rd = Reader(f, depths, layouts, fields, telecine)
     size = os.fstat(f.fileno()).st_size if hasattr(f, 'fileno') else None
     p = rd.header.payload
     offs = []
@@ -575,6 +578,17 @@ def scan(f, depths=(8,), layouts=('420',), fields=False):
         offs.append(off)
         f.seek(off + p)
     return rd.header, rd.header_bytes, offs
+
+
+def file_fetch(f, offsets):
+    """fetch(i, buf) over a scanned file (``scan``): payload i of the file into ``buf`` by seek + readinto."""
+    def fetch(i, buf):
+        f.seek(offsets[i])
+        mv = memoryview(buf).cast('B')
+        if _readinto_full(f, mv) != len(mv):
+            raise Y4MError('Y4M: truncated frame %d' % i)
+        return True
+    return fetch
 
 
 class Frames:
@@ -615,13 +629,7 @@ class Frames:
 
     @classmethod
     def from_file(cls, f, offsets, first, stop, payload, pinned=None, fields=1, behind=0):
-        def fetch(i, buf):
-            f.seek(offsets[i])
-            mv = memoryview(buf).cast('B')
-            if _readinto_full(f, mv) != len(mv):
-                raise Y4MError('Y4M: truncated frame %d' % i)
-            return True
-        return cls(payload=payload, fetch=fetch, first=first, stop=min(stop + behind, fields * len(offsets)), pinned=pinned,
+        return cls(payload=payload, fetch=file_fetch(f, offsets), first=first, stop=min(stop + behind, fields * len(offsets)), pinned=pinned,
                    fields=fields, behind=behind)
 
     def has(self, i):

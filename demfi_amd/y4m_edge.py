@@ -442,3 +442,79 @@ class Y4mEdge:
         for j, c in enumerate(counts):
             sink(k0 + j, self.h_yuv[i][pos:pos + c])
             pos += c
+
+
+class IvtcScorer:
+    """The scorer of ``telecine.FilmFrames`` on the GPU (``--ivtc``): the two launches of csrc/ivtc.hip over a device ring of luma
+    planes of its own, on a stream of its own.  ``put`` copies the luma of a new payload (its first h*w samples) into the ring
+    slot i mod RING through a pinned twin; ``comb`` and ``sad`` are ONE launch each, read back with one event wait; neither waits
+    on the compute stream.  RING = 8: cycle c reads payloads 5c-2 .. 5c+5 (``FilmFrames``), and a slot is taken back 8 payloads
+    later, after the waits of the cycle that read it.  MAX = the entries of one call: a cycle has five."""
+    RING, MAX = 8, 8
+
+    def __init__(self, lib, h, w, depth, cthresh, device):
+        self.lib, self.h, self.w, self.es = lib, h, w, 2 if depth > 8 else 1
+        self.thresh = cthresh << (depth - 8)
+        self.Lb = h * w * self.es                            # bytes of a luma plane
+        self.stream = torch.cuda.Stream(device)
+        with torch.cuda.stream(self.stream):                 # the device buffers belong to the stream that alone touches them
+            self.ring = torch.empty((self.RING, self.Lb), dtype=torch.uint8, device=device)
+            self.offs = torch.empty(4 * self.MAX, dtype=torch.int64, device=device)
+            self.cnt = torch.empty(6 * self.MAX, dtype=torch.int32, device=device)
+            self.sads = torch.empty(self.MAX, dtype=torch.int64, device=device)
+        self.h_ring = torch.empty((self.RING, self.Lb), dtype=torch.uint8).pin_memory()
+        self.h_offs = torch.empty(4 * self.MAX, dtype=torch.int64).pin_memory()
+        self.h_cnt = torch.empty(6 * self.MAX, dtype=torch.int32).pin_memory()
+        self.h_sads = torch.empty(self.MAX, dtype=torch.int64).pin_memory()
+        self.held = {}                                       # payload index -> ring slot
+
+    def put(self, i, payload):
+        sl = i % self.RING
+        if sl in self.held.values():
+            raise RuntimeError('ivtc: payload %d needs the ring slot of a payload still in use' % i)
+        self.held[i] = sl
+        self.h_ring[sl].numpy()[:] = np.frombuffer(memoryview(payload).cast('B'), np.uint8)[:self.Lb]
+        with torch.cuda.stream(self.stream):
+            self.ring[sl].copy_(self.h_ring[sl], non_blocking=True)
+
+    def forget(self, i):
+        self.held.pop(i, None)
+
+    def _off(self, i):
+        return -1 if i is None else self.held[i] * self.Lb
+
+    def _call(self, offs, launch, dev, host, words):
+        """The offsets go up, ``launch`` runs behind them on the stream, ``words`` results come back; one event wait."""
+        m = len(offs)
+        self.h_offs[:m] = torch.tensor(offs, dtype=torch.int64)
+        with torch.cuda.stream(self.stream):
+            self.offs[:m].copy_(self.h_offs[:m], non_blocking=True)
+            launch(self.stream.cuda_stream)
+            host[:words].copy_(dev[:words], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        ev.synchronize()
+        return host[:words].tolist()
+
+    def comb(self, entries):
+        n = len(entries)
+        if n > self.MAX:
+            raise RuntimeError('ivtc: %d entries in one call, %d at most' % (n, self.MAX))
+        if n == 0:
+            return []
+        offs = [self._off(t) for t, _ in entries] + [self._off(b) for _, bots in entries for b in bots]
+        out = self._call(offs, lambda st: L.check(self.lib.demfi_luma_comb_counts(
+            self.ring.data_ptr(), self.offs.data_ptr(), self.offs[n:].data_ptr(), n, self.h, self.w, self.es, self.thresh,
+            self.cnt.data_ptr(), st), 'luma_comb_counts'), self.cnt, self.h_cnt, 6 * n)
+        return [[None if b is None else (out[6 * i + 2 * k], out[6 * i + 2 * k + 1]) for k, b in enumerate(bots)]
+                for i, (_, bots) in enumerate(entries)]
+
+    def sad(self, quads):
+        n = len(quads)
+        if n > self.MAX:
+            raise RuntimeError('ivtc: %d entries in one call, %d at most' % (n, self.MAX))
+        if n == 0:
+            return []
+        return self._call([self._off(i) for q in quads for i in q], lambda st: L.check(self.lib.demfi_luma_woven_sad(
+            self.ring.data_ptr(), self.offs.data_ptr(), n, self.h, self.w, self.es, self.sads.data_ptr(), st), 'luma_woven_sad'),
+            self.sads, self.h_sads, n)

@@ -461,6 +461,26 @@ int demfi_yuv_bob(void* payloads, int64_t stride_bytes, int n, int h, int w, int
 int demfi_yuv_deint_adaptive(void* base, int64_t size_bytes, const int64_t* offsets, const int64_t* offsets_dev, int n, int h, int w,
                              int layout, int sample_bytes, uint64_t odd_mask, void* stream);
 
+/* ---- inverse telecine of the Y4M edge (csrc/ivtc.hip; demfi_amd/video.py --ivtc) ------------------------------------------------
+ * A woven frame W(top, bot) has the even rows of the luma plane (the first h*w samples of a payload; sample_bytes = 1, or 2 for
+ * 16-bit little-endian samples) of payload `top` and the odd rows of that of payload `bot`; it is read in place, never built.
+ * Offsets are int64 BYTE offsets from base in DEVICE memory (even ones for 16-bit samples).  Any h, w in 2..16384; one launch for
+ * n entries; nothing but the output words is written, and those are zeroed on the stream first; n = 0 does nothing.
+ * luma_comb_counts: entry i has the top payload at top_offsets[i] and three candidates for the bottom field at
+ * bot_offsets[3i + k], k = 0, 1, 2 (c, p, n of demfi_amd/telecine.py), -1 for an absent one.  out[6i + 2k] = the most combed
+ * samples in one 16x16 block (blocks from the top-left corner, partial at the right and bottom), out[6i + 2k + 1] = the combed
+ * samples of the plane, of W(top, candidate k); both stay 0 for an absent candidate.  A sample of row y, 2 <= y <= h-3, is combed
+ * when, with d1 = W[y] - W[y-1] and d2 = W[y] - W[y+1], (d1 > T and d2 > T) or (d1 < -T and d2 < -T), and
+ * |W[y-2] + 4 W[y] + W[y+2] - 3 (W[y-1] + W[y+1])| > 6 T, T = thresh_s = the threshold times 2^(depth-8), 0 .. 2^20.  Exact
+ * integers; the numpy definition is telecine.comb_counts_np.  The three candidates are scored in one pass over their shared even
+ * rows: the top plane and each present candidate's plane are read about once.
+ * luma_woven_sad: out[i] (uint64) = sum |W(a_top, a_bot) - W(b_top, b_bot)| over the luma plane, the four payloads at
+ * offsets[4i .. 4i+3] in that order; the numpy definition is telecine.woven_sad_np. */
+int demfi_luma_comb_counts(const uint8_t* base, const int64_t* top_offsets, const int64_t* bot_offsets, int n, int h, int w,
+                           int sample_bytes, int thresh_s, uint32_t* out, void* stream);
+int demfi_luma_woven_sad(const uint8_t* base, const int64_t* offsets, int n, int h, int w, int sample_bytes, uint64_t* out,
+                         void* stream);
+
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
  * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
