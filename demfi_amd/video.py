@@ -69,6 +69,23 @@ frame that is still combed (more than ``--ivtc-combpel`` samples in a 16x16 bloc
 (``--ivtc-combed bob``, the default) or passed through (``keep``) and reported.  Not offered: hybrid film / video material (30i
 sections are decimated like the rest), other cadences, a scene-change guard for the decimator, interlaced output, more than one
 rank, and ``--ivtc`` together with ``--deinterlace``.
+
+``--crop auto`` finds letterbox and pillarbox bars (scope films in 16:9, 4:3 in 16:9, windowboxed captures) and keeps them away from
+the network (``demfi_amd.letterbox``): a pre-pass counts, for every row and column of the luma plane of the probed payloads
+(``--crop-probe``, default all), the samples above ``--crop-limit`` (24 at 8 bits, ffmpeg ``cropdetect``'s) in ONE launch per 16
+planes (csrc/crop.hip, defined by ``letterbox.line_counts_np``); a line with more than ``--crop-noise`` (1/256) of its samples lit is
+picture, the union of the frames' extents, grown to the chroma grid, is the picture rectangle.  Every payload is then cropped on the
+host as the last stage in front of the frames (behind ``--ivtc``'s film frames, in front of the deinterlacer, whose row pairs the
+alignment keeps), everything downstream -- the network, scene cuts, repeated frames, tiles, rank sharding -- runs on the smaller
+frame, and every output payload is padded back with exact black of the stream's range (``--crop-output pad``, the default: the
+output has the input's size) or written as it is (``cropped``).  The forward's cost follows the area, so 1920x800 of picture in
+1920x1080 runs about a quarter faster, and no interpolated frame carries picture into the bars.  ``--crop T:B:L:R`` gives the four
+bar widths instead: nothing is probed, and it works on pipes, where ``auto`` is refused because the bars of a stream are known only
+at its end.  With several ranks every rank runs the same pre-pass and arrives at the same rectangle.  A rectangle below 64x64 is
+not cropped to (``auto``: reported; explicit: an error, like a misaligned one); ``auto`` on a clip without bars, or an all-black
+one, gives the bytes of a run without the switch.  Not offered: bars that change within a stream (the union is taken), ``--crop`` on
+``demfi_amd.clip``, restoring the input's own bar samples (output bars are exact black); scene-cut and repeated-frame decisions are
+made over the cropped payloads, so they can differ from those of an uncropped run.
 """
 import os
 import sys
@@ -80,6 +97,7 @@ from . import _lib as L
 from . import cadence as K
 from . import deint as I
 from . import dist as D
+from . import letterbox as LB
 from . import retime as R
 from . import scene as S
 from . import telecine as TC
@@ -120,6 +138,20 @@ def check_ivtc(ivtc, deinterlace, world=1):
     if ivtc and world > 1:
         raise ValueError('VideoRunner: ivtc with %d ranks: which frames are dropped depends on the whole prefix of the input, so a rank '
                          'cannot place its block of windows from k and r alone; run --ivtc on one rank' % world)
+
+
+def check_crop(crop, limit=LB.DEFAULT_LIMIT, noise=LB.DEFAULT_NOISE, probe=LB.DEFAULT_PROBE, output='pad'):
+    """The crop switches checked: (crop, (limit, noise, probe, output)).  The four secondary ones say how ``crop`` works, so any of
+    them without it is an error."""
+    crop, params = LB.check_crop(crop), LB.check_params(limit, noise, probe, output)
+    if crop is None and params != (LB.DEFAULT_LIMIT, LB.DEFAULT_NOISE, LB.DEFAULT_PROBE, 'pad'):
+        raise ValueError('--crop-limit, --crop-noise, --crop-probe and --crop-output (crop_limit, crop_noise, crop_probe, crop_output) '
+                         'say how --crop works: give --crop auto or --crop T:B:L:R with them')
+    return crop, params
+
+
+AUTO_NEEDS_A_FILE = ('--crop auto needs a regular input file: the bars of a stream are known only at its end; give the four bar '
+                     'widths instead, --crop T:B:L:R (crop=(T, B, L, R)), for instance from ffmpeg -vf cropdetect')
 
 
 def check_deinterlace_mode(deinterlace, mode, dedup):
@@ -169,17 +201,35 @@ class VideoRunner:
     block above which a matched frame counts as combed, ``ivtc_combed`` what happens to such a frame: 'bob' (default) or 'keep'.
     One rank only, and not with ``deinterlace`` (refused here).  After a run ``last_matches`` = {'c': , 'p': , 'n': } counts of the
     payloads' matches, ``last_dropped`` = the input payloads dropped, ``last_combed`` = the film frames left combed.  Off by
-    default: nothing changes anywhere without it."""
+    default: nothing changes anywhere without it.  ``crop``: None (default), 'auto' or the bar widths (T, B, L, R) in luma samples
+    (``demfi_amd.letterbox``): the payloads are cropped to the picture rectangle in front of everything that runs on the GPU and the
+    outputs are padded back with black (``crop_output`` 'pad', default) or written at the cropped size ('cropped').  'auto' finds the
+    rectangle in a pre-pass over the luma planes of ``crop_probe`` ('all', or N payloads spread over the input) with the limit
+    ``crop_limit`` (8-bit steps, default 24) and the allowance ``crop_noise`` (a Fraction of a line, default 1/256); it needs a regular
+    file (``run_file``) and is refused on ``run_stream`` before anything is allocated; the four numbers work everywhere and launch
+    nothing.  An explicit rectangle that is misaligned (top and left on the chroma grid, rows in units of 4 for interlaced 4:2:0) or
+    keeps fewer than 64 rows or columns is a ValueError once the header is known, before a library is loaded.  After a run
+    ``last_crop`` = (top, bottom, left, right) or None when nothing was cropped, ``last_crop_probed`` = payloads probed,
+    ``last_crop_note`` = None or why an 'auto' rectangle was not used.  Not offered: bars that change within a stream (the union is
+    taken), restoring the input's own bar samples (output bars are exact black); scene cuts and repeated frames are decided over the
+    cropped payloads, so they can differ from those of an uncropped run.  The four secondary arguments without ``crop`` are an
+    error; without ``crop`` nothing changes anywhere: no buffer, stream or launch is added."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
                  tile_high_depth=False, deinterlace=False, deinterlace_mode='bob', ivtc=False, ivtc_cthresh=TC.DEFAULT_CTHRESH,
-                 ivtc_combpel=TC.DEFAULT_COMBPEL, ivtc_combed=TC.DEFAULT_COMBED, **runner_kw):
+                 ivtc_combpel=TC.DEFAULT_COMBPEL, ivtc_combed=TC.DEFAULT_COMBED, crop=None, crop_limit=LB.DEFAULT_LIMIT,
+                 crop_noise=LB.DEFAULT_NOISE, crop_probe=LB.DEFAULT_PROBE, crop_output='pad', **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.crop, (self.crop_limit, self.crop_noise, self.crop_probe, self.crop_output) = check_crop(
+            crop, crop_limit, crop_noise, crop_probe, crop_output)
+        self.last_crop, self.last_crop_probed, self.last_crop_note, self.last_crop_seconds = None, 0, None, 0.0
+        self.last_input_size = None
         self.ivtc = bool(ivtc)
         self.ivtc_params = TC.check_params(ivtc_cthresh, ivtc_combpel, ivtc_combed)
         check_ivtc(self.ivtc, deinterlace)
         self._film = None
+        self._matrix_h = None                            # a cropped run: the input's own height chooses the 'auto' matrix
         self.deinterlace_mode = deinterlace_mode
         if matrix not in ('auto',) + tuple(y4m.MATRICES):
             raise ValueError("matrix must be 'auto', 'bt601' or 'bt709', got %r" % matrix)
@@ -275,6 +325,82 @@ class VideoRunner:
         self._film = TC.FilmFrames(read, hdr, IvtcScorer(L.load(), hdr.h, hdr.w, hdr.depth, cthresh, device), combpel, combed)
         return self._film
 
+    def _crop_stage(self, in_hdr, per, probe=None):
+        """The ``letterbox.Cropper`` of this input (``in_hdr``: its header, ``per``: 2 when its payloads stay interlaced), or None
+        when nothing is cropped; before anything else is allocated for the input.  ``probe()``: the pre-pass of 'auto', which gives the
+        detected rectangle or None.  Sets ``last_crop`` (the rectangle or None), ``last_crop_probed`` and ``last_crop_note``."""
+        self.last_crop, self.last_crop_probed, self.last_crop_note, self.last_crop_seconds = None, 0, None, 0.0
+        self.last_input_size = (in_hdr.h, in_hdr.w)
+        if self.crop is None:
+            return None
+        if self.crop == 'auto':
+            rect, explicit = probe(), False
+        else:
+            rect, explicit = LB.bars_rect(self.crop, in_hdr.h, in_hdr.w), True
+        self.last_crop, self.last_crop_note = LB.check_rect(rect, in_hdr.h, in_hdr.w, in_hdr.layout, per, explicit)
+        return LB.Cropper(in_hdr, self.last_crop) if self.last_crop is not None else None
+
+    def crop_report(self):
+        """One line on what the crop stage of the last run did."""
+        if self.last_crop is None:
+            line = self.last_crop_note or 'crop: the picture fills the frame; nothing is cropped'
+        else:
+            (t, b, l, r), (h, w) = self.last_crop, self.last_input_size
+            line = 'crop: bars %d:%d:%d:%d (T:B:L:R), %dx%d of %dx%d runs, output %s' % (t, h - b, l, w - r, r - l, b - t, w, h,
+                                                                                          self.crop_output)
+        if self.crop == 'auto':
+            line += '; %d payloads probed in %.2f s' % (self.last_crop_probed, self.last_crop_seconds)
+        return line
+
+    def _probe_rect(self, f, offs, in_hdr):
+        """The pre-pass of ``crop='auto'`` over the scanned file ``f``: the union of the extents of the probed payloads' luma planes,
+        counted on the GPU.  Every rank probes the same payloads and arrives at the same rectangle: no collective."""
+        import time
+        from .y4m_edge import LineScorer
+        t0 = time.perf_counter()
+        sc = LineScorer(L.load(), in_hdr.h, in_hdr.w, in_hdr.depth, self.crop_limit, next(self.model.parameters()).device)
+        ext = LB.Extent(self.crop_noise)
+        for rows, cols in sc.counts(f, offs, LB.probe_indices(len(offs), self.crop_probe)):
+            ext.push(rows, cols)
+        self.last_crop_probed, self.last_crop_seconds = sc.probed, time.perf_counter() - t0
+        return ext.rect()
+
+    def _headers(self, full_hdr, cropper):
+        """(the header everything downstream works on, the header of the output written) of an input whose progressive header is
+        ``full_hdr``: the cropped one runs; the full size is written unless ``crop_output`` is 'cropped'."""
+        if cropper is None:
+            return full_hdr, self._out_header(full_hdr)
+        hdr = LB.cropped_header(full_hdr, cropper.rect)
+        ohdr = self._out_header(hdr)
+        return hdr, (ohdr if self.crop_output == 'cropped' else LB.resized_header(ohdr, full_hdr.h, full_hdr.w))
+
+    @staticmethod
+    def _cropped(fetch, cropper):
+        """``fetch(i, buf)`` of full payloads -> one of cropped payloads: the full payload goes into a scratch buffer, its rectangle into ``buf``."""
+        if cropper is None:
+            return fetch
+        import numpy as np
+        scratch = np.empty(cropper.Pf, np.uint8)
+
+        def crop_fetch(i, buf):
+            if not fetch(i, scratch):
+                return False
+            cropper.crop_into(scratch, buf)
+            return True
+        return crop_fetch
+
+    def _padded(self, sink, cropper):
+        """``sink(k, payloads)`` of full payloads -> one of cropped payloads, padded back to the full size with black on the way."""
+        if cropper is None or self.crop_output == 'cropped':
+            return sink
+        import numpy as np
+
+        def pad_sink(k, payloads):
+            full = np.empty((len(payloads), cropper.Pf), np.uint8)
+            cropper.pad_into(payloads, full)
+            sink(k, full)
+        return pad_sink
+
     def _behind(self, order):
         """``y4m.Frames(behind=...)``: the adaptive mode reads two fields before and after every field it rebuilds."""
         return 2 if order is not None and self.deinterlace_mode == 'adaptive' else 0
@@ -313,7 +439,7 @@ class VideoRunner:
         return n
 
     def _edge(self, hdr, with_s1, order=None):
-        return YuvEdge(y4m.auto_matrix(hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
+        return YuvEdge(y4m.auto_matrix(self._matrix_h or hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
                        self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup, order, self.deinterlace_mode)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
@@ -330,22 +456,31 @@ class VideoRunner:
     def run_stream(self, src, dst):
         """One rank, sequential binary streams (stdin / stdout work): nothing is seeked, the input is read in batches of
         windows and every batch is written (and flushed) as it drains.  Returns (windows, frames written)."""
+        if self.crop == 'auto':
+            raise ValueError('VideoRunner.run_stream: ' + AUTO_NEEDS_A_FILE)
         rd = y4m.Reader(src, self.depths, self.layouts, self.deinterlace, self.ivtc)
         self._film = None
-        hdr, order, per = self._progressive(rd.header)
+        full_hdr, order, per = self._progressive(rd.header)
+        cropper = self._crop_stage(rd.header, per)
+        hdr, out_hdr = self._headers(full_hdr, cropper)  # hdr: what runs (cropped); out_hdr: what is written
+        self._matrix_h = full_hdr.h if cropper is not None else None
         self._check_depth(hdr)
         cr = self._clip_runner(hdr, 1, 0)
-        wr = y4m.Writer(dst, self._out_header(hdr))
+        wr = y4m.Writer(dst, out_hdr)
         if self.ivtc:                                    # downstream sees an ordinary progressive input at the film rate
             film = self._film_frames(lambda i, buf: rd.read_into(buf), rd.header, cr.runner.engine.device)
-            frames = y4m.Frames(payload=hdr.payload, fetch=film, full_length=self.full_length)
+            frames = y4m.Frames(payload=hdr.payload, fetch=self._cropped(film, cropper), full_length=self.full_length)
+        elif cropper is not None:                        # the crop is the last host stage in front of the frames
+            frames = y4m.Frames(payload=hdr.payload, fetch=self._cropped(lambda i, buf: rd.read_into(buf), cropper),
+                                full_length=self.full_length, fields=per, behind=self._behind(order))
         else:
             frames = y4m.Frames(rd, full_length=self.full_length, fields=per, behind=self._behind(order))
         self.last_dups = []
 
-        def sink(k, payloads):
+        def write(k, payloads):
             wr.write(payloads)
             dst.flush()
+        sink = self._padded(write, cropper)
         if self.dedup is not None:
             n = self._run_dedup(cr, hdr, frames, sink, order)
             dst.flush()
@@ -373,33 +508,38 @@ class VideoRunner:
         self.last_dups, self._film = [], None
         with open(in_path, 'rb') as f:
             in_hdr, _, offs = y4m.scan(f, self.depths, self.layouts, self.deinterlace, self.ivtc)
-            hdr, order, per = self._progressive(in_hdr)
+            full_hdr, order, per = self._progressive(in_hdr)
+            cropper = self._crop_stage(in_hdr, per, lambda: self._probe_rect(f, offs, in_hdr))
+            hdr, out_hdr = self._headers(full_hdr, cropper)                          # hdr: what runs (cropped); out_hdr: what is written
+            self._matrix_h = full_hdr.h if cropper is not None else None
             self._check_depth(hdr)
             n_in = TC.n_film_frames(len(offs)) if self.ivtc else per * len(offs)     # an interlaced input counts as its fields
-            ohdr = self._out_header(hdr)
-            hb = ohdr.encode()
+            hb = out_hdr.encode()
             total = self._n_out(n_in, hdr)
             if rank == 0:
                 with open(out_path, 'wb') as o:
                     o.write(hb)
-                    o.truncate(y4m.frame_offset(len(hb), total, hdr.payload))
+                    o.truncate(y4m.frame_offset(len(hb), total, out_hdr.payload))
             D.barrier()
             cr = self._clip_runner(hdr, world, rank)
             full = self.full_length
 
             def file_frames(first, stop, **kw):
                 """Frames first .. stop-1 of the input: its payloads by seek, or (one rank, from frame 0) the film frames made of them."""
-                if not self.ivtc:
+                if not self.ivtc and cropper is None:
                     return y4m.Frames.from_file(f, offs, first, stop, hdr.payload, **kw)
+                if not self.ivtc:                        # ``from_file`` with the crop behind its fetch
+                    return y4m.Frames(payload=hdr.payload, fetch=self._cropped(y4m.file_fetch(f, offs), cropper), first=first,
+                                      stop=min(stop + kw.get('behind', 0), kw.get('fields', 1) * len(offs)), **kw)
                 if first != 0:
                     raise RuntimeError('ivtc: film frames are made in order from frame 0, not from frame %d' % first)
                 fetch = y4m.file_fetch(f, offs)
                 film = self._film_frames(lambda i, buf: i < len(offs) and fetch(i, buf), in_hdr, cr.runner.engine.device)
-                return y4m.Frames(payload=hdr.payload, fetch=film, stop=min(stop, n_in))
+                return y4m.Frames(payload=hdr.payload, fetch=self._cropped(film, cropper), stop=min(stop, n_in))
             if self.dedup is not None:
                 with open(out_path, 'r+b') as o:
-                    wr = y4m.Writer(o, ohdr, at=len(hb))
-                    n = self._run_dedup(cr, hdr, file_frames(0, n_in, fields=per), lambda k, p: wr.write(p), order)
+                    wr = y4m.Writer(o, out_hdr, at=len(hb))
+                    n = self._run_dedup(cr, hdr, file_frames(0, n_in, fields=per), self._padded(lambda k, p: wr.write(p), cropper), order)
                 return n, wr.frames
             lo, wins = cr.my_windows(n_in, full)
             if not wins:
@@ -409,11 +549,12 @@ class VideoRunner:
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
             first = S.first_frame(lo) if self.scene_cut is not None else max(lo, 0)
             frames = file_frames(first, lo + len(wins) + 3, fields=per, behind=self._behind(order))
-            at = R.block_offset(len(hb), lo, self._ratio(hdr), hdr.payload, full)
+            at = R.block_offset(len(hb), lo, self._ratio(hdr), out_hdr.payload, full)
             kw = {'window_index': lambda j: lo + j} if full else {}
             with open(out_path, 'r+b') as o:
-                wr = y4m.Writer(o, ohdr, at=at)
-                n = self._run(cr, hdr, lambda: lo, lambda: cr.runner.run_clip_u8(frames, wins, lambda k, p: wr.write(p), batch=self.batch,
+                wr = y4m.Writer(o, out_hdr, at=at)
+                sink = self._padded(lambda k, p: wr.write(p), cropper)
+                n = self._run(cr, hdr, lambda: lo, lambda: cr.runner.run_clip_u8(frames, wins, sink, batch=self.batch,
                                                                                  yuv=self._edge(hdr, lambda k: lo + k == last, order), **kw))
             self.last_decode_peak = frames.peak
             return n, wr.frames
@@ -437,6 +578,21 @@ def _fps_arg(text):
     except ValueError as e:
         import argparse
         raise argparse.ArgumentTypeError(str(e))
+
+
+def _value_arg(fn):
+    def arg(text):
+        try:
+            return fn(text)
+        except ValueError as e:
+            import argparse
+            raise argparse.ArgumentTypeError(str(e))
+    return arg
+
+
+_crop_arg = _value_arg(LB.parse_crop)
+_crop_probe_arg = _value_arg(LB.parse_probe)
+_crop_noise_arg = _value_arg(lambda text: LB.check_params(noise=text.replace(':', '/'))[1])
 
 
 def parser():
@@ -524,6 +680,21 @@ def parser():
                     help='with --ivtc: what a matched frame that is still combed becomes (video inserts, bad edits, a stream that starts '
                          'mid-cycle): bob (default) rebuilds it from its top field, keep passes it through.  Its index is reported '
                          'either way')
+    ap.add_argument('--crop', type=_crop_arg, default=None, metavar='auto|T:B:L:R',
+                    help='keep letterbox and pillarbox bars away from the network: crop every payload to the picture, run on the smaller '
+                         'frame, and pad the output back with black.  auto: find the bars in a pre-pass over the input (a regular file, '
+                         'not a pipe); T:B:L:R: the widths of the top, bottom, left and right bars in luma samples, for instance from '
+                         'ffmpeg -vf cropdetect (works on pipes).  Edges lie on the chroma grid (even for 4:2:0; rows in units of 4 with '
+                         '--deinterlace); at least %dx%d is kept.  Off by default' % (LB.MIN_ACTIVE, LB.MIN_ACTIVE))
+    ap.add_argument('--crop-limit', type=int, default=None, metavar='L',
+                    help='with --crop auto: a luma sample above L (8-bit steps, 0..255) is lit; default %d, ffmpeg cropdetect\'s' % LB.DEFAULT_LIMIT)
+    ap.add_argument('--crop-noise', type=_crop_noise_arg, default=None, metavar='N/D',
+                    help='with --crop auto: a row or column is picture when more than this fraction of its samples is lit (default %s), '
+                         'so specks do not make a line and subtitle text does' % LB.DEFAULT_NOISE)
+    ap.add_argument('--crop-probe', type=_crop_probe_arg, default=None, metavar='all|N',
+                    help='with --crop auto: look at all payloads (default) or at N spread evenly over the input')
+    ap.add_argument('--crop-output', default=None, choices=list(LB.OUTPUTS),
+                    help='with --crop: pad (default) writes the input\'s frame size with black bars, cropped writes the picture rectangle alone')
     T.add_arguments(ap)
     return ap
 
@@ -542,6 +713,15 @@ def main(argv=None):
         check_deinterlace_mode(a.deinterlace, a.deinterlace_mode, a.dedup or None)
         check_ivtc(a.ivtc, a.deinterlace)
         TC.check_params(a.ivtc_cthresh, a.ivtc_combpel, a.ivtc_combed)
+        if a.crop is None and any(v is not None for v in (a.crop_limit, a.crop_noise, a.crop_probe, a.crop_output)):
+            raise ValueError('--crop-limit, --crop-noise, --crop-probe and --crop-output say how --crop works: give --crop auto or '
+                             '--crop T:B:L:R with them')
+        crop_kw = {k: v for k, v in (('crop', a.crop), ('crop_limit', a.crop_limit), ('crop_noise', a.crop_noise),
+                                     ('crop_probe', a.crop_probe), ('crop_output', a.crop_output)) if v is not None}
+        check_crop(*(crop_kw.get(k, d) for k, d in (('crop', None), ('crop_limit', LB.DEFAULT_LIMIT), ('crop_noise', LB.DEFAULT_NOISE),
+                                                    ('crop_probe', LB.DEFAULT_PROBE), ('crop_output', 'pad'))))
+        if a.crop == 'auto' and not (_is_regular(a.input) and os.path.isfile(a.input) and _is_regular(a.output)):
+            raise ValueError(AUTO_NEEDS_A_FILE + ' (and a regular output file)')
     except ValueError as e:
         parser().error(str(e))
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
@@ -573,9 +753,9 @@ def main(argv=None):
                      tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth, layouts=a.any_layout, dedup=a.dedup or None,
                      dedup_max_hold=a.dedup_max_hold, tile_high_depth=a.tile_high_depth, deinterlace=a.deinterlace,
                      deinterlace_mode=a.deinterlace_mode, ivtc=a.ivtc, ivtc_cthresh=a.ivtc_cthresh, ivtc_combpel=a.ivtc_combpel,
-                     ivtc_combed=a.ivtc_combed)
+                     ivtc_combed=a.ivtc_combed, **crop_kw)
     t0 = time.perf_counter()
-    if world > 1:
+    if world > 1 or a.crop == 'auto':                        # the pre-pass seeks: regular files
         nw, nf = vr.run_file(a.input, a.output, world, rank)
     else:
         src = sys.stdin.buffer if a.input == '-' else open(a.input, 'rb')
@@ -592,6 +772,8 @@ def main(argv=None):
               float(vr.last_cut_windows)]
     tw, tf, tst, ti, tp, tc = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
     if rank == 0:
+        if a.crop is not None:
+            print('demfi_amd.video: ' + vr.crop_report(), file=sys.stderr)
         if tw == 0:
             print('demfi_amd.video: %s: no window, only the header was written' %
                   ('no input frame' if a.full_length else 'fewer than 4 input frames'), file=sys.stderr)
@@ -604,6 +786,8 @@ def main(argv=None):
                           'tile': vr.last_plan.label() if vr.last_plan is not None else None, 'depth': vr.last_depth, 'layout': vr.last_layout,
                           'fields': vr.last_fields, 'ivtc_matches': vr.last_matches if a.ivtc else None,
                           'ivtc_dropped': vr.last_dropped if a.ivtc else None, 'ivtc_combed': vr.last_combed if a.ivtc else None,
+                          'crop': list(vr.last_crop) if vr.last_crop is not None else None,
+                          'crop_probe_seconds': round(vr.last_crop_seconds, 3) if a.crop == 'auto' else None,
                           'weights': os.path.basename(a.checkpoint) if a.checkpoint else 'synthetic_state_dict(0) (random init: no checkpoint given)',
                           'out': a.output}), file=sys.stderr)
     D.finalize()

@@ -518,3 +518,51 @@ class IvtcScorer:
         return self._call([self._off(i) for q in quads for i in q], lambda st: L.check(self.lib.demfi_luma_woven_sad(
             self.ring.data_ptr(), self.offs.data_ptr(), n, self.h, self.w, self.es, self.sads.data_ptr(), st), 'luma_woven_sad'),
             self.sads, self.h_sads, n)
+
+
+class LineScorer:
+    """The pre-pass of ``--crop auto`` on the GPU (``demfi_amd.letterbox``): the lit samples of every row and column of the luma
+    planes of the probed payloads, ``demfi_luma_line_counts`` of csrc/crop.hip, on a stream of its own over device buffers that
+    only that stream touches.  ``counts(f, offsets, indices)`` reads only the luma of each probed payload (its first h*w samples,
+    by seek) straight into a pinned ring, and per batch of up to MAX planes makes the copies, ONE launch and the copies back, read
+    with one event wait; it never waits on the compute stream.  ``probed``: the payloads looked at so far."""
+    MAX = 16
+
+    def __init__(self, lib, h, w, depth, limit, device):
+        self.lib, self.h, self.w, self.es = lib, h, w, 2 if depth > 8 else 1
+        self.thresh = limit << (depth - 8)
+        self.Lb = h * w * self.es                            # bytes of a luma plane
+        self.stream = torch.cuda.Stream(device)
+        with torch.cuda.stream(self.stream):
+            self.ring = torch.empty((self.MAX, self.Lb), dtype=torch.uint8, device=device)
+            self.offs = torch.arange(self.MAX, dtype=torch.int64, device=device) * self.Lb
+            self.rows = torch.empty((self.MAX, h), dtype=torch.int32, device=device)
+            self.cols = torch.empty((self.MAX, w), dtype=torch.int32, device=device)
+        self.h_ring = torch.empty((self.MAX, self.Lb), dtype=torch.uint8).pin_memory()
+        self.h_rows = torch.empty((self.MAX, h), dtype=torch.int32).pin_memory()
+        self.h_cols = torch.empty((self.MAX, w), dtype=torch.int32).pin_memory()
+        self.probed = 0
+
+    def counts(self, f, offsets, indices):
+        """(rows [h], cols [w]) uint32 of payload i of the scanned file ``f`` (``y4m.scan``'s offsets) for every i of ``indices``."""
+        from .y4m import file_fetch
+        fetch = file_fetch(f, offsets)
+        for b0 in range(0, len(indices), self.MAX):
+            batch = indices[b0:b0 + self.MAX]
+            m = len(batch)
+            for j, i in enumerate(batch):
+                fetch(i, self.h_ring[j].numpy())
+            with torch.cuda.stream(self.stream):
+                self.ring[:m].copy_(self.h_ring[:m], non_blocking=True)
+                L.check(self.lib.demfi_luma_line_counts(self.ring.data_ptr(), self.offs.data_ptr(), m, self.h, self.w, self.es, self.thresh,
+                                                        self.rows.data_ptr(), self.cols.data_ptr(), self.stream.cuda_stream),
+                        'luma_line_counts')
+                self.h_rows[:m].copy_(self.rows[:m], non_blocking=True)
+                self.h_cols[:m].copy_(self.cols[:m], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+            ev.synchronize()
+            self.probed += m
+            rows, cols = self.h_rows[:m].numpy().view(np.uint32).copy(), self.h_cols[:m].numpy().view(np.uint32).copy()
+            for j in range(m):
+                yield rows[j], cols[j]

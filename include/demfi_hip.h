@@ -481,6 +481,16 @@ int demfi_luma_comb_counts(const uint8_t* base, const int64_t* top_offsets, cons
 int demfi_luma_woven_sad(const uint8_t* base, const int64_t* offsets, int n, int h, int w, int sample_bytes, uint64_t* out,
                          void* stream);
 
+/* ---- letterbox and pillarbox bars of the Y4M edge (csrc/crop.hip; demfi_amd/video.py --crop auto) ----------------------------------
+ * luma_line_counts: plane i is the luma plane (the first h*w samples; sample_bytes = 1, or 2 for 16-bit little-endian samples) of
+ * the payload at base + offsets[i] (n int64 BYTE offsets in DEVICE memory, any order; even ones for 16-bit samples).
+ * rows[i*h + y] = the samples of row y strictly greater than thresh, cols[i*w + x] = those of column x (device memory, n*h and
+ * n*w uint32, zeroed on the stream first); thresh = the limit times 2^(depth-8), 0 .. 65535.  Exact integers; the numpy
+ * definition is demfi_amd/letterbox.py line_counts_np.  Any h, w in 2..16384; one launch for n planes; every sample is loaded
+ * once; nothing but rows and cols is written; n = 0 does nothing. */
+int demfi_luma_line_counts(const uint8_t* base, const int64_t* offsets, int n, int h, int w, int sample_bytes, int64_t thresh,
+                           uint32_t* rows, uint32_t* cols, void* stream);
+
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
  * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
