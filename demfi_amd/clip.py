@@ -166,7 +166,7 @@ class ClipRunner:
     """x M interpolation of whole clips on this rank's GPU: frames in (host uint8 BGR), frames out (sink or files)."""
 
     def __init__(self, model, height, width, n_tst=3, mfi=8, batch=4, world=1, rank=0, final_only=True, n_ctx=None, n_trunk=None, auto=False,
-                 retime=None, tile=None, tile_margin=T.DEFAULT_MARGIN):
+                 retime=None, tile=None, tile_margin=T.DEFAULT_MARGIN, instant_counts=None):
         from .runner import WindowRunner
         # tile: None (the whole frame in one forward), 'auto' or (th, tw): frames run as the overlapping tiles of
         # tiling.plan_tiles, ``tile_margin`` pixels next to every cut thrown away.  A plan of one tile is the untiled path.
@@ -176,10 +176,10 @@ class ClipRunner:
         rh, rw = self.plan.tile if self.plan is not None else (height, width)
         # the clip pipeline delivers the LAST recursion's frames only (like test_custom, utils.py:1430-1434), so the decoder
         # passes that only produce the earlier recursions' frames need not run: same delivered bytes (WindowRunner.final_only).
-        # retime: the frame rate ratio of the Y4M edge (demfi_amd.video --fps), see WindowRunner
+        # retime: the frame rate ratio of the Y4M edge (demfi_amd.video --fps), see WindowRunner; instant_counts: as there (--shutter)
         with self.oversize_hint():
             self.runner = WindowRunner(model, rh, rw, n_tst, mfi, final_only=final_only, n_ctx=n_ctx, n_trunk=n_trunk, auto=auto,
-                                       retime=retime, tiles=self.plan)
+                                       retime=retime, tiles=self.plan, instant_counts=instant_counts)
         self.mfi, self.batch = mfi, batch
         self.world, self.rank = world, rank
         self.ts = t_schedule(mfi) if retime is None else None

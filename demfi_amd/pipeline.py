@@ -21,6 +21,7 @@ from . import cadence as K
 from . import deint as I
 from . import retime as R
 from . import scene as S
+from . import shutter as SH
 from .y4m_edge import TileGrid, Y4mEdge, consecutive, fill_sink_records, max_runs    # noqa: F401  (fill_sink_records: for the runner)
 
 
@@ -33,12 +34,40 @@ def deint_conflict(mode, has_fields, has_dedup):
         return 'dedup' if has_fields else 'fields'
 
 
-class EdgeSpec(namedtuple('EdgeSpec', 'y4m cuts full depth layout dedup fields deint_mode',
-                          defaults=(False, False, False, 8, '420', None, None, 'bob'))):
+_EdgeFields = namedtuple('EdgeSpec', 'y4m cuts full depth layout dedup fields deint_mode', defaults=(False, False, False, 8, '420', None, None, 'bob'))
+
+
+class EdgeSpec(_EdgeFields):
     """What a run of ``WindowRunner.run_clip_u8`` asks of its edge (default: the BGR edge).  ``y4m``: the Y4M edge; ``cuts``: scene cuts are detected;
     ``full``: the full-length timeline; ``depth``: bits per sample; ``layout``: one of ``y4m.LAYOUTS``; ``dedup``: None or (hi, lo, frac, max_hold);
-    ``fields``: None or the field order 't' / 'b' of an interlaced input; ``deint_mode``: one of ``deint.MODES``.  Hashable: (batch, spec) is what a
-    cached ``ClipPipeline`` can be reused for."""
+    ``fields``: None or the field order 't' / 'b' of an interlaced input; ``deint_mode``: one of ``deint.MODES``; ``shutter``: None or (S, D) of a
+    synthesized shutter (``demfi_amd.shutter``).  Hashable: (batch, spec) is what a cached ``ClipPipeline`` can be reused for.
+    ``shutter`` comes last and by keyword only, and it is kept beside the tuple's eight items, not among them: a spec without a shutter is, item
+    for item, the record it was before there was one, and one with a shutter equals no plain tuple.  What the namedtuple makes from its items
+    alone does not know it: ``_make``, ``_asdict`` and pickling drop ``shutter``; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
+    shutter = None
+
+    def __new__(cls, *args, shutter=None, **kw):
+        self = super().__new__(cls, *args, **kw)
+        if shutter is not None:
+            self.shutter = (int(shutter[0]), int(shutter[1]))
+        return self
+
+    def _replace(self, **kw):
+        shutter = kw.pop('shutter', self.shutter)
+        return type(self)(*super()._replace(**kw), shutter=shutter)
+
+    def __eq__(self, other):
+        return tuple.__eq__(self, other) is True and self.shutter == getattr(other, 'shutter', None)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((tuple(self), self.shutter))
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + ', shutter=%r)' % (self.shutter,)
 
     @classmethod
     def of(cls, yuv):
@@ -46,7 +75,7 @@ class EdgeSpec(namedtuple('EdgeSpec', 'y4m cuts full depth layout dedup fields d
         dedup, fields = getattr(yuv, 'dedup', None), getattr(yuv, 'fields', None)
         return cls(yuv is not None, getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False)), int(getattr(yuv, 'depth', 8)),
                    getattr(yuv, 'layout', '420'), tuple(dedup) if dedup is not None else None, fields,
-                   getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob')
+                   getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob', shutter=getattr(yuv, 'shutter', None))
 
     hi = property(lambda self: self.depth > 8, doc='16-bit frames: the samples of a stream above 8 bits')
 
@@ -54,6 +83,7 @@ class EdgeSpec(namedtuple('EdgeSpec', 'y4m cuts full depth layout dedup fields d
         """Every rule about what goes together, before anything is allocated, for a run on a ``retimed`` runner (built with a ratio)."""
         other, edge_only = self.deint_mode != 'bob', self.hi or self.dedup is not None or self.fields is not None
         deint = deint_conflict(self.deint_mode, self.fields is not None, self.dedup is not None)
+        sh = self.shutter
         for bad, what in ((self.fields not in (None, 't', 'b'), "fields must be None, 't' or 'b', got %r" % (self.fields,)),
                           (deint, 'deint_mode %r with fields=%r, dedup=%r' % (self.deint_mode, self.fields, self.dedup)),
                           (edge_only and not self.y4m, '16-bit frames, repeated frames and fields are those of the Y4M edge (yuv=...) only'),
@@ -62,7 +92,13 @@ class EdgeSpec(namedtuple('EdgeSpec', 'y4m cuts full depth layout dedup fields d
                           (self.dedup is not None and not (retimed and has_window_index and reuse_frames),
                            'repeated frames need a retimed runner (r = M for x M), window_index and reuse_frames'),
                           (self.cuts and not (retimed and reuse_frames), 'scene cuts need a retimed runner (r = M for x M) and reuse_frames'),
-                          (self.full and not (retimed and has_window_index), 'the full-length timeline needs a retimed runner and window_index')):
+                          (self.full and not (retimed and has_window_index), 'the full-length timeline needs a retimed runner and window_index'),
+                          (sh is not None and not (1 <= sh[0] <= sh[1] and sh[0] <= SH.MAX_SAMPLES),
+                           'shutter must be None or (S, D) with 1 <= S <= D and S <= %d, got %r' % (SH.MAX_SAMPLES, sh)),
+                          (sh is not None and not (retimed and self.y4m),
+                           'a shutter needs the Y4M edge on a retimed runner, built with the fine ratio r D'),
+                          (sh is not None and self.dedup is not None,
+                           'a shutter does not go with repeated frames (dedup): its groups are laid over the regular fine timeline')):
             if bad:
                 raise ValueError('WindowRunner.run_clip_u8: ' + what)
 

@@ -178,9 +178,17 @@ def padded_slots(r, n_ctx, counts=None):
     return sum(-c % n_ctx for c in (counts if counts is not None else _period_counts(r)))
 
 
-def default_n_ctx(r, fits, largest=8):
+def default_n_ctx(r, fits, largest=8, counts=None, slack=0):
     """The batched plan's n_ctx for ratio r: among 1 .. ``largest`` where ``fits(n_ctx)`` (the workspace fits the GPU), the
-    size with the fewest padded slots over one period of the schedule (``padded_slots``); ties go to the larger size."""
-    counts = _period_counts(r)
+    size with the fewest padded slots over one period of the schedule (``padded_slots``); ties go to the larger size.
+    ``counts``: the instants per window of a schedule that runs only some of the ratio's instants (``shutter.period_counts``).
+    ``slack``: the share of the period's instants that may be padded for the sake of a larger size: the largest size within it
+    wins (0, the default: only sizes that pad nothing win that way, which is the rule above).  Window counts of 11 and 8 instants
+    pad nothing only at 1, the non-batched plan; an eighth of slack takes 4, which pads one slot in 19.  That the largest size within the
+    slack is the fastest, and the eighth a shutter's schedule is given, rest on ONE measurement (profiles/shutter.md: 24 -> 60 at 180
+    degrees, 720p, 1.707 s at n_ctx = 1 against 1.324 s at 4), not on a model of what a padded slot and a larger batch cost."""
+    counts = counts if counts is not None else _period_counts(r)
     ok = [d for d in range(1, largest + 1) if d == 1 or fits(d)]
-    return min(ok, key=lambda d: (padded_slots(r, d, counts), -d))
+    pads = {d: padded_slots(r, d, counts) for d in ok}
+    within = [d for d in ok if pads[d] <= slack * sum(counts)]
+    return max(within) if within else min(ok, key=lambda d: (pads[d], -d))

@@ -30,7 +30,7 @@ U16_DTYPES = tuple(d for d in (torch.int16, getattr(torch, 'uint16', None)) if d
 
 
 def choose_config(H, W, n_tst, mfi, dtype_code, use_graph, n_ctx, n_trunk, auto, retime, env, cached, total_memory, free_memory,
-                  workspace_bytes, final_only=False):
+                  workspace_bytes, final_only=False, instant_counts=None):
     """The launch configuration of a WindowRunner at the padded size H x W: {'n_ctx', 'n_trunk', 'batched', 'final_only',
     'chosen_by'}.  Touches neither torch nor the GPU.  env: mapping (the environment); cached: (n_ctx, n_trunk) of an engine the
     model already holds for this frame size, or None; total_memory: bytes of the device; free_memory(): its free bytes (called
@@ -38,7 +38,9 @@ def choose_config(H, W, n_tst, mfi, dtype_code, use_graph, n_ctx, n_trunk, auto,
     Explicit n_ctx / n_trunk are taken as given.  Otherwise env DEMFI_NCTX / DEMFI_NTRUNK, else the shape of the cached engine
     (batched x M plan only, when its n_ctx > 1 divides M-1), else FIXED values that depend on the arguments and the part only
     (7 / 3 at 720p x8, fp16 N_tst=3 as well as fp32 N_tst=5; 5 / 3 at 1080p x16 fp16); ``auto`` (or env DEMFI_AUTO=1) opts into a
-    probe of the free memory instead.  DEMFI_TB=0: the non-batched plan.  retime (a Fraction): ``retime.default_n_ctx``."""
+    probe of the free memory instead.  DEMFI_TB=0: the non-batched plan.  retime (a Fraction): ``retime.default_n_ctx``, over
+    ``instant_counts`` (the instants per window over a period) when the edge runs only some of the ratio's instants (a shutter); such a
+    schedule may pad an eighth of its instants for a larger n_ctx, since its window counts are seldom multiples of anything."""
     def ws(trunks, ctxs):
         return workspace_bytes(H, W, max(n_tst, 3), dtype_code, trunks, ctxs)
     auto = bool(auto or env.get('DEMFI_AUTO') == '1')
@@ -60,7 +62,8 @@ def choose_config(H, W, n_tst, mfi, dtype_code, use_graph, n_ctx, n_trunk, auto,
         if n_ctx is None and retime is not None:
             # fewest padded per-t slots over one period of the schedule, among the sizes whose workspace fits the GPU
             how = how or 'retime schedule'
-            n_ctx = R.default_n_ctx(retime, lambda d: 0 < ws(n_trunk or 2, d) <= total_memory)
+            n_ctx = R.default_n_ctx(retime, lambda d: 0 < ws(n_trunk or 2, d) <= total_memory, counts=instant_counts,
+                                    slack=Fraction(1, 8) if instant_counts is not None else 0)
             if n_trunk is None and n_ctx > 1:    # n_ctx = 1 falls back to the non-batched plan and its two trunk sets
                 n_trunk = 3 if 0 < ws(3, n_ctx) <= total_memory // 2 else 2
         if n_ctx is None and cached is not None and (mfi - 1) % cached[0] == 0:
@@ -105,7 +108,7 @@ def choose_config(H, W, n_tst, mfi, dtype_code, use_graph, n_ctx, n_trunk, auto,
 
 class WindowRunner:
     def __init__(self, model, height, width, n_tst=3, mfi=8, use_graph=True, final_only=False, n_ctx=None, n_trunk=None, auto=False,
-                 retime=None, tiles=None):
+                 retime=None, tiles=None, instant_counts=None):
         """final_only: produce the frames of the LAST recursion only (what test / test_custom consume, utils.py:1430-1434):
         the warp + D2 tail of the earlier recursions feeds nothing else and is skipped (batched plan only); the delivered
         frames are bit-identical.
@@ -116,7 +119,8 @@ class WindowRunner:
         retime: output / input frame rate ratio r >= 1 (a Fraction) of the Y4M edge of ``run_clip_u8`` in place of x M: window k
         runs the instants of ``retime.window_plan`` (``mfi`` is not used).  An explicit n_ctx is taken as given; the default is
         ``retime.default_n_ctx`` over the sizes whose workspace fits the GPU.  ``instants_run`` / ``instants_padded`` count the
-        time instants run and the padded per-t slots of short batched chunks.
+        time instants run and the padded per-t slots of short batched chunks.  instant_counts: the instants per window, over one period,
+        of an edge that runs only some of the ratio's instants (``shutter.period_counts``); the default n_ctx is then sized by them.
         tiles: a multi-tile ``tiling.Plan`` whose tile size is height x width: ``run_clip_u8`` then takes and gives frames of the
         plan's size and runs every window once per tile (``demfi_amd.pipeline``); every other entry point stays at the tile's size."""
         if tiles is not None and (tiles.n_tiles < 2 or tuple(tiles.tile) != (height, width)):
@@ -140,7 +144,8 @@ class WindowRunner:
             H, W, n_tst, mfi, L.F32 if model.path_dtype == torch.float32 else L.F16, use_graph, n_ctx, n_trunk, auto, self.retime,
             env=os.environ, cached=(eng.n_ctx, eng.n_trunk) if eng is not None else None, final_only=final_only,
             total_memory=torch.cuda.get_device_properties(model.device).total_memory if torch.cuda.is_available() else 288 * 10 ** 9,
-            free_memory=lambda: torch.cuda.mem_get_info(model.device)[0], workspace_bytes=self.lib.demfi_workspace_bytes)
+            free_memory=lambda: torch.cuda.mem_get_info(model.device)[0], workspace_bytes=self.lib.demfi_workspace_bytes,
+            instant_counts=instant_counts)
         self.n_ctx, self.n_trunk, self.tb, self.final_only = (self.config[k] for k in ('n_ctx', 'n_trunk', 'batched', 'final_only'))
         self.model = model
         self._HW = (H, W)
@@ -164,6 +169,7 @@ class WindowRunner:
         self.instants_run = 0                        # time instants run (padded slots not counted)
         self.instants_padded = 0                     # per-t slots of short batched chunks that ran a repeated t and wrote nothing
         self.cut_windows = 0                         # windows run as scene-cut windows (two runs, no interpolation)
+        self.shutter_mixed = self.shutter_carried = 0    # a shutter's fine frames mixed / samples carried between batches (``y4m_edge.Shutter``)
         self.last_cuts = []                          # frames that start a scene, as the last run_clip_u8 with scene cuts found them
 
     # ---------------------------------------------------------------------------------------------------------

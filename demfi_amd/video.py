@@ -86,6 +86,21 @@ not cropped to (``auto``: reported; explicit: an error, like a misaligned one); 
 one, gives the bytes of a run without the switch.  Not offered: bars that change within a stream (the union is taken), ``--crop`` on
 ``demfi_amd.clip``, restoring the input's own bar samples (output bars are exact black); scene-cut and repeated-frame decisions are
 made over the cropped payloads, so they can differ from those of an uncropped run.
+
+``--shutter ANGLE`` (degrees, N or N/D, 0 < ANGLE <= 360) with ``--shutter-samples S`` (1 .. 32, default 4) synthesizes motion blur
+(``demfi_amd.shutter``): every written frame is the average of S finer frames spread over an exposure of ANGLE/360 of its frame period,
+from its own time on, instead of one sharp frame -- 180 degrees is the film look, and 24 -> 60 stops strobing.  D = 360 S / ANGLE must
+be an integer; the fine stream is this module's own timeline at the ratio r D (at most ``retime.MAX_RATIO``, checked once the header is
+known), written frame c averages the fine frames c D .. c D + S - 1 that exist and lie in the scene of the first (``--scene-cut``), and
+the written stream has the header, the length and the timing of a run without the switch.  The runner is built for the fine ratio and
+``shutter.filter_plan`` leaves every window only the instants its samples need; behind the batch's gather ONE launch
+(csrc/shutter.hip ``demfi_payload_mix``, defined by ``shutter.mix_np``: (2 sum + k) // (2 k) of the stored samples, round half up, the
+payload one flat array) mixes every group whose last sample has arrived into the buffer that crosses D2H, and the samples of the group
+still open carry over to the next batch on the device, so the bytes do not depend on the batch size.  Works with every switch above
+(the stage sits behind whole payloads; run behind each of them on the GPU except ``--tile-high-depth``, whose two halves are) except
+``--dedup``; one rank.  Not offered: linear-light mixing (the average is taken over the
+gamma-encoded samples), weighted windows (triangle, gaussian), an exposure centred on the frame time, ``--dedup``, several ranks,
+F_out < F_in, ``demfi_amd.clip``.  Without the switch no buffer, launch or stream is added and every byte stays the same.
 """
 import os
 import sys
@@ -100,6 +115,7 @@ from . import dist as D
 from . import letterbox as LB
 from . import retime as R
 from . import scene as S
+from . import shutter as SH
 from . import telecine as TC
 from . import tiling as T
 from . import y4m
@@ -114,11 +130,12 @@ class YuvEdge:
     ``depth``: bits per sample, 8, or 10 / 12 / 14 / 16 for payloads of 16-bit samples.  ``layout``: the payloads' chroma
     layout, one of ``y4m.LAYOUTS`` (``siting`` only matters to '420').  ``dedup``: None, or (hi, lo, frac, max_hold) of
     repeated-frame detection (``demfi_amd.cadence``).  ``fields``: None, or the field order 't' / 'b' of an interlaced input whose
-    fields are the stream's frames (``demfi_amd.deint``), rebuilt by ``deint_mode`` 'bob' or 'adaptive'."""
+    fields are the stream's frames (``demfi_amd.deint``), rebuilt by ``deint_mode`` 'bob' or 'adaptive'.  ``shutter``: None, or (S, D) of a
+    synthesized shutter (``demfi_amd.shutter``): the runner then has the fine ratio r D and the payloads handed out are the mixed ones."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
-                 fields=None, deint_mode='bob'):
-        self.dedup = dedup
+                 fields=None, deint_mode='bob', shutter=None):
+        self.dedup, self.shutter = dedup, shutter
         self.fields, self.deint_mode = fields, deint_mode
         self.depth = y4m.check_depth(depth)
         self.layout = y4m.check_layout(layout)
@@ -148,6 +165,28 @@ def check_crop(crop, limit=LB.DEFAULT_LIMIT, noise=LB.DEFAULT_NOISE, probe=LB.DE
         raise ValueError('--crop-limit, --crop-noise, --crop-probe and --crop-output (crop_limit, crop_noise, crop_probe, crop_output) '
                          'say how --crop works: give --crop auto or --crop T:B:L:R with them')
     return crop, params
+
+
+def check_shutter(shutter, samples=None, dedup=None, world=1):
+    """The shutter switches checked: None, or (S, D) of ``shutter.check_params``.  ``samples`` (None: the default) says how ``shutter``
+    works, so it is an error without it; a shutter does not go with ``--dedup`` or with more than one rank."""
+    if shutter is None:
+        if samples is not None:
+            raise ValueError('--shutter-samples (shutter_samples) says how --shutter works: give --shutter ANGLE with it')
+        return None
+    sd = SH.check_params(shutter, SH.DEFAULT_SAMPLES if samples is None else samples)
+    if dedup not in (None, False):
+        raise ValueError('--shutter does not go with --dedup: the sub-frames of a written frame are laid over the regular fine timeline, which '
+                         'repeated frames left out of the input bend; run one of the two')
+    check_shutter_ranks(sd, world)
+    return sd
+
+
+def check_shutter_ranks(shutter, world):
+    """A shutter runs on one rank: the sub-frames of a written frame straddle the ranks' blocks of windows."""
+    if shutter is not None and world > 1:
+        raise ValueError('VideoRunner: shutter with %d ranks: the sub-frames of a written frame straddle the ranks\' blocks of windows; run '
+                         '--shutter on one rank' % world)
 
 
 AUTO_NEEDS_A_FILE = ('--crop auto needs a regular input file: the bars of a stream are known only at its end; give the four bar '
@@ -213,14 +252,24 @@ class VideoRunner:
     ``last_crop_note`` = None or why an 'auto' rectangle was not used.  Not offered: bars that change within a stream (the union is
     taken), restoring the input's own bar samples (output bars are exact black); scene cuts and repeated frames are decided over the
     cropped payloads, so they can differ from those of an uncropped run.  The four secondary arguments without ``crop`` are an
-    error; without ``crop`` nothing changes anywhere: no buffer, stream or launch is added."""
+    error; without ``crop`` nothing changes anywhere: no buffer, stream or launch is added.  ``shutter``: None (default) or the shutter
+    angle in degrees (an int, a Fraction or an "N/D" string, 0 < angle <= 360) of synthesized motion blur (``demfi_amd.shutter``) with
+    ``shutter_samples`` = S sub-frames (1 .. 32; None, the default, is 4; given without ``shutter`` it is an error): every written frame is the
+    rounded average of the fine frames c D .. c D + S - 1, D = 360 S / angle (an integer, or a ValueError here), of the stream at the
+    ratio r D, which is refused above ``retime.MAX_RATIO`` once the header is known, before anything is allocated.  Not with ``dedup``
+    (refused here) and on one rank (``run_file`` refuses more).  After a run ``last_shutter`` = (S, D) or None, ``last_instants`` counts
+    the instants that ran (those the written frames need), ``last_st_frames`` the fine frames that went into the mixes and
+    ``last_shutter_carried`` the samples that were carried from one batch to the next on the device."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
                  tile_high_depth=False, deinterlace=False, deinterlace_mode='bob', ivtc=False, ivtc_cthresh=TC.DEFAULT_CTHRESH,
                  ivtc_combpel=TC.DEFAULT_COMBPEL, ivtc_combed=TC.DEFAULT_COMBED, crop=None, crop_limit=LB.DEFAULT_LIMIT,
-                 crop_noise=LB.DEFAULT_NOISE, crop_probe=LB.DEFAULT_PROBE, crop_output='pad', **runner_kw):
+                 crop_noise=LB.DEFAULT_NOISE, crop_probe=LB.DEFAULT_PROBE, crop_output='pad', shutter=None,
+                 shutter_samples=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.shutter = check_shutter(shutter, shutter_samples, dedup)     # (S, D) or None
+        self.last_shutter, self.last_shutter_carried = None, 0
         self.crop, (self.crop_limit, self.crop_noise, self.crop_probe, self.crop_output) = check_crop(
             crop, crop_limit, crop_noise, crop_probe, crop_output)
         self.last_crop, self.last_crop_probed, self.last_crop_note, self.last_crop_seconds = None, 0, None, 0.0
@@ -413,13 +462,20 @@ class VideoRunner:
                              '--tile-high-depth (tile_high_depth=True)' % (self.tile, hdr.depth, hdr.ctag))
         self.last_depth, self.last_layout = hdr.depth, hdr.layout
 
-    def _clip_runner(self, hdr, world, rank):
+    def _fine_ratio(self, hdr):
+        """The ratio the runner is built with: r, or with a shutter that of the fine stream, r D (refused above ``retime.MAX_RATIO``)."""
         r = self._ratio(hdr)
-        key = (hdr.h, hdr.w, world, rank, r)
+        return r if self.shutter is None else SH.fine_ratio(r, self.shutter[1])
+
+    def _clip_runner(self, hdr, world, rank):
+        r, kw = self._fine_ratio(hdr), {}
+        key = (hdr.h, hdr.w, world, rank, r, self.shutter)
         cr = self._runners.get(key)
         if cr is None:
+            if self.shutter is not None:             # only some of the fine ratio's instants run: the batched plan is sized by those
+                kw['instant_counts'] = SH.period_counts(self._ratio(hdr), *self.shutter)
             cr = self._runners[key] = ClipRunner(self.model, hdr.h, hdr.w, self.n_tst, self.mfi or 8, batch=self.batch, world=world,
-                                                 rank=rank, **dict(self.runner_kw, retime=r))
+                                                 rank=rank, **dict(self.runner_kw, retime=r, **kw))
         self.last_plan = cr.plan
         return cr
 
@@ -427,7 +483,7 @@ class VideoRunner:
         """fn() runs windows lo, lo+1, ... of the input on cr, lo = first() once it has run; returns its window count and sets
         the per-run counters."""
         rn = cr.runner
-        i0, p0, c0 = rn.instants_run, rn.instants_padded, rn.cut_windows
+        i0, p0, c0, m0, s0 = rn.instants_run, rn.instants_padded, rn.cut_windows, rn.shutter_mixed, rn.shutter_carried
         with cr.oversize_hint():
             n = fn()
         lo = first()
@@ -436,11 +492,15 @@ class VideoRunner:
         self.last_cut_windows = rn.cut_windows - c0
         r = self._ratio(hdr)
         self.last_st_frames = sum(kind == R.ST for k in range(lo, lo + n) for _, kind, _ in R.window_outputs(k, r, full_length=self.full_length))
+        self.last_shutter = self.shutter
+        self.last_shutter_carried = rn.shutter_carried - s0
+        if self.shutter is not None:                 # the fine frames that went into the mixes
+            self.last_st_frames = rn.shutter_mixed - m0
         return n
 
     def _edge(self, hdr, with_s1, order=None):
         return YuvEdge(y4m.auto_matrix(self._matrix_h or hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
-                       self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup, order, self.deinterlace_mode)
+                       self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
@@ -465,6 +525,7 @@ class VideoRunner:
         hdr, out_hdr = self._headers(full_hdr, cropper)  # hdr: what runs (cropped); out_hdr: what is written
         self._matrix_h = full_hdr.h if cropper is not None else None
         self._check_depth(hdr)
+        self._fine_ratio(hdr)
         cr = self._clip_runner(hdr, 1, 0)
         wr = y4m.Writer(dst, out_hdr)
         if self.ivtc:                                    # downstream sees an ordinary progressive input at the film rate
@@ -505,6 +566,7 @@ class VideoRunner:
             raise ValueError('VideoRunner: dedup with %d ranks: which frames are kept depends on the whole prefix of the input, so a rank '
                              'cannot place its block of windows from k and r alone; run --dedup on one rank' % world)
         check_ivtc(self.ivtc, self.deinterlace, world)
+        check_shutter_ranks(self.shutter, world)
         self.last_dups, self._film = [], None
         with open(in_path, 'rb') as f:
             in_hdr, _, offs = y4m.scan(f, self.depths, self.layouts, self.deinterlace, self.ivtc)
@@ -513,6 +575,7 @@ class VideoRunner:
             hdr, out_hdr = self._headers(full_hdr, cropper)                          # hdr: what runs (cropped); out_hdr: what is written
             self._matrix_h = full_hdr.h if cropper is not None else None
             self._check_depth(hdr)
+            self._fine_ratio(hdr)
             n_in = TC.n_film_frames(len(offs)) if self.ivtc else per * len(offs)     # an interlaced input counts as its fields
             hb = out_hdr.encode()
             total = self._n_out(n_in, hdr)
@@ -544,6 +607,7 @@ class VideoRunner:
             lo, wins = cr.my_windows(n_in, full)
             if not wins:
                 self.last_instants, self.last_st_frames, self.last_cuts, self.last_cut_windows = (0, 0), 0, [], 0
+                self.last_shutter, self.last_shutter_carried = self.shutter, 0
                 return 0, 0
             last = R.first_window(n_in, full) + R.n_windows(n_in, full) - 1
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
@@ -695,6 +759,15 @@ def parser():
                     help='with --crop auto: look at all payloads (default) or at N spread evenly over the input')
     ap.add_argument('--crop-output', default=None, choices=list(LB.OUTPUTS),
                     help='with --crop: pad (default) writes the input\'s frame size with black bars, cropped writes the picture rectangle alone')
+    ap.add_argument('--shutter', type=_value_arg(SH.parse_shutter), default=None, metavar='ANGLE',
+                    help='synthesize motion blur: every written frame is the average of --shutter-samples finer frames spread over an '
+                         'exposure of ANGLE/360 of its frame period, from its own time on (ANGLE in degrees, N or N/D, 0 < ANGLE <= 360; 180 '
+                         'is the film look).  Only the time instants those frames need are run, the mix is one launch per batch on the '
+                         'GPU and only written frames leave it; samples on the far side of a scene cut (--scene-cut) are left out.  The '
+                         'average is taken over the stored (gamma) samples.  S*360/ANGLE must be an integer and F_out/F_in times it at '
+                         'most %d.  One rank only; not with --dedup.  Off by default' % R.MAX_RATIO)
+    ap.add_argument('--shutter-samples', type=int, default=None, metavar='S',
+                    help='with --shutter: the sub-frames averaged per written frame, 1 .. %d (default %d)' % (SH.MAX_SAMPLES, SH.DEFAULT_SAMPLES))
     T.add_arguments(ap)
     return ap
 
@@ -722,9 +795,13 @@ def main(argv=None):
                                                     ('crop_probe', LB.DEFAULT_PROBE), ('crop_output', 'pad'))))
         if a.crop == 'auto' and not (_is_regular(a.input) and os.path.isfile(a.input) and _is_regular(a.output)):
             raise ValueError(AUTO_NEEDS_A_FILE + ' (and a regular output file)')
+        check_shutter(a.shutter, a.shutter_samples, a.dedup or None)
     except ValueError as e:
         parser().error(str(e))
+    shutter_kw = {k: v for k, v in (('shutter', a.shutter), ('shutter_samples', a.shutter_samples)) if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
+    if world > 1 and a.shutter is not None:
+        raise SystemExit('demfi_amd.video: --shutter runs on one rank (the sub-frames of a written frame straddle the ranks\' blocks)')
     if world > 1 and a.dedup:
         raise SystemExit('demfi_amd.video: --dedup runs on one rank (which frames are kept depends on the whole prefix of the input)')
     if world > 1 and a.ivtc:
@@ -753,7 +830,7 @@ def main(argv=None):
                      tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth, layouts=a.any_layout, dedup=a.dedup or None,
                      dedup_max_hold=a.dedup_max_hold, tile_high_depth=a.tile_high_depth, deinterlace=a.deinterlace,
                      deinterlace_mode=a.deinterlace_mode, ivtc=a.ivtc, ivtc_cthresh=a.ivtc_cthresh, ivtc_combpel=a.ivtc_combpel,
-                     ivtc_combed=a.ivtc_combed, **crop_kw)
+                     ivtc_combed=a.ivtc_combed, **crop_kw, **shutter_kw)
     t0 = time.perf_counter()
     if world > 1 or a.crop == 'auto':                        # the pre-pass seeks: regular files
         nw, nf = vr.run_file(a.input, a.output, world, rank)
@@ -777,7 +854,8 @@ def main(argv=None):
         if tw == 0:
             print('demfi_amd.video: %s: no window, only the header was written' %
                   ('no input frame' if a.full_length else 'fewer than 4 input frames'), file=sys.stderr)
-        print(json.dumps({'windows': int(tw), 'frames_written': int(tf), 'seconds': round(dt, 2), 'ranks': world,
+        extra = {'shutter': {'angle': str(a.shutter), 'samples': vr.last_shutter[0], 'fine_per_written': vr.last_shutter[1]}} if a.shutter else {}
+        print(json.dumps({**extra, 'windows': int(tw), 'frames_written': int(tf), 'seconds': round(dt, 2), 'ranks': world,
                           'St_frames_per_s': round(tst / dt, 2) if dt > 0 else None,
                           'frames_per_s': round(tf / dt, 2) if dt > 0 else None,
                           'fps_out': str(vr.last_fps_out) if vr.last_fps_out is not None else None,

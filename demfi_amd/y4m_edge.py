@@ -1,6 +1,6 @@
 """The Y4M edge of the clip pipeline (``demfi_amd.pipeline``): Y4M payloads in and out, every window on its own plan, all options in
 one ``pipeline.EdgeSpec``.  One stage per job, each with its own buffers: ``Ingest``, ``SceneScores``, ``DedupProbe``, the pure function
-``plan_batch`` and a ``FrameIO`` chosen once; ``Y4mEdge`` keeps their order and the payloads' way out."""
+``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, ``Shutter``; ``Y4mEdge`` keeps their order and the payloads' way out."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +11,7 @@ from . import cadence as K
 from . import deint as I
 from . import retime as R
 from . import scene as S
+from . import shutter as SH
 from .y4m import payload_size
 
 # int64 word positions in a demfi_u8_sink record (256 bytes: the context's "sink" buffer)
@@ -250,10 +251,19 @@ def plan_batch(spec, r, wins, n, window_index, with_s1, det, kept, frames, slot_
     scene detector ``det`` ``scene.window_runs`` (a cut window is two runs), with the ``kept`` frames of a --dedup run ``cadence.window_runs`` over
     kept indices.  Returns (runs as (slots, instants, kinds kept), outs[w] as (run of the batch, kind, instant index) in stream order, the cut windows
     among them, the St frames planned over kept frames).  Pure."""
-    runs, outs, cut_windows, st_frames = [], [], 0, 0
+    return plan_fine(spec, r, wins, n, window_index, with_s1, det, kept, frames, slot_of)[:4]
+
+
+def plan_fine(spec, r, wins, n, window_index, with_s1, det, kept, frames, slot_of):
+    """``plan_batch`` and, behind its four values, what a shutter needs to know of the batch: fine[w] = (is window w a cut window, [(stream index i,
+    does it come from the right run of the cut window)] of its outputs in stream order), and whether the batch holds the clip's last window.  With
+    ``spec.shutter`` = (S, D) the ratio r is that of the fine stream and every window's plan goes through ``shutter.filter_plan``: only the outputs
+    the written frames need, and the instants those name, are left.  Pure."""
+    runs, outs, cut_windows, st_frames, fine, ends = [], [], 0, 0, [], False
     for wi, win in enumerate(wins):
         k = window_index(n + wi) if window_index is not None else win[2]
         last = with_s1(n + wi)
+        ends, cut = ends or bool(last), False
         if kept is not None:                         # the plans of ``cadence`` over the kept frames; slots by kept index
             is_cut = det.is_cut if det is not None else None
             sr, so = K.window_runs(k, r, kept.s, kept.n, is_cut, spec.full)
@@ -261,15 +271,76 @@ def plan_batch(spec, r, wins, n, window_index, with_s1, det, kept, frames, slot_
             st_frames += sum(kind == R.ST for _, _, kind, _ in so)
         elif det is None:
             ts, o = R.window_plan(k, r, last, spec.full)
-            sr, so = None, [(None, 0, kind, j) for _, kind, j in o]
+            sr, so = [(None, ts)], [(i, 0, kind, j) for i, kind, j in o]
         else:
             is_cut = S.with_sentinels(det.is_cut, k + 3 if last else None) if spec.full else det.is_cut
             sr, so = S.window_runs(k, r, last, is_cut, spec.full)
+            cut = len(sr) > 1
             cut_windows += len(sr) - 1
-        wr = [(frames[wi], ts)] if sr is None else [([slot_of[x] for x in S.runner_order(tup)], ts) for tup, ts in sr]
+        right = {i for i, run, _, _ in so if cut and run == 1}
+        if spec.shutter is not None:
+            sr, so = SH.filter_plan(sr, so, *spec.shutter)
+        wr = [(frames[wi] if tup is None else [slot_of[x] for x in S.runner_order(tup)], ts) for tup, ts in sr]
         outs.append([(len(runs) + run, kind, j) for _, run, kind, j in so])
+        fine.append((cut, [(i, i in right) for i, _, _, _ in so]))
         runs += [(fr, ts, {kind for _, run, kind, _ in so if run == ri}) for ri, (fr, ts) in enumerate(wr)]
-    return runs, outs, cut_windows, st_frames
+    return runs, outs, cut_windows, st_frames, fine, ends
+
+
+class Shutter:
+    """Fine payloads gathered -> written payloads mixed (``demfi_amd.shutter``, ``spec.shutter`` = (S, D)).  Written frame c averages the
+    fine frames c D .. c D + S - 1 of its scene that exist.  After a batch's gather ``mix`` closes every group whose last sample has arrived
+    (all open groups when the batch holds the clip's last window) and ONE ``demfi_payload_mix`` launch on the compute stream writes them into
+    ``mixed[i]``, which is what crosses D2H; a written frame counts to the window that completed it.  The samples of the one group still open
+    (at most ``lead`` = S - 1 of them, consecutive rows at the end of the gather) carry over on the device: ``carry`` copies them into the
+    ``lead`` rows in front of the next batch's gather (yuv_out[i] has that many more rows), so which batch a sample came with never shows.
+    The runner counts for it, as it counts cut windows: ``shutter_mixed`` the fine frames that went into the mixes, ``shutter_carried`` the
+    samples carried from one batch to the next.  ``h_offs``: the pinned offset tables, one per buffer set; table i is written again two
+    batches later, when the host has drained the batch that last copied from it (``ClipPipeline._drain`` waits for that batch's D2H, which
+    waited for its compute, where the copy of the table ran)."""
+
+    def __init__(self, runner, spec, nout, batch, Pb, es, dev):
+        (self.S, self.D), self.rn, self.lib, self.Pb, self.es = spec.shutter, runner, runner.lib, Pb, es
+        self.lead = self.S - 1
+        # written frames of a batch: the multiples of D among the fine indices of its windows (each owns up to J, the last one of the full-length
+        # timeline 2 J, nout in all), and the group carried into it
+        self.rows = nout // self.D + batch + 2
+        self.mixed = [torch.empty((self.rows, Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.offs = [torch.empty(self.rows * self.S, dtype=torch.int64, device=dev) for _ in range(2)]
+        self.h_offs = [torch.empty((self.rows, self.S), dtype=torch.int64).pin_memory() for _ in range(2)]
+        self.begin()
+
+    def begin(self):
+        self.open, self.scene = [], 0                # open: (fine index, scene, row) of the samples of the open group
+
+    def carry(self, i, yuv_out):
+        """Before batch i's gather (compute stream): the open group's samples move from the end of the other buffer's gather in front of this one's."""
+        m = len(self.open)
+        if not m:
+            return
+        a = self.open[0][2]
+        if m > self.lead or [row for _, _, row in self.open] != list(range(a, a + m)):
+            raise RuntimeError('shutter: %d open samples at rows %s for %d carry rows' % (m, [row for _, _, row in self.open], self.lead))
+        yuv_out[i][self.lead - m:self.lead].copy_(yuv_out[1 - i][a:a + m])
+        self.rn.shutter_carried += m
+        self.open = [(g, sc, self.lead - m + j) for j, (g, sc, _) in enumerate(self.open)]
+
+    def mix(self, i, fine, ends, yuv_out, stream):
+        """fine[w] = ``plan_fine``'s for window w, gathered into yuv_out[i] from row ``lead`` on; returns the written payloads per window."""
+        S = self.S
+        table, counts, self.open, self.scene = SH.close_groups(self.open, fine, self.scene, ends, S, self.D, self.lead)
+        nc = len(table)
+        if nc > self.rows:
+            raise RuntimeError('shutter: %d written frames for %d payload rows' % (nc, self.rows))
+        if nc:
+            self.rn.shutter_mixed += sum(len(t) for t in table)
+            host = self.h_offs[i][:nc]
+            host.numpy()[:] = [[rw * self.Pb for rw in t] + [-1] * (S - len(t)) for t in table]
+            od = self.offs[i][:nc * S]
+            od.copy_(host.view(-1), non_blocking=True)
+            L.check(self.lib.demfi_payload_mix(yuv_out[i].data_ptr(), host.data_ptr(), od.data_ptr(), nc, S, self.Pb // self.es, self.es,
+                                               self.mixed[i].data_ptr(), self.Pb, stream.cuda_stream), 'payload_mix')
+        return counts
 
 
 class TileGrid:
@@ -340,8 +411,12 @@ class Y4mEdge:
         self.t = [torch.empty((runs_max * io.nt, nJ), dtype=torch.float32, device=dev) for _ in range(2)]
         self.sinks = [torch.empty((runs_max * io.nt, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)]
         self.offs = [torch.empty(nout, dtype=torch.int64, device=dev) for _ in range(2)]
-        self.yuv_out = [torch.empty((nout, ing.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.h_yuv = [torch.empty((nout, ing.Pb), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        # a shutter mixes the gathered (fine) payloads into written ones: those cross D2H, and yuv_out[i] gets its carry rows in front
+        sh = self.shutter = Shutter(runner, spec, nout, batch, ing.Pb, ing.es, dev) if spec.shutter is not None else None
+        lead, nhost = (sh.lead, sh.rows) if sh is not None else (0, nout)
+        self.yuv_out = [torch.empty((lead + nout, ing.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.written = sh.mixed if sh is not None else self.yuv_out
+        self.h_yuv = [torch.empty((nhost, ing.Pb), dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.yuv = self.window_index = self.det = self.kept = self.gather = None
 
     def __getattr__(self, name):                     # J, tiler, in_place and, on a crop-run-stitch edge only, tcomb: the frame IO's
@@ -356,6 +431,8 @@ class Y4mEdge:
         """A run starts; returns the frames to make resident first: with scene cuts, frame k0 - 1 of a first window k0 >= 1."""
         ing, sc = self.ingest, self.scores
         self.yuv, self.window_index, self.det, ing.raw = yuv, window_index, None, {}
+        if self.shutter is not None:
+            self.shutter.begin()
         ing.to_bgr, self.gather, sad = yuv_calls(self.rn.lib, self.spec, ing.fh, ing.fw, yuv)
         if sc is None:
             return ()
@@ -380,13 +457,18 @@ class Y4mEdge:
 
     def run(self, i, n, wins, frames, cur):
         """Plans the batch's windows, runs them and gathers their outputs into yuv_out[i].  Returns (payloads per window, slots read)."""
-        runs, outs, cut_windows, st_frames = plan_batch(self.spec, self.r, wins, n, self.window_index, self.yuv.with_s1, self.det, self.kept,
-                                                        frames, self.slots.slot_of)
+        runs, outs, cut_windows, st_frames, fine, ends = plan_fine(self.spec, self.r, wins, n, self.window_index, self.yuv.with_s1, self.det,
+                                                                   self.kept, frames, self.slots.slot_of)
         self.rn.cut_windows += cut_windows
         if self.kept is not None:
             self.kept.st_frames += st_frames
         self._run_windows(i, runs)
-        return self._gather(i, outs, cur), [fr for fr, _, _ in runs]
+        sh, read = self.shutter, [fr for fr, _, _ in runs]
+        if sh is None:
+            return self._gather(i, outs, cur), read
+        sh.carry(i, self.yuv_out)
+        self._gather(i, outs, cur, sh.lead)
+        return sh.mix(i, fine, ends, self.yuv_out, cur), read
 
     def _run_windows(self, i, runs):
         """Planned run w = (4 slots, instants, kinds) becomes the ``io.nt`` runner runs w * nt + j, which run its instants into ``io.dst[i]``;
@@ -421,9 +503,10 @@ class Y4mEdge:
         rn._end(cur)
         io.after(i, runs, cur)
 
-    def _gather(self, i, outs, cur):
-        """outs[w] = window w's outputs as (run, kind, instant index), from comb[i] -> yuv_out[i]; returns the payloads per window."""
-        comb, dst, J = self.io.comb[i], self.yuv_out[i], self.J
+    def _gather(self, i, outs, cur, lead=0):
+        """outs[w] = window w's outputs as (run, kind, instant index), from comb[i] -> yuv_out[i] from row ``lead`` on; returns the payloads per
+        window."""
+        comb, dst, J = self.io.comb[i], self.yuv_out[i][lead:], self.J
         c0, c1 = comb.stride()[:2]
         offs = [run * c0 + (0 if kind == R.S0 else J + 1 if kind == R.S1 else 1 + j) * c1 for o in outs for run, kind, j in o]
         nf = len(offs)
@@ -435,12 +518,13 @@ class Y4mEdge:
         return [len(o) for o in outs]
 
     def d2h(self, i, counts):
-        self.h_yuv[i][:sum(counts)].copy_(self.yuv_out[i][:sum(counts)], non_blocking=True)
+        self.h_yuv[i][:sum(counts)].copy_(self.written[i][:sum(counts)], non_blocking=True)
 
     def drain(self, i, k0, counts, sink):
         pos = 0
         for j, c in enumerate(counts):
-            sink(k0 + j, self.h_yuv[i][pos:pos + c])
+            if c or self.shutter is None:            # a window that completed no written frame has nothing to hand out
+                sink(k0 + j, self.h_yuv[i][pos:pos + c])
             pos += c
 
 

@@ -491,6 +491,22 @@ int demfi_luma_woven_sad(const uint8_t* base, const int64_t* offsets, int n, int
 int demfi_luma_line_counts(const uint8_t* base, const int64_t* offsets, int n, int h, int w, int sample_bytes, int64_t thresh,
                            uint32_t* rows, uint32_t* cols, void* stream);
 
+/* ---- synthesized motion blur of the Y4M edge (csrc/shutter.hip; demfi_amd/video.py --shutter) -------------------------------------
+ * payload_mix: written payload i (n per launch) is the rounded box average of the fine payloads it keeps: row i has smax (1..32)
+ * int64 BYTE offsets from base, offsets[i*smax .. i*smax + smax - 1], the k_i kept ones first and -1 behind them (k_i >= 1).  Every
+ * one of the P stored samples (sample_bytes = 1, or 2 for 16-bit little-endian samples: even addresses and stride) of the payload at
+ * dst + i*dst_stride becomes (2 * sum + k_i) / (2 * k_i) of the samples at its position in the kept payloads: round half up, exact
+ * integers, in the stored (gamma) values; the numpy definition is demfi_amd/shutter.py mix_np.  The payload is one flat array: layout,
+ * depth, matrix and range do not matter.  The offsets are passed twice with the same content: offsets in HOST memory, checked here
+ * before anything is launched (a row whose first offset is -1, a kept offset behind a -1 or an offset below -1 is DEMFI_ERR_ARG, and
+ * so are smax outside 1..32, a bad sample_bytes and dst_stride < P * sample_bytes), and offsets_dev in DEVICE memory, read by the
+ * kernel.  When base + every kept offset, dst and dst_stride are multiples of 16 every thread makes 16 output bytes from 16-byte loads
+ * and one 16-byte store (the last P * sample_bytes mod 16 bytes of a row sample by sample); otherwise the whole launch goes sample by
+ * sample with the same arithmetic.  The bytes between P * sample_bytes and dst_stride are not written.  One launch for all n rows, no
+ * LDS, no atomics; the sources may overlap each other but not dst; n <= 0 does nothing. */
+int demfi_payload_mix(const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, int n, int smax, int64_t P,
+                      int sample_bytes, uint8_t* dst, int64_t dst_stride, void* stream);
+
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
  * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
