@@ -51,8 +51,8 @@ picture moves diff is large and out = sp, the bob.  Scene cuts need nothing spec
 and the result falls back to the spatial value.  Output field f depends on payloads p-1, p and p+1 of the input only.
 
 Out of scope: ``--dedup`` together with the adaptive mode (repeated frames are staged and discarded one field at a time, the
-adaptive mode needs two fields of lookahead; ``--deinterlace-mode bob`` is the way out), mixed-mode streams (``Im``) and interlaced
-output.  Film carried by 3:2 pulldown is not deinterlaced but put back together: ``demfi_amd.telecine`` (``--ivtc``).
+adaptive mode needs two fields of lookahead; ``--deinterlace-mode bob`` is the way out), mixed-mode streams (``Im``).  Interlaced
+output is ``demfi_amd.interlace`` (``--interlace``), which weaves by this module's field convention.  Film carried by 3:2 pulldown is not deinterlaced but put back together: ``demfi_amd.telecine`` (``--ivtc``).
 """
 import numpy as np
 

@@ -4,7 +4,8 @@ edge object per format, ``BgrEdge`` (BGR frames in and out) or ``y4m_edge.Y4mEdg
 same methods.  Per run: ``attach`` the host frames, then ``begin``, which names the frames to make resident first.  Per batch: ``around`` names the
 frames needed besides its windows', ``upload`` copies one frame into a slot and ``uploaded`` follows the copies (h2d stream), ``run`` computes
 (compute stream), ``d2h`` copies the outputs to pinned memory (d2h stream), ``drain`` hands them to the sink; what ``run`` returns goes to ``d2h`` /
-``drain``.  ``ClipPipeline`` is the double-buffered batch loop.  A runner of tiles (``WindowRunner(tiles=plan)``, ``demfi_amd.tiling``) has the tile's
+``drain``; after the last batch ``flush`` names what the edge still holds back (None, or the odd last frame of an interlaced ``--dedup`` run), which
+takes the same way out.  ``ClipPipeline`` is the double-buffered batch loop.  A runner of tiles (``WindowRunner(tiles=plan)``, ``demfi_amd.tiling``) has the tile's
 size while the slots and the outputs keep the frame's: ``Tiler`` crops every uploaded frame into its tiles once, each (run, tile) pair is one run, and
 one stitch launch per batch pastes the kept rectangles into the full-size outputs.  16-bit frames are not cropped or stitched (``TileGrid``): their
 ingest and egress kernels address a tile inside the full frames."""
@@ -19,6 +20,7 @@ import torch
 from . import _lib as L
 from . import cadence as K
 from . import deint as I
+from . import interlace as IL
 from . import retime as R
 from . import scene as S
 from . import shutter as SH
@@ -41,33 +43,38 @@ class EdgeSpec(_EdgeFields):
     """What a run of ``WindowRunner.run_clip_u8`` asks of its edge (default: the BGR edge).  ``y4m``: the Y4M edge; ``cuts``: scene cuts are detected;
     ``full``: the full-length timeline; ``depth``: bits per sample; ``layout``: one of ``y4m.LAYOUTS``; ``dedup``: None or (hi, lo, frac, max_hold);
     ``fields``: None or the field order 't' / 'b' of an interlaced input; ``deint_mode``: one of ``deint.MODES``; ``shutter``: None or (S, D) of a
-    synthesized shutter (``demfi_amd.shutter``).  Hashable: (batch, spec) is what a cached ``ClipPipeline`` can be reused for.
-    ``shutter`` comes last and by keyword only, and it is kept beside the tuple's eight items, not among them: a spec without a shutter is, item
-    for item, the record it was before there was one, and one with a shutter equals no plain tuple.  What the namedtuple makes from its items
-    alone does not know it: ``_make``, ``_asdict`` and pickling drop ``shutter``; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
+    synthesized shutter (``demfi_amd.shutter``); ``interlace``: None or (field order 't' / 'b', low-pass mode) of interlaced output
+    (``demfi_amd.interlace``).  Hashable: (batch, spec) is what a cached ``ClipPipeline`` can be reused for.
+    ``shutter`` and ``interlace`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec without
+    them is, item for item, the record it was before there were any, and one with either equals no plain tuple.  What the namedtuple makes from
+    its items alone does not know them: ``_make``, ``_asdict`` and pickling drop both; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
     shutter = None
+    interlace = None
 
-    def __new__(cls, *args, shutter=None, **kw):
+    def __new__(cls, *args, shutter=None, interlace=None, **kw):
         self = super().__new__(cls, *args, **kw)
         if shutter is not None:
             self.shutter = (int(shutter[0]), int(shutter[1]))
+        if interlace is not None:
+            self.interlace = tuple(interlace)
         return self
 
     def _replace(self, **kw):
-        shutter = kw.pop('shutter', self.shutter)
-        return type(self)(*super()._replace(**kw), shutter=shutter)
+        shutter, interlace = kw.pop('shutter', self.shutter), kw.pop('interlace', self.interlace)
+        return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace)
 
     def __eq__(self, other):
-        return tuple.__eq__(self, other) is True and self.shutter == getattr(other, 'shutter', None)
+        return (tuple.__eq__(self, other) is True and self.shutter == getattr(other, 'shutter', None)
+                and self.interlace == getattr(other, 'interlace', None))
 
     def __ne__(self, other):
         return not self == other
 
     def __hash__(self):
-        return hash((tuple(self), self.shutter))
+        return hash((tuple(self), self.shutter) if self.interlace is None else (tuple(self), self.shutter, self.interlace))
 
     def __repr__(self):
-        return super().__repr__()[:-1] + ', shutter=%r)' % (self.shutter,)
+        return super().__repr__()[:-1] + ', shutter=%r%s)' % (self.shutter, ', interlace=%r' % (self.interlace,) if self.interlace is not None else '')
 
     @classmethod
     def of(cls, yuv):
@@ -75,7 +82,8 @@ class EdgeSpec(_EdgeFields):
         dedup, fields = getattr(yuv, 'dedup', None), getattr(yuv, 'fields', None)
         return cls(yuv is not None, getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False)), int(getattr(yuv, 'depth', 8)),
                    getattr(yuv, 'layout', '420'), tuple(dedup) if dedup is not None else None, fields,
-                   getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob', shutter=getattr(yuv, 'shutter', None))
+                   getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob', shutter=getattr(yuv, 'shutter', None),
+                   interlace=getattr(yuv, 'interlace', None))
 
     hi = property(lambda self: self.depth > 8, doc='16-bit frames: the samples of a stream above 8 bits')
 
@@ -83,7 +91,7 @@ class EdgeSpec(_EdgeFields):
         """Every rule about what goes together, before anything is allocated, for a run on a ``retimed`` runner (built with a ratio)."""
         other, edge_only = self.deint_mode != 'bob', self.hi or self.dedup is not None or self.fields is not None
         deint = deint_conflict(self.deint_mode, self.fields is not None, self.dedup is not None)
-        sh = self.shutter
+        sh, il = self.shutter, self.interlace
         for bad, what in ((self.fields not in (None, 't', 'b'), "fields must be None, 't' or 'b', got %r" % (self.fields,)),
                           (deint, 'deint_mode %r with fields=%r, dedup=%r' % (self.deint_mode, self.fields, self.dedup)),
                           (edge_only and not self.y4m, '16-bit frames, repeated frames and fields are those of the Y4M edge (yuv=...) only'),
@@ -98,7 +106,10 @@ class EdgeSpec(_EdgeFields):
                           (sh is not None and not (retimed and self.y4m),
                            'a shutter needs the Y4M edge on a retimed runner, built with the fine ratio r D'),
                           (sh is not None and self.dedup is not None,
-                           'a shutter does not go with repeated frames (dedup): its groups are laid over the regular fine timeline')):
+                           'a shutter does not go with repeated frames (dedup): its groups are laid over the regular fine timeline'),
+                          (il is not None and not (len(il) == 2 and il[0] in ('t', 'b') and il[1] in IL.LOWPASS),
+                           "interlace must be None or (field order 't' / 'b', low-pass mode of %s), got %r" % (IL.LOWPASS, il)),
+                          (il is not None and not (retimed and self.y4m), 'interlaced output needs the Y4M edge on a retimed runner')):
             if bad:
                 raise ValueError('WindowRunner.run_clip_u8: ' + what)
 
@@ -213,6 +224,7 @@ class BgrEdge:
         return ()
 
     attach = around = lambda self, *args: []         # noqa: E731  nothing to attach to; no frame needed besides a batch's own
+    flush = lambda self, *args: None                 # noqa: E731  nothing is held back past the last batch
 
     def upload(self, sl, idx, f):
         if tuple(f.shape) != (self.fh, self.fw, 3) or f.dtype != torch.uint8:
@@ -390,6 +402,16 @@ class ClipPipeline:
             n, b, extra = n + len(wins), b + 1, ()
             wins = list(itertools.islice(it, self.batch))
         self._drain(pending, ev_d2h, sink)
+        res = edge.flush(b & 1, cur)                 # what the edge held back past the last batch: it counts to the last window
+        if res is not None:                          # buffer set b & 1 is free: the batch that last used it was drained
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            with torch.cuda.stream(self.d2h):
+                self.d2h.wait_event(ev)
+                edge.d2h(b & 1, res)
+                ev_d2h[b & 1] = torch.cuda.Event()
+                ev_d2h[b & 1].record(self.d2h)
+            self._drain((b & 1, n - 1, res), ev_d2h, sink)
         return n
 
     def _drain(self, pending, ev_d2h, sink):

@@ -40,8 +40,8 @@ progressive payloads, for tests and documents.
 Known limit: combing weaker than T scores (0, 0), so a slow-moving mixed frame can tie with its clean candidate and keep c.
 
 Out of scope: hybrid material (true 30i sections are decimated like the rest), cadences other than cycle 5 / drop 1, a scene-change
-guard for the decimator, interlaced output, more than one rank (which frames are dropped depends on the whole prefix of the input,
-as with ``--dedup``), and ``--ivtc`` together with ``--deinterlace``.
+guard for the decimator, more than one rank (which frames are dropped depends on the whole prefix of the input,
+as with ``--dedup``), and ``--ivtc`` together with ``--deinterlace``.  Interlaced output is ``--interlace`` (``demfi_amd.interlace``).
 """
 from collections import deque
 from fractions import Fraction

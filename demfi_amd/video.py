@@ -43,8 +43,8 @@ order, each at its own time instant, so n payloads at F are a progressive stream
 ``--mfi 2``).  The payload is uploaded as it is and one launch rebuilds the other field's rows in place by an edge-directed line
 average (csrc/deint.hip, defined by ``deint.bob_plane_np``) before it is converted; everything behind that -- rates, scene cuts,
 repeated frames, the full-length timeline, tiles, depths, layouts, rank sharding -- runs on the progressive stream unchanged.
-``--fps`` and ``--mfi`` count from the field rate 2F.  The output is always progressive.  Not offered: mixed-mode streams (``Im``;
-film carried by pulldown goes through ``--ivtc`` below) and interlaced output; the quarter-row chroma offset of interlaced 4:2:0 fields is not modelled; a
+``--fps`` and ``--mfi`` count from the field rate 2F.  The output is progressive unless ``--interlace`` (below) weaves it back into fields.  Not offered: mixed-mode streams (``Im``;
+film carried by pulldown goes through ``--ivtc`` below); the quarter-row chroma offset of interlaced 4:2:0 fields is not modelled; a
 payload is uploaded once per field.
 
 ``--deinterlace-mode adaptive`` (with ``--deinterlace``; the default ``bob`` is the above) rebuilds the missing rows motion-adaptively
@@ -67,8 +67,8 @@ payloads are ONE launch and the decimation metrics another (csrc/ivtc.hip, defin
 ``woven_sad_np``) over a small device ring of luma planes on a stream of its own; the kept frames are woven on the host.  A matched
 frame that is still combed (more than ``--ivtc-combpel`` samples in a 16x16 block) is bobbed from its top field
 (``--ivtc-combed bob``, the default) or passed through (``keep``) and reported.  Not offered: hybrid film / video material (30i
-sections are decimated like the rest), other cadences, a scene-change guard for the decimator, interlaced output, more than one
-rank, and ``--ivtc`` together with ``--deinterlace``.
+sections are decimated like the rest), other cadences, a scene-change guard for the decimator, more than one
+rank, and ``--ivtc`` together with ``--deinterlace``.  Interlaced output is ``--interlace`` below.
 
 ``--crop auto`` finds letterbox and pillarbox bars (scope films in 16:9, 4:3 in 16:9, windowboxed captures) and keeps them away from
 the network (``demfi_amd.letterbox``): a pre-pass counts, for every row and column of the luma plane of the probed payloads
@@ -101,6 +101,23 @@ still open carry over to the next batch on the device, so the bytes do not depen
 ``--dedup``; one rank.  Not offered: linear-light mixing (the average is taken over the
 gamma-encoded samples), weighted windows (triangle, gaussian), an exposure centred on the frame time, ``--dedup``, several ranks,
 F_out < F_in, ``demfi_amd.clip``.  Without the switch no buffer, launch or stream is added and every byte stays the same.
+
+``--interlace tff|bff`` with ``--interlace-lowpass off|linear|complex`` (default ``linear``) writes interlaced output
+(``demfi_amd.interlace``): frames 2q and 2q + 1 of the progressive stream a run without the switch writes (with ``--shutter``: its mixed
+frames) become the first and the second field in time of written payload q -- rows of parity ``deint.field_parity(order, 0)`` of every
+plane from the first, the others from the second --, an odd last frame is woven with itself, and the header is the progressive one with
+``It`` / ``Ib`` and half the rate.  ``--fps`` and ``--mfi`` keep their meaning: they name the field rate, as behind ``--deinterlace``, so
+``--deinterlace --fps 60000/1001 --interlace tff`` is 50i -> 59.94i (header ``F30000:1001 It``), and 25p or ``--ivtc`` film go to 59.94i
+the same way.  The low-pass damps interline twitter; it is computed from rows of the one frame that owns the output row.  Behind the
+gather (behind the mix with ``--shutter``) ONE launch per batch (csrc/interlace.hip ``demfi_payload_weave``, defined by
+``interlace.weave_payload_np``) weaves every pair whose second frame has arrived into the buffer that crosses D2H, half the bytes of the
+progressive run; the one open frame carries over to the next batch on the device, so the bytes do not depend on the batch size.  Works
+with every switch above; a payload may hold fields of two scenes, which is ordinary interlaced video.  With ``--crop`` the bars go back
+on the host behind the weave, and the rectangle must keep field parity in every plane: rows in units of 2, of 4 for 4:2:0 (``auto`` grows
+to that grid, an explicit misaligned rectangle is the usual error).  One rank.  Not offered: the quarter-row chroma offset of
+interlaced 4:2:0 fields, fusing the weave into the gather so that unused rows are never converted, ``Im`` output, several ranks,
+``demfi_amd.clip``, numeric equality with ffmpeg's ``interlace`` / ``tinterlace`` filters.  Without the switch no buffer, launch or stream
+is added and every byte stays the same.
 """
 import os
 import sys
@@ -112,6 +129,7 @@ from . import _lib as L
 from . import cadence as K
 from . import deint as I
 from . import dist as D
+from . import interlace as IL
 from . import letterbox as LB
 from . import retime as R
 from . import scene as S
@@ -131,11 +149,14 @@ class YuvEdge:
     layout, one of ``y4m.LAYOUTS`` (``siting`` only matters to '420').  ``dedup``: None, or (hi, lo, frac, max_hold) of
     repeated-frame detection (``demfi_amd.cadence``).  ``fields``: None, or the field order 't' / 'b' of an interlaced input whose
     fields are the stream's frames (``demfi_amd.deint``), rebuilt by ``deint_mode`` 'bob' or 'adaptive'.  ``shutter``: None, or (S, D) of a
-    synthesized shutter (``demfi_amd.shutter``): the runner then has the fine ratio r D and the payloads handed out are the mixed ones."""
+    synthesized shutter (``demfi_amd.shutter``): the runner then has the fine ratio r D and the payloads handed out are the mixed ones.
+    ``interlace``: None, or the field order ('tff' / 'bff' / 't' / 'b') of interlaced output (``demfi_amd.interlace``) with the low-pass mode
+    ``interlace_lowpass`` (None: 'linear'; an error without ``interlace``): the payloads handed out are the woven pairs."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
-                 fields=None, deint_mode='bob', shutter=None):
+                 fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None):
         self.dedup, self.shutter = dedup, shutter
+        self.interlace = check_interlace(interlace, interlace_lowpass)
         self.fields, self.deint_mode = fields, deint_mode
         self.depth = y4m.check_depth(depth)
         self.layout = y4m.check_layout(layout)
@@ -180,6 +201,25 @@ def check_shutter(shutter, samples=None, dedup=None, world=1):
                          'repeated frames left out of the input bend; run one of the two')
     check_shutter_ranks(sd, world)
     return sd
+
+
+def check_interlace(interlace, lowpass=None, world=1):
+    """The interlace switches checked: None, or (field order 't' / 'b', low-pass mode).  ``lowpass`` (None: 'linear') says how ``interlace``
+    works, so it is an error without it; interlaced output runs on one rank."""
+    if interlace is None:
+        if lowpass is not None:
+            raise ValueError('--interlace-lowpass (interlace_lowpass) says how --interlace works: give --interlace tff or bff with it')
+        return None
+    il = (IL.parse_order(interlace), IL.check_lowpass(lowpass))
+    check_interlace_ranks(il, world)
+    return il
+
+
+def check_interlace_ranks(interlace, world):
+    """Interlaced output runs on one rank: the two frames of a written payload can straddle two ranks' blocks of windows."""
+    if interlace is not None and world > 1:
+        raise ValueError('VideoRunner: interlace with %d ranks: the two frames of a written payload can straddle the ranks\' blocks of '
+                         'windows; run --interlace on one rank' % world)
 
 
 def check_shutter_ranks(shutter, world):
@@ -259,15 +299,25 @@ class VideoRunner:
     ratio r D, which is refused above ``retime.MAX_RATIO`` once the header is known, before anything is allocated.  Not with ``dedup``
     (refused here) and on one rank (``run_file`` refuses more).  After a run ``last_shutter`` = (S, D) or None, ``last_instants`` counts
     the instants that ran (those the written frames need), ``last_st_frames`` the fine frames that went into the mixes and
-    ``last_shutter_carried`` the samples that were carried from one batch to the next on the device."""
+    ``last_shutter_carried`` the samples that were carried from one batch to the next on the device.  ``interlace``: None (default), or
+    'tff' / 'bff' ('t' / 'b'): interlaced output (``demfi_amd.interlace``).  Frames 2q and 2q + 1 of the progressive stream a run without the
+    switch writes (with ``shutter``: its mixed frames) become the first and the second field of written payload q, an odd last frame is woven
+    with itself, and the header says ``It`` / ``Ib`` at half the rate: ``mfi`` and ``fps`` name the field rate.  ``interlace_lowpass``: None (the
+    default, 'linear'), 'off', 'linear' or 'complex', the vertical filter against interline twitter, within each field's own frame; given
+    without ``interlace`` it is an error.  ONE launch per batch weaves (csrc/interlace.hip ``demfi_payload_weave``), the one open frame is
+    carried on the device and only woven payloads cross D2H.  A ``crop`` rectangle must then keep field parity: rows in units of 2 (4 for
+    4:2:0).  One rank (``run_file`` refuses more).  After a run ``last_interlace`` = 't', 'b' or None and ``last_interlace_carried`` = the
+    frames carried from one batch to the next.  Without it no buffer, launch or stream is added and every byte stays the same."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
                  tile_high_depth=False, deinterlace=False, deinterlace_mode='bob', ivtc=False, ivtc_cthresh=TC.DEFAULT_CTHRESH,
                  ivtc_combpel=TC.DEFAULT_COMBPEL, ivtc_combed=TC.DEFAULT_COMBED, crop=None, crop_limit=LB.DEFAULT_LIMIT,
                  crop_noise=LB.DEFAULT_NOISE, crop_probe=LB.DEFAULT_PROBE, crop_output='pad', shutter=None,
-                 shutter_samples=None, **runner_kw):
+                 shutter_samples=None, interlace=None, interlace_lowpass=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.interlace = check_interlace(interlace, interlace_lowpass)    # (order, low-pass mode) or None
+        self.last_interlace, self.last_interlace_carried = None, 0
         self.shutter = check_shutter(shutter, shutter_samples, dedup)     # (S, D) or None
         self.last_shutter, self.last_shutter_carried = None, 0
         self.crop, (self.crop_limit, self.crop_noise, self.crop_probe, self.crop_output) = check_crop(
@@ -326,11 +376,15 @@ class VideoRunner:
 
     def _out_header(self, hdr):
         ohdr = R.output_header(hdr, hdr.fps * self._ratio(hdr))
+        if self.interlace is not None:               # the same stream as fields: the I tag of the order, half the rate
+            ohdr = IL.interlaced_header(ohdr, self.interlace[0])
         self.last_fps_out = ohdr.fps
         return ohdr
 
     def _n_out(self, n_in, hdr):
-        return R.n_output_frames(n_in, self._ratio(hdr), self.full_length)
+        """Payloads written for n_in input frames: the output frames, or with ``interlace`` their pairs."""
+        n = R.n_output_frames(n_in, self._ratio(hdr), self.full_length)
+        return IL.n_payloads(n) if self.interlace is not None else n
 
     def _progressive(self, hdr):
         """(the header everything downstream works on, field order or None, input frames per payload) of an input with header
@@ -386,7 +440,9 @@ class VideoRunner:
             rect, explicit = probe(), False
         else:
             rect, explicit = LB.bars_rect(self.crop, in_hdr.h, in_hdr.w), True
-        self.last_crop, self.last_crop_note = LB.check_rect(rect, in_hdr.h, in_hdr.w, in_hdr.layout, per, explicit)
+        # interlaced output: the rectangle must keep field parity in every plane of the written payloads, as for interlaced input
+        self.last_crop, self.last_crop_note = LB.check_rect(rect, in_hdr.h, in_hdr.w, in_hdr.layout, 2 if self.interlace is not None else per,
+                                                            explicit)
         return LB.Cropper(in_hdr, self.last_crop) if self.last_crop is not None else None
 
     def crop_report(self):
@@ -484,6 +540,7 @@ class VideoRunner:
         the per-run counters."""
         rn = cr.runner
         i0, p0, c0, m0, s0 = rn.instants_run, rn.instants_padded, rn.cut_windows, rn.shutter_mixed, rn.shutter_carried
+        w0 = rn.interlace_carried
         with cr.oversize_hint():
             n = fn()
         lo = first()
@@ -494,13 +551,16 @@ class VideoRunner:
         self.last_st_frames = sum(kind == R.ST for k in range(lo, lo + n) for _, kind, _ in R.window_outputs(k, r, full_length=self.full_length))
         self.last_shutter = self.shutter
         self.last_shutter_carried = rn.shutter_carried - s0
+        self.last_interlace = self.interlace[0] if self.interlace is not None else None
+        self.last_interlace_carried = rn.interlace_carried - w0
         if self.shutter is not None:                 # the fine frames that went into the mixes
             self.last_st_frames = rn.shutter_mixed - m0
         return n
 
     def _edge(self, hdr, with_s1, order=None):
         return YuvEdge(y4m.auto_matrix(self._matrix_h or hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
-                       self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter)
+                       self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
+                       *(self.interlace or (None, None)))
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
@@ -567,6 +627,7 @@ class VideoRunner:
                              'cannot place its block of windows from k and r alone; run --dedup on one rank' % world)
         check_ivtc(self.ivtc, self.deinterlace, world)
         check_shutter_ranks(self.shutter, world)
+        check_interlace_ranks(self.interlace, world)
         self.last_dups, self._film = [], None
         with open(in_path, 'rb') as f:
             in_hdr, _, offs = y4m.scan(f, self.depths, self.layouts, self.deinterlace, self.ivtc)
@@ -608,12 +669,14 @@ class VideoRunner:
             if not wins:
                 self.last_instants, self.last_st_frames, self.last_cuts, self.last_cut_windows = (0, 0), 0, [], 0
                 self.last_shutter, self.last_shutter_carried = self.shutter, 0
+                self.last_interlace, self.last_interlace_carried = (self.interlace[0] if self.interlace is not None else None), 0
                 return 0, 0
             last = R.first_window(n_in, full) + R.n_windows(n_in, full) - 1
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
             first = S.first_frame(lo) if self.scene_cut is not None else max(lo, 0)
             frames = file_frames(first, lo + len(wins) + 3, fields=per, behind=self._behind(order))
-            at = R.block_offset(len(hb), lo, self._ratio(hdr), out_hdr.payload, full)
+            # interlaced output is one rank's: its payloads follow the header
+            at = len(hb) if self.interlace is not None else R.block_offset(len(hb), lo, self._ratio(hdr), out_hdr.payload, full)
             kw = {'window_index': lambda j: lo + j} if full else {}
             with open(out_path, 'r+b') as o:
                 wr = y4m.Writer(o, out_hdr, at=at)
@@ -669,7 +732,7 @@ def parser():
                                         '-f yuv4mpegpipe -; with --any-layout also 4:2:2, 4:4:4 and grey (C422, C444, Cmono and, with '
                                         '--high-depth, C422pNN, C444pNN, CmonoNN), e.g. ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 '
                                         '-f yuv4mpegpipe -; with --deinterlace also interlaced streams of a fixed field order (It, Ib), every '
-                                        'field a frame at twice the rate.  Output: progressive, C420jpeg (C420pNN at the input\'s depth; the input\'s layout and '
+                                        'field a frame at twice the rate.  Output: progressive (with --interlace: It or Ib at half the rate), C420jpeg (C420pNN at the input\'s depth; the input\'s layout and '
                                         'depth for the other layouts), the input\'s '
                                         'matrix and range.  n input frames give (n-3)*M + 1 output frames: the first and the last '
                                         'input frame have no output, as in the reference (--full-length: n*M frames from input '
@@ -717,7 +780,7 @@ def parser():
                     help='also take interlaced input (It: top field first, Ib: bottom field first; 1080i, 576i, 480i, DV) and bob it on '
                          'the GPU: every field becomes a progressive frame at its own time instant (the other field\'s rows are rebuilt '
                          'by an edge-directed line average), so n payloads at F count as 2n frames at 2F: --mfi M gives 2*M*F, --fps '
-                         'must be at least 2F, and 50i --mfi 2 is 100p.  The output is progressive.  Mixed-mode streams (Im) stay '
+                         'must be at least 2F, and 50i --mfi 2 is 100p.  The output is progressive (fields again with --interlace).  Mixed-mode streams (Im) stay '
                          'refused (film carried by 3:2 pulldown: --ivtc).  Off by default (progressive input only); changes nothing for a progressive stream')
     ap.add_argument('--deinterlace-mode', default='bob', choices=list(I.MODES),
                     help='with --deinterlace: bob (default) rebuilds the other field\'s rows from the field alone; adaptive also looks at '
@@ -768,6 +831,17 @@ def parser():
                          'most %d.  One rank only; not with --dedup.  Off by default' % R.MAX_RATIO)
     ap.add_argument('--shutter-samples', type=int, default=None, metavar='S',
                     help='with --shutter: the sub-frames averaged per written frame, 1 .. %d (default %d)' % (SH.MAX_SAMPLES, SH.DEFAULT_SAMPLES))
+    ap.add_argument('--interlace', type=_value_arg(IL.parse_order), default=None, metavar='tff|bff',
+                    help='write interlaced output: frames 2q and 2q+1 of the output stream become the first and the second field of payload '
+                         'q (tff: the first is the top field, the even rows; bff: the bottom field), an odd last frame is woven with itself, '
+                         'and the header says It / Ib at half the rate, so --fps and --mfi name the FIELD rate: --deinterlace --fps '
+                         '60000/1001 --interlace tff turns 50i into 59.94i, --ivtc --fps 60000/1001 --interlace tff film into 59.94i.  '
+                         'One launch per batch on the GPU; half the bytes leave it.  With --crop, rows in units of 2 (4 for 4:2:0).  One '
+                         'rank only.  Off by default')
+    ap.add_argument('--interlace-lowpass', default=None, choices=list(IL.LOWPASS),
+                    help='with --interlace: the vertical filter against interline twitter, within each field\'s own frame: linear '
+                         '(default, (a + 2c + b + 2) >> 2 over the rows above and below), complex (a five-row filter that keeps more '
+                         'detail) or off')
     T.add_arguments(ap)
     return ap
 
@@ -796,12 +870,16 @@ def main(argv=None):
         if a.crop == 'auto' and not (_is_regular(a.input) and os.path.isfile(a.input) and _is_regular(a.output)):
             raise ValueError(AUTO_NEEDS_A_FILE + ' (and a regular output file)')
         check_shutter(a.shutter, a.shutter_samples, a.dedup or None)
+        check_interlace(a.interlace, a.interlace_lowpass)
     except ValueError as e:
         parser().error(str(e))
-    shutter_kw = {k: v for k, v in (('shutter', a.shutter), ('shutter_samples', a.shutter_samples)) if v is not None}
+    shutter_kw = {k: v for k, v in (('shutter', a.shutter), ('shutter_samples', a.shutter_samples), ('interlace', a.interlace),
+                                    ('interlace_lowpass', a.interlace_lowpass)) if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     if world > 1 and a.shutter is not None:
         raise SystemExit('demfi_amd.video: --shutter runs on one rank (the sub-frames of a written frame straddle the ranks\' blocks)')
+    if world > 1 and a.interlace is not None:
+        raise SystemExit('demfi_amd.video: --interlace runs on one rank (the two frames of a written payload can straddle the ranks\' blocks)')
     if world > 1 and a.dedup:
         raise SystemExit('demfi_amd.video: --dedup runs on one rank (which frames are kept depends on the whole prefix of the input)')
     if world > 1 and a.ivtc:
@@ -855,6 +933,8 @@ def main(argv=None):
             print('demfi_amd.video: %s: no window, only the header was written' %
                   ('no input frame' if a.full_length else 'fewer than 4 input frames'), file=sys.stderr)
         extra = {'shutter': {'angle': str(a.shutter), 'samples': vr.last_shutter[0], 'fine_per_written': vr.last_shutter[1]}} if a.shutter else {}
+        if a.interlace is not None:
+            extra['interlace'] = {'order': vr.last_interlace, 'lowpass': vr.interlace[1], 'carried': vr.last_interlace_carried}
         print(json.dumps({**extra, 'windows': int(tw), 'frames_written': int(tf), 'seconds': round(dt, 2), 'ranks': world,
                           'St_frames_per_s': round(tst / dt, 2) if dt > 0 else None,
                           'frames_per_s': round(tf / dt, 2) if dt > 0 else None,

@@ -1,6 +1,6 @@
 """The Y4M edge of the clip pipeline (``demfi_amd.pipeline``): Y4M payloads in and out, every window on its own plan, all options in
 one ``pipeline.EdgeSpec``.  One stage per job, each with its own buffers: ``Ingest``, ``SceneScores``, ``DedupProbe``, the pure function
-``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, ``Shutter``; ``Y4mEdge`` keeps their order and the payloads' way out."""
+``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, ``Shutter`` and ``Interlacer``; ``Y4mEdge`` keeps their order and the payloads' way out."""
 import ctypes as C
 
 import numpy as np
@@ -9,6 +9,7 @@ import torch
 from . import _lib as L
 from . import cadence as K
 from . import deint as I
+from . import interlace as IL
 from . import retime as R
 from . import scene as S
 from . import shutter as SH
@@ -299,13 +300,14 @@ class Shutter:
     batches later, when the host has drained the batch that last copied from it (``ClipPipeline._drain`` waits for that batch's D2H, which
     waited for its compute, where the copy of the table ran)."""
 
-    def __init__(self, runner, spec, nout, batch, Pb, es, dev):
+    def __init__(self, runner, spec, nout, batch, Pb, es, dev, front=0):
         (self.S, self.D), self.rn, self.lib, self.Pb, self.es = spec.shutter, runner, runner.lib, Pb, es
+        self.front = front                           # rows left free in front of mixed[i] for the stage behind (``Interlacer``'s carry row)
         self.lead = self.S - 1
         # written frames of a batch: the multiples of D among the fine indices of its windows (each owns up to J, the last one of the full-length
         # timeline 2 J, nout in all), and the group carried into it
         self.rows = nout // self.D + batch + 2
-        self.mixed = [torch.empty((self.rows, Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.mixed = [torch.empty((front + self.rows, Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.offs = [torch.empty(self.rows * self.S, dtype=torch.int64, device=dev) for _ in range(2)]
         self.h_offs = [torch.empty((self.rows, self.S), dtype=torch.int64).pin_memory() for _ in range(2)]
         self.begin()
@@ -339,8 +341,77 @@ class Shutter:
             od = self.offs[i][:nc * S]
             od.copy_(host.view(-1), non_blocking=True)
             L.check(self.lib.demfi_payload_mix(yuv_out[i].data_ptr(), host.data_ptr(), od.data_ptr(), nc, S, self.Pb // self.es, self.es,
-                                               self.mixed[i].data_ptr(), self.Pb, stream.cuda_stream), 'payload_mix')
+                                               self.mixed[i][self.front:].data_ptr(), self.Pb, stream.cuda_stream), 'payload_mix')
         return counts
+
+
+class Interlacer:
+    """Progressive payloads -> woven ones (``demfi_amd.interlace``, ``spec.interlace`` = (field order, low-pass mode)).  Written payload q
+    weaves frames 2q (the first field in time) and 2q + 1 of the progressive stream.  The stage sits behind the gather, or behind
+    ``Shutter.mix``: after a batch's frames are written into ``src[i]`` from row ``lead`` on, ``weave`` closes every pair whose second frame has
+    arrived (``interlace.close_pairs``; the odd tail too when the batch holds the clip's last window) and ONE ``demfi_payload_weave`` launch on
+    the compute stream writes them into ``woven[i]``, which is what crosses D2H; a woven payload counts to the window that completed it.  The
+    one frame still open carries over on the device: ``carry`` copies it into row 0 of the next batch's source buffer (``lead`` = 1 row in
+    front of its frames), so which batch a frame came with never shows.  A run whose edge never learns which window is the last (``--dedup``)
+    ends with ``flush``, which weaves the open frame with itself.  The runner counts: ``interlace_woven`` the payloads woven,
+    ``interlace_carried`` the frames carried from one batch to the next.  ``h_offs``: the pinned offset tables, one per buffer set, rewritten
+    two batches later, when the host has drained the batch that last copied from them (as ``Shutter.h_offs``)."""
+    lead = 1
+
+    def __init__(self, runner, spec, rows_in, h, w, Pb, es, dev):
+        (self.order, self.lowpass), self.rn, self.lib, self.Pb, self.es = spec.interlace, runner, runner.lib, Pb, es
+        self.q0, self.mode, self.peak = I.field_parity(self.order, 0), IL.LOWPASS.index(self.lowpass), (1 << spec.depth) - 1
+        self.planes = np.ascontiguousarray(IL.plane_shapes(h, w, spec.layout), dtype=np.int32)
+        self.rows = rows_in // 2 + 1                 # pairs of the carried frame and a batch's rows_in frames, the odd tail among them
+        self.woven = [torch.empty((self.rows, Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.offs = [torch.empty(self.rows * 2, dtype=torch.int64, device=dev) for _ in range(2)]
+        self.h_offs = [torch.empty((self.rows, 2), dtype=torch.int64).pin_memory() for _ in range(2)]
+        self.begin()
+
+    def begin(self):
+        self.open = None                             # (buffer set, row) of the one open frame
+
+    def carry(self, i, src):
+        """Before batch i's frames are written (compute stream): the open frame moves from the other buffer set in front of this one's."""
+        if self.open is None:
+            return
+        j, row = self.open
+        if j != i:
+            src[i][0].copy_(src[j][row])
+            self.rn.interlace_carried += 1
+        elif row != 0:
+            raise RuntimeError('interlace: the open frame lies at row %d of the buffer set about to be written' % row)
+        self.open = (i, 0)
+
+    def _launch(self, i, pairs, src, stream):
+        nc = len(pairs)
+        if nc > self.rows:
+            raise RuntimeError('interlace: %d woven payloads for %d payload rows' % (nc, self.rows))
+        if nc:
+            self.rn.interlace_woven += nc
+            host = self.h_offs[i][:nc]
+            host.numpy()[:] = [[a * self.Pb, b * self.Pb] for a, b in pairs]
+            od = self.offs[i][:nc * 2]
+            od.copy_(host.view(-1), non_blocking=True)
+            L.check(self.lib.demfi_payload_weave(src[i].data_ptr(), host.data_ptr(), od.data_ptr(), nc, self.planes.ctypes.data, len(self.planes),
+                                                 self.es, self.peak, self.q0, self.mode, self.woven[i].data_ptr(), self.Pb, stream.cuda_stream),
+                    'payload_weave')
+
+    def weave(self, i, counts, ends, src, stream):
+        """counts[w]: the progressive frames of window w, written into src[i] from row ``lead`` on; returns the woven payloads per window."""
+        pairs, woven, left = IL.close_pairs(0 if self.open is not None else None, counts, ends, self.lead)
+        self.open = (i, left) if left is not None else None
+        self._launch(i, pairs, src, stream)
+        return woven
+
+    def flush(self, i, src, stream):
+        """After the last batch: the frame still open, if any, is woven with itself into woven[i]; returns the payloads (0 or 1)."""
+        if self.open is None:
+            return 0
+        self.carry(i, src)
+        self.open = None
+        self._launch(i, [(0, 0)], src, stream)
+        return 1
 
 
 class TileGrid:
@@ -412,10 +483,16 @@ class Y4mEdge:
         self.sinks = [torch.empty((runs_max * io.nt, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)]
         self.offs = [torch.empty(nout, dtype=torch.int64, device=dev) for _ in range(2)]
         # a shutter mixes the gathered (fine) payloads into written ones: those cross D2H, and yuv_out[i] gets its carry rows in front
-        sh = self.shutter = Shutter(runner, spec, nout, batch, ing.Pb, ing.es, dev) if spec.shutter is not None else None
-        lead, nhost = (sh.lead, sh.rows) if sh is not None else (0, nout)
+        # interlaced output weaves the progressive payloads (gathered, or mixed) in pairs: the woven ones cross D2H, and the buffer it reads gets
+        # its carry row in front
+        front = Interlacer.lead if spec.interlace is not None else 0
+        sh = self.shutter = Shutter(runner, spec, nout, batch, ing.Pb, ing.es, dev, front) if spec.shutter is not None else None
+        lead, nhost = (sh.lead, sh.rows) if sh is not None else (front, nout)
         self.yuv_out = [torch.empty((lead + nout, ing.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.written = sh.mixed if sh is not None else self.yuv_out
+        il = self.interlacer = Interlacer(runner, spec, nhost, h, w, ing.Pb, ing.es, dev) if spec.interlace is not None else None
+        if il is not None:
+            self.progressive, self.written, nhost = self.written, il.woven, il.rows
         self.h_yuv = [torch.empty((nhost, ing.Pb), dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.yuv = self.window_index = self.det = self.kept = self.gather = None
 
@@ -433,6 +510,8 @@ class Y4mEdge:
         self.yuv, self.window_index, self.det, ing.raw = yuv, window_index, None, {}
         if self.shutter is not None:
             self.shutter.begin()
+        if self.interlacer is not None:
+            self.interlacer.begin()
         ing.to_bgr, self.gather, sad = yuv_calls(self.rn.lib, self.spec, ing.fh, ing.fw, yuv)
         if sc is None:
             return ()
@@ -463,12 +542,24 @@ class Y4mEdge:
         if self.kept is not None:
             self.kept.st_frames += st_frames
         self._run_windows(i, runs)
-        sh, read = self.shutter, [fr for fr, _, _ in runs]
+        sh, il, read = self.shutter, self.interlacer, [fr for fr, _, _ in runs]
+        if il is not None:
+            il.carry(i, self.progressive)
         if sh is None:
-            return self._gather(i, outs, cur), read
-        sh.carry(i, self.yuv_out)
-        self._gather(i, outs, cur, sh.lead)
-        return sh.mix(i, fine, ends, self.yuv_out, cur), read
+            counts = self._gather(i, outs, cur, il.lead if il is not None else 0)
+        else:
+            sh.carry(i, self.yuv_out)
+            self._gather(i, outs, cur, sh.lead)
+            counts = sh.mix(i, fine, ends, self.yuv_out, cur)
+        if il is not None:
+            counts = il.weave(i, counts, ends, self.progressive, cur)
+        return counts, read
+
+    def flush(self, i, cur):
+        """After the last batch's ``run``: what is still to be written into buffer set i (None: nothing), for ``d2h`` and ``drain``."""
+        if self.interlacer is None or not self.interlacer.flush(i, self.progressive, cur):
+            return None
+        return [1]
 
     def _run_windows(self, i, runs):
         """Planned run w = (4 slots, instants, kinds) becomes the ``io.nt`` runner runs w * nt + j, which run its instants into ``io.dst[i]``;
@@ -523,7 +614,7 @@ class Y4mEdge:
     def drain(self, i, k0, counts, sink):
         pos = 0
         for j, c in enumerate(counts):
-            if c or self.shutter is None:            # a window that completed no written frame has nothing to hand out
+            if c or (self.shutter is None and self.interlacer is None):  # a window that completed no written payload has nothing to hand out
                 sink(k0 + j, self.h_yuv[i][pos:pos + c])
             pos += c
 

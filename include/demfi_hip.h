@@ -507,6 +507,26 @@ int demfi_luma_line_counts(const uint8_t* base, const int64_t* offsets, int n, i
 int demfi_payload_mix(const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, int n, int smax, int64_t P,
                       int sample_bytes, uint8_t* dst, int64_t dst_stride, void* stream);
 
+/* ---- interlaced output of the Y4M edge (csrc/interlace.hip; demfi_amd/video.py --interlace) ------------------------------------------
+ * payload_weave: written payload i (n per launch) weaves two progressive payloads: row i has two int64 BYTE offsets from base,
+ * offsets[2 i] the frame of the first field in time and offsets[2 i + 1] that of the second (equal for an odd tail).  A payload is
+ * n_planes (1..3) planes one behind the other, plane p of planes[2 p] rows and planes[2 p + 1] columns of samples (1..32768 each;
+ * planes is HOST memory); sample_bytes = 1, or 2 for 16-bit little-endian samples (even addresses and stride).  Output row y of a
+ * plane comes from the first source when y mod 2 == q0 (0 or 1), else from the second, low-passed vertically within that one source,
+ * rows clamped to the plane: lowpass 0 = off (c), 1 = linear ((a + 2 c + b + 2) >> 2), 2 = complex (v = clip((4 + 6 c + 2 (a + b) - a2
+ * - b2) >> 3, 0, peak); a + b > 2 c ? max(v, c) : min(v, c)) with c, a / b, a2 / b2 the source's rows y, y -/+ 1, y -/+ 2; the numpy
+ * definition is demfi_amd/interlace.py weave_payload_np.  The payload is written at dst + i*dst_stride; the bytes between its end and
+ * dst_stride are not written.  The offsets are passed twice with the same content: offsets in HOST memory, checked here before
+ * anything is launched, and offsets_dev in DEVICE memory, read by the kernel.  DEMFI_ERR_ARG, with nothing launched: a NULL buffer,
+ * sample_bytes not 1 or 2, 16-bit samples at an odd address, offset or stride, peak outside 1..65535 (1..255 for bytes), q0 or
+ * lowpass out of range, no plane or more than three, a plane size out of range, dst_stride below the payload, a negative offset.
+ * When base + every offset, every plane's first byte and row length in bytes, dst and dst_stride are multiples of 16 every thread
+ * walks a 16-byte column down a strip of rows with 16-byte loads and streaming stores; otherwise the whole launch goes sample by
+ * sample with the same arithmetic (decided per launch).  One launch for all n rows, no LDS, no atomics; the sources may overlap each
+ * other but not dst; n <= 0 does nothing. */
+int demfi_payload_weave(const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, int n, const int32_t* planes,
+                        int n_planes, int sample_bytes, int peak, int q0, int lowpass, uint8_t* dst, int64_t dst_stride, void* stream);
+
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
  * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
