@@ -22,14 +22,7 @@ import torch
 
 from demfi_amd import _lib as L
 from demfi_amd.engine import Plan, _Src, _view
-
-G = 4                 # guard pixels on every side of a frame
-GAP = 256             # poisoned bytes between two blocks (at least)
-POISON = 0xFF
-
-
-class GuardError(AssertionError):
-    pass
+from tests.guarded_arena import G, GAP, POISON, GuardError    # one error type and one guard geometry for both harnesses
 
 
 class _Block:

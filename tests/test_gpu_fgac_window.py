@@ -11,33 +11,41 @@ pytestmark = pytest.mark.gpu
 
 from demfi_amd import _lib as L, synthetic_state_dict     # noqa: E402
 from oracle import demfi_oracle as O                      # noqa: E402
+from tests import guarded_arena as GA                     # noqa: E402
 
 DEV = 'cuda:0'
 
 
 def _nhwc(t):
-    h, w, c = t.shape
-    return L.View(t.data_ptr(), c, w * c, 1, 0, 1 if t.dtype == torch.float32 else 0, 0)
+    """demfi_view of one NHWC image [H,W,C], strides from the tensor."""
+    return L.View(t.data_ptr(), t.stride(1), t.stride(0), 1, 0, 1 if t.dtype == torch.float32 else 0, 0)
 
 
-def _run(rk, sk, fl, rr, mode, sr=0):
-    """rk, sk: fp16 NHWC GPU tensors; returns (fac [C,H,W] fp32 cpu, attn [E,H,W] cpu)."""
+def _run(rk, sk, fl, rr, mode, sr=0, al=None, want_attn=True):
+    """rk, sk: NHWC GPU tensors of the path dtype; returns (fac [C,H,W] fp32 cpu, attn [E,H,W] cpu, or None without attn_out).
+    al: the allocator of tests/guarded_arena.py that the views (ref_k, source_k, the pooled copies, out) and the bare pointers (flow,
+    attn_out) are cut from; every launch goes through GA.launch.  Plain contiguous tensors by default."""
     lib = L.load()
+    al = al if al is not None else GA.Plain(DEV)
     H, W, Cc = rk.shape
     st = torch.cuda.current_stream().cuda_stream
+    rk = al.fill(al.fat(1, H, W, Cc, rk.dtype, name='ref_k'), rk[None])[0]
+    sk = al.fill(al.fat(1, H, W, Cc, sk.dtype, name='source_k'), sk[None])[0]
+    fl = al.fill(al.flat(1, (2, H, W), torch.float32, name='flow'), fl[None])
     if sr:
-        rk2, sk2 = torch.empty_like(rk), torch.empty_like(sk)
+        rk2, sk2 = al.fat(1, H, W, Cc, rk.dtype, name='ref_k pooled')[0], al.fat(1, H, W, Cc, sk.dtype, name='source_k pooled')[0]
         for a, b in ((rk, rk2), (sk, sk2)):
             va, vb = _nhwc(a), _nhwc(b)
-            L.check(lib.demfi_avg_pool_fat(C.byref(va), C.byref(vb), Cc, H, W, sr, st))
+            GA.launch(al, lambda: lib.demfi_avg_pool_fat(C.byref(va), C.byref(vb), Cc, H, W, sr, st), [b], 'avg pool')
         rk, sk = rk2, sk2
-    out = torch.zeros_like(rk)
+    out = al.fat(1, H, W, Cc, rk.dtype, name='fac')[0]
     R = 2 * rr + 1
-    attn = torch.zeros(R * R, H, W, device=DEV)
+    attn = al.flat(1, (R * R, H, W), torch.float32, name='attn') if want_attn else None
     vr, vs, vo = _nhwc(rk), _nhwc(sk), _nhwc(out)
-    L.check(lib.demfi_fgac_window(C.byref(vr), C.byref(vs), fl.data_ptr(), C.byref(vo), Cc, H, W, rr, mode, attn.data_ptr(), st))
-    torch.cuda.synchronize()
-    return out.permute(2, 0, 1).float().cpu(), attn.cpu()
+    GA.launch(al, lambda: lib.demfi_fgac_window(C.byref(vr), C.byref(vs), fl.data_ptr(), C.byref(vo), Cc, H, W, rr, mode,
+                                                attn.data_ptr() if want_attn else None, st),
+              [out] + ([attn] if want_attn else []), 'fgac window')
+    return out.permute(2, 0, 1).float().cpu(), attn[0].cpu() if want_attn else None
 
 
 @pytest.mark.parametrize('rr,sr', [(1, 0), (2, 0), (1, 1)])
