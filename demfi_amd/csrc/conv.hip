@@ -21,7 +21,8 @@ bool persist_eligible(const demfi_conv* h)
     if (h->n_chunks != 1 || h->n_pieces != 1 || h->chunks[0].nks != 4 || h->rec_bytes != 128) return false;
     const demfi_piece& p = h->pieces[0];
     if (!p.fat || p.nch != 64 || p.up_shift != 0 || !p.v.ptr || p.v.is_f32) return false;
-    return persist_out_eligible(h, h->nco == 2);                  // the staged-store kernel (NCO == 2) also has a tanh epilogue
+    if (!persist_out_eligible(h, h->nco == 2)) return false;      // the staged-store kernel (NCO == 2) also has a tanh epilogue
+    return demfi_c64_strides_ok(h);                               // conv_c64.hip: 32-bit lane offsets inside a tile
 }
 
 // THIN epilogue of the narrow kernel: <= 32 packed couts, every octet routed to a planar fp32 [C,H,W] destination
@@ -56,7 +57,10 @@ static bool narrow_eligible(const demfi_conv* h)
         if ((p.lds_ch * 2) % 16 || (p.nch * 2) % 16) return false;
         if (p.v.ptr == nullptr) continue;
         if (!p.fat || p.up_shift != 0 || p.v.is_f32 || p.v.sc != 1) return false;
-        if (p.v.sy * 2 * 16 >= (int64_t)1 << 31 || p.v.sx * 2 * 64 >= (int64_t)1 << 31) return false;   // 32-bit offsets inside a tile
+        // 32-bit offsets inside a tile: the DMA lanes form ly * sy + lxx * sx in a signed int (conv_narrow.hip), so the SUM is bounded
+        // (16 rows, 64 records: the 7x7 window is 14 x 38) and no stride is negative.  tests/far_memory.py PITCH_FAMILIES names 16 / 64.
+        if (p.v.sy < 0 || p.v.sx < 0 || p.v.sy >= (int64_t)1 << 31 || p.v.sx >= (int64_t)1 << 31) return false;
+        if (p.v.sy * 2 * 16 + p.v.sx * 2 * 64 >= (int64_t)1 << 31) return false;
         ++nreal;
     }
     if (nreal < 1 || nreal > 2) return false;

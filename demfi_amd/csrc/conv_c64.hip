@@ -26,6 +26,12 @@ constexpr int P_TILE_BYTES = P_NI * 1024;                       // 44,032 B per 
 
 constexpr int P_NT = NT + 64;                                   // 4 MFMA waves + 1 DMA wave
 
+// Both kernels add ONE 32-bit per-lane byte offset to a uniform 64-bit tile base.  Source: the DMA lanes' off[] spans the haloed window,
+// up to P_LH rows and P_LW records (+ the 128-byte record) from the tile origin, a signed int in the 32-cout kernel.  Destination of the
+// staged-store kernel: the helpers' doff[] spans the TH x TW output tile.  (The MFMA waves' own stores and every residual load multiply
+// int64 strides.)  A view beyond these bounds is not this family's: demfi_conv_owner passes it on.
+constexpr int64_t P_OFF_LIMIT = (int64_t)1 << 31;
+
 // One k-step pair of fragments: 2 k-steps x (NCO A fragments + 2 B fragments)
 
 #ifndef DEMFI_P_NDMA
@@ -665,6 +671,19 @@ static int launch_stg(const demfi_conv* h, const demfi_conv* dev, hipStream_t st
 }  // namespace
 
 int demfi_c64_trace_collect(unsigned long long* acc) { return TRACE_DRAIN(acc, true); }
+
+bool demfi_c64_strides_ok(const demfi_conv* h)
+{
+    const demfi_view& s = h->pieces[0].v;
+    if (s.sy < 0 || s.sx < 0 || s.sy >= P_OFF_LIMIT || s.sx >= P_OFF_LIMIT) return false;
+    if ((s.sy * P_LH + s.sx * P_LW) * 2 + 128 >= P_OFF_LIMIT) return false;
+    if (h->nco == 2) {
+        const demfi_view& d = h->segs[h->sub_seg[0]].dst;
+        if (d.sy < 0 || d.sx < 0 || d.sy >= P_OFF_LIMIT || d.sx >= P_OFF_LIMIT) return false;
+        if ((d.sy * TH + d.sx * TW) * 2 + 128 >= P_OFF_LIMIT) return false;
+    }
+    return true;
+}
 
 int demfi_c64_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st)
 {

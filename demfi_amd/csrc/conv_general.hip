@@ -112,9 +112,11 @@ __global__ __launch_bounds__(NT, (NCO <= 1 ? 4 : (NCO == 2 ? 3 : 2))) void conv_
                 // general kernel's layers: profiles/r03_notes.md section 13)
                 constexpr int STG_UNR = 4;
                 // interior tiles of tensors below 4 GiB per image (every tile but the frame's border): no bounds tests, 32-bit offsets
-                // from a uniform base (the saddr form of the load: no 64-bit address arithmetic per item)
-                const bool fast = src != nullptr && iy0 >= 0 && iy0 + LH <= inH && ix0 >= 0 && ix0 + LW <= inW &&
-                                  (uint64_t)(((inH - 1) >> ush) + 1) * (uint64_t)sy < ((uint64_t)1 << 32) && sy >= 0 && sx >= 0;
+                // from a uniform base (the saddr form of the load: no 64-bit address arithmetic per item).  "Below 4 GiB" is rows * sy
+                // PLUS columns * sx: a view may have sx > sy (rows interleaved between two records), so neither product bounds the other
+                const bool fast = src != nullptr && iy0 >= 0 && iy0 + LH <= inH && ix0 >= 0 && ix0 + LW <= inW && sy >= 0 && sx >= 0 &&
+                                  sy < ((int64_t)1 << 32) && sx < ((int64_t)1 << 32) &&
+                                  (uint64_t)(((inH - 1) >> ush) + 1) * (uint64_t)sy + (uint64_t)(((inW - 1) >> ush) + 1) * (uint64_t)sx < ((uint64_t)1 << 32);
                 if (fast) {
                     const uint32_t sy32 = (uint32_t)sy, sx32 = (uint32_t)sx;
                     for (int it0 = tid; it0 < nitems; it0 += STG_UNR * NT) {

@@ -7,6 +7,7 @@
 int demfi_conv_general_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, size_t lds);
 // conv_c64.hip: 3x3, one 64-channel NHWC piece, 32 / 64 couts (staged-store kernel for 64)
 int demfi_c64_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st);
+bool demfi_c64_strides_ok(const demfi_conv* h);      // the 32-bit lane offsets of both kernels hold this view's strides
 // conv_narrow.hip: 3x3 / 7x7 over one chunk of 16 / 32 / 64 channels; thin: planar fp32 outputs (no 7x7 instantiation)
 int demfi_narrow_launch(const demfi_conv* h, const demfi_conv* dev, hipStream_t st, bool thin);
 // conv_sep.hip: the round-1..5 SepConvGRU kernel (1x5 / 5x1, two 64-channel pieces)

@@ -378,8 +378,9 @@ static bool sep_eligible(const demfi_conv* h)
         if (ch.n_pieces != 1 || ch.nks != 4) return false;
         const demfi_piece& p = h->pieces[ch.first_piece];
         if (!p.fat || p.nch != 64 || p.up_shift || p.v.ptr == nullptr || p.v.sc != 1 || p.v.is_f32) return false;
-        // 32-bit per-lane offsets inside a tile
-        if (p.v.sy * 2 * 40 >= (int64_t)1 << 31 || p.v.sx * 2 * 40 >= (int64_t)1 << 31) return false;
+        // 32-bit per-lane offsets inside a tile: a signed sum of a line and a pixel offset (tests/far_memory.py PITCH_FAMILIES names 40 / 40)
+        if (p.v.sy < 0 || p.v.sx < 0 || p.v.sy >= (int64_t)1 << 31 || p.v.sx >= (int64_t)1 << 31) return false;
+        if (p.v.sy * 2 * 40 + p.v.sx * 2 * 40 >= (int64_t)1 << 31) return false;
     }
     for (int cb = 0; cb < h->cout_pad / 64; ++cb) {
         const int sgi = h->sub_seg[cb * 2];

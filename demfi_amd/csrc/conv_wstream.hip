@@ -271,7 +271,9 @@ static bool wstream_eligible(const demfi_conv* h, int ks = 7, int nch = 2)
         const demfi_piece& p = h->pieces[ch.first_piece];
         if (!p.fat || p.nch != 32 || p.up_shift || !p.v.ptr || p.v.sc != 1 || p.v.is_f32) return false;
         if (ks == 7 && (p.v.sx != p0.v.sx || p.v.sy != p0.v.sy || p.v.sb != p0.v.sb)) return false;
-        if (p.v.sy * 2 * 40 >= (int64_t)1 << 31 || p.v.sx * 2 * 48 >= (int64_t)1 << 31) return false;   // 32-bit per-lane offsets inside a tile
+        // 32-bit per-lane offsets inside a tile: a signed sum of a row and a record offset (tests/far_memory.py PITCH_FAMILIES names 40 / 48)
+        if (p.v.sy < 0 || p.v.sx < 0 || p.v.sy >= (int64_t)1 << 31 || p.v.sx >= (int64_t)1 << 31) return false;
+        if (p.v.sy * 2 * 40 + p.v.sx * 2 * 48 >= (int64_t)1 << 31) return false;
     }
     const int sgi = h->sub_seg[0];
     if (sgi < 0 || (nch == 2 && (h->sub_seg[1] != sgi || h->oct_ch[4] != h->oct_ch[0] + 32))) return false;

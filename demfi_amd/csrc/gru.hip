@@ -670,7 +670,8 @@ bool g_layer_ok(const demfi_conv* h)
         if (ch.n_pieces != 1 || ch.nks != 4) return false;
         const demfi_piece& p = h->pieces[ch.first_piece];
         if (!p.fat || p.nch != 64 || p.up_shift || !p.v.ptr || p.v.sc != 1 || p.v.is_f32) return false;
-        if (p.v.sy * 2 * 24 + p.v.sx * 2 * 40 >= (int64_t)1 << 31) return false;        // 32-bit per-lane offsets inside a window
+        if (p.v.sy < 0 || p.v.sx < 0 || p.v.sy >= (int64_t)1 << 31 || p.v.sx >= (int64_t)1 << 31) return false;
+        if (p.v.sy * 2 * 24 + p.v.sx * 2 * 40 >= (int64_t)1 << 31) return false;        // 32-bit per-lane offsets inside a window (tests/far_memory.py PITCH_FAMILIES names 24 / 40)
     }
     const int sgi = h->sub_seg[0];
     if (sgi < 0 || h->sub_seg[1] != sgi) return false;
@@ -703,7 +704,7 @@ int g_launch(GArgs& a, const demfi_conv* h, const demfi_seg& out, void* stream)
     a.n_ls = (a.Llen + GCfg<MODE>::TL - 1) / GCfg<MODE>::TL;
     const int64_t total = (int64_t)a.n_pt * a.n_ls * a.batch;
     if (total <= 0 || total >= (int64_t)1 << 30) return demfi_set_error(DEMFI_ERR_ARG, "demfi_gru: empty or oversized launch");
-    if (a.d_sl * 24 + a.d_sp * 40 >= (int64_t)1 << 31) return demfi_set_error(DEMFI_ERR_ARG, "demfi_gru: destination strides exceed 32-bit lane offsets");
+    if (a.d_sl < 0 || a.d_sp < 0 || a.d_sl >= (int64_t)1 << 31 || a.d_sp >= (int64_t)1 << 31 || a.d_sl * 24 + a.d_sp * 40 >= (int64_t)1 << 31) return demfi_set_error(DEMFI_ERR_ARG, "demfi_gru: destination strides exceed 32-bit lane offsets");
     DEMFI_LDS_ATTR(gru_sep5_kernel<MODE>);
     const int grid = total >= 256 ? 256 : (int)total;
     hipLaunchKernelGGL(gru_sep5_kernel<MODE>, dim3(grid), dim3(G_NTHREADS), GCfg<MODE>::LDS, (hipStream_t)stream, a);

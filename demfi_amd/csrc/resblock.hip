@@ -534,7 +534,9 @@ extern "C" int demfi_resblock_eligible(const demfi_conv* h1, const demfi_conv* h
     if ((const char*)s2.res.ptr + (int64_t)h2->oct_ch[0] * 2 != (const char*)x.ptr || s2.res.sx != x.sx || s2.res.sy != x.sy || s2.res.sb != x.sb || s2.res.sc != 1) return 0;
     if (s2.dst.ptr == x.ptr) return 0;                           // in-place is not possible: neighbouring strips read the halo
     // 32-bit per-lane offsets inside a window / an output block
-    if (x.sy * 2 * 20 + x.sx * 2 * 40 >= (int64_t)1 << 31 || s2.dst.sy * 2 * 20 + s2.dst.sx * 2 * 40 >= (int64_t)1 << 31) return 0;
+    for (const demfi_view* v : {&x, &s2.dst})
+        if (v->sy < 0 || v->sx < 0 || v->sy >= (int64_t)1 << 31 || v->sx >= (int64_t)1 << 31) return 0;
+    if (x.sy * 2 * 20 + x.sx * 2 * 40 >= (int64_t)1 << 31 || s2.dst.sy * 2 * 20 + s2.dst.sx * 2 * 40 >= (int64_t)1 << 31) return 0;      // (tests/far_memory.py PITCH_FAMILIES names 20 / 40)
     return 1;
 }
 

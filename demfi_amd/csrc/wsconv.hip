@@ -441,10 +441,12 @@ bool demfi_ws2_eligible(const demfi_conv* h)
             } else {
                 const demfi_piece& z = h->pieces[ch.first_piece + 2];
                 if (!q.v.ptr || !q.fat || q.nch != 8 || q.up_shift || q.v.sc != 1 || q.v.is_f32 || z.v.ptr != nullptr || z.nch != 8) return false;
+                if (q.v.sy < 0 || q.v.sx < 0 || q.v.sy >= (int64_t)1 << 30 || q.v.sx >= (int64_t)1 << 30) return false;
                 if (q.v.sy * 4 * 40 + q.v.sx * 4 * 40 >= (int64_t)1 << 31) return false;
             }
         }
-        if (p.v.sy * 4 * 40 + p.v.sx * 4 * 40 >= (int64_t)1 << 31) return false;       // 32-bit per-lane offsets inside a tile
+        if (p.v.sy < 0 || p.v.sx < 0 || p.v.sy >= (int64_t)1 << 30 || p.v.sx >= (int64_t)1 << 30) return false;
+        if (p.v.sy * 4 * 40 + p.v.sx * 4 * 40 >= (int64_t)1 << 31) return false;       // 32-bit per-lane offsets inside a tile (tests/far_memory.py PITCH_FAMILIES names 80 / 80 bytes)
     }
     for (int b = 0; b < nblk; ++b) {
         const int sgi = h->sub_seg[nco * b];
@@ -455,6 +457,14 @@ bool demfi_ws2_eligible(const demfi_conv* h)
         if (sg.mode != DEMFI_MODE_STORE || sg.scale != 1 || sg.dy || sg.dx || !sg.dst.ptr || sg.dst.is_f32 || sg.dst.sc != 1 || sg.aux.ptr) return false;
         if (sg.act != DEMFI_ACT_NONE && sg.act != DEMFI_ACT_RELU) return false;
         if (sg.res.ptr && (sg.res.is_f32 || sg.res.sc != 1)) return false;
+        // WsBlock holds d_sx / d_sy / r_sx / r_sy as int bytes; a lane multiplies its column of the WHOLE row (up to the padded width)
+        // by sx and a row of its group (< 8 = RPW of both tile shapes) by sy in 32 bits (item_store, res_fetch)
+        const int64_t wpad = ((int64_t)h->W + 31) / 32 * 32;
+        for (const demfi_view* v : {&sg.dst, &sg.res}) {
+            if (!v->ptr) continue;
+            if (v->sx < 0 || v->sy < 0 || v->sx >= (int64_t)1 << 30 || v->sy >= (int64_t)1 << 30) return false;
+            if (v->sx * 2 * wpad + 64 >= (int64_t)1 << 31 || v->sy * 2 * 8 >= (int64_t)1 << 31) return false;
+        }
     }
     if (h->u8_sink || h->pack.ptr) return false;
     return true;

@@ -44,9 +44,10 @@ class _Block:
 
 
 class GuardedPlan(Plan):
-    def __init__(self, H, W, dtype=torch.float16, device='cuda:0', state_dict=None, capacity=32 << 20):
+    def __init__(self, H, W, dtype=torch.float16, device='cuda:0', state_dict=None, capacity=32 << 20, slab=None):
+        """slab: a uint8 tensor to build the plan in (tests/far_memory.py: one multi-GiB slab for every case); it is poisoned here."""
         super().__init__(H, W, dtype, device, state_dict)
-        self.slab = torch.full((capacity,), POISON, dtype=torch.uint8, device=self.device)
+        self.slab = torch.full((capacity,), POISON, dtype=torch.uint8, device=self.device) if slab is None else slab.fill_(POISON)
         self._cur = (-self.slab.data_ptr()) % 256 + GAP
         self._blocks = []                 # in address order
         self._by_key = {}                 # data_ptr of the interior -> block

@@ -29,6 +29,12 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _gate_agnostic(pl):
+    """tests/far_memory.py, pitch cases: the strides decide the owner, so a body's assertion about the layout its family's kernel owns does
+    not apply (the result is checked against the same reference whoever runs it).  False on every other plan."""
+    return getattr(pl, 'gate_agnostic', False)
+
+
 def _view_planar(t, c0=0):
     Ct, h, w = t.shape
     return L.View(t.data_ptr() + c0 * h * w * 4, 1, w, h * w, 0, 1, 0)
@@ -145,7 +151,7 @@ def _fused_resblock(plan_cls, case, rec=None):
     # the same block writing to y1 through the fused kernel
     pl.conv(seg, 'conv2f', [pl.fsrc(t, 0)], [_Dst(pl.fview(y1), range(64), L.ACT_NONE, res=pl.fview(x))], H, W, batch=B, weight=w2, bias=b2)
     pl._upload()
-    assert pl.lib.demfi_resblock_eligible(C.byref(pl._descs[0]), C.byref(pl._descs[2])) == 1
+    assert pl.lib.demfi_resblock_eligible(C.byref(pl._descs[0]), C.byref(pl._descs[2])) == 1 or _gate_agnostic(pl)
     assert pl.lib.demfi_resblock_eligible(C.byref(pl._descs[1]), C.byref(pl._descs[2])) == 0      # not a block: no ReLU / wrong chaining
     _launch(pl, rec, 'resblock', (0, 2), [y1], _stream())
     torch.cuda.synchronize()
@@ -196,7 +202,7 @@ def _rdb_growth_conv(plan_cls, H, W, q, rec=None):
     srcs = [pl.fsrc(cat, 0, c0=192, nch=96)] + ([pl.fsrc(grow, 96, c0=0, nch=32 * q)] if q else [])
     pl.conv([], 'rdb', srcs, [_Dst(pl.fview(grow, 32 * q), range(32), L.ACT_RELU)], H, W, weight=wt, bias=bs)
     d = pl._descs[0]
-    assert d.rec_bytes == 64 and d.cout_perm == 1 and d.n_chunks == 3 + q      # the shape the streamed-weight kernel owns
+    assert (d.rec_bytes == 64 and d.cout_perm == 1 and d.n_chunks == 3 + q) or _gate_agnostic(pl)      # the shape the streamed-weight kernel owns
     pl._upload()
     _prefill(pl, grow[..., 32 * q:32 * q + 32])                 # a guarded plan: poison in the channel range the launch writes, and only there
     _launch(pl, rec, 'conv', (0,), [(grow, 32 * q, 32 * q + 32)], _stream())
@@ -424,7 +430,7 @@ def _streamed_weight_conv_7x7(plan_cls, H, W, batch, act, rec=None):
     bs = torch.randn(64) * 0.1
     pl.conv([], 'Ch_Reducer', [pl.fsrc(b, 0, 0, 64), pl.fsrc(b, 64, 64, 64), pl.fsrc(b, 128, 128, 64)],
             [_Dst(pl.fview(out), range(64), act)], H, W, batch=batch, weight=wt, bias=bs)
-    assert pl._descs[0].cout_perm == 1, 'the layer must be packed for the streamed-weight kernel'
+    assert pl._descs[0].cout_perm == 1 or _gate_agnostic(pl), 'the layer must be packed for the streamed-weight kernel'
     pl._upload()
     for rep in range(2):
         _prefill(pl, out, 7.0)
@@ -488,7 +494,7 @@ def _stride2_4x4_conv(plan_cls, case, H, W, batch, rec=None):
     pl.conv([], 'enc', srcs, [_Dst(pl.fview(out), range(cout), act, res=pl.fview(res) if with_res else None)], H, W, stride=2, batch=batch,
             weight=wt, bias=bs)
     d = pl._descs[0]
-    assert d.rec_bytes == 64 and d.nco == 2 and d.cout_perm == 1 and d.n_chunks == sum((t + 31) // 32 for _, t in pieces)      # the shape wsconv.hip owns
+    assert (d.rec_bytes == 64 and d.nco == 2 and d.cout_perm == 1 and d.n_chunks == sum((t + 31) // 32 for _, t in pieces)) or _gate_agnostic(pl)      # the shape wsconv.hip owns
     pl._upload()
     for rep in range(2):
         _prefill(pl, out, 7.0)
@@ -554,7 +560,7 @@ def _conv3x3_over_units(plan_cls, case, H, W, batch, rec=None):
     bs = torch.randn(cout) * 0.1
     pl.conv([], 'dec', srcs, [_Dst(pl.fview(out), range(cout), act, res=pl.fview(res) if with_res else None)], H, W, batch=batch, weight=wt, bias=bs)
     d = pl._descs[0]
-    assert d.rec_bytes == 64 and d.nco == 2 and d.cout_perm == 1 and d.n_chunks == cin // 32
+    assert (d.rec_bytes == 64 and d.nco == 2 and d.cout_perm == 1 and d.n_chunks == cin // 32) or _gate_agnostic(pl)
     pl._upload()
     for rep in range(2):
         _prefill(pl, out, 7.0)
@@ -602,7 +608,7 @@ def _conv3x3_two_piece_tail(plan_cls, H, W, batch, rec=None):
     pl.conv([], 'Dec_first_2#t', [pl.fsrc(h, 0), pl.fsrc_map(r16, m16, b=None), pl.fsrc_map(a8, list(range(75, 83)), b=None)],
             [_Dst(pl.fview(out), range(64), L.ACT_RELU, res=res)], H, W, batch=batch, weight=wt, bias=bs)
     d = pl._descs[0]
-    assert d.rec_bytes == 64 and d.nco == 2 and d.cout_perm == 1 and d.n_chunks == 3 and d.chunks[2].n_pieces == 3
+    assert (d.rec_bytes == 64 and d.nco == 2 and d.cout_perm == 1 and d.n_chunks == 3 and d.chunks[2].n_pieces == 3) or _gate_agnostic(pl)
     pl._upload()
     for rep in range(2):
         _prefill(pl, out, 7.0)
@@ -818,8 +824,8 @@ def _gru_half_step(plan_cls, kh, kw, H, W, batch, rec=None):
     pl.conv(seg, 'q', [pl.fsrc(rh2, 0), pl.fsrc(xx, 64)],
             [_Dst(pl.fview(hn2), range(64), mode=L.MODE_GRU, res=pl.fview(h), aux=pl.fview(zb))], H, W, batch=batch, weight=wq, bias=bq)
     pl._upload()
-    assert pl.lib.demfi_gru_r_eligible(C.byref(pl._descs[0])) == 1
-    assert pl.lib.demfi_gru_zq_eligible(C.byref(pl._descs[1]), C.byref(pl._descs[2])) == 1
+    assert pl.lib.demfi_gru_r_eligible(C.byref(pl._descs[0])) == 1 or _gate_agnostic(pl)
+    assert pl.lib.demfi_gru_zq_eligible(C.byref(pl._descs[1]), C.byref(pl._descs[2])) == 1 or _gate_agnostic(pl)
     assert pl.lib.demfi_gru_zq_eligible(C.byref(pl._descs[0]), C.byref(pl._descs[2])) == 0          # r is not an update gate
     assert pl.lib.demfi_gru_r_eligible(C.byref(pl._descs[1])) == 0
     for rep in range(2):                                   # twice: the launches leave no state behind

@@ -320,7 +320,7 @@ class _WarpSet:
         occ = self.al.flat(self.nb, (H, W), torch.float32, name='occ')
         bt = L.Batch()
         bt.nb, bt._pad = self.nb, outer
-        bt.a = bt.b = self.ab_stride
+        bt.a, bt.b = self.ab_stride, (GA.bstride(self.B) if self.ab_stride else 0)      # each its own: tests/far_memory.py moves one of them apart
         bt.o = GA.bstride(out)
         bt.t = GA.bstride(self.t)
         bt.p[0], bt.p[1] = GA.bstride(self.dfa), GA.bstride(self.dfb)
