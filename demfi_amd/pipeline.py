@@ -22,6 +22,7 @@ from . import cadence as K
 from . import deint as I
 from . import interlace as IL
 from . import retime as R
+from . import scale as SC
 from . import scene as S
 from . import shutter as SH
 from .y4m_edge import TileGrid, Y4mEdge, consecutive, fill_sink_records, max_runs    # noqa: F401  (fill_sink_records: for the runner)
@@ -44,37 +45,43 @@ class EdgeSpec(_EdgeFields):
     ``full``: the full-length timeline; ``depth``: bits per sample; ``layout``: one of ``y4m.LAYOUTS``; ``dedup``: None or (hi, lo, frac, max_hold);
     ``fields``: None or the field order 't' / 'b' of an interlaced input; ``deint_mode``: one of ``deint.MODES``; ``shutter``: None or (S, D) of a
     synthesized shutter (``demfi_amd.shutter``); ``interlace``: None or (field order 't' / 'b', low-pass mode) of interlaced output
-    (``demfi_amd.interlace``).  Hashable: (batch, spec) is what a cached ``ClipPipeline`` can be reused for.
-    ``shutter`` and ``interlace`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec without
-    them is, item for item, the record it was before there were any, and one with either equals no plain tuple.  What the namedtuple makes from
-    its items alone does not know them: ``_make``, ``_asdict`` and pickling drop both; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
+    (``demfi_amd.interlace``); ``scale``: None or (w, h, filter) of resized output (``demfi_amd.scale``).  Hashable: (batch, spec) is what a
+    cached ``ClipPipeline`` can be reused for.
+    ``shutter``, ``interlace`` and ``scale`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
+    without them is, item for item, the record it was before there were any, and one with any of them equals no plain tuple.  What the namedtuple makes
+    from its items alone does not know them: ``_make``, ``_asdict`` and pickling drop them; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
     shutter = None
     interlace = None
+    scale = None
 
-    def __new__(cls, *args, shutter=None, interlace=None, **kw):
+    def __new__(cls, *args, shutter=None, interlace=None, scale=None, **kw):
         self = super().__new__(cls, *args, **kw)
         if shutter is not None:
             self.shutter = (int(shutter[0]), int(shutter[1]))
         if interlace is not None:
             self.interlace = tuple(interlace)
+        if scale is not None:
+            self.scale = (int(scale[0]), int(scale[1]), scale[2])
         return self
 
     def _replace(self, **kw):
-        shutter, interlace = kw.pop('shutter', self.shutter), kw.pop('interlace', self.interlace)
-        return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace)
+        shutter, interlace, scale = kw.pop('shutter', self.shutter), kw.pop('interlace', self.interlace), kw.pop('scale', self.scale)
+        return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace, scale=scale)
 
     def __eq__(self, other):
         return (tuple.__eq__(self, other) is True and self.shutter == getattr(other, 'shutter', None)
-                and self.interlace == getattr(other, 'interlace', None))
+                and self.interlace == getattr(other, 'interlace', None) and self.scale == getattr(other, 'scale', None))
 
     def __ne__(self, other):
         return not self == other
 
     def __hash__(self):
-        return hash((tuple(self), self.shutter) if self.interlace is None else (tuple(self), self.shutter, self.interlace))
+        key = (tuple(self), self.shutter) if self.interlace is None else (tuple(self), self.shutter, self.interlace)
+        return hash(key if self.scale is None else key + ('scale', self.scale))
 
     def __repr__(self):
-        return super().__repr__()[:-1] + ', shutter=%r%s)' % (self.shutter, ', interlace=%r' % (self.interlace,) if self.interlace is not None else '')
+        return super().__repr__()[:-1] + ', shutter=%r%s%s)' % (self.shutter, ', interlace=%r' % (self.interlace,) if self.interlace is not None else '',
+                                                               ', scale=%r' % (self.scale,) if self.scale is not None else '')
 
     @classmethod
     def of(cls, yuv):
@@ -83,7 +90,7 @@ class EdgeSpec(_EdgeFields):
         return cls(yuv is not None, getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False)), int(getattr(yuv, 'depth', 8)),
                    getattr(yuv, 'layout', '420'), tuple(dedup) if dedup is not None else None, fields,
                    getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob', shutter=getattr(yuv, 'shutter', None),
-                   interlace=getattr(yuv, 'interlace', None))
+                   interlace=getattr(yuv, 'interlace', None), scale=getattr(yuv, 'scale', None))
 
     hi = property(lambda self: self.depth > 8, doc='16-bit frames: the samples of a stream above 8 bits')
 
@@ -91,7 +98,7 @@ class EdgeSpec(_EdgeFields):
         """Every rule about what goes together, before anything is allocated, for a run on a ``retimed`` runner (built with a ratio)."""
         other, edge_only = self.deint_mode != 'bob', self.hi or self.dedup is not None or self.fields is not None
         deint = deint_conflict(self.deint_mode, self.fields is not None, self.dedup is not None)
-        sh, il = self.shutter, self.interlace
+        sh, il, sc = self.shutter, self.interlace, self.scale
         for bad, what in ((self.fields not in (None, 't', 'b'), "fields must be None, 't' or 'b', got %r" % (self.fields,)),
                           (deint, 'deint_mode %r with fields=%r, dedup=%r' % (self.deint_mode, self.fields, self.dedup)),
                           (edge_only and not self.y4m, '16-bit frames, repeated frames and fields are those of the Y4M edge (yuv=...) only'),
@@ -109,7 +116,10 @@ class EdgeSpec(_EdgeFields):
                            'a shutter does not go with repeated frames (dedup): its groups are laid over the regular fine timeline'),
                           (il is not None and not (len(il) == 2 and il[0] in ('t', 'b') and il[1] in IL.LOWPASS),
                            "interlace must be None or (field order 't' / 'b', low-pass mode of %s), got %r" % (IL.LOWPASS, il)),
-                          (il is not None and not (retimed and self.y4m), 'interlaced output needs the Y4M edge on a retimed runner')):
+                          (il is not None and not (retimed and self.y4m), 'interlaced output needs the Y4M edge on a retimed runner'),
+                          (sc is not None and not (len(sc) == 3 and sc[0] >= 1 and sc[1] >= 1 and sc[2] in SC.FILTERS),
+                           'scale must be None or (w, h, filter of %s), got %r' % (SC.FILTERS, sc)),
+                          (sc is not None and not (retimed and self.y4m), 'resized output needs the Y4M edge on a retimed runner')):
             if bad:
                 raise ValueError('WindowRunner.run_clip_u8: ' + what)
 

@@ -171,6 +171,7 @@ class WindowRunner:
         self.cut_windows = 0                         # windows run as scene-cut windows (two runs, no interpolation)
         self.shutter_mixed = self.shutter_carried = 0    # a shutter's fine frames mixed / samples carried between batches (``y4m_edge.Shutter``)
         self.interlace_woven = self.interlace_carried = 0    # interlaced output: payloads woven / frames carried between batches (``y4m_edge.Interlacer``)
+        self.scale_payloads = 0                      # resized output: payloads resampled (``y4m_edge.Scaler``)
         self.last_cuts = []                          # frames that start a scene, as the last run_clip_u8 with scene cuts found them
 
     # ---------------------------------------------------------------------------------------------------------

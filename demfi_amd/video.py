@@ -118,6 +118,22 @@ to that grid, an explicit misaligned rectangle is the usual error).  One rank.  
 interlaced 4:2:0 fields, fusing the weave into the gather so that unused rows are never converted, ``Im`` output, several ranks,
 ``demfi_amd.clip``, numeric equality with ffmpeg's ``interlace`` / ``tinterlace`` filters.  Without the switch no buffer, launch or stream
 is added and every byte stays the same.
+
+``--scale WxH`` (width first, as ffmpeg's ``-s``) with ``--scale-filter lanczos3|bicubic|bilinear`` (default ``lanczos3``) resizes the
+output on the GPU (``demfi_amd.scale``), the other half of a standards conversion: 576i50 -> 480i59.94 is ``--deinterlace --fps 60000/1001
+--scale 720x480 --interlace tff``.  Every progressive payload a run without the switch writes (with ``--shutter``: its mixed frames) is
+resampled plane by plane with a separable polyphase filter in exact integers (Q14 weights that sum to one, six fractional bits between the
+passes): behind the gather and the mix, in front of the weave, so the scaler never sees woven fields.  ONE launch per batch
+(csrc/scale.hip ``demfi_payload_scale``, defined by ``scale.scale_payload_np``; the weights come from the tables of ``scale.axis_table``
+alone) writes the buffer that crosses D2H or that the weave reads; only resized payloads leave the device.  The header gets W, H and
+the pixel aspect that keeps the display aspect (720x576 ``A16:15`` -> 720x480 ``A8:9``).  The stage keeps nothing from one payload to the
+next, so it works with every switch above and with several ranks (as far as the other switches do).  With ``--crop`` only under
+``--crop-output cropped``: the picture rectangle is what is scaled (``pad`` is refused); with ``--interlace`` H lies on the interlaced
+grid (rows in units of 2, of 4 for 4:2:0).  A shrink is limited to 32 taps an axis (16:3 with lanczos3, 8:1 bicubic, 16:1 bilinear).  A
+size equal to the run's own builds no stage and gives the bytes of a run without the switch.  Not offered: scaling in front of the
+network (cheaper for a shrink), chroma siting offsets (chroma planes are resampled centre-aligned, as planes in their own right),
+``-1`` / keep-aspect sizes, linear-light resampling, ``demfi_amd.clip``, numeric equality with swscale or zimg.  Without the switch no
+buffer, launch or stream is added and every byte stays the same.
 """
 import os
 import sys
@@ -132,6 +148,7 @@ from . import dist as D
 from . import interlace as IL
 from . import letterbox as LB
 from . import retime as R
+from . import scale as SC
 from . import scene as S
 from . import shutter as SH
 from . import telecine as TC
@@ -151,11 +168,16 @@ class YuvEdge:
     fields are the stream's frames (``demfi_amd.deint``), rebuilt by ``deint_mode`` 'bob' or 'adaptive'.  ``shutter``: None, or (S, D) of a
     synthesized shutter (``demfi_amd.shutter``): the runner then has the fine ratio r D and the payloads handed out are the mixed ones.
     ``interlace``: None, or the field order ('tff' / 'bff' / 't' / 'b') of interlaced output (``demfi_amd.interlace``) with the low-pass mode
-    ``interlace_lowpass`` (None: 'linear'; an error without ``interlace``): the payloads handed out are the woven pairs."""
+    ``interlace_lowpass`` (None: 'linear'; an error without ``interlace``): the payloads handed out are the woven pairs.  ``scale``: None, or
+    (w, h) or (w, h, filter) of resized output (``demfi_amd.scale``; ``scale_filter`` names the filter of a pair, None: 'lanczos3'): the
+    payloads handed out have that size."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
-                 fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None):
+                 fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None):
         self.dedup, self.shutter = dedup, shutter
+        if scale is not None and len(scale) == 3 and scale_filter is None:
+            scale, scale_filter = tuple(scale[:2]), scale[2]
+        self.scale = check_scale(scale, scale_filter)
         self.interlace = check_interlace(interlace, interlace_lowpass)
         self.fields, self.deint_mode = fields, deint_mode
         self.depth = y4m.check_depth(depth)
@@ -213,6 +235,21 @@ def check_interlace(interlace, lowpass=None, world=1):
     il = (IL.parse_order(interlace), IL.check_lowpass(lowpass))
     check_interlace_ranks(il, world)
     return il
+
+
+def check_scale(scale, scale_filter=None, crop=None, crop_output='pad'):
+    """The scale switches checked: None, or (w, h, filter).  ``scale`` is (w, h) or a 'WxH' string, width first; ``scale_filter`` (None:
+    'lanczos3') says how ``scale`` works, so it is an error without it.  With ``crop`` the picture rectangle is what gets scaled, so
+    the output must be the cropped one."""
+    if scale is None:
+        if scale_filter is not None:
+            raise ValueError('--scale-filter (scale_filter) says how --scale works: give --scale WxH with it')
+        return None
+    w, h = SC.parse_size(scale) if isinstance(scale, str) else SC.check_size(scale)
+    if crop is not None and crop_output != 'cropped':
+        raise ValueError('--scale with --crop needs --crop-output cropped (crop_output=\'cropped\'): the picture rectangle is what is scaled, '
+                         'and with pad the bars would have to go back around a picture of another size')
+    return w, h, SC.check_filter(scale_filter)
 
 
 def check_interlace_ranks(interlace, world):
@@ -307,15 +344,25 @@ class VideoRunner:
     without ``interlace`` it is an error.  ONE launch per batch weaves (csrc/interlace.hip ``demfi_payload_weave``), the one open frame is
     carried on the device and only woven payloads cross D2H.  A ``crop`` rectangle must then keep field parity: rows in units of 2 (4 for
     4:2:0).  One rank (``run_file`` refuses more).  After a run ``last_interlace`` = 't', 'b' or None and ``last_interlace_carried`` = the
-    frames carried from one batch to the next.  Without it no buffer, launch or stream is added and every byte stays the same."""
+    frames carried from one batch to the next.  Without it no buffer, launch or stream is added and every byte stays the same.  ``scale``:
+    None (default), (w, h) or a 'WxH' string, width first: resized output (``demfi_amd.scale``).  Every progressive payload the run would
+    write is resampled to w x h on the GPU, behind the gather and the shutter's mix and in front of the weave, by ONE launch per batch
+    (csrc/scale.hip ``demfi_payload_scale``); the header gets the size and the pixel aspect that keeps the display aspect.
+    ``scale_filter``: None (the default, 'lanczos3'), 'lanczos3', 'bicubic' or 'bilinear'; given without ``scale`` it is an error.  With
+    ``crop`` only under ``crop_output='cropped'`` (refused here); with ``interlace`` h must be a multiple of 2 (4 for 4:2:0), and a shrink
+    takes at most 32 taps an axis (both refused once the header is known, before anything is allocated).  A size equal to the run's own
+    builds no stage.  Any number of ranks.  After a run ``last_scale`` = (w, h, filter), or None when nothing was resized, and
+    ``last_scale_payloads`` = the payloads resampled.  Without it no buffer, launch or stream is added and every byte stays the same."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
                  tile_high_depth=False, deinterlace=False, deinterlace_mode='bob', ivtc=False, ivtc_cthresh=TC.DEFAULT_CTHRESH,
                  ivtc_combpel=TC.DEFAULT_COMBPEL, ivtc_combed=TC.DEFAULT_COMBED, crop=None, crop_limit=LB.DEFAULT_LIMIT,
                  crop_noise=LB.DEFAULT_NOISE, crop_probe=LB.DEFAULT_PROBE, crop_output='pad', shutter=None,
-                 shutter_samples=None, interlace=None, interlace_lowpass=None, **runner_kw):
+                 shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.scale = check_scale(scale, scale_filter, crop, crop_output)  # (w, h, filter) or None
+        self.last_scale, self.last_scale_payloads = None, 0
         self.interlace = check_interlace(interlace, interlace_lowpass)    # (order, low-pass mode) or None
         self.last_interlace, self.last_interlace_carried = None, 0
         self.shutter = check_shutter(shutter, shutter_samples, dedup)     # (S, D) or None
@@ -374,8 +421,27 @@ class VideoRunner:
         """The ratio r = F_out / F_in of this input: M for x M, whose per-window plans (``retime``) give exactly the x M stream."""
         return Fraction(self.mfi) if self.mfi is not None else R.ratio(hdr.fps, self.fps)
 
+    def _scale_of(self, hdr):
+        """What the scale stage does to a run on frames of ``hdr``: None (no switch, or the run's own size: no stage), or (w, h, filter).
+        Before anything is allocated: with interlaced output h lies on the interlaced grid, and no plane takes more than 32 taps."""
+        if self.scale is None:
+            return None
+        w, h, filt = self.scale
+        if self.interlace is not None:
+            SC.check_interlaced_rows(h, hdr.layout)
+        if (w, h) == (hdr.w, hdr.h):
+            return None
+        for (ri, ci), (ro, co) in zip(IL.plane_shapes(hdr.h, hdr.w, hdr.layout), IL.plane_shapes(h, w, hdr.layout)):
+            for n_in, n_out in ((ci, co), (ri, ro)):
+                if SC.n_taps(n_in, n_out, filt) > SC.MAX_TAPS:
+                    SC.axis_table(n_in, n_out, filt)                     # the refusal, in its own words
+        return self.scale
+
     def _out_header(self, hdr):
         ohdr = R.output_header(hdr, hdr.fps * self._ratio(hdr))
+        sc = self._scale_of(hdr)
+        if sc is not None:                           # the size and the pixel aspect that keeps the display aspect
+            ohdr = SC.scaled_header(ohdr, sc[0], sc[1])
         if self.interlace is not None:               # the same stream as fields: the I tag of the order, half the rate
             ohdr = IL.interlaced_header(ohdr, self.interlace[0])
         self.last_fps_out = ohdr.fps
@@ -540,7 +606,7 @@ class VideoRunner:
         the per-run counters."""
         rn = cr.runner
         i0, p0, c0, m0, s0 = rn.instants_run, rn.instants_padded, rn.cut_windows, rn.shutter_mixed, rn.shutter_carried
-        w0 = rn.interlace_carried
+        w0, z0 = rn.interlace_carried, rn.scale_payloads
         with cr.oversize_hint():
             n = fn()
         lo = first()
@@ -553,6 +619,7 @@ class VideoRunner:
         self.last_shutter_carried = rn.shutter_carried - s0
         self.last_interlace = self.interlace[0] if self.interlace is not None else None
         self.last_interlace_carried = rn.interlace_carried - w0
+        self.last_scale, self.last_scale_payloads = self._scale_of(hdr), rn.scale_payloads - z0
         if self.shutter is not None:                 # the fine frames that went into the mixes
             self.last_st_frames = rn.shutter_mixed - m0
         return n
@@ -560,7 +627,7 @@ class VideoRunner:
     def _edge(self, hdr, with_s1, order=None):
         return YuvEdge(y4m.auto_matrix(self._matrix_h or hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
                        self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
-                       *(self.interlace or (None, None)))
+                       *(self.interlace or (None, None)), self._scale_of(hdr))
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
@@ -670,6 +737,7 @@ class VideoRunner:
                 self.last_instants, self.last_st_frames, self.last_cuts, self.last_cut_windows = (0, 0), 0, [], 0
                 self.last_shutter, self.last_shutter_carried = self.shutter, 0
                 self.last_interlace, self.last_interlace_carried = (self.interlace[0] if self.interlace is not None else None), 0
+                self.last_scale, self.last_scale_payloads = self._scale_of(hdr), 0
                 return 0, 0
             last = R.first_window(n_in, full) + R.n_windows(n_in, full) - 1
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
@@ -732,7 +800,7 @@ def parser():
                                         '-f yuv4mpegpipe -; with --any-layout also 4:2:2, 4:4:4 and grey (C422, C444, Cmono and, with '
                                         '--high-depth, C422pNN, C444pNN, CmonoNN), e.g. ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 '
                                         '-f yuv4mpegpipe -; with --deinterlace also interlaced streams of a fixed field order (It, Ib), every '
-                                        'field a frame at twice the rate.  Output: progressive (with --interlace: It or Ib at half the rate), C420jpeg (C420pNN at the input\'s depth; the input\'s layout and '
+                                        'field a frame at twice the rate.  Output: progressive (with --interlace: It or Ib at half the rate), the input\'s size (with --scale: WxH), C420jpeg (C420pNN at the input\'s depth; the input\'s layout and '
                                         'depth for the other layouts), the input\'s '
                                         'matrix and range.  n input frames give (n-3)*M + 1 output frames: the first and the last '
                                         'input frame have no output, as in the reference (--full-length: n*M frames from input '
@@ -842,6 +910,16 @@ def parser():
                     help='with --interlace: the vertical filter against interline twitter, within each field\'s own frame: linear '
                          '(default, (a + 2c + b + 2) >> 2 over the rows above and below), complex (a five-row filter that keeps more '
                          'detail) or off')
+    ap.add_argument('--scale', type=_value_arg(SC.parse_size), default=None, metavar='WxH',
+                    help='resize the output on the GPU to W x H: WIDTH FIRST, as ffmpeg\'s -s (--tile is rows first).  Every progressive '
+                         'frame the run would write is resampled (behind --shutter\'s mix, in front of --interlace\'s weave, so fields are '
+                         'never scaled) by one launch per batch, and the header keeps the display aspect: 720x576 A16:15 becomes 720x480 '
+                         'A8:9.  --deinterlace --fps 60000/1001 --scale 720x480 --interlace tff turns 576i50 into 480i59.94.  With --crop '
+                         'only under --crop-output cropped; with --interlace H in units of 2 (4 for 4:2:0); a shrink beyond 32 taps an '
+                         'axis (16:3 with lanczos3) is refused.  The input\'s own size changes nothing.  Off by default')
+    ap.add_argument('--scale-filter', default=None, choices=list(SC.FILTERS),
+                    help='with --scale: lanczos3 (default), bicubic (Catmull-Rom) or bilinear; each is stretched for a shrink, so it '
+                         'low-passes')
     T.add_arguments(ap)
     return ap
 
@@ -871,10 +949,12 @@ def main(argv=None):
             raise ValueError(AUTO_NEEDS_A_FILE + ' (and a regular output file)')
         check_shutter(a.shutter, a.shutter_samples, a.dedup or None)
         check_interlace(a.interlace, a.interlace_lowpass)
+        check_scale(a.scale, a.scale_filter, a.crop, crop_kw.get('crop_output', 'pad'))
     except ValueError as e:
         parser().error(str(e))
     shutter_kw = {k: v for k, v in (('shutter', a.shutter), ('shutter_samples', a.shutter_samples), ('interlace', a.interlace),
-                                    ('interlace_lowpass', a.interlace_lowpass)) if v is not None}
+                                    ('interlace_lowpass', a.interlace_lowpass), ('scale', a.scale),
+                                    ('scale_filter', a.scale_filter)) if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     if world > 1 and a.shutter is not None:
         raise SystemExit('demfi_amd.video: --shutter runs on one rank (the sub-frames of a written frame straddle the ranks\' blocks)')
@@ -935,6 +1015,9 @@ def main(argv=None):
         extra = {'shutter': {'angle': str(a.shutter), 'samples': vr.last_shutter[0], 'fine_per_written': vr.last_shutter[1]}} if a.shutter else {}
         if a.interlace is not None:
             extra['interlace'] = {'order': vr.last_interlace, 'lowpass': vr.interlace[1], 'carried': vr.last_interlace_carried}
+        if a.scale is not None:
+            extra['scale'] = {'size': '%dx%d' % vr.scale[:2], 'filter': vr.scale[2], 'resized': vr.last_scale is not None,
+                              'payloads': vr.last_scale_payloads}
         print(json.dumps({**extra, 'windows': int(tw), 'frames_written': int(tf), 'seconds': round(dt, 2), 'ranks': world,
                           'St_frames_per_s': round(tst / dt, 2) if dt > 0 else None,
                           'frames_per_s': round(tf / dt, 2) if dt > 0 else None,

@@ -1,6 +1,7 @@
 """The Y4M edge of the clip pipeline (``demfi_amd.pipeline``): Y4M payloads in and out, every window on its own plan, all options in
 one ``pipeline.EdgeSpec``.  One stage per job, each with its own buffers: ``Ingest``, ``SceneScores``, ``DedupProbe``, the pure function
-``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, ``Shutter`` and ``Interlacer``; ``Y4mEdge`` keeps their order and the payloads' way out."""
+``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, ``Shutter``, ``Scaler`` and ``Interlacer``; ``Y4mEdge`` keeps their order and the
+payloads' way out."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +12,7 @@ from . import cadence as K
 from . import deint as I
 from . import interlace as IL
 from . import retime as R
+from . import scale as SC
 from . import scene as S
 from . import shutter as SH
 from .y4m import payload_size
@@ -345,6 +347,46 @@ class Shutter:
         return counts
 
 
+class Scaler:
+    """Progressive payloads -> resized ones (``demfi_amd.scale``, ``spec.scale`` = (w, h, filter)).  The stage sits behind the gather, or behind
+    ``Shutter.mix``, and in front of ``Interlacer.weave``: after a batch's progressive payloads lie in the rows 0, 1, ... of ``src[i]``, ``scale``
+    resamples all of them with ONE ``demfi_payload_scale`` launch on the compute stream into ``scaled[i]`` from row ``front`` on (``front``: the
+    rows left free for the stage behind, the ``Interlacer``'s carry row); ``scaled[i]`` is what crosses D2H, or what the weave reads.  Stateless
+    per payload: no sample carries over from one batch to the next, so which batch a frame came with never shows, and the stage works on every
+    rank.  The tables of ``scale.table_blob`` are the only source of the weights; they are uploaded once, here.  The runner counts
+    ``scale_payloads``.  ``h_offs``: the pinned offset tables, one per buffer set, rewritten two batches later, when the host has drained the
+    batch that last copied from them (as ``Shutter.h_offs``)."""
+
+    def __init__(self, runner, spec, rows, h, w, es, dev, front=0):
+        (self.w, self.h, self.filter), self.rn, self.lib, self.es, self.front, self.rows = spec.scale, runner, runner.lib, es, front, rows
+        self.peak, self.Pb_in = (1 << spec.depth) - 1, payload_size(h, w, spec.layout) * es
+        self.Pb = payload_size(self.h, self.w, spec.layout) * es             # bytes of a resized payload
+        shapes_in, shapes_out = IL.plane_shapes(h, w, spec.layout), IL.plane_shapes(self.h, self.w, spec.layout)
+        self.planes_in, self.planes_out = (np.ascontiguousarray(a, dtype=np.int32) for a in (shapes_in, shapes_out))
+        blob, self.desc = SC.table_blob(shapes_in, shapes_out, self.filter)
+        self.tables = torch.from_numpy(blob).to(dev)
+        self.scaled = [torch.empty((front + rows, self.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.offs = [torch.empty(rows, dtype=torch.int64, device=dev) for _ in range(2)]
+        self.h_offs = [torch.empty(rows, dtype=torch.int64).pin_memory() for _ in range(2)]
+
+    def scale(self, i, counts, src, stream):
+        """counts[w]: the progressive payloads of window w, which lie in src[i] from row 0 on; they are resized into scaled[i] from row ``front`` on."""
+        m = sum(counts)
+        if m > self.rows:
+            raise RuntimeError('scale: %d payloads for %d payload rows' % (m, self.rows))
+        if m:
+            self.rn.scale_payloads += m
+            host = self.h_offs[i][:m]
+            host.numpy()[:] = np.arange(m, dtype=np.int64) * self.Pb_in
+            od = self.offs[i][:m]
+            od.copy_(host, non_blocking=True)
+            L.check(self.lib.demfi_payload_scale(src[i].data_ptr(), host.data_ptr(), od.data_ptr(), m, self.planes_in.ctypes.data,
+                                                 self.planes_out.ctypes.data, len(self.planes_in), self.es, self.peak, self.tables.data_ptr(),
+                                                 self.desc.ctypes.data, self.scaled[i][self.front:].data_ptr(), self.Pb, stream.cuda_stream),
+                    'payload_scale')
+        return counts
+
+
 class Interlacer:
     """Progressive payloads -> woven ones (``demfi_amd.interlace``, ``spec.interlace`` = (field order, low-pass mode)).  Written payload q
     weaves frames 2q (the first field in time) and 2q + 1 of the progressive stream.  The stage sits behind the gather, or behind
@@ -485,15 +527,24 @@ class Y4mEdge:
         # a shutter mixes the gathered (fine) payloads into written ones: those cross D2H, and yuv_out[i] gets its carry rows in front
         # interlaced output weaves the progressive payloads (gathered, or mixed) in pairs: the woven ones cross D2H, and the buffer it reads gets
         # its carry row in front
+        # resized output resamples the progressive payloads (gathered, or mixed) into buffers of the output size: the carry row of the weave
+        # then lies in front of those, the weave and the pinned staging buffers have the output's size, and only resized payloads cross D2H
         front = Interlacer.lead if spec.interlace is not None else 0
+        scaled = spec.scale is not None and tuple(spec.scale[:2]) != (w, h)      # the run's own size: no stage, the bytes of a run without
+        sfront, front = (front, 0) if scaled else (0, front)
         sh = self.shutter = Shutter(runner, spec, nout, batch, ing.Pb, ing.es, dev, front) if spec.shutter is not None else None
         lead, nhost = (sh.lead, sh.rows) if sh is not None else (front, nout)
+        self.gather_lead = lead
         self.yuv_out = [torch.empty((lead + nout, ing.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.written = sh.mixed if sh is not None else self.yuv_out
-        il = self.interlacer = Interlacer(runner, spec, nhost, h, w, ing.Pb, ing.es, dev) if spec.interlace is not None else None
+        sc = self.scaler = Scaler(runner, spec, nhost, h, w, ing.es, dev, sfront) if scaled else None
+        oh, ow, oPb = (sc.h, sc.w, sc.Pb) if scaled else (h, w, ing.Pb)
+        if sc is not None:
+            self.unscaled, self.written = self.written, sc.scaled
+        il = self.interlacer = Interlacer(runner, spec, nhost, oh, ow, oPb, ing.es, dev) if spec.interlace is not None else None
         if il is not None:
             self.progressive, self.written, nhost = self.written, il.woven, il.rows
-        self.h_yuv = [torch.empty((nhost, ing.Pb), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.h_yuv = [torch.empty((nhost, oPb), dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.yuv = self.window_index = self.det = self.kept = self.gather = None
 
     def __getattr__(self, name):                     # J, tiler, in_place and, on a crop-run-stitch edge only, tcomb: the frame IO's
@@ -542,15 +593,17 @@ class Y4mEdge:
         if self.kept is not None:
             self.kept.st_frames += st_frames
         self._run_windows(i, runs)
-        sh, il, read = self.shutter, self.interlacer, [fr for fr, _, _ in runs]
+        sh, sc, il, read = self.shutter, self.scaler, self.interlacer, [fr for fr, _, _ in runs]
         if il is not None:
             il.carry(i, self.progressive)
         if sh is None:
-            counts = self._gather(i, outs, cur, il.lead if il is not None else 0)
+            counts = self._gather(i, outs, cur, self.gather_lead)
         else:
             sh.carry(i, self.yuv_out)
             self._gather(i, outs, cur, sh.lead)
             counts = sh.mix(i, fine, ends, self.yuv_out, cur)
+        if sc is not None:
+            counts = sc.scale(i, counts, self.unscaled, cur)
         if il is not None:
             counts = il.weave(i, counts, ends, self.progressive, cur)
         return counts, read

@@ -527,6 +527,32 @@ int demfi_payload_mix(const uint8_t* base, const int64_t* offsets, const int64_t
 int demfi_payload_weave(const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, int n, const int32_t* planes,
                         int n_planes, int sample_bytes, int peak, int q0, int lowpass, uint8_t* dst, int64_t dst_stride, void* stream);
 
+/* ---- resized output of the Y4M edge (csrc/scale.hip; demfi_amd/video.py --scale) -------------------------------------------------------
+ * payload_scale: written payload i (n per launch) is the source payload at base + offsets[i] (int64 BYTE offsets) with every plane
+ * resampled by a separable polyphase filter.  A payload is n_planes (1..3) planes one behind the other; plane p has planes_in[2 p] rows
+ * and planes_in[2 p + 1] columns of samples in the source and planes_out[2 p] x planes_out[2 p + 1] in dst (1..32768 each; both lists
+ * are HOST memory; a payload stays below 2^31 bytes); sample_bytes = 1, or 2 for 16-bit little-endian samples (even addresses, offsets
+ * and stride).  The function computes no weights: tables_dev is one DEVICE blob (4-byte aligned) that holds, per plane and axis, first
+ * (int32 [n_out]: the source index of tap 0 of output sample o; indices clamp to the axis where they are used) and coef (int16
+ * [n_out][T], Q14, a row sums to 1 << 14), as demfi_amd/scale.py axis_table gives them (table_blob lays them out); table_desc is HOST
+ * memory, int32 [6 n_planes + 1]: per plane the byte offsets in the blob of the horizontal first and coef, the horizontal taps Tx, the
+ * byte offsets of the vertical first and coef, the vertical taps Ty; the last word is the blob's size in bytes.  In exact integers,
+ * >> an arithmetic shift:  t = (sum_j cx[xo][j] src[y][clamp(fx[xo] + j)] + 128) >> 8 (signed, unclamped), then
+ * v = clip((sum_j cy[yo][j] t[clamp(fy[yo] + j)][xo] + 2^19) >> 20, 0, peak); the numpy definition is scale_payload_np.  The payload
+ * is written at dst + i*dst_stride; the bytes between its end and dst_stride are not written.  The offsets are passed twice with the
+ * same content: offsets in HOST memory, checked here before anything is launched, and offsets_dev in DEVICE memory, read by the kernel.
+ * DEMFI_ERR_ARG, with nothing launched: a NULL buffer, n < 0, no plane or more than three, a plane size out of range, sample_bytes not
+ * 1 or 2, 16-bit samples at an odd address, offset or stride, peak outside 1..65535 (1..255 for bytes), taps outside 1..32, a table
+ * offset that is negative, misaligned (first: 4 bytes, coef: 2) or ends behind the blob, a payload of 2^31 bytes or more, dst_stride
+ * below the output payload, a negative offset.  One launch for all n payloads: a 256-thread workgroup owns 64 columns x 16 rows of one
+ * output plane (fewer rows beyond a 4:1 shrink), keeps the horizontal pass of the source rows they need in 24 KiB of LDS as int32 and
+ * reads them back with 128-bit reads for the vertical pass; both sums in int32 for bytes, the vertical one in 64 bits for 16-bit
+ * samples; 4- or 8-byte stores where the destination address allows.  No atomics; the sources may overlap each other but not dst;
+ * n == 0 does nothing. */
+int demfi_payload_scale(const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, int n, const int32_t* planes_in,
+                        const int32_t* planes_out, int n_planes, int sample_bytes, int peak, const uint8_t* tables_dev,
+                        const int32_t* table_desc, uint8_t* dst, int64_t dst_stride, void* stream);
+
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
  * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
