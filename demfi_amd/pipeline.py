@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import bitdepth as BD
 from . import cadence as K
 from . import deint as I
 from . import interlace as IL
@@ -45,16 +46,19 @@ class EdgeSpec(_EdgeFields):
     ``full``: the full-length timeline; ``depth``: bits per sample; ``layout``: one of ``y4m.LAYOUTS``; ``dedup``: None or (hi, lo, frac, max_hold);
     ``fields``: None or the field order 't' / 'b' of an interlaced input; ``deint_mode``: one of ``deint.MODES``; ``shutter``: None or (S, D) of a
     synthesized shutter (``demfi_amd.shutter``); ``interlace``: None or (field order 't' / 'b', low-pass mode) of interlaced output
-    (``demfi_amd.interlace``); ``scale``: None or (w, h, filter) of resized output (``demfi_amd.scale``).  Hashable: (batch, spec) is what a
-    cached ``ClipPipeline`` can be reused for.
-    ``shutter``, ``interlace`` and ``scale`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
+    (``demfi_amd.interlace``); ``scale``: None or (w, h, filter) of resized output (``demfi_amd.scale``); ``depths``: None or (input depth,
+    working depth, output depth, dither mode or None) of a run that changes the bit depth (``demfi_amd.bitdepth``): ``depth`` and ``hi`` then
+    mean the WORKING depth, the payloads come in at the input's and leave at the output's; three equal depths are None.  Hashable: (batch,
+    spec) is what a cached ``ClipPipeline`` can be reused for.
+    ``shutter``, ``interlace``, ``scale`` and ``depths`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
     without them is, item for item, the record it was before there were any, and one with any of them equals no plain tuple.  What the namedtuple makes
     from its items alone does not know them: ``_make``, ``_asdict`` and pickling drop them; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
     shutter = None
     interlace = None
     scale = None
+    depths = None
 
-    def __new__(cls, *args, shutter=None, interlace=None, scale=None, **kw):
+    def __new__(cls, *args, shutter=None, interlace=None, scale=None, depths=None, **kw):
         self = super().__new__(cls, *args, **kw)
         if shutter is not None:
             self.shutter = (int(shutter[0]), int(shutter[1]))
@@ -62,26 +66,32 @@ class EdgeSpec(_EdgeFields):
             self.interlace = tuple(interlace)
         if scale is not None:
             self.scale = (int(scale[0]), int(scale[1]), scale[2])
+        if not BD.is_noop(depths):
+            self.depths = (int(depths[0]), int(depths[1]), int(depths[2]), depths[3])
         return self
 
     def _replace(self, **kw):
         shutter, interlace, scale = kw.pop('shutter', self.shutter), kw.pop('interlace', self.interlace), kw.pop('scale', self.scale)
-        return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace, scale=scale)
+        depths = kw.pop('depths', self.depths)
+        return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace, scale=scale, depths=depths)
 
     def __eq__(self, other):
         return (tuple.__eq__(self, other) is True and self.shutter == getattr(other, 'shutter', None)
-                and self.interlace == getattr(other, 'interlace', None) and self.scale == getattr(other, 'scale', None))
+                and self.interlace == getattr(other, 'interlace', None) and self.scale == getattr(other, 'scale', None)
+                and self.depths == getattr(other, 'depths', None))
 
     def __ne__(self, other):
         return not self == other
 
     def __hash__(self):
         key = (tuple(self), self.shutter) if self.interlace is None else (tuple(self), self.shutter, self.interlace)
-        return hash(key if self.scale is None else key + ('scale', self.scale))
+        key = key if self.scale is None else key + ('scale', self.scale)
+        return hash(key if self.depths is None else key + ('depths', self.depths))
 
     def __repr__(self):
         return super().__repr__()[:-1] + ', shutter=%r%s%s)' % (self.shutter, ', interlace=%r' % (self.interlace,) if self.interlace is not None else '',
-                                                               ', scale=%r' % (self.scale,) if self.scale is not None else '')
+                                                               (', scale=%r' % (self.scale,) if self.scale is not None else '')
+                                                               + (', depths=%r' % (self.depths,) if self.depths is not None else ''))
 
     @classmethod
     def of(cls, yuv):
@@ -90,7 +100,7 @@ class EdgeSpec(_EdgeFields):
         return cls(yuv is not None, getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False)), int(getattr(yuv, 'depth', 8)),
                    getattr(yuv, 'layout', '420'), tuple(dedup) if dedup is not None else None, fields,
                    getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob', shutter=getattr(yuv, 'shutter', None),
-                   interlace=getattr(yuv, 'interlace', None), scale=getattr(yuv, 'scale', None))
+                   interlace=getattr(yuv, 'interlace', None), scale=getattr(yuv, 'scale', None), depths=getattr(yuv, 'depths', None))
 
     hi = property(lambda self: self.depth > 8, doc='16-bit frames: the samples of a stream above 8 bits')
 
@@ -98,7 +108,7 @@ class EdgeSpec(_EdgeFields):
         """Every rule about what goes together, before anything is allocated, for a run on a ``retimed`` runner (built with a ratio)."""
         other, edge_only = self.deint_mode != 'bob', self.hi or self.dedup is not None or self.fields is not None
         deint = deint_conflict(self.deint_mode, self.fields is not None, self.dedup is not None)
-        sh, il, sc = self.shutter, self.interlace, self.scale
+        sh, il, sc, dp = self.shutter, self.interlace, self.scale, self.depths
         for bad, what in ((self.fields not in (None, 't', 'b'), "fields must be None, 't' or 'b', got %r" % (self.fields,)),
                           (deint, 'deint_mode %r with fields=%r, dedup=%r' % (self.deint_mode, self.fields, self.dedup)),
                           (edge_only and not self.y4m, '16-bit frames, repeated frames and fields are those of the Y4M edge (yuv=...) only'),
@@ -119,7 +129,12 @@ class EdgeSpec(_EdgeFields):
                           (il is not None and not (retimed and self.y4m), 'interlaced output needs the Y4M edge on a retimed runner'),
                           (sc is not None and not (len(sc) == 3 and sc[0] >= 1 and sc[1] >= 1 and sc[2] in SC.FILTERS),
                            'scale must be None or (w, h, filter of %s), got %r' % (SC.FILTERS, sc)),
-                          (sc is not None and not (retimed and self.y4m), 'resized output needs the Y4M edge on a retimed runner')):
+                          (sc is not None and not (retimed and self.y4m), 'resized output needs the Y4M edge on a retimed runner'),
+                          (dp is not None and not (dp[0] <= dp[1] >= dp[2] and dp[1] == self.depth and all(d in (8, 10, 12, 14, 16) for d in dp[:3])
+                                                   and (dp[3] in BD.DITHERS if dp[2] < dp[1] else dp[3] is None)),
+                           'depths must be None or (input, working, output depth, dither mode of %s where the output is below the working '
+                           'depth, else None) with input <= working == depth >= output, got %r at depth %r' % (BD.DITHERS, dp, self.depth)),
+                          (dp is not None and not (retimed and self.y4m), 'a change of bit depth needs the Y4M edge on a retimed runner')):
             if bad:
                 raise ValueError('WindowRunner.run_clip_u8: ' + what)
 
@@ -365,7 +380,7 @@ class ClipPipeline:
     def run(self, host_frames, windows, sink, reuse_frames, yuv, window_index):
         edge, slots, h2d, cur = self.edge, self.slots, self.h2d, torch.cuda.current_stream(self.dev)
         slots.reset()
-        edge.attach(host_frames)
+        edge.attach(host_frames, yuv)
         it = iter(windows)
         wins = list(itertools.islice(it, self.batch))
         if not wins:

@@ -172,6 +172,7 @@ class WindowRunner:
         self.shutter_mixed = self.shutter_carried = 0    # a shutter's fine frames mixed / samples carried between batches (``y4m_edge.Shutter``)
         self.interlace_woven = self.interlace_carried = 0    # interlaced output: payloads woven / frames carried between batches (``y4m_edge.Interlacer``)
         self.scale_payloads = 0                      # resized output: payloads resampled (``y4m_edge.Scaler``)
+        self.depth_promoted = self.depth_requantised = 0     # bit depth: payloads promoted at ingest / requantised at egress (``demfi_amd.bitdepth``)
         self.last_cuts = []                          # frames that start a scene, as the last run_clip_u8 with scene cuts found them
 
     # ---------------------------------------------------------------------------------------------------------
@@ -630,6 +631,10 @@ class WindowRunner:
         those frames.  ``yuv.deint_mode`` = 'adaptive' ('bob' when absent): every field is rebuilt by the motion-adaptive rule instead
         (``demfi_yuv_deint_adaptive``), which reads fields f-2 .. f+2: host_frames must then also hold the two fields before the first
         one named and answer ``has(f)`` for the fields after the last (``y4m.Frames(behind=2)``); not together with ``yuv.dedup``.
+        ``yuv.depths`` = (input depth, working depth, output depth, dither mode or None) (None when absent; ``demfi_amd.bitdepth``):
+        ``yuv.depth`` is the working depth, host_frames[i] holds samples of the input's depth, which are promoted on the GPU behind
+        their upload (``demfi_payload_promote``), and the payloads the sink gets have the output's depth, requantised on the GPU as the
+        last stage (``demfi_payload_requant``).
         Returns the number of windows run."""
         spec = EdgeSpec.of(yuv)
         spec.check(self.retime is not None, window_index is not None, reuse_frames)

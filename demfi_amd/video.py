@@ -134,6 +134,26 @@ size equal to the run's own builds no stage and gives the bytes of a run without
 network (cheaper for a shrink), chroma siting offsets (chroma planes are resampled centre-aligned, as planes in their own right),
 ``-1`` / keep-aspect sizes, linear-light resampling, ``demfi_amd.clip``, numeric equality with swscale or zimg.  Without the switch no
 buffer, launch or stream is added and every byte stays the same.
+
+``--work-depth W`` and ``--out-depth D`` (8, 10, 12, 14 or 16 each) with ``--dither bayer|none`` (default ``bayer``) choose the stream's bit
+depth (``demfi_amd.bitdepth``).  work = W if given, else max(input depth, D); out = D if given, else the INPUT's depth: ``--out-depth 10``
+turns an 8-bit stream into ``C420p10`` for a Main10 encoder, ``--work-depth 12`` alone is 8 -> 12 -> 8, dithered.  With a working depth above
+the input's every payload is uploaded at the input's sample size and promoted on the GPU right behind its copy (csrc/bitdepth.hip
+``demfi_payload_promote``, one launch per run of uploaded slots), so everything downstream -- the deinterlacer, scene scores, the repeated-frame
+probe, the 16-bit frame path, the network's egress, the shutter's mix, the scaler, the weave -- sees and rounds a W-bit stream.  With an
+output depth below the working depth every written payload is requantised as the last device stage, gather -> mix -> scale -> weave ->
+requant -> D2H (``demfi_payload_requant``, one launch per batch), so only D-bit payloads leave the device: 16 -> 8 sends half the bytes.  One
+integer rule, out = clip(off_out + floor(((v - off_in) num + T) / den), 0, peak_out) (``bitdepth.convert_payload_np``): limited range is a
+pure shift in every plane, full range scales by peak_out / peak_in around 0 (luma) and 2^(d-1) (chroma); T = den / 2 going up and with
+``none``, with ``bayer`` going down the threshold of the 8x8 ordered-dither index of the sample's position in its plane, the same in every
+frame, and with ``--interlace`` taken from the row within its field.  An input above 8 bits still needs ``--high-depth``, which says what is
+taken; an 8-bit input with a deeper working depth runs on the 16-bit frame path without it; with ``--tile`` a working depth above 8 needs
+``--tile-high-depth``.  ``--dtype fp16`` resolves 10 bits fully and about 12 at best, so W >= 12 wants ``--dtype fp32``; it is not refused.
+``--ivtc`` and ``--crop auto`` decide in front of the device stages on the input's own samples, at the input's depth.  Both stages keep
+nothing between payloads: every switch above and several ranks work.  Refused: W below the input's depth, D above W, ``--dither`` where
+nothing is requantised.  Depths that resolve to the input's build no stage, no buffer and no launch and give the bytes of a run without the
+switches.  Not offered: error diffusion, random or blue-noise dither, patterns that change from frame to frame, ``demfi_amd.clip``, changing
+the range or the matrix on the way.
 """
 import os
 import sys
@@ -142,6 +162,7 @@ from fractions import Fraction
 import torch
 
 from . import _lib as L
+from . import bitdepth as BD
 from . import cadence as K
 from . import deint as I
 from . import dist as D
@@ -170,11 +191,17 @@ class YuvEdge:
     ``interlace``: None, or the field order ('tff' / 'bff' / 't' / 'b') of interlaced output (``demfi_amd.interlace``) with the low-pass mode
     ``interlace_lowpass`` (None: 'linear'; an error without ``interlace``): the payloads handed out are the woven pairs.  ``scale``: None, or
     (w, h) or (w, h, filter) of resized output (``demfi_amd.scale``; ``scale_filter`` names the filter of a pair, None: 'lanczos3'): the
-    payloads handed out have that size."""
+    payloads handed out have that size.  ``depths``: None, or (input depth, working depth, output depth, dither mode or None) of
+    ``bitdepth.resolve``: the payloads handed in have the input's depth, ``depth`` is then the WORKING depth, and the payloads handed out
+    have the output's."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
-                 fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None):
+                 fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None,
+                 depths=None):
         self.dedup, self.shutter = dedup, shutter
+        self.depths = None if BD.is_noop(depths) else tuple(depths)
+        if self.depths is not None and self.depths[1] != depth:
+            raise ValueError('YuvEdge: depths=%r with depth=%r: depth is the working depth' % (self.depths, depth))
         if scale is not None and len(scale) == 3 and scale_filter is None:
             scale, scale_filter = tuple(scale[:2]), scale[2]
         self.scale = check_scale(scale, scale_filter)
@@ -250,6 +277,14 @@ def check_scale(scale, scale_filter=None, crop=None, crop_output='pad'):
         raise ValueError('--scale with --crop needs --crop-output cropped (crop_output=\'cropped\'): the picture rectangle is what is scaled, '
                          'and with pad the bars would have to go back around a picture of another size')
     return w, h, SC.check_filter(scale_filter)
+
+
+def check_depths(work_depth=None, out_depth=None, dither=None):
+    """The bit-depth switches checked as far as they can be before a header is known (``bitdepth.check_switches``): depths of
+    ``y4m.DEPTHS``, D <= W, and ``dither`` ('bayer' / 'none'; None: 'bayer') says how a requantisation rounds, so it is an error without
+    either depth.  What depends on the input's depth (W below it, a ``dither`` where the output ends at the working depth) is refused by
+    ``bitdepth.resolve`` once the header is known, before anything is allocated.  Returns (work_depth, out_depth, dither)."""
+    return BD.check_switches(work_depth, out_depth, dither)
 
 
 def check_interlace_ranks(interlace, world):
@@ -352,15 +387,27 @@ class VideoRunner:
     ``crop`` only under ``crop_output='cropped'`` (refused here); with ``interlace`` h must be a multiple of 2 (4 for 4:2:0), and a shrink
     takes at most 32 taps an axis (both refused once the header is known, before anything is allocated).  A size equal to the run's own
     builds no stage.  Any number of ranks.  After a run ``last_scale`` = (w, h, filter), or None when nothing was resized, and
-    ``last_scale_payloads`` = the payloads resampled.  Without it no buffer, launch or stream is added and every byte stays the same."""
+    ``last_scale_payloads`` = the payloads resampled.  Without it no buffer, launch or stream is added and every byte stays the same.
+    ``work_depth``, ``out_depth``: None (default) or a depth of ``y4m.DEPTHS`` (``demfi_amd.bitdepth``): the depth every stage computes at
+    (payloads are promoted on the GPU right behind their upload; default max(input depth, ``out_depth``)) and the depth written (requantised
+    on the GPU as the last device stage; default the INPUT's depth, so ``work_depth=12`` alone is 8 -> 12 -> 8).  ``dither``: None (the
+    default, 'bayer'), 'bayer' or 'none', how a requantisation rounds; given without either depth it is an error here, and where the output
+    ends at the working depth once the header is known, like a ``work_depth`` below the input's depth; ``out_depth`` above ``work_depth`` is
+    refused here.  An input above 8 bits still needs ``high_depth``; with ``tile`` a working depth above 8 needs ``tile_high_depth``.  Any
+    number of ranks.  After a run ``last_depth`` = the depth written, ``last_depths`` = (input, working, output depth, dither mode or None),
+    or None when nothing changed, ``last_depth_promoted`` / ``last_depth_requantised`` = the payloads that went through the two stages.
+    Depths that resolve to the input's add no buffer, launch or stream and every byte stays the same."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
                  tile_high_depth=False, deinterlace=False, deinterlace_mode='bob', ivtc=False, ivtc_cthresh=TC.DEFAULT_CTHRESH,
                  ivtc_combpel=TC.DEFAULT_COMBPEL, ivtc_combed=TC.DEFAULT_COMBED, crop=None, crop_limit=LB.DEFAULT_LIMIT,
                  crop_noise=LB.DEFAULT_NOISE, crop_probe=LB.DEFAULT_PROBE, crop_output='pad', shutter=None,
-                 shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, **runner_kw):
+                 shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, work_depth=None,
+                 out_depth=None, dither=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.work_depth, self.out_depth, self.dither = check_depths(work_depth, out_depth, dither)
+        self.last_depths, self.last_depth_promoted, self.last_depth_requantised = None, 0, 0
         self.scale = check_scale(scale, scale_filter, crop, crop_output)  # (w, h, filter) or None
         self.last_scale, self.last_scale_payloads = None, 0
         self.interlace = check_interlace(interlace, interlace_lowpass)    # (order, low-pass mode) or None
@@ -437,8 +484,13 @@ class VideoRunner:
                     SC.axis_table(n_in, n_out, filt)                     # the refusal, in its own words
         return self.scale
 
+    def _depths_of(self, hdr):
+        """(input, working, output depth, dither mode or None) of a run on the stream of ``hdr`` (``bitdepth.resolve``, with its refusals),
+        before anything is allocated; without the switches three times the input's depth."""
+        return BD.resolve(hdr.depth, self.work_depth, self.out_depth, self.dither)
+
     def _out_header(self, hdr):
-        ohdr = R.output_header(hdr, hdr.fps * self._ratio(hdr))
+        ohdr = BD.depth_header(R.output_header(hdr, hdr.fps * self._ratio(hdr)), self._depths_of(hdr)[2])
         sc = self._scale_of(hdr)
         if sc is not None:                           # the size and the pixel aspect that keeps the display aspect
             ohdr = SC.scaled_header(ohdr, sc[0], sc[1])
@@ -565,6 +617,9 @@ class VideoRunner:
         if cropper is None or self.crop_output == 'cropped':
             return sink
         import numpy as np
+        out = self._depths_of(cropper.full)[2]
+        if out != cropper.full.depth:                # the payloads written have the output's depth: so have the bars and their black
+            cropper = LB.Cropper(BD.depth_header(cropper.full, out), cropper.rect)
 
         def pad_sink(k, payloads):
             full = np.empty((len(payloads), cropper.Pf), np.uint8)
@@ -577,12 +632,17 @@ class VideoRunner:
         return 2 if order is not None and self.deinterlace_mode == 'adaptive' else 0
 
     def _check_depth(self, hdr):
-        """Before anything is allocated for this input: a stream above 8 bits runs as tiles only with ``tile_high_depth``."""
-        if hdr.depth > 8 and self.tile is not None and not self.tile_high_depth:
-            raise ValueError('VideoRunner: tile=%r with a %d-bit stream (C%s): tiles move 8-bit pixels, so --tile and high bit '
-                             'depth do not go together unless asked for; run it untiled, convert the input to 8 bits, or pass '
-                             '--tile-high-depth (tile_high_depth=True)' % (self.tile, hdr.depth, hdr.ctag))
-        self.last_depth, self.last_layout = hdr.depth, hdr.layout
+        """Before anything is allocated for this input: the depths resolve (``_depths_of``), and frames above 8 bits -- the WORKING depth
+        decides -- run as tiles only with ``tile_high_depth``.  ``last_depth`` is the depth written."""
+        d_in, work, out, _ = depths = self._depths_of(hdr)
+        if work > 8 and self.tile is not None and not self.tile_high_depth:
+            what = 'a %d-bit stream (C%s)' % (hdr.depth, hdr.ctag) if work == d_in else 'a working depth of %d bits (--work-depth / --out-depth)' % work
+            raise ValueError('VideoRunner: tile=%r with %s: tiles move 8-bit pixels, so --tile and high bit '
+                             'depth do not go together unless asked for; run it untiled, %s, or pass '
+                             '--tile-high-depth (tile_high_depth=True)' % (self.tile, what, 'convert the input to 8 bits' if work == d_in
+                                                                           else 'work at 8 bits'))
+        self.last_depths = None if BD.is_noop(depths) else depths
+        self.last_depth, self.last_layout = out, hdr.layout
 
     def _fine_ratio(self, hdr):
         """The ratio the runner is built with: r, or with a shutter that of the fine stream, r D (refused above ``retime.MAX_RATIO``)."""
@@ -606,7 +666,7 @@ class VideoRunner:
         the per-run counters."""
         rn = cr.runner
         i0, p0, c0, m0, s0 = rn.instants_run, rn.instants_padded, rn.cut_windows, rn.shutter_mixed, rn.shutter_carried
-        w0, z0 = rn.interlace_carried, rn.scale_payloads
+        w0, z0, dp0, dq0 = rn.interlace_carried, rn.scale_payloads, rn.depth_promoted, rn.depth_requantised
         with cr.oversize_hint():
             n = fn()
         lo = first()
@@ -620,14 +680,16 @@ class VideoRunner:
         self.last_interlace = self.interlace[0] if self.interlace is not None else None
         self.last_interlace_carried = rn.interlace_carried - w0
         self.last_scale, self.last_scale_payloads = self._scale_of(hdr), rn.scale_payloads - z0
+        self.last_depth_promoted, self.last_depth_requantised = rn.depth_promoted - dp0, rn.depth_requantised - dq0
         if self.shutter is not None:                 # the fine frames that went into the mixes
             self.last_st_frames = rn.shutter_mixed - m0
         return n
 
     def _edge(self, hdr, with_s1, order=None):
+        depths = self._depths_of(hdr)                # hdr has the input's depth; the edge works at depths[1]
         return YuvEdge(y4m.auto_matrix(self._matrix_h or hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
-                       self.scene_cut, self.full_length, hdr.depth, hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
-                       *(self.interlace or (None, None)), self._scale_of(hdr))
+                       self.scene_cut, self.full_length, depths[1], hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
+                       *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
@@ -738,6 +800,7 @@ class VideoRunner:
                 self.last_shutter, self.last_shutter_carried = self.shutter, 0
                 self.last_interlace, self.last_interlace_carried = (self.interlace[0] if self.interlace is not None else None), 0
                 self.last_scale, self.last_scale_payloads = self._scale_of(hdr), 0
+                self.last_depth_promoted = self.last_depth_requantised = 0
                 return 0, 0
             last = R.first_window(n_in, full) + R.n_windows(n_in, full) - 1
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
@@ -801,7 +864,7 @@ def parser():
                                         '--high-depth, C422pNN, C444pNN, CmonoNN), e.g. ffmpeg -i in.mov -pix_fmt yuv422p10le -strict -1 '
                                         '-f yuv4mpegpipe -; with --deinterlace also interlaced streams of a fixed field order (It, Ib), every '
                                         'field a frame at twice the rate.  Output: progressive (with --interlace: It or Ib at half the rate), the input\'s size (with --scale: WxH), C420jpeg (C420pNN at the input\'s depth; the input\'s layout and '
-                                        'depth for the other layouts), the input\'s '
+                                        'depth for the other layouts; with --out-depth D, or --work-depth W alone, the tag of depth D, or of the input\'s), the input\'s '
                                         'matrix and range.  n input frames give (n-3)*M + 1 output frames: the first and the last '
                                         'input frame have no output, as in the reference (--full-length: n*M frames from input '
                                         'frame 0 on).  All logging goes to stderr.')
@@ -920,6 +983,22 @@ def parser():
     ap.add_argument('--scale-filter', default=None, choices=list(SC.FILTERS),
                     help='with --scale: lanczos3 (default), bicubic (Catmull-Rom) or bilinear; each is stretched for a shrink, so it '
                          'low-passes')
+    ap.add_argument('--work-depth', type=int, default=None, choices=list(y4m.DEPTHS), metavar='W',
+                    help='the bit depth every stage computes at (8, 10, 12, 14 or 16; at least the input\'s): every payload is promoted to W bits '
+                         'on the GPU right behind its upload, so the deinterlacer, the scene scores, the network\'s 16-bit frame path, the shutter\'s '
+                         'mix, the scaler and the weave round at W bits and not at the input\'s 8.  Default: the larger of the input\'s depth and '
+                         '--out-depth.  The output keeps the INPUT\'s depth unless --out-depth says otherwise: --work-depth 12 alone on an 8-bit '
+                         'stream is 8 -> 12 -> 8, dithered.  An 8-bit input needs no --high-depth for it; with --tile it needs '
+                         '--tile-high-depth.  fp16 resolves 10 bits fully and about 12 at best: W >= 12 wants --dtype fp32')
+    ap.add_argument('--out-depth', type=int, default=None, choices=list(y4m.DEPTHS), metavar='D',
+                    help='write the output at D bits (8, 10, 12, 14 or 16; at most the working depth), e.g. --out-depth 10 on an 8-bit stream for a '
+                         'Main10 encoder (C420p10).  Below the working depth every written payload is requantised on the GPU as the last '
+                         'stage (behind --shutter, --scale and --interlace), so only D-bit payloads leave it; see --dither.  Default: the '
+                         'input\'s depth')
+    ap.add_argument('--dither', default=None, choices=list(BD.DITHERS),
+                    help='with an output depth below the working depth: bayer (default) rounds with an 8x8 ordered-dither threshold, the same '
+                         'pattern in every frame and in both fields of an interlaced payload, so a smooth gradient keeps its mean and does not '
+                         'band; none rounds half up.  An error where nothing is requantised')
     T.add_arguments(ap)
     return ap
 
@@ -950,11 +1029,13 @@ def main(argv=None):
         check_shutter(a.shutter, a.shutter_samples, a.dedup or None)
         check_interlace(a.interlace, a.interlace_lowpass)
         check_scale(a.scale, a.scale_filter, a.crop, crop_kw.get('crop_output', 'pad'))
+        check_depths(a.work_depth, a.out_depth, a.dither)
     except ValueError as e:
         parser().error(str(e))
     shutter_kw = {k: v for k, v in (('shutter', a.shutter), ('shutter_samples', a.shutter_samples), ('interlace', a.interlace),
                                     ('interlace_lowpass', a.interlace_lowpass), ('scale', a.scale),
-                                    ('scale_filter', a.scale_filter)) if v is not None}
+                                    ('scale_filter', a.scale_filter), ('work_depth', a.work_depth), ('out_depth', a.out_depth),
+                                    ('dither', a.dither)) if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     if world > 1 and a.shutter is not None:
         raise SystemExit('demfi_amd.video: --shutter runs on one rank (the sub-frames of a written frame straddle the ranks\' blocks)')
@@ -1004,8 +1085,8 @@ def main(argv=None):
     torch.cuda.synchronize()
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
     counts = [float(nw), float(nf), float(vr.last_st_frames), float(vr.last_instants[0]), float(vr.last_instants[1]),
-              float(vr.last_cut_windows)]
-    tw, tf, tst, ti, tp, tc = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
+              float(vr.last_cut_windows), float(vr.last_depth_promoted), float(vr.last_depth_requantised)]
+    tw, tf, tst, ti, tp, tc, tdp, tdq = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
     if rank == 0:
         if a.crop is not None:
             print('demfi_amd.video: ' + vr.crop_report(), file=sys.stderr)
@@ -1018,13 +1099,17 @@ def main(argv=None):
         if a.scale is not None:
             extra['scale'] = {'size': '%dx%d' % vr.scale[:2], 'filter': vr.scale[2], 'resized': vr.last_scale is not None,
                               'payloads': vr.last_scale_payloads}
+        depth = vr.last_depth                        # the depth written; with a depth switch the whole story
+        if any(v is not None for v in (a.work_depth, a.out_depth, a.dither)) and vr.last_depths is not None:
+            depth = {'in': vr.last_depths[0], 'work': vr.last_depths[1], 'out': vr.last_depths[2], 'dither': vr.last_depths[3],
+                     'promoted': int(tdp), 'requantised': int(tdq)}
         print(json.dumps({**extra, 'windows': int(tw), 'frames_written': int(tf), 'seconds': round(dt, 2), 'ranks': world,
                           'St_frames_per_s': round(tst / dt, 2) if dt > 0 else None,
                           'frames_per_s': round(tf / dt, 2) if dt > 0 else None,
                           'fps_out': str(vr.last_fps_out) if vr.last_fps_out is not None else None,
                           'instants_run': int(ti), 'instants_padded': int(tp), 'cut_windows': int(tc), 'dups': len(vr.last_dups),
                           'tiles': vr.last_plan.n_tiles if vr.last_plan is not None else 1,
-                          'tile': vr.last_plan.label() if vr.last_plan is not None else None, 'depth': vr.last_depth, 'layout': vr.last_layout,
+                          'tile': vr.last_plan.label() if vr.last_plan is not None else None, 'depth': depth, 'layout': vr.last_layout,
                           'fields': vr.last_fields, 'ivtc_matches': vr.last_matches if a.ivtc else None,
                           'ivtc_dropped': vr.last_dropped if a.ivtc else None, 'ivtc_combed': vr.last_combed if a.ivtc else None,
                           'crop': list(vr.last_crop) if vr.last_crop is not None else None,

@@ -1,7 +1,7 @@
 """The Y4M edge of the clip pipeline (``demfi_amd.pipeline``): Y4M payloads in and out, every window on its own plan, all options in
 one ``pipeline.EdgeSpec``.  One stage per job, each with its own buffers: ``Ingest``, ``SceneScores``, ``DedupProbe``, the pure function
-``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, ``Shutter``, ``Scaler`` and ``Interlacer``; ``Y4mEdge`` keeps their order and the
-payloads' way out."""
+``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, ``Shutter``, ``Scaler``, ``Interlacer`` and ``Requantizer``; ``Y4mEdge``
+keeps their order and the payloads' way out."""
 import ctypes as C
 
 import numpy as np
@@ -98,11 +98,32 @@ class Ingest:
         self.yuv_in = torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev)
         if self.adaptive:                            # five payload offsets per field rebuilt in a batch (at most nsl); reused in stream order
             self.dei_offs = torch.empty(5 * nsl, dtype=torch.int64, device=dev)
+        # a working depth above the input's (``spec.depths``, ``demfi_amd.bitdepth``): payloads are copied into ``staged`` at the input's sample
+        # size, so H2D carries the input's bytes, and ``promote`` writes them into yuv_in at the working depth before anything else reads them
+        self.staged, self.up, self.full_range = None, self.yuv_in, False     # full_range: the stream's, set by ``Y4mEdge.attach``
+        if spec.depths is not None and spec.depths[1] > spec.depths[0]:
+            self.d_in, self.d_work = spec.depths[:2]
+            self.es_in = 2 if self.d_in > 8 else 1
+            self.staged = self.up = torch.empty((nsl, self.P * self.es_in), dtype=torch.uint8, device=dev)
+            self.planes = np.ascontiguousarray(IL.plane_shapes(h, w, spec.layout), dtype=np.int32)
+            self.pro_host = np.arange(nsl, dtype=np.int64) * (self.P * self.es_in)       # slot -> its byte offset in ``staged``, host and device
+            self.pro_offs = torch.from_numpy(self.pro_host).to(dev)
 
     def upload(self, sl, idx, f):
-        if tuple(f.shape) != (self.Pb,) or f.dtype != torch.uint8:
-            raise ValueError('frame %d: expected a uint8 [%d] %s payload, got %s %s' % (idx, self.Pb, self.layout, f.dtype, tuple(f.shape)))
-        self.yuv_in[sl].copy_(f, non_blocking=True)
+        if tuple(f.shape) != (self.up.shape[1],) or f.dtype != torch.uint8:
+            raise ValueError('frame %d: expected a uint8 [%d] %s payload, got %s %s' % (idx, self.up.shape[1], self.layout, f.dtype, tuple(f.shape)))
+        self.up[sl].copy_(f, non_blocking=True)
+
+    def promote(self, new, stream):
+        """The payloads just copied for the (frame, slot) pairs ``new`` go from ``staged`` to yuv_in at the working depth: ONE
+        ``demfi_payload_promote`` launch per run of consecutive slots, in front of everything that reads yuv_in."""
+        if self.staged is None or not new:
+            return
+        for s0, cnt in consecutive([sl for _, sl in new]):
+            L.check(self.rn.lib.demfi_payload_promote(self.staged.data_ptr(), self.pro_host[s0:].ctypes.data, self.pro_offs[s0:].data_ptr(), cnt,
+                                                      self.planes.ctypes.data, len(self.planes), self.es_in, self.es, self.d_in, self.d_work,
+                                                      int(self.full_range), self.yuv_in[s0].data_ptr(), self.Pb, stream.cuda_stream), 'payload_promote')
+        self.rn.depth_promoted += len(new)
 
     def bob(self, new, stream):
         """The payloads just copied for the (field, slot) pairs ``new`` become progressive in place (at most 64 per launch)."""
@@ -220,6 +241,7 @@ class DedupProbe:
         with torch.cuda.stream(self.h2d):
             sl, _ = self.slots.acquire(key, self.h2d)
             self.ingest.upload(sl, idx, f)
+            self.ingest.promote([(idx, sl)], self.h2d)
             self.ingest.bob([(idx, sl)], self.h2d)
         return sl
 
@@ -456,6 +478,39 @@ class Interlacer:
         return 1
 
 
+class Requantizer:
+    """Written payloads at the working depth -> the output's (``demfi_amd.bitdepth``, ``spec.depths`` = (input, working, output depth, dither
+    mode) with output < working).  The last device stage: after a batch's payloads lie in the rows 0, 1, ... of ``src[i]`` (the gather's, the
+    mix's, the scaler's or the weave's), ``requant`` takes all of them down with ONE ``demfi_payload_requant`` launch on the compute stream
+    into ``out[i]``, buffers of the output's payload size, which are what crosses D2H: 16 -> 8 sends half the bytes.  ``field_rows``: the
+    payloads hold two fields (``spec.interlace``), so the dither's row is the row within its field.  Stateless per payload: which batch a
+    payload came with never shows, and the stage works on every rank.  The runner counts ``depth_requantised``.  The offsets are those of
+    consecutive rows, the same in every batch: one table, uploaded once."""
+
+    def __init__(self, runner, spec, rows, h, w, dev):
+        (_, self.d_work, self.d_out, dither), self.rn, self.lib, self.rows = spec.depths, runner, runner.lib, rows
+        self.es_in, self.es = 2 if self.d_work > 8 else 1, 2 if self.d_out > 8 else 1
+        self.dither, self.field_rows = int(dither == 'bayer'), int(spec.interlace is not None)
+        P = payload_size(h, w, spec.layout)
+        self.Pb_in, self.Pb = P * self.es_in, P * self.es                 # bytes of a payload before and behind
+        self.planes = np.ascontiguousarray(IL.plane_shapes(h, w, spec.layout), dtype=np.int32)
+        self.out = [torch.empty((rows, self.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.h_offs = np.arange(rows, dtype=np.int64) * self.Pb_in
+        self.offs = torch.from_numpy(self.h_offs).to(dev)
+
+    def requant(self, i, counts, src, full_range, stream):
+        """counts[w]: the written payloads of window w, which lie in src[i] from row 0 on; they are requantised into out[i] from row 0 on."""
+        m = sum(counts)
+        if m > self.rows:
+            raise RuntimeError('requant: %d payloads for %d payload rows' % (m, self.rows))
+        if m:
+            self.rn.depth_requantised += m
+            L.check(self.lib.demfi_payload_requant(src[i].data_ptr(), self.h_offs.ctypes.data, self.offs.data_ptr(), m, self.planes.ctypes.data,
+                                                   len(self.planes), self.es_in, self.es, self.d_work, self.d_out, int(full_range), self.dither,
+                                                   self.field_rows, self.out[i].data_ptr(), self.Pb, stream.cuda_stream), 'payload_requant')
+        return counts
+
+
 class TileGrid:
     """A multi-tile plan for the 16-bit frames of the Y4M edge: the sizes ``pipeline.Tiler`` gives, and no device side.  The ingest of
     a (run, tile) pair reads its source rectangle out of the full frame slots and its egress writes its kept rectangle into the full
@@ -544,14 +599,22 @@ class Y4mEdge:
         il = self.interlacer = Interlacer(runner, spec, nhost, oh, ow, oPb, ing.es, dev) if spec.interlace is not None else None
         if il is not None:
             self.progressive, self.written, nhost = self.written, il.woven, il.rows
+        # an output depth below the working depth requantises what would be written, as the last device stage: only payloads of the
+        # output's sample size cross D2H
+        rq = self.requantizer = (Requantizer(runner, spec, nhost, oh, ow, dev) if spec.depths is not None and spec.depths[2] < spec.depths[1]
+                                 else None)
+        if rq is not None:
+            self.deep, self.written, oPb = self.written, rq.out, rq.Pb
         self.h_yuv = [torch.empty((nhost, oPb), dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.yuv = self.window_index = self.det = self.kept = self.gather = None
 
     def __getattr__(self, name):                     # J, tiler, in_place and, on a crop-run-stitch edge only, tcomb: the frame IO's
         return getattr(self.__dict__['io'], name)
 
-    def attach(self, host_frames):
-        """Before a run's first window is asked for.  --dedup: ``host_frames`` is the ``KeptFrames`` that stages frames through ``probe``."""
+    def attach(self, host_frames, yuv=None):
+        """Before a run's first window is asked for.  --dedup: ``host_frames`` is the ``KeptFrames`` that stages frames through ``probe``, and
+        a frame staged is promoted there (``spec.depths``), which needs the range of the stream ``yuv``."""
+        self.ingest.full_range = bool(getattr(yuv, 'full_range', False))
         if self.probe is not None:
             self.kept = self.probe.attach(host_frames)
 
@@ -578,6 +641,7 @@ class Y4mEdge:
     def uploaded(self, new, h2d):
         """After a batch's copies (h2d stream): its (frame, slot) pairs and the kept frames staged since become frame slots; then the SADs."""
         ing, probe = self.ingest, self.probe
+        ing.promote(new, h2d)                        # a working depth above the input's: first of all
         new = ing._adaptive(new, h2d) if ing.adaptive else ing.bob(new, h2d)      # adaptive: the fields just rebuilt, not those uploaded
         if probe is not None:                        # the frames kept since the last batch were bobbed when they were staged
             new, probe.pending = probe.pending + list(new), []
@@ -606,12 +670,16 @@ class Y4mEdge:
             counts = sc.scale(i, counts, self.unscaled, cur)
         if il is not None:
             counts = il.weave(i, counts, ends, self.progressive, cur)
+        if self.requantizer is not None:
+            counts = self.requantizer.requant(i, counts, self.deep, self.yuv.full_range, cur)
         return counts, read
 
     def flush(self, i, cur):
         """After the last batch's ``run``: what is still to be written into buffer set i (None: nothing), for ``d2h`` and ``drain``."""
         if self.interlacer is None or not self.interlacer.flush(i, self.progressive, cur):
             return None
+        if self.requantizer is not None:
+            self.requantizer.requant(i, [1], self.deep, self.yuv.full_range, cur)
         return [1]
 
     def _run_windows(self, i, runs):

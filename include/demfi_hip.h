@@ -553,6 +553,34 @@ int demfi_payload_scale(const uint8_t* base, const int64_t* offsets, const int64
                         const int32_t* planes_out, int n_planes, int sample_bytes, int peak, const uint8_t* tables_dev,
                         const int32_t* table_desc, uint8_t* dst, int64_t dst_stride, void* stream);
 
+/* ---- bit depth of the Y4M edge (csrc/bitdepth.hip; demfi_amd/video.py --work-depth / --out-depth) ------------------------------------
+ * payload_promote / payload_requant: written payload i (n per launch) is the source payload at base + offsets[i] (int64 BYTE offsets)
+ * with every sample taken from depth_in to depth_out bits (8, 10, 12, 14 or 16 each; promote: depth_out > depth_in, requant: depth_out <
+ * depth_in).  A payload is n_planes (1..3) planes one behind the other, plane p of planes[2 p] rows and planes[2 p + 1] columns of samples
+ * (1..2^20 each, 2^30 samples a plane at most; planes is HOST memory), the first luma, the others chroma; in_bytes / out_bytes are the bytes of a source / written
+ * sample: 1 at 8 bits, 2 (little-endian; even addresses, offsets and stride) above.  In exact integers, floor the mathematical floor:
+ *   out = clip(off_out + floor(((v - off_in) * num + T) / den), 0, 2^depth_out - 1)
+ * full_range = 0: off = 0 and (num, den) = (2^(depth_out - depth_in), 1) going up, (1, 2^(depth_in - depth_out)) going down; full_range = 1:
+ * (num, den) = (2^depth_out - 1, 2^depth_in - 1), off = 0 for luma and 2^(depth - 1) for chroma on each side.  T = den / 2 for promote and
+ * for dither = 0; dither = 1 (requant): T = ((2 B + 1) * den) >> 7, B the 8x8 ordered-dither index of the sample's column x and row y
+ * within its plane, B = sum_{i=0..2} (((x ^ y) >> i) & 1) << (5 - 2 i) | ((y >> i) & 1) << (4 - 2 i), with y = row >> 1 when field_rows = 1
+ * (the payload holds two fields).  v is the stored sample, whatever it holds.  The numpy definition is demfi_amd/bitdepth.py
+ * convert_payload_np.  The payload is written at dst + i*dst_stride; the bytes between its end and dst_stride are not written.  The
+ * offsets are passed twice with the same content: offsets in HOST memory, checked here before anything is launched, and offsets_dev in
+ * DEVICE memory, read by the kernel.  DEMFI_ERR_ARG, with nothing launched: a NULL buffer, n < 0, no plane or more than three, a plane
+ * size out of range, a depth that is none of the five or goes the wrong way, sample bytes that do not fit the depths, a flag that is
+ * neither 0 nor 1, 16-bit samples at an odd address, offset or stride, dst_stride below the written payload, a negative offset.  When base
+ * + every offset, every plane's first sample and row length are multiples of 8 source samples and dst and dst_stride multiples of 8
+ * written samples, every thread makes 8 samples from one 16-byte (8-byte for bytes) load with one streaming store of 16 (8) bytes;
+ * otherwise the whole launch goes sample by sample with the same arithmetic (decided per launch).  One launch for all n payloads, no LDS,
+ * no atomics, no table; the sources may overlap each other but not dst; n == 0 does nothing. */
+int demfi_payload_promote(const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, int n, const int32_t* planes,
+                          int n_planes, int in_bytes, int out_bytes, int depth_in, int depth_out, int full_range, uint8_t* dst,
+                          int64_t dst_stride, void* stream);
+int demfi_payload_requant(const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, int n, const int32_t* planes,
+                          int n_planes, int in_bytes, int out_bytes, int depth_in, int depth_out, int full_range, int dither,
+                          int field_rows, uint8_t* dst, int64_t dst_stride, void* stream);
+
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
  * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
