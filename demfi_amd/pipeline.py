@@ -4,8 +4,8 @@ edge object per format, ``BgrEdge`` (BGR frames in and out) or ``y4m_edge.Y4mEdg
 same methods.  Per run: ``attach`` the host frames, then ``begin``, which names the frames to make resident first.  Per batch: ``around`` names the
 frames needed besides its windows', ``upload`` copies one frame into a slot and ``uploaded`` follows the copies (h2d stream), ``run`` computes
 (compute stream), ``d2h`` copies the outputs to pinned memory (d2h stream), ``drain`` hands them to the sink; what ``run`` returns goes to ``d2h`` /
-``drain``; after the last batch ``flush`` names what the edge still holds back (None, or the odd last frame of an interlaced ``--dedup`` run), which
-takes the same way out.  ``ClipPipeline`` is the double-buffered batch loop.  A runner of tiles (``WindowRunner(tiles=plan)``, ``demfi_amd.tiling``) has the tile's
+``drain``; after the last batch ``flush`` names what the edge still holds back (None, or what a ``y4m_edge.Stage`` behind the gather flushed: the odd
+last frame of an interlaced ``--dedup`` run), which takes the same way out. ``ClipPipeline`` is the double-buffered batch loop.  A runner of tiles (``WindowRunner(tiles=plan)``, ``demfi_amd.tiling``) has the tile's
 size while the slots and the outputs keep the frame's: ``Tiler`` crops every uploaded frame into its tiles once, each (run, tile) pair is one run, and
 one stitch launch per batch pastes the kept rectangles into the full-size outputs.  16-bit frames are not cropped or stitched (``TileGrid``): their
 ingest and egress kernels address a tile inside the full frames."""

@@ -217,14 +217,26 @@ class YuvEdge:
         self.full_length = full_length
 
 
-def check_ivtc(ivtc, deinterlace, world=1):
-    """``--ivtc`` does not go with ``--deinterlace`` or with more than one rank."""
+ONE_RANK = {        # the switches that run on one rank only, and why
+    'dedup': 'which frames are kept depends on the whole prefix of the input, so a rank cannot place its block of windows from k and r alone',
+    'ivtc': 'which frames are dropped depends on the whole prefix of the input, so a rank cannot place its block of windows from k and r alone',
+    'shutter': 'the sub-frames of a written frame straddle the ranks\' blocks of windows',
+    'interlace': 'the two frames of a written payload can straddle the ranks\' blocks of windows',
+}
+
+
+def check_one_rank(world, **switches):
+    """The switches of ``ONE_RANK`` that are set (neither None nor False) are refused with more than one rank."""
+    for name, why in ONE_RANK.items():
+        if world > 1 and switches.get(name) not in (None, False):
+            raise ValueError('VideoRunner: %s with %d ranks: %s; run --%s on one rank' % (name, world, why, name))
+
+
+def check_ivtc(ivtc, deinterlace):
+    """``--ivtc`` does not go with ``--deinterlace``."""
     if ivtc and deinterlace:
         raise ValueError('--ivtc does not go with --deinterlace: inverse telecine puts the fields of a film frame back together, the '
                          'deinterlacer makes a frame of every field; choose one (film carried by 3:2 pulldown: --ivtc)')
-    if ivtc and world > 1:
-        raise ValueError('VideoRunner: ivtc with %d ranks: which frames are dropped depends on the whole prefix of the input, so a rank '
-                         'cannot place its block of windows from k and r alone; run --ivtc on one rank' % world)
 
 
 def check_crop(crop, limit=LB.DEFAULT_LIMIT, noise=LB.DEFAULT_NOISE, probe=LB.DEFAULT_PROBE, output='pad'):
@@ -248,7 +260,7 @@ def check_shutter(shutter, samples=None, dedup=None, world=1):
     if dedup not in (None, False):
         raise ValueError('--shutter does not go with --dedup: the sub-frames of a written frame are laid over the regular fine timeline, which '
                          'repeated frames left out of the input bend; run one of the two')
-    check_shutter_ranks(sd, world)
+    check_one_rank(world, shutter=sd)
     return sd
 
 
@@ -260,7 +272,7 @@ def check_interlace(interlace, lowpass=None, world=1):
             raise ValueError('--interlace-lowpass (interlace_lowpass) says how --interlace works: give --interlace tff or bff with it')
         return None
     il = (IL.parse_order(interlace), IL.check_lowpass(lowpass))
-    check_interlace_ranks(il, world)
+    check_one_rank(world, interlace=il)
     return il
 
 
@@ -287,18 +299,11 @@ def check_depths(work_depth=None, out_depth=None, dither=None):
     return BD.check_switches(work_depth, out_depth, dither)
 
 
-def check_interlace_ranks(interlace, world):
-    """Interlaced output runs on one rank: the two frames of a written payload can straddle two ranks' blocks of windows."""
-    if interlace is not None and world > 1:
-        raise ValueError('VideoRunner: interlace with %d ranks: the two frames of a written payload can straddle the ranks\' blocks of '
-                         'windows; run --interlace on one rank' % world)
-
-
-def check_shutter_ranks(shutter, world):
-    """A shutter runs on one rank: the sub-frames of a written frame straddle the ranks' blocks of windows."""
-    if shutter is not None and world > 1:
-        raise ValueError('VideoRunner: shutter with %d ranks: the sub-frames of a written frame straddle the ranks\' blocks of windows; run '
-                         '--shutter on one rank' % world)
+# what a run adds to each of these counters of its ``WindowRunner`` is kept in the ``VideoRunner`` attribute named here (None: it goes into
+# ``last_instants`` = (run, padded), and a shutter's fine frames into ``last_st_frames``: ``VideoRunner._counted``)
+COUNTERS = {'instants_run': None, 'instants_padded': None, 'shutter_mixed': None, 'cut_windows': 'last_cut_windows',
+            'shutter_carried': 'last_shutter_carried', 'interlace_carried': 'last_interlace_carried', 'scale_payloads': 'last_scale_payloads',
+            'depth_promoted': 'last_depth_promoted', 'depth_requantised': 'last_depth_requantised'}
 
 
 AUTO_NEEDS_A_FILE = ('--crop auto needs a regular input file: the bars of a stream are known only at its end; give the four bar '
@@ -407,13 +412,12 @@ class VideoRunner:
                  out_depth=None, dither=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
         self.work_depth, self.out_depth, self.dither = check_depths(work_depth, out_depth, dither)
-        self.last_depths, self.last_depth_promoted, self.last_depth_requantised = None, 0, 0
         self.scale = check_scale(scale, scale_filter, crop, crop_output)  # (w, h, filter) or None
-        self.last_scale, self.last_scale_payloads = None, 0
         self.interlace = check_interlace(interlace, interlace_lowpass)    # (order, low-pass mode) or None
-        self.last_interlace, self.last_interlace_carried = None, 0
         self.shutter = check_shutter(shutter, shutter_samples, dedup)     # (S, D) or None
-        self.last_shutter, self.last_shutter_carried = None, 0
+        self.last_depths = self.last_scale = self.last_interlace = self.last_shutter = None
+        for attr in filter(None, COUNTERS.values()):
+            setattr(self, attr, 0)
         self.crop, (self.crop_limit, self.crop_noise, self.crop_probe, self.crop_output) = check_crop(
             crop, crop_limit, crop_noise, crop_probe, crop_output)
         self.last_crop, self.last_crop_probed, self.last_crop_note, self.last_crop_seconds = None, 0, None, 0.0
@@ -456,7 +460,6 @@ class VideoRunner:
         self.last_st_frames = 0
         self.last_fps_out = None
         self.last_cuts = []
-        self.last_cut_windows = 0
         if dedup is None or dedup is False:
             self.dedup = None
             K.check_params(max_hold=dedup_max_hold)
@@ -665,25 +668,24 @@ class VideoRunner:
         """fn() runs windows lo, lo+1, ... of the input on cr, lo = first() once it has run; returns its window count and sets
         the per-run counters."""
         rn = cr.runner
-        i0, p0, c0, m0, s0 = rn.instants_run, rn.instants_padded, rn.cut_windows, rn.shutter_mixed, rn.shutter_carried
-        w0, z0, dp0, dq0 = rn.interlace_carried, rn.scale_payloads, rn.depth_promoted, rn.depth_requantised
+        before = {name: getattr(rn, name) for name in COUNTERS}
         with cr.oversize_hint():
             n = fn()
-        lo = first()
-        self.last_instants = (rn.instants_run - i0, rn.instants_padded - p0)
-        self.last_cuts = list(rn.last_cuts) if self.scene_cut is not None else []
-        self.last_cut_windows = rn.cut_windows - c0
-        r = self._ratio(hdr)
-        self.last_st_frames = sum(kind == R.ST for k in range(lo, lo + n) for _, kind, _ in R.window_outputs(k, r, full_length=self.full_length))
-        self.last_shutter = self.shutter
-        self.last_shutter_carried = rn.shutter_carried - s0
-        self.last_interlace = self.interlace[0] if self.interlace is not None else None
-        self.last_interlace_carried = rn.interlace_carried - w0
-        self.last_scale, self.last_scale_payloads = self._scale_of(hdr), rn.scale_payloads - z0
-        self.last_depth_promoted, self.last_depth_requantised = rn.depth_promoted - dp0, rn.depth_requantised - dq0
-        if self.shutter is not None:                 # the fine frames that went into the mixes
-            self.last_st_frames = rn.shutter_mixed - m0
+        lo, r = first(), self._ratio(hdr)
+        self._counted(hdr, {name: getattr(rn, name) - before[name] for name in COUNTERS}, list(rn.last_cuts) if self.scene_cut is not None else [],
+                      sum(kind == R.ST for k in range(lo, lo + n) for _, kind, _ in R.window_outputs(k, r, full_length=self.full_length)))
         return n
+
+    def _counted(self, hdr, added, cuts, st_frames):
+        """The per-run values of a run on the stream of ``hdr``: ``added[name]`` is what it added to the runner's counter ``name`` of
+        ``COUNTERS`` (a rank without a window: zeros), ``cuts`` the frames that start a scene, ``st_frames`` the St frames its windows own."""
+        for name, attr in COUNTERS.items():
+            if attr is not None:
+                setattr(self, attr, added[name])
+        self.last_instants, self.last_cuts = (added['instants_run'], added['instants_padded']), cuts
+        self.last_st_frames = added['shutter_mixed'] if self.shutter is not None else st_frames     # the fine frames that went into the mixes
+        self.last_shutter, self.last_scale = self.shutter, self._scale_of(hdr)
+        self.last_interlace = self.interlace[0] if self.interlace is not None else None
 
     def _edge(self, hdr, with_s1, order=None):
         depths = self._depths_of(hdr)                # hdr has the input's depth; the edge works at depths[1]
@@ -751,12 +753,7 @@ class VideoRunner:
         """Rank ``rank`` of ``world`` on regular files: one scan of the input's frame headers, this rank's block of windows
         (``dist.shard_windows``), its frames written at ``header + i*(6 + payload)``.  Rank 0 writes the header and sizes the
         output file; all ranks meet at a barrier before writing.  Returns (windows, frames written) of this rank."""
-        if self.dedup is not None and world > 1:
-            raise ValueError('VideoRunner: dedup with %d ranks: which frames are kept depends on the whole prefix of the input, so a rank '
-                             'cannot place its block of windows from k and r alone; run --dedup on one rank' % world)
-        check_ivtc(self.ivtc, self.deinterlace, world)
-        check_shutter_ranks(self.shutter, world)
-        check_interlace_ranks(self.interlace, world)
+        check_one_rank(world, dedup=self.dedup, ivtc=self.ivtc, shutter=self.shutter, interlace=self.interlace)
         self.last_dups, self._film = [], None
         with open(in_path, 'rb') as f:
             in_hdr, _, offs = y4m.scan(f, self.depths, self.layouts, self.deinterlace, self.ivtc)
@@ -796,11 +793,7 @@ class VideoRunner:
                 return n, wr.frames
             lo, wins = cr.my_windows(n_in, full)
             if not wins:
-                self.last_instants, self.last_st_frames, self.last_cuts, self.last_cut_windows = (0, 0), 0, [], 0
-                self.last_shutter, self.last_shutter_carried = self.shutter, 0
-                self.last_interlace, self.last_interlace_carried = (self.interlace[0] if self.interlace is not None else None), 0
-                self.last_scale, self.last_scale_payloads = self._scale_of(hdr), 0
-                self.last_depth_promoted = self.last_depth_requantised = 0
+                self._counted(hdr, dict.fromkeys(COUNTERS, 0), [], 0)
                 return 0, 0
             last = R.first_window(n_in, full) + R.n_windows(n_in, full) - 1
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
@@ -820,22 +813,6 @@ class VideoRunner:
 
 def _is_regular(path):
     return path != '-' and (not os.path.exists(path) or os.path.isfile(path))
-
-
-def _scene_cut_arg(text):
-    try:
-        return S.check_threshold(text)
-    except ValueError as e:
-        import argparse
-        raise argparse.ArgumentTypeError(str(e))
-
-
-def _fps_arg(text):
-    try:
-        return R.parse_fps(text)
-    except ValueError as e:
-        import argparse
-        raise argparse.ArgumentTypeError(str(e))
 
 
 def _value_arg(fn):
@@ -872,7 +849,7 @@ def parser():
     ap.add_argument('output', help="Y4M file, or - for stdout")
     rate = ap.add_mutually_exclusive_group()
     rate.add_argument('--mfi', type=int, default=None, help='multiple_MFI: output frame rate = M x input (main.py:98); default 8')
-    rate.add_argument('--fps', type=_fps_arg, default=None,
+    rate.add_argument('--fps', type=_value_arg(R.parse_fps), default=None,
                       help='output frame rate N, N/D or N:D (exact: 60000/1001, not 59.94), at least the input rate; output frame '
                            'i is at input time 1 + i*F_in/F_out')
     ap.add_argument('--n-tst', type=int, default=3, help='N_tst recursive boosts (main.py:101)')
@@ -881,7 +858,7 @@ def parser():
     ap.add_argument('--matrix', default='auto', choices=['auto', 'bt601', 'bt709'],
                     help='YCbCr matrix of the input (and output); auto: BT.709 when H >= 720, else BT.601')
     ap.add_argument('--batch', type=int, default=4, help='windows per batch (the input frames held are bounded by it)')
-    ap.add_argument('--scene-cut', nargs='?', type=_scene_cut_arg, const=S.DEFAULT_THRESHOLD, default=None, metavar='T',
+    ap.add_argument('--scene-cut', nargs='?', type=_value_arg(S.check_threshold), const=S.DEFAULT_THRESHOLD, default=None, metavar='T',
                     help='detect scene cuts (score = min(mafd, |mafd - previous mafd|) of the payload samples, in percent; a cut where '
                          'score >= T, T in (0, 100], default %g) and never interpolate across one: the frames next to a cut '
                          'hold the nearest input frame.  Off unless given' % S.DEFAULT_THRESHOLD)
@@ -1017,9 +994,6 @@ def main(argv=None):
         check_deinterlace_mode(a.deinterlace, a.deinterlace_mode, a.dedup or None)
         check_ivtc(a.ivtc, a.deinterlace)
         TC.check_params(a.ivtc_cthresh, a.ivtc_combpel, a.ivtc_combed)
-        if a.crop is None and any(v is not None for v in (a.crop_limit, a.crop_noise, a.crop_probe, a.crop_output)):
-            raise ValueError('--crop-limit, --crop-noise, --crop-probe and --crop-output say how --crop works: give --crop auto or '
-                             '--crop T:B:L:R with them')
         crop_kw = {k: v for k, v in (('crop', a.crop), ('crop_limit', a.crop_limit), ('crop_noise', a.crop_noise),
                                      ('crop_probe', a.crop_probe), ('crop_output', a.crop_output)) if v is not None}
         check_crop(*(crop_kw.get(k, d) for k, d in (('crop', None), ('crop_limit', LB.DEFAULT_LIMIT), ('crop_noise', LB.DEFAULT_NOISE),
@@ -1037,14 +1011,10 @@ def main(argv=None):
                                     ('scale_filter', a.scale_filter), ('work_depth', a.work_depth), ('out_depth', a.out_depth),
                                     ('dither', a.dither)) if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
-    if world > 1 and a.shutter is not None:
-        raise SystemExit('demfi_amd.video: --shutter runs on one rank (the sub-frames of a written frame straddle the ranks\' blocks)')
-    if world > 1 and a.interlace is not None:
-        raise SystemExit('demfi_amd.video: --interlace runs on one rank (the two frames of a written payload can straddle the ranks\' blocks)')
-    if world > 1 and a.dedup:
-        raise SystemExit('demfi_amd.video: --dedup runs on one rank (which frames are kept depends on the whole prefix of the input)')
-    if world > 1 and a.ivtc:
-        raise SystemExit('demfi_amd.video: --ivtc runs on one rank (which frames are dropped depends on the whole prefix of the input)')
+    try:
+        check_one_rank(world, dedup=a.dedup, ivtc=a.ivtc, shutter=a.shutter, interlace=a.interlace)
+    except ValueError as e:
+        raise SystemExit('demfi_amd.video: ' + str(e))
     if world > 1 and not (_is_regular(a.input) and os.path.isfile(a.input) and _is_regular(a.output)):
         raise SystemExit('demfi_amd.video: with %d ranks IN and OUT must be regular files (ranks write at byte offsets)' % world)
     out_fd = None

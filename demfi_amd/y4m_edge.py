@@ -1,8 +1,14 @@
 """The Y4M edge of the clip pipeline (``demfi_amd.pipeline``): Y4M payloads in and out, every window on its own plan, all options in
 one ``pipeline.EdgeSpec``.  One stage per job, each with its own buffers: ``Ingest``, ``SceneScores``, ``DedupProbe``, the pure function
-``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, ``Shutter``, ``Scaler``, ``Interlacer`` and ``Requantizer``; ``Y4mEdge``
-keeps their order and the payloads' way out."""
+``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, the ``Stage`` chain that ``egress_layout`` sizes: ``Shutter``,
+``Scaler``, ``Interlacer`` and ``Requantizer``, in that order, each only when ``spec`` asks for it; ``Y4mEdge`` loops over them and keeps the
+payloads' way out.
+
+The buffer rule of the chain: a stage reads its payloads from row ``lead`` of its source buffer on (the ``lead`` rows in front are where it
+carries what it holds open from one batch to the next), so a buffer has as many rows as its producer can write, plus the ``lead`` of its consumer
+in front.  The gather is producer number zero, the pinned host buffers are the last consumer and read from row 0."""
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -137,6 +143,12 @@ class Ingest:
                                                   sum(q[c0 + j] << j for j in range(c)), stream.cuda_stream), 'yuv_bob')
         return new
 
+    def rebuilt(self, new, stream):
+        """The payloads just copied for the (frame, slot) pairs ``new`` become progressive payloads at the working depth: promoted first of
+        all, then made progressive.  Returns the pairs that now are (adaptive: the fields just rebuilt, not those uploaded)."""
+        self.promote(new, stream)
+        return self._adaptive(new, stream) if self.adaptive else self.bob(new, stream)
+
     def around(self, needed, has):
         """Adaptive: the fields f-2 .. f+2 of every field f of ``needed`` not rebuilt yet, as far as the input has them (``has``)."""
         if not self.adaptive:
@@ -241,8 +253,7 @@ class DedupProbe:
         with torch.cuda.stream(self.h2d):
             sl, _ = self.slots.acquire(key, self.h2d)
             self.ingest.upload(sl, idx, f)
-            self.ingest.promote([(idx, sl)], self.h2d)
-            self.ingest.bob([(idx, sl)], self.h2d)
+            self.ingest.rebuilt([(idx, sl)], self.h2d)
         return sl
 
     def block_counts(self, sl, ref):
@@ -312,31 +323,97 @@ def plan_fine(spec, r, wins, n, window_index, with_s1, det, kept, frames, slot_o
     return runs, outs, cut_windows, st_frames, fine, ends
 
 
-class Shutter:
-    """Fine payloads gathered -> written payloads mixed (``demfi_amd.shutter``, ``spec.shutter`` = (S, D)).  Written frame c averages the
-    fine frames c D .. c D + S - 1 of its scene that exist.  After a batch's gather ``mix`` closes every group whose last sample has arrived
-    (all open groups when the batch holds the clip's last window) and ONE ``demfi_payload_mix`` launch on the compute stream writes them into
-    ``mixed[i]``, which is what crosses D2H; a written frame counts to the window that completed it.  The samples of the one group still open
-    (at most ``lead`` = S - 1 of them, consecutive rows at the end of the gather) carry over on the device: ``carry`` copies them into the
-    ``lead`` rows in front of the next batch's gather (yuv_out[i] has that many more rows), so which batch a sample came with never shows.
-    The runner counts for it, as it counts cut windows: ``shutter_mixed`` the fine frames that went into the mixes, ``shutter_carried`` the
-    samples carried from one batch to the next.  ``h_offs``: the pinned offset tables, one per buffer set; table i is written again two
-    batches later, when the host has drained the batch that last copied from it (``ClipPipeline._drain`` waits for that batch's D2H, which
-    waited for its compute, where the copy of the table ran)."""
+Buffer = namedtuple('Buffer', 'name lead rows Pb h w')
 
-    def __init__(self, runner, spec, nout, batch, Pb, es, dev, front=0):
-        (self.S, self.D), self.rn, self.lib, self.Pb, self.es = spec.shutter, runner, runner.lib, Pb, es
-        self.front = front                           # rows left free in front of mixed[i] for the stage behind (``Interlacer``'s carry row)
-        self.lead = self.S - 1
+
+def egress_layout(spec, nout, batch, h, w):
+    """The buffers behind the gather of ``nout`` h x w payloads a batch (of ``batch`` windows) by the module's buffer rule, for the stages
+    ``spec`` asks for, in their order mix -> scale -> weave -> requant: a ``Buffer`` (name of its producer, free rows in front = the ``lead`` of
+    its consumer, the most payloads its producer writes per batch, bytes of a payload, frame size) for the gather and every stage built, then
+    (rows, payload bytes) of the pinned host buffers.  Pure: allocates nothing."""
+    es, chain = 2 if spec.hi else 1, []
+
+    def add(name, lead, rows, es=es):                # lead: what the stage itself needs in front of its source's payloads
+        chain.append((name, lead, rows, payload_size(h, w, spec.layout) * es, h, w))
+    add('gather', 0, nout)
+    if spec.shutter is not None:
         # written frames of a batch: the multiples of D among the fine indices of its windows (each owns up to J, the last one of the full-length
-        # timeline 2 J, nout in all), and the group carried into it
-        self.rows = nout // self.D + batch + 2
-        self.mixed = [torch.empty((front + self.rows, Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.offs = [torch.empty(self.rows * self.S, dtype=torch.int64, device=dev) for _ in range(2)]
-        self.h_offs = [torch.empty((self.rows, self.S), dtype=torch.int64).pin_memory() for _ in range(2)]
-        self.begin()
+        # timeline 2 J, nout in all), and the group carried into it; the open group's samples carry in front of the gather
+        add('mix', spec.shutter[0] - 1, nout // spec.shutter[1] + batch + 2)
+    if spec.scale is not None and tuple(spec.scale[:2]) != (w, h):       # the run's own size: no stage, the bytes of a run without
+        w, h = spec.scale[:2]
+        add('scale', 0, chain[-1][2])
+    if spec.interlace is not None:                   # pairs of the carried frame and a batch's frames, the odd tail among them
+        add('weave', 1, chain[-1][2] // 2 + 1)
+    if spec.depths is not None and spec.depths[2] < spec.depths[1]:
+        add('requant', 0, chain[-1][2], 2 if spec.depths[2] > 8 else 1)
+    leads = [c[1] for c in chain[1:]] + [0]
+    return [Buffer(c[0], lead, *c[2:]) for c, lead in zip(chain, leads)] + [chain[-1][2:4]]
 
-    def begin(self):
+
+class Stage:
+    """One device stage behind the gather: after a batch's payloads lie in ``src[i]`` from row ``lead`` on, ``run`` writes its own into
+    ``out[i]`` from row ``front`` on (the ``lead`` of the stage behind) with ONE launch on the compute stream, and returns the payloads per
+    window.  ``src`` / ``own``: the ``Buffer`` it reads and the one it writes (``egress_layout``); ``rows``, ``Pb``, ``h``, ``w``: of ``own``.
+    ``begin(yuv)`` resets what a stage keeps within a run, ``carry(i, src)`` runs before the batch's gather, ``flush(i, src, stream)`` after
+    the last batch and returns the payloads it still wrote (0 or 1).  ``regroups``: a window may complete no payload of the stage.
+    ``offs`` / ``h_offs``: the offset tables of the launch, ``width`` offsets a payload written (0: the stage has a table of its own), on the
+    device and pinned, one per buffer set; table i is written again two batches later, when the host has drained the batch that last copied
+    from it (``ClipPipeline._drain`` waits for that batch's D2H, which waited for its compute, where the copy of the table ran)."""
+    regroups, width = False, 1
+
+    def __init__(self, runner, spec, src, own, dev):
+        self.rn, self.lib, self.es = runner, runner.lib, 2 if spec.hi else 1
+        self.lead, self.front, self.rows, self.Pb, self.h, self.w = src.lead, own.lead, own.rows, own.Pb, own.h, own.w
+        self.out = [torch.empty((own.lead + own.rows, own.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        if self.width:
+            self.offs = [torch.empty(self.rows * self.width, dtype=torch.int64, device=dev) for _ in range(2)]
+            self.h_offs = [torch.empty((self.rows, self.width), dtype=torch.int64).pin_memory() for _ in range(2)]
+
+    def begin(self, yuv):
+        pass
+
+    def carry(self, i, src):
+        pass
+
+    def flush(self, i, src, stream):
+        return 0
+
+    def _table(self, i, offsets):
+        host = self.h_offs[i][:len(offsets)]
+        host.numpy()[:] = offsets
+        od = self.offs[i][:host.numel()]
+        od.copy_(host.view(-1), non_blocking=True)
+        return host.data_ptr(), od.data_ptr()
+
+    def _launch(self, i, offsets, src, stream, counted=None):
+        """The payloads of the byte offsets ``offsets`` [n, width] into src[i] are written into out[i]; the runner's ``counter`` goes up by
+        ``counted`` (None: n)."""
+        n = len(offsets)
+        if n > self.rows:
+            raise RuntimeError(self.too_many % (n, self.rows))
+        setattr(self.rn, self.counter, getattr(self.rn, self.counter) + (n if counted is None else counted))
+        if n:
+            self._call(src[i].data_ptr(), *self._table(i, offsets), n, self.out[i][self.front:].data_ptr(), stream.cuda_stream)
+
+
+class Shutter(Stage):
+    """Fine payloads gathered -> written payloads mixed (``demfi_amd.shutter``, ``spec.shutter`` = (S, D)).  Written frame c averages the
+    fine frames c D .. c D + S - 1 of its scene that exist.  After a batch's gather ``run`` closes every group whose last sample has arrived
+    (all open groups when the batch holds the clip's last window) and ``demfi_payload_mix`` writes them; a written frame counts to the window
+    that completed it.  The samples of the one group still open (at most ``lead`` = S - 1 of them, consecutive rows at the end of the gather)
+    carry over on the device: ``carry`` copies them into the ``lead`` rows in front of the next batch's gather, so which batch a sample came
+    with never shows.  The runner counts for it, as it counts cut windows: ``shutter_mixed`` the fine frames that went into the mixes,
+    ``shutter_carried`` the samples carried from one batch to the next."""
+    regroups, counter, too_many = True, 'shutter_mixed', 'shutter: %d written frames for %d payload rows'
+
+    def __init__(self, runner, spec, src, own, dev):
+        self.S, self.D = spec.shutter
+        self.width = self.S
+        super().__init__(runner, spec, src, own, dev)
+        self.begin(None)
+
+    def begin(self, yuv):
         self.open, self.scene = [], 0                # open: (fine index, scene, row) of the samples of the open group
 
     def carry(self, i, yuv_out):
@@ -351,88 +428,61 @@ class Shutter:
         self.rn.shutter_carried += m
         self.open = [(g, sc, self.lead - m + j) for j, (g, sc, _) in enumerate(self.open)]
 
-    def mix(self, i, fine, ends, yuv_out, stream):
-        """fine[w] = ``plan_fine``'s for window w, gathered into yuv_out[i] from row ``lead`` on; returns the written payloads per window."""
-        S = self.S
-        table, counts, self.open, self.scene = SH.close_groups(self.open, fine, self.scene, ends, S, self.D, self.lead)
-        nc = len(table)
-        if nc > self.rows:
-            raise RuntimeError('shutter: %d written frames for %d payload rows' % (nc, self.rows))
-        if nc:
-            self.rn.shutter_mixed += sum(len(t) for t in table)
-            host = self.h_offs[i][:nc]
-            host.numpy()[:] = [[rw * self.Pb for rw in t] + [-1] * (S - len(t)) for t in table]
-            od = self.offs[i][:nc * S]
-            od.copy_(host.view(-1), non_blocking=True)
-            L.check(self.lib.demfi_payload_mix(yuv_out[i].data_ptr(), host.data_ptr(), od.data_ptr(), nc, S, self.Pb // self.es, self.es,
-                                               self.mixed[i][self.front:].data_ptr(), self.Pb, stream.cuda_stream), 'payload_mix')
+    def run(self, i, counts, batch, yuv_out, stream):
+        """batch = (fine, ends) of ``plan_fine``: fine[w] for window w, gathered into yuv_out[i] from row ``lead`` on."""
+        fine, ends = batch
+        table, counts, self.open, self.scene = SH.close_groups(self.open, fine, self.scene, ends, self.S, self.D, self.lead)
+        self._launch(i, [[rw * self.Pb for rw in t] + [-1] * (self.S - len(t)) for t in table], yuv_out, stream, sum(len(t) for t in table))
         return counts
 
+    def _call(self, src, host, offs, n, dst, stream):
+        L.check(self.lib.demfi_payload_mix(src, host, offs, n, self.S, self.Pb // self.es, self.es, dst, self.Pb, stream), 'payload_mix')
 
-class Scaler:
-    """Progressive payloads -> resized ones (``demfi_amd.scale``, ``spec.scale`` = (w, h, filter)).  The stage sits behind the gather, or behind
-    ``Shutter.mix``, and in front of ``Interlacer.weave``: after a batch's progressive payloads lie in the rows 0, 1, ... of ``src[i]``, ``scale``
-    resamples all of them with ONE ``demfi_payload_scale`` launch on the compute stream into ``scaled[i]`` from row ``front`` on (``front``: the
-    rows left free for the stage behind, the ``Interlacer``'s carry row); ``scaled[i]`` is what crosses D2H, or what the weave reads.  Stateless
-    per payload: no sample carries over from one batch to the next, so which batch a frame came with never shows, and the stage works on every
-    rank.  The tables of ``scale.table_blob`` are the only source of the weights; they are uploaded once, here.  The runner counts
-    ``scale_payloads``.  ``h_offs``: the pinned offset tables, one per buffer set, rewritten two batches later, when the host has drained the
-    batch that last copied from them (as ``Shutter.h_offs``)."""
 
-    def __init__(self, runner, spec, rows, h, w, es, dev, front=0):
-        (self.w, self.h, self.filter), self.rn, self.lib, self.es, self.front, self.rows = spec.scale, runner, runner.lib, es, front, rows
-        self.peak, self.Pb_in = (1 << spec.depth) - 1, payload_size(h, w, spec.layout) * es
-        self.Pb = payload_size(self.h, self.w, spec.layout) * es             # bytes of a resized payload
-        shapes_in, shapes_out = IL.plane_shapes(h, w, spec.layout), IL.plane_shapes(self.h, self.w, spec.layout)
+class Scaler(Stage):
+    """Progressive payloads -> resized ones (``demfi_amd.scale``, ``spec.scale`` = (w, h, filter)): behind the gather or the mix and in front
+    of the weave, so the scaler never sees woven fields.  ``demfi_payload_scale`` resamples all of a batch's payloads.  Stateless per payload:
+    no sample carries over from one batch to the next, so which batch a frame came with never shows, and the stage works on every rank.  The
+    tables of ``scale.table_blob`` are the only source of the weights; they are uploaded once, here.  The runner counts ``scale_payloads``."""
+    counter, too_many = 'scale_payloads', 'scale: %d payloads for %d payload rows'
+
+    def __init__(self, runner, spec, src, own, dev):
+        super().__init__(runner, spec, src, own, dev)
+        self.filter, self.peak, self.Pb_in = spec.scale[2], (1 << spec.depth) - 1, src.Pb
+        shapes_in, shapes_out = IL.plane_shapes(src.h, src.w, spec.layout), IL.plane_shapes(self.h, self.w, spec.layout)
         self.planes_in, self.planes_out = (np.ascontiguousarray(a, dtype=np.int32) for a in (shapes_in, shapes_out))
         blob, self.desc = SC.table_blob(shapes_in, shapes_out, self.filter)
         self.tables = torch.from_numpy(blob).to(dev)
-        self.scaled = [torch.empty((front + rows, self.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.offs = [torch.empty(rows, dtype=torch.int64, device=dev) for _ in range(2)]
-        self.h_offs = [torch.empty(rows, dtype=torch.int64).pin_memory() for _ in range(2)]
 
-    def scale(self, i, counts, src, stream):
-        """counts[w]: the progressive payloads of window w, which lie in src[i] from row 0 on; they are resized into scaled[i] from row ``front`` on."""
-        m = sum(counts)
-        if m > self.rows:
-            raise RuntimeError('scale: %d payloads for %d payload rows' % (m, self.rows))
-        if m:
-            self.rn.scale_payloads += m
-            host = self.h_offs[i][:m]
-            host.numpy()[:] = np.arange(m, dtype=np.int64) * self.Pb_in
-            od = self.offs[i][:m]
-            od.copy_(host, non_blocking=True)
-            L.check(self.lib.demfi_payload_scale(src[i].data_ptr(), host.data_ptr(), od.data_ptr(), m, self.planes_in.ctypes.data,
-                                                 self.planes_out.ctypes.data, len(self.planes_in), self.es, self.peak, self.tables.data_ptr(),
-                                                 self.desc.ctypes.data, self.scaled[i][self.front:].data_ptr(), self.Pb, stream.cuda_stream),
-                    'payload_scale')
+    def run(self, i, counts, batch, src, stream):
+        self._launch(i, np.arange(sum(counts), dtype=np.int64)[:, None] * self.Pb_in, src, stream)
         return counts
 
+    def _call(self, src, host, offs, n, dst, stream):
+        L.check(self.lib.demfi_payload_scale(src, host, offs, n, self.planes_in.ctypes.data, self.planes_out.ctypes.data, len(self.planes_in),
+                                             self.es, self.peak, self.tables.data_ptr(), self.desc.ctypes.data, dst, self.Pb, stream),
+                'payload_scale')
 
-class Interlacer:
+
+class Interlacer(Stage):
     """Progressive payloads -> woven ones (``demfi_amd.interlace``, ``spec.interlace`` = (field order, low-pass mode)).  Written payload q
-    weaves frames 2q (the first field in time) and 2q + 1 of the progressive stream.  The stage sits behind the gather, or behind
-    ``Shutter.mix``: after a batch's frames are written into ``src[i]`` from row ``lead`` on, ``weave`` closes every pair whose second frame has
-    arrived (``interlace.close_pairs``; the odd tail too when the batch holds the clip's last window) and ONE ``demfi_payload_weave`` launch on
-    the compute stream writes them into ``woven[i]``, which is what crosses D2H; a woven payload counts to the window that completed it.  The
-    one frame still open carries over on the device: ``carry`` copies it into row 0 of the next batch's source buffer (``lead`` = 1 row in
-    front of its frames), so which batch a frame came with never shows.  A run whose edge never learns which window is the last (``--dedup``)
-    ends with ``flush``, which weaves the open frame with itself.  The runner counts: ``interlace_woven`` the payloads woven,
-    ``interlace_carried`` the frames carried from one batch to the next.  ``h_offs``: the pinned offset tables, one per buffer set, rewritten
-    two batches later, when the host has drained the batch that last copied from them (as ``Shutter.h_offs``)."""
-    lead = 1
+    weaves frames 2q (the first field in time) and 2q + 1 of the progressive stream.  After a batch's frames are written into ``src[i]``
+    ``run`` closes every pair whose second frame has arrived (``interlace.close_pairs``; the odd tail too when the batch holds the clip's last
+    window) and ``demfi_payload_weave`` writes them; a woven payload counts to the window that completed it.  The one frame still open
+    carries over on the device: ``carry`` copies it into row 0 of the next batch's source buffer (``lead`` = 1 row in front of its frames),
+    so which batch a frame came with never shows.  A run whose edge never learns which window is the last (``--dedup``) ends with ``flush``,
+    which weaves the open frame with itself.  The runner counts: ``interlace_woven`` the payloads woven, ``interlace_carried`` the frames
+    carried from one batch to the next."""
+    regroups, width, counter, too_many = True, 2, 'interlace_woven', 'interlace: %d woven payloads for %d payload rows'
 
-    def __init__(self, runner, spec, rows_in, h, w, Pb, es, dev):
-        (self.order, self.lowpass), self.rn, self.lib, self.Pb, self.es = spec.interlace, runner, runner.lib, Pb, es
+    def __init__(self, runner, spec, src, own, dev):
+        super().__init__(runner, spec, src, own, dev)
+        self.order, self.lowpass = spec.interlace
         self.q0, self.mode, self.peak = I.field_parity(self.order, 0), IL.LOWPASS.index(self.lowpass), (1 << spec.depth) - 1
-        self.planes = np.ascontiguousarray(IL.plane_shapes(h, w, spec.layout), dtype=np.int32)
-        self.rows = rows_in // 2 + 1                 # pairs of the carried frame and a batch's rows_in frames, the odd tail among them
-        self.woven = [torch.empty((self.rows, Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.offs = [torch.empty(self.rows * 2, dtype=torch.int64, device=dev) for _ in range(2)]
-        self.h_offs = [torch.empty((self.rows, 2), dtype=torch.int64).pin_memory() for _ in range(2)]
-        self.begin()
+        self.planes = np.ascontiguousarray(IL.plane_shapes(self.h, self.w, spec.layout), dtype=np.int32)
+        self.begin(None)
 
-    def begin(self):
+    def begin(self, yuv):
         self.open = None                             # (buffer set, row) of the one open frame
 
     def carry(self, i, src):
@@ -447,68 +497,60 @@ class Interlacer:
             raise RuntimeError('interlace: the open frame lies at row %d of the buffer set about to be written' % row)
         self.open = (i, 0)
 
-    def _launch(self, i, pairs, src, stream):
-        nc = len(pairs)
-        if nc > self.rows:
-            raise RuntimeError('interlace: %d woven payloads for %d payload rows' % (nc, self.rows))
-        if nc:
-            self.rn.interlace_woven += nc
-            host = self.h_offs[i][:nc]
-            host.numpy()[:] = [[a * self.Pb, b * self.Pb] for a, b in pairs]
-            od = self.offs[i][:nc * 2]
-            od.copy_(host.view(-1), non_blocking=True)
-            L.check(self.lib.demfi_payload_weave(src[i].data_ptr(), host.data_ptr(), od.data_ptr(), nc, self.planes.ctypes.data, len(self.planes),
-                                                 self.es, self.peak, self.q0, self.mode, self.woven[i].data_ptr(), self.Pb, stream.cuda_stream),
-                    'payload_weave')
-
-    def weave(self, i, counts, ends, src, stream):
-        """counts[w]: the progressive frames of window w, written into src[i] from row ``lead`` on; returns the woven payloads per window."""
-        pairs, woven, left = IL.close_pairs(0 if self.open is not None else None, counts, ends, self.lead)
+    def run(self, i, counts, batch, src, stream):
+        """counts[w]: the progressive frames of window w, written into src[i] from row ``lead`` on; batch[1]: it holds the clip's last window."""
+        pairs, woven, left = IL.close_pairs(0 if self.open is not None else None, counts, batch[1], self.lead)
         self.open = (i, left) if left is not None else None
-        self._launch(i, pairs, src, stream)
+        self._launch(i, [[a * self.Pb, b * self.Pb] for a, b in pairs], src, stream)
         return woven
 
     def flush(self, i, src, stream):
-        """After the last batch: the frame still open, if any, is woven with itself into woven[i]; returns the payloads (0 or 1)."""
         if self.open is None:
             return 0
         self.carry(i, src)
         self.open = None
-        self._launch(i, [(0, 0)], src, stream)
+        self._launch(i, [[0, 0]], src, stream)
         return 1
 
+    def _call(self, src, host, offs, n, dst, stream):
+        L.check(self.lib.demfi_payload_weave(src, host, offs, n, self.planes.ctypes.data, len(self.planes), self.es, self.peak, self.q0,
+                                             self.mode, dst, self.Pb, stream), 'payload_weave')
 
-class Requantizer:
+
+class Requantizer(Stage):
     """Written payloads at the working depth -> the output's (``demfi_amd.bitdepth``, ``spec.depths`` = (input, working, output depth, dither
-    mode) with output < working).  The last device stage: after a batch's payloads lie in the rows 0, 1, ... of ``src[i]`` (the gather's, the
-    mix's, the scaler's or the weave's), ``requant`` takes all of them down with ONE ``demfi_payload_requant`` launch on the compute stream
-    into ``out[i]``, buffers of the output's payload size, which are what crosses D2H: 16 -> 8 sends half the bytes.  ``field_rows``: the
-    payloads hold two fields (``spec.interlace``), so the dither's row is the row within its field.  Stateless per payload: which batch a
-    payload came with never shows, and the stage works on every rank.  The runner counts ``depth_requantised``.  The offsets are those of
-    consecutive rows, the same in every batch: one table, uploaded once."""
+    mode) with output < working).  The last device stage: ``demfi_payload_requant`` takes all of a batch's payloads down into buffers of the
+    output's payload size, which are what crosses D2H: 16 -> 8 sends half the bytes.  ``field_rows``: the payloads hold two fields
+    (``spec.interlace``), so the dither's row is the row within its field.  Stateless per payload: which batch a payload came with never
+    shows, and the stage works on every rank.  The runner counts ``depth_requantised``.  The offsets are those of consecutive rows, the same
+    in every batch: one table, uploaded once, that no batch rewrites."""
+    width, counter, too_many = 0, 'depth_requantised', 'requant: %d payloads for %d payload rows'
 
-    def __init__(self, runner, spec, rows, h, w, dev):
-        (_, self.d_work, self.d_out, dither), self.rn, self.lib, self.rows = spec.depths, runner, runner.lib, rows
+    def __init__(self, runner, spec, src, own, dev):
+        super().__init__(runner, spec, src, own, dev)
+        _, self.d_work, self.d_out, dither = spec.depths
         self.es_in, self.es = 2 if self.d_work > 8 else 1, 2 if self.d_out > 8 else 1
         self.dither, self.field_rows = int(dither == 'bayer'), int(spec.interlace is not None)
-        P = payload_size(h, w, spec.layout)
-        self.Pb_in, self.Pb = P * self.es_in, P * self.es                 # bytes of a payload before and behind
-        self.planes = np.ascontiguousarray(IL.plane_shapes(h, w, spec.layout), dtype=np.int32)
-        self.out = [torch.empty((rows, self.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.h_offs = np.arange(rows, dtype=np.int64) * self.Pb_in
+        self.planes = np.ascontiguousarray(IL.plane_shapes(self.h, self.w, spec.layout), dtype=np.int32)
+        self.h_offs = np.arange(self.rows, dtype=np.int64) * src.Pb
         self.offs = torch.from_numpy(self.h_offs).to(dev)
 
-    def requant(self, i, counts, src, full_range, stream):
-        """counts[w]: the written payloads of window w, which lie in src[i] from row 0 on; they are requantised into out[i] from row 0 on."""
-        m = sum(counts)
-        if m > self.rows:
-            raise RuntimeError('requant: %d payloads for %d payload rows' % (m, self.rows))
-        if m:
-            self.rn.depth_requantised += m
-            L.check(self.lib.demfi_payload_requant(src[i].data_ptr(), self.h_offs.ctypes.data, self.offs.data_ptr(), m, self.planes.ctypes.data,
-                                                   len(self.planes), self.es_in, self.es, self.d_work, self.d_out, int(full_range), self.dither,
-                                                   self.field_rows, self.out[i].data_ptr(), self.Pb, stream.cuda_stream), 'payload_requant')
+    def begin(self, yuv):
+        self.full_range = int(yuv.full_range)
+
+    def _table(self, i, offsets):
+        return self.h_offs.ctypes.data, self.offs.data_ptr()
+
+    def run(self, i, counts, batch, src, stream):
+        self._launch(i, range(sum(counts)), src, stream)
         return counts
+
+    def _call(self, src, host, offs, n, dst, stream):
+        L.check(self.lib.demfi_payload_requant(src, host, offs, n, self.planes.ctypes.data, len(self.planes), self.es_in, self.es, self.d_work,
+                                               self.d_out, self.full_range, self.dither, self.field_rows, dst, self.Pb, stream), 'payload_requant')
+
+
+STAGES = {'mix': Shutter, 'scale': Scaler, 'weave': Interlacer, 'requant': Requantizer}
 
 
 class TileGrid:
@@ -558,7 +600,10 @@ class FrameIO:
 class Y4mEdge:
     """Y4M payloads in; sink(k, payloads [c, P]) out, the c output frames window k owns in stream order.  ``spec``: the run's
     ``pipeline.EdgeSpec``; ``tiler``: None, a ``pipeline.Tiler`` (8-bit frames) or a ``TileGrid`` (16-bit).  ONE gather launch per batch
-    converts the outputs in comb[i] into yuv_out[i] in stream order; the payload buffers are uint8 tensors sized in bytes."""
+    converts the outputs in comb[i] into yuv_out[i] in stream order; the payload buffers are uint8 tensors sized in bytes.  ``stages``: the
+    ``Stage`` objects behind the gather in their order, sized by ``egress_layout`` and run one after the other on the compute stream, each on the
+    buffers of the one before it (``sources``); ``written``: the buffers of the last of them, or yuv_out, which ``d2h`` copies into the pinned
+    ``h_yuv``.  Without a stage no buffer, table or launch is added."""
 
     def __init__(self, runner, batch, slots, spec, tiler, h2d):
         self.rn, self.slots, self.spec = runner, slots, spec
@@ -579,33 +624,17 @@ class Y4mEdge:
         self.t = [torch.empty((runs_max * io.nt, nJ), dtype=torch.float32, device=dev) for _ in range(2)]
         self.sinks = [torch.empty((runs_max * io.nt, nJ, 32), dtype=torch.int64, device=dev) for _ in range(2)]
         self.offs = [torch.empty(nout, dtype=torch.int64, device=dev) for _ in range(2)]
-        # a shutter mixes the gathered (fine) payloads into written ones: those cross D2H, and yuv_out[i] gets its carry rows in front
-        # interlaced output weaves the progressive payloads (gathered, or mixed) in pairs: the woven ones cross D2H, and the buffer it reads gets
-        # its carry row in front
-        # resized output resamples the progressive payloads (gathered, or mixed) into buffers of the output size: the carry row of the weave
-        # then lies in front of those, the weave and the pinned staging buffers have the output's size, and only resized payloads cross D2H
-        front = Interlacer.lead if spec.interlace is not None else 0
-        scaled = spec.scale is not None and tuple(spec.scale[:2]) != (w, h)      # the run's own size: no stage, the bytes of a run without
-        sfront, front = (front, 0) if scaled else (0, front)
-        sh = self.shutter = Shutter(runner, spec, nout, batch, ing.Pb, ing.es, dev, front) if spec.shutter is not None else None
-        lead, nhost = (sh.lead, sh.rows) if sh is not None else (front, nout)
-        self.gather_lead = lead
-        self.yuv_out = [torch.empty((lead + nout, ing.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.written = sh.mixed if sh is not None else self.yuv_out
-        sc = self.scaler = Scaler(runner, spec, nhost, h, w, ing.es, dev, sfront) if scaled else None
-        oh, ow, oPb = (sc.h, sc.w, sc.Pb) if scaled else (h, w, ing.Pb)
-        if sc is not None:
-            self.unscaled, self.written = self.written, sc.scaled
-        il = self.interlacer = Interlacer(runner, spec, nhost, oh, ow, oPb, ing.es, dev) if spec.interlace is not None else None
-        if il is not None:
-            self.progressive, self.written, nhost = self.written, il.woven, il.rows
-        # an output depth below the working depth requantises what would be written, as the last device stage: only payloads of the
-        # output's sample size cross D2H
-        rq = self.requantizer = (Requantizer(runner, spec, nhost, oh, ow, dev) if spec.depths is not None and spec.depths[2] < spec.depths[1]
-                                 else None)
-        if rq is not None:
-            self.deep, self.written, oPb = self.written, rq.out, rq.Pb
-        self.h_yuv = [torch.empty((nhost, oPb), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        # the last buffer of the chain is what crosses D2H: only mixed, resized, woven payloads of the output's sample size leave the device
+        *bufs, host = egress_layout(spec, nout, batch, h, w)
+        self.lead = bufs[0].lead                     # the free rows in front of the gather
+        self.yuv_out = [torch.empty((self.lead + nout, ing.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.stages, self.sources, self.written = [], [], self.yuv_out       # sources[j]: the buffers stages[j] reads
+        for src, own in zip(bufs, bufs[1:]):
+            st = STAGES[own.name](runner, spec, src, own, dev)
+            self.stages.append(st)
+            self.sources.append(self.written)
+            self.written = st.out
+        self.h_yuv = [torch.empty(host, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.yuv = self.window_index = self.det = self.kept = self.gather = None
 
     def __getattr__(self, name):                     # J, tiler, in_place and, on a crop-run-stitch edge only, tcomb: the frame IO's
@@ -622,10 +651,8 @@ class Y4mEdge:
         """A run starts; returns the frames to make resident first: with scene cuts, frame k0 - 1 of a first window k0 >= 1."""
         ing, sc = self.ingest, self.scores
         self.yuv, self.window_index, self.det, ing.raw = yuv, window_index, None, {}
-        if self.shutter is not None:
-            self.shutter.begin()
-        if self.interlacer is not None:
-            self.interlacer.begin()
+        for st in self.stages:
+            st.begin(yuv)
         ing.to_bgr, self.gather, sad = yuv_calls(self.rn.lib, self.spec, ing.fh, ing.fw, yuv)
         if sc is None:
             return ()
@@ -641,8 +668,7 @@ class Y4mEdge:
     def uploaded(self, new, h2d):
         """After a batch's copies (h2d stream): its (frame, slot) pairs and the kept frames staged since become frame slots; then the SADs."""
         ing, probe = self.ingest, self.probe
-        ing.promote(new, h2d)                        # a working depth above the input's: first of all
-        new = ing._adaptive(new, h2d) if ing.adaptive else ing.bob(new, h2d)      # adaptive: the fields just rebuilt, not those uploaded
+        new = ing.rebuilt(new, h2d)
         if probe is not None:                        # the frames kept since the last batch were bobbed when they were staged
             new, probe.pending = probe.pending + list(new), []
         ing.to_frames(new, h2d)
@@ -657,30 +683,23 @@ class Y4mEdge:
         if self.kept is not None:
             self.kept.st_frames += st_frames
         self._run_windows(i, runs)
-        sh, sc, il, read = self.shutter, self.scaler, self.interlacer, [fr for fr, _, _ in runs]
-        if il is not None:
-            il.carry(i, self.progressive)
-        if sh is None:
-            counts = self._gather(i, outs, cur, self.gather_lead)
-        else:
-            sh.carry(i, self.yuv_out)
-            self._gather(i, outs, cur, sh.lead)
-            counts = sh.mix(i, fine, ends, self.yuv_out, cur)
-        if sc is not None:
-            counts = sc.scale(i, counts, self.unscaled, cur)
-        if il is not None:
-            counts = il.weave(i, counts, ends, self.progressive, cur)
-        if self.requantizer is not None:
-            counts = self.requantizer.requant(i, counts, self.deep, self.yuv.full_range, cur)
-        return counts, read
+        for st, src in zip(reversed(self.stages), reversed(self.sources)):   # the carries are independent copies: the last stage's goes first
+            st.carry(i, src)
+        counts = self._gather(i, outs, cur, self.lead)
+        for st, src in zip(self.stages, self.sources):
+            counts = st.run(i, counts, (fine, ends), src, cur)
+        return counts, [fr for fr, _, _ in runs]
 
     def flush(self, i, cur):
-        """After the last batch's ``run``: what is still to be written into buffer set i (None: nothing), for ``d2h`` and ``drain``."""
-        if self.interlacer is None or not self.interlacer.flush(i, self.progressive, cur):
-            return None
-        if self.requantizer is not None:
-            self.requantizer.requant(i, [1], self.deep, self.yuv.full_range, cur)
-        return [1]
+        """After the last batch's ``run``: what is still to be written into buffer set i (None: nothing), for ``d2h`` and ``drain``.  Once a
+        stage has flushed a payload, the stages behind it run on it (no plan goes with it: no stage that regroups may follow one that flushes)."""
+        counts = None
+        for st, src in zip(self.stages, self.sources):
+            if counts is not None:
+                counts = st.run(i, counts, None, src, cur)
+            elif st.flush(i, src, cur):
+                counts = [1]
+        return counts
 
     def _run_windows(self, i, runs):
         """Planned run w = (4 slots, instants, kinds) becomes the ``io.nt`` runner runs w * nt + j, which run its instants into ``io.dst[i]``;
@@ -735,7 +754,7 @@ class Y4mEdge:
     def drain(self, i, k0, counts, sink):
         pos = 0
         for j, c in enumerate(counts):
-            if c or (self.shutter is None and self.interlacer is None):  # a window that completed no written payload has nothing to hand out
+            if c or not any(st.regroups for st in self.stages):          # a window that completed no written payload has nothing to hand out
                 sink(k0 + j, self.h_yuv[i][pos:pos + c])
             pos += c
 

@@ -9,7 +9,7 @@ from demfi_amd import cadence as K
 from demfi_amd import retime as R
 from demfi_amd import scene as S
 from demfi_amd.pipeline import EdgeSpec, deint_conflict, residency_order
-from demfi_amd.y4m_edge import plan_batch
+from demfi_amd.y4m_edge import egress_layout, plan_batch
 
 
 # ---- EdgeSpec.of -----------------------------------------------------------------------------------------------------------------
@@ -192,3 +192,45 @@ def test_residency_order():
     assert [wi for wi, _ in got] == [None, None, 0, 0, 0, 0, 1, 1, 1, 1, None, None]
     assert list(residency_order((), wins, [])) == [(0, 6), (0, 7), (0, 5), (0, 8), (1, 7), (1, 8), (1, 6), (1, 9)]
     assert [idx for _, idx in residency_order((), wins, [3, 4, 10])] == [3, 4, 6, 7, 5, 8, 7, 8, 6, 9, 10]   # lookbehind, windows, lookahead
+
+
+# ---- egress_layout: the buffer rule of the stages behind the gather ----------------------------------------------------------------
+_G0, _G1 = ('gather', 0, 9, 10368, 48, 72), ('gather', 1, 9, 10368, 48, 72)
+_LAYOUTS = {        # (shutter, scale, interlace, requant) -> the buffers as (producer, free rows in front, rows, payload bytes, h, w), then the host's
+    (0, 0, 0, 0): [_G0, (9, 10368)],
+    (0, 0, 0, 1): [_G0, ('requant', 0, 9, 5184, 48, 72), (9, 5184)],
+    (0, 0, 1, 0): [_G1, ('weave', 0, 5, 10368, 48, 72), (5, 10368)],
+    (0, 0, 1, 1): [_G1, ('weave', 0, 5, 10368, 48, 72), ('requant', 0, 5, 5184, 48, 72), (5, 5184)],
+    (0, 1, 0, 0): [_G0, ('scale', 0, 9, 18432, 64, 96), (9, 18432)],
+    (0, 1, 0, 1): [_G0, ('scale', 0, 9, 18432, 64, 96), ('requant', 0, 9, 9216, 64, 96), (9, 9216)],
+    (0, 1, 1, 0): [_G0, ('scale', 1, 9, 18432, 64, 96), ('weave', 0, 5, 18432, 64, 96), (5, 18432)],
+    (0, 1, 1, 1): [_G0, ('scale', 1, 9, 18432, 64, 96), ('weave', 0, 5, 18432, 64, 96), ('requant', 0, 5, 9216, 64, 96), (5, 9216)],
+    (1, 0, 0, 0): [_G1, ('mix', 0, 8, 10368, 48, 72), (8, 10368)],
+    (1, 0, 0, 1): [_G1, ('mix', 0, 8, 10368, 48, 72), ('requant', 0, 8, 5184, 48, 72), (8, 5184)],
+    (1, 0, 1, 0): [_G1, ('mix', 1, 8, 10368, 48, 72), ('weave', 0, 5, 10368, 48, 72), (5, 10368)],
+    (1, 0, 1, 1): [_G1, ('mix', 1, 8, 10368, 48, 72), ('weave', 0, 5, 10368, 48, 72), ('requant', 0, 5, 5184, 48, 72), (5, 5184)],
+    (1, 1, 0, 0): [_G1, ('mix', 0, 8, 10368, 48, 72), ('scale', 0, 8, 18432, 64, 96), (8, 18432)],
+    (1, 1, 0, 1): [_G1, ('mix', 0, 8, 10368, 48, 72), ('scale', 0, 8, 18432, 64, 96), ('requant', 0, 8, 9216, 64, 96), (8, 9216)],
+    (1, 1, 1, 0): [_G1, ('mix', 0, 8, 10368, 48, 72), ('scale', 1, 8, 18432, 64, 96), ('weave', 0, 5, 18432, 64, 96), (5, 18432)],
+    (1, 1, 1, 1): [_G1, ('mix', 0, 8, 10368, 48, 72), ('scale', 1, 8, 18432, 64, 96), ('weave', 0, 5, 18432, 64, 96),
+                   ('requant', 0, 5, 9216, 64, 96), (5, 9216)],
+}
+
+
+def _egress_spec(sh, sc, il, rq, scale=(96, 64, 'lanczos3')):
+    return EdgeSpec(y4m=True, depth=10, shutter=(2, 4) if sh else None, scale=scale if sc else None,
+                    interlace=('t', 'linear') if il else None, depths=(10, 10, 8, 'bayer') if rq else None)
+
+
+@pytest.mark.parametrize('which', sorted(_LAYOUTS))
+def test_egress_layout_every_subset_of_the_stages(which):
+    """9 payloads a batch of 4 windows, 72x48 4:2:0 at a working depth of 10: 10368 bytes a payload, 18432 resized to 96x64, 9216 of those at
+    8 bits.  A buffer has its producer's rows plus its consumer's lead (shutter (2, 4): 1, weave: 1) in front; the host takes the last one's."""
+    assert egress_layout(_egress_spec(*which), 9, 4, 48, 72) == _LAYOUTS[which]
+
+
+def test_egress_layout_the_runs_own_size_builds_no_scaler():
+    for which in sorted(_LAYOUTS):
+        if which[1]:
+            same = egress_layout(_egress_spec(*which, scale=(72, 48, 'bicubic')), 9, 4, 48, 72)
+            assert same == _LAYOUTS[(which[0], 0) + which[2:]] and 'scale' not in [b[0] for b in same[:-1]]

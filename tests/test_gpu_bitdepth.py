@@ -24,6 +24,7 @@ from demfi_amd import interlace as IL                                           
 from demfi_amd import scene as S                                                     # noqa: E402
 from demfi_amd import y4m                                                            # noqa: E402
 from demfi_amd.video import VideoRunner                                              # noqa: E402
+from demfi_amd.y4m_edge import Requantizer                                           # noqa: E402
 from tests import test_gpu_dedup as D                                                # noqa: E402
 from tests import test_gpu_interlace as TI                                           # noqa: E402
 from tests import test_gpu_y4m_layouts as Y                                          # noqa: E402
@@ -306,7 +307,7 @@ def test_a_promotion_8_to_10(model16, clip8, tmp_path):
         assert (nw, nf) == (3, 7) and vr.last_depths == (8, 10, 10, None) and vr.last_depth_promoted == 6
     for cr in vr._runners.values():
         edge = cr.runner._pipeline.edge
-        assert edge.requantizer is None and edge.ingest.staged.shape[1] * 2 == edge.ingest.yuv_in.shape[1]     # H2D carries the input's bytes
+        assert not any(isinstance(st, Requantizer) for st in edge.stages) and edge.ingest.staged.shape[1] * 2 == edge.ingest.yuv_in.shape[1]     # H2D carries the input's bytes
 
 
 def test_a_promotion_8_to_12_422_full_range_and_a_rate(model16):
@@ -371,7 +372,7 @@ def test_b_demotion_16_to_10_and_the_d2h_size(model16):
     vr, got = _demoted(model16, data, 8, 'none', mfi=2, high_depth=True, layouts=True)
     for cr in vr._runners.values():
         edge = cr.runner._pipeline.edge
-        assert edge.requantizer is not None and edge.written is edge.requantizer.out and edge.ingest.staged is None
+        assert isinstance(edge.stages[-1], Requantizer) and edge.written is edge.stages[-1].out and edge.ingest.staged is None
         assert edge.h_yuv[0].shape[1] * 2 == edge.yuv_out[0].shape[1] == 2 * y4m.payload_size(48, 72, '422')     # 16 -> 8: half the bytes cross D2H
 
 
@@ -392,6 +393,19 @@ def test_b_demotion_behind_the_weave_takes_field_rows(model16):
     assert got != BD.requant_stream_np(plain, 8, 'bayer', field_rows=False)
     vr, got = _demoted(model16, D._repeat(data, [1, 2, 1, 1, 2, 1]), 8, mfi=2, interlace='bff', dedup=True, high_depth=True)
     assert vr.last_dups == [2, 6]
+
+
+def test_b_demotion_behind_the_whole_chain_at_every_batch_size(model16, clip10):
+    """gather -> mix -> scale -> weave -> requant in one run: the bytes are those of the run without ``out_depth`` requantised on the host,
+    whatever the batch size, and at batch 1 both carries ran; with ``--dedup`` the flush goes through resized buffers and the requantiser."""
+    kw = dict(fps=Fraction(60), shutter=360, scale=(96, 64), interlace='tff', high_depth=True)
+    vr, got = _demoted(model16, clip10, 8, batch=1, **kw)
+    assert vr.last_shutter_carried > 0 and vr.last_interlace_carried > 0
+    assert (_header(got).w, _header(got).h, _header(got).interlace) == (96, 64, 't')
+    for batch in (2, 4):
+        assert _run(model16, clip10, batch=batch, out_depth=8, **kw)[3] == got
+    vr, got = _demoted(model16, D._repeat(clip10, [1, 2, 1, 1, 2, 1]), 8, mfi=2, dedup=True, scale=(96, 64), interlace='bff', high_depth=True)
+    assert vr.last_dups == [2, 6] and (_header(got).w, _header(got).h, _header(got).interlace) == (96, 64, 'b')
 
 
 def test_b_demotion_with_a_crop_pads_with_exact_black_at_the_output_depth(model16):
@@ -441,7 +455,7 @@ def test_switches_that_resolve_to_the_input_depth_build_nothing(model16, clip8, 
         assert got == plain and vr.last_depths is None and (vr.last_depth_promoted, vr.last_depth_requantised) == (0, 0)
         for cr in vr._runners.values():
             edge = cr.runner._pipeline.edge
-            assert edge.requantizer is None and edge.ingest.staged is None and edge.written is edge.yuv_out and edge.spec.depths is None
+            assert not any(isinstance(st, Requantizer) for st in edge.stages) and edge.ingest.staged is None and edge.written is edge.yuv_out and edge.spec.depths is None
     plain10 = _run(model16, clip10, mfi=2, high_depth=True)[3]
     assert _run(model16, clip10, mfi=2, high_depth=True, work_depth=10, out_depth=10)[3] == plain10
 

@@ -24,6 +24,7 @@ from demfi_amd import retime as R                                               
 from demfi_amd import scene as S                                                     # noqa: E402
 from demfi_amd import y4m                                                            # noqa: E402
 from demfi_amd.video import VideoRunner                                              # noqa: E402
+from demfi_amd.y4m_edge import Interlacer                                            # noqa: E402
 from tests import test_gpu_dedup as D                                                # noqa: E402
 from tests import test_gpu_y4m_layouts as Y                                          # noqa: E402
 
@@ -439,12 +440,13 @@ def test_a_run_without_the_switch_builds_no_interlacer(model16, clip7):
     assert vr.last_interlace is None and vr.last_interlace_carried == 0
     for cr in vr._runners.values():
         edge = cr.runner._pipeline.edge
-        assert edge.interlacer is None and edge.written is edge.yuv_out and cr.runner.interlace_woven == 0
+        assert not any(isinstance(st, Interlacer) for st in edge.stages) and edge.written is edge.yuv_out and cr.runner.interlace_woven == 0
     vr, nw, nf, got = _run(model16, clip7, mfi=2, interlace='tff')
     for cr in vr._runners.values():
         edge = cr.runner._pipeline.edge
-        assert edge.interlacer is not None and edge.written is edge.interlacer.woven and cr.runner.interlace_woven == nf == 5
-        assert edge.h_yuv[0].shape[0] == edge.interlacer.rows < edge.yuv_out[0].shape[0]      # the pinned buffers hold woven payloads
+        (interlacer,) = [st for st in edge.stages if isinstance(st, Interlacer)]
+        assert edge.written is interlacer.out and cr.runner.interlace_woven == nf == 5
+        assert edge.h_yuv[0].shape[0] == interlacer.rows < edge.yuv_out[0].shape[0]      # the pinned buffers hold woven payloads
 
 
 def test_more_than_one_rank_is_refused_before_anything_runs(model16, clip7, tmp_path):

@@ -23,6 +23,7 @@ from demfi_amd import scale as SC                                               
 from demfi_amd import scene as S                                                     # noqa: E402
 from demfi_amd import y4m                                                            # noqa: E402
 from demfi_amd.video import VideoRunner                                              # noqa: E402
+from demfi_amd.y4m_edge import Scaler                                                # noqa: E402
 from tests import test_gpu_dedup as D                                                # noqa: E402
 from tests import test_gpu_interlace as TI                                           # noqa: E402
 from tests import test_gpu_y4m_layouts as Y                                          # noqa: E402
@@ -367,18 +368,19 @@ def test_the_run_s_own_size_builds_no_scaler(model16, clip7):
     plain_vr, nw, nf, plain = _run(model16, clip7, mfi=2)
     for cr in plain_vr._runners.values():
         edge = cr.runner._pipeline.edge
-        assert edge.scaler is None and edge.written is edge.yuv_out and cr.runner.scale_payloads == 0
+        assert not any(isinstance(st, Scaler) for st in edge.stages) and edge.written is edge.yuv_out and cr.runner.scale_payloads == 0
     assert plain_vr.last_scale is None and plain_vr.last_scale_payloads == 0
     vr, nw, nf, got = _run(model16, clip7, mfi=2, scale=(96, 64), scale_filter='bicubic')
     assert got == plain and vr.last_scale is None and vr.last_scale_payloads == 0
     for cr in vr._runners.values():
         edge = cr.runner._pipeline.edge
-        assert edge.scaler is None and edge.written is edge.yuv_out and cr.runner.scale_payloads == 0
+        assert not any(isinstance(st, Scaler) for st in edge.stages) and edge.written is edge.yuv_out and cr.runner.scale_payloads == 0
     vr, nw, nf, got = _run(model16, clip7, mfi=2, scale=SHRINK)
     for cr in vr._runners.values():
         edge = cr.runner._pipeline.edge
-        assert edge.scaler is not None and edge.written is edge.scaler.scaled and cr.runner.scale_payloads == nf == 9
-        assert edge.h_yuv[0].shape[1] == edge.scaler.Pb == y4m.payload_size(48, 72) < edge.yuv_out[0].shape[1]   # only resized payloads cross D2H
+        (scaler,) = [st for st in edge.stages if isinstance(st, Scaler)]
+        assert edge.written is scaler.out and cr.runner.scale_payloads == nf == 9
+        assert edge.h_yuv[0].shape[1] == scaler.Pb == y4m.payload_size(48, 72) < edge.yuv_out[0].shape[1]   # only resized payloads cross D2H
 
 
 def test_refusals_before_anything_runs(model16, clip7):

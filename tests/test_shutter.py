@@ -376,3 +376,42 @@ def test_video_runner_refuses_before_a_library_is_loaded(tmp_path):
     import io
     with pytest.raises(ValueError, match='more than 64'):
         far.run_stream(io.BytesIO(src.read_bytes()), io.BytesIO())
+
+
+def test_every_one_rank_switch_is_refused_with_two_ranks_before_anything_is_allocated(tmp_path):
+    from demfi_amd import video
+    src = tmp_path / 'in.y4m'
+    src.write_bytes(b'YUV4MPEG2 W96 H64 F24:1 Ip C420jpeg\n' + (b'FRAME\n' + bytes(96 * 64 * 3 // 2)) * 5)
+    assert list(video.ONE_RANK) == ['dedup', 'ivtc', 'shutter', 'interlace']
+    for kw, what in ((dict(dedup=True), 'dedup with 2 ranks.*one rank'), (dict(ivtc=True), 'ivtc with 2 ranks.*one rank'),
+                     (dict(shutter=180), 'shutter with 2 ranks'), (dict(interlace='tff'), 'interlace with 2 ranks')):
+        with pytest.raises(ValueError, match=what):
+            video.VideoRunner(None, mfi=2, **kw).run_file(str(src), str(tmp_path / 'out.y4m'), world=2, rank=1)     # no model: nothing ran
+        with pytest.raises(ValueError, match=what):
+            video.check_one_rank(2, **kw)
+        video.check_one_rank(1, **kw)
+        video.check_one_rank(2, **{k: None for k in kw})
+    video.check_one_rank(2, dedup=False, ivtc=False)
+    assert not (tmp_path / 'out.y4m').exists()
+
+
+def test_the_counter_table_names_counters_the_runner_has_and_attributes_the_video_runner_has():
+    import ast
+    import inspect
+    import textwrap
+
+    from demfi_amd import video
+    from demfi_amd.runner import WindowRunner
+    init = ast.parse(textwrap.dedent(inspect.getsource(WindowRunner.__init__)))
+    zeroed = {t.attr for node in ast.walk(init) if isinstance(node, ast.Assign) and isinstance(node.value, ast.Constant) and node.value.value == 0
+              for t in node.targets if isinstance(t, ast.Attribute) and isinstance(t.value, ast.Name) and t.value.id == 'self'}
+    assert set(video.COUNTERS) <= zeroed and len(video.COUNTERS) == 9
+    vr = video.VideoRunner(None)
+    kept = [attr for attr in video.COUNTERS.values() if attr is not None]
+    assert len(kept) == len(set(kept)) == 6 and all(attr.startswith('last_') and getattr(vr, attr) == 0 for attr in kept)
+    assert vr.last_instants == (0, 0) and vr.last_st_frames == 0
+    vr = video.VideoRunner(None, mfi=2, shutter=180, interlace='bff')
+    vr._counted(SimpleNamespace(w=96, h=64, layout='420'), {name: i + 1 for i, name in enumerate(video.COUNTERS)}, [3], 7)
+    assert vr.last_instants == (1, 2) and vr.last_st_frames == 3 and vr.last_cuts == [3] and vr.last_cut_windows == 4
+    assert (vr.last_shutter_carried, vr.last_interlace_carried, vr.last_scale_payloads, vr.last_depth_promoted, vr.last_depth_requantised) == (5, 6, 7, 8, 9)
+    assert (vr.last_shutter, vr.last_interlace, vr.last_scale) == ((4, 8), 'b', None)
