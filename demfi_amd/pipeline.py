@@ -48,18 +48,22 @@ class EdgeSpec(_EdgeFields):
     synthesized shutter (``demfi_amd.shutter``); ``interlace``: None or (field order 't' / 'b', low-pass mode) of interlaced output
     (``demfi_amd.interlace``); ``scale``: None or (w, h, filter) of resized output (``demfi_amd.scale``); ``depths``: None or (input depth,
     working depth, output depth, dither mode or None) of a run that changes the bit depth (``demfi_amd.bitdepth``): ``depth`` and ``hi`` then
-    mean the WORKING depth, the payloads come in at the input's and leave at the output's; three equal depths are None.  Hashable: (batch,
-    spec) is what a cached ``ClipPipeline`` can be reused for.
-    ``shutter``, ``interlace``, ``scale`` and ``depths`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
+    mean the WORKING depth, the payloads come in at the input's and leave at the output's; three equal depths are None;
+    ``shutter_window``: None (the box) or 'triangle', the weights of a shutter's mix (``shutter.window_weights``; only with ``shutter``).
+    Hashable: (batch, spec) is what a cached ``ClipPipeline`` can be reused for.
+    ``shutter``, ``interlace``, ``scale``, ``depths`` and ``shutter_window`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
     without them is, item for item, the record it was before there were any, and one with any of them equals no plain tuple.  What the namedtuple makes
     from its items alone does not know them: ``_make``, ``_asdict`` and pickling drop them; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
     shutter = None
     interlace = None
     scale = None
     depths = None
+    shutter_window = None
 
-    def __new__(cls, *args, shutter=None, interlace=None, scale=None, depths=None, **kw):
+    def __new__(cls, *args, shutter=None, interlace=None, scale=None, depths=None, shutter_window=None, **kw):
         self = super().__new__(cls, *args, **kw)
+        if shutter_window not in (None, 'box'):      # the box is the spec without the field
+            self.shutter_window = shutter_window
         if shutter is not None:
             self.shutter = (int(shutter[0]), int(shutter[1]))
         if interlace is not None:
@@ -72,13 +76,13 @@ class EdgeSpec(_EdgeFields):
 
     def _replace(self, **kw):
         shutter, interlace, scale = kw.pop('shutter', self.shutter), kw.pop('interlace', self.interlace), kw.pop('scale', self.scale)
-        depths = kw.pop('depths', self.depths)
-        return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace, scale=scale, depths=depths)
+        depths, window = kw.pop('depths', self.depths), kw.pop('shutter_window', self.shutter_window)
+        return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace, scale=scale, depths=depths, shutter_window=window)
 
     def __eq__(self, other):
         return (tuple.__eq__(self, other) is True and self.shutter == getattr(other, 'shutter', None)
                 and self.interlace == getattr(other, 'interlace', None) and self.scale == getattr(other, 'scale', None)
-                and self.depths == getattr(other, 'depths', None))
+                and self.depths == getattr(other, 'depths', None) and self.shutter_window == getattr(other, 'shutter_window', None))
 
     def __ne__(self, other):
         return not self == other
@@ -86,12 +90,14 @@ class EdgeSpec(_EdgeFields):
     def __hash__(self):
         key = (tuple(self), self.shutter) if self.interlace is None else (tuple(self), self.shutter, self.interlace)
         key = key if self.scale is None else key + ('scale', self.scale)
-        return hash(key if self.depths is None else key + ('depths', self.depths))
+        key = key if self.depths is None else key + ('depths', self.depths)
+        return hash(key if self.shutter_window is None else key + ('shutter_window', self.shutter_window))
 
     def __repr__(self):
         return super().__repr__()[:-1] + ', shutter=%r%s%s)' % (self.shutter, ', interlace=%r' % (self.interlace,) if self.interlace is not None else '',
                                                                (', scale=%r' % (self.scale,) if self.scale is not None else '')
-                                                               + (', depths=%r' % (self.depths,) if self.depths is not None else ''))
+                                                               + (', depths=%r' % (self.depths,) if self.depths is not None else '')
+                                                               + (', shutter_window=%r' % self.shutter_window if self.shutter_window is not None else ''))
 
     @classmethod
     def of(cls, yuv):
@@ -100,7 +106,8 @@ class EdgeSpec(_EdgeFields):
         return cls(yuv is not None, getattr(yuv, 'scene_cut', None) is not None, bool(getattr(yuv, 'full_length', False)), int(getattr(yuv, 'depth', 8)),
                    getattr(yuv, 'layout', '420'), tuple(dedup) if dedup is not None else None, fields,
                    getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob', shutter=getattr(yuv, 'shutter', None),
-                   interlace=getattr(yuv, 'interlace', None), scale=getattr(yuv, 'scale', None), depths=getattr(yuv, 'depths', None))
+                   interlace=getattr(yuv, 'interlace', None), scale=getattr(yuv, 'scale', None), depths=getattr(yuv, 'depths', None),
+                   shutter_window=getattr(yuv, 'shutter_window', None))
 
     hi = property(lambda self: self.depth > 8, doc='16-bit frames: the samples of a stream above 8 bits')
 
@@ -108,7 +115,7 @@ class EdgeSpec(_EdgeFields):
         """Every rule about what goes together, before anything is allocated, for a run on a ``retimed`` runner (built with a ratio)."""
         other, edge_only = self.deint_mode != 'bob', self.hi or self.dedup is not None or self.fields is not None
         deint = deint_conflict(self.deint_mode, self.fields is not None, self.dedup is not None)
-        sh, il, sc, dp = self.shutter, self.interlace, self.scale, self.depths
+        sh, il, sc, dp, win = self.shutter, self.interlace, self.scale, self.depths, self.shutter_window
         for bad, what in ((self.fields not in (None, 't', 'b'), "fields must be None, 't' or 'b', got %r" % (self.fields,)),
                           (deint, 'deint_mode %r with fields=%r, dedup=%r' % (self.deint_mode, self.fields, self.dedup)),
                           (edge_only and not self.y4m, '16-bit frames, repeated frames and fields are those of the Y4M edge (yuv=...) only'),
@@ -124,6 +131,8 @@ class EdgeSpec(_EdgeFields):
                            'a shutter needs the Y4M edge on a retimed runner, built with the fine ratio r D'),
                           (sh is not None and self.dedup is not None,
                            'a shutter does not go with repeated frames (dedup): its groups are laid over the regular fine timeline'),
+                          (win is not None and (win not in SH.WINDOWS or sh is None),
+                           'shutter_window must be None or one of %s, and only with a shutter, got %r with shutter=%r' % (SH.WINDOWS, win, sh)),
                           (il is not None and not (len(il) == 2 and il[0] in ('t', 'b') and il[1] in IL.LOWPASS),
                            "interlace must be None or (field order 't' / 'b', low-pass mode of %s), got %r" % (IL.LOWPASS, il)),
                           (il is not None and not (retimed and self.y4m), 'interlaced output needs the Y4M edge on a retimed runner'),

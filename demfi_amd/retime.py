@@ -1,4 +1,5 @@
-"""Output frame rate F_out for any rational ratio r = F_out / F_in >= 1 of the Y4M video path (``python -m demfi_amd.video --fps``).
+"""Output frame rate F_out for any rational ratio r = F_out / F_in > 0 of the Y4M video path (``python -m demfi_amd.video --fps``;
+r < 1, an output rate below the input's, with ``--downconvert``).
 
 Pure Python over ``fractions.Fraction``.  Input frames are numbered 0 .. n-1 and window k is (B-1, B0, B1, B2) = (k, k+1, k+2,
 k+3).  Output frame i sits at tau_i = 1 + i / r, in input frames; the output holds every i with tau_i <= n - 2, so
@@ -7,9 +8,10 @@ N_out = floor((n-3) r) + 1 for n >= 4.  Output frame i is
   * S1 of the last window when tau_i = n - 2,
   * otherwise St of window k = floor(tau_i) - 1 at t = float32(tau_i - floor(tau_i)) = float32((i q - k p) / p) for r = p / q,
     rounded once from the exact rational.
-Window k owns the output indices ceil(k r) .. ceil((k+1) r) - 1 (at least one, as r >= 1), plus S1 when it is the last window
-and (n-3) r is an integer.  It runs the instants T_k: the distinct St t values of its outputs in increasing order, or the
-single instant t = 1/2 when it has none (its only output is S0 or S1).  S0 and S1 come from the window's first instant.
+Window k owns the output indices ceil(k r) .. ceil((k+1) r) - 1 (at least one when r >= 1; possibly none when r < 1: at most
+ceil(r) in any case), plus S1 when it is the last window and (n-3) r is an integer.  It runs the instants T_k: the distinct St t
+values of its outputs in increasing order, or the single instant t = 1/2 when it has outputs but no St among them (S0 or S1
+only).  S0 and S1 come from the window's first instant.  A window that owns no output runs nothing: T_k is empty.
 
 For r = M this is exactly the x M stream of ``y4m``: ``n_output_frames`` / ``output_index`` / ``output_header`` and the t
 values of ``harness.t_schedule(M)``.  Everything about window k follows from k and r alone, so a stream is scheduled as it
@@ -53,12 +55,14 @@ def parse_fps(text):
 MAX_RATIO = 64
 
 
-def ratio(fps_in, fps_out):
-    """r = F_out / F_in (reduced); ValueError below 1 (dropping frames is not offered) and above ``MAX_RATIO`` (a window keeps
-    ceil(r) + 2 frame slots on the GPU)."""
+def ratio(fps_in, fps_out, down=False):
+    """r = F_out / F_in (reduced); ValueError below 1 (unless ``down``: then below 1 / ``MAX_RATIO``) and above ``MAX_RATIO`` (a
+    window keeps ceil(r) + 2 frame slots on the GPU)."""
     r = Fraction(fps_out) / Fraction(fps_in)
-    if r < 1:
+    if r < 1 and not down:
         raise ValueError('output frame rate %s is below the input rate %s: only F_out >= F_in is supported' % (fps_out, fps_in))
+    if r * MAX_RATIO < 1:
+        raise ValueError('output frame rate %s is less than 1/%d of the input rate %s' % (fps_out, MAX_RATIO, fps_in))
     if r > MAX_RATIO:
         raise ValueError('output frame rate %s is more than %d times the input rate %s' % (fps_out, MAX_RATIO, fps_in))
     return r
@@ -128,23 +132,25 @@ def window_outputs(k, r, last=False, full_length=False):
     return out
 
 
-def instants(k, r, full_length=False):
-    """T_k: the float32 t values window k runs, in increasing order (t = 1/2 alone when it has no St output)."""
-    ts = sorted({t for _, kind, t in window_outputs(k, r, full_length=full_length) if kind == ST})
-    return ts or [0.5]
+def instants(k, r, full_length=False, last=False):
+    """T_k: the float32 t values window k runs, in increasing order: t = 1/2 alone when it has outputs but no St among them, none
+    when it owns no output (r < 1 only; ``last``: the S1 and its hold count as the last window's)."""
+    outs = window_outputs(k, r, last, full_length)
+    ts = sorted({t for _, kind, t in outs if kind == ST})
+    return ts or ([0.5] if outs or Fraction(r) >= 1 else [])
 
 
 def window_plan(k, r, last=False, full_length=False):
     """(T_k, [(output index, kind, instant index)]): window k's instants and, per output in stream order, which instant's St
     it is (S0 / S1: instant 0, the window's first)."""
     outs = window_outputs(k, r, last, full_length)
-    ts = instants(k, r, full_length)
+    ts = instants(k, r, full_length, last)
     pos = {t: j for j, t in enumerate(ts)}
     return ts, [(i, kind, pos[t] if kind == ST else 0) for i, kind, t in outs]
 
 
 def max_instants(r):
-    """Upper bound of |T_k| over all windows: ceil(r) (a window owns at most ceil(r) outputs)."""
+    """Upper bound of |T_k| over all windows: ceil(r) (a window owns at most ceil(r) outputs; 1 for r < 1)."""
     return math.ceil(Fraction(r))
 
 
@@ -166,7 +172,7 @@ SCAN_WINDOWS = 1000
 
 
 def _period_counts(r):
-    """|T_k| of the windows of one period (at most ``SCAN_WINDOWS`` of them)."""
+    """|T_k| of the windows of one period (at most ``SCAN_WINDOWS`` of them); 0 for a window that owns no output (r < 1)."""
     r = Fraction(r)
     return [len(instants(k, r)) for k in range(min(r.denominator, SCAN_WINDOWS))]
 

@@ -116,7 +116,7 @@ class WindowRunner:
         values are taken as given (n_ctx must divide M-1 for the batched plan; the workspace must fit or engine creation
         fails loudly).  None = default: ``choose_config``.  The chosen values and how they were chosen are exposed as
         ``self.n_ctx`` / ``self.n_trunk`` / ``self.config`` and printed by bench.py.
-        retime: output / input frame rate ratio r >= 1 (a Fraction) of the Y4M edge of ``run_clip_u8`` in place of x M: window k
+        retime: output / input frame rate ratio r in 1/64 .. 64 (a Fraction) of the Y4M edge of ``run_clip_u8`` in place of x M: window k
         runs the instants of ``retime.window_plan`` (``mfi`` is not used).  An explicit n_ctx is taken as given; the default is
         ``retime.default_n_ctx`` over the sizes whose workspace fits the GPU.  ``instants_run`` / ``instants_padded`` count the
         time instants run and the padded per-t slots of short batched chunks.  instant_counts: the instants per window, over one period,
@@ -136,8 +136,8 @@ class WindowRunner:
         if retime is not None and not isinstance(retime, (int, Fraction)):
             raise TypeError('WindowRunner: retime must be an int or a Fraction, got %r' % (retime,))
         self.retime = Fraction(retime) if retime is not None else None
-        if self.retime is not None and not 1 <= self.retime <= R.MAX_RATIO:
-            raise ValueError('WindowRunner: retime ratio %s outside 1 .. %d' % (self.retime, R.MAX_RATIO))
+        if self.retime is not None and not Fraction(1, R.MAX_RATIO) <= self.retime <= R.MAX_RATIO:
+            raise ValueError('WindowRunner: retime ratio %s outside 1/%d .. %d' % (self.retime, R.MAX_RATIO, R.MAX_RATIO))
         self.lib = L.load()
         eng = model._engines.get((H, W, model.path_dtype))     # the plain slot only: never forward()'s batch engine
         self.config = choose_config(
@@ -169,6 +169,7 @@ class WindowRunner:
         self.instants_run = 0                        # time instants run (padded slots not counted)
         self.instants_padded = 0                     # per-t slots of short batched chunks that ran a repeated t and wrote nothing
         self.cut_windows = 0                         # windows run as scene-cut windows (two runs, no interpolation)
+        self.windows_skipped = 0                     # r < 1: windows of the Y4M edge that own no output and ran nothing
         self.shutter_mixed = self.shutter_carried = 0    # a shutter's fine frames mixed / samples carried between batches (``y4m_edge.Shutter``)
         self.interlace_woven = self.interlace_carried = 0    # interlaced output: payloads woven / frames carried between batches (``y4m_edge.Interlacer``)
         self.scale_payloads = 0                      # resized output: payloads resampled (``y4m_edge.Scaler``)

@@ -153,10 +153,12 @@ def window_runs(k, r, last, is_cut, full_length=False):
     """What window k runs for ratio r (``--mfi M`` is r = M): (runs, outs).  runs = [((B-1, B0, B1, B2), instants)];
     outs = [(output index, run, kind, instant index)] in stream order -- kind S0 / St / S1 of that run, as in
     ``retime.window_plan``.  The outputs are those of ``retime.window_outputs(k, r, last, full_length)``; on the full-length
-    timeline ``is_cut`` must hold the sentinels (``with_sentinels``)."""
+    timeline ``is_cut`` must hold the sentinels (``with_sentinels``).  With r < 1 a window may own no output, or a cut window outputs
+    on one side only: a run without an output is not returned (a cut window's right outputs keep the kind S1, whatever their run's
+    number); with r >= 1 a cut window is always its two runs."""
     if k < -1 or not is_cut_window(k, is_cut):
         ts, outs = R.window_plan(k, r, last, full_length)
-        return [(clip_tuple(k, is_cut), ts)], [(i, 0, kind, j) for i, kind, j in outs]
+        return ([(clip_tuple(k, is_cut), ts)] if ts else []), [(i, 0, kind, j) for i, kind, j in outs]
     r = Fraction(r)
     left, right = cut_runs(k, is_cut)
     sh = 1 if full_length else 0
@@ -167,7 +169,11 @@ def window_runs(k, r, last, is_cut, full_length=False):
             outs.append((i, 0, R.S0, 0))
         else:
             outs.append((i, 1, R.S1, 0))
-    return [(left, [0.5]), (right, [0.5])], outs
+    runs = [(left, [0.5]), (right, [0.5])]
+    if r < 1:                                        # the side without an output does not run
+        used = sorted({run for _, run, _, _ in outs})
+        runs, outs = [runs[run] for run in used], [(i, used.index(run), kind, j) for i, run, kind, j in outs]
+    return runs, outs
 
 
 def runner_order(tup):

@@ -1,4 +1,4 @@
-"""Video streams in, video streams out: x M interpolation of a YUV4MPEG2 (Y4M) stream, or retiming to any higher frame rate.
+"""Video streams in, video streams out: x M interpolation of a YUV4MPEG2 (Y4M) stream, or retiming to any other frame rate.
 
     ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe - | python -m demfi_amd.video - - --mfi 8 | ffmpeg -f yuv4mpegpipe -i - out.mp4
     ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe - | python -m demfi_amd.video - - --fps 60000/1001 | ffmpeg -f yuv4mpegpipe -i - out.mp4
@@ -8,7 +8,13 @@ The frames are those of the folder path (``python -m demfi_amd.clip``) for the s
 then St for t = 1/M .. (M-1)/M; after the last window its S1.  n input frames give (n-3)*M + 1 output frames: the first and
 the last input frame have no output of their own, as in the reference.  ``--fps F_out`` (an exact fraction, F_out >= F_in) puts
 output frame i at input time 1 + i * F_in / F_out instead and runs only the time instants those frames need
-(``demfi_amd.retime``); ``--fps M*F_in`` gives the bytes of ``--mfi M``.  ``--full-length`` covers the input's whole timeline
+(``demfi_amd.retime``); ``--fps M*F_in`` gives the bytes of ``--mfi M``.  ``--downconvert`` lets F_out lie below F_in, down to 1/64 of
+it (60p -> 25p; behind ``--deinterlace`` below the field rate, so that ``--deinterlace --downconvert --fps 50 --interlace tff`` is
+59.94i -> 50i, header ``F25:1 It``; behind ``--ivtc`` below the film rate): the same timeline with the output frames further apart.
+Window k owns the outputs ceil(k r) .. ceil((k+1) r) - 1, possibly none; a window that owns none runs no instant and launches nothing
+of the network (``last_windows_skipped``), though its frames are uploaded as ever, once each, for the scene scores.  Every switch below
+works with it except ``--dedup``, which is refused once the header is known; with F_out >= F_in it changes nothing.  Each written frame
+then stands for more than one input frame period, so ``--shutter`` belongs with it.  ``--full-length`` covers the input's whole timeline
 instead: output frame i sits at input time i * F_in / F_out, so n frames give n*M (ceil(n * F_out / F_in)) output frames that
 stay aligned with the input's audio; the clip's ends clamp the windows next to them like scene cuts and the last input frame
 is held to the end.
@@ -96,11 +102,16 @@ the written stream has the header, the length and the timing of a run without th
 ``shutter.filter_plan`` leaves every window only the instants its samples need; behind the batch's gather ONE launch
 (csrc/shutter.hip ``demfi_payload_mix``, defined by ``shutter.mix_np``: (2 sum + k) // (2 k) of the stored samples, round half up, the
 payload one flat array) mixes every group whose last sample has arrived into the buffer that crosses D2H, and the samples of the group
-still open carry over to the next batch on the device, so the bytes do not depend on the batch size.  Works with every switch above
+still open carry over to the next batch on the device, so the bytes do not depend on the batch size.  ``--shutter-window box|triangle``
+(default ``box``; an error without ``--shutter``) weighs the samples: triangle gives sample j the weight min(j + 1, S - j), and a group
+mixes to (2 sum w x + W) // (2 W) with W the sum of the weights it keeps (csrc/shutter.hip ``demfi_payload_mix_w``, defined by
+``shutter.mix_np(..., weights=...)``; ONE launch as for the box).  With ``--downconvert`` the fine ratio r D may lie below D and below 1:
+a window then brings fewer than D fine frames, or none.  Works with every switch above
 (the stage sits behind whole payloads; run behind each of them on the GPU except ``--tile-high-depth``, whose two halves are) except
 ``--dedup``; one rank.  Not offered: linear-light mixing (the average is taken over the
-gamma-encoded samples), weighted windows (triangle, gaussian), an exposure centred on the frame time, ``--dedup``, several ranks,
-F_out < F_in, ``demfi_amd.clip``.  Without the switch no buffer, launch or stream is added and every byte stays the same.
+gamma-encoded samples), gaussian or free weights, an exposure centred on the frame time, ``--dedup`` (also with ``--downconvert`` alone
+below the input rate), several ranks, ``demfi_amd.clip``.  Without the switch no buffer, launch or stream is added and every byte stays
+the same.
 
 ``--interlace tff|bff`` with ``--interlace-lowpass off|linear|complex`` (default ``linear``) writes interlaced output
 (``demfi_amd.interlace``): frames 2q and 2q + 1 of the progressive stream a run without the switch writes (with ``--shutter``: its mixed
@@ -193,12 +204,14 @@ class YuvEdge:
     (w, h) or (w, h, filter) of resized output (``demfi_amd.scale``; ``scale_filter`` names the filter of a pair, None: 'lanczos3'): the
     payloads handed out have that size.  ``depths``: None, or (input depth, working depth, output depth, dither mode or None) of
     ``bitdepth.resolve``: the payloads handed in have the input's depth, ``depth`` is then the WORKING depth, and the payloads handed out
-    have the output's."""
+    have the output's.  ``shutter_window``: None ('box') or 'triangle', the weights of the shutter's mix (``shutter.window_weights``); an
+    error without ``shutter``."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
                  fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None,
-                 depths=None):
+                 depths=None, shutter_window=None):
         self.dedup, self.shutter = dedup, shutter
+        self.shutter_window = check_shutter_window(shutter, shutter_window)
         self.depths = None if BD.is_noop(depths) else tuple(depths)
         if self.depths is not None and self.depths[1] != depth:
             raise ValueError('YuvEdge: depths=%r with depth=%r: depth is the working depth' % (self.depths, depth))
@@ -264,6 +277,16 @@ def check_shutter(shutter, samples=None, dedup=None, world=1):
     return sd
 
 
+def check_shutter_window(shutter, window=None):
+    """The shutter's window checked: 'box' or 'triangle' (``shutter.WINDOWS``; None: 'box'), or None without a shutter.  ``window`` says how
+    ``shutter`` works, so it is an error without it."""
+    if shutter is None:
+        if window is not None:
+            raise ValueError('--shutter-window (shutter_window) says how --shutter works: give --shutter ANGLE with it')
+        return None
+    return SH.check_window(window)
+
+
 def check_interlace(interlace, lowpass=None, world=1):
     """The interlace switches checked: None, or (field order 't' / 'b', low-pass mode).  ``lowpass`` (None: 'linear') says how ``interlace``
     works, so it is an error without it; interlaced output runs on one rank."""
@@ -323,8 +346,8 @@ def check_deinterlace_mode(deinterlace, mode, dedup):
 
 
 class VideoRunner:
-    """x M interpolation (``mfi``, default 8) or retiming to the output frame rate ``fps`` (a Fraction >= the input's rate) of
-    Y4M input on this rank's GPU; give one of the two.  ``matrix``: 'auto' (BT.709 when H >= 720, else BT.601), 'bt601'
+    """x M interpolation (``mfi``, default 8) or retiming to the output frame rate ``fps`` (a Fraction >= the input's rate; with ``down``
+    at least 1/64 of it) of Y4M input on this rank's GPU; give one of the two.  ``matrix``: 'auto' (BT.709 when H >= 720, else BT.601), 'bt601'
     or 'bt709'; the output uses the input's matrix and range, so an ffmpeg round trip keeps the colours.  ``scene_cut``: None
     (default) or the threshold T in (0, 100] of scene-cut detection: no window interpolates across a cut (``demfi_amd.scene``);
     the output's timing is unchanged.  ``full_length``: the output covers the input's whole timeline (``retime``): output
@@ -401,7 +424,13 @@ class VideoRunner:
     refused here.  An input above 8 bits still needs ``high_depth``; with ``tile`` a working depth above 8 needs ``tile_high_depth``.  Any
     number of ranks.  After a run ``last_depth`` = the depth written, ``last_depths`` = (input, working, output depth, dither mode or None),
     or None when nothing changed, ``last_depth_promoted`` / ``last_depth_requantised`` = the payloads that went through the two stages.
-    Depths that resolve to the input's add no buffer, launch or stream and every byte stays the same."""
+    Depths that resolve to the input's add no buffer, launch or stream and every byte stays the same.  ``down``: False (default) or True:
+    ``fps`` may lie below the input's rate (behind ``deinterlace`` below the field rate, behind ``ivtc`` below the film rate), r = F_out /
+    F_in in 1/64 .. 1 (``retime.ratio(..., down=True)``).  The timeline is ``retime``'s; a window that owns no output runs nothing and
+    ``last_windows_skipped`` counts those of the last run.  Not with ``dedup`` below the input rate (refused once the header is known);
+    with ``fps`` at or above the input's rate nothing changes.  ``shutter_window``: None (the default, 'box'), 'box' or 'triangle', the
+    weights of the shutter's samples (``shutter.window_weights``); given without ``shutter`` it is an error.  After a run
+    ``last_shutter_window`` = 'box', 'triangle' or None without a shutter."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
@@ -409,13 +438,16 @@ class VideoRunner:
                  ivtc_combpel=TC.DEFAULT_COMBPEL, ivtc_combed=TC.DEFAULT_COMBED, crop=None, crop_limit=LB.DEFAULT_LIMIT,
                  crop_noise=LB.DEFAULT_NOISE, crop_probe=LB.DEFAULT_PROBE, crop_output='pad', shutter=None,
                  shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, work_depth=None,
-                 out_depth=None, dither=None, **runner_kw):
+                 out_depth=None, dither=None, down=False, shutter_window=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.down = bool(down)
         self.work_depth, self.out_depth, self.dither = check_depths(work_depth, out_depth, dither)
         self.scale = check_scale(scale, scale_filter, crop, crop_output)  # (w, h, filter) or None
         self.interlace = check_interlace(interlace, interlace_lowpass)    # (order, low-pass mode) or None
         self.shutter = check_shutter(shutter, shutter_samples, dedup)     # (S, D) or None
-        self.last_depths = self.last_scale = self.last_interlace = self.last_shutter = None
+        self.shutter_window = check_shutter_window(self.shutter, shutter_window)     # 'box' / 'triangle', None without a shutter
+        self.last_depths = self.last_scale = self.last_interlace = self.last_shutter = self.last_shutter_window = None
+        self.last_windows_skipped = 0
         for attr in filter(None, COUNTERS.values()):
             setattr(self, attr, 0)
         self.crop, (self.crop_limit, self.crop_noise, self.crop_probe, self.crop_output) = check_crop(
@@ -469,7 +501,7 @@ class VideoRunner:
 
     def _ratio(self, hdr):
         """The ratio r = F_out / F_in of this input: M for x M, whose per-window plans (``retime``) give exactly the x M stream."""
-        return Fraction(self.mfi) if self.mfi is not None else R.ratio(hdr.fps, self.fps)
+        return Fraction(self.mfi) if self.mfi is not None else R.ratio(hdr.fps, self.fps, self.down)
 
     def _scale_of(self, hdr):
         """What the scale stage does to a run on frames of ``hdr``: None (no switch, or the run's own size: no stage), or (w, h, filter).
@@ -514,9 +546,9 @@ class VideoRunner:
         if self.ivtc:
             fhdr = TC.film_header(hdr)
             self.last_fields = None
-            if self.fps is not None and self.fps < fhdr.fps:
+            if self.fps is not None and self.fps < fhdr.fps and not self.down:
                 raise ValueError('VideoRunner: output frame rate %s is below the film rate %s of the telecined input (%s frames/s, four '
-                                 'film frames in five): --ivtc gives the film frames, so F_out must be at least %s'
+                                 'film frames in five): --ivtc gives the film frames, so F_out must be at least %s (or pass --downconvert)'
                                  % (self.fps, fhdr.fps, hdr.fps, fhdr.fps))
             return fhdr, None, 1
         order = hdr.interlace if hdr.interlace in ('t', 'b') else None
@@ -524,9 +556,9 @@ class VideoRunner:
         if order is None:
             return hdr, None, 1
         phdr = I.progressive_header(hdr)
-        if self.fps is not None and self.fps < phdr.fps:
+        if self.fps is not None and self.fps < phdr.fps and not self.down:
             raise ValueError('VideoRunner: output frame rate %s is below the field rate %s of the interlaced input (%s frames/s, two fields '
-                             'each): --deinterlace gives one frame per field, so F_out must be at least %s'
+                             'each): --deinterlace gives one frame per field, so F_out must be at least %s (or pass --downconvert)'
                              % (self.fps, phdr.fps, hdr.fps, phdr.fps))
         return phdr, order, 2
 
@@ -648,13 +680,17 @@ class VideoRunner:
         self.last_depth, self.last_layout = out, hdr.layout
 
     def _fine_ratio(self, hdr):
-        """The ratio the runner is built with: r, or with a shutter that of the fine stream, r D (refused above ``retime.MAX_RATIO``)."""
+        """The ratio the runner is built with: r, or with a shutter that of the fine stream, r D (refused above ``retime.MAX_RATIO``).
+        ``dedup`` is refused here for r < 1: ``cadence`` plans over the kept frames for r >= 1 only."""
         r = self._ratio(hdr)
+        if r < 1 and self.dedup is not None:
+            raise ValueError('VideoRunner: --dedup does not go with an output rate below the input\'s (%s of it, --downconvert): repeated '
+                             'frames are planned for F_out >= F_in only; run one of the two' % r)
         return r if self.shutter is None else SH.fine_ratio(r, self.shutter[1])
 
     def _clip_runner(self, hdr, world, rank):
         r, kw = self._fine_ratio(hdr), {}
-        key = (hdr.h, hdr.w, world, rank, r, self.shutter)
+        key = (hdr.h, hdr.w, world, rank, r, self.shutter)   # the window is the edge's (``EdgeSpec``), not the runner's
         cr = self._runners.get(key)
         if cr is None:
             if self.shutter is not None:             # only some of the fine ratio's instants run: the batched plan is sized by those
@@ -668,10 +704,11 @@ class VideoRunner:
         """fn() runs windows lo, lo+1, ... of the input on cr, lo = first() once it has run; returns its window count and sets
         the per-run counters."""
         rn = cr.runner
-        before = {name: getattr(rn, name) for name in COUNTERS}
+        before, skipped = {name: getattr(rn, name) for name in COUNTERS}, rn.windows_skipped
         with cr.oversize_hint():
             n = fn()
         lo, r = first(), self._ratio(hdr)
+        self.last_windows_skipped = rn.windows_skipped - skipped
         self._counted(hdr, {name: getattr(rn, name) - before[name] for name in COUNTERS}, list(rn.last_cuts) if self.scene_cut is not None else [],
                       sum(kind == R.ST for k in range(lo, lo + n) for _, kind, _ in R.window_outputs(k, r, full_length=self.full_length)))
         return n
@@ -684,14 +721,14 @@ class VideoRunner:
                 setattr(self, attr, added[name])
         self.last_instants, self.last_cuts = (added['instants_run'], added['instants_padded']), cuts
         self.last_st_frames = added['shutter_mixed'] if self.shutter is not None else st_frames     # the fine frames that went into the mixes
-        self.last_shutter, self.last_scale = self.shutter, self._scale_of(hdr)
+        self.last_shutter, self.last_scale, self.last_shutter_window = self.shutter, self._scale_of(hdr), self.shutter_window
         self.last_interlace = self.interlace[0] if self.interlace is not None else None
 
     def _edge(self, hdr, with_s1, order=None):
         depths = self._depths_of(hdr)                # hdr has the input's depth; the edge works at depths[1]
         return YuvEdge(y4m.auto_matrix(self._matrix_h or hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
                        self.scene_cut, self.full_length, depths[1], hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
-                       *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths)
+                       *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths, shutter_window=self.shutter_window)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
@@ -794,6 +831,7 @@ class VideoRunner:
             lo, wins = cr.my_windows(n_in, full)
             if not wins:
                 self._counted(hdr, dict.fromkeys(COUNTERS, 0), [], 0)
+                self.last_windows_skipped = 0
                 return 0, 0
             last = R.first_window(n_in, full) + R.n_windows(n_in, full) - 1
             # scene cuts: a block starting at window lo >= 1 also reads frame lo - 1 (score_{lo+1} needs mafd_lo)
@@ -850,8 +888,14 @@ def parser():
     rate = ap.add_mutually_exclusive_group()
     rate.add_argument('--mfi', type=int, default=None, help='multiple_MFI: output frame rate = M x input (main.py:98); default 8')
     rate.add_argument('--fps', type=_value_arg(R.parse_fps), default=None,
-                      help='output frame rate N, N/D or N:D (exact: 60000/1001, not 59.94), at least the input rate; output frame '
-                           'i is at input time 1 + i*F_in/F_out')
+                      help='output frame rate N, N/D or N:D (exact: 60000/1001, not 59.94), at least the input rate (below it with '
+                           '--downconvert); output frame i is at input time 1 + i*F_in/F_out')
+    ap.add_argument('--downconvert', action='store_true',
+                    help='let --fps lie below the input rate (down to 1/%d of it; behind --deinterlace below the field rate, behind --ivtc '
+                         'below the film rate): 60p -> 25p, 59.94i -> 50i with --deinterlace --fps 50 --interlace tff.  The output frames '
+                         'sit on the same timeline, further apart; windows that own no output frame run nothing.  Use --shutter with it: '
+                         'the temporal aperture is what keeps a lower rate from juddering.  Not with --dedup.  Changes nothing for '
+                         'F_out >= F_in.  Off by default (a lower rate is refused)' % R.MAX_RATIO)
     ap.add_argument('--n-tst', type=int, default=3, help='N_tst recursive boosts (main.py:101)')
     ap.add_argument('--dtype', default='fp16', choices=['fp16', 'fp32'])
     ap.add_argument('--checkpoint', default='', help="reference checkpoint (.pt holding 'state_dict_Model')")
@@ -939,6 +983,10 @@ def parser():
                          'most %d.  One rank only; not with --dedup.  Off by default' % R.MAX_RATIO)
     ap.add_argument('--shutter-samples', type=int, default=None, metavar='S',
                     help='with --shutter: the sub-frames averaged per written frame, 1 .. %d (default %d)' % (SH.MAX_SAMPLES, SH.DEFAULT_SAMPLES))
+    ap.add_argument('--shutter-window', default=None, choices=list(SH.WINDOWS),
+                    help='with --shutter: the weights of the sub-frames: box (default) averages them, triangle weighs sample j of S by '
+                         'min(j + 1, S - j) (1,2,2,1 of four), a softer exposure; a group cut short by a scene cut or the end of the '
+                         'stream is renormalised by the weights it keeps')
     ap.add_argument('--interlace', type=_value_arg(IL.parse_order), default=None, metavar='tff|bff',
                     help='write interlaced output: frames 2q and 2q+1 of the output stream become the first and the second field of payload '
                          'q (tff: the first is the top field, the even rows; bff: the bottom field), an odd last frame is woven with itself, '
@@ -1000,7 +1048,7 @@ def main(argv=None):
                                                     ('crop_probe', LB.DEFAULT_PROBE), ('crop_output', 'pad'))))
         if a.crop == 'auto' and not (_is_regular(a.input) and os.path.isfile(a.input) and _is_regular(a.output)):
             raise ValueError(AUTO_NEEDS_A_FILE + ' (and a regular output file)')
-        check_shutter(a.shutter, a.shutter_samples, a.dedup or None)
+        check_shutter_window(check_shutter(a.shutter, a.shutter_samples, a.dedup or None), a.shutter_window)
         check_interlace(a.interlace, a.interlace_lowpass)
         check_scale(a.scale, a.scale_filter, a.crop, crop_kw.get('crop_output', 'pad'))
         check_depths(a.work_depth, a.out_depth, a.dither)
@@ -1009,7 +1057,7 @@ def main(argv=None):
     shutter_kw = {k: v for k, v in (('shutter', a.shutter), ('shutter_samples', a.shutter_samples), ('interlace', a.interlace),
                                     ('interlace_lowpass', a.interlace_lowpass), ('scale', a.scale),
                                     ('scale_filter', a.scale_filter), ('work_depth', a.work_depth), ('out_depth', a.out_depth),
-                                    ('dither', a.dither)) if v is not None}
+                                    ('dither', a.dither), ('shutter_window', a.shutter_window)) if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     try:
         check_one_rank(world, dedup=a.dedup, ivtc=a.ivtc, shutter=a.shutter, interlace=a.interlace)
@@ -1039,7 +1087,7 @@ def main(argv=None):
                      tile=a.tile, tile_margin=a.tile_margin, high_depth=a.high_depth, layouts=a.any_layout, dedup=a.dedup or None,
                      dedup_max_hold=a.dedup_max_hold, tile_high_depth=a.tile_high_depth, deinterlace=a.deinterlace,
                      deinterlace_mode=a.deinterlace_mode, ivtc=a.ivtc, ivtc_cthresh=a.ivtc_cthresh, ivtc_combpel=a.ivtc_combpel,
-                     ivtc_combed=a.ivtc_combed, **crop_kw, **shutter_kw)
+                     ivtc_combed=a.ivtc_combed, down=a.downconvert, **crop_kw, **shutter_kw)
     t0 = time.perf_counter()
     if world > 1 or a.crop == 'auto':                        # the pre-pass seeks: regular files
         nw, nf = vr.run_file(a.input, a.output, world, rank)
@@ -1064,6 +1112,10 @@ def main(argv=None):
             print('demfi_amd.video: %s: no window, only the header was written' %
                   ('no input frame' if a.full_length else 'fewer than 4 input frames'), file=sys.stderr)
         extra = {'shutter': {'angle': str(a.shutter), 'samples': vr.last_shutter[0], 'fine_per_written': vr.last_shutter[1]}} if a.shutter else {}
+        if a.shutter_window is not None:
+            extra['shutter']['window'] = vr.last_shutter_window
+        if a.downconvert:
+            extra['windows_skipped'] = vr.last_windows_skipped
         if a.interlace is not None:
             extra['interlace'] = {'order': vr.last_interlace, 'lowpass': vr.interlace[1], 'carried': vr.last_interlace_carried}
         if a.scale is not None:

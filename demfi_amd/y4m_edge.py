@@ -294,7 +294,9 @@ def plan_fine(spec, r, wins, n, window_index, with_s1, det, kept, frames, slot_o
     """``plan_batch`` and, behind its four values, what a shutter needs to know of the batch: fine[w] = (is window w a cut window, [(stream index i,
     does it come from the right run of the cut window)] of its outputs in stream order), and whether the batch holds the clip's last window.  With
     ``spec.shutter`` = (S, D) the ratio r is that of the fine stream and every window's plan goes through ``shutter.filter_plan``: only the outputs
-    the written frames need, and the instants those name, are left.  Pure."""
+    the written frames need, and the instants those name, are left.  With r < 1 (``--downconvert``) a window may own no output, or be left
+    none by the filter: it gets no run and no output, and its entry of ``fine`` still says whether it is a cut window, since the scene
+    changes on it.  Pure."""
     runs, outs, cut_windows, st_frames, fine, ends = [], [], 0, 0, [], False
     for wi, win in enumerate(wins):
         k = window_index(n + wi) if window_index is not None else win[2]
@@ -307,13 +309,13 @@ def plan_fine(spec, r, wins, n, window_index, with_s1, det, kept, frames, slot_o
             st_frames += sum(kind == R.ST for _, _, kind, _ in so)
         elif det is None:
             ts, o = R.window_plan(k, r, last, spec.full)
-            sr, so = [(None, ts)], [(i, 0, kind, j) for i, kind, j in o]
+            sr, so = ([(None, ts)] if ts else []), [(i, 0, kind, j) for i, kind, j in o]
         else:
             is_cut = S.with_sentinels(det.is_cut, k + 3 if last else None) if spec.full else det.is_cut
             sr, so = S.window_runs(k, r, last, is_cut, spec.full)
-            cut = len(sr) > 1
-            cut_windows += len(sr) - 1
-        right = {i for i, run, _, _ in so if cut and run == 1}
+            cut = k >= -1 and S.is_cut_window(k, is_cut)     # two runs; with r < 1 those of the two that have an output
+            cut_windows += int(cut and bool(sr))
+        right = {i for i, _, kind, _ in so if cut and kind == R.S1}      # a cut window's right run gives its frame as S1
         if spec.shutter is not None:
             sr, so = SH.filter_plan(sr, so, *spec.shutter)
         wr = [(frames[wi] if tup is None else [slot_of[x] for x in S.runner_order(tup)], ts) for tup, ts in sr]
@@ -400,7 +402,8 @@ class Stage:
 class Shutter(Stage):
     """Fine payloads gathered -> written payloads mixed (``demfi_amd.shutter``, ``spec.shutter`` = (S, D)).  Written frame c averages the
     fine frames c D .. c D + S - 1 of its scene that exist.  After a batch's gather ``run`` closes every group whose last sample has arrived
-    (all open groups when the batch holds the clip's last window) and ``demfi_payload_mix`` writes them; a written frame counts to the window
+    (all open groups when the batch holds the clip's last window) and ``demfi_payload_mix`` writes them (``spec.shutter_window`` 'triangle':
+    ``demfi_payload_mix_w`` with the weights of ``shutter.window_weights``); a written frame counts to the window
     that completed it.  The samples of the one group still open (at most ``lead`` = S - 1 of them, consecutive rows at the end of the gather)
     carry over on the device: ``carry`` copies them into the ``lead`` rows in front of the next batch's gather, so which batch a sample came
     with never shows.  The runner counts for it, as it counts cut windows: ``shutter_mixed`` the fine frames that went into the mixes,
@@ -411,6 +414,8 @@ class Shutter(Stage):
         self.S, self.D = spec.shutter
         self.width = self.S
         super().__init__(runner, spec, src, own, dev)
+        w = SH.window_weights(spec.shutter_window, self.S)               # a weighted window: the kept samples are a prefix, one vector serves
+        self.weights = None if set(w) == {1} else np.ascontiguousarray(w, dtype=np.int32)
         self.begin(None)
 
     def begin(self, yuv):
@@ -436,7 +441,11 @@ class Shutter(Stage):
         return counts
 
     def _call(self, src, host, offs, n, dst, stream):
-        L.check(self.lib.demfi_payload_mix(src, host, offs, n, self.S, self.Pb // self.es, self.es, dst, self.Pb, stream), 'payload_mix')
+        if self.weights is None:                     # the box, and a triangle of up to two samples, which is one
+            L.check(self.lib.demfi_payload_mix(src, host, offs, n, self.S, self.Pb // self.es, self.es, dst, self.Pb, stream), 'payload_mix')
+        else:
+            L.check(self.lib.demfi_payload_mix_w(src, host, offs, n, self.S, self.Pb // self.es, self.es, dst, self.Pb, self.weights.ctypes.data,
+                                                 stream), 'payload_mix_w')
 
 
 class Scaler(Stage):
@@ -682,7 +691,9 @@ class Y4mEdge:
         self.rn.cut_windows += cut_windows
         if self.kept is not None:
             self.kept.st_frames += st_frames
-        self._run_windows(i, runs)
+        self.rn.windows_skipped += sum(not o for o in outs)               # r < 1: windows that own no output (or none a shutter needs)
+        if runs:
+            self._run_windows(i, runs)
         for st, src in zip(reversed(self.stages), reversed(self.sources)):   # the carries are independent copies: the last stage's goes first
             st.carry(i, src)
         counts = self._gather(i, outs, cur, self.lead)
@@ -743,9 +754,10 @@ class Y4mEdge:
         nf = len(offs)
         if nf > dst.shape[0]:
             raise RuntimeError('retime: %d outputs for %d payload slots' % (nf, dst.shape[0]))
-        od = self.offs[i][:nf]
-        od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
-        self.gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), nf, cur.cuda_stream)
+        if nf:                                       # r < 1: a batch may own no output
+            od = self.offs[i][:nf]
+            od.copy_(torch.tensor(offs, dtype=torch.int64).pin_memory(), non_blocking=True)
+            self.gather(comb.data_ptr(), od.data_ptr(), dst.data_ptr(), nf, cur.cuda_stream)
         return [len(o) for o in outs]
 
     def d2h(self, i, counts):

@@ -507,6 +507,16 @@ int demfi_luma_line_counts(const uint8_t* base, const int64_t* offsets, int n, i
 int demfi_payload_mix(const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, int n, int smax, int64_t P,
                       int sample_bytes, uint8_t* dst, int64_t dst_stride, void* stream);
 
+/* payload_mix_w: payload_mix with a weighted window (--shutter-window; the numpy definition is mix_np(..., weights=...)).  weights is
+ * HOST memory: smax int32 weights w_j >= 1 whose sum is at most 4096, one vector for all rows of the launch.  The kept offsets of a row
+ * are its first k_i samples, so with W = w_0 + .. + w_(k_i - 1) every stored sample becomes (2 * sum_j w_j x_j + W) / (2 W): round half
+ * up, exact integers (32-bit accumulators: 2 * 4096 * 65535 + 4096 < 2^30; the division is one multiply-high with the constants of
+ * demfi_amd/shutter.py magic_w, computed here on the host for every k and passed to the kernel by value).  Everything else is
+ * payload_mix: the same checks, paths, strides and launch shape.  DEMFI_ERR_ARG, launching nothing, also for weights == NULL, a weight
+ * below 1 and a sum of weights above 4096.  All weights 1 give the bytes of payload_mix. */
+int demfi_payload_mix_w(const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, int n, int smax, int64_t P,
+                        int sample_bytes, uint8_t* dst, int64_t dst_stride, const int32_t* weights, void* stream);
+
 /* ---- interlaced output of the Y4M edge (csrc/interlace.hip; demfi_amd/video.py --interlace) ------------------------------------------
  * payload_weave: written payload i (n per launch) weaves two progressive payloads: row i has two int64 BYTE offsets from base,
  * offsets[2 i] the frame of the first field in time and offsets[2 i + 1] that of the second (equal for an odd tail).  A payload is
