@@ -21,6 +21,7 @@ from . import _lib as L
 from . import bitdepth as BD
 from . import cadence as K
 from . import deint as I
+from . import denoise as DN
 from . import interlace as IL
 from . import retime as R
 from . import scale as SC
@@ -49,9 +50,11 @@ class EdgeSpec(_EdgeFields):
     (``demfi_amd.interlace``); ``scale``: None or (w, h, filter) of resized output (``demfi_amd.scale``); ``depths``: None or (input depth,
     working depth, output depth, dither mode or None) of a run that changes the bit depth (``demfi_amd.bitdepth``): ``depth`` and ``hi`` then
     mean the WORKING depth, the payloads come in at the input's and leave at the output's; three equal depths are None;
-    ``shutter_window``: None (the box) or 'triangle', the weights of a shutter's mix (``shutter.window_weights``; only with ``shutter``).
+    ``shutter_window``: None (the box) or 'triangle', the weights of a shutter's mix (``shutter.window_weights``; only with ``shutter``);
+    ``denoise``: None or (A, B, R) of the temporal denoiser in front of the network (``demfi_amd.denoise``: thresholds at the 8-bit scale, frames
+    on each side), kept beside the tuple like the others.  ``reach``: how far the frames an ingest stage reads lie from the frame it writes.
     Hashable: (batch, spec) is what a cached ``ClipPipeline`` can be reused for.
-    ``shutter``, ``interlace``, ``scale``, ``depths`` and ``shutter_window`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
+    ``shutter``, ``interlace``, ``scale``, ``depths``, ``shutter_window`` and ``denoise`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
     without them is, item for item, the record it was before there were any, and one with any of them equals no plain tuple.  What the namedtuple makes
     from its items alone does not know them: ``_make``, ``_asdict`` and pickling drop them; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
     shutter = None
@@ -59,9 +62,12 @@ class EdgeSpec(_EdgeFields):
     scale = None
     depths = None
     shutter_window = None
+    denoise = None
 
-    def __new__(cls, *args, shutter=None, interlace=None, scale=None, depths=None, shutter_window=None, **kw):
+    def __new__(cls, *args, shutter=None, interlace=None, scale=None, depths=None, shutter_window=None, denoise=None, **kw):
         self = super().__new__(cls, *args, **kw)
+        if denoise is not None:
+            self.denoise = tuple(int(v) for v in denoise)
         if shutter_window not in (None, 'box'):      # the box is the spec without the field
             self.shutter_window = shutter_window
         if shutter is not None:
@@ -76,13 +82,15 @@ class EdgeSpec(_EdgeFields):
 
     def _replace(self, **kw):
         shutter, interlace, scale = kw.pop('shutter', self.shutter), kw.pop('interlace', self.interlace), kw.pop('scale', self.scale)
-        depths, window = kw.pop('depths', self.depths), kw.pop('shutter_window', self.shutter_window)
-        return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace, scale=scale, depths=depths, shutter_window=window)
+        depths, window, denoise = kw.pop('depths', self.depths), kw.pop('shutter_window', self.shutter_window), kw.pop('denoise', self.denoise)
+        return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace, scale=scale, depths=depths, shutter_window=window,
+                          denoise=denoise)
 
     def __eq__(self, other):
         return (tuple.__eq__(self, other) is True and self.shutter == getattr(other, 'shutter', None)
                 and self.interlace == getattr(other, 'interlace', None) and self.scale == getattr(other, 'scale', None)
-                and self.depths == getattr(other, 'depths', None) and self.shutter_window == getattr(other, 'shutter_window', None))
+                and self.depths == getattr(other, 'depths', None) and self.shutter_window == getattr(other, 'shutter_window', None)
+                and self.denoise == getattr(other, 'denoise', None))
 
     def __ne__(self, other):
         return not self == other
@@ -91,13 +99,15 @@ class EdgeSpec(_EdgeFields):
         key = (tuple(self), self.shutter) if self.interlace is None else (tuple(self), self.shutter, self.interlace)
         key = key if self.scale is None else key + ('scale', self.scale)
         key = key if self.depths is None else key + ('depths', self.depths)
-        return hash(key if self.shutter_window is None else key + ('shutter_window', self.shutter_window))
+        key = key if self.shutter_window is None else key + ('shutter_window', self.shutter_window)
+        return hash(key if self.denoise is None else key + ('denoise', self.denoise))
 
     def __repr__(self):
         return super().__repr__()[:-1] + ', shutter=%r%s%s)' % (self.shutter, ', interlace=%r' % (self.interlace,) if self.interlace is not None else '',
                                                                (', scale=%r' % (self.scale,) if self.scale is not None else '')
                                                                + (', depths=%r' % (self.depths,) if self.depths is not None else '')
-                                                               + (', shutter_window=%r' % self.shutter_window if self.shutter_window is not None else ''))
+                                                               + (', shutter_window=%r' % self.shutter_window if self.shutter_window is not None else '')
+                                                               + (', denoise=%r' % (self.denoise,) if self.denoise is not None else ''))
 
     @classmethod
     def of(cls, yuv):
@@ -107,15 +117,18 @@ class EdgeSpec(_EdgeFields):
                    getattr(yuv, 'layout', '420'), tuple(dedup) if dedup is not None else None, fields,
                    getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob', shutter=getattr(yuv, 'shutter', None),
                    interlace=getattr(yuv, 'interlace', None), scale=getattr(yuv, 'scale', None), depths=getattr(yuv, 'depths', None),
-                   shutter_window=getattr(yuv, 'shutter_window', None))
+                   shutter_window=getattr(yuv, 'shutter_window', None), denoise=getattr(yuv, 'denoise', None))
 
     hi = property(lambda self: self.depth > 8, doc='16-bit frames: the samples of a stream above 8 bits')
+    reach = property(lambda self: DN.reach(self.denoise[2], self.fields is not None) if self.denoise is not None
+                     else 2 if self.fields is not None and self.deint_mode == 'adaptive' else 0,
+                     doc='frames before and after a frame that its ingest reads: the adaptive deinterlacer 2 fields, the denoiser R (bobbed fields: 2 R)')
 
     def check(self, retimed, has_window_index, reuse_frames):
         """Every rule about what goes together, before anything is allocated, for a run on a ``retimed`` runner (built with a ratio)."""
         other, edge_only = self.deint_mode != 'bob', self.hi or self.dedup is not None or self.fields is not None
         deint = deint_conflict(self.deint_mode, self.fields is not None, self.dedup is not None)
-        sh, il, sc, dp, win = self.shutter, self.interlace, self.scale, self.depths, self.shutter_window
+        sh, il, sc, dp, win, dn = self.shutter, self.interlace, self.scale, self.depths, self.shutter_window, self.denoise
         for bad, what in ((self.fields not in (None, 't', 'b'), "fields must be None, 't' or 'b', got %r" % (self.fields,)),
                           (deint, 'deint_mode %r with fields=%r, dedup=%r' % (self.deint_mode, self.fields, self.dedup)),
                           (edge_only and not self.y4m, '16-bit frames, repeated frames and fields are those of the Y4M edge (yuv=...) only'),
@@ -143,7 +156,15 @@ class EdgeSpec(_EdgeFields):
                                                    and (dp[3] in BD.DITHERS if dp[2] < dp[1] else dp[3] is None)),
                            'depths must be None or (input, working, output depth, dither mode of %s where the output is below the working '
                            'depth, else None) with input <= working == depth >= output, got %r at depth %r' % (BD.DITHERS, dp, self.depth)),
-                          (dp is not None and not (retimed and self.y4m), 'a change of bit depth needs the Y4M edge on a retimed runner')):
+                          (dp is not None and not (retimed and self.y4m), 'a change of bit depth needs the Y4M edge on a retimed runner'),
+                          (dn is not None and not (len(dn) == 3 and 0 <= dn[0] <= dn[1] <= 255 and 1 <= dn[2] <= DN.MAX_RADIUS),
+                           'denoise must be None or (A, B, R) with 0 <= A <= B <= 255 and 1 <= R <= %d, got %r' % (DN.MAX_RADIUS, dn)),
+                          (dn is not None and not (retimed and self.y4m and reuse_frames),
+                           'the denoiser needs the Y4M edge on a retimed runner and reuse_frames (slots are keyed by frame)'),
+                          (dn is not None and self.dedup is not None,
+                           'the denoiser does not go with repeated frames (dedup): kept frames are staged one at a time, without look-ahead'),
+                          (dn is not None and other,
+                           'the denoiser does not go with deint_mode %r: two deferred look-ahead stages in a row' % (self.deint_mode,))):
             if bad:
                 raise ValueError('WindowRunner.run_clip_u8: ' + what)
 
@@ -378,7 +399,7 @@ class ClipPipeline:
         self.h2d, self.d2h = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
         plan = runner.tiles
         fh, fw = (plan.h, plan.w) if plan is not None else (runner.h, runner.w)
-        look = 4 if spec.fields is not None and spec.deint_mode == 'adaptive' else 0                 # two fields behind a batch's frames and two ahead
+        look = 2 * spec.reach                        # the frames an ingest stage reads behind a batch's frames and ahead of them (adaptive: two fields each)
         self.slots = FrameSlots(max(2 * batch + 8 + look, 8 * batch), fh, fw, dev, torch.int16 if spec.hi else torch.uint8)
         # 16-bit frames: tiles are read and written inside the full frames.  8-bit: the frames stitched per batch are a run's J + 2
         # (a cut window is two runs), or M + 1

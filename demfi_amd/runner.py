@@ -174,6 +174,7 @@ class WindowRunner:
         self.interlace_woven = self.interlace_carried = 0    # interlaced output: payloads woven / frames carried between batches (``y4m_edge.Interlacer``)
         self.scale_payloads = 0                      # resized output: payloads resampled (``y4m_edge.Scaler``)
         self.depth_promoted = self.depth_requantised = 0     # bit depth: payloads promoted at ingest / requantised at egress (``demfi_amd.bitdepth``)
+        self.denoised = 0                            # temporal denoiser: frames denoised at ingest (``demfi_amd.denoise``)
         self.last_cuts = []                          # frames that start a scene, as the last run_clip_u8 with scene cuts found them
 
     # ---------------------------------------------------------------------------------------------------------
@@ -636,6 +637,11 @@ class WindowRunner:
         ``yuv.depth`` is the working depth, host_frames[i] holds samples of the input's depth, which are promoted on the GPU behind
         their upload (``demfi_payload_promote``), and the payloads the sink gets have the output's depth, requantised on the GPU as the
         last stage (``demfi_payload_requant``).
+        ``yuv.denoise`` = (A, B, R) (None when absent; ``demfi_amd.denoise``): every frame is denoised on the GPU from the frames up to R
+        before and after it (over the fields of ``yuv.fields``: 2 R, those of its parity) behind the promotion and the bob
+        (``demfi_payload_denoise``) and everything else runs on the denoised stream; host_frames must then also hold that many frames before
+        the first one named and answer ``has(f)`` for those after the last (``y4m.Frames(behind=reach)``); not together with ``yuv.dedup``
+        or the adaptive ``yuv.deint_mode``.
         Returns the number of windows run."""
         spec = EdgeSpec.of(yuv)
         spec.check(self.retime is not None, window_index is not None, reuse_frames)

@@ -165,6 +165,26 @@ nothing between payloads: every switch above and several ranks work.  Refused: W
 nothing is requantised.  Depths that resolve to the input's build no stage, no buffer and no launch and give the bytes of a run without the
 switches.  Not offered: error diffusion, random or blue-noise dither, patterns that change from frame to frame, ``demfi_amd.clip``, changing
 the range or the matrix on the way.
+
+``--denoise [A[:B]]`` with ``--denoise-radius R`` (1 .. 3, default 2) cleans noisy input in front of the network (``demfi_amd.denoise``): a
+deblurring network sharpens grain and tape noise with everything else, and noise that differs from frame to frame is motion that is not
+there -- it hurts the flow and inflates the scene scores.  Every stored sample becomes the rounded mean of itself and of the samples at its
+position in up to R frames before and R after: each side walks outward on its own and stops for good at the first sample that differs from
+the frame's own by more than A or brings the side's accumulated difference above B (8-bit steps, 0 <= A <= B <= 255, default 5:10, A alone
+is A:2A, one pair for every plane, shifted to the working depth), the idea of ffmpeg's ``atadenoise`` in its serial mode; ``--denoise 0`` is
+the identity.  The stage sits at the ingest, H2D -> promote (``--work-depth``) -> bob -> denoise -> everything else: ONE launch per batch
+(csrc/denoise.hip ``demfi_payload_denoise``, defined by ``denoise.denoise_payload_np``; the payload one flat array, so every depth and layout
+is served) writes the denoised payloads into a second buffer beside the uploaded ones, which the denoiser alone reads from then on; the
+conversion to frames, the tiles and the scene scores read the denoised ones, so a run with the switch writes the bytes of a run without it
+over the stream denoised on the host.  Behind ``--deinterlace`` (bob) frame f is field f and its neighbours are the fields of the same
+parity f +- 2, f +- 4, ..  A frame is denoised once the R frames (2 R fields) after it are uploaded, in the batch that first names it; a
+rank's block also reads that many frames before it and after it; no payload is uploaded more often, and an output frame depends on the
+input frames f - R .. f + R only, whatever the batch size and the rank count.  ``--ivtc`` and ``--crop`` are host stages in front: their
+frames are ordinary frames, and they decide on the input's own samples.  Works with every switch above except ``--dedup`` (kept frames are
+staged one at a time, without look-ahead) and ``--deinterlace-mode adaptive`` (two deferred look-ahead stages in a row), both refused
+before anything is allocated.  Not offered: spatial filtering, separate chroma thresholds, motion-compensated averaging, stopping at
+detected cuts (the thresholds do that per sample), numeric equality with ffmpeg's ``atadenoise``, decisions of ``--ivtc`` / ``--crop auto`` on
+denoised samples, ``demfi_amd.clip``.  Without the switch no buffer, table, launch or slot is added and every byte stays the same.
 """
 import os
 import sys
@@ -176,6 +196,7 @@ from . import _lib as L
 from . import bitdepth as BD
 from . import cadence as K
 from . import deint as I
+from . import denoise as DN
 from . import dist as D
 from . import interlace as IL
 from . import letterbox as LB
@@ -205,12 +226,13 @@ class YuvEdge:
     payloads handed out have that size.  ``depths``: None, or (input depth, working depth, output depth, dither mode or None) of
     ``bitdepth.resolve``: the payloads handed in have the input's depth, ``depth`` is then the WORKING depth, and the payloads handed out
     have the output's.  ``shutter_window``: None ('box') or 'triangle', the weights of the shutter's mix (``shutter.window_weights``); an
-    error without ``shutter``."""
+    error without ``shutter``.  ``denoise``: None, or (A, B, R) of the temporal denoiser in front of the network (``demfi_amd.denoise``)."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
                  fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None,
-                 depths=None, shutter_window=None):
+                 depths=None, shutter_window=None, denoise=None):
         self.dedup, self.shutter = dedup, shutter
+        self.denoise = None if denoise is None else DN.check_params(*denoise)
         self.shutter_window = check_shutter_window(shutter, shutter_window)
         self.depths = None if BD.is_noop(depths) else tuple(depths)
         if self.depths is not None and self.depths[1] != depth:
@@ -322,11 +344,39 @@ def check_depths(work_depth=None, out_depth=None, dither=None):
     return BD.check_switches(work_depth, out_depth, dither)
 
 
+def check_denoise(denoise, radius=None, dedup=None, deinterlace_mode='bob'):
+    """The denoise switches checked: None, or (A, B, R) of ``denoise.check_params``.  ``denoise``: None / False (off), True (the defaults
+    5:10), A (A:2A), (A, B) or an "A[:B]" string; ``radius`` (None: 2) says how ``denoise`` works, so it is an error without it.  The
+    denoiser does not go with ``--dedup`` or with ``--deinterlace-mode adaptive``."""
+    if denoise is None or denoise is False:
+        if radius is not None:
+            raise ValueError('--denoise-radius (denoise_radius) says how --denoise works: give --denoise [A[:B]] with it')
+        return None
+    if denoise is True:
+        denoise = DN.DEFAULTS
+    elif isinstance(denoise, str):
+        denoise = DN.parse_denoise(denoise)
+    elif isinstance(denoise, int):
+        denoise = (denoise, None)
+    if not isinstance(denoise, (tuple, list)) or len(denoise) != 2:
+        raise ValueError('denoise must be None, True, A, (A, B) or "A[:B]", got %r' % (denoise,))
+    dn = DN.check_params(denoise[0], denoise[1], radius)
+    if dedup not in (None, False):
+        raise ValueError('--denoise does not go with --dedup: repeated frames are staged and discarded one frame at a time, the denoiser '
+                         'needs the frames after the one it cleans; run one of the two')
+    if deinterlace_mode != 'bob':
+        raise ValueError('--denoise does not go with --deinterlace-mode %s: both wait for frames ahead and the first rebuilds its payloads in '
+                         'place; use --deinterlace-mode bob with --denoise' % deinterlace_mode)
+    return dn
+
+
 # what a run adds to each of these counters of its ``WindowRunner`` is kept in the ``VideoRunner`` attribute named here (None: it goes into
 # ``last_instants`` = (run, padded), and a shutter's fine frames into ``last_st_frames``: ``VideoRunner._counted``)
 COUNTERS = {'instants_run': None, 'instants_padded': None, 'shutter_mixed': None, 'cut_windows': 'last_cut_windows',
             'shutter_carried': 'last_shutter_carried', 'interlace_carried': 'last_interlace_carried', 'scale_payloads': 'last_scale_payloads',
             'depth_promoted': 'last_depth_promoted', 'depth_requantised': 'last_depth_requantised'}
+# the counters of the ingest stages that came after those: kept the same way, in a table of their own
+INGEST_COUNTERS = {'denoised': 'last_denoised'}
 
 
 AUTO_NEEDS_A_FILE = ('--crop auto needs a regular input file: the bars of a stream are known only at its end; give the four bar '
@@ -430,7 +480,13 @@ class VideoRunner:
     ``last_windows_skipped`` counts those of the last run.  Not with ``dedup`` below the input rate (refused once the header is known);
     with ``fps`` at or above the input's rate nothing changes.  ``shutter_window``: None (the default, 'box'), 'box' or 'triangle', the
     weights of the shutter's samples (``shutter.window_weights``); given without ``shutter`` it is an error.  After a run
-    ``last_shutter_window`` = 'box', 'triangle' or None without a shutter."""
+    ``last_shutter_window`` = 'box', 'triangle' or None without a shutter.  ``denoise``: None (default), True (the thresholds 5:10), A
+    (A:2A), (A, B) or an "A[:B]" string, at the 8-bit scale with 0 <= A <= B <= 255: the temporal denoiser in front of the network
+    (``demfi_amd.denoise``) with ``denoise_radius`` = R frames on each side (1 .. 3; None, the default, is 2; given without ``denoise`` it is
+    an error).  Every frame is denoised on the GPU behind the promotion and the bob (csrc/denoise.hip ``demfi_payload_denoise``, ONE launch
+    per batch) and everything behind that, scene cuts included, runs on the denoised stream.  Not with ``dedup`` or
+    ``deinterlace_mode='adaptive'`` (refused here).  Any number of ranks.  After a run ``last_denoised`` = the frames denoised.  Without it
+    no buffer, table, launch or slot is added and every byte stays the same."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
@@ -438,8 +494,9 @@ class VideoRunner:
                  ivtc_combpel=TC.DEFAULT_COMBPEL, ivtc_combed=TC.DEFAULT_COMBED, crop=None, crop_limit=LB.DEFAULT_LIMIT,
                  crop_noise=LB.DEFAULT_NOISE, crop_probe=LB.DEFAULT_PROBE, crop_output='pad', shutter=None,
                  shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, work_depth=None,
-                 out_depth=None, dither=None, down=False, shutter_window=None, **runner_kw):
+                 out_depth=None, dither=None, down=False, shutter_window=None, denoise=None, denoise_radius=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.denoise = check_denoise(denoise, denoise_radius, dedup, deinterlace_mode)   # (A, B, R) or None
         self.down = bool(down)
         self.work_depth, self.out_depth, self.dither = check_depths(work_depth, out_depth, dither)
         self.scale = check_scale(scale, scale_filter, crop, crop_output)  # (w, h, filter) or None
@@ -448,7 +505,7 @@ class VideoRunner:
         self.shutter_window = check_shutter_window(self.shutter, shutter_window)     # 'box' / 'triangle', None without a shutter
         self.last_depths = self.last_scale = self.last_interlace = self.last_shutter = self.last_shutter_window = None
         self.last_windows_skipped = 0
-        for attr in filter(None, COUNTERS.values()):
+        for attr in filter(None, list(COUNTERS.values()) + list(INGEST_COUNTERS.values())):
             setattr(self, attr, 0)
         self.crop, (self.crop_limit, self.crop_noise, self.crop_probe, self.crop_output) = check_crop(
             crop, crop_limit, crop_noise, crop_probe, crop_output)
@@ -663,7 +720,10 @@ class VideoRunner:
         return pad_sink
 
     def _behind(self, order):
-        """``y4m.Frames(behind=...)``: the adaptive mode reads two fields before and after every field it rebuilds."""
+        """``y4m.Frames(behind=...)``: the reach of the edge's ingest.  The adaptive mode reads two fields before and after every field it
+        rebuilds, the denoiser R frames (over the fields of an interlaced input 2 R)."""
+        if self.denoise is not None:
+            return DN.reach(self.denoise[2], order is not None)
         return 2 if order is not None and self.deinterlace_mode == 'adaptive' else 0
 
     def _check_depth(self, hdr):
@@ -704,12 +764,12 @@ class VideoRunner:
         """fn() runs windows lo, lo+1, ... of the input on cr, lo = first() once it has run; returns its window count and sets
         the per-run counters."""
         rn = cr.runner
-        before, skipped = {name: getattr(rn, name) for name in COUNTERS}, rn.windows_skipped
+        before, skipped = {name: getattr(rn, name) for name in (*COUNTERS, *INGEST_COUNTERS)}, rn.windows_skipped
         with cr.oversize_hint():
             n = fn()
         lo, r = first(), self._ratio(hdr)
         self.last_windows_skipped = rn.windows_skipped - skipped
-        self._counted(hdr, {name: getattr(rn, name) - before[name] for name in COUNTERS}, list(rn.last_cuts) if self.scene_cut is not None else [],
+        self._counted(hdr, {name: getattr(rn, name) - before[name] for name in before}, list(rn.last_cuts) if self.scene_cut is not None else [],
                       sum(kind == R.ST for k in range(lo, lo + n) for _, kind, _ in R.window_outputs(k, r, full_length=self.full_length)))
         return n
 
@@ -719,6 +779,8 @@ class VideoRunner:
         for name, attr in COUNTERS.items():
             if attr is not None:
                 setattr(self, attr, added[name])
+        for name, attr in INGEST_COUNTERS.items():
+            setattr(self, attr, added.get(name, 0))
         self.last_instants, self.last_cuts = (added['instants_run'], added['instants_padded']), cuts
         self.last_st_frames = added['shutter_mixed'] if self.shutter is not None else st_frames     # the fine frames that went into the mixes
         self.last_shutter, self.last_scale, self.last_shutter_window = self.shutter, self._scale_of(hdr), self.shutter_window
@@ -728,7 +790,8 @@ class VideoRunner:
         depths = self._depths_of(hdr)                # hdr has the input's depth; the edge works at depths[1]
         return YuvEdge(y4m.auto_matrix(self._matrix_h or hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
                        self.scene_cut, self.full_length, depths[1], hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
-                       *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths, shutter_window=self.shutter_window)
+                       *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths, shutter_window=self.shutter_window,
+                       denoise=self.denoise)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
@@ -758,7 +821,8 @@ class VideoRunner:
         wr = y4m.Writer(dst, out_hdr)
         if self.ivtc:                                    # downstream sees an ordinary progressive input at the film rate
             film = self._film_frames(lambda i, buf: rd.read_into(buf), rd.header, cr.runner.engine.device)
-            frames = y4m.Frames(payload=hdr.payload, fetch=self._cropped(film, cropper), full_length=self.full_length)
+            frames = y4m.Frames(payload=hdr.payload, fetch=self._cropped(film, cropper), full_length=self.full_length,
+                                behind=self._behind(None))
         elif cropper is not None:                        # the crop is the last host stage in front of the frames
             frames = y4m.Frames(payload=hdr.payload, fetch=self._cropped(lambda i, buf: rd.read_into(buf), cropper),
                                 full_length=self.full_length, fields=per, behind=self._behind(order))
@@ -822,7 +886,8 @@ class VideoRunner:
                     raise RuntimeError('ivtc: film frames are made in order from frame 0, not from frame %d' % first)
                 fetch = y4m.file_fetch(f, offs)
                 film = self._film_frames(lambda i, buf: i < len(offs) and fetch(i, buf), in_hdr, cr.runner.engine.device)
-                return y4m.Frames(payload=hdr.payload, fetch=self._cropped(film, cropper), stop=min(stop, n_in))
+                return y4m.Frames(payload=hdr.payload, fetch=self._cropped(film, cropper), stop=min(stop + kw.get('behind', 0), n_in),
+                                  behind=kw.get('behind', 0))
             if self.dedup is not None:
                 with open(out_path, 'r+b') as o:
                     wr = y4m.Writer(o, out_hdr, at=len(hb))
@@ -1024,6 +1089,18 @@ def parser():
                     help='with an output depth below the working depth: bayer (default) rounds with an 8x8 ordered-dither threshold, the same '
                          'pattern in every frame and in both fields of an interlaced payload, so a smooth gradient keeps its mean and does not '
                          'band; none rounds half up.  An error where nothing is requantised')
+    ap.add_argument('--denoise', nargs='?', type=_value_arg(DN.parse_denoise), const=DN.DEFAULTS, default=None, metavar='A[:B]',
+                    help='clean noisy input (DV, 576i / 480i captures, telecined broadcasts) on the GPU in front of the network: every sample '
+                         'becomes the rounded mean of itself and of the samples at its position in the frames before and after it, as far '
+                         'as they stay close.  Each side walks outward on its own and stops for good at the first sample that differs from '
+                         'the frame\'s own by more than A or brings the side\'s summed difference above B (8-bit steps, 0 <= A <= B <= 255, '
+                         'one pair for all planes; default %d:%d; A alone means A:2A; 0 changes nothing), so moving edges and cuts are left '
+                         'alone.  Behind --ivtc, --crop, --work-depth and --deinterlace (there over fields of the same parity), in front of '
+                         'everything else, scene scores included.  Not with --dedup or --deinterlace-mode adaptive.  Off by default'
+                         % DN.DEFAULTS)
+    ap.add_argument('--denoise-radius', type=int, default=None, metavar='R',
+                    help='with --denoise: the frames looked at on each side, 1 .. %d (default %d); costs R frames of lookahead, 2 R fields '
+                         'behind --deinterlace' % (DN.MAX_RADIUS, DN.DEFAULT_RADIUS))
     T.add_arguments(ap)
     return ap
 
@@ -1052,12 +1129,14 @@ def main(argv=None):
         check_interlace(a.interlace, a.interlace_lowpass)
         check_scale(a.scale, a.scale_filter, a.crop, crop_kw.get('crop_output', 'pad'))
         check_depths(a.work_depth, a.out_depth, a.dither)
+        check_denoise(a.denoise, a.denoise_radius, a.dedup or None, a.deinterlace_mode)
     except ValueError as e:
         parser().error(str(e))
     shutter_kw = {k: v for k, v in (('shutter', a.shutter), ('shutter_samples', a.shutter_samples), ('interlace', a.interlace),
                                     ('interlace_lowpass', a.interlace_lowpass), ('scale', a.scale),
                                     ('scale_filter', a.scale_filter), ('work_depth', a.work_depth), ('out_depth', a.out_depth),
-                                    ('dither', a.dither), ('shutter_window', a.shutter_window)) if v is not None}
+                                    ('dither', a.dither), ('shutter_window', a.shutter_window), ('denoise', a.denoise),
+                                    ('denoise_radius', a.denoise_radius)) if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     try:
         check_one_rank(world, dedup=a.dedup, ivtc=a.ivtc, shutter=a.shutter, interlace=a.interlace)
@@ -1103,8 +1182,8 @@ def main(argv=None):
     torch.cuda.synchronize()
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
     counts = [float(nw), float(nf), float(vr.last_st_frames), float(vr.last_instants[0]), float(vr.last_instants[1]),
-              float(vr.last_cut_windows), float(vr.last_depth_promoted), float(vr.last_depth_requantised)]
-    tw, tf, tst, ti, tp, tc, tdp, tdq = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
+              float(vr.last_cut_windows), float(vr.last_depth_promoted), float(vr.last_depth_requantised), float(vr.last_denoised)]
+    tw, tf, tst, ti, tp, tc, tdp, tdq, tdn = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
     if rank == 0:
         if a.crop is not None:
             print('demfi_amd.video: ' + vr.crop_report(), file=sys.stderr)
@@ -1118,6 +1197,8 @@ def main(argv=None):
             extra['windows_skipped'] = vr.last_windows_skipped
         if a.interlace is not None:
             extra['interlace'] = {'order': vr.last_interlace, 'lowpass': vr.interlace[1], 'carried': vr.last_interlace_carried}
+        if a.denoise is not None:
+            extra['denoise'] = {'a': vr.denoise[0], 'b': vr.denoise[1], 'radius': vr.denoise[2], 'frames': int(tdn)}
         if a.scale is not None:
             extra['scale'] = {'size': '%dx%d' % vr.scale[:2], 'filter': vr.scale[2], 'resized': vr.last_scale is not None,
                               'payloads': vr.last_scale_payloads}

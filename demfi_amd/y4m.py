@@ -605,7 +605,7 @@ class Frames:
     same tensor: the payload is read once and never copied.  ``first`` / ``stop``, ``n``, ``is_last``, ``windows`` and the
     dropping count fields; ``peak`` counts the payload tensors held.
     ``behind`` = b (default 0: nothing changes): for a consumer that also reads the b frames before every frame it names and the
-    frames after it (the motion-adaptive deinterlacer, b = 2 fields): the input starts b frames earlier (at frame 0 at the
+    frames after it (the motion-adaptive deinterlacer, b = 2 fields; the temporal denoiser, b = R frames or 2 R fields): the input starts b frames earlier (at frame 0 at the
     earliest) and b more frames are kept behind, so ``peak`` grows by at most the payloads those b frames and the b frames read
     ahead by ``has`` add."""
 

@@ -16,6 +16,7 @@ import torch
 from . import _lib as L
 from . import cadence as K
 from . import deint as I
+from . import denoise as DN
 from . import interlace as IL
 from . import retime as R
 from . import scale as SC
@@ -92,7 +93,13 @@ class Ingest:
     ``demfi_yuv_deint_adaptive`` launch per batch (at most 64 fields each) that also reads the kept rows of fields f-2, f-1, f+1 and f+2 out of THEIR
     slots, so those must have been uploaded (``around`` names them to the batch loop) but need not have been rebuilt, nor stay raw: a launch reads
     only kept rows and writes only missing ones (the hazard rule of csrc/deint.hip).  A field is rebuilt in the batch that first names it in a window
-    (or as the scene detector's predecessor frame); until then it is ``raw``.  No payload is uploaded more often than by the bob: once per field."""
+    (or as the scene detector's predecessor frame); until then it is ``raw``.  No payload is uploaded more often than by the bob: once per field.
+    ``spec.denoise`` = (A, B, R) (``demfi_amd.denoise``): behind the promotion and the bob ONE ``demfi_payload_denoise`` launch per batch (at most 64
+    frames each) writes the denoised payload of every frame the batch names for the first time into ``clean`` [nslot, Pb], slot for slot beside
+    ``yuv_in``, from the frames f - R step .. f + R step in yuv_in (step 2 over bobbed fields), which the denoiser alone reads from then on:
+    ``payloads`` is the buffer everything behind it reads.  The bookkeeping is the adaptive deinterlacer's with ``reach`` = R step in place of 2:
+    ``around`` names the frames to upload, a frame uploaded ahead of its window waits in ``raw``, ``rebuilt`` returns the frames just denoised."""
+    denoise = clean = None                           # without --denoise: no buffer, table or launch
 
     def __init__(self, runner, slots, spec, h, w, tiler=None):
         self.rn, self.slots, self.tiler, self.fh, self.fw = runner, slots, tiler, h, w
@@ -104,6 +111,11 @@ class Ingest:
         self.yuv_in = torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev)
         if self.adaptive:                            # five payload offsets per field rebuilt in a batch (at most nsl); reused in stream order
             self.dei_offs = torch.empty(5 * nsl, dtype=torch.int64, device=dev)
+        if spec.denoise is not None:                 # 2 R + 1 source offsets and one destination offset per frame denoised in a batch
+            a, b, self.radius = spec.denoise
+            self.denoise, self.step = DN.thresholds(spec.depth, a, b), 2 if spec.fields is not None else 1
+            self.clean = torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev)
+            self.dn_offs = torch.empty((2 * self.radius + 2) * nsl, dtype=torch.int64, device=dev)
         # a working depth above the input's (``spec.depths``, ``demfi_amd.bitdepth``): payloads are copied into ``staged`` at the input's sample
         # size, so H2D carries the input's bytes, and ``promote`` writes them into yuv_in at the working depth before anything else reads them
         self.staged, self.up, self.full_range = None, self.yuv_in, False     # full_range: the stream's, set by ``Y4mEdge.attach``
@@ -147,16 +159,49 @@ class Ingest:
         """The payloads just copied for the (frame, slot) pairs ``new`` become progressive payloads at the working depth: promoted first of
         all, then made progressive.  Returns the pairs that now are (adaptive: the fields just rebuilt, not those uploaded)."""
         self.promote(new, stream)
-        return self._adaptive(new, stream) if self.adaptive else self.bob(new, stream)
+        new = self._adaptive(new, stream) if self.adaptive else self.bob(new, stream)
+        return self._denoise(new, stream) if self.denoise is not None else new
+
+    payloads = property(lambda self: self.yuv_in if self.clean is None else self.clean, doc='the payloads everything behind the ingest reads')
+    reach = property(lambda self: DN.reach(self.radius, self.step == 2) if self.denoise is not None else 2 if self.adaptive else 0,
+                     doc='how far the frames a deferred launch reads lie from the frame it writes')
 
     def around(self, needed, has):
-        """Adaptive: the fields f-2 .. f+2 of every field f of ``needed`` not rebuilt yet, as far as the input has them (``has``)."""
-        if not self.adaptive:
+        """Adaptive, denoise: the frames f-reach .. f+reach of every frame f of ``needed`` not rebuilt / denoised yet, as far as the input has
+        them (``has``)."""
+        reach = self.reach
+        if not reach:
             return []
         needed = set(needed)
         self._needed, self._has = sorted(needed), has
         todo = [f for f in self._needed if f in self.raw or f not in self.slots.slot_of]
-        return sorted({g for f in todo for g in range(max(f - 2, 0), f + 3) if g not in needed and (g < f or has(g))})
+        return sorted({g for f in todo for g in range(max(f - reach, 0), f + reach + 1) if g not in needed and (g < f or has(g))})
+
+    def _denoise(self, new, stream):
+        """The frames of this batch that still wait get their denoised payloads in ``clean``; returns them as (frame, slot) pairs."""
+        slot_of, taps = self.slots.slot_of, 2 * self.radius + 1
+        self.raw.update(new)
+        self.raw = {f: sl for f, sl in self.raw.items() if slot_of.get(f) == sl}     # a slot the ring took back is forgotten
+        todo = [f for f in self._needed if f in self.raw]
+        done = 0
+        for c0 in range(0, len(todo), 64):
+            fs = todo[c0:c0 + 64]
+            offs = []
+            for f in fs:                             # a frame of the input that is not resident must not pass for an absent one
+                nb = DN.neighbours(f, self.radius, self.step, lambda g: g < f or self._has(g))
+                gone = [g for g in nb if g is not None and g not in slot_of]
+                if gone:
+                    raise RuntimeError('denoise: frame %d needs frame %d, which is not resident' % (f, gone[0]))
+                offs += [-1 if g is None else slot_of[g] * self.Pb for g in nb] + [slot_of[f] * self.Pb]
+            host = torch.tensor(offs, dtype=torch.int64).pin_memory()
+            od = self.dn_offs[(taps + 1) * done:(taps + 1) * (done + len(fs))]
+            od.copy_(host, non_blocking=True)
+            L.check(self.rn.lib.demfi_payload_denoise(self.yuv_in.data_ptr(), self.yuv_in.numel(), host.data_ptr(), od.data_ptr(), len(fs), taps,
+                                                      self.P, self.es, *self.denoise, self.clean.data_ptr(), self.clean.numel(),
+                                                      stream.cuda_stream), 'payload_denoise')
+            done += len(fs)
+        self.rn.denoised += len(todo)
+        return [(f, self.raw.pop(f)) for f in todo]
 
     def _adaptive(self, new, stream):
         """The fields of this batch that are still raw become progressive frames in place; returns them as (field, slot) pairs."""
@@ -186,7 +231,7 @@ class Ingest:
         """The progressive payloads of the (frame, slot) pairs ``new`` -> their BGR frame slots (and tiles)."""
         sls = [sl for _, sl in new]
         for s0, cnt in consecutive(sls):
-            self.to_bgr(self.yuv_in[s0].data_ptr(), self.slots.frames[s0].data_ptr(), cnt, stream.cuda_stream)
+            self.to_bgr(self.payloads[s0].data_ptr(), self.slots.frames[s0].data_ptr(), cnt, stream.cuda_stream)
         if self.tiler is not None:
             self.tiler.crop(sls, stream)
 
@@ -207,12 +252,13 @@ class SceneScores:
         Frame j-1 is resident: it was uploaded in this batch or in the previous one (windows are consecutive), and a slot is
         reused only after all nslot >= 2 * batch + 8 slots have been (adaptive deinterlacing: nslot >= 2 * batch + 12, and batch b
         uploads up to frame k + 2 * batch + 4, its two fields of lookahead included, so it takes back the slots of frames up to
-        k - 8 at most, while batch b-1 reads frames from k - 1 on and its rebuild launches, queued on h2d before, from k - 3 on).
+        k - 8 at most, while batch b-1 reads frames from k - 1 on and its rebuild launches, queued on h2d before, from k - 3 on;
+        denoising: the same with its reach in place of 2, nslot >= 2 * batch + 8 + 2 * reach; the SADs are those of the denoised payloads).
         The wait does not wait on the compute stream: the
         ``busy`` waits queued on h2d before this batch's copies are on the compute of the batch that last read a reused
         slot, and that batch is at least two back (batch b-1 reads frames k .. k + batch + 2 of its first window k, batch b
         uploads frames up to k + 2 * batch + 2 only), so the host already waited for it when it drained that batch's D2H."""
-        det, slot_of, P, yuv_in = self.det, self.slots.slot_of, self.ingest.P, self.ingest.yuv_in
+        det, slot_of, P, yuv_in = self.det, self.slots.slot_of, self.ingest.P, self.ingest.payloads
         js = sorted(j for j in new_frames if j >= det.next)
         if not js:
             return

@@ -461,6 +461,27 @@ int demfi_yuv_bob(void* payloads, int64_t stride_bytes, int n, int h, int w, int
 int demfi_yuv_deint_adaptive(void* base, int64_t size_bytes, const int64_t* offsets, const int64_t* offsets_dev, int n, int h, int w,
                              int layout, int sample_bytes, uint64_t odd_mask, void* stream);
 
+/* ---- temporal denoising of the Y4M edge (csrc/denoise.hip; demfi_amd/video.py --denoise) --------------------------------------------
+ * payload_denoise: frame i (n = 0..64 per launch) has taps + 1 int64 BYTE offsets, offsets[i*(taps+1) .. i*(taps+1) + taps]: first the
+ * taps = 2 R + 1 (3, 5 or 7) payloads of frames f - R step .. f + R step of the stream in that order, offsets from src, -1 for a frame
+ * the stream does not have (the centre, entry R, must be present), then the offset from dst at which the denoised payload of f is
+ * written.  A payload is one flat array of P stored samples (sample_bytes = 1, or 2 for 16-bit little-endian samples: even addresses and
+ * offsets): layout, depth, matrix and range do not matter.  With c the centre's sample, each side walks outward from the centre on its
+ * own, adds up d = |x - c| and stops for good at the first absent payload, the first d > thr_a or the first accumulated d > thr_b; the
+ * output is (2 * sum + k) / (2 * k) over c and the k - 1 samples taken before the stops, round half up, exact integers; the numpy
+ * definition is demfi_amd/denoise.py denoise_payload_np (thr_a, thr_b: its thresholds at the stream's depth, 0 <= thr_a <= thr_b <= 255
+ * for bytes, <= 65535 for 16-bit samples).  src is only read and dst only written.  The offsets are passed twice with the same content:
+ * offsets in HOST memory, checked here before anything is launched, and offsets_dev in DEVICE memory, read by the kernel.
+ * DEMFI_ERR_ARG, with nothing launched: a NULL buffer, n outside 0..64, taps not 3, 5 or 7, sample_bytes not 1 or 2, thresholds out of
+ * range, P outside 1..2^40, 16-bit samples at an odd address or offset, an offset below -1, an absent centre, a payload that leaves
+ * src .. src + src_bytes or dst .. dst + dst_bytes, two frames whose destinations overlap, src and dst buffers that overlap.  When src +
+ * every present offset and dst + every destination offset are multiples of 16 every thread makes 16 output bytes from 16-byte loads and
+ * one 16-byte store (the last P * sample_bytes mod 16 bytes of a payload sample by sample); otherwise the whole launch goes sample by
+ * sample with the same arithmetic.  Every offset and index is 64-bit.  One launch for all n frames, no LDS, no atomics, plain stores;
+ * n == 0 does nothing. */
+int demfi_payload_denoise(const uint8_t* src, int64_t src_bytes, const int64_t* offsets, const int64_t* offsets_dev, int n, int taps,
+                          int64_t P, int sample_bytes, int thr_a, int thr_b, uint8_t* dst, int64_t dst_bytes, void* stream);
+
 /* ---- inverse telecine of the Y4M edge (csrc/ivtc.hip; demfi_amd/video.py --ivtc) ------------------------------------------------
  * A woven frame W(top, bot) has the even rows of the luma plane (the first h*w samples of a payload; sample_bytes = 1, or 2 for
  * 16-bit little-endian samples) of payload `top` and the odd rows of that of payload `bot`; it is read in place, never built.
