@@ -20,6 +20,7 @@ import torch
 from . import _lib as L
 from . import bitdepth as BD
 from . import cadence as K
+from . import colour as CL
 from . import deint as I
 from . import denoise as DN
 from . import interlace as IL
@@ -52,9 +53,12 @@ class EdgeSpec(_EdgeFields):
     mean the WORKING depth, the payloads come in at the input's and leave at the output's; three equal depths are None;
     ``shutter_window``: None (the box) or 'triangle', the weights of a shutter's mix (``shutter.window_weights``; only with ``shutter``);
     ``denoise``: None or (A, B, R) of the temporal denoiser in front of the network (``demfi_amd.denoise``: thresholds at the 8-bit scale, frames
-    on each side), kept beside the tuple like the others.  ``reach``: how far the frames an ingest stage reads lie from the frame it writes.
+    on each side), kept beside the tuple like the others;
+    ``colour``: None or (transfer of ``colour.TRANSFERS`` or None, output matrix 'bt601' / 'bt709' or None, output full range or None) of
+    ``demfi_amd.colour``: linear light for the mix and the scaler, and the matrix and range written where they differ from the input's
+    (three times None is None), kept beside the tuple like ``scale`` and ``denoise``.  ``reach``: how far the frames an ingest stage reads lie from the frame it writes.
     Hashable: (batch, spec) is what a cached ``ClipPipeline`` can be reused for.
-    ``shutter``, ``interlace``, ``scale``, ``depths``, ``shutter_window`` and ``denoise`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
+    ``shutter``, ``interlace``, ``scale``, ``depths``, ``shutter_window``, ``denoise`` and ``colour`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
     without them is, item for item, the record it was before there were any, and one with any of them equals no plain tuple.  What the namedtuple makes
     from its items alone does not know them: ``_make``, ``_asdict`` and pickling drop them; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
     shutter = None
@@ -63,9 +67,12 @@ class EdgeSpec(_EdgeFields):
     depths = None
     shutter_window = None
     denoise = None
+    colour = None
 
-    def __new__(cls, *args, shutter=None, interlace=None, scale=None, depths=None, shutter_window=None, denoise=None, **kw):
+    def __new__(cls, *args, shutter=None, interlace=None, scale=None, depths=None, shutter_window=None, denoise=None, colour=None, **kw):
         self = super().__new__(cls, *args, **kw)
+        if colour is not None and any(v is not None for v in colour):     # three times None is the spec without the field
+            self.colour = (colour[0], colour[1], None if colour[2] is None else bool(colour[2]))
         if denoise is not None:
             self.denoise = tuple(int(v) for v in denoise)
         if shutter_window not in (None, 'box'):      # the box is the spec without the field
@@ -83,14 +90,15 @@ class EdgeSpec(_EdgeFields):
     def _replace(self, **kw):
         shutter, interlace, scale = kw.pop('shutter', self.shutter), kw.pop('interlace', self.interlace), kw.pop('scale', self.scale)
         depths, window, denoise = kw.pop('depths', self.depths), kw.pop('shutter_window', self.shutter_window), kw.pop('denoise', self.denoise)
+        colour = kw.pop('colour', self.colour)
         return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace, scale=scale, depths=depths, shutter_window=window,
-                          denoise=denoise)
+                          denoise=denoise, colour=colour)
 
     def __eq__(self, other):
         return (tuple.__eq__(self, other) is True and self.shutter == getattr(other, 'shutter', None)
                 and self.interlace == getattr(other, 'interlace', None) and self.scale == getattr(other, 'scale', None)
                 and self.depths == getattr(other, 'depths', None) and self.shutter_window == getattr(other, 'shutter_window', None)
-                and self.denoise == getattr(other, 'denoise', None))
+                and self.denoise == getattr(other, 'denoise', None) and self.colour == getattr(other, 'colour', None))
 
     def __ne__(self, other):
         return not self == other
@@ -100,14 +108,16 @@ class EdgeSpec(_EdgeFields):
         key = key if self.scale is None else key + ('scale', self.scale)
         key = key if self.depths is None else key + ('depths', self.depths)
         key = key if self.shutter_window is None else key + ('shutter_window', self.shutter_window)
-        return hash(key if self.denoise is None else key + ('denoise', self.denoise))
+        key = key if self.denoise is None else key + ('denoise', self.denoise)
+        return hash(key if self.colour is None else key + ('colour', self.colour))
 
     def __repr__(self):
         return super().__repr__()[:-1] + ', shutter=%r%s%s)' % (self.shutter, ', interlace=%r' % (self.interlace,) if self.interlace is not None else '',
                                                                (', scale=%r' % (self.scale,) if self.scale is not None else '')
                                                                + (', depths=%r' % (self.depths,) if self.depths is not None else '')
                                                                + (', shutter_window=%r' % self.shutter_window if self.shutter_window is not None else '')
-                                                               + (', denoise=%r' % (self.denoise,) if self.denoise is not None else ''))
+                                                               + (', denoise=%r' % (self.denoise,) if self.denoise is not None else '')
+                                                               + (', colour=%r' % (self.colour,) if self.colour is not None else ''))
 
     @classmethod
     def of(cls, yuv):
@@ -117,7 +127,7 @@ class EdgeSpec(_EdgeFields):
                    getattr(yuv, 'layout', '420'), tuple(dedup) if dedup is not None else None, fields,
                    getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob', shutter=getattr(yuv, 'shutter', None),
                    interlace=getattr(yuv, 'interlace', None), scale=getattr(yuv, 'scale', None), depths=getattr(yuv, 'depths', None),
-                   shutter_window=getattr(yuv, 'shutter_window', None), denoise=getattr(yuv, 'denoise', None))
+                   shutter_window=getattr(yuv, 'shutter_window', None), denoise=getattr(yuv, 'denoise', None), colour=getattr(yuv, 'colour', None))
 
     hi = property(lambda self: self.depth > 8, doc='16-bit frames: the samples of a stream above 8 bits')
     reach = property(lambda self: DN.reach(self.denoise[2], self.fields is not None) if self.denoise is not None
@@ -128,7 +138,7 @@ class EdgeSpec(_EdgeFields):
         """Every rule about what goes together, before anything is allocated, for a run on a ``retimed`` runner (built with a ratio)."""
         other, edge_only = self.deint_mode != 'bob', self.hi or self.dedup is not None or self.fields is not None
         deint = deint_conflict(self.deint_mode, self.fields is not None, self.dedup is not None)
-        sh, il, sc, dp, win, dn = self.shutter, self.interlace, self.scale, self.depths, self.shutter_window, self.denoise
+        sh, il, sc, dp, win, dn, co = self.shutter, self.interlace, self.scale, self.depths, self.shutter_window, self.denoise, self.colour
         for bad, what in ((self.fields not in (None, 't', 'b'), "fields must be None, 't' or 'b', got %r" % (self.fields,)),
                           (deint, 'deint_mode %r with fields=%r, dedup=%r' % (self.deint_mode, self.fields, self.dedup)),
                           (edge_only and not self.y4m, '16-bit frames, repeated frames and fields are those of the Y4M edge (yuv=...) only'),
@@ -164,7 +174,14 @@ class EdgeSpec(_EdgeFields):
                           (dn is not None and self.dedup is not None,
                            'the denoiser does not go with repeated frames (dedup): kept frames are staged one at a time, without look-ahead'),
                           (dn is not None and other,
-                           'the denoiser does not go with deint_mode %r: two deferred look-ahead stages in a row' % (self.deint_mode,))):
+                           'the denoiser does not go with deint_mode %r: two deferred look-ahead stages in a row' % (self.deint_mode,)),
+                          (co is not None and not (len(co) == 3 and co[0] in (None,) + CL.TRANSFERS and co[1] in (None,) + tuple(CL.y4m.MATRICES)),
+                           'colour must be None or (transfer of %s or None, out matrix of %s or None, out full range or None), got %r'
+                           % (CL.TRANSFERS, tuple(CL.y4m.MATRICES), co)),
+                          (co is not None and not (retimed and self.y4m), 'linear light and an output matrix or range need the Y4M edge on a retimed runner'),
+                          (co is not None and co[0] is not None and self.depth > CL.MAX_DEPTH,
+                           'linear light needs a working depth of at most %d bits, got %d: above, 16 bits of light do not tell the codes apart'
+                           % (CL.MAX_DEPTH, self.depth))):
             if bad:
                 raise ValueError('WindowRunner.run_clip_u8: ' + what)
 

@@ -143,7 +143,7 @@ next, so it works with every switch above and with several ranks (as far as the 
 grid (rows in units of 2, of 4 for 4:2:0).  A shrink is limited to 32 taps an axis (16:3 with lanczos3, 8:1 bicubic, 16:1 bilinear).  A
 size equal to the run's own builds no stage and gives the bytes of a run without the switch.  Not offered: scaling in front of the
 network (cheaper for a shrink), chroma siting offsets (chroma planes are resampled centre-aligned, as planes in their own right),
-``-1`` / keep-aspect sizes, linear-light resampling, ``demfi_amd.clip``, numeric equality with swscale or zimg.  Without the switch no
+``-1`` / keep-aspect sizes, ``demfi_amd.clip``, numeric equality with swscale or zimg (linear-light resampling: ``--linear-light``).  Without the switch no
 buffer, launch or stream is added and every byte stays the same.
 
 ``--work-depth W`` and ``--out-depth D`` (8, 10, 12, 14 or 16 each) with ``--dither bayer|none`` (default ``bayer``) choose the stream's bit
@@ -163,8 +163,19 @@ taken; an 8-bit input with a deeper working depth runs on the 16-bit frame path 
 ``--ivtc`` and ``--crop auto`` decide in front of the device stages on the input's own samples, at the input's depth.  Both stages keep
 nothing between payloads: every switch above and several ranks work.  Refused: W below the input's depth, D above W, ``--dither`` where
 nothing is requantised.  Depths that resolve to the input's build no stage, no buffer and no launch and give the bytes of a run without the
-switches.  Not offered: error diffusion, random or blue-noise dither, patterns that change from frame to frame, ``demfi_amd.clip``, changing
-the range or the matrix on the way.
+switches.  Not offered: error diffusion, random or blue-noise dither, patterns that change from frame to frame, ``demfi_amd.clip`` (changing
+the range or the matrix on the way: ``--out-matrix`` / ``--out-range``).
+
+``--linear-light [bt709|srgb]``, ``--out-matrix auto|bt601|bt709`` and ``--out-range limited|full`` (``demfi_amd.colour``): with
+``--linear-light`` the shutter's mix and the scaler work on light, not on the stored, gamma-encoded samples: the gather writes linear
+payloads (uint16 planes B, G, R through the inverse OETF's table), the unchanged mix and scale kernels run on those, and an encode stage
+takes them back, gather-to-linear -> mix -> scale -> encode -> weave -> requant (csrc/colour.hip ``demfi_bgr_to_linear_gather`` /
+``demfi_linear_to_yuv``, defined by ``colour.linearize_np`` / ``colour.encode_payload_np``).  Working depths 8, 10 and 12 (above: refused
+once the header is known); without ``--shutter`` or an effective ``--scale`` it builds nothing.  ``--out-matrix`` / ``--out-range`` bind the
+gather (or the encode) to another matrix and range than the input's; ``auto`` is BT.709 when the height written is 720 or more; the
+requantisation, the black of ``--crop-output pad`` and the header's XCOLORRANGE follow the range written, everything in front of the network
+keeps the input's.  Not offered: primaries / gamut conversion, PQ and HLG, linear-light ``--interlace-lowpass`` or ``--denoise``, a matrix
+tag (Y4M has none), ``demfi_amd.clip``.  Without the three switches no buffer, table, launch or stream is added and every byte stays the same.
 
 ``--denoise [A[:B]]`` with ``--denoise-radius R`` (1 .. 3, default 2) cleans noisy input in front of the network (``demfi_amd.denoise``): a
 deblurring network sharpens grain and tape noise with everything else, and noise that differs from frame to frame is motion that is not
@@ -195,6 +206,7 @@ import torch
 from . import _lib as L
 from . import bitdepth as BD
 from . import cadence as K
+from . import colour as CL
 from . import deint as I
 from . import denoise as DN
 from . import dist as D
@@ -226,12 +238,17 @@ class YuvEdge:
     payloads handed out have that size.  ``depths``: None, or (input depth, working depth, output depth, dither mode or None) of
     ``bitdepth.resolve``: the payloads handed in have the input's depth, ``depth`` is then the WORKING depth, and the payloads handed out
     have the output's.  ``shutter_window``: None ('box') or 'triangle', the weights of the shutter's mix (``shutter.window_weights``); an
-    error without ``shutter``.  ``denoise``: None, or (A, B, R) of the temporal denoiser in front of the network (``demfi_amd.denoise``)."""
+    error without ``shutter``.  ``denoise``: None, or (A, B, R) of the temporal denoiser in front of the network (``demfi_amd.denoise``).
+    ``linear_light``: None, or the transfer ('bt709' / 'srgb'; True: 'bt709') through which the mix and the scaler work in linear light
+    (``demfi_amd.colour``); ``out_matrix`` ('bt601' / 'bt709') and ``out_range`` ('limited' / 'full'): None, or the matrix and range of the
+    payloads handed out, where ``matrix`` and ``full_range`` are those of the payloads handed in.  ``colour`` = (transfer, out matrix, out
+    full range), or None without the three."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
                  fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None,
-                 depths=None, shutter_window=None, denoise=None):
+                 depths=None, shutter_window=None, denoise=None, linear_light=None, out_matrix=None, out_range=None):
         self.dedup, self.shutter = dedup, shutter
+        self.colour = check_colour(linear_light, out_matrix, out_range)
         self.denoise = None if denoise is None else DN.check_params(*denoise)
         self.shutter_window = check_shutter_window(shutter, shutter_window)
         self.depths = None if BD.is_noop(depths) else tuple(depths)
@@ -336,6 +353,17 @@ def check_scale(scale, scale_filter=None, crop=None, crop_output='pad'):
     return w, h, SC.check_filter(scale_filter)
 
 
+def check_colour(linear_light=None, out_matrix=None, out_range=None, auto=False):
+    """The colour switches checked: None without them, or (transfer or None, out matrix or None, out full range or None).  'auto' as the
+    output matrix is the ``VideoRunner``'s to resolve (it knows the height written): only with ``auto``."""
+    transfer, matrix, rng = CL.check_switches(linear_light, out_matrix, out_range)
+    if matrix == 'auto' and not auto:
+        raise ValueError("out_matrix='auto' is resolved by VideoRunner from the height written; give 'bt601' or 'bt709' here")
+    if transfer is None and matrix is None and rng is None:
+        return None
+    return transfer, matrix, None if rng is None else rng == 'full'
+
+
 def check_depths(work_depth=None, out_depth=None, dither=None):
     """The bit-depth switches checked as far as they can be before a header is known (``bitdepth.check_switches``): depths of
     ``y4m.DEPTHS``, D <= W, and ``dither`` ('bayer' / 'none'; None: 'bayer') says how a requantisation rounds, so it is an error without
@@ -375,6 +403,8 @@ def check_denoise(denoise, radius=None, dedup=None, deinterlace_mode='bob'):
 COUNTERS = {'instants_run': None, 'instants_padded': None, 'shutter_mixed': None, 'cut_windows': 'last_cut_windows',
             'shutter_carried': 'last_shutter_carried', 'interlace_carried': 'last_interlace_carried', 'scale_payloads': 'last_scale_payloads',
             'depth_promoted': 'last_depth_promoted', 'depth_requantised': 'last_depth_requantised'}
+# and of the egress stages that came after: linear light (``y4m_edge.Encoder``)
+EGRESS_COUNTERS = {'colour_encoded': 'last_colour_encoded'}
 # the counters of the ingest stages that came after those: kept the same way, in a table of their own
 INGEST_COUNTERS = {'denoised': 'last_denoised'}
 
@@ -486,7 +516,11 @@ class VideoRunner:
     an error).  Every frame is denoised on the GPU behind the promotion and the bob (csrc/denoise.hip ``demfi_payload_denoise``, ONE launch
     per batch) and everything behind that, scene cuts included, runs on the denoised stream.  Not with ``dedup`` or
     ``deinterlace_mode='adaptive'`` (refused here).  Any number of ranks.  After a run ``last_denoised`` = the frames denoised.  Without it
-    no buffer, table, launch or slot is added and every byte stays the same."""
+    no buffer, table, launch or slot is added and every byte stays the same.  ``linear_light``: None (default), True / 'bt709' or
+    'srgb': the shutter's mix and the scaler work in linear light through that transfer (``demfi_amd.colour``); ``out_matrix``: None (the
+    input's), 'auto' (by the height written), 'bt601' or 'bt709'; ``out_range``: None (the input's), 'limited' or 'full'.  Linear light at a
+    working depth above 12 bits is refused once the header is known.  After a run ``last_colour`` = (transfer or None, matrix, full range)
+    the run wrote with, or None without the three, and ``last_colour_encoded`` = the payloads the encode stage took back."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
@@ -494,8 +528,11 @@ class VideoRunner:
                  ivtc_combpel=TC.DEFAULT_COMBPEL, ivtc_combed=TC.DEFAULT_COMBED, crop=None, crop_limit=LB.DEFAULT_LIMIT,
                  crop_noise=LB.DEFAULT_NOISE, crop_probe=LB.DEFAULT_PROBE, crop_output='pad', shutter=None,
                  shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, work_depth=None,
-                 out_depth=None, dither=None, down=False, shutter_window=None, denoise=None, denoise_radius=None, **runner_kw):
+                 out_depth=None, dither=None, down=False, shutter_window=None, denoise=None, denoise_radius=None, linear_light=None,
+                 out_matrix=None, out_range=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.colour = check_colour(linear_light, out_matrix, out_range, auto=True)   # (transfer, out matrix or 'auto', out full range) or None
+        self.last_colour = None
         self.denoise = check_denoise(denoise, denoise_radius, dedup, deinterlace_mode)   # (A, B, R) or None
         self.down = bool(down)
         self.work_depth, self.out_depth, self.dither = check_depths(work_depth, out_depth, dither)
@@ -505,7 +542,7 @@ class VideoRunner:
         self.shutter_window = check_shutter_window(self.shutter, shutter_window)     # 'box' / 'triangle', None without a shutter
         self.last_depths = self.last_scale = self.last_interlace = self.last_shutter = self.last_shutter_window = None
         self.last_windows_skipped = 0
-        for attr in filter(None, list(COUNTERS.values()) + list(INGEST_COUNTERS.values())):
+        for attr in filter(None, list(COUNTERS.values()) + list(INGEST_COUNTERS.values()) + list(EGRESS_COUNTERS.values())):
             setattr(self, attr, 0)
         self.crop, (self.crop_limit, self.crop_noise, self.crop_probe, self.crop_output) = check_crop(
             crop, crop_limit, crop_noise, crop_probe, crop_output)
@@ -588,8 +625,28 @@ class VideoRunner:
             ohdr = SC.scaled_header(ohdr, sc[0], sc[1])
         if self.interlace is not None:               # the same stream as fields: the I tag of the order, half the rate
             ohdr = IL.interlaced_header(ohdr, self.interlace[0])
+        if self.colour is not None:                  # the range written; Y4M has no tag for the matrix
+            ohdr = CL.range_header(ohdr, self._colour_of(hdr)[2])
         self.last_fps_out = ohdr.fps
         return ohdr
+
+    def _in_matrix(self, hdr):
+        """The matrix of the input: ``matrix``, 'auto' by the input's own height (a cropped run: the full frame's)."""
+        return y4m.auto_matrix(self._matrix_h or hdr.h) if self.matrix == 'auto' else self.matrix
+
+    def _colour_of(self, hdr):
+        """(transfer or None, matrix, full range) the run on frames of ``hdr`` writes with, or None without the colour switches;
+        ``colour.resolve``: 'auto' goes by the height actually written -- behind the scaler, and with ``crop_output`` 'pad' the full
+        frame's.  Before anything is allocated: linear light at a working depth above 12 bits is refused."""
+        if self.colour is None:
+            return None
+        transfer, matrix, full = self.colour
+        if transfer is not None:
+            CL.check_depth(self._depths_of(hdr)[1])
+        sc = self._scale_of(hdr)
+        out_h = sc[1] if sc is not None else (self._matrix_h or hdr.h) if self.crop_output == 'pad' else hdr.h
+        matrix, full = CL.resolve(matrix, None if full is None else 'full' if full else 'limited', self._in_matrix(hdr), hdr.full_range, out_h)
+        return transfer, matrix, full
 
     def _n_out(self, n_in, hdr):
         """Payloads written for n_in input frames: the output frames, or with ``interlace`` their pairs."""
@@ -712,6 +769,10 @@ class VideoRunner:
         out = self._depths_of(cropper.full)[2]
         if out != cropper.full.depth:                # the payloads written have the output's depth: so have the bars and their black
             cropper = LB.Cropper(BD.depth_header(cropper.full, out), cropper.rect)
+        if self.colour is not None:                  # and the range written: its black
+            full = cropper.full.full_range if self.colour[2] is None else self.colour[2]
+            if full != cropper.full.full_range:
+                cropper = LB.Cropper(CL.range_header(cropper.full, full), cropper.rect)
 
         def pad_sink(k, payloads):
             full = np.empty((len(payloads), cropper.Pf), np.uint8)
@@ -736,6 +797,7 @@ class VideoRunner:
                              'depth do not go together unless asked for; run it untiled, %s, or pass '
                              '--tile-high-depth (tile_high_depth=True)' % (self.tile, what, 'convert the input to 8 bits' if work == d_in
                                                                            else 'work at 8 bits'))
+        self._colour_of(hdr)                         # linear light above 12 bits is refused here
         self.last_depths = None if BD.is_noop(depths) else depths
         self.last_depth, self.last_layout = out, hdr.layout
 
@@ -764,7 +826,7 @@ class VideoRunner:
         """fn() runs windows lo, lo+1, ... of the input on cr, lo = first() once it has run; returns its window count and sets
         the per-run counters."""
         rn = cr.runner
-        before, skipped = {name: getattr(rn, name) for name in (*COUNTERS, *INGEST_COUNTERS)}, rn.windows_skipped
+        before, skipped = {name: getattr(rn, name) for name in (*COUNTERS, *INGEST_COUNTERS, *EGRESS_COUNTERS)}, rn.windows_skipped
         with cr.oversize_hint():
             n = fn()
         lo, r = first(), self._ratio(hdr)
@@ -779,8 +841,9 @@ class VideoRunner:
         for name, attr in COUNTERS.items():
             if attr is not None:
                 setattr(self, attr, added[name])
-        for name, attr in INGEST_COUNTERS.items():
+        for name, attr in (*INGEST_COUNTERS.items(), *EGRESS_COUNTERS.items()):
             setattr(self, attr, added.get(name, 0))
+        self.last_colour = self._colour_of(hdr)
         self.last_instants, self.last_cuts = (added['instants_run'], added['instants_padded']), cuts
         self.last_st_frames = added['shutter_mixed'] if self.shutter is not None else st_frames     # the fine frames that went into the mixes
         self.last_shutter, self.last_scale, self.last_shutter_window = self.shutter, self._scale_of(hdr), self.shutter_window
@@ -788,10 +851,12 @@ class VideoRunner:
 
     def _edge(self, hdr, with_s1, order=None):
         depths = self._depths_of(hdr)                # hdr has the input's depth; the edge works at depths[1]
-        return YuvEdge(y4m.auto_matrix(self._matrix_h or hdr.h) if self.matrix == 'auto' else self.matrix, hdr.full_range, hdr.chroma, with_s1,
+        colour = self._colour_of(hdr)
+        kw = {} if colour is None else {'linear_light': colour[0], 'out_matrix': colour[1], 'out_range': 'full' if colour[2] else 'limited'}
+        return YuvEdge(self._in_matrix(hdr), hdr.full_range, hdr.chroma, with_s1,
                        self.scene_cut, self.full_length, depths[1], hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
                        *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths, shutter_window=self.shutter_window,
-                       denoise=self.denoise)
+                       denoise=self.denoise, **kw)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
@@ -1101,6 +1166,17 @@ def parser():
     ap.add_argument('--denoise-radius', type=int, default=None, metavar='R',
                     help='with --denoise: the frames looked at on each side, 1 .. %d (default %d); costs R frames of lookahead, 2 R fields '
                          'behind --deinterlace' % (DN.MAX_RADIUS, DN.DEFAULT_RADIUS))
+    ap.add_argument('--linear-light', nargs='?', const=CL.TRANSFERS[0], default=None, choices=list(CL.TRANSFERS), metavar='TRANSFER',
+                    help='mix (--shutter) and resample (--scale) light, not stored samples: the frames behind the network are taken to '
+                         'scene-linear light through the inverse of TRANSFER (bt709: the BT.709 / BT.601 / BT.2020-SDR OETF, the default; '
+                         'srgb), the mix and the scaler work on 16-bit linear B, G, R planes, and an encode stage takes the result back, so a '
+                         'bright object over a dark ground smears as on a real shutter and fine bright detail keeps its brightness when it '
+                         'shrinks.  Working depths 8, 10 and 12; without --shutter or --scale it builds nothing.  Off by default')
+    ap.add_argument('--out-matrix', default=None, choices=list(CL.OUT_MATRICES),
+                    help='YCbCr matrix of the OUTPUT (default: the input\'s, --matrix); auto: BT.709 when the height written is >= 720, else '
+                         'BT.601, so --scale 1920x1080 of an SD stream leaves as BT.709.  Y4M has no tag for it')
+    ap.add_argument('--out-range', default=None, choices=list(CL.OUT_RANGES),
+                    help='range of the OUTPUT (default: the input\'s); the header gets XCOLORRANGE=FULL or LIMITED when the range changes')
     T.add_arguments(ap)
     return ap
 
@@ -1130,13 +1206,15 @@ def main(argv=None):
         check_scale(a.scale, a.scale_filter, a.crop, crop_kw.get('crop_output', 'pad'))
         check_depths(a.work_depth, a.out_depth, a.dither)
         check_denoise(a.denoise, a.denoise_radius, a.dedup or None, a.deinterlace_mode)
+        check_colour(a.linear_light, a.out_matrix, a.out_range, auto=True)
     except ValueError as e:
         parser().error(str(e))
     shutter_kw = {k: v for k, v in (('shutter', a.shutter), ('shutter_samples', a.shutter_samples), ('interlace', a.interlace),
                                     ('interlace_lowpass', a.interlace_lowpass), ('scale', a.scale),
                                     ('scale_filter', a.scale_filter), ('work_depth', a.work_depth), ('out_depth', a.out_depth),
                                     ('dither', a.dither), ('shutter_window', a.shutter_window), ('denoise', a.denoise),
-                                    ('denoise_radius', a.denoise_radius)) if v is not None}
+                                    ('denoise_radius', a.denoise_radius), ('linear_light', a.linear_light), ('out_matrix', a.out_matrix),
+                                    ('out_range', a.out_range)) if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     try:
         check_one_rank(world, dedup=a.dedup, ivtc=a.ivtc, shutter=a.shutter, interlace=a.interlace)
@@ -1202,6 +1280,9 @@ def main(argv=None):
         if a.scale is not None:
             extra['scale'] = {'size': '%dx%d' % vr.scale[:2], 'filter': vr.scale[2], 'resized': vr.last_scale is not None,
                               'payloads': vr.last_scale_payloads}
+        if vr.last_colour is not None:
+            extra['colour'] = {'linear_light': vr.last_colour[0], 'matrix': vr.last_colour[1], 'range': 'full' if vr.last_colour[2] else 'limited',
+                               'encoded': vr.last_colour_encoded}
         depth = vr.last_depth                        # the depth written; with a depth switch the whole story
         if any(v is not None for v in (a.work_depth, a.out_depth, a.dither)) and vr.last_depths is not None:
             depth = {'in': vr.last_depths[0], 'work': vr.last_depths[1], 'out': vr.last_depths[2], 'dither': vr.last_depths[3],

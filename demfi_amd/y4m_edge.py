@@ -1,7 +1,8 @@
 """The Y4M edge of the clip pipeline (``demfi_amd.pipeline``): Y4M payloads in and out, every window on its own plan, all options in
 one ``pipeline.EdgeSpec``.  One stage per job, each with its own buffers: ``Ingest``, ``SceneScores``, ``DedupProbe``, the pure function
 ``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, the ``Stage`` chain that ``egress_layout`` sizes: ``Shutter``,
-``Scaler``, ``Interlacer`` and ``Requantizer``, in that order, each only when ``spec`` asks for it; ``Y4mEdge`` loops over them and keeps the
+``Scaler``, ``Encoder`` (linear light: the gather then writes linear payloads, ``demfi_amd.colour``), ``Interlacer`` and ``Requantizer``, in
+that order, each only when ``spec`` asks for it; ``Y4mEdge`` loops over them and keeps the
 payloads' way out.
 
 The buffer rule of the chain: a stage reads its payloads from row ``lead`` of its source buffer on (the ``lead`` rows in front are where it
@@ -15,6 +16,7 @@ import torch
 
 from . import _lib as L
 from . import cadence as K
+from . import colour as CL
 from . import deint as I
 from . import denoise as DN
 from . import interlace as IL
@@ -52,8 +54,18 @@ def consecutive(sls):
         r = e
 
 
+def egress_colour(spec, yuv):
+    """(matrix code, full range 0 / 1) of the payloads written: those of ``spec.colour`` = (transfer, out matrix, out full range) where it names
+    them (``--out-matrix`` / ``--out-range``), else the stream's (``yuv``).  Everything behind the gather that knows the range uses these;
+    everything in front of the network keeps the input's."""
+    _, matrix, full = spec.colour or (None, None, None)
+    return ({'bt601': L.BT601, 'bt709': L.BT709}[matrix] if matrix is not None else yuv.matrix,
+            int(yuv.full_range if full is None else full))
+
+
 def yuv_calls(lib, spec, h, w, yuv):
-    """The three launches of the Y4M edge for h x w frames of ``spec``'s depth and layout, bound to the stream's matrix, range and siting (``yuv``):
+    """The three launches of the Y4M edge for h x w frames of ``spec``'s depth and layout, bound to the stream's matrix, range and siting (``yuv``;
+    the gather, which makes every written sample, to ``egress_colour``: without ``spec.colour`` the same):
     to_bgr(src, dst, cnt, stream) converts cnt consecutive payloads to BGR frames, gather(base, offs, dst, n, stream) converts the n frames at base +
     offs[] to consecutive payloads, sad(base, a, b, m, out, stream) scores m payload pairs. Pointers are addresses; every stride and offset counts
     samples, which are bytes at depth 8.  4:2:0 has C functions of its own (8-bit: csrc/yuv.hip), 4:2:2, 4:4:4 and mono those of the layouts family,
@@ -66,13 +78,13 @@ def yuv_calls(lib, spec, h, w, yuv):
     names += ('yuv420p16_sad' if hi else 'yuv420_sad',)
     c_bgr, c_gather, c_sad = (getattr(lib, 'demfi_' + nm) for nm in names)
     fmt = ((spec.depth,) if hi else ()) + ((lc,) if lc else ()) + (yuv.matrix, int(yuv.full_range))
-    site = () if lc else (yuv.siting,)
+    site, out = () if lc else (yuv.siting,), fmt[:-2] + egress_colour(spec, yuv)
 
     def to_bgr(src, dst, cnt, stream):
         L.check(c_bgr(src, P, dst, F, cnt, h, w, *fmt, *site, stream), names[0])
 
     def gather(base, offs, dst, n, stream):
-        L.check(c_gather(base, offs, dst, P, n, h, w, *fmt, stream), names[1])
+        L.check(c_gather(base, offs, dst, P, n, h, w, *out, stream), names[1])
 
     def sad(base, a, b, m, out, stream):
         L.check(c_sad(base, a, b, m, P, out, stream), names[2])
@@ -374,29 +386,52 @@ def plan_fine(spec, r, wins, n, window_index, with_s1, det, kept, frames, slot_o
 Buffer = namedtuple('Buffer', 'name lead rows Pb h w')
 
 
+class LinearBuffer(Buffer):
+    """A ``Buffer`` of LINEAR payloads (``demfi_amd.colour``): uint16 [3, h, w], ``Pb`` = 6 h w whatever the run's depth and layout.  The six
+    fields and nothing else; what differs is how ``sample_format`` reads it."""
+    __slots__ = ()
+
+
+def linear_light(spec, h, w):
+    """Does a run of ``spec`` on h x w frames work in linear light?  With a transfer (``spec.colour[0]``) and a mix or a scale stage: a
+    transfer alone has nothing to do its work for, builds nothing and gives the bytes of a run without it."""
+    return (spec.colour is not None and spec.colour[0] is not None
+            and (spec.shutter is not None or (spec.scale is not None and tuple(spec.scale[:2]) != (w, h))))
+
+
+def sample_format(spec, buf):
+    """(bytes per sample, [(rows, cols)] of the planes, peak) of the payloads in ``buf``: what a stage that reads it goes by."""
+    if isinstance(buf, LinearBuffer):
+        return 2, [(buf.h, buf.w)] * 3, CL.LIN_PEAK
+    return 2 if spec.hi else 1, IL.plane_shapes(buf.h, buf.w, spec.layout), (1 << spec.depth) - 1
+
+
 def egress_layout(spec, nout, batch, h, w):
     """The buffers behind the gather of ``nout`` h x w payloads a batch (of ``batch`` windows) by the module's buffer rule, for the stages
-    ``spec`` asks for, in their order mix -> scale -> weave -> requant: a ``Buffer`` (name of its producer, free rows in front = the ``lead`` of
+    ``spec`` asks for, in their order mix -> scale -> encode -> weave -> requant: a ``Buffer`` (name of its producer, free rows in front = the ``lead`` of
     its consumer, the most payloads its producer writes per batch, bytes of a payload, frame size) for the gather and every stage built, then
-    (rows, payload bytes) of the pinned host buffers.  Pure: allocates nothing."""
-    es, chain = 2 if spec.hi else 1, []
+    (rows, payload bytes) of the pinned host buffers.  In linear light (``linear_light``) the gather, the mix and the scale buffers are
+    ``LinearBuffer``s and an ``encode`` stage behind them writes the Y'CbCr payloads.  Pure: allocates nothing."""
+    es, chain, lin = 2 if spec.hi else 1, [], linear_light(spec, h, w)
 
-    def add(name, lead, rows, es=es):                # lead: what the stage itself needs in front of its source's payloads
-        chain.append((name, lead, rows, payload_size(h, w, spec.layout) * es, h, w))
-    add('gather', 0, nout)
+    def add(name, lead, rows, es=es, lin=False):     # lead: what the stage itself needs in front of its source's payloads
+        chain.append((LinearBuffer if lin else Buffer, name, lead, rows, 6 * h * w if lin else payload_size(h, w, spec.layout) * es, h, w))
+    add('gather', 0, nout, lin=lin)
     if spec.shutter is not None:
         # written frames of a batch: the multiples of D among the fine indices of its windows (each owns up to J, the last one of the full-length
         # timeline 2 J, nout in all), and the group carried into it; the open group's samples carry in front of the gather
-        add('mix', spec.shutter[0] - 1, nout // spec.shutter[1] + batch + 2)
+        add('mix', spec.shutter[0] - 1, nout // spec.shutter[1] + batch + 2, lin=lin)
     if spec.scale is not None and tuple(spec.scale[:2]) != (w, h):       # the run's own size: no stage, the bytes of a run without
         w, h = spec.scale[:2]
-        add('scale', 0, chain[-1][2])
+        add('scale', 0, chain[-1][3], lin=lin)
+    if lin:                                          # linear payloads -> the run's Y'CbCr payloads, in front of everything that reads those
+        add('encode', 0, chain[-1][3])
     if spec.interlace is not None:                   # pairs of the carried frame and a batch's frames, the odd tail among them
-        add('weave', 1, chain[-1][2] // 2 + 1)
+        add('weave', 1, chain[-1][3] // 2 + 1)
     if spec.depths is not None and spec.depths[2] < spec.depths[1]:
-        add('requant', 0, chain[-1][2], 2 if spec.depths[2] > 8 else 1)
-    leads = [c[1] for c in chain[1:]] + [0]
-    return [Buffer(c[0], lead, *c[2:]) for c, lead in zip(chain, leads)] + [chain[-1][2:4]]
+        add('requant', 0, chain[-1][3], 2 if spec.depths[2] > 8 else 1)
+    leads = [c[2] for c in chain[1:]] + [0]
+    return [c[0](c[1], lead, *c[3:]) for c, lead in zip(chain, leads)] + [chain[-1][3:5]]
 
 
 class Stage:
@@ -411,7 +446,7 @@ class Stage:
     regroups, width = False, 1
 
     def __init__(self, runner, spec, src, own, dev):
-        self.rn, self.lib, self.es = runner, runner.lib, 2 if spec.hi else 1
+        self.rn, self.lib, self.spec, self.es = runner, runner.lib, spec, sample_format(spec, src)[0]    # es: bytes of a sample it reads
         self.lead, self.front, self.rows, self.Pb, self.h, self.w = src.lead, own.lead, own.rows, own.Pb, own.h, own.w
         self.out = [torch.empty((own.lead + own.rows, own.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
         if self.width:
@@ -503,8 +538,8 @@ class Scaler(Stage):
 
     def __init__(self, runner, spec, src, own, dev):
         super().__init__(runner, spec, src, own, dev)
-        self.filter, self.peak, self.Pb_in = spec.scale[2], (1 << spec.depth) - 1, src.Pb
-        shapes_in, shapes_out = IL.plane_shapes(src.h, src.w, spec.layout), IL.plane_shapes(self.h, self.w, spec.layout)
+        self.filter, self.Pb_in = spec.scale[2], src.Pb
+        (_, shapes_in, self.peak), shapes_out = sample_format(spec, src), sample_format(spec, own)[1]
         self.planes_in, self.planes_out = (np.ascontiguousarray(a, dtype=np.int32) for a in (shapes_in, shapes_out))
         blob, self.desc = SC.table_blob(shapes_in, shapes_out, self.filter)
         self.tables = torch.from_numpy(blob).to(dev)
@@ -591,7 +626,7 @@ class Requantizer(Stage):
         self.offs = torch.from_numpy(self.h_offs).to(dev)
 
     def begin(self, yuv):
-        self.full_range = int(yuv.full_range)
+        self.full_range = egress_colour(self.spec, yuv)[1]
 
     def _table(self, i, offsets):
         return self.h_offs.ctypes.data, self.offs.data_ptr()
@@ -605,7 +640,32 @@ class Requantizer(Stage):
                                                self.d_out, self.full_range, self.dither, self.field_rows, dst, self.Pb, stream), 'payload_requant')
 
 
-STAGES = {'mix': Shutter, 'scale': Scaler, 'weave': Interlacer, 'requant': Requantizer}
+class Encoder(Stage):
+    """Linear payloads -> the run's Y'CbCr payloads (``demfi_amd.colour``, ``spec.colour`` = (transfer, out matrix, out full range)): behind
+    the mix and the scaler, which worked in light, and in front of the weave and the requantisation, which see the payloads they always
+    saw.  ``demfi_linear_to_yuv`` takes all of a batch's payloads through the inverse table of ``colour.inverse_table``, uploaded once,
+    here, and then through the gather's own arithmetic with the egress matrix and range.  Stateless per payload, like the scaler: the stage
+    works on every rank.  The runner counts ``colour_encoded``."""
+    counter, too_many = 'colour_encoded', 'encode: %d payloads for %d payload rows'
+
+    def __init__(self, runner, spec, src, own, dev):
+        super().__init__(runner, spec, src, own, dev)
+        self.Pb_in, self.depth, self.layout = src.Pb, spec.depth, L.YUV_LAYOUT[spec.layout]
+        self.inv = torch.from_numpy(CL.tables(spec.colour[0], spec.depth)[1].view(np.int16)).to(dev)
+
+    def begin(self, yuv):
+        self.matrix, self.full_range = egress_colour(self.spec, yuv)
+
+    def run(self, i, counts, batch, src, stream):
+        self._launch(i, np.arange(sum(counts), dtype=np.int64)[:, None] * self.Pb_in, src, stream)
+        return counts
+
+    def _call(self, src, host, offs, n, dst, stream):
+        L.check(self.lib.demfi_linear_to_yuv(src, host, offs, n, self.h, self.w, self.depth, self.layout, self.matrix, self.full_range,
+                                             self.inv.data_ptr(), dst, self.Pb, stream), 'linear_to_yuv')
+
+
+STAGES = {'mix': Shutter, 'scale': Scaler, 'encode': Encoder, 'weave': Interlacer, 'requant': Requantizer}
 
 
 class TileGrid:
@@ -682,7 +742,10 @@ class Y4mEdge:
         # the last buffer of the chain is what crosses D2H: only mixed, resized, woven payloads of the output's sample size leave the device
         *bufs, host = egress_layout(spec, nout, batch, h, w)
         self.lead = bufs[0].lead                     # the free rows in front of the gather
-        self.yuv_out = [torch.empty((self.lead + nout, ing.Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.yuv_out = [torch.empty((self.lead + nout, bufs[0].Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.fwd = None                              # linear light: the gather writes linear payloads through this table, uploaded once
+        if isinstance(bufs[0], LinearBuffer):
+            self.fwd = torch.from_numpy(CL.forward_table(spec.colour[0], spec.depth).view(np.int16)).to(dev)
         self.stages, self.sources, self.written = [], [], self.yuv_out       # sources[j]: the buffers stages[j] reads
         for src, own in zip(bufs, bufs[1:]):
             st = STAGES[own.name](runner, spec, src, own, dev)
@@ -709,6 +772,8 @@ class Y4mEdge:
         for st in self.stages:
             st.begin(yuv)
         ing.to_bgr, self.gather, sad = yuv_calls(self.rn.lib, self.spec, ing.fh, ing.fw, yuv)
+        if self.fwd is not None:
+            self.gather = self._linear_gather
         if sc is None:
             return ()
         sc.sad, det = sad, S.Detector(ing.P, yuv.scene_cut, first=S.first_frame(window_index(0) if window_index is not None else first_win[2]),
@@ -716,6 +781,12 @@ class Y4mEdge:
         sc.det = self.det = det
         self.rn.last_cuts = det.cuts
         return (det.next - 1,) if det.next - 1 < first_win[2] else ()
+
+    def _linear_gather(self, base, offs, dst, n, stream):
+        """The gather of a linear-light run: the same frames of ``comb`` at the same offsets (in samples), written as linear payloads."""
+        ing = self.ingest
+        L.check(self.rn.lib.demfi_bgr_to_linear_gather(base, offs, dst, 3 * ing.fh * ing.fw, n, ing.fh, ing.fw, ing.es, self.spec.depth,
+                                                       self.fwd.data_ptr(), stream), 'bgr_to_linear_gather')
 
     def upload(self, sl, idx, f):
         self.ingest.upload(sl, idx, f)

@@ -612,6 +612,28 @@ int demfi_payload_requant(const uint8_t* base, const int64_t* offsets, const int
                           int n_planes, int in_bytes, int out_bytes, int depth_in, int depth_out, int full_range, int dither,
                           int field_rows, uint8_t* dst, int64_t dst_stride, void* stream);
 
+/* ---- linear light at the Y4M edge (csrc/colour.hip; demfi_amd/video.py --linear-light) -------------------------------------------------
+ * A LINEAR payload of an h x w frame is uint16 [3, h, w]: planes B, G, R at full resolution, linear light 0 .. 65535, whatever the working
+ * depth (8, 10 or 12) and the chroma layout.  The functions compute no transfer function: fwd_table (DEVICE, uint16 [2^depth]: code ->
+ * linear value) and inv_table (DEVICE, uint16 [65536]: linear value -> the code nearest in light) are those of demfi_amd/colour.py
+ * (forward_table / inverse_table), and the numpy definitions are linearize_np / encode_payload_np there, matched bit for bit.
+ * bgr_to_linear_gather: written payload i (n per launch) is the interleaved BGR frame of codes at base + src_offsets[i] (DEVICE int64
+ * offsets in SAMPLES of sample_bytes = 1, uint8 at depth 8, or 2, uint16), every code replaced by fwd_table[code] (a stored value above
+ * the peak reads the peak's entry); it is written at dst + i*dst_stride (uint16 samples, at least 3 h w).
+ * linear_to_yuv: written payload i is the linear payload at src + offsets[i] (int64 BYTE offsets, even) taken to codes through inv_table
+ * and then to Y'CbCr by the arithmetic of demfi_bgr_to_yuv420_gather / demfi_bgr_to_yuvl_gather and their 16-bit forms (matrix, range,
+ * rounding, 2x2 box, 4:2:2 [1,2,1]); any layout of demfi_yuv_layout; samples are bytes at depth 8, 16-bit little-endian above; it is
+ * written at dst + i*dst_stride BYTES.  The offsets are passed twice with the same content: offsets in HOST memory, checked here before
+ * anything is launched, and offsets_dev in DEVICE memory, read by the kernel.
+ * DEMFI_ERR_ARG, with nothing launched: a NULL buffer, n < 0, a frame size outside 2..16384, a depth other than 8, 10 or 12, sample_bytes
+ * that do not fit the depth, an unknown layout, matrix or range flag, 16-bit samples at an odd address, offset or stride, a dst_stride
+ * below the written payload, a negative offset.  One launch for all n payloads: a lane owns 8 pixels of a row (4:2:0 encode: of two rows);
+ * fwd_table is copied into LDS once per workgroup, inv_table is read through L2.  No atomics; n == 0 does nothing. */
+int demfi_bgr_to_linear_gather(const void* base, const int64_t* src_offsets, uint16_t* dst, int64_t dst_stride, int n, int h, int w,
+                               int sample_bytes, int depth, const uint16_t* fwd_table, void* stream);
+int demfi_linear_to_yuv(const uint8_t* src, const int64_t* offsets, const int64_t* offsets_dev, int n, int h, int w, int depth, int layout,
+                        int matrix, int full_range, const uint16_t* inv_table, uint8_t* dst, int64_t dst_stride, void* stream);
+
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
  * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
