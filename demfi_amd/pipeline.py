@@ -23,6 +23,7 @@ from . import cadence as K
 from . import colour as CL
 from . import deint as I
 from . import denoise as DN
+from . import grain as GR
 from . import interlace as IL
 from . import retime as R
 from . import scale as SC
@@ -56,9 +57,11 @@ class EdgeSpec(_EdgeFields):
     on each side), kept beside the tuple like the others;
     ``colour``: None or (transfer of ``colour.TRANSFERS`` or None, output matrix 'bt601' / 'bt709' or None, output full range or None) of
     ``demfi_amd.colour``: linear light for the mix and the scaler, and the matrix and range written where they differ from the input's
-    (three times None is None), kept beside the tuple like ``scale`` and ``denoise``.  ``reach``: how far the frames an ingest stage reads lie from the frame it writes.
+    (three times None is None), kept beside the tuple like ``scale`` and ``denoise``.
+    ``grain``: None or (S16, r, C16, curve, seed) of the film grain added behind the encode and in front of the weave (``demfi_amd.grain``),
+    kept beside the tuple like ``denoise`` and ``colour``; S16 = 0 is None.  ``reach``: how far the frames an ingest stage reads lie from the frame it writes.
     Hashable: (batch, spec) is what a cached ``ClipPipeline`` can be reused for.
-    ``shutter``, ``interlace``, ``scale``, ``depths``, ``shutter_window``, ``denoise`` and ``colour`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
+    ``shutter``, ``interlace``, ``scale``, ``depths``, ``shutter_window``, ``denoise``, ``colour`` and ``grain`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
     without them is, item for item, the record it was before there were any, and one with any of them equals no plain tuple.  What the namedtuple makes
     from its items alone does not know them: ``_make``, ``_asdict`` and pickling drop them; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
     shutter = None
@@ -68,9 +71,13 @@ class EdgeSpec(_EdgeFields):
     shutter_window = None
     denoise = None
     colour = None
+    grain = None
 
-    def __new__(cls, *args, shutter=None, interlace=None, scale=None, depths=None, shutter_window=None, denoise=None, colour=None, **kw):
+    def __new__(cls, *args, shutter=None, interlace=None, scale=None, depths=None, shutter_window=None, denoise=None, colour=None, grain=None,
+                **kw):
         self = super().__new__(cls, *args, **kw)
+        if grain is not None and int(grain[0]) != 0:                      # no strength is the spec without the field
+            self.grain = (int(grain[0]), int(grain[1]), int(grain[2]), grain[3], int(grain[4]))
         if colour is not None and any(v is not None for v in colour):     # three times None is the spec without the field
             self.colour = (colour[0], colour[1], None if colour[2] is None else bool(colour[2]))
         if denoise is not None:
@@ -90,15 +97,16 @@ class EdgeSpec(_EdgeFields):
     def _replace(self, **kw):
         shutter, interlace, scale = kw.pop('shutter', self.shutter), kw.pop('interlace', self.interlace), kw.pop('scale', self.scale)
         depths, window, denoise = kw.pop('depths', self.depths), kw.pop('shutter_window', self.shutter_window), kw.pop('denoise', self.denoise)
-        colour = kw.pop('colour', self.colour)
+        colour, grain = kw.pop('colour', self.colour), kw.pop('grain', self.grain)
         return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace, scale=scale, depths=depths, shutter_window=window,
-                          denoise=denoise, colour=colour)
+                          denoise=denoise, colour=colour, grain=grain)
 
     def __eq__(self, other):
         return (tuple.__eq__(self, other) is True and self.shutter == getattr(other, 'shutter', None)
                 and self.interlace == getattr(other, 'interlace', None) and self.scale == getattr(other, 'scale', None)
                 and self.depths == getattr(other, 'depths', None) and self.shutter_window == getattr(other, 'shutter_window', None)
-                and self.denoise == getattr(other, 'denoise', None) and self.colour == getattr(other, 'colour', None))
+                and self.denoise == getattr(other, 'denoise', None) and self.colour == getattr(other, 'colour', None)
+                and self.grain == getattr(other, 'grain', None))
 
     def __ne__(self, other):
         return not self == other
@@ -109,7 +117,8 @@ class EdgeSpec(_EdgeFields):
         key = key if self.depths is None else key + ('depths', self.depths)
         key = key if self.shutter_window is None else key + ('shutter_window', self.shutter_window)
         key = key if self.denoise is None else key + ('denoise', self.denoise)
-        return hash(key if self.colour is None else key + ('colour', self.colour))
+        key = key if self.colour is None else key + ('colour', self.colour)
+        return hash(key if self.grain is None else key + ('grain', self.grain))
 
     def __repr__(self):
         return super().__repr__()[:-1] + ', shutter=%r%s%s)' % (self.shutter, ', interlace=%r' % (self.interlace,) if self.interlace is not None else '',
@@ -117,7 +126,8 @@ class EdgeSpec(_EdgeFields):
                                                                + (', depths=%r' % (self.depths,) if self.depths is not None else '')
                                                                + (', shutter_window=%r' % self.shutter_window if self.shutter_window is not None else '')
                                                                + (', denoise=%r' % (self.denoise,) if self.denoise is not None else '')
-                                                               + (', colour=%r' % (self.colour,) if self.colour is not None else ''))
+                                                               + (', colour=%r' % (self.colour,) if self.colour is not None else '')
+                                                               + (', grain=%r' % (self.grain,) if self.grain is not None else ''))
 
     @classmethod
     def of(cls, yuv):
@@ -127,18 +137,26 @@ class EdgeSpec(_EdgeFields):
                    getattr(yuv, 'layout', '420'), tuple(dedup) if dedup is not None else None, fields,
                    getattr(yuv, 'deint_mode', 'bob') if fields is not None else 'bob', shutter=getattr(yuv, 'shutter', None),
                    interlace=getattr(yuv, 'interlace', None), scale=getattr(yuv, 'scale', None), depths=getattr(yuv, 'depths', None),
-                   shutter_window=getattr(yuv, 'shutter_window', None), denoise=getattr(yuv, 'denoise', None), colour=getattr(yuv, 'colour', None))
+                   shutter_window=getattr(yuv, 'shutter_window', None), denoise=getattr(yuv, 'denoise', None), colour=getattr(yuv, 'colour', None),
+                   grain=getattr(yuv, 'grain', None))
 
     hi = property(lambda self: self.depth > 8, doc='16-bit frames: the samples of a stream above 8 bits')
     reach = property(lambda self: DN.reach(self.denoise[2], self.fields is not None) if self.denoise is not None
                      else 2 if self.fields is not None and self.deint_mode == 'adaptive' else 0,
                      doc='frames before and after a frame that its ingest reads: the adaptive deinterlacer 2 fields, the denoiser R (bobbed fields: 2 R)')
 
+    def _grain_ok(self):
+        try:
+            return GR.check_params(self.grain) == self.grain
+        except ValueError:
+            return False
+
     def check(self, retimed, has_window_index, reuse_frames):
         """Every rule about what goes together, before anything is allocated, for a run on a ``retimed`` runner (built with a ratio)."""
         other, edge_only = self.deint_mode != 'bob', self.hi or self.dedup is not None or self.fields is not None
         deint = deint_conflict(self.deint_mode, self.fields is not None, self.dedup is not None)
         sh, il, sc, dp, win, dn, co = self.shutter, self.interlace, self.scale, self.depths, self.shutter_window, self.denoise, self.colour
+        gr = self.grain
         for bad, what in ((self.fields not in (None, 't', 'b'), "fields must be None, 't' or 'b', got %r" % (self.fields,)),
                           (deint, 'deint_mode %r with fields=%r, dedup=%r' % (self.deint_mode, self.fields, self.dedup)),
                           (edge_only and not self.y4m, '16-bit frames, repeated frames and fields are those of the Y4M edge (yuv=...) only'),
@@ -181,7 +199,10 @@ class EdgeSpec(_EdgeFields):
                           (co is not None and not (retimed and self.y4m), 'linear light and an output matrix or range need the Y4M edge on a retimed runner'),
                           (co is not None and co[0] is not None and self.depth > CL.MAX_DEPTH,
                            'linear light needs a working depth of at most %d bits, got %d: above, 16 bits of light do not tell the codes apart'
-                           % (CL.MAX_DEPTH, self.depth))):
+                           % (CL.MAX_DEPTH, self.depth)),
+                          (gr is not None and not self._grain_ok(), 'grain must be None or (S16 in 0..%d, r in 0..2, C16 in 0..16, curve of %s, '
+                           'seed in 0..2^32-1), got %r' % (GR.MAX_S16, GR.CURVES, gr)),
+                          (gr is not None and not (retimed and self.y4m), 'film grain needs the Y4M edge on a retimed runner')):
             if bad:
                 raise ValueError('WindowRunner.run_clip_u8: ' + what)
 

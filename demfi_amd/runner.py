@@ -175,6 +175,7 @@ class WindowRunner:
         self.scale_payloads = 0                      # resized output: payloads resampled (``y4m_edge.Scaler``)
         self.depth_promoted = self.depth_requantised = 0     # bit depth: payloads promoted at ingest / requantised at egress (``demfi_amd.bitdepth``)
         self.denoised = 0                            # temporal denoiser: frames denoised at ingest (``demfi_amd.denoise``)
+        self.grain_payloads = 0                      # film grain: payloads grained at egress (``y4m_edge.Grain``)
         self.colour_encoded = 0                      # linear light: payloads taken back to Y'CbCr (``y4m_edge.Encoder``)
         self.last_cuts = []                          # frames that start a scene, as the last run_clip_u8 with scene cuts found them
 

@@ -196,6 +196,23 @@ staged one at a time, without look-ahead) and ``--deinterlace-mode adaptive`` (t
 before anything is allocated.  Not offered: spatial filtering, separate chroma thresholds, motion-compensated averaging, stopping at
 detected cuts (the thresholds do that per sample), numeric equality with ffmpeg's ``atadenoise``, decisions of ``--ivtc`` / ``--crop auto`` on
 denoised samples, ``demfi_amd.clip``.  Without the switch no buffer, table, launch or slot is added and every byte stays the same.
+
+``--grain S`` with ``--grain-size 0|1|2``, ``--grain-chroma C``, ``--grain-curve film|flat`` and ``--grain-seed N`` adds synthetic film grain to
+every progressive payload the run would hand to the weave, the requantiser or D2H (``demfi_amd.grain``): ``--denoise`` removes grain on
+purpose, the network, ``--shutter`` and ``--scale`` smooth what is left, and the result looks synthetic next to untouched material and bands
+at 8 and 10 bits.  S is the grain's standard deviation in 8-bit code values at the curve's peak (0 .. 8, in sixteenths), the size how coarse
+it is (binomial taps over white cells; default 1), C the chroma strength relative to luma (0 .. 1, default 0.5; 0: luma only), the curve
+``film`` (default: peaks in the midtones, a quarter at black and white, by the frame's own luma) or ``flat``, the seed a uint32 (default 0).
+The chain is gather -> mix -> scale -> encode -> grain -> weave -> requant -> D2H: ONE launch per batch (csrc/grain.hip
+``demfi_payload_grain``, byte for byte ``grain.grain_payload_np``) behind everything that would average grain away and in front of the weave
+(both fields of a payload get independent grain) and the dither.  The rule: out = clip(v + ((F G[luma code] + 2^15) >> 16), min(lo, v),
+max(hi, v)) with F a hashed, binomially filtered field of (seed, frame, plane, x, y) and G a host-built gain table; grain never pushes a
+legal sample out of the legal range and never pulls an illegal one in.  Frame n is a running count of the frames written, so a run with
+the switch writes ``grain.grain_stream_np`` of the stream a run without it writes, whatever the batch size; ``--crop-output pad`` pads behind
+D2H, so the bars stay exact black.  One rank (the count would restart on a second; the field is a pure function of n, so handing each rank
+its first n is all several ranks would take).  ``--grain 0`` builds no stage.  Not offered: measuring the grain ``--denoise`` removed and
+matching it, grain correlated in time, AR-model grain as in AV1, per-plane curves, grain in linear light, several ranks,
+``demfi_amd.clip``.  Without the switch no buffer, table, launch or stream is added and every byte stays the same.
 """
 import os
 import sys
@@ -210,6 +227,7 @@ from . import colour as CL
 from . import deint as I
 from . import denoise as DN
 from . import dist as D
+from . import grain as GR
 from . import interlace as IL
 from . import letterbox as LB
 from . import retime as R
@@ -242,12 +260,14 @@ class YuvEdge:
     ``linear_light``: None, or the transfer ('bt709' / 'srgb'; True: 'bt709') through which the mix and the scaler work in linear light
     (``demfi_amd.colour``); ``out_matrix`` ('bt601' / 'bt709') and ``out_range`` ('limited' / 'full'): None, or the matrix and range of the
     payloads handed out, where ``matrix`` and ``full_range`` are those of the payloads handed in.  ``colour`` = (transfer, out matrix, out
-    full range), or None without the three."""
+    full range), or None without the three.  ``grain``: None, or (S16, r, C16, curve, seed) of the film grain added to every progressive payload
+    in front of the weave (``demfi_amd.grain``); S16 = 0 is None."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
                  fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None,
-                 depths=None, shutter_window=None, denoise=None, linear_light=None, out_matrix=None, out_range=None):
+                 depths=None, shutter_window=None, denoise=None, linear_light=None, out_matrix=None, out_range=None, grain=None):
         self.dedup, self.shutter = dedup, shutter
+        self.grain = None if grain is None or not GR.check_params(grain)[0] else GR.check_params(grain)
         self.colour = check_colour(linear_light, out_matrix, out_range)
         self.denoise = None if denoise is None else DN.check_params(*denoise)
         self.shutter_window = check_shutter_window(shutter, shutter_window)
@@ -277,9 +297,16 @@ ONE_RANK = {        # the switches that run on one rank only, and why
 }
 
 
+# and of the egress stages that came after: kept the same way, in a table of their own
+ONE_RANK_EGRESS = {
+    'grain': 'frame n of the grain is a running count of the frames a rank writes, so a second rank would restart it (the field is a pure '
+             'function of n: handing each rank its first n is all it would take)',
+}
+
+
 def check_one_rank(world, **switches):
-    """The switches of ``ONE_RANK`` that are set (neither None nor False) are refused with more than one rank."""
-    for name, why in ONE_RANK.items():
+    """The switches of ``ONE_RANK`` and ``ONE_RANK_EGRESS`` that are set (neither None nor False) are refused with more than one rank."""
+    for name, why in (*ONE_RANK.items(), *ONE_RANK_EGRESS.items()):
         if world > 1 and switches.get(name) not in (None, False):
             raise ValueError('VideoRunner: %s with %d ranks: %s; run --%s on one rank' % (name, world, why, name))
 
@@ -398,13 +425,22 @@ def check_denoise(denoise, radius=None, dedup=None, deinterlace_mode='bob'):
     return dn
 
 
+def check_grain(grain=None, size=None, chroma=None, curve=None, seed=None, world=1):
+    """The grain switches checked: None (no ``grain``, or S = 0: no stage) or (S16, r, C16, curve, seed) of ``grain.check_grain``.  ``grain``:
+    S as a number or a decimal string, 0 .. 8; ``size`` 0, 1 or 2 (None: 1); ``chroma`` C in 0 .. 1 (None: 0.5); ``curve`` 'film' / 'flat' (None:
+    'film'); ``seed`` a uint32 (None: 0).  The four say how ``grain`` works, so any of them without it is an error; grain runs on one rank."""
+    params = GR.check_grain(grain, size, chroma, curve, seed)
+    check_one_rank(world, grain=params)
+    return params
+
+
 # what a run adds to each of these counters of its ``WindowRunner`` is kept in the ``VideoRunner`` attribute named here (None: it goes into
 # ``last_instants`` = (run, padded), and a shutter's fine frames into ``last_st_frames``: ``VideoRunner._counted``)
 COUNTERS = {'instants_run': None, 'instants_padded': None, 'shutter_mixed': None, 'cut_windows': 'last_cut_windows',
             'shutter_carried': 'last_shutter_carried', 'interlace_carried': 'last_interlace_carried', 'scale_payloads': 'last_scale_payloads',
             'depth_promoted': 'last_depth_promoted', 'depth_requantised': 'last_depth_requantised'}
-# and of the egress stages that came after: linear light (``y4m_edge.Encoder``)
-EGRESS_COUNTERS = {'colour_encoded': 'last_colour_encoded'}
+# and of the egress stages that came after: linear light (``y4m_edge.Encoder``), film grain (``y4m_edge.Grain``)
+EGRESS_COUNTERS = {'colour_encoded': 'last_colour_encoded', 'grain_payloads': 'last_grain_payloads'}
 # the counters of the ingest stages that came after those: kept the same way, in a table of their own
 INGEST_COUNTERS = {'denoised': 'last_denoised'}
 
@@ -520,7 +556,14 @@ class VideoRunner:
     'srgb': the shutter's mix and the scaler work in linear light through that transfer (``demfi_amd.colour``); ``out_matrix``: None (the
     input's), 'auto' (by the height written), 'bt601' or 'bt709'; ``out_range``: None (the input's), 'limited' or 'full'.  Linear light at a
     working depth above 12 bits is refused once the header is known.  After a run ``last_colour`` = (transfer or None, matrix, full range)
-    the run wrote with, or None without the three, and ``last_colour_encoded`` = the payloads the encode stage took back."""
+    the run wrote with, or None without the three, and ``last_colour_encoded`` = the payloads the encode stage took back.  ``grain``: None
+    (default) or S, the standard deviation in 8-bit code values (a number or a decimal string, 0 .. 8, in sixteenths) of synthetic film
+    grain (``demfi_amd.grain``) added on the GPU to every progressive payload behind the mix, the scaler and the encode and in front of the
+    weave and the requantisation (csrc/grain.hip ``demfi_payload_grain``, ONE launch per batch); ``grain_size`` 0, 1 or 2 (None: 1),
+    ``grain_chroma`` C in 0 .. 1 (None: 0.5), ``grain_curve`` 'film' / 'flat' (None: 'film'), ``grain_seed`` a uint32 (None: 0); any of the four
+    without ``grain`` is an error.  One rank (``run_file`` refuses more).  ``grain=0`` builds no stage.  After a run ``last_grain`` = (S16,
+    r, C16, curve, seed) or None and ``last_grain_payloads`` = the payloads grained.  Without it no buffer, table, launch or stream is added
+    and every byte stays the same."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
@@ -529,8 +572,11 @@ class VideoRunner:
                  crop_noise=LB.DEFAULT_NOISE, crop_probe=LB.DEFAULT_PROBE, crop_output='pad', shutter=None,
                  shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, work_depth=None,
                  out_depth=None, dither=None, down=False, shutter_window=None, denoise=None, denoise_radius=None, linear_light=None,
-                 out_matrix=None, out_range=None, **runner_kw):
+                 out_matrix=None, out_range=None, grain=None, grain_size=None, grain_chroma=None, grain_curve=None, grain_seed=None,
+                 **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.grain = check_grain(grain, grain_size, grain_chroma, grain_curve, grain_seed)   # (S16, r, C16, curve, seed) or None
+        self.last_grain = None
         self.colour = check_colour(linear_light, out_matrix, out_range, auto=True)   # (transfer, out matrix or 'auto', out full range) or None
         self.last_colour = None
         self.denoise = check_denoise(denoise, denoise_radius, dedup, deinterlace_mode)   # (A, B, R) or None
@@ -847,7 +893,7 @@ class VideoRunner:
         self.last_instants, self.last_cuts = (added['instants_run'], added['instants_padded']), cuts
         self.last_st_frames = added['shutter_mixed'] if self.shutter is not None else st_frames     # the fine frames that went into the mixes
         self.last_shutter, self.last_scale, self.last_shutter_window = self.shutter, self._scale_of(hdr), self.shutter_window
-        self.last_interlace = self.interlace[0] if self.interlace is not None else None
+        self.last_interlace, self.last_grain = self.interlace[0] if self.interlace is not None else None, self.grain
 
     def _edge(self, hdr, with_s1, order=None):
         depths = self._depths_of(hdr)                # hdr has the input's depth; the edge works at depths[1]
@@ -856,7 +902,7 @@ class VideoRunner:
         return YuvEdge(self._in_matrix(hdr), hdr.full_range, hdr.chroma, with_s1,
                        self.scene_cut, self.full_length, depths[1], hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
                        *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths, shutter_window=self.shutter_window,
-                       denoise=self.denoise, **kw)
+                       denoise=self.denoise, grain=self.grain, **kw)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
@@ -919,7 +965,7 @@ class VideoRunner:
         """Rank ``rank`` of ``world`` on regular files: one scan of the input's frame headers, this rank's block of windows
         (``dist.shard_windows``), its frames written at ``header + i*(6 + payload)``.  Rank 0 writes the header and sizes the
         output file; all ranks meet at a barrier before writing.  Returns (windows, frames written) of this rank."""
-        check_one_rank(world, dedup=self.dedup, ivtc=self.ivtc, shutter=self.shutter, interlace=self.interlace)
+        check_one_rank(world, dedup=self.dedup, ivtc=self.ivtc, shutter=self.shutter, interlace=self.interlace, grain=self.grain)
         self.last_dups, self._film = [], None
         with open(in_path, 'rb') as f:
             in_hdr, _, offs = y4m.scan(f, self.depths, self.layouts, self.deinterlace, self.ivtc)
@@ -990,6 +1036,14 @@ def _value_arg(fn):
         except ValueError as e:
             import argparse
             raise argparse.ArgumentTypeError(str(e))
+    return arg
+
+
+def _grain_arg(fn):
+    """The text of a decimal grain switch, checked by ``fn`` and handed on as it is: ``VideoRunner`` takes S and C, not their sixteenths."""
+    def arg(text):
+        fn(text)
+        return text.strip()
     return arg
 
 
@@ -1177,6 +1231,25 @@ def parser():
                          'BT.601, so --scale 1920x1080 of an SD stream leaves as BT.709.  Y4M has no tag for it')
     ap.add_argument('--out-range', default=None, choices=list(CL.OUT_RANGES),
                     help='range of the OUTPUT (default: the input\'s); the header gets XCOLORRANGE=FULL or LIMITED when the range changes')
+    ap.add_argument('--grain', type=_value_arg(_grain_arg(GR.parse_strength)), default=None, metavar='S',
+                    help='add synthetic film grain on the GPU to every frame written: --denoise, the network, --shutter and --scale leave a '
+                         'picture cleaner than any camera original, which looks synthetic next to untouched material and bands at 8 and 10 '
+                         'bits.  S is the grain\'s standard deviation in 8-bit code values at the curve\'s peak, 0 .. 8, a decimal in sixteenths '
+                         '(1 to 2 is fine film, 4 is coarse; 0 builds nothing).  Behind --shutter, --scale and --linear-light\'s encode, which would '
+                         'average it away, in front of --interlace (both fields get their own grain) and --out-depth\'s dither; one launch per '
+                         'batch.  Grain never leaves the legal range.  Every frame gets fresh grain from (seed, frame number), so the bytes '
+                         'do not depend on --batch.  One rank only.  Off by default')
+    ap.add_argument('--grain-size', type=int, default=None, choices=[0, 1, 2], metavar='R',
+                    help='with --grain: how coarse the grain is: 0 white noise, 1 (default) a 3x3, 2 a 5x5 binomial blur of it; the '
+                         'strength stays S')
+    ap.add_argument('--grain-chroma', type=_value_arg(_grain_arg(GR.parse_chroma)), default=None, metavar='C',
+                    help='with --grain: the strength of the chroma planes\' grain relative to luma, 0 .. 1 in sixteenths (default 0.5; 0: '
+                         'luma only)')
+    ap.add_argument('--grain-curve', default=None, choices=list(GR.CURVES),
+                    help='with --grain: film (default) follows the frame\'s own luma, full strength in the midtones and a quarter at black '
+                         'and white; flat is the same everywhere')
+    ap.add_argument('--grain-seed', type=_value_arg(GR.parse_seed), default=None, metavar='N',
+                    help='with --grain: a 32-bit seed (default 0); the same seed gives the same bytes')
     T.add_arguments(ap)
     return ap
 
@@ -1207,6 +1280,7 @@ def main(argv=None):
         check_depths(a.work_depth, a.out_depth, a.dither)
         check_denoise(a.denoise, a.denoise_radius, a.dedup or None, a.deinterlace_mode)
         check_colour(a.linear_light, a.out_matrix, a.out_range, auto=True)
+        grain = check_grain(a.grain, a.grain_size, a.grain_chroma, a.grain_curve, a.grain_seed)
     except ValueError as e:
         parser().error(str(e))
     shutter_kw = {k: v for k, v in (('shutter', a.shutter), ('shutter_samples', a.shutter_samples), ('interlace', a.interlace),
@@ -1214,10 +1288,12 @@ def main(argv=None):
                                     ('scale_filter', a.scale_filter), ('work_depth', a.work_depth), ('out_depth', a.out_depth),
                                     ('dither', a.dither), ('shutter_window', a.shutter_window), ('denoise', a.denoise),
                                     ('denoise_radius', a.denoise_radius), ('linear_light', a.linear_light), ('out_matrix', a.out_matrix),
-                                    ('out_range', a.out_range)) if v is not None}
+                                    ('out_range', a.out_range), ('grain', a.grain), ('grain_size', a.grain_size),
+                                    ('grain_chroma', a.grain_chroma), ('grain_curve', a.grain_curve), ('grain_seed', a.grain_seed))
+                  if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     try:
-        check_one_rank(world, dedup=a.dedup, ivtc=a.ivtc, shutter=a.shutter, interlace=a.interlace)
+        check_one_rank(world, dedup=a.dedup, ivtc=a.ivtc, shutter=a.shutter, interlace=a.interlace, grain=grain)
     except ValueError as e:
         raise SystemExit('demfi_amd.video: ' + str(e))
     if world > 1 and not (_is_regular(a.input) and os.path.isfile(a.input) and _is_regular(a.output)):
@@ -1280,6 +1356,10 @@ def main(argv=None):
         if a.scale is not None:
             extra['scale'] = {'size': '%dx%d' % vr.scale[:2], 'filter': vr.scale[2], 'resized': vr.last_scale is not None,
                               'payloads': vr.last_scale_payloads}
+        if a.grain is not None:
+            g = vr.last_grain
+            extra['grain'] = {'payloads': vr.last_grain_payloads} if g is None else {
+                'strength': g[0] / 16, 'size': g[1], 'chroma': g[2] / 16, 'curve': g[3], 'seed': g[4], 'payloads': vr.last_grain_payloads}
         if vr.last_colour is not None:
             extra['colour'] = {'linear_light': vr.last_colour[0], 'matrix': vr.last_colour[1], 'range': 'full' if vr.last_colour[2] else 'limited',
                                'encoded': vr.last_colour_encoded}

@@ -1,7 +1,7 @@
 """The Y4M edge of the clip pipeline (``demfi_amd.pipeline``): Y4M payloads in and out, every window on its own plan, all options in
 one ``pipeline.EdgeSpec``.  One stage per job, each with its own buffers: ``Ingest``, ``SceneScores``, ``DedupProbe``, the pure function
 ``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, the ``Stage`` chain that ``egress_layout`` sizes: ``Shutter``,
-``Scaler``, ``Encoder`` (linear light: the gather then writes linear payloads, ``demfi_amd.colour``), ``Interlacer`` and ``Requantizer``, in
+``Scaler``, ``Encoder`` (linear light: the gather then writes linear payloads, ``demfi_amd.colour``), ``Grain``, ``Interlacer`` and ``Requantizer``, in
 that order, each only when ``spec`` asks for it; ``Y4mEdge`` loops over them and keeps the
 payloads' way out.
 
@@ -19,6 +19,7 @@ from . import cadence as K
 from . import colour as CL
 from . import deint as I
 from . import denoise as DN
+from . import grain as GR
 from . import interlace as IL
 from . import retime as R
 from . import scale as SC
@@ -408,7 +409,7 @@ def sample_format(spec, buf):
 
 def egress_layout(spec, nout, batch, h, w):
     """The buffers behind the gather of ``nout`` h x w payloads a batch (of ``batch`` windows) by the module's buffer rule, for the stages
-    ``spec`` asks for, in their order mix -> scale -> encode -> weave -> requant: a ``Buffer`` (name of its producer, free rows in front = the ``lead`` of
+    ``spec`` asks for, in their order mix -> scale -> encode -> grain -> weave -> requant: a ``Buffer`` (name of its producer, free rows in front = the ``lead`` of
     its consumer, the most payloads its producer writes per batch, bytes of a payload, frame size) for the gather and every stage built, then
     (rows, payload bytes) of the pinned host buffers.  In linear light (``linear_light``) the gather, the mix and the scale buffers are
     ``LinearBuffer``s and an ``encode`` stage behind them writes the Y'CbCr payloads.  Pure: allocates nothing."""
@@ -426,7 +427,9 @@ def egress_layout(spec, nout, batch, h, w):
         add('scale', 0, chain[-1][3], lin=lin)
     if lin:                                          # linear payloads -> the run's Y'CbCr payloads, in front of everything that reads those
         add('encode', 0, chain[-1][3])
-    if spec.interlace is not None:                   # pairs of the carried frame and a batch's frames, the odd tail among them
+    if spec.grain is not None:                       # every progressive payload of its source, in place of it: the same rows and size
+        add('grain', 0, chain[-1][3])
+    if spec.interlace is not None:                  # pairs of the carried frame and a batch's frames, the odd tail among them
         add('weave', 1, chain[-1][3] // 2 + 1)
     if spec.depths is not None and spec.depths[2] < spec.depths[1]:
         add('requant', 0, chain[-1][3], 2 if spec.depths[2] > 8 else 1)
@@ -665,7 +668,53 @@ class Encoder(Stage):
                                              self.inv.data_ptr(), dst, self.Pb, stream), 'linear_to_yuv')
 
 
-STAGES = {'mix': Shutter, 'scale': Scaler, 'encode': Encoder, 'weave': Interlacer, 'requant': Requantizer}
+class Grain(Stage):
+    """Progressive payloads -> the same payloads with film grain (``demfi_amd.grain``, ``spec.grain`` = (S16, r, C16, curve, seed)): behind
+    the mix, the scaler and the encode, which would average grain away, and in front of the weave and the requantisation, so both fields
+    of a woven payload get independent grain and the dither sees it.  ``demfi_payload_grain`` grains all of a batch's payloads.  Stateless
+    per payload except for ``n``, the running count of the progressive frames the stage has seen in this run: payload j of a batch is
+    frame n + j, whose three keys (``grain.plane_key``) go up beside its offset, so which batch a frame came with never shows.  ``begin``
+    resets n and takes the range written from ``egress_colour``; the two gain tables of ``grain.gain_tables`` are the only source of the
+    strength and the curve and are uploaded once per range, there.  The count restarts on every rank, so the stage runs on one
+    (``video.ONE_RANK_EGRESS``); the field is a pure function of n, so handing each rank its first n is all several would take.  The
+    runner counts ``grain_payloads``."""
+    counter, too_many = 'grain_payloads', 'grain: %d payloads for %d payload rows'
+
+    def __init__(self, runner, spec, src, own, dev):
+        super().__init__(runner, spec, src, own, dev)
+        self.params, self.depth, self.dev = GR.check_params(spec.grain), spec.depth, dev
+        self.planes = np.ascontiguousarray(IL.plane_shapes(self.h, self.w, spec.layout), dtype=np.int32)
+        self.keys = [torch.empty(self.rows * 3, dtype=torch.int32, device=dev) for _ in range(2)]
+        self.h_keys = [torch.empty((self.rows, 3), dtype=torch.int32).pin_memory() for _ in range(2)]
+        self.n, self.full_range, self.h_gains, self.gains = 0, None, None, None
+
+    def begin(self, yuv):
+        full = egress_colour(self.spec, yuv)[1]
+        if full != self.full_range:                  # the curve's t goes by the range written
+            self.full_range = full
+            self.h_gains = np.ascontiguousarray(GR.gain_tables(self.depth, self.params, full), dtype=np.int32)
+            self.gains = torch.from_numpy(self.h_gains).to(self.dev)
+        self.n = 0
+
+    def run(self, i, counts, batch, src, stream):
+        m, seed = sum(counts), self.params[4]
+        if m > self.rows:
+            raise RuntimeError(self.too_many % (m, self.rows))
+        if m:
+            self.h_keys[i].numpy().view(np.uint32)[:m] = [[GR.plane_key(seed, self.n + j, p) for p in range(3)] for j in range(m)]
+            self.keys[i][:3 * m].copy_(self.h_keys[i][:m].view(-1), non_blocking=True)
+        self._i = i
+        self._launch(i, np.arange(m, dtype=np.int64)[:, None] * self.Pb, src, stream)
+        self.n += m
+        return counts
+
+    def _call(self, src, host, offs, n, dst, stream):
+        L.check(self.lib.demfi_payload_grain(src, host, offs, self.h_keys[self._i].data_ptr(), self.keys[self._i].data_ptr(), n,
+                                             self.planes.ctypes.data, len(self.planes), self.es, self.depth, self.full_range, self.params[1],
+                                             self.h_gains.ctypes.data, self.gains.data_ptr(), dst, self.Pb, stream), 'payload_grain')
+
+
+STAGES = {'mix': Shutter, 'scale': Scaler, 'encode': Encoder, 'grain': Grain, 'weave': Interlacer, 'requant': Requantizer}
 
 
 class TileGrid:

@@ -612,6 +612,34 @@ int demfi_payload_requant(const uint8_t* base, const int64_t* offsets, const int
                           int n_planes, int in_bytes, int out_bytes, int depth_in, int depth_out, int full_range, int dither,
                           int field_rows, uint8_t* dst, int64_t dst_stride, void* stream);
 
+/* ---- film grain at the egress of the Y4M edge (csrc/grain.hip; demfi_amd/video.py --grain) ---------------------------------------------
+ * payload_grain: written payload i (n per launch) is the source payload at base + offsets[i] (int64 BYTE offsets) with synthetic grain
+ * added.  A payload is n_planes (1 or 3) planes one behind the other, plane p of planes[2 p] rows and planes[2 p + 1] columns of samples
+ * (1..65531 each; HOST memory; a payload stays below 2^31 bytes), the first luma, the others chroma of one shape: the luma's or half of
+ * it, rounded up, on either axis (sx, sy = 1 or 2).  sample_bytes = 1 at depth 8, 2 (little-endian; even addresses, offsets and stride) at
+ * 10, 12, 14 and 16.  keys: uint32 [3 n], the key of plane p of payload i at keys[3 i + p] (demfi_amd/grain.py plane_key; three words per
+ * payload whatever n_planes); gains: int32 [2][256], the gain tables of luma and chroma (grain.gain_tables).  In exact integers, >> an
+ * arithmetic shift, mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 on uint32:
+ *   white(X, Y) = b0 + b1 + b2 + b3 - 510 over the bytes of mix32(key ^ mix32((Y << 16) | X))
+ *   F(x, y)     = sum over i, j in -size..size of c[i] c[j] white(x + 2 + i, y + 2 + j), c = [1], [1,2,1], [1,4,6,4,1] for size 0, 1, 2
+ *   out         = clip(v + ((F * G[min(L >> (depth - 8), 255)] + 2^15) >> 16), min(lo, v), max(hi, v))
+ * L is the source payload's own luma: v in the luma plane, for the chroma sample (x, y) the luma sample at (min(x sx, w - 1), min(y sy,
+ * h - 1)); lo / hi: full_range = 0: 16 << (depth - 8) and 235 << (depth - 8) (chroma: 240 << (depth - 8)), full_range = 1: 0 and 2^depth
+ * - 1.  v is the stored sample, whatever it holds.  The numpy definition is grain.grain_payload_np.  The payload is written at dst +
+ * i*dst_stride; the bytes between its end and dst_stride are not written.  offsets, keys and gains are passed twice with the same
+ * content: in HOST memory, checked here before anything is launched, and (offsets_dev, keys_dev, gains_dev) in DEVICE memory, read by
+ * the kernel.  DEMFI_ERR_ARG, with nothing launched: a NULL buffer, n < 0, a plane count other than 1 or 3, a plane size out of range,
+ * chroma planes that do not fit the luma plane, a depth that is none of the five, sample_bytes that do not fit it, full_range not 0 or 1,
+ * size outside 0..2, a gain that is negative or so large that F * G + 2^15 could leave int32 at this size, a payload of 2^31 bytes or
+ * more, 16-bit samples at an odd address, offset or stride, keys_dev or gains_dev off a 4-byte boundary, dst_stride below the payload, a
+ * negative offset.  One launch for all n payloads: a 256-thread workgroup owns 64 columns x 16 rows of one plane, hashes the white
+ * cells of the tile and its halo once into LDS (int16), runs the separable taps through LDS (size 0: no LDS for the noise), keeps the
+ * plane's gain table in LDS and moves the samples with 16-byte loads and stores where the addresses allow, sample by sample otherwise.
+ * No atomics; the sources may overlap each other but not dst; n == 0 does nothing. */
+int demfi_payload_grain(const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, const uint32_t* keys,
+                        const uint32_t* keys_dev, int n, const int32_t* planes, int n_planes, int sample_bytes, int depth, int full_range,
+                        int size, const int32_t* gains, const int32_t* gains_dev, uint8_t* dst, int64_t dst_stride, void* stream);
+
 /* ---- linear light at the Y4M edge (csrc/colour.hip; demfi_amd/video.py --linear-light) -------------------------------------------------
  * A LINEAR payload of an h x w frame is uint16 [3, h, w]: planes B, G, R at full resolution, linear light 0 .. 65535, whatever the working
  * depth (8, 10 or 12) and the chroma layout.  The functions compute no transfer function: fwd_table (DEVICE, uint16 [2^depth]: code ->
