@@ -24,40 +24,18 @@
 // floor).  (v - off_in) * num + T is negative for chroma below neutral and reaches 65535 * 65535 + 65534 for stored samples above their
 // peak, so a signed value or a bias would need 64 bits (bitdepth.accumulator_bounds); the kernel divides magnitudes instead: for a =
 // v - off_in >= 0 the quotient of a num + T, for a < 0 minus the quotient of |a| num + (den - 1 - T), both below 2^32.
-#include "common.h"
+#include "payload_kit.h"
 
 namespace {
 
 constexpr int NT = 256;                 // threads of a workgroup
-constexpr int MAXP = 3;                 // planes of a payload at most
 enum { M_UP = 0, M_DOWN = 1, M_FULL = 2 };
-typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
-
-struct Planes {
-    int n;
-    int rows[MAXP], cols[MAXP];
-    int64_t start[MAXP];                // first sample of the plane in the payload
-};
 
 struct Rule {                           // uniform over the launch; off[0] luma, off[1] chroma
     int off_in[2], off_out[2];
     uint32_t num, den, magic;
     int shift;                          // limited range: |d_out - d_in|; full range: s of the reciprocal
     int peak, bayer, field_rows;
-};
-
-template <typename T> struct Word;      // the 8 samples of an item
-template <> struct Word<uint8_t> {
-    typedef u2_t V;
-    static __device__ __forceinline__ uint32_t at(const V& v, int i) { return (v[i >> 2] >> (8 * (i & 3))) & 0xffu; }
-    static __device__ __forceinline__ void put(V& v, int i, uint32_t x) { v[i >> 2] |= x << (8 * (i & 3)); }
-    static __device__ __forceinline__ V zero() { return V{0u, 0u}; }
-};
-template <> struct Word<uint16_t> {
-    typedef u4_t V;
-    static __device__ __forceinline__ uint32_t at(const V& v, int i) { return (v[i >> 1] >> (16 * (i & 1))) & 0xffffu; }
-    static __device__ __forceinline__ void put(V& v, int i, uint32_t x) { v[i >> 1] |= x << (16 * (i & 1)); }
-    static __device__ __forceinline__ V zero() { return V{0u, 0u, 0u, 0u}; }
 };
 
 // bits 0, 1, 2 of a -> bits 5, 3, 1; G = F >> 1.  B(x, y) = F((x ^ y) & 7) | G(y & 7)
@@ -90,7 +68,7 @@ template <int MODE> __device__ __forceinline__ uint32_t convert(uint32_t v, uint
 // grid: x = chunks of NT items of a plane (strided), y = (payload, plane) pairs (strided).  WIDE: item = row * words + word of 8 samples;
 // else item = row * cols + column.
 template <typename TI, typename TO, int MODE, bool WIDE>
-__global__ __launch_bounds__(NT) void payload_depth_kernel(const uint8_t* __restrict__ base, const int64_t* __restrict__ offs, int n, Planes pl,
+__global__ __launch_bounds__(NT) void payload_depth_kernel(const uint8_t* __restrict__ base, const int64_t* __restrict__ offs, int n, PlaneList pl,
                                                           Rule rule, uint8_t* __restrict__ dst, int64_t dst_stride)
 {
     constexpr int ei = (int)sizeof(TI), eo = (int)sizeof(TO);
@@ -105,14 +83,14 @@ __global__ __launch_bounds__(NT) void payload_depth_kernel(const uint8_t* __rest
             for (uint32_t it = blockIdx.x * NT + threadIdx.x; it < items; it += gridDim.x * NT) {
                 const uint32_t y = it / words, c = it - y * words;
                 const int64_t at = (int64_t)y * cols + (int64_t)c * 8;       // the item's first sample in the plane
-                const typename Word<TI>::V v = *gcp<typename Word<TI>::V>(src + at * ei);
+                const typename Strip<TI>::V v = *gcp<typename Strip<TI>::V>(src + at * ei);   // an item of the wide path is aligned
                 const uint32_t yy = (rule.field_rows ? y >> 1 : y) & 7u;
                 const uint32_t fy = bayer_f(yy), gy = fy >> 1;
-                typename Word<TO>::V o = Word<TO>::zero();
+                typename Strip<TO>::V o = Strip<TO>::zero();
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
-                    Word<TO>::put(o, i, convert<MODE>(Word<TI>::at(v, i), threshold<MODE>((bayer_f((uint32_t)i) ^ fy) | gy, rule), chroma, rule));
-                __builtin_nontemporal_store(o, gp<typename Word<TO>::V>(out + at * eo));
+                    Strip<TO>::put(o, i, convert<MODE>(Strip<TI>::at(v, i), threshold<MODE>((bayer_f((uint32_t)i) ^ fy) | gy, rule), chroma, rule));
+                __builtin_nontemporal_store(o, gp<typename Strip<TO>::V>(out + at * eo));
             }
         } else {
             const uint32_t items = cols * rows;                             // <= 2^30
@@ -128,8 +106,6 @@ __global__ __launch_bounds__(NT) void payload_depth_kernel(const uint8_t* __rest
     }
 }
 
-bool is_depth(int d) { return d == 8 || d == 10 || d == 12 || d == 14 || d == 16; }
-
 // both entry points: ``up`` says which way the depths must go
 int payload_depth(const char* fn, bool up, const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, int n, const int32_t* planes,
                   int n_planes, int in_bytes, int out_bytes, int depth_in, int depth_out, int full_range, int dither, int field_rows,
@@ -137,7 +113,6 @@ int payload_depth(const char* fn, bool up, const uint8_t* base, const int64_t* o
 {
     if (n < 0) return demfi_set_error(DEMFI_ERR_ARG, "%s: n=%d", fn, n);
     if (!base || !offsets || !offsets_dev || !planes || !dst) return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer", fn);
-    if (n_planes < 1 || n_planes > MAXP) return demfi_set_error(DEMFI_ERR_ARG, "%s: %d planes (1..%d)", fn, n_planes, MAXP);
     if (!is_depth(depth_in) || !is_depth(depth_out) || (up ? depth_out <= depth_in : depth_out >= depth_in))
         return demfi_set_error(DEMFI_ERR_ARG, "%s: %d -> %d bits (8, 10, 12, 14 or 16 each, going %s)", fn, depth_in, depth_out, up ? "up" : "down");
     if (in_bytes != (depth_in > 8 ? 2 : 1) || out_bytes != (depth_out > 8 ? 2 : 1))
@@ -145,29 +120,16 @@ int payload_depth(const char* fn, bool up, const uint8_t* base, const int64_t* o
                                depth_in, depth_out);
     if ((full_range | 1) != 1 || (dither | 1) != 1 || (field_rows | 1) != 1)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: full_range=%d, dither=%d, field_rows=%d (0 or 1 each)", fn, full_range, dither, field_rows);
-    Planes pl = {};
-    pl.n = n_planes;
-    int64_t P = 0, most = 0;
+    PlaneSet ps;
+    if (int st = parse_planes(fn, planes, n_planes, 1 << 20, (int64_t)1 << 30, false, &ps)) return st;
+    const PlaneList& pl = ps.pl;
     bool by8 = true;                                                         // every plane starts and every row ends on 8 samples
-    for (int p = 0; p < n_planes; ++p) {
-        const int rows = planes[2 * p], cols = planes[2 * p + 1];
-        if (rows < 1 || cols < 1 || rows > (1 << 20) || cols > (1 << 20) || (int64_t)rows * cols > ((int64_t)1 << 30))
-            return demfi_set_error(DEMFI_ERR_ARG, "%s: plane %d is %d x %d (1..2^20 each, 2^30 samples at most)", fn, p, rows, cols);
-        pl.rows[p] = rows, pl.cols[p] = cols, pl.start[p] = P;
-        by8 = by8 && P % 8 == 0 && cols % 8 == 0;
-        most = max(most, (int64_t)rows * cols);
-        P += (int64_t)rows * cols;
-    }
-    if (dst_stride < P * out_bytes)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: dst_stride=%lld below the %lld bytes of a payload", fn, (long long)dst_stride,
-                               (long long)(P * out_bytes));
+    for (int p = 0; p < n_planes; ++p) by8 = by8 && pl.start[p] % 8 == 0 && pl.cols[p] % 8 == 0;
+    if (int st = check_dst_stride(fn, dst_stride, ps.P * out_bytes)) return st;
     uintptr_t lo_in = (uintptr_t)base, lo_out = (uintptr_t)dst | (uintptr_t)dst_stride;   // the low bits of every address the kernel forms
-    for (int r = 0; r < n; ++r) {
-        if (offsets[r] < 0) return demfi_set_error(DEMFI_ERR_ARG, "%s: row %d offset is %lld", fn, r, (long long)offsets[r]);
-        lo_in |= (uintptr_t)offsets[r];
-    }
-    if ((in_bytes == 2 && (lo_in & 1)) || (out_bytes == 2 && (lo_out & 1)))
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: 16-bit samples at an odd address, offset or stride", fn);
+    if (int st = walk_offsets(fn, offsets, n, 1, 1, OFFS_ALL, 0, NO_LIMIT, 0, &lo_in)) return st;
+    if (int st = check_even(fn, in_bytes, lo_in)) return st;
+    if (int st = check_even(fn, out_bytes, lo_out)) return st;
     if (n == 0) return DEMFI_OK;
     const bool wide = by8 && (lo_in & (uintptr_t)(8 * in_bytes - 1)) == 0 && (lo_out & (uintptr_t)(8 * out_bytes - 1)) == 0;
 
@@ -186,19 +148,18 @@ int payload_depth(const char* fn, bool up, const uint8_t* base, const int64_t* o
         rule.magic = (uint32_t)(((1ull << 32) * ((1ull << l) - rule.den)) / rule.den + 1ull);
         rule.shift = l - 1;
     }
-    const int64_t items = wide ? most / 8 : most;
-    const dim3 grid((unsigned)min((items + NT - 1) / NT, (int64_t)4096), (unsigned)min((int64_t)n * n_planes, (int64_t)4096));
-    const hipStream_t st = (hipStream_t)stream;
-#define DEPTH_LAUNCH(TI, TO, M, W) \
-    hipLaunchKernelGGL((payload_depth_kernel<TI, TO, M, W>), grid, dim3(NT), 0, st, base, offsets_dev, n, pl, rule, dst, dst_stride)
-#define DEPTH_MODES(TI, TO, W) \
-    do { if (mode == M_UP) DEPTH_LAUNCH(TI, TO, M_UP, W); else if (mode == M_DOWN) DEPTH_LAUNCH(TI, TO, M_DOWN, W); else DEPTH_LAUNCH(TI, TO, M_FULL, W); } while (0)
-#define DEPTH_TYPES(W) \
-    do { if (in_bytes == 1) DEPTH_MODES(uint8_t, uint16_t, W); else if (out_bytes == 1) DEPTH_MODES(uint16_t, uint8_t, W); else DEPTH_MODES(uint16_t, uint16_t, W); } while (0)
-    if (wide) DEPTH_TYPES(true); else DEPTH_TYPES(false);
-#undef DEPTH_TYPES
-#undef DEPTH_MODES
-#undef DEPTH_LAUNCH
+    const dim3 grid = planes_grid(wide ? ps.most / 8 : ps.most, NT, n, n_planes);
+    // storage: 0 = bytes -> 16 bits, 1 = 16 bits -> bytes, 2 = 16 -> 16 (a byte source always has a 16-bit destination)
+    by_int<0, 2>(in_bytes == 1 ? 0 : out_bytes == 1 ? 1 : 2, [&](auto s) {
+        typedef typename std::conditional<TAG_VALUE(s) == 0, uint8_t, uint16_t>::type TI;
+        typedef typename std::conditional<TAG_VALUE(s) == 1, uint8_t, uint16_t>::type TO;
+        by_int<M_UP, M_FULL>(mode, [&](auto m) {
+            by_bool(wide, [&](auto w) {
+                hipLaunchKernelGGL((payload_depth_kernel<TI, TO, TAG_VALUE(m), TAG_VALUE(w)>), grid, dim3(NT), 0, (hipStream_t)stream, base,
+                                   offsets_dev, n, pl, rule, dst, dst_stride);
+            });
+        });
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }

@@ -141,8 +141,7 @@ __global__ __launch_bounds__(NT) void linear_to_yuv_kernel(const uint8_t* __rest
 int check_frame(const char* fn, int n, int h, int w, int depth)
 {
     if (n < 0) return demfi_set_error(DEMFI_ERR_ARG, "%s: n=%d", fn, n);
-    if (h < 2 || w < 2 || h > 16384 || w > 16384)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: frame size %dx%d outside 2..16384", fn, h, w);
+    if (int st = check_frame_size(fn, h, w)) return st;
     if (depth != 8 && depth != 10 && depth != 12)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: bit depth %d (8, 10 or 12: above, 16 bits of light do not tell the codes apart)", fn, depth);
     return DEMFI_OK;
@@ -175,8 +174,7 @@ extern "C" int demfi_bgr_to_linear_gather(const void* base, const int64_t* src_o
     if (!base || !src_offsets || !dst || !fwd_table) return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer", fn);
     int st = check_frame(fn, n, h, w, depth);
     if (st < 0) return st;
-    if (sample_bytes != 1 && sample_bytes != 2)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: %d bytes per sample (1 or 2)", fn, sample_bytes);
+    if (int st = check_sample_bytes(fn, sample_bytes)) return st;
     if (sample_bytes == 1 && depth != 8)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: %d-bit codes in bytes", fn, depth);
     if (((uintptr_t)dst & 1) || ((uintptr_t)fwd_table & 1) || (sample_bytes == 2 && ((uintptr_t)base & 1)))
@@ -188,12 +186,10 @@ extern "C" int demfi_bgr_to_linear_gather(const void* base, const int64_t* src_o
     const dim3 grid = lanes_grid(n, h, w);
     const int peak = (1 << depth) - 1;
     hipStream_t s = (hipStream_t)stream;
-    if (sample_bytes == 1)
-        hipLaunchKernelGGL(bgr_to_linear_gather_kernel<uint8_t>, grid, dim3(NT), 0, s, (const uint8_t*)base, src_offsets, dst, dst_stride, n, h,
-                           w, peak, fwd_table);
-    else
-        hipLaunchKernelGGL(bgr_to_linear_gather_kernel<uint16_t>, grid, dim3(NT), 0, s, (const uint16_t*)base, src_offsets, dst, dst_stride, n,
+    by_sample(sample_bytes, [&](auto t) {
+        hipLaunchKernelGGL(bgr_to_linear_gather_kernel<TAG_TYPE(t)>, grid, dim3(NT), 0, s, (const TAG_TYPE(t)*)base, src_offsets, dst, dst_stride, n,
                            h, w, peak, fwd_table);
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }
@@ -212,16 +208,11 @@ extern "C" int demfi_linear_to_yuv(const uint8_t* src, const int64_t* offsets, c
         return demfi_set_error(DEMFI_ERR_ARG, "%s: matrix %d / full_range %d", fn, matrix, full_range);
     const int out_bytes = depth > 8 ? 2 : 1;
     const int64_t payload = payload_of(layout, h, w) * out_bytes;
-    if (dst_stride < payload)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: dst_stride=%lld below the %lld bytes of a payload", fn, (long long)dst_stride,
-                               (long long)payload);
+    if (int st = check_dst_stride(fn, dst_stride, payload)) return st;
     uintptr_t odd = (uintptr_t)src | (uintptr_t)inv_table;
     if (out_bytes == 2) odd |= (uintptr_t)dst | (uintptr_t)dst_stride;
-    for (int i = 0; i < n; ++i) {
-        if (offsets[i] < 0) return demfi_set_error(DEMFI_ERR_ARG, "%s: row %d offset is %lld", fn, i, (long long)offsets[i]);
-        odd |= (uintptr_t)offsets[i];
-    }
-    if (odd & 1) return demfi_set_error(DEMFI_ERR_ARG, "%s: 16-bit samples at an odd address, offset or stride", fn);
+    if (int st = walk_offsets(fn, offsets, n, 1, 1, OFFS_ALL, 0, NO_LIMIT, 0, &odd)) return st;
+    if (int st = check_even(fn, 2, odd)) return st;                     // the linear payloads are 16-bit whatever the output is
     if (n == 0) return DEMFI_OK;
     const dim3 grid = lanes_grid(n, layout == DEMFI_YUV_420 ? (h + 1) / 2 : h, w);
     const ToYuv k = to_yuv_coefs(matrix, full_range, depth);

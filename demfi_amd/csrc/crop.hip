@@ -12,7 +12,7 @@
 // bytes of row t of the tile and sends them off with ONE atomicAdd per (row, tile column), the four waves add their column
 // counters in LDS and thread t sends columns t and t + 256 off with ONE atomicAdd per (column, tile row): consecutive lanes,
 // consecutive words.  Zero sums (bars) send nothing.  Integer adds are exact in any order.
-#include "common.h"
+#include "payload_kit.h"
 
 namespace {
 
@@ -22,26 +22,6 @@ constexpr int TW = 64 * SW;             // tile width
 constexpr int RS = 32;                  // rows of a wave
 constexpr int TH = (NT / 64) * RS;      // tile height
 constexpr int RB = 64 + 4;              // bytes of a row's lane counts in LDS: 17 words, so the row sums read without bank conflicts
-
-typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
-typedef u2_t u2_unaligned __attribute__((aligned(1)));
-typedef u4_t u4_unaligned2 __attribute__((aligned(2)));
-
-template <typename T> struct Strip;     // 8 consecutive samples as one packed word
-template <> struct Strip<uint8_t> {
-    typedef u2_t word;
-    static __device__ __forceinline__ word load(const uint8_t* p) { return *(const DEMFI_GLOBAL u2_unaligned*)p; }
-    static __device__ __forceinline__ uint32_t at(const word& v, int i) { return ((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 0xffu; }
-};
-template <> struct Strip<uint16_t> {
-    typedef u4_t word;
-    static __device__ __forceinline__ word load(const uint16_t* p) { return *(const DEMFI_GLOBAL u4_unaligned2*)p; }
-    static __device__ __forceinline__ uint32_t at(const word& v, int i)
-    {
-        const uint32_t d = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
-        return (d >> (16 * (i & 1))) & 0xffffu;
-    }
-};
 
 // grid: x = the tiles of a plane, y = planes (strided).  T: the sample type; offsets count bytes.
 template <typename T>
@@ -66,7 +46,7 @@ __global__ __launch_bounds__(NT) void luma_line_counts_kernel(const uint8_t* __r
         if (sw == SW) {
 #pragma unroll 4
             for (int r = 0; r < nr; ++r) {
-                const typename Strip<T>::word v = Strip<T>::load(p + (int64_t)r * w);
+                const typename Strip<T>::V v = Strip<T>::load(p + (int64_t)r * w);
                 uint32_t k = 0;
 #pragma unroll
                 for (int i = 0; i < SW; ++i) {
@@ -119,25 +99,20 @@ extern "C" int demfi_luma_line_counts(const uint8_t* base, const int64_t* offset
     const char* fn = "demfi_luma_line_counts";
     if (!base || !offsets || !rows || !cols || n < 0)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer or n=%d", fn, n);
-    if (h < 2 || w < 2 || h > 16384 || w > 16384)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: frame size %dx%d outside 2..16384", fn, h, w);
-    if (sample_bytes != 1 && sample_bytes != 2)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: %d bytes per sample (1 or 2)", fn, sample_bytes);
+    if (int st = check_frame_size(fn, h, w)) return st;
+    if (int st = check_sample_bytes(fn, sample_bytes)) return st;
     if (thresh < 0 || thresh > 65535)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: threshold %lld outside 0..65535", fn, (long long)thresh);
-    if (sample_bytes == 2 && ((uintptr_t)base & 1))
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: 16-bit samples at an odd address", fn);
+    if (int st = check_even(fn, sample_bytes, (uintptr_t)base)) return st;
     if (n == 0) return DEMFI_OK;
     DEMFI_HIP_CHECK(hipMemsetAsync(rows, 0, (size_t)n * h * sizeof(uint32_t), (hipStream_t)stream));
     DEMFI_HIP_CHECK(hipMemsetAsync(cols, 0, (size_t)n * w * sizeof(uint32_t), (hipStream_t)stream));
     const int tiles = ((w + TW - 1) / TW) * ((h + TH - 1) / TH);         // at most 32 * 128
     const dim3 grid((unsigned)tiles, (unsigned)min(n, 65535));
-    if (sample_bytes == 1)
-        hipLaunchKernelGGL(luma_line_counts_kernel<uint8_t>, grid, dim3(NT), 0, (hipStream_t)stream, base, offsets, n, h, w, (uint32_t)thresh,
+    by_sample(sample_bytes, [&](auto t) {
+        hipLaunchKernelGGL(luma_line_counts_kernel<TAG_TYPE(t)>, grid, dim3(NT), 0, (hipStream_t)stream, base, offsets, n, h, w, (uint32_t)thresh,
                            rows, cols);
-    else
-        hipLaunchKernelGGL(luma_line_counts_kernel<uint16_t>, grid, dim3(NT), 0, (hipStream_t)stream, base, offsets, n, h, w, (uint32_t)thresh,
-                           rows, cols);
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }

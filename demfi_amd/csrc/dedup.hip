@@ -12,7 +12,7 @@
 // alignment: the 8-byte (16-byte) loads are unaligned ones, which global memory serves (tile.hip's copy_piece and
 // yuv420_sad_kernel read the same way).  Partial blocks go sample by sample.  A workgroup is ONE wave: the reduction is a ballot
 // and a popcount, and lane 0 adds the wave's counts with one atomicAdd per counter (integer adds are exact in any order).
-#include "common.h"
+#include "payload_kit.h"
 
 namespace {
 
@@ -20,25 +20,10 @@ constexpr int NT = 64;
 constexpr int BS = 8;                   // block side
 constexpr int64_t MAX_THRESHOLD = (int64_t)1 << 40;   // hi_s * 64 stays far inside 64 bits
 
-typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
-typedef u2_t u2_unaligned __attribute__((aligned(1)));
-typedef u4_t u4_unaligned2 __attribute__((aligned(2)));
-
-// SAD of 8 consecutive samples
-__device__ __forceinline__ uint32_t row_sad(const uint8_t* a, const uint8_t* b, uint32_t acc)
+// SAD of 8 consecutive samples at any sample address
+template <typename T> __device__ __forceinline__ uint32_t row_sad(const T* a, const T* b, uint32_t acc)
 {
-    const u2_t x = *(const DEMFI_GLOBAL u2_unaligned*)a, y = *(const DEMFI_GLOBAL u2_unaligned*)b;
-    acc = __builtin_amdgcn_sad_u8(x.x, y.x, acc);
-    return __builtin_amdgcn_sad_u8(x.y, y.y, acc);
-}
-
-__device__ __forceinline__ uint32_t row_sad(const uint16_t* a, const uint16_t* b, uint32_t acc)
-{
-    const u4_t x = *(const DEMFI_GLOBAL u4_unaligned2*)a, y = *(const DEMFI_GLOBAL u4_unaligned2*)b;
-    acc = __builtin_amdgcn_sad_u16(x.x, y.x, acc);
-    acc = __builtin_amdgcn_sad_u16(x.y, y.y, acc);
-    acc = __builtin_amdgcn_sad_u16(x.z, y.z, acc);
-    return __builtin_amdgcn_sad_u16(x.w, y.w, acc);
+    return Strip<T>::sad(Strip<T>::load(a), Strip<T>::load(b), acc);
 }
 
 // grid: x = waves over the blocks of a plane, y = pairs (strided).  T: the sample type; offsets count bytes.
@@ -90,24 +75,19 @@ extern "C" int demfi_luma_block_counts(const uint8_t* base, const int64_t* a_off
     const char* fn = "demfi_luma_block_counts";
     if (!base || !a_offsets || !b_offsets || !counts || n < 0)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer or n=%d", fn, n);
-    if (h < 2 || w < 2 || h > 16384 || w > 16384)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: frame size %dx%d outside 2..16384", fn, h, w);
-    if (sample_bytes != 1 && sample_bytes != 2)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: %d bytes per sample (1 or 2)", fn, sample_bytes);
+    if (int st = check_frame_size(fn, h, w)) return st;
+    if (int st = check_sample_bytes(fn, sample_bytes)) return st;
     if (hi_s < 0 || lo_s < 0 || hi_s > MAX_THRESHOLD || lo_s > MAX_THRESHOLD)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: thresholds %lld, %lld outside 0..2^40", fn, (long long)hi_s, (long long)lo_s);
-    if (sample_bytes == 2 && ((uintptr_t)base & 1))
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: 16-bit samples at an odd address", fn);
+    if (int st = check_even(fn, sample_bytes, (uintptr_t)base)) return st;
     if (n == 0) return DEMFI_OK;
     DEMFI_HIP_CHECK(hipMemsetAsync(counts, 0, (size_t)n * 2 * sizeof(uint32_t), (hipStream_t)stream));
     const int nblk = ((w + BS - 1) / BS) * ((h + BS - 1) / BS);
     const dim3 grid((unsigned)((nblk + NT - 1) / NT), (unsigned)min(n, 65535));
-    if (sample_bytes == 1)
-        hipLaunchKernelGGL(luma_block_counts_kernel<uint8_t>, grid, dim3(NT), 0, (hipStream_t)stream, base, a_offsets, b_offsets, n, h, w,
+    by_sample(sample_bytes, [&](auto t) {
+        hipLaunchKernelGGL(luma_block_counts_kernel<TAG_TYPE(t)>, grid, dim3(NT), 0, (hipStream_t)stream, base, a_offsets, b_offsets, n, h, w,
                            (uint64_t)hi_s, (uint64_t)lo_s, counts);
-    else
-        hipLaunchKernelGGL(luma_block_counts_kernel<uint16_t>, grid, dim3(NT), 0, (hipStream_t)stream, base, a_offsets, b_offsets, n, h, w,
-                           (uint64_t)hi_s, (uint64_t)lo_s, counts);
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }

@@ -235,24 +235,17 @@ extern "C" int demfi_yuv_deint_adaptive(void* base, int64_t size_bytes, const in
     const char* fn = "demfi_yuv_deint_adaptive";
     if (!base || !offsets || !offsets_dev || n < 0 || n > 64)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer or n=%d outside 0..64", fn, n);
-    if (h < 2 || w < 2 || h > 16384 || w > 16384)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: frame size %dx%d outside 2..16384", fn, h, w);
+    if (int st = check_frame_size(fn, h, w)) return st;
     if (layout != DEMFI_YUV_420 && layout != DEMFI_YUV_422 && layout != DEMFI_YUV_444 && layout != DEMFI_YUV_MONO)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: layout %d", fn, layout);
-    if (sample_bytes != 1 && sample_bytes != 2)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: %d bytes per sample (1 or 2)", fn, sample_bytes);
-    if (sample_bytes == 2 && ((uintptr_t)base & 1))
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: 16-bit samples at an odd address", fn);
+    if (int st = check_sample_bytes(fn, sample_bytes)) return st;
     const int64_t pb = payload_of(layout, h, w) * sample_bytes;
+    // a field's five payloads: absent ones anywhere but its own, in the middle; a whole payload inside the buffer
+    uintptr_t low = (uintptr_t)base;
+    if (int st = walk_offsets(fn, offsets, n, 5, 5, OFFS_BUT_CENTRE, 2, size_bytes - pb, 0, &low)) return st;
+    if (int st = check_even(fn, sample_bytes, low)) return st;
     for (int i = 0; i < n; ++i) {
         const int64_t* o = offsets + 5 * i;
-        for (int k = 0; k < 5; ++k) {
-            if (o[k] == -1 && k != 2) continue;
-            if (o[k] < 0 || o[k] > size_bytes - pb || (sample_bytes == 2 && (o[k] & 1)))
-                return demfi_set_error(DEMFI_ERR_ARG, "%s: field %d, payload %d of 5: offset %lld (payloads of %lld bytes in a buffer of %lld%s)",
-                                       fn, i, k, (long long)o[k], (long long)pb, (long long)size_bytes,
-                                       k == 2 ? "; the field's own payload cannot be absent" : "");
-        }
         if (o[1] < 0 && o[3] < 0)
             return demfi_set_error(DEMFI_ERR_ARG, "%s: field %d has neither the field before it nor the one after it", fn, i);
         for (int j = 0; j < i; ++j)
@@ -264,10 +257,9 @@ extern "C" int demfi_yuv_deint_adaptive(void* base, int64_t size_bytes, const in
     const int cw = layout == DEMFI_YUV_444 ? w : layout == DEMFI_YUV_MONO ? 0 : (w + 1) / 2;
     const int64_t lanes = (int64_t)((h + 1) / 2) * ((w + SX - 1) / SX) + 2 * (int64_t)((ch + 1) / 2) * ((cw + SX - 1) / SX);
     const dim3 grid((unsigned)((lanes + NT - 1) / NT), (unsigned)n);
-    if (sample_bytes == 1)
-        hipLaunchKernelGGL(adaptive_kernel<uint8_t>, grid, dim3(NT), 0, (hipStream_t)stream, (uint8_t*)base, offsets_dev, h, w, ch, cw, odd_mask);
-    else
-        hipLaunchKernelGGL(adaptive_kernel<uint16_t>, grid, dim3(NT), 0, (hipStream_t)stream, (uint8_t*)base, offsets_dev, h, w, ch, cw, odd_mask);
+    by_sample(sample_bytes, [&](auto t) {
+        hipLaunchKernelGGL(adaptive_kernel<TAG_TYPE(t)>, grid, dim3(NT), 0, (hipStream_t)stream, (uint8_t*)base, offsets_dev, h, w, ch, cw, odd_mask);
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }
@@ -278,14 +270,11 @@ extern "C" int demfi_yuv_bob(void* payloads, int64_t stride_bytes, int n, int h,
     const char* fn = "demfi_yuv_bob";
     if (!payloads || n < 0 || n > 64)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer or n=%d outside 0..64", fn, n);
-    if (h < 2 || w < 2 || h > 16384 || w > 16384)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: frame size %dx%d outside 2..16384", fn, h, w);
+    if (int st = check_frame_size(fn, h, w)) return st;
     if (layout != DEMFI_YUV_420 && layout != DEMFI_YUV_422 && layout != DEMFI_YUV_444 && layout != DEMFI_YUV_MONO)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: layout %d", fn, layout);
-    if (sample_bytes != 1 && sample_bytes != 2)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: %d bytes per sample (1 or 2)", fn, sample_bytes);
-    if (sample_bytes == 2 && (((uintptr_t)payloads & 1) || (stride_bytes & 1)))
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: 16-bit samples at an odd address or stride", fn);
+    if (int st = check_sample_bytes(fn, sample_bytes)) return st;
+    if (int st = check_even(fn, sample_bytes, (uintptr_t)payloads | (uintptr_t)stride_bytes)) return st;
     if (stride_bytes < payload_of(layout, h, w) * sample_bytes)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: stride of %lld bytes below the payload's %lld", fn, (long long)stride_bytes,
                                (long long)(payload_of(layout, h, w) * sample_bytes));
@@ -294,12 +283,9 @@ extern "C" int demfi_yuv_bob(void* payloads, int64_t stride_bytes, int n, int h,
     const int cw = layout == DEMFI_YUV_444 ? w : layout == DEMFI_YUV_MONO ? 0 : (w + 1) / 2;
     const int64_t lanes = (int64_t)((h + 1) / 2) * ((w + SX - 1) / SX) + 2 * (int64_t)((ch + 1) / 2) * ((cw + SX - 1) / SX);
     const dim3 grid((unsigned)((lanes + NT - 1) / NT), (unsigned)n);
-    if (sample_bytes == 1)
-        hipLaunchKernelGGL(bob_kernel<uint8_t>, grid, dim3(NT), 0, (hipStream_t)stream, (uint8_t*)payloads, stride_bytes, h, w, ch, cw,
-                           odd_mask);
-    else
-        hipLaunchKernelGGL(bob_kernel<uint16_t>, grid, dim3(NT), 0, (hipStream_t)stream, (uint8_t*)payloads, stride_bytes, h, w, ch, cw,
-                           odd_mask);
+    by_sample(sample_bytes, [&](auto t) {
+        hipLaunchKernelGGL(bob_kernel<TAG_TYPE(t)>, grid, dim3(NT), 0, (hipStream_t)stream, (uint8_t*)payloads, stride_bytes, h, w, ch, cw, odd_mask);
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }

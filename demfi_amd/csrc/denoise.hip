@@ -17,7 +17,7 @@
 // from the host copy of the offsets, for the launch as a whole.  The last P * es mod 16 bytes of a payload go sample by sample.  Otherwise
 // (mono frames of odd size have an odd P) a thread owns one sample at a time, consecutive lanes consecutive samples; the arithmetic is the
 // same.  Every byte offset and every index inside a payload is 64-bit: the payload ring of 8K 16-bit video passes 4 GiB.
-#include "common.h"
+#include "payload_kit.h"
 
 namespace {
 
@@ -34,18 +34,6 @@ __device__ __forceinline__ uint32_t mean_of(uint32_t s, uint32_t n)
     for (uint32_t k = 2; k <= 7; ++k) m = n == k ? MAGIC[k - 1] : m;
     return __umulhi(2u * s + n, m);
 }
-
-template <typename T> struct Samples;   // the 16 / sizeof(T) samples of a 16-byte word
-template <> struct Samples<uint8_t> {
-    static constexpr int N = 16;
-    static __device__ __forceinline__ uint32_t at(const u4_t& v, int i) { return (v[i >> 2] >> (8 * (i & 3))) & 0xffu; }
-    static __device__ __forceinline__ void put(u4_t& v, int i, uint32_t x) { v[i >> 2] |= x << (8 * (i & 3)); }
-};
-template <> struct Samples<uint16_t> {
-    static constexpr int N = 8;
-    static __device__ __forceinline__ uint32_t at(const u4_t& v, int i) { return (v[i >> 1] >> (16 * (i & 1))) & 0xffffu; }
-    static __device__ __forceinline__ void put(u4_t& v, int i, uint32_t x) { v[i >> 1] |= x << (16 * (i & 1)); }
-};
 
 // One step of a side's walk: the sample x of the next frame outward.  alive: the side has not stopped yet.
 __device__ __forceinline__ void step(uint32_t c, uint32_t x, uint32_t A, uint32_t B, uint32_t& acc, bool& alive, uint32_t& sum, uint32_t& n)
@@ -133,22 +121,6 @@ __global__ __launch_bounds__(NT) void payload_denoise_kernel(const uint8_t* __re
     }
 }
 
-template <typename T, int R>
-void launch(bool vec, dim3 grid, hipStream_t st, const uint8_t* src, const int64_t* offs, int n, int64_t P, uint32_t A, uint32_t B, uint8_t* dst)
-{
-    if (vec) hipLaunchKernelGGL((payload_denoise_kernel<T, R, true>), grid, dim3(NT), 0, st, src, offs, n, P, A, B, dst);
-    else     hipLaunchKernelGGL((payload_denoise_kernel<T, R, false>), grid, dim3(NT), 0, st, src, offs, n, P, A, B, dst);
-}
-
-template <typename T>
-void launch_r(int R, bool vec, dim3 grid, hipStream_t st, const uint8_t* src, const int64_t* offs, int n, int64_t P, uint32_t A, uint32_t B,
-              uint8_t* dst)
-{
-    if (R == 1) launch<T, 1>(vec, grid, st, src, offs, n, P, A, B, dst);
-    else if (R == 2) launch<T, 2>(vec, grid, st, src, offs, n, P, A, B, dst);
-    else launch<T, 3>(vec, grid, st, src, offs, n, P, A, B, dst);
-}
-
 }  // namespace
 
 extern "C" int demfi_payload_denoise(const uint8_t* src, int64_t src_bytes, const int64_t* offsets, const int64_t* offsets_dev, int n, int taps,
@@ -158,8 +130,7 @@ extern "C" int demfi_payload_denoise(const uint8_t* src, int64_t src_bytes, cons
     if (!src || !offsets || !offsets_dev || !dst) return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer", fn);
     if (n < 0 || n > NMAX) return demfi_set_error(DEMFI_ERR_ARG, "%s: n=%d outside 0..%d", fn, n, NMAX);
     if (taps != 3 && taps != 5 && taps != 7) return demfi_set_error(DEMFI_ERR_ARG, "%s: taps=%d (3, 5 or 7)", fn, taps);
-    if (sample_bytes != 1 && sample_bytes != 2)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: %d bytes per sample (1 or 2)", fn, sample_bytes);
+    if (int st = check_sample_bytes(fn, sample_bytes)) return st;
     const int peak = sample_bytes == 1 ? 255 : 65535;
     if (thr_a < 0 || thr_b < thr_a || thr_b > peak)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: thresholds A=%d, B=%d need 0 <= A <= B <= %d", fn, thr_a, thr_b, peak);
@@ -168,27 +139,17 @@ extern "C" int demfi_payload_denoise(const uint8_t* src, int64_t src_bytes, cons
     if (src_bytes < pb || dst_bytes < pb)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: buffers of %lld and %lld bytes for payloads of %lld", fn, (long long)src_bytes,
                                (long long)dst_bytes, (long long)pb);
-    if (sample_bytes == 2 && (((uintptr_t)src | (uintptr_t)dst) & 1))
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: 16-bit samples at an odd address", fn);
+    if (int st = check_even(fn, sample_bytes, (uintptr_t)src | (uintptr_t)dst)) return st;
     if ((uintptr_t)src < (uintptr_t)dst + (uintptr_t)dst_bytes && (uintptr_t)dst < (uintptr_t)src + (uintptr_t)src_bytes)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: the source and the destination buffer overlap", fn);
     const int R = taps / 2, width = taps + 1;
     uintptr_t low = 0;                                                   // the low bits of every address the kernel forms
+    // the sources: absent anywhere but at the centre, a whole payload inside src; then the destinations, inside dst
+    if (int st = walk_offsets(fn, offsets, n, width, taps, OFFS_BUT_CENTRE, R, src_bytes - pb, (uintptr_t)src, &low)) return st;
+    if (int st = walk_offsets(fn, offsets + taps, n, width, 1, OFFS_ALL, 0, dst_bytes - pb, (uintptr_t)dst, &low)) return st;
+    if (int st = check_even(fn, sample_bytes, low)) return st;
     for (int i = 0; i < n; ++i) {
-        const int64_t* o = offsets + (int64_t)i * width;
-        for (int k = 0; k < taps; ++k) {
-            if (o[k] == -1 && k != R) continue;
-            if (o[k] < 0 || o[k] > src_bytes - pb || (sample_bytes == 2 && (o[k] & 1)))
-                return demfi_set_error(DEMFI_ERR_ARG, "%s: frame %d, payload %d of %d: offset %lld (payloads of %lld bytes in a buffer of %lld%s)",
-                                       fn, i, k, taps, (long long)o[k], (long long)pb, (long long)src_bytes,
-                                       k == R ? "; the centre cannot be absent" : "");
-            low |= (uintptr_t)(src + o[k]);
-        }
-        const int64_t d = o[taps];
-        if (d < 0 || d > dst_bytes - pb || (sample_bytes == 2 && (d & 1)))
-            return demfi_set_error(DEMFI_ERR_ARG, "%s: frame %d: destination offset %lld (payloads of %lld bytes in a buffer of %lld)", fn, i,
-                                   (long long)d, (long long)pb, (long long)dst_bytes);
-        low |= (uintptr_t)(dst + d);
+        const int64_t d = offsets[(int64_t)i * width + taps];
         for (int j = 0; j < i; ++j) {
             const int64_t e = offsets[(int64_t)j * width + taps];
             if (e > d - pb && e < d + pb)
@@ -197,13 +158,15 @@ extern "C" int demfi_payload_denoise(const uint8_t* src, int64_t src_bytes, cons
     }
     if (n == 0) return DEMFI_OK;
     const bool vec = (low & 15) == 0;
-    const int per = 16 / sample_bytes;                                   // samples of a 16-byte word
-    const int64_t units = vec ? P / per + P % per : P;                   // what the kernel strides over: words and tail samples, or samples
-    const int64_t chunks = (units + NT - 1) / NT;
-    const dim3 grid((unsigned)min(chunks, (int64_t)4096), (unsigned)n);
-    const hipStream_t st = (hipStream_t)stream;
-    if (sample_bytes == 1) launch_r<uint8_t>(R, vec, grid, st, src, offsets_dev, n, P, (uint32_t)thr_a, (uint32_t)thr_b, dst);
-    else                   launch_r<uint16_t>(R, vec, grid, st, src, offsets_dev, n, P, (uint32_t)thr_a, (uint32_t)thr_b, dst);
+    const dim3 grid = rows_grid(stream_units(P, sample_bytes, vec), NT, n);
+    by_sample(sample_bytes, [&](auto t) {
+        by_int<1, 3>(R, [&](auto r) {
+            by_bool(vec, [&](auto v) {
+                hipLaunchKernelGGL((payload_denoise_kernel<TAG_TYPE(t), TAG_VALUE(r), TAG_VALUE(v)>), grid, dim3(NT), 0, (hipStream_t)stream, src,
+                                   offsets_dev, n, P, (uint32_t)thr_a, (uint32_t)thr_b, dst);
+            });
+        });
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }

@@ -28,13 +28,11 @@
 //   sample by sample (decided per item: ragged right edges and rows that start off 16 bytes).  The plane's gain table is in LDS.
 // No atomics, plain vector stores; payload offsets and r * dst_stride are 64-bit; every LDS index is formed from the thread's own tile
 // coordinates and every global one is checked against the plane, so no table or key content can take an access out of bounds.
-#include <type_traits>
-#include "common.h"
+#include "payload_kit.h"
 
 namespace {
 
 constexpr int NT = 256;                 // threads of a workgroup
-constexpr int MAXP = 3;                 // planes of a payload at most
 constexpr int TW = 64, TH = 16;         // columns and rows of a tile
 constexpr int MAXR = 2;
 constexpr int WS = TW + 16;             // row stride of the white cells (int16): a row is 160 bytes, every 8-cell segment 16-byte aligned
@@ -81,11 +79,6 @@ __device__ __forceinline__ int white_cell(uint32_t key, uint32_t X, uint32_t Y)
 template <int R> __device__ __forceinline__ constexpr int tap(int i)
 {
     return R == 0 ? 1 : R == 1 ? (i == 1 ? 2 : 1) : (i == 2 ? 6 : (i == 1 || i == 3) ? 4 : 1);
-}
-
-template <typename T> __device__ __forceinline__ uint32_t word_at(const u4_t& v, int i)
-{
-    return sizeof(T) == 1 ? (v[i >> 2] >> (8 * (i & 3))) & 0xffu : (v[i >> 1] >> (16 * (i & 1))) & 0xffffu;
 }
 
 // grid: x = tiles of a plane (the most any plane has), y = (payload, plane) pairs (strided)
@@ -149,7 +142,7 @@ __global__ __launch_bounds__(NT) void payload_grain_kernel(const uint8_t* __rest
             if (WIDE) {
                 const u4_t w = *gcp<u4_t>(sp);
 #pragma unroll
-                for (int k = 0; k < SPT; ++k) v[k] = word_at<T>(w, k);
+                for (int k = 0; k < SPT; ++k) v[k] = Samples<T>::at(w, k);
             } else {
 #pragma unroll
                 for (int k = 0; k < SPT; ++k) v[k] = k < nv ? (uint32_t)gcp<T>(sp)[k] : 0u;
@@ -186,10 +179,7 @@ __global__ __launch_bounds__(NT) void payload_grain_kernel(const uint8_t* __rest
             if (WIDE) {
                 u4_t w = {0u, 0u, 0u, 0u};
 #pragma unroll
-                for (int k = 0; k < SPT; ++k) {
-                    if (es == 1) w[k >> 2] |= o[k] << (8 * (k & 3));
-                    else w[k >> 1] |= o[k] << (16 * (k & 1));
-                }
+                for (int k = 0; k < SPT; ++k) Samples<T>::put(w, k, o[k]);
                 *gp<u4_t>(dp) = w;
             } else {
 #pragma unroll
@@ -202,8 +192,6 @@ __global__ __launch_bounds__(NT) void payload_grain_kernel(const uint8_t* __rest
     }
 }
 
-bool is_depth(int d) { return d == 8 || d == 10 || d == 12 || d == 14 || d == 16; }
-
 }  // namespace
 
 extern "C" int demfi_payload_grain(const uint8_t* base, const int64_t* offsets, const int64_t* offsets_dev, const uint32_t* keys,
@@ -215,23 +203,21 @@ extern "C" int demfi_payload_grain(const uint8_t* base, const int64_t* offsets, 
     if (!base || !offsets || !offsets_dev || !keys || !keys_dev || !planes || !gains || !gains_dev || !dst)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer", fn);
     if (n < 0) return demfi_set_error(DEMFI_ERR_ARG, "%s: n=%d", fn, n);
-    if (n_planes != 1 && n_planes != MAXP) return demfi_set_error(DEMFI_ERR_ARG, "%s: %d planes (1 or %d)", fn, n_planes, MAXP);
     if (!is_depth(depth) || sample_bytes != (depth > 8 ? 2 : 1))
         return demfi_set_error(DEMFI_ERR_ARG, "%s: %d bits in %d bytes per sample (8 bits in 1; 10, 12, 14 or 16 in 2)", fn, depth, sample_bytes);
-    if ((full_range | 1) != 1) return demfi_set_error(DEMFI_ERR_ARG, "%s: full_range=%d (0 or 1)", fn, full_range);
+    if (int st = check_flag(fn, "full_range", full_range)) return st;
     if (size < 0 || size > MAXR) return demfi_set_error(DEMFI_ERR_ARG, "%s: size=%d (0..%d)", fn, size, MAXR);
+    PlaneSet ps;
+    if (int st = parse_planes(fn, planes, n_planes, MAX_SIDE, (int64_t)MAX_SIDE * MAX_SIDE, true, &ps)) return st;
+    const int64_t P = ps.P;
     Planes pl = {};
     pl.n = n_planes, pl.sx = pl.sy = 1;
-    int64_t P = 0, most = 0;
+    int64_t most = 0;                                                        // tiles of the plane that has the most
     for (int p = 0; p < n_planes; ++p) {
-        const int rows = planes[2 * p], cols = planes[2 * p + 1];
-        if (rows < 1 || cols < 1 || rows > MAX_SIDE || cols > MAX_SIDE)
-            return demfi_set_error(DEMFI_ERR_ARG, "%s: plane %d is %d x %d (1..%d each)", fn, p, rows, cols, MAX_SIDE);
-        pl.rows[p] = rows, pl.cols[p] = cols, pl.start[p] = P;
-        pl.tiles_x[p] = (cols + TW - 1) / TW;
-        pl.tiles[p] = pl.tiles_x[p] * ((rows + TH - 1) / TH);
+        pl.rows[p] = ps.pl.rows[p], pl.cols[p] = ps.pl.cols[p], pl.start[p] = ps.pl.start[p];
+        pl.tiles_x[p] = (pl.cols[p] + TW - 1) / TW;
+        pl.tiles[p] = pl.tiles_x[p] * ((pl.rows[p] + TH - 1) / TH);
         most = max(most, (int64_t)pl.tiles[p]);
-        P += (int64_t)rows * cols;
     }
     if (n_planes == MAXP) {                                                  // the chroma planes: one shape, the luma's or half of it, rounded up
         const int h = pl.rows[0], w = pl.cols[0], ch = pl.rows[1], cw = pl.cols[1];
@@ -242,15 +228,10 @@ extern "C" int demfi_payload_grain(const uint8_t* base, const int64_t* offsets, 
     }
     if (P * sample_bytes >= ((int64_t)1 << 31))
         return demfi_set_error(DEMFI_ERR_ARG, "%s: a payload of %lld bytes (below 2^31)", fn, (long long)(P * sample_bytes));
-    if (dst_stride < P * sample_bytes)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: dst_stride=%lld below the %lld bytes of a payload", fn, (long long)dst_stride,
-                               (long long)(P * sample_bytes));
+    if (int st = check_dst_stride(fn, dst_stride, P * sample_bytes)) return st;
     uintptr_t odd = (uintptr_t)base | (uintptr_t)dst | (uintptr_t)dst_stride;
-    for (int i = 0; i < n; ++i) {
-        if (offsets[i] < 0) return demfi_set_error(DEMFI_ERR_ARG, "%s: row %d offset is %lld", fn, i, (long long)offsets[i]);
-        odd |= (uintptr_t)offsets[i];
-    }
-    if (sample_bytes == 2 && (odd & 1)) return demfi_set_error(DEMFI_ERR_ARG, "%s: 16-bit samples at an odd address, offset or stride", fn);
+    if (int st = walk_offsets(fn, offsets, n, 1, 1, OFFS_ALL, 0, NO_LIMIT, 0, &odd)) return st;
+    if (int st = check_even(fn, sample_bytes, odd)) return st;
     if (((uintptr_t)gains_dev & 3) || ((uintptr_t)keys_dev & 3))
         return demfi_set_error(DEMFI_ERR_ARG, "%s: gains_dev or keys_dev is not on a 4-byte boundary", fn);
     // |F| <= 510 * (sum of the taps)^2: the 32-bit product holds for gains up to this
@@ -266,14 +247,12 @@ extern "C" int demfi_payload_grain(const uint8_t* base, const int64_t* offsets, 
         rule.hi[c] = full_range ? (1 << depth) - 1 : (c ? 240 : 235) << rule.shift;
     }
     const dim3 grid((unsigned)most, (unsigned)min((int64_t)n * n_planes, (int64_t)4096));
-    const hipStream_t st = (hipStream_t)stream;
-#define GRAIN_LAUNCH(T, R) \
-    hipLaunchKernelGGL((payload_grain_kernel<T, R>), grid, dim3(NT), 0, st, base, offsets_dev, keys_dev, n, pl, rule, gains_dev, dst, dst_stride)
-#define GRAIN_SIZES(T) \
-    do { if (size == 0) GRAIN_LAUNCH(T, 0); else if (size == 1) GRAIN_LAUNCH(T, 1); else GRAIN_LAUNCH(T, 2); } while (0)
-    if (sample_bytes == 1) GRAIN_SIZES(uint8_t); else GRAIN_SIZES(uint16_t);
-#undef GRAIN_SIZES
-#undef GRAIN_LAUNCH
+    by_sample(sample_bytes, [&](auto t) {
+        by_int<0, MAXR>(size, [&](auto r) {
+            hipLaunchKernelGGL((payload_grain_kernel<TAG_TYPE(t), TAG_VALUE(r)>), grid, dim3(NT), 0, (hipStream_t)stream, base, offsets_dev, keys_dev,
+                               n, pl, rule, gains_dev, dst, dst_stride);
+        });
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }

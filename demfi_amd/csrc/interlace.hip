@@ -24,32 +24,13 @@
 // 1080p 4:2:0 meet it on all three planes.  Otherwise (mono, odd widths, 1918-wide frames) the whole launch goes sample by sample: an
 // item is one sample, consecutive lanes take consecutive samples of a row, and a thread reads the owner's 1, 3 or 5 samples itself
 // (the rows repeat in the caches); the arithmetic is the same.
-#include "common.h"
+#include "payload_kit.h"
 
 namespace {
 
 constexpr int NT = 256;                 // threads of a workgroup
-constexpr int MAXP = 3;                 // planes of a payload at most
 constexpr int STRIP = 8;                // output rows a thread of the wide path walks down (even: a wave's rows share their parity)
 enum { LP_OFF = 0, LP_LINEAR = 1, LP_COMPLEX = 2 };
-
-struct Planes {
-    int n;
-    int rows[MAXP], cols[MAXP];
-    int64_t start[MAXP];                // first sample of the plane in the payload
-};
-
-template <typename T> struct Samples;   // the 16 / sizeof(T) samples of a 16-byte word
-template <> struct Samples<uint8_t> {
-    static constexpr int N = 16;
-    static __device__ __forceinline__ int at(const u4_t& v, int i) { return (int)((v[i >> 2] >> (8 * (i & 3))) & 0xffu); }
-    static __device__ __forceinline__ void put(u4_t& v, int i, uint32_t x) { v[i >> 2] |= x << (8 * (i & 3)); }
-};
-template <> struct Samples<uint16_t> {
-    static constexpr int N = 8;
-    static __device__ __forceinline__ int at(const u4_t& v, int i) { return (int)((v[i >> 1] >> (16 * (i & 1))) & 0xffffu); }
-    static __device__ __forceinline__ void put(u4_t& v, int i, uint32_t x) { v[i >> 1] |= x << (16 * (i & 1)); }
-};
 
 // the filter of one sample: a2, a, c, b, b2 = the owner's rows y-2 .. y+2 (clamped) at the sample's column
 template <int MODE> __device__ __forceinline__ uint32_t lowpass(int a2, int a, int c, int b, int b2, int peak)
@@ -74,12 +55,10 @@ template <typename T, int MODE, int HALO> __device__ __forceinline__ u4_t filter
     return o;
 }
 
-__device__ __forceinline__ int clamp_row(int y, int rows) { return min(max(y, 0), rows - 1); }
-
 // grid: x = chunks of NT items of a plane (strided), y = (payload, plane) pairs (strided).  Wide path: item = strip * words + word.
 template <typename T, int MODE>
 __global__ __launch_bounds__(NT) void payload_weave_wide_kernel(const uint8_t* __restrict__ base, const int64_t* __restrict__ offs, int n,
-                                                               Planes pl, int peak, int q0, uint8_t* __restrict__ dst,
+                                                               PlaneList pl, int peak, int q0, uint8_t* __restrict__ dst,
                                                                int64_t dst_stride)
 {
     constexpr int HALO = MODE == LP_OFF ? 0 : MODE == LP_LINEAR ? 1 : 2;
@@ -130,7 +109,7 @@ __global__ __launch_bounds__(NT) void payload_weave_wide_kernel(const uint8_t* _
 // the sample-by-sample path: item = one sample of the plane, y * cols + x
 template <typename T, int MODE>
 __global__ __launch_bounds__(NT) void payload_weave_sample_kernel(const uint8_t* __restrict__ base, const int64_t* __restrict__ offs, int n,
-                                                                 Planes pl, int peak, int q0, uint8_t* __restrict__ dst, int64_t dst_stride)
+                                                                 PlaneList pl, int peak, int q0, uint8_t* __restrict__ dst, int64_t dst_stride)
 {
     constexpr int es = (int)sizeof(T);
     for (int rp = blockIdx.y; rp < n * pl.n; rp += gridDim.y) {
@@ -168,65 +147,33 @@ extern "C" int demfi_payload_weave(const uint8_t* base, const int64_t* offsets, 
     const char* fn = "demfi_payload_weave";
     if (n <= 0) return DEMFI_OK;
     if (!base || !offsets || !offsets_dev || !planes || !dst) return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer", fn);
-    if (n_planes < 1 || n_planes > MAXP) return demfi_set_error(DEMFI_ERR_ARG, "%s: %d planes (1..%d)", fn, n_planes, MAXP);
-    if (sample_bytes != 1 && sample_bytes != 2)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: %d bytes per sample (1 or 2)", fn, sample_bytes);
-    if (peak < 1 || peak > 65535 || (sample_bytes == 1 && peak > 255))
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: peak=%d outside 1..%d", fn, peak, sample_bytes == 1 ? 255 : 65535);
-    if (q0 != 0 && q0 != 1) return demfi_set_error(DEMFI_ERR_ARG, "%s: q0=%d (0 or 1)", fn, q0);
+    if (int st = check_sample_bytes(fn, sample_bytes)) return st;
+    if (int st = check_peak(fn, peak, sample_bytes)) return st;
+    if (int st = check_flag(fn, "q0", q0)) return st;
     if (lowpass < LP_OFF || lowpass > LP_COMPLEX) return demfi_set_error(DEMFI_ERR_ARG, "%s: low-pass mode %d (0, 1 or 2)", fn, lowpass);
-    Planes pl = {};
-    pl.n = n_planes;
-    int64_t P = 0;
+    PlaneSet ps;
+    if (int st = parse_planes(fn, planes, n_planes, 32768, (int64_t)32768 * 32768, false, &ps)) return st;
+    const PlaneList& pl = ps.pl;
+    if (int st = check_dst_stride(fn, dst_stride, ps.P * sample_bytes)) return st;
     uintptr_t low = (uintptr_t)base | (uintptr_t)dst | (uintptr_t)dst_stride;    // the low bits of every row start the kernel forms
-    for (int p = 0; p < n_planes; ++p) {
-        const int rows = planes[2 * p], cols = planes[2 * p + 1];
-        if (rows < 1 || cols < 1 || rows > 32768 || cols > 32768)
-            return demfi_set_error(DEMFI_ERR_ARG, "%s: plane %d is %d x %d (1..32768 each)", fn, p, rows, cols);
-        pl.rows[p] = rows, pl.cols[p] = cols, pl.start[p] = P;
-        low |= (uintptr_t)(P * sample_bytes) | (uintptr_t)((int64_t)cols * sample_bytes);
-        P += (int64_t)rows * cols;
-    }
-    if (dst_stride < P * sample_bytes)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: dst_stride=%lld below the %lld bytes of a payload", fn, (long long)dst_stride,
-                               (long long)(P * sample_bytes));
-    uintptr_t odd = (uintptr_t)base | (uintptr_t)dst | (uintptr_t)dst_stride;
-    for (int64_t i = 0; i < 2 * (int64_t)n; ++i) {
-        if (offsets[i] < 0) return demfi_set_error(DEMFI_ERR_ARG, "%s: row %lld offset %d is %lld", fn, (long long)(i / 2), (int)(i & 1),
-                                                   (long long)offsets[i]);
-        low |= (uintptr_t)offsets[i];
-        odd |= (uintptr_t)offsets[i];
-    }
-    if (sample_bytes == 2 && (odd & 1)) return demfi_set_error(DEMFI_ERR_ARG, "%s: 16-bit samples at an odd address or stride", fn);
+    if (int st = walk_offsets(fn, offsets, n, 2, 2, OFFS_ALL, 0, NO_LIMIT, 0, &low)) return st;
+    if (int st = check_even(fn, sample_bytes, low)) return st;
+    for (int p = 0; p < n_planes; ++p) low |= (uintptr_t)(pl.start[p] * sample_bytes) | (uintptr_t)((int64_t)pl.cols[p] * sample_bytes);
     const bool wide = (low & 15) == 0;
-    const int64_t pairs = (int64_t)n * n_planes;
-    const hipStream_t st = (hipStream_t)stream;
-    if (wide) {
-        int64_t most = 0;
-        for (int p = 0; p < n_planes; ++p)
-            most = max(most, ((int64_t)pl.cols[p] * sample_bytes / 16) * ((pl.rows[p] + STRIP - 1) / STRIP));
-        const dim3 grid((unsigned)min((most + NT - 1) / NT, (int64_t)4096), (unsigned)min(pairs, (int64_t)4096));
-#define WEAVE_WIDE(T, M) \
-    hipLaunchKernelGGL((payload_weave_wide_kernel<T, M>), grid, dim3(NT), 0, st, base, offsets_dev, n, pl, peak, q0, dst, dst_stride)
-        if (sample_bytes == 1) {
-            if (lowpass == LP_OFF) WEAVE_WIDE(uint8_t, LP_OFF); else if (lowpass == LP_LINEAR) WEAVE_WIDE(uint8_t, LP_LINEAR); else WEAVE_WIDE(uint8_t, LP_COMPLEX);
-        } else {
-            if (lowpass == LP_OFF) WEAVE_WIDE(uint16_t, LP_OFF); else if (lowpass == LP_LINEAR) WEAVE_WIDE(uint16_t, LP_LINEAR); else WEAVE_WIDE(uint16_t, LP_COMPLEX);
-        }
-#undef WEAVE_WIDE
-    } else {
-        int64_t most = 0;
-        for (int p = 0; p < n_planes; ++p) most = max(most, (int64_t)pl.rows[p] * pl.cols[p]);
-        const dim3 grid((unsigned)min((most + NT - 1) / NT, (int64_t)4096), (unsigned)min(pairs, (int64_t)4096));
-#define WEAVE_SAMPLE(T, M) \
-    hipLaunchKernelGGL((payload_weave_sample_kernel<T, M>), grid, dim3(NT), 0, st, base, offsets_dev, n, pl, peak, q0, dst, dst_stride)
-        if (sample_bytes == 1) {
-            if (lowpass == LP_OFF) WEAVE_SAMPLE(uint8_t, LP_OFF); else if (lowpass == LP_LINEAR) WEAVE_SAMPLE(uint8_t, LP_LINEAR); else WEAVE_SAMPLE(uint8_t, LP_COMPLEX);
-        } else {
-            if (lowpass == LP_OFF) WEAVE_SAMPLE(uint16_t, LP_OFF); else if (lowpass == LP_LINEAR) WEAVE_SAMPLE(uint16_t, LP_LINEAR); else WEAVE_SAMPLE(uint16_t, LP_COMPLEX);
-        }
-#undef WEAVE_SAMPLE
-    }
+    int64_t most = 0;                                                    // items of the largest plane: 16-byte columns x strips, or samples
+    for (int p = 0; p < n_planes; ++p)
+        most = max(most, wide ? ((int64_t)pl.cols[p] * sample_bytes / 16) * ((pl.rows[p] + STRIP - 1) / STRIP) : (int64_t)pl.rows[p] * pl.cols[p]);
+    const dim3 grid = planes_grid(most, NT, n, n_planes);
+    by_sample(sample_bytes, [&](auto t) {
+        by_int<LP_OFF, LP_COMPLEX>(lowpass, [&](auto m) {
+            if (wide)
+                hipLaunchKernelGGL((payload_weave_wide_kernel<TAG_TYPE(t), TAG_VALUE(m)>), grid, dim3(NT), 0, (hipStream_t)stream, base, offsets_dev,
+                                   n, pl, peak, q0, dst, dst_stride);
+            else
+                hipLaunchKernelGGL((payload_weave_sample_kernel<TAG_TYPE(t), TAG_VALUE(m)>), grid, dim3(NT), 0, (hipStream_t)stream, base,
+                                   offsets_dev, n, pl, peak, q0, dst, dst_stride);
+        });
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }

@@ -13,7 +13,7 @@
 // of a block row, so a wave reads contiguous runs of 512 bytes (1 KiB); a row starts at any alignment and the loads are unaligned
 // ones, as in dedup.hip.  A strip cut by the right edge goes sample by sample.  The two lanes of a block add their counts, then
 // the wave reduces: one atomicMax and one atomicAdd per wave and candidate (integer results are exact in any order).
-#include "common.h"
+#include "payload_kit.h"
 
 namespace {
 
@@ -24,37 +24,6 @@ constexpr int SAD_NT = 256;
 constexpr int SAD_WGS = 128;
 constexpr int MAX_THRESH = 1 << 20;     // 6 T and every sum of five samples stay far inside 32 bits
 
-typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
-typedef u2_t u2_unaligned __attribute__((aligned(1)));
-typedef u4_t u4_unaligned2 __attribute__((aligned(2)));
-
-template <typename T> struct Strip;     // 8 consecutive samples as one packed word
-template <> struct Strip<uint8_t> {
-    typedef u2_t word;
-    static __device__ __forceinline__ word load(const uint8_t* p) { return *(const DEMFI_GLOBAL u2_unaligned*)p; }
-    static __device__ __forceinline__ int at(const word& v, int i) { return (int)(((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 0xffu); }
-    static __device__ __forceinline__ uint32_t sad(const word& a, const word& b, uint32_t acc)
-    {
-        return __builtin_amdgcn_sad_u8(a.y, b.y, __builtin_amdgcn_sad_u8(a.x, b.x, acc));
-    }
-};
-template <> struct Strip<uint16_t> {
-    typedef u4_t word;
-    static __device__ __forceinline__ word load(const uint16_t* p) { return *(const DEMFI_GLOBAL u4_unaligned2*)p; }
-    static __device__ __forceinline__ int at(const word& v, int i)
-    {
-        const uint32_t d = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
-        return (int)((d >> (16 * (i & 1))) & 0xffffu);
-    }
-    static __device__ __forceinline__ uint32_t sad(const word& a, const word& b, uint32_t acc)
-    {
-        acc = __builtin_amdgcn_sad_u16(a.x, b.x, acc);
-        acc = __builtin_amdgcn_sad_u16(a.y, b.y, acc);
-        acc = __builtin_amdgcn_sad_u16(a.z, b.z, acc);
-        return __builtin_amdgcn_sad_u16(a.w, b.w, acc);
-    }
-};
-
 __device__ __forceinline__ bool is_combed(int c, int up, int dn, int up2, int dn2, int t)
 {
     const int d1 = c - up, d2 = c - dn;
@@ -64,9 +33,9 @@ __device__ __forceinline__ bool is_combed(int c, int up, int dn, int up2, int dn
 
 // combed samples among the 8 of a row: centre c, the rows next to it, the rows two away
 template <typename T>
-__device__ __forceinline__ int row_combed(const typename Strip<T>::word& c, const typename Strip<T>::word& up,
-                                          const typename Strip<T>::word& dn, const typename Strip<T>::word& up2,
-                                          const typename Strip<T>::word& dn2, int t)
+__device__ __forceinline__ int row_combed(const typename Strip<T>::V& c, const typename Strip<T>::V& up,
+                                          const typename Strip<T>::V& dn, const typename Strip<T>::V& up2,
+                                          const typename Strip<T>::V& dn2, int t)
 {
     int k = 0;
 #pragma unroll
@@ -76,9 +45,9 @@ __device__ __forceinline__ int row_combed(const typename Strip<T>::word& c, cons
 }
 
 // row r of a plane's strip, or nothing for a row outside the plane (such a row is never used)
-template <typename T> __device__ __forceinline__ typename Strip<T>::word strip_row(const T* plane, int r, int h, int w, int x0)
+template <typename T> __device__ __forceinline__ typename Strip<T>::V strip_row(const T* plane, int r, int h, int w, int x0)
 {
-    typename Strip<T>::word z = {};
+    typename Strip<T>::V z = {};
     return r >= 0 && r < h ? Strip<T>::load(plane + (int64_t)r * w + x0) : z;
 }
 
@@ -88,7 +57,7 @@ __global__ __launch_bounds__(NT) void luma_comb_counts_kernel(const uint8_t* __r
                                                              const int64_t* __restrict__ bot_offs, int n, int h, int w, int t,
                                                              uint32_t* __restrict__ out)
 {
-    typedef typename Strip<T>::word W;
+    typedef typename Strip<T>::V W;
     const int nbx = (w + BS - 1) / BS, nby = (h + BS - 1) / BS, nsx = 2 * nbx;
     const int si = blockIdx.x * NT + threadIdx.x;
     const bool live = si < nsx * nby;
@@ -211,12 +180,9 @@ __global__ __launch_bounds__(SAD_NT) void luma_woven_sad_kernel(const uint8_t* _
 
 int check_plane(const char* fn, const void* base, int h, int w, int sample_bytes)
 {
-    if (h < 2 || w < 2 || h > 16384 || w > 16384)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: frame size %dx%d outside 2..16384", fn, h, w);
-    if (sample_bytes != 1 && sample_bytes != 2)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: %d bytes per sample (1 or 2)", fn, sample_bytes);
-    if (sample_bytes == 2 && ((uintptr_t)base & 1))
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: 16-bit samples at an odd address", fn);
+    if (int st = check_frame_size(fn, h, w)) return st;
+    if (int st = check_sample_bytes(fn, sample_bytes)) return st;
+    if (int st = check_even(fn, sample_bytes, (uintptr_t)base)) return st;
     return DEMFI_OK;
 }
 
@@ -236,12 +202,10 @@ extern "C" int demfi_luma_comb_counts(const uint8_t* base, const int64_t* top_of
     DEMFI_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n * 6 * sizeof(uint32_t), (hipStream_t)stream));
     const int strips = 2 * ((w + BS - 1) / BS) * ((h + BS - 1) / BS);
     const dim3 grid((unsigned)((strips + NT - 1) / NT), (unsigned)min(n, 65535));
-    if (sample_bytes == 1)
-        hipLaunchKernelGGL(luma_comb_counts_kernel<uint8_t>, grid, dim3(NT), 0, (hipStream_t)stream, base, top_offsets, bot_offsets, n, h, w,
+    by_sample(sample_bytes, [&](auto t) {
+        hipLaunchKernelGGL(luma_comb_counts_kernel<TAG_TYPE(t)>, grid, dim3(NT), 0, (hipStream_t)stream, base, top_offsets, bot_offsets, n, h, w,
                            thresh_s, out);
-    else
-        hipLaunchKernelGGL(luma_comb_counts_kernel<uint16_t>, grid, dim3(NT), 0, (hipStream_t)stream, base, top_offsets, bot_offsets, n, h, w,
-                           thresh_s, out);
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }
@@ -258,12 +222,10 @@ extern "C" int demfi_luma_woven_sad(const uint8_t* base, const int64_t* offsets,
     DEMFI_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n * sizeof(uint64_t), (hipStream_t)stream));
     const int pieces = h * ((w + SW - 1) / SW);
     const dim3 grid((unsigned)min((pieces + SAD_NT - 1) / SAD_NT, SAD_WGS), (unsigned)min(n, 65535));
-    if (sample_bytes == 1)
-        hipLaunchKernelGGL(luma_woven_sad_kernel<uint8_t>, grid, dim3(SAD_NT), 0, (hipStream_t)stream, base, offsets, n, h, w,
+    by_sample(sample_bytes, [&](auto t) {
+        hipLaunchKernelGGL(luma_woven_sad_kernel<TAG_TYPE(t)>, grid, dim3(SAD_NT), 0, (hipStream_t)stream, base, offsets, n, h, w,
                            (unsigned long long*)out);
-    else
-        hipLaunchKernelGGL(luma_woven_sad_kernel<uint16_t>, grid, dim3(SAD_NT), 0, (hipStream_t)stream, base, offsets, n, h, w,
-                           (unsigned long long*)out);
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }

@@ -21,12 +21,11 @@
 //   one 4- or 8-byte word when the destination address allows, else (and at the plane's right edge) sample by sample.
 // No atomics; every LDS and source index is clamped where it is formed, so no table content can take an access out of bounds.  Payload
 // offsets and r * dst_stride are 64-bit; offsets inside a payload fit 32 bits (the entry point refuses payloads of 2^31 bytes).
-#include "common.h"
+#include "payload_kit.h"
 
 namespace {
 
 constexpr int NT = 256;                 // threads of a workgroup
-constexpr int MAXP = 3;                 // planes of a payload at most
 constexpr int TW = 64, TH = 16;         // output columns and rows of a tile
 constexpr int MAXR = 96;                // source rows a tile holds in LDS
 constexpr int MAXT = 32;                // taps at most
@@ -46,9 +45,6 @@ struct Planes {
 };
 
 typedef int i4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // the vertical sum with its rounding term -> the sample
 template <typename A> __device__ __forceinline__ uint32_t clip_sample(A acc, int peak)
@@ -56,10 +52,6 @@ template <typename A> __device__ __forceinline__ uint32_t clip_sample(A acc, int
     const A v = acc >> (QBITS + FRAC);
     return (uint32_t)(v < 0 ? (A)0 : v > (A)peak ? (A)peak : v);
 }
-
-template <typename T> struct Acc;       // the vertical accumulator of a sample type
-template <> struct Acc<uint8_t> { typedef int type; };
-template <> struct Acc<uint16_t> { typedef int64_t type; };
 
 // grid: x = tiles of a plane (the most any plane has), y = (payload, plane) pairs (strided)
 template <typename T>
@@ -166,22 +158,20 @@ extern "C" int demfi_payload_scale(const uint8_t* base, const int64_t* offsets, 
     if (!base || !offsets || !offsets_dev || !planes_in || !planes_out || !tables_dev || !table_desc || !dst)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer", fn);
     if (n < 0) return demfi_set_error(DEMFI_ERR_ARG, "%s: n=%d", fn, n);
-    if (n_planes < 1 || n_planes > MAXP) return demfi_set_error(DEMFI_ERR_ARG, "%s: %d planes (1..%d)", fn, n_planes, MAXP);
-    if (sample_bytes != 1 && sample_bytes != 2)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: %d bytes per sample (1 or 2)", fn, sample_bytes);
-    if (peak < 1 || peak > 65535 || (sample_bytes == 1 && peak > 255))
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: peak=%d outside 1..%d", fn, peak, sample_bytes == 1 ? 255 : 65535);
+    if (int st = check_sample_bytes(fn, sample_bytes)) return st;
+    if (int st = check_peak(fn, peak, sample_bytes)) return st;
+    PlaneSet in, out;
+    if (int st = parse_planes(fn, planes_in, n_planes, 32768, (int64_t)32768 * 32768, false, &in)) return st;
+    if (int st = parse_planes(fn, planes_out, n_planes, 32768, (int64_t)32768 * 32768, false, &out)) return st;
+    const int64_t Pin = in.P, Pout = out.P;
     Planes pl = {};
     pl.n = n_planes;
     const int64_t blob = table_desc[6 * n_planes];                          // bytes of tables_dev
-    int64_t Pin = 0, Pout = 0, most = 0;
+    int64_t most = 0;                                                        // tiles of the plane that has the most
     for (int p = 0; p < n_planes; ++p) {
         Plane& P = pl.p[p];
-        P.rows_in = planes_in[2 * p], P.cols_in = planes_in[2 * p + 1], P.rows_out = planes_out[2 * p], P.cols_out = planes_out[2 * p + 1];
-        for (int v : {P.rows_in, P.cols_in, P.rows_out, P.cols_out})
-            if (v < 1 || v > 32768)
-                return demfi_set_error(DEMFI_ERR_ARG, "%s: plane %d is %d x %d -> %d x %d (1..32768 each)", fn, p, P.rows_in, P.cols_in,
-                                       P.rows_out, P.cols_out);
+        P.rows_in = in.pl.rows[p], P.cols_in = in.pl.cols[p], P.rows_out = out.pl.rows[p], P.cols_out = out.pl.cols[p];
+        P.start_in = in.pl.start[p], P.start_out = out.pl.start[p];
         const int32_t* d = table_desc + 6 * p;
         P.fx = d[0], P.cx = d[1], P.tx = d[2], P.fy = d[3], P.cy = d[4], P.ty = d[5];
         if (P.tx < 1 || P.tx > MAXT || P.ty < 1 || P.ty > MAXT)
@@ -199,30 +189,21 @@ extern "C" int demfi_payload_scale(const uint8_t* base, const int64_t* offsets, 
         P.tiles_x = (P.cols_out + TW - 1) / TW;
         P.tiles = P.tiles_x * ((P.rows_out + th - 1) / th);
         most = max(most, (int64_t)P.tiles);
-        P.start_in = Pin, P.start_out = Pout;
-        Pin += (int64_t)P.rows_in * P.cols_in;
-        Pout += (int64_t)P.rows_out * P.cols_out;
     }
     if (Pin * sample_bytes >= ((int64_t)1 << 31) || Pout * sample_bytes >= ((int64_t)1 << 31))
         return demfi_set_error(DEMFI_ERR_ARG, "%s: payloads of %lld -> %lld bytes (below 2^31 each)", fn, (long long)(Pin * sample_bytes),
                                (long long)(Pout * sample_bytes));
-    if (dst_stride < Pout * sample_bytes)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: dst_stride=%lld below the %lld bytes of a payload", fn, (long long)dst_stride,
-                               (long long)(Pout * sample_bytes));
+    if (int st = check_dst_stride(fn, dst_stride, Pout * sample_bytes)) return st;
     uintptr_t odd = (uintptr_t)base | (uintptr_t)dst | (uintptr_t)dst_stride;
-    for (int i = 0; i < n; ++i) {
-        if (offsets[i] < 0) return demfi_set_error(DEMFI_ERR_ARG, "%s: row %d offset is %lld", fn, i, (long long)offsets[i]);
-        odd |= (uintptr_t)offsets[i];
-    }
-    if (sample_bytes == 2 && (odd & 1)) return demfi_set_error(DEMFI_ERR_ARG, "%s: 16-bit samples at an odd address, offset or stride", fn);
+    if (int st = walk_offsets(fn, offsets, n, 1, 1, OFFS_ALL, 0, NO_LIMIT, 0, &odd)) return st;
+    if (int st = check_even(fn, sample_bytes, odd)) return st;
     if (((uintptr_t)tables_dev & 3)) return demfi_set_error(DEMFI_ERR_ARG, "%s: tables_dev is not on a 4-byte boundary", fn);
     if (n == 0) return DEMFI_OK;
     const dim3 grid((unsigned)most, (unsigned)min((int64_t)n * n_planes, (int64_t)4096));
-    const hipStream_t st = (hipStream_t)stream;
-    if (sample_bytes == 1)
-        hipLaunchKernelGGL(payload_scale_kernel<uint8_t>, grid, dim3(NT), 0, st, base, offsets_dev, n, pl, peak, tables_dev, dst, dst_stride);
-    else
-        hipLaunchKernelGGL(payload_scale_kernel<uint16_t>, grid, dim3(NT), 0, st, base, offsets_dev, n, pl, peak, tables_dev, dst, dst_stride);
+    by_sample(sample_bytes, [&](auto t) {
+        hipLaunchKernelGGL(payload_scale_kernel<TAG_TYPE(t)>, grid, dim3(NT), 0, (hipStream_t)stream, base, offsets_dev, n, pl, peak, tables_dev, dst,
+                           dst_stride);
+    });
     DEMFI_HIP_CHECK(hipGetLastError());
     return DEMFI_OK;
 }

@@ -11,14 +11,12 @@
 //
 // The rectangles come from device memory and the kernels cannot trust them: a tile whose rectangle leaves the frame (or whose
 // kept rectangle leaves its tile) is skipped as a whole, so no launch reads or writes outside the buffers it was sized for.
-#include "common.h"
+#include "payload_kit.h"
 
 namespace {
 
 constexpr int NT = 256;
 constexpr int RECT = 6;               // int32 per tile: source y0, x0; kept y0, x0, y1, x1 (frame coordinates)
-
-typedef u4_t u4_unaligned __attribute__((aligned(1)));
 
 // piece c of the n-byte row src -> dst
 __device__ __forceinline__ void copy_piece(uint8_t* dst, const uint8_t* src, int n, int c)
@@ -28,7 +26,7 @@ __device__ __forceinline__ void copy_piece(uint8_t* dst, const uint8_t* src, int
     const int cnt = c == 0 ? head : min(16, n - lo);
     if (cnt <= 0) return;
     if (cnt == 16) {
-        *gp<u4_t>(dst + lo) = *(const DEMFI_GLOBAL u4_unaligned*)(src + lo);
+        *gp<u4_t>(dst + lo) = *(const DEMFI_GLOBAL u4_a1*)(src + lo);
         return;
     }
 #pragma unroll
@@ -85,8 +83,7 @@ int check_tiles(const char* fn, const void* a, const void* b, int n, int h, int 
 {
     if (!a || !b || !rects || !rects_dev || n < 0)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer or n=%d", fn, n);
-    if (h < 2 || w < 2 || h > 16384 || w > 16384)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: frame size %dx%d outside 2..16384", fn, h, w);
+    if (int st = check_frame_size(fn, h, w)) return st;
     if (th < 2 || tw < 2 || th > h || tw > w)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: tile size %dx%d outside 2..%dx%d", fn, th, tw, h, w);
     if (n_tiles < 1 || n_tiles > 65535)

@@ -244,16 +244,13 @@ __global__ __launch_bounds__(NT) void bgr_to_yuv420_gather_kernel(const uint8_t*
 }
 
 // ---- the SAD of scene-cut detection, over either sample type ------------------------------------------------------------------
-typedef u4_t u4_align1 __attribute__((aligned(1)));
-typedef u4_t u4_align2 __attribute__((aligned(2)));
-
 __device__ __forceinline__ uint32_t sad_one(uint8_t x, uint8_t y, uint32_t acc) { return __builtin_amdgcn_sad_u8(x, y, acc); }
 __device__ __forceinline__ uint32_t sad_one(uint16_t x, uint16_t y, uint32_t acc) { return __builtin_amdgcn_sad_u16(x, y, acc); }
 
 // 16 bytes at a (16-byte aligned) against 16 at b (sample-aligned, which global memory serves): four v_sad_u8 / v_sad_u16
 __device__ __forceinline__ uint32_t sad_vec(const uint8_t* a, const uint8_t* b, uint32_t acc)
 {
-    const u4_t x = *(const DEMFI_GLOBAL u4_t*)a, y = *(const DEMFI_GLOBAL u4_align1*)b;
+    const u4_t x = *(const DEMFI_GLOBAL u4_t*)a, y = *(const DEMFI_GLOBAL u4_a1*)b;
     acc = __builtin_amdgcn_sad_u8(x.x, y.x, acc);
     acc = __builtin_amdgcn_sad_u8(x.y, y.y, acc);
     acc = __builtin_amdgcn_sad_u8(x.z, y.z, acc);
@@ -262,7 +259,7 @@ __device__ __forceinline__ uint32_t sad_vec(const uint8_t* a, const uint8_t* b, 
 
 __device__ __forceinline__ uint32_t sad_vec(const uint16_t* a, const uint16_t* b, uint32_t acc)
 {
-    const u4_t x = *(const DEMFI_GLOBAL u4_t*)a, y = *(const DEMFI_GLOBAL u4_align2*)b;
+    const u4_t x = *(const DEMFI_GLOBAL u4_t*)a, y = *(const DEMFI_GLOBAL u4_a2*)b;
     acc = __builtin_amdgcn_sad_u16(x.x, y.x, acc);
     acc = __builtin_amdgcn_sad_u16(x.y, y.y, acc);
     acc = __builtin_amdgcn_sad_u16(x.z, y.z, acc);

@@ -1,5 +1,6 @@
-// What the units of the Y4M stream edge share (yuv.hip, yuv_family.hip): the matrix coefficients, the argument check and launch
-// grid of the host side, and the device-side access to samples of either type.
+// What the colour conversions of the Y4M stream edge share (yuv.hip, yuv_family.hip, deint.hip, colour.hip): the matrix coefficients,
+// the argument check and launch grid of the host side, and the device-side access to samples of either type.  The packed-word typedefs,
+// Acc<T> and the small argument checks are payload_kit.h's, which every payload stage shares.
 //
 // The definition of every conversion is numpy code in demfi_amd/y4m.py; the kernels match it bit for bit.  Samples and BGR values at
 // bit depth d hold 0 .. peak = 2^d - 1, in uint8 (d = 8) or uint16 (d = 8 .. 16).  With s = 2^(d-8): limited range is Y 16s .. 235s
@@ -8,7 +9,7 @@
 // -ffp-contract=off); chroma enters the matrix in 1/16 units; ONE round-half-up, clamp to [0, peak].  d = 8 gives the Q16
 // coefficients of the 8-bit kernels exactly (255 / (219 * 1) and 219 * 1 / 255 are the same float64 values as 255 / 219, 219 / 255).
 #pragma once
-#include "common.h"
+#include "payload_kit.h"
 #include <math.h>
 
 namespace {
@@ -94,8 +95,7 @@ inline int check_args(const char* fn, const void* src, const void* dst, int n, i
         return demfi_set_error(DEMFI_ERR_ARG, "%s: NULL buffer or n=%d", fn, n);
     if (sample_bytes == 2 && (((uintptr_t)src & 1) || ((uintptr_t)dst & 1)))
         return demfi_set_error(DEMFI_ERR_ARG, "%s: buffers of 16-bit samples must be 2-byte aligned", fn);
-    if (h < 2 || w < 2 || h > 16384 || w > 16384)
-        return demfi_set_error(DEMFI_ERR_ARG, "%s: frame size %dx%d outside 2..16384", fn, h, w);
+    if (int st = check_frame_size(fn, h, w)) return st;
     if (depth < 8 || depth > 16)
         return demfi_set_error(DEMFI_ERR_ARG, "%s: bit depth %d outside 8..16", fn, depth);
     if ((matrix != DEMFI_BT601 && matrix != DEMFI_BT709) || (full_range != 0 && full_range != 1))
@@ -111,10 +111,7 @@ inline dim3 grid_for(int n, int rows, int w)
 }
 
 // ---- the two sample types -------------------------------------------------------------------------------------------------
-template <typename T> struct Acc;                                   // accumulator of a sample type
-template <> struct Acc<uint8_t> { typedef int type; };
-template <> struct Acc<uint16_t> { typedef int64_t type; };
-
+// Acc<T>, the accumulator of a sample type, is payload_kit.h's
 template <int BYTES> struct Word;                                   // the access of BYTES bytes
 template <> struct Word<4> { typedef uint32_t type; };
 template <> struct Word<8> { typedef uint64_t type; };

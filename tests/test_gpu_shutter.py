@@ -90,7 +90,7 @@ def _check_kernel(P, es, smax, n, shift, gap, seed=0):
 
 
 @pytest.mark.parametrize('es', [1, 2], ids=['bytes', '16-bit'])
-@pytest.mark.parametrize('P', [1, 15, 16, 17, 4099, 64 * 96 * 3 // 2])
+@pytest.mark.parametrize('P', [1, 15, 16, 17, 33, 4099, 64 * 96 * 3 // 2])
 def test_kernel_equals_the_numpy_definition(P, es):
     """Aligned sources, dst and stride take the 16-byte path (with its sample-by-sample tail when P es is no multiple of 16); sources at odd
     byte offsets (2 mod 16 for 16-bit samples) and an odd stride take the sample-by-sample path."""
