@@ -175,7 +175,8 @@ class WindowRunner:
         self.scale_payloads = 0                      # resized output: payloads resampled (``y4m_edge.Scaler``)
         self.depth_promoted = self.depth_requantised = 0     # bit depth: payloads promoted at ingest / requantised at egress (``demfi_amd.bitdepth``)
         self.denoised = 0                            # temporal denoiser: frames denoised at ingest (``demfi_amd.denoise``)
-        self.grain_payloads = 0                      # film grain: payloads grained at egress (``y4m_edge.Grain``)
+        self.deblocked = 0                           # deblocking: payloads deblocked at ingest (``demfi_amd.deblock``)
+        self.grain_payloads = 0                     # film grain: payloads grained at egress (``y4m_edge.Grain``)
         self.colour_encoded = 0                      # linear light: payloads taken back to Y'CbCr (``y4m_edge.Encoder``)
         self.last_cuts = []                          # frames that start a scene, as the last run_clip_u8 with scene cuts found them
 
@@ -644,6 +645,9 @@ class WindowRunner:
         (``demfi_payload_denoise``) and everything else runs on the denoised stream; host_frames must then also hold that many frames before
         the first one named and answer ``has(f)`` for those after the last (``y4m.Frames(behind=reach)``); not together with ``yuv.dedup``
         or the adaptive ``yuv.deint_mode``.
+        ``yuv.deblock`` = (A, B) (None when absent; ``demfi_amd.deblock``): every uploaded payload is deblocked in place on the GPU behind
+        the promotion and in front of everything else (``demfi_payload_deblock``), on the grid of 8 shifted by ``yuv.crop_rect`` (the
+        rectangle the payloads were cropped to, None when absent); goes with everything.
         Returns the number of windows run."""
         spec = EdgeSpec.of(yuv)
         spec.check(self.retime is not None, window_index is not None, reuse_frames)

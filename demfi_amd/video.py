@@ -213,6 +213,26 @@ D2H, so the bars stay exact black.  One rank (the count would restart on a secon
 its first n is all several ranks would take).  ``--grain 0`` builds no stage.  Not offered: measuring the grain ``--denoise`` removed and
 matching it, grain correlated in time, AR-model grain as in AV1, per-plane curves, grain in linear light, several ranks,
 ``demfi_amd.clip``.  Without the switch no buffer, table, launch or stream is added and every byte stays the same.
+
+``--deblock [A[:B]]`` smooths the block edges of 8x8-DCT coded input (DV, 576i / 480i captures, NTSC DVDs behind ``--ivtc``, broadcast
+captures) in front of the network (``demfi_amd.deblock``): a deblurring network sharpens a block edge like any other edge and the flow sees a
+grid that never moves over content that does, so the output blocks more crisply than the input and shimmers between the interpolated
+instants; ``--denoise`` is purely temporal and preserves an edge that sits still.  The rule is H.264's intra-edge (bS = 4) luma filter as a
+post filter on the fixed grid of 8, on every plane as a plane in its own right: a line p3 p2 p1 p0 | q0 q1 q2 q3 across an edge changes only
+when |p0-q0| < a, |p1-p0| < b and |q1-q0| < b, up to three samples a side when that side is flat (|p0-q0| < (a >> 2) + 2 and |p2-p0| < b), one
+otherwise; all vertical edges first, then all horizontal ones on that result.  A and B are 8-bit steps (0 <= B <= A <= 255, default 16:4, A
+alone is A : (A + 3) // 4, one pair for every plane, shifted to the working depth); ``--deblock 0`` builds no stage.  The stage sits at the top
+of the ingest, H2D -> promote (``--work-depth``) -> deblock -> bob / adaptive -> denoise -> frames, tiles, scene scores, dedup probe: ONE
+launch per run of consecutive newly uploaded slots (csrc/deblock.hip ``demfi_payload_deblock``, byte for byte
+``deblock.deblock_payload_np``) works in place on the uploaded payloads, a workgroup per tile whose borders lie half way between edges, so a
+run with the switch writes the bytes of a run without it over the stream deblocked on the host.  Under ``--deinterlace`` (either mode) each
+field of each plane is filtered as a plane of its own, edges every 8 field rows, so nothing is averaged across two time instants; behind
+``--ivtc`` the film frames are progressive and filtered as such.  With ``--crop`` the grid belongs to the uncropped stream: the rectangle's top
+and left give the phases.  ``--ivtc`` and ``--crop auto`` decide in front of the device, on the input's own samples.  The stage keeps nothing
+between payloads and needs no look-ahead: every switch above and several ranks work, ``--dedup`` and ``--deinterlace-mode adaptive`` included.
+Not offered: frame-DCT blocks of interlaced material, whose edges fall every 4 field rows; grids other than 8, and material scaled after
+coding; strength from a quantiser, and per-plane thresholds; deringing; ``demfi_amd.clip``; numeric equality with ffmpeg's ``deblock`` /
+``pp``.  Without the switch no buffer, table, launch or counter is added and every byte stays the same.
 """
 import os
 import sys
@@ -224,6 +244,7 @@ from . import _lib as L
 from . import bitdepth as BD
 from . import cadence as K
 from . import colour as CL
+from . import deblock as DB
 from . import deint as I
 from . import denoise as DN
 from . import dist as D
@@ -261,12 +282,17 @@ class YuvEdge:
     (``demfi_amd.colour``); ``out_matrix`` ('bt601' / 'bt709') and ``out_range`` ('limited' / 'full'): None, or the matrix and range of the
     payloads handed out, where ``matrix`` and ``full_range`` are those of the payloads handed in.  ``colour`` = (transfer, out matrix, out
     full range), or None without the three.  ``grain``: None, or (S16, r, C16, curve, seed) of the film grain added to every progressive payload
-    in front of the weave (``demfi_amd.grain``); S16 = 0 is None."""
+    in front of the weave (``demfi_amd.grain``); S16 = 0 is None.  ``deblock``: None, or (A, B) of the deblocking filter at the top of the ingest
+    (``demfi_amd.deblock``); A = 0 is None.  ``crop_rect``: None, or the rectangle (top, bottom, left, right) the payloads handed in were cropped
+    to out of their stream, which shifts the deblocking grid."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
                  fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None,
-                 depths=None, shutter_window=None, denoise=None, linear_light=None, out_matrix=None, out_range=None, grain=None):
+                 depths=None, shutter_window=None, denoise=None, linear_light=None, out_matrix=None, out_range=None, grain=None,
+                 deblock=None, crop_rect=None):
         self.dedup, self.shutter = dedup, shutter
+        self.deblock = check_deblock(deblock)
+        self.crop_rect = None if crop_rect is None else tuple(int(v) for v in crop_rect)
         self.grain = None if grain is None or not GR.check_params(grain)[0] else GR.check_params(grain)
         self.colour = check_colour(linear_light, out_matrix, out_range)
         self.denoise = None if denoise is None else DN.check_params(*denoise)
@@ -425,6 +451,23 @@ def check_denoise(denoise, radius=None, dedup=None, deinterlace_mode='bob'):
     return dn
 
 
+def check_deblock(deblock):
+    """The deblock switch checked: None (off, or A = 0: no stage), or (A, B) of ``deblock.check_params``.  ``deblock``: None / False (off), True
+    (the defaults 16:4), A (A : (A + 3) // 4), (A, B) or an "A[:B]" string.  Goes with every other switch and any number of ranks."""
+    if deblock is None or deblock is False:
+        return None
+    if deblock is True:
+        deblock = DB.DEFAULTS
+    elif isinstance(deblock, str):
+        deblock = DB.parse_deblock(deblock)
+    elif isinstance(deblock, int):
+        deblock = (deblock, None)
+    if not isinstance(deblock, (tuple, list)) or len(deblock) != 2:
+        raise ValueError('deblock must be None, True, A, (A, B) or "A[:B]", got %r' % (deblock,))
+    ab = DB.check_params(deblock[0], deblock[1])
+    return ab if ab[0] else None
+
+
 def check_grain(grain=None, size=None, chroma=None, curve=None, seed=None, world=1):
     """The grain switches checked: None (no ``grain``, or S = 0: no stage) or (S16, r, C16, curve, seed) of ``grain.check_grain``.  ``grain``:
     S as a number or a decimal string, 0 .. 8; ``size`` 0, 1 or 2 (None: 1); ``chroma`` C in 0 .. 1 (None: 0.5); ``curve`` 'film' / 'flat' (None:
@@ -442,7 +485,7 @@ COUNTERS = {'instants_run': None, 'instants_padded': None, 'shutter_mixed': None
 # and of the egress stages that came after: linear light (``y4m_edge.Encoder``), film grain (``y4m_edge.Grain``)
 EGRESS_COUNTERS = {'colour_encoded': 'last_colour_encoded', 'grain_payloads': 'last_grain_payloads'}
 # the counters of the ingest stages that came after those: kept the same way, in a table of their own
-INGEST_COUNTERS = {'denoised': 'last_denoised'}
+INGEST_COUNTERS = {'denoised': 'last_denoised', 'deblocked': 'last_deblocked'}
 
 
 AUTO_NEEDS_A_FILE = ('--crop auto needs a regular input file: the bars of a stream are known only at its end; give the four bar '
@@ -563,7 +606,12 @@ class VideoRunner:
     ``grain_chroma`` C in 0 .. 1 (None: 0.5), ``grain_curve`` 'film' / 'flat' (None: 'film'), ``grain_seed`` a uint32 (None: 0); any of the four
     without ``grain`` is an error.  One rank (``run_file`` refuses more).  ``grain=0`` builds no stage.  After a run ``last_grain`` = (S16,
     r, C16, curve, seed) or None and ``last_grain_payloads`` = the payloads grained.  Without it no buffer, table, launch or stream is added
-    and every byte stays the same."""
+    and every byte stays the same.  ``deblock``: None (default), True (the thresholds 16:4), A (A : (A + 3) // 4), (A, B) or an "A[:B]" string,
+    at the 8-bit scale with 0 <= B <= A <= 255: the block edges of every uploaded payload are smoothed in place on the GPU at the top of the
+    ingest (``demfi_amd.deblock``, csrc/deblock.hip ``demfi_payload_deblock``, ONE launch per run of uploaded slots), on the grid of 8 of the
+    uncropped stream (``crop`` gives the phases), field by field under ``deinterlace``; everything behind runs on the deblocked stream.  Goes
+    with every other switch and any number of ranks.  ``deblock=0`` builds no stage.  After a run ``last_deblocked`` = the payloads
+    deblocked.  Without it no buffer, table, launch or counter is added and every byte stays the same."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
@@ -573,8 +621,9 @@ class VideoRunner:
                  shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, work_depth=None,
                  out_depth=None, dither=None, down=False, shutter_window=None, denoise=None, denoise_radius=None, linear_light=None,
                  out_matrix=None, out_range=None, grain=None, grain_size=None, grain_chroma=None, grain_curve=None, grain_seed=None,
-                 **runner_kw):
+                 deblock=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.deblock = check_deblock(deblock)            # (A, B) or None
         self.grain = check_grain(grain, grain_size, grain_chroma, grain_curve, grain_seed)   # (S16, r, C16, curve, seed) or None
         self.last_grain = None
         self.colour = check_colour(linear_light, out_matrix, out_range, auto=True)   # (transfer, out matrix or 'auto', out full range) or None
@@ -902,7 +951,8 @@ class VideoRunner:
         return YuvEdge(self._in_matrix(hdr), hdr.full_range, hdr.chroma, with_s1,
                        self.scene_cut, self.full_length, depths[1], hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
                        *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths, shutter_window=self.shutter_window,
-                       denoise=self.denoise, grain=self.grain, **kw)
+                       denoise=self.denoise, grain=self.grain, deblock=self.deblock,
+                       crop_rect=self.last_crop if self.deblock is not None else None, **kw)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
@@ -1217,6 +1267,14 @@ def parser():
                          'alone.  Behind --ivtc, --crop, --work-depth and --deinterlace (there over fields of the same parity), in front of '
                          'everything else, scene scores included.  Not with --dedup or --deinterlace-mode adaptive.  Off by default'
                          % DN.DEFAULTS)
+    ap.add_argument('--deblock', nargs='?', type=_value_arg(DB.parse_deblock), const=DB.DEFAULTS, default=None, metavar='A[:B]',
+                    help='smooth the block edges of 8x8-DCT coded input (DV, 576i / 480i captures, DVDs, broadcast captures) on the GPU in front '
+                         'of everything else: H.264\'s intra-edge filter on the fixed grid of 8, in every plane.  A line across an edge changes '
+                         'only when the step over the edge is below A and the steps next to it are below B (8-bit steps, 0 <= B <= A <= 255, '
+                         'one pair for all planes; default %d:%d; A alone means A:(A+3)//4; 0 builds nothing), up to three samples a side '
+                         'where the side is flat, so real edges are left alone.  With --deinterlace every field is filtered on its own; '
+                         'with --crop the grid stays that of the uncropped stream.  Works with every other switch and any number of ranks.  '
+                         'Off by default' % DB.DEFAULTS)
     ap.add_argument('--denoise-radius', type=int, default=None, metavar='R',
                     help='with --denoise: the frames looked at on each side, 1 .. %d (default %d); costs R frames of lookahead, 2 R fields '
                          'behind --deinterlace' % (DN.MAX_RADIUS, DN.DEFAULT_RADIUS))
@@ -1279,6 +1337,7 @@ def main(argv=None):
         check_scale(a.scale, a.scale_filter, a.crop, crop_kw.get('crop_output', 'pad'))
         check_depths(a.work_depth, a.out_depth, a.dither)
         check_denoise(a.denoise, a.denoise_radius, a.dedup or None, a.deinterlace_mode)
+        check_deblock(a.deblock)
         check_colour(a.linear_light, a.out_matrix, a.out_range, auto=True)
         grain = check_grain(a.grain, a.grain_size, a.grain_chroma, a.grain_curve, a.grain_seed)
     except ValueError as e:
@@ -1289,7 +1348,8 @@ def main(argv=None):
                                     ('dither', a.dither), ('shutter_window', a.shutter_window), ('denoise', a.denoise),
                                     ('denoise_radius', a.denoise_radius), ('linear_light', a.linear_light), ('out_matrix', a.out_matrix),
                                     ('out_range', a.out_range), ('grain', a.grain), ('grain_size', a.grain_size),
-                                    ('grain_chroma', a.grain_chroma), ('grain_curve', a.grain_curve), ('grain_seed', a.grain_seed))
+                                    ('grain_chroma', a.grain_chroma), ('grain_curve', a.grain_curve), ('grain_seed', a.grain_seed),
+                                    ('deblock', a.deblock))
                   if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     try:
@@ -1336,8 +1396,8 @@ def main(argv=None):
     torch.cuda.synchronize()
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
     counts = [float(nw), float(nf), float(vr.last_st_frames), float(vr.last_instants[0]), float(vr.last_instants[1]),
-              float(vr.last_cut_windows), float(vr.last_depth_promoted), float(vr.last_depth_requantised), float(vr.last_denoised)]
-    tw, tf, tst, ti, tp, tc, tdp, tdq, tdn = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
+              float(vr.last_cut_windows), float(vr.last_depth_promoted), float(vr.last_depth_requantised), float(vr.last_denoised), float(vr.last_deblocked)]
+    tw, tf, tst, ti, tp, tc, tdp, tdq, tdn, tdb = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
     if rank == 0:
         if a.crop is not None:
             print('demfi_amd.video: ' + vr.crop_report(), file=sys.stderr)
@@ -1353,6 +1413,8 @@ def main(argv=None):
             extra['interlace'] = {'order': vr.last_interlace, 'lowpass': vr.interlace[1], 'carried': vr.last_interlace_carried}
         if a.denoise is not None:
             extra['denoise'] = {'a': vr.denoise[0], 'b': vr.denoise[1], 'radius': vr.denoise[2], 'frames': int(tdn)}
+        if a.deblock is not None:
+            extra['deblock'] = {'a': a.deblock[0], 'b': a.deblock[1], 'payloads': int(tdb)}
         if a.scale is not None:
             extra['scale'] = {'size': '%dx%d' % vr.scale[:2], 'filter': vr.scale[2], 'resized': vr.last_scale is not None,
                               'payloads': vr.last_scale_payloads}

@@ -17,6 +17,7 @@ import torch
 from . import _lib as L
 from . import cadence as K
 from . import colour as CL
+from . import deblock as DB
 from . import deint as I
 from . import denoise as DN
 from . import grain as GR
@@ -111,8 +112,14 @@ class Ingest:
     frames each) writes the denoised payload of every frame the batch names for the first time into ``clean`` [nslot, Pb], slot for slot beside
     ``yuv_in``, from the frames f - R step .. f + R step in yuv_in (step 2 over bobbed fields), which the denoiser alone reads from then on:
     ``payloads`` is the buffer everything behind it reads.  The bookkeeping is the adaptive deinterlacer's with ``reach`` = R step in place of 2:
-    ``around`` names the frames to upload, a frame uploaded ahead of its window waits in ``raw``, ``rebuilt`` returns the frames just denoised."""
+    ``around`` names the frames to upload, a frame uploaded ahead of its window waits in ``raw``, ``rebuilt`` returns the frames just denoised.
+    ``spec.deblock`` = (A, B) (``demfi_amd.deblock``): behind the promotion and in front of everything else that reads yuv_in ONE
+    ``demfi_payload_deblock`` launch per run of consecutive newly uploaded slots smooths the block edges of their payloads in place, every plane
+    (interlaced input: every field of every plane) as ``deblock.plane_table`` lays them out; the phases of the grid are those of the crop
+    rectangle that left the payloads of their uncropped stream (``crop_rect`` of the run's ``yuv``, taken by ``attach``).  The stage keeps
+    nothing between payloads, so it needs no look-ahead and no bookkeeping; the runner counts ``deblocked``."""
     denoise = clean = None                           # without --denoise: no buffer, table or launch
+    deblock = None                                   # without --deblock: no table, launch or counter
 
     def __init__(self, runner, slots, spec, h, w, tiler=None):
         self.rn, self.slots, self.tiler, self.fh, self.fw = runner, slots, tiler, h, w
@@ -129,6 +136,9 @@ class Ingest:
             self.denoise, self.step = DN.thresholds(spec.depth, a, b), 2 if spec.fields is not None else 1
             self.clean = torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev)
             self.dn_offs = torch.empty((2 * self.radius + 2) * nsl, dtype=torch.int64, device=dev)
+        if spec.deblock is not None:                 # the thresholds at the working depth; the plane table is a host array the entry point reads
+            self.deblock = DB.thresholds(spec.depth, *spec.deblock)
+            self.attach(None)
         # a working depth above the input's (``spec.depths``, ``demfi_amd.bitdepth``): payloads are copied into ``staged`` at the input's sample
         # size, so H2D carries the input's bytes, and ``promote`` writes them into yuv_in at the working depth before anything else reads them
         self.staged, self.up, self.full_range = None, self.yuv_in, False     # full_range: the stream's, set by ``Y4mEdge.attach``
@@ -144,6 +154,24 @@ class Ingest:
         if tuple(f.shape) != (self.up.shape[1],) or f.dtype != torch.uint8:
             raise ValueError('frame %d: expected a uint8 [%d] %s payload, got %s %s' % (idx, self.up.shape[1], self.layout, f.dtype, tuple(f.shape)))
         self.up[sl].copy_(f, non_blocking=True)
+
+    def attach(self, yuv):
+        """A run on the stream ``yuv`` starts: its range, for the promotion, and the crop rectangle its payloads were cut out with
+        (``crop_rect``; None: none), for the phases of the deblocking grid."""
+        self.full_range = bool(getattr(yuv, 'full_range', False))
+        if self.deblock is not None:
+            self.db_planes = np.ascontiguousarray(DB.plane_table(self.fh, self.fw, self.layout, self.fields, getattr(yuv, 'crop_rect', None)),
+                                                  dtype=np.int64)
+
+    def deblocked(self, new, stream):
+        """The payloads just copied (and promoted) for the (frame, slot) pairs ``new`` are deblocked in place: ONE ``demfi_payload_deblock``
+        launch per run of consecutive slots, in front of everything else that reads yuv_in."""
+        if self.deblock is None or not new:
+            return
+        for s0, cnt in consecutive([sl for _, sl in new]):
+            L.check(self.rn.lib.demfi_payload_deblock(self.yuv_in[s0].data_ptr(), self.Pb, cnt, self.db_planes.ctypes.data, len(self.db_planes),
+                                                      self.es, *self.deblock, stream.cuda_stream), 'payload_deblock')
+        self.rn.deblocked += len(new)
 
     def promote(self, new, stream):
         """The payloads just copied for the (frame, slot) pairs ``new`` go from ``staged`` to yuv_in at the working depth: ONE
@@ -170,8 +198,10 @@ class Ingest:
 
     def rebuilt(self, new, stream):
         """The payloads just copied for the (frame, slot) pairs ``new`` become progressive payloads at the working depth: promoted first of
-        all, then made progressive.  Returns the pairs that now are (adaptive: the fields just rebuilt, not those uploaded)."""
+        all, deblocked (``spec.deblock``), then made progressive.  Returns the pairs that now are (adaptive: the fields just rebuilt, not those
+        uploaded)."""
         self.promote(new, stream)
+        self.deblocked(new, stream)
         new = self._adaptive(new, stream) if self.adaptive else self.bob(new, stream)
         return self._denoise(new, stream) if self.denoise is not None else new
 
@@ -810,7 +840,7 @@ class Y4mEdge:
     def attach(self, host_frames, yuv=None):
         """Before a run's first window is asked for.  --dedup: ``host_frames`` is the ``KeptFrames`` that stages frames through ``probe``, and
         a frame staged is promoted there (``spec.depths``), which needs the range of the stream ``yuv``."""
-        self.ingest.full_range = bool(getattr(yuv, 'full_range', False))
+        self.ingest.attach(yuv)
         if self.probe is not None:
             self.kept = self.probe.attach(host_frames)
 

@@ -482,6 +482,26 @@ int demfi_yuv_deint_adaptive(void* base, int64_t size_bytes, const int64_t* offs
 int demfi_payload_denoise(const uint8_t* src, int64_t src_bytes, const int64_t* offsets, const int64_t* offsets_dev, int n, int taps,
                           int64_t P, int sample_bytes, int thr_a, int thr_b, uint8_t* dst, int64_t dst_bytes, void* stream);
 
+/* ---- deblocking of the Y4M edge (csrc/deblock.hip; demfi_amd/video.py --deblock) ------------------------------------------------------
+ * payload_deblock: the n (>= 0, any number) payloads at payloads + i*stride_bytes are deblocked IN PLACE (sample_bytes = 1, or 2 for 16-bit
+ * little-endian samples: even address and stride).  planes: the plane table in HOST memory, n_planes (1..6: 3 planes x 2 fields) entries of
+ * six int64 each, what demfi_amd/deblock.py plane_table gives: the plane's first sample in the payload, its rows and cols (1..16384 each),
+ * its row pitch in samples (>= cols; two rows for a field of an interlaced payload) and its x and y phase (0..7: the columns and rows that
+ * a crop removed in front of it, mod 8).  The entries must not share a sample.  Every entry is filtered as a plane in its own right by
+ * H.264's intra-edge (bS = 4) luma filter on the fixed grid of 8: a vertical edge at column x when (x + x phase) % 8 == 0 and 4 <= x <=
+ * cols - 4, rows likewise; a line p3 p2 p1 p0 | q0 q1 q2 q3 across an edge changes only when |p0-q0| < thr_a, |p1-p0| < thr_b and
+ * |q1-q0| < thr_b, a side takes the strong form when also |p0-q0| < thr_s and |p2-p0| < thr_b (q side: the mirror image), p3 and q3 never
+ * change; all vertical edges first, then all horizontal edges on that result.  Exact integers; the numpy definition is
+ * deblock_payload_np, matched byte for byte (thr_a, thr_b, thr_s: deblock.thresholds at the stream's depth, 0 <= thr_b <= thr_a <= 255
+ * for bytes, <= 65535 for 16-bit samples, thr_s likewise).  A workgroup owns a tile of a plane whose borders lie half way between edges,
+ * so it reads and writes nothing another workgroup touches: no second buffer, no atomics.  Samples no entry names and everything between
+ * the payloads are neither read nor written.
+ * DEMFI_ERR_ARG, with nothing launched: a NULL buffer, n < 0, sample_bytes not 1 or 2, n_planes outside 1..6, thresholds out of range, a
+ * plane that starts below sample 0, a side outside 1..16384, a pitch below cols, a phase outside 0..7, 16-bit samples at an odd address
+ * or stride, stride_bytes below the bytes the table reaches.  One launch for all planes of all n payloads; n == 0 does nothing. */
+int demfi_payload_deblock(void* payloads, int64_t stride_bytes, int n, const int64_t* planes, int n_planes, int sample_bytes, int thr_a,
+                          int thr_b, int thr_s, void* stream);
+
 /* ---- inverse telecine of the Y4M edge (csrc/ivtc.hip; demfi_amd/video.py --ivtc) ------------------------------------------------
  * A woven frame W(top, bot) has the even rows of the luma plane (the first h*w samples of a payload; sample_bytes = 1, or 2 for
  * 16-bit little-endian samples) of payload `top` and the odd rows of that of payload `bot`; it is read in place, never built.
