@@ -31,8 +31,8 @@ remainders of the plane in line with it, which is why the kernel may work in pla
 
 ``deblock_payload_np`` is the definition the kernel (csrc/deblock.hip, ``demfi_payload_deblock``) is held to, byte for byte; ``plane_table``
 is what the two share.  Not offered: frame-DCT blocks of interlaced material, whose edges fall every 4 field rows; grids other than 8, and
-material scaled after coding; strength from a quantiser, and per-plane thresholds; deringing; ``demfi_amd.clip``; numeric equality with
-ffmpeg's ``deblock`` / ``pp``.
+material scaled after coding; strength from a quantiser, and per-plane thresholds; ``demfi_amd.clip``; numeric equality with ffmpeg's
+``deblock`` / ``pp``.  Ringing is the business of ``--dering`` (``demfi_amd.dering``), which runs directly behind this stage.
 """
 import re
 

@@ -176,6 +176,7 @@ class WindowRunner:
         self.depth_promoted = self.depth_requantised = 0     # bit depth: payloads promoted at ingest / requantised at egress (``demfi_amd.bitdepth``)
         self.denoised = 0                            # temporal denoiser: frames denoised at ingest (``demfi_amd.denoise``)
         self.deblocked = 0                           # deblocking: payloads deblocked at ingest (``demfi_amd.deblock``)
+        self.deringed = 0                            # deringing: payloads deringed at ingest (``demfi_amd.dering``)
         self.grain_payloads = 0                     # film grain: payloads grained at egress (``y4m_edge.Grain``)
         self.colour_encoded = 0                      # linear light: payloads taken back to Y'CbCr (``y4m_edge.Encoder``)
         self.last_cuts = []                          # frames that start a scene, as the last run_clip_u8 with scene cuts found them
@@ -648,6 +649,9 @@ class WindowRunner:
         ``yuv.deblock`` = (A, B) (None when absent; ``demfi_amd.deblock``): every uploaded payload is deblocked in place on the GPU behind
         the promotion and in front of everything else (``demfi_payload_deblock``), on the grid of 8 shifted by ``yuv.crop_rect`` (the
         rectangle the payloads were cropped to, None when absent); goes with everything.
+        ``yuv.dering`` = (P, S, D) (None when absent; ``demfi_amd.dering``): every uploaded payload is deringed on the GPU behind the
+        deblocker and in front of everything else (one device copy into a scratch buffer, then ``demfi_payload_dering`` back into place),
+        on the same grid; goes with everything.
         Returns the number of windows run."""
         spec = EdgeSpec.of(yuv)
         spec.check(self.retime is not None, window_index is not None, reuse_frames)

@@ -231,8 +231,29 @@ field of each plane is filtered as a plane of its own, edges every 8 field rows,
 and left give the phases.  ``--ivtc`` and ``--crop auto`` decide in front of the device, on the input's own samples.  The stage keeps nothing
 between payloads and needs no look-ahead: every switch above and several ranks work, ``--dedup`` and ``--deinterlace-mode adaptive`` included.
 Not offered: frame-DCT blocks of interlaced material, whose edges fall every 4 field rows; grids other than 8, and material scaled after
-coding; strength from a quantiser, and per-plane thresholds; deringing; ``demfi_amd.clip``; numeric equality with ffmpeg's ``deblock`` /
-``pp``.  Without the switch no buffer, table, launch or counter is added and every byte stays the same.
+coding; strength from a quantiser, and per-plane thresholds; ``demfi_amd.clip``; numeric equality with ffmpeg's ``deblock`` / ``pp``;
+ringing is the business of ``--dering``.  Without the switch no buffer, table, launch or counter is added and every byte stays the same.
+
+``--dering [P[:S[:D]]]`` removes the other artefact of 8x8-DCT coded input, ringing and mosquito noise beside strong edges, in front of the
+network (``demfi_amd.dering``): a deblurring network sharpens the ripples like any other fine detail, and because they change with the
+coder's quantiser from frame to frame the flow sees motion that is not there; ``--denoise`` stops at any difference above A, which ringing
+beside a moving edge always is, and ``--deblock`` touches only samples within 3 of a grid line.  The rule is AV1's constrained directional
+enhancement filter (CDEF) in exact integers, on every plane as a plane in its own right: every 8x8 block of the coder's grid finds the
+dominant one of 8 directions, a sample is smoothed strongly along it (4 primary taps, strength P scaled by the block's directional
+variance, none in a flat block) and weakly across it (8 secondary taps, strength S), every tap through a constraint function that leaves it
+alone when it differs from the centre by more than the strength allows (damping D), so real edges stay, and the result is clamped to the
+extremes of what it read.  P (0 .. 15), S (0 .. 4) and D (3 .. 6) are 8-bit steps, one triple for every plane, shifted to the working depth;
+the default 4:2:5 is the middle of AV1's range and has not been tuned against this network; P alone is P : min((P + 1) // 2, 4) : 5;
+``--dering 0:0`` builds no stage.  The stage sits behind the deblocker, H2D -> promote (``--work-depth``) -> deblock -> dering -> bob /
+adaptive -> denoise -> frames, tiles, scene scores, dedup probe: the filter reads a halo of unfiltered samples and cannot work in place, so
+per run of consecutive newly uploaded slots one device copy takes the payloads into a scratch buffer and ONE launch (csrc/dering.hip
+``demfi_payload_dering``, byte for byte ``dering.dering_payload_np``) writes them back deringed; a run with the switch writes the bytes of a
+run without it over the stream deringed on the host.  Under ``--deinterlace`` (either mode) each field of each plane is a plane of its own;
+with ``--crop`` the grid belongs to the uncropped stream.  The stage keeps nothing between payloads and needs no look-ahead: every switch
+above and several ranks work.  Not offered: equality with libaom / dav1d output (the strengths are per stream and not per superblock, every
+plane searches its own direction, there is no skip map); strength from a quantiser; per-plane strengths; 4x4 chroma blocks; frame-DCT
+blocks of interlaced material; ``demfi_amd.clip``.  Without the switch no buffer, table, launch, copy or counter is added and every byte
+stays the same.
 """
 import os
 import sys
@@ -247,6 +268,7 @@ from . import colour as CL
 from . import deblock as DB
 from . import deint as I
 from . import denoise as DN
+from . import dering as DR
 from . import dist as D
 from . import grain as GR
 from . import interlace as IL
@@ -284,14 +306,16 @@ class YuvEdge:
     full range), or None without the three.  ``grain``: None, or (S16, r, C16, curve, seed) of the film grain added to every progressive payload
     in front of the weave (``demfi_amd.grain``); S16 = 0 is None.  ``deblock``: None, or (A, B) of the deblocking filter at the top of the ingest
     (``demfi_amd.deblock``); A = 0 is None.  ``crop_rect``: None, or the rectangle (top, bottom, left, right) the payloads handed in were cropped
-    to out of their stream, which shifts the deblocking grid."""
+    to out of their stream, which shifts the block grid of both.  ``dering``: None, or (P, S, D) of the deringing filter behind the deblocker
+    (``demfi_amd.dering``); P = S = 0 is None."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
                  fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None,
                  depths=None, shutter_window=None, denoise=None, linear_light=None, out_matrix=None, out_range=None, grain=None,
-                 deblock=None, crop_rect=None):
+                 deblock=None, crop_rect=None, dering=None):
         self.dedup, self.shutter = dedup, shutter
         self.deblock = check_deblock(deblock)
+        self.dering = check_dering(dering)
         self.crop_rect = None if crop_rect is None else tuple(int(v) for v in crop_rect)
         self.grain = None if grain is None or not GR.check_params(grain)[0] else GR.check_params(grain)
         self.colour = check_colour(linear_light, out_matrix, out_range)
@@ -468,6 +492,24 @@ def check_deblock(deblock):
     return ab if ab[0] else None
 
 
+def check_dering(dering):
+    """The dering switch checked: None (off, or P = S = 0: no stage), or (P, S, D) of ``dering.check_params``.  ``dering``: None / False (off),
+    True (the defaults 4:2:5), P (P : min((P + 1) // 2, 4) : 5), (P, S), (P, S, D) or a "P[:S[:D]]" string.  Goes with every other switch and
+    any number of ranks."""
+    if dering is None or dering is False:
+        return None
+    if dering is True:
+        dering = DR.DEFAULTS
+    elif isinstance(dering, str):
+        dering = DR.parse_dering(dering)
+    elif isinstance(dering, int):
+        dering = (dering,)
+    if not isinstance(dering, (tuple, list)) or not 1 <= len(dering) <= 3:
+        raise ValueError('dering must be None, True, P, (P, S), (P, S, D) or "P[:S[:D]]", got %r' % (dering,))
+    psd = DR.check_params(*dering)
+    return psd if psd[0] or psd[1] else None
+
+
 def check_grain(grain=None, size=None, chroma=None, curve=None, seed=None, world=1):
     """The grain switches checked: None (no ``grain``, or S = 0: no stage) or (S16, r, C16, curve, seed) of ``grain.check_grain``.  ``grain``:
     S as a number or a decimal string, 0 .. 8; ``size`` 0, 1 or 2 (None: 1); ``chroma`` C in 0 .. 1 (None: 0.5); ``curve`` 'film' / 'flat' (None:
@@ -485,7 +527,7 @@ COUNTERS = {'instants_run': None, 'instants_padded': None, 'shutter_mixed': None
 # and of the egress stages that came after: linear light (``y4m_edge.Encoder``), film grain (``y4m_edge.Grain``)
 EGRESS_COUNTERS = {'colour_encoded': 'last_colour_encoded', 'grain_payloads': 'last_grain_payloads'}
 # the counters of the ingest stages that came after those: kept the same way, in a table of their own
-INGEST_COUNTERS = {'denoised': 'last_denoised', 'deblocked': 'last_deblocked'}
+INGEST_COUNTERS = {'denoised': 'last_denoised', 'deblocked': 'last_deblocked', 'deringed': 'last_deringed'}
 
 
 AUTO_NEEDS_A_FILE = ('--crop auto needs a regular input file: the bars of a stream are known only at its end; give the four bar '
@@ -611,7 +653,13 @@ class VideoRunner:
     ingest (``demfi_amd.deblock``, csrc/deblock.hip ``demfi_payload_deblock``, ONE launch per run of uploaded slots), on the grid of 8 of the
     uncropped stream (``crop`` gives the phases), field by field under ``deinterlace``; everything behind runs on the deblocked stream.  Goes
     with every other switch and any number of ranks.  ``deblock=0`` builds no stage.  After a run ``last_deblocked`` = the payloads
-    deblocked.  Without it no buffer, table, launch or counter is added and every byte stays the same."""
+    deblocked.  Without it no buffer, table, launch or counter is added and every byte stays the same.  ``dering``: None (default), True (the
+    strengths 4:2:5, AV1's middle of the range, not tuned against this network), P (P : min((P + 1) // 2, 4) : 5), (P, S), (P, S, D) or a
+    "P[:S[:D]]" string, at the 8-bit scale with 0 <= P <= 15, 0 <= S <= 4, 3 <= D <= 6: ringing beside edges is smoothed on the GPU behind the
+    deblocker (``demfi_amd.dering``: AV1's CDEF; csrc/dering.hip ``demfi_payload_dering``, one device copy into a scratch buffer and ONE launch
+    per run of uploaded slots), on the block grid of the uncropped stream, field by field under ``deinterlace``; everything behind runs on the
+    deringed stream.  Goes with every other switch and any number of ranks.  ``dering=(0, 0)`` builds no stage.  After a run ``last_deringed``
+    = the payloads deringed.  Without it no buffer, table, launch, copy or counter is added and every byte stays the same."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
@@ -621,9 +669,10 @@ class VideoRunner:
                  shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, work_depth=None,
                  out_depth=None, dither=None, down=False, shutter_window=None, denoise=None, denoise_radius=None, linear_light=None,
                  out_matrix=None, out_range=None, grain=None, grain_size=None, grain_chroma=None, grain_curve=None, grain_seed=None,
-                 deblock=None, **runner_kw):
+                 deblock=None, dering=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
         self.deblock = check_deblock(deblock)            # (A, B) or None
+        self.dering = check_dering(dering)               # (P, S, D) or None
         self.grain = check_grain(grain, grain_size, grain_chroma, grain_curve, grain_seed)   # (S16, r, C16, curve, seed) or None
         self.last_grain = None
         self.colour = check_colour(linear_light, out_matrix, out_range, auto=True)   # (transfer, out matrix or 'auto', out full range) or None
@@ -951,8 +1000,8 @@ class VideoRunner:
         return YuvEdge(self._in_matrix(hdr), hdr.full_range, hdr.chroma, with_s1,
                        self.scene_cut, self.full_length, depths[1], hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
                        *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths, shutter_window=self.shutter_window,
-                       denoise=self.denoise, grain=self.grain, deblock=self.deblock,
-                       crop_rect=self.last_crop if self.deblock is not None else None, **kw)
+                       denoise=self.denoise, grain=self.grain, deblock=self.deblock, dering=self.dering,
+                       crop_rect=self.last_crop if self.deblock is not None or self.dering is not None else None, **kw)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
         """The --dedup run of ``frames`` (``y4m.Frames`` over the whole input) on cr: the windows are those of the kept frames."""
@@ -1275,6 +1324,15 @@ def parser():
                          'where the side is flat, so real edges are left alone.  With --deinterlace every field is filtered on its own; '
                          'with --crop the grid stays that of the uncropped stream.  Works with every other switch and any number of ranks.  '
                          'Off by default' % DB.DEFAULTS)
+    ap.add_argument('--dering', nargs='?', type=_value_arg(DR.parse_dering), const=DR.DEFAULTS, default=None, metavar='P[:S[:D]]',
+                    help='smooth the ringing and mosquito noise beside the edges of 8x8-DCT coded input on the GPU, behind --deblock and in front '
+                         'of everything else: AV1\'s constrained directional enhancement filter in every plane.  Every 8x8 block finds its '
+                         'dominant direction; samples are smoothed along it with strength P (0 .. %d) and across it with strength S (0 .. %d), and '
+                         'a neighbour that differs by more than the strength allows (damping D, %d .. %d) is left out, so real edges stay.  '
+                         '8-bit steps, one triple for all planes; default %d:%d:%d (the middle of AV1\'s range, not tuned against this network); '
+                         'P alone means P:min((P+1)//2,4):5; 0:0 builds nothing.  With --deinterlace every field is filtered on its own; with '
+                         '--crop the grid stays that of the uncropped stream.  Works with every other switch and any number of ranks.  '
+                         'Off by default' % ((DR.MAX_P, DR.MAX_S, DR.MIN_D, DR.MAX_D) + DR.DEFAULTS))
     ap.add_argument('--denoise-radius', type=int, default=None, metavar='R',
                     help='with --denoise: the frames looked at on each side, 1 .. %d (default %d); costs R frames of lookahead, 2 R fields '
                          'behind --deinterlace' % (DN.MAX_RADIUS, DN.DEFAULT_RADIUS))
@@ -1338,6 +1396,7 @@ def main(argv=None):
         check_depths(a.work_depth, a.out_depth, a.dither)
         check_denoise(a.denoise, a.denoise_radius, a.dedup or None, a.deinterlace_mode)
         check_deblock(a.deblock)
+        check_dering(a.dering)
         check_colour(a.linear_light, a.out_matrix, a.out_range, auto=True)
         grain = check_grain(a.grain, a.grain_size, a.grain_chroma, a.grain_curve, a.grain_seed)
     except ValueError as e:
@@ -1349,7 +1408,7 @@ def main(argv=None):
                                     ('denoise_radius', a.denoise_radius), ('linear_light', a.linear_light), ('out_matrix', a.out_matrix),
                                     ('out_range', a.out_range), ('grain', a.grain), ('grain_size', a.grain_size),
                                     ('grain_chroma', a.grain_chroma), ('grain_curve', a.grain_curve), ('grain_seed', a.grain_seed),
-                                    ('deblock', a.deblock))
+                                    ('deblock', a.deblock), ('dering', a.dering))
                   if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     try:
@@ -1396,8 +1455,9 @@ def main(argv=None):
     torch.cuda.synchronize()
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
     counts = [float(nw), float(nf), float(vr.last_st_frames), float(vr.last_instants[0]), float(vr.last_instants[1]),
-              float(vr.last_cut_windows), float(vr.last_depth_promoted), float(vr.last_depth_requantised), float(vr.last_denoised), float(vr.last_deblocked)]
-    tw, tf, tst, ti, tp, tc, tdp, tdq, tdn, tdb = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
+              float(vr.last_cut_windows), float(vr.last_depth_promoted), float(vr.last_depth_requantised), float(vr.last_denoised), float(vr.last_deblocked),
+              float(vr.last_deringed)]
+    tw, tf, tst, ti, tp, tc, tdp, tdq, tdn, tdb, tdr = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
     if rank == 0:
         if a.crop is not None:
             print('demfi_amd.video: ' + vr.crop_report(), file=sys.stderr)
@@ -1415,6 +1475,8 @@ def main(argv=None):
             extra['denoise'] = {'a': vr.denoise[0], 'b': vr.denoise[1], 'radius': vr.denoise[2], 'frames': int(tdn)}
         if a.deblock is not None:
             extra['deblock'] = {'a': a.deblock[0], 'b': a.deblock[1], 'payloads': int(tdb)}
+        if a.dering is not None:
+            extra['dering'] = {'p': a.dering[0], 's': a.dering[1], 'd': a.dering[2], 'payloads': int(tdr)}
         if a.scale is not None:
             extra['scale'] = {'size': '%dx%d' % vr.scale[:2], 'filter': vr.scale[2], 'resized': vr.last_scale is not None,
                               'payloads': vr.last_scale_payloads}

@@ -20,6 +20,7 @@ from . import colour as CL
 from . import deblock as DB
 from . import deint as I
 from . import denoise as DN
+from . import dering as DR
 from . import grain as GR
 from . import interlace as IL
 from . import retime as R
@@ -117,9 +118,14 @@ class Ingest:
     ``demfi_payload_deblock`` launch per run of consecutive newly uploaded slots smooths the block edges of their payloads in place, every plane
     (interlaced input: every field of every plane) as ``deblock.plane_table`` lays them out; the phases of the grid are those of the crop
     rectangle that left the payloads of their uncropped stream (``crop_rect`` of the run's ``yuv``, taken by ``attach``).  The stage keeps
-    nothing between payloads, so it needs no look-ahead and no bookkeeping; the runner counts ``deblocked``."""
+    nothing between payloads, so it needs no look-ahead and no bookkeeping; the runner counts ``deblocked``.
+    ``spec.dering`` = (P, S, D) (``demfi_amd.dering``): behind the deblocker and in front of everything else that reads yuv_in.  The filter
+    reads a halo of unfiltered samples and cannot work in place: per run of consecutive newly uploaded slots ONE device copy takes the run's
+    payloads into ``dr_scratch`` (shaped like yuv_in) and ONE ``demfi_payload_dering`` launch writes them back into yuv_in deringed, every plane
+    (every field of every plane) of ``deblock.plane_table`` on the same grid.  Nothing is kept between payloads; the runner counts ``deringed``."""
     denoise = clean = None                           # without --denoise: no buffer, table or launch
     deblock = None                                   # without --deblock: no table, launch or counter
+    dering = None                                    # without --dering: no buffer, table, launch, copy or counter
 
     def __init__(self, runner, slots, spec, h, w, tiler=None):
         self.rn, self.slots, self.tiler, self.fh, self.fw = runner, slots, tiler, h, w
@@ -138,6 +144,10 @@ class Ingest:
             self.dn_offs = torch.empty((2 * self.radius + 2) * nsl, dtype=torch.int64, device=dev)
         if spec.deblock is not None:                 # the thresholds at the working depth; the plane table is a host array the entry point reads
             self.deblock = DB.thresholds(spec.depth, *spec.deblock)
+        if spec.dering is not None:                  # the strengths at the 8-bit scale and the depth; the scratch the launch reads
+            self.dering = (spec.depth,) + DR.check_params(*spec.dering)
+            self.dr_scratch = torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev)
+        if self.deblock is not None or self.dering is not None:
             self.attach(None)
         # a working depth above the input's (``spec.depths``, ``demfi_amd.bitdepth``): payloads are copied into ``staged`` at the input's sample
         # size, so H2D carries the input's bytes, and ``promote`` writes them into yuv_in at the working depth before anything else reads them
@@ -157,10 +167,13 @@ class Ingest:
 
     def attach(self, yuv):
         """A run on the stream ``yuv`` starts: its range, for the promotion, and the crop rectangle its payloads were cut out with
-        (``crop_rect``; None: none), for the phases of the deblocking grid."""
+        (``crop_rect``; None: none), for the phases of the block grid of the deblocker and the deringing filter."""
         self.full_range = bool(getattr(yuv, 'full_range', False))
         if self.deblock is not None:
             self.db_planes = np.ascontiguousarray(DB.plane_table(self.fh, self.fw, self.layout, self.fields, getattr(yuv, 'crop_rect', None)),
+                                                  dtype=np.int64)
+        if self.dering is not None:
+            self.dr_planes = np.ascontiguousarray(DB.plane_table(self.fh, self.fw, self.layout, self.fields, getattr(yuv, 'crop_rect', None)),
                                                   dtype=np.int64)
 
     def deblocked(self, new, stream):
@@ -172,6 +185,18 @@ class Ingest:
             L.check(self.rn.lib.demfi_payload_deblock(self.yuv_in[s0].data_ptr(), self.Pb, cnt, self.db_planes.ctypes.data, len(self.db_planes),
                                                       self.es, *self.deblock, stream.cuda_stream), 'payload_deblock')
         self.rn.deblocked += len(new)
+
+    def deringed(self, new, stream):
+        """The payloads just copied (promoted, deblocked) for the (frame, slot) pairs ``new`` are deringed: per run of consecutive slots ONE
+        device copy into the scratch on the ingest stream, then ONE ``demfi_payload_dering`` launch from the scratch back into yuv_in."""
+        if self.dering is None or not new:
+            return
+        for s0, cnt in consecutive([sl for _, sl in new]):
+            self.dr_scratch[s0:s0 + cnt].copy_(self.yuv_in[s0:s0 + cnt], non_blocking=True)
+            L.check(self.rn.lib.demfi_payload_dering(self.dr_scratch[s0].data_ptr(), self.Pb, self.yuv_in[s0].data_ptr(), self.Pb, cnt,
+                                                     self.dr_planes.ctypes.data, len(self.dr_planes), self.es, *self.dering,
+                                                     stream.cuda_stream), 'payload_dering')
+        self.rn.deringed += len(new)
 
     def promote(self, new, stream):
         """The payloads just copied for the (frame, slot) pairs ``new`` go from ``staged`` to yuv_in at the working depth: ONE
@@ -198,10 +223,11 @@ class Ingest:
 
     def rebuilt(self, new, stream):
         """The payloads just copied for the (frame, slot) pairs ``new`` become progressive payloads at the working depth: promoted first of
-        all, deblocked (``spec.deblock``), then made progressive.  Returns the pairs that now are (adaptive: the fields just rebuilt, not those
+        all, deblocked (``spec.deblock``), deringed (``spec.dering``), then made progressive.  Returns the pairs that now are (adaptive: the fields just rebuilt, not those
         uploaded)."""
         self.promote(new, stream)
         self.deblocked(new, stream)
+        self.deringed(new, stream)
         new = self._adaptive(new, stream) if self.adaptive else self.bob(new, stream)
         return self._denoise(new, stream) if self.denoise is not None else new
 

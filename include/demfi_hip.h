@@ -502,6 +502,27 @@ int demfi_payload_denoise(const uint8_t* src, int64_t src_bytes, const int64_t* 
 int demfi_payload_deblock(void* payloads, int64_t stride_bytes, int n, const int64_t* planes, int n_planes, int sample_bytes, int thr_a,
                           int thr_b, int thr_s, void* stream);
 
+/* ---- deringing of the Y4M edge (csrc/dering.hip; demfi_amd/video.py --dering) ----------------------------------------------------------
+ * payload_dering: the n (>= 0, any number) payloads at src + i*src_stride_bytes are deringed into dst + i*dst_stride_bytes, OUT OF PLACE: the
+ * two ranges must not overlap (sample_bytes = 1, or 2 for 16-bit little-endian samples: even addresses and strides).  planes: the plane
+ * table in HOST memory as for demfi_payload_deblock, n_planes (1..6) entries of six int64 each: first sample, rows, cols (1..16384 each),
+ * row pitch in samples (>= cols), x and y phase (0..7).  The entries must not share a sample.  Every entry is filtered as a plane in its own
+ * right by AV1's constrained directional enhancement filter: blocks of 8x8 start at column x when (x + x phase) % 8 == 0, rows likewise
+ * (the first and last block of an axis may be partial); a block's direction is the first of the greatest of 8 costs over x = min(v >>
+ * (depth - 8), 255) - 128 at positions clamped into the plane, its variance (cost[dir] - cost[dir ^ 4]) >> 10 scales the primary strength;
+ * a sample takes 4 primary taps along the direction (weights 4, 2) and 8 secondary taps along dir +- 2 (weights 2, 1), each through
+ * constrain(diff, thr, damping), rounds the sum / 16 to nearest, ties away from zero, and is clamped to the extremes of itself and its
+ * taps; taps outside the plane are skipped.  pri (0..15), sec (0..4) and damping (3..6) are at the 8-bit scale and depth (8, 10, 12, 14 or
+ * 16; above 8 needs sample_bytes = 2) shifts them inside.  Exact integers; the numpy definition is dering.dering_payload_np, matched byte
+ * for byte.  Every sample of every entry is written; where the entries do not name every sample up to the last one they reach, the
+ * payloads are copied first, so dst holds whole payloads.  Nothing between the payloads is read or written.
+ * DEMFI_ERR_ARG, with nothing launched: a NULL buffer, n < 0, sample_bytes not 1 or 2, a depth outside the list or above 8 in bytes, pri,
+ * sec or damping out of range, n_planes outside 1..6, a plane that starts below sample 0, a side outside 1..16384, a pitch below cols, a
+ * phase outside 0..7, 16-bit samples at an odd address or stride, a stride below the bytes the table reaches or so large that n of them
+ * leave int64, src and dst ranges that overlap.  One launch for all planes of all n payloads; n == 0 does nothing. */
+int demfi_payload_dering(const void* src, int64_t src_stride_bytes, void* dst, int64_t dst_stride_bytes, int n, const int64_t* planes,
+                         int n_planes, int sample_bytes, int depth, int pri, int sec, int damping, void* stream);
+
 /* ---- inverse telecine of the Y4M edge (csrc/ivtc.hip; demfi_amd/video.py --ivtc) ------------------------------------------------
  * A woven frame W(top, bot) has the even rows of the luma plane (the first h*w samples of a payload; sample_bytes = 1, or 2 for
  * 16-bit little-endian samples) of payload `top` and the odd rows of that of payload `bot`; it is read in place, never built.
