@@ -177,6 +177,7 @@ class WindowRunner:
         self.denoised = 0                            # temporal denoiser: frames denoised at ingest (``demfi_amd.denoise``)
         self.deblocked = 0                           # deblocking: payloads deblocked at ingest (``demfi_amd.deblock``)
         self.deringed = 0                            # deringing: payloads deringed at ingest (``demfi_amd.dering``)
+        self.debanded = 0                            # debanding: payloads debanded at ingest (``demfi_amd.deband``)
         self.grain_payloads = 0                     # film grain: payloads grained at egress (``y4m_edge.Grain``)
         self.colour_encoded = 0                      # linear light: payloads taken back to Y'CbCr (``y4m_edge.Encoder``)
         self.last_cuts = []                          # frames that start a scene, as the last run_clip_u8 with scene cuts found them
@@ -652,6 +653,9 @@ class WindowRunner:
         ``yuv.dering`` = (P, S, D) (None when absent; ``demfi_amd.dering``): every uploaded payload is deringed on the GPU behind the
         deblocker and in front of everything else (one device copy into a scratch buffer, then ``demfi_payload_dering`` back into place),
         on the same grid; goes with everything.
+        ``yuv.deband`` = (T, R) (None when absent; ``demfi_amd.deband``): every uploaded payload is debanded on the GPU behind the deringing
+        filter and in front of everything else (one device copy into the scratch buffer the deringing filter uses, then
+        ``demfi_payload_deband`` back into place); goes with everything.
         Returns the number of windows run."""
         spec = EdgeSpec.of(yuv)
         spec.check(self.retime is not None, window_index is not None, reuse_frames)

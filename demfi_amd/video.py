@@ -254,6 +254,27 @@ above and several ranks work.  Not offered: equality with libaom / dav1d output 
 plane searches its own direction, there is no skip map); strength from a quantiser; per-plane strengths; 4x4 chroma blocks; frame-DCT
 blocks of interlaced material; ``demfi_amd.clip``.  Without the switch no buffer, table, launch, copy or counter is added and every byte
 stays the same.
+
+``--deband [T[:R]]`` removes the third artefact of low-bitrate 8-bit input, banding, in front of the network (``demfi_amd.deband``): a sky, a
+wall or a fade arrives as plateaus one code apart; the promotion to the working depth is a pure shift and keeps the steps (4 codes at 10
+bits), the network sharpens a contour of one code like any other edge, and the egress can only bury it in grain.  The rule is a
+range-limited box mean (Lee's sigma filter with a hard threshold) in exact integers, on every plane as a plane in its own right: a sample
+becomes the mean, rounded to nearest, of the samples of its (2R + 1)^2 window that differ from it by less than T, the window clipped
+symmetrically about the sample at the plane's borders, so every affine plane comes back exactly and a step of T or more stays an edge.  T
+(0 .. 8) is in 8-bit steps, shifted to the working depth, R (1 .. 16) in samples, one pair for every plane; the default 2:16 has not been
+tuned against this network; T alone is T:16; ``--deband 0`` builds no stage.  At equal input and working depth a band of one code rounds
+back to itself: the switch wants ``--work-depth 10`` or more on 8-bit input (it is not refused without).  Bands narrower than about R / T
+come back unchanged, plateaus of 16 to 32 samples come back as ramps with steps of at most one code; fine detail within T is averaged like
+a band (``profiles/deband.md`` has the price).  The stage sits directly behind the deringing filter, H2D -> promote -> deblock -> dering ->
+deband -> bob / adaptive -> denoise -> frames, tiles, scene scores, dedup probe: per run of consecutive newly uploaded slots one device
+copy takes the payloads into the scratch buffer (the deringing filter's where both switches are given) and ONE launch (csrc/deband.hip
+``demfi_payload_deband``, byte for byte ``deband.deband_payload_np``) writes them back; a run with the switch writes the bytes of a run
+without it over the stream debanded on the host.  Under ``--deinterlace`` (either mode) each field of each plane is a plane of its own and R
+counts field rows.  The stage keeps nothing between payloads and needs no look-ahead: every switch above and several ranks work.  Not
+offered: debanding behind ``--denoise`` (that stage is deferred and has its own buffer); randomly placed reference samples in the manner of
+``f3kdb`` / ffmpeg's ``deband``; dither or grain at this stage (``--grain`` is the place); per-plane pairs; a radius above 16; bands narrower
+than about R / T; ``demfi_amd.clip``; numeric equality with any ffmpeg filter.  Without the switch no buffer, table, launch, copy or counter
+is added and every byte stays the same.
 """
 import os
 import sys
@@ -265,6 +286,7 @@ from . import _lib as L
 from . import bitdepth as BD
 from . import cadence as K
 from . import colour as CL
+from . import deband as BA
 from . import deblock as DB
 from . import deint as I
 from . import denoise as DN
@@ -307,15 +329,17 @@ class YuvEdge:
     in front of the weave (``demfi_amd.grain``); S16 = 0 is None.  ``deblock``: None, or (A, B) of the deblocking filter at the top of the ingest
     (``demfi_amd.deblock``); A = 0 is None.  ``crop_rect``: None, or the rectangle (top, bottom, left, right) the payloads handed in were cropped
     to out of their stream, which shifts the block grid of both.  ``dering``: None, or (P, S, D) of the deringing filter behind the deblocker
-    (``demfi_amd.dering``); P = S = 0 is None."""
+    (``demfi_amd.dering``); P = S = 0 is None.  ``deband``: None, or (T, R) of the debanding filter behind that (``demfi_amd.deband``); T = 0 is
+    None."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
                  fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None,
                  depths=None, shutter_window=None, denoise=None, linear_light=None, out_matrix=None, out_range=None, grain=None,
-                 deblock=None, crop_rect=None, dering=None):
+                 deblock=None, crop_rect=None, dering=None, deband=None):
         self.dedup, self.shutter = dedup, shutter
         self.deblock = check_deblock(deblock)
         self.dering = check_dering(dering)
+        self.deband = check_deband(deband)
         self.crop_rect = None if crop_rect is None else tuple(int(v) for v in crop_rect)
         self.grain = None if grain is None or not GR.check_params(grain)[0] else GR.check_params(grain)
         self.colour = check_colour(linear_light, out_matrix, out_range)
@@ -510,6 +534,23 @@ def check_dering(dering):
     return psd if psd[0] or psd[1] else None
 
 
+def check_deband(deband):
+    """The deband switch checked: None (off, or T = 0: no stage), or (T, R) of ``deband.check_params``.  ``deband``: None / False (off),
+    True (the defaults 2:16), T (T:16), (T, R) or a "T[:R]" string.  Goes with every other switch and any number of ranks."""
+    if deband is None or deband is False:
+        return None
+    if deband is True:
+        deband = BA.DEFAULTS
+    elif isinstance(deband, str):
+        deband = BA.parse_deband(deband)
+    elif isinstance(deband, int):
+        deband = (deband,)
+    if not isinstance(deband, (tuple, list)) or not 1 <= len(deband) <= 2:
+        raise ValueError('deband must be None, True, T, (T, R) or "T[:R]", got %r' % (deband,))
+    tr = BA.check_params(*deband)
+    return tr if tr[0] else None
+
+
 def check_grain(grain=None, size=None, chroma=None, curve=None, seed=None, world=1):
     """The grain switches checked: None (no ``grain``, or S = 0: no stage) or (S16, r, C16, curve, seed) of ``grain.check_grain``.  ``grain``:
     S as a number or a decimal string, 0 .. 8; ``size`` 0, 1 or 2 (None: 1); ``chroma`` C in 0 .. 1 (None: 0.5); ``curve`` 'film' / 'flat' (None:
@@ -527,7 +568,7 @@ COUNTERS = {'instants_run': None, 'instants_padded': None, 'shutter_mixed': None
 # and of the egress stages that came after: linear light (``y4m_edge.Encoder``), film grain (``y4m_edge.Grain``)
 EGRESS_COUNTERS = {'colour_encoded': 'last_colour_encoded', 'grain_payloads': 'last_grain_payloads'}
 # the counters of the ingest stages that came after those: kept the same way, in a table of their own
-INGEST_COUNTERS = {'denoised': 'last_denoised', 'deblocked': 'last_deblocked', 'deringed': 'last_deringed'}
+INGEST_COUNTERS = {'denoised': 'last_denoised', 'deblocked': 'last_deblocked', 'deringed': 'last_deringed', 'debanded': 'last_debanded'}
 
 
 AUTO_NEEDS_A_FILE = ('--crop auto needs a regular input file: the bars of a stream are known only at its end; give the four bar '
@@ -659,7 +700,14 @@ class VideoRunner:
     deblocker (``demfi_amd.dering``: AV1's CDEF; csrc/dering.hip ``demfi_payload_dering``, one device copy into a scratch buffer and ONE launch
     per run of uploaded slots), on the block grid of the uncropped stream, field by field under ``deinterlace``; everything behind runs on the
     deringed stream.  Goes with every other switch and any number of ranks.  ``dering=(0, 0)`` builds no stage.  After a run ``last_deringed``
-    = the payloads deringed.  Without it no buffer, table, launch, copy or counter is added and every byte stays the same."""
+    = the payloads deringed.  Without it no buffer, table, launch, copy or counter is added and every byte stays the same.  ``deband``: None
+    (default), True (2:16, not tuned against this network), T (T:16), (T, R) or a "T[:R]" string, T in 8-bit steps with 0 <= T <= 8, R in
+    samples with 1 <= R <= 16: bands are smoothed on the GPU directly behind the deringing filter (``demfi_amd.deband``: a range-limited box
+    mean; csrc/deband.hip ``demfi_payload_deband``, one device copy into a scratch buffer, shared with ``dering``, and ONE launch per run of
+    uploaded slots), field by field under ``deinterlace``; everything behind runs on the debanded stream.  It does its work at a working
+    depth above the input's (``work_depth=10`` or more on 8-bit input) and is not refused without.  Goes with every other switch and any
+    number of ranks.  ``deband=0`` builds no stage.  After a run ``last_debanded`` = the payloads debanded.  Without it no buffer, table,
+    launch, copy or counter is added and every byte stays the same."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
@@ -669,10 +717,11 @@ class VideoRunner:
                  shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, work_depth=None,
                  out_depth=None, dither=None, down=False, shutter_window=None, denoise=None, denoise_radius=None, linear_light=None,
                  out_matrix=None, out_range=None, grain=None, grain_size=None, grain_chroma=None, grain_curve=None, grain_seed=None,
-                 deblock=None, dering=None, **runner_kw):
+                 deblock=None, dering=None, deband=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
         self.deblock = check_deblock(deblock)            # (A, B) or None
         self.dering = check_dering(dering)               # (P, S, D) or None
+        self.deband = check_deband(deband)               # (T, R) or None
         self.grain = check_grain(grain, grain_size, grain_chroma, grain_curve, grain_seed)   # (S16, r, C16, curve, seed) or None
         self.last_grain = None
         self.colour = check_colour(linear_light, out_matrix, out_range, auto=True)   # (transfer, out matrix or 'auto', out full range) or None
@@ -1000,7 +1049,7 @@ class VideoRunner:
         return YuvEdge(self._in_matrix(hdr), hdr.full_range, hdr.chroma, with_s1,
                        self.scene_cut, self.full_length, depths[1], hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
                        *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths, shutter_window=self.shutter_window,
-                       denoise=self.denoise, grain=self.grain, deblock=self.deblock, dering=self.dering,
+                       denoise=self.denoise, grain=self.grain, deblock=self.deblock, dering=self.dering, deband=self.deband,
                        crop_rect=self.last_crop if self.deblock is not None or self.dering is not None else None, **kw)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
@@ -1333,6 +1382,15 @@ def parser():
                          'P alone means P:min((P+1)//2,4):5; 0:0 builds nothing.  With --deinterlace every field is filtered on its own; with '
                          '--crop the grid stays that of the uncropped stream.  Works with every other switch and any number of ranks.  '
                          'Off by default' % ((DR.MAX_P, DR.MAX_S, DR.MIN_D, DR.MAX_D) + DR.DEFAULTS))
+    ap.add_argument('--deband', nargs='?', type=_value_arg(BA.parse_deband), const=BA.DEFAULTS, default=None, metavar='T[:R]',
+                    help='smooth the bands of coarsely quantised input on the GPU, directly behind --dering and in front of everything else: '
+                         'every sample becomes the rounded mean of the samples of its (2R+1)x(2R+1) window that differ from it by less than T, '
+                         'in every plane; a step of T or more stays an edge and every even gradient comes back exactly.  T (0 .. %d) in 8-bit '
+                         'steps, R (%d .. %d) in samples, one pair for all planes; default %d:%d (not tuned against this network); T alone '
+                         'means T:16; 0 builds nothing.  Wants --work-depth 10 or more on 8-bit input: at equal input and working depth a band of '
+                         'one code rounds back to itself.  Bands narrower than about R/T stay.  With --deinterlace every field is filtered on its '
+                         'own.  Works with every other switch and any number of ranks.  Off by default'
+                         % ((BA.MAX_T, BA.MIN_R, BA.MAX_R) + BA.DEFAULTS))
     ap.add_argument('--denoise-radius', type=int, default=None, metavar='R',
                     help='with --denoise: the frames looked at on each side, 1 .. %d (default %d); costs R frames of lookahead, 2 R fields '
                          'behind --deinterlace' % (DN.MAX_RADIUS, DN.DEFAULT_RADIUS))
@@ -1397,6 +1455,7 @@ def main(argv=None):
         check_denoise(a.denoise, a.denoise_radius, a.dedup or None, a.deinterlace_mode)
         check_deblock(a.deblock)
         check_dering(a.dering)
+        check_deband(a.deband)
         check_colour(a.linear_light, a.out_matrix, a.out_range, auto=True)
         grain = check_grain(a.grain, a.grain_size, a.grain_chroma, a.grain_curve, a.grain_seed)
     except ValueError as e:
@@ -1408,7 +1467,7 @@ def main(argv=None):
                                     ('denoise_radius', a.denoise_radius), ('linear_light', a.linear_light), ('out_matrix', a.out_matrix),
                                     ('out_range', a.out_range), ('grain', a.grain), ('grain_size', a.grain_size),
                                     ('grain_chroma', a.grain_chroma), ('grain_curve', a.grain_curve), ('grain_seed', a.grain_seed),
-                                    ('deblock', a.deblock), ('dering', a.dering))
+                                    ('deblock', a.deblock), ('dering', a.dering), ('deband', a.deband))
                   if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     try:
@@ -1456,8 +1515,8 @@ def main(argv=None):
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
     counts = [float(nw), float(nf), float(vr.last_st_frames), float(vr.last_instants[0]), float(vr.last_instants[1]),
               float(vr.last_cut_windows), float(vr.last_depth_promoted), float(vr.last_depth_requantised), float(vr.last_denoised), float(vr.last_deblocked),
-              float(vr.last_deringed)]
-    tw, tf, tst, ti, tp, tc, tdp, tdq, tdn, tdb, tdr = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
+              float(vr.last_deringed), float(vr.last_debanded)]
+    tw, tf, tst, ti, tp, tc, tdp, tdq, tdn, tdb, tdr, tba = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
     if rank == 0:
         if a.crop is not None:
             print('demfi_amd.video: ' + vr.crop_report(), file=sys.stderr)
@@ -1477,6 +1536,8 @@ def main(argv=None):
             extra['deblock'] = {'a': a.deblock[0], 'b': a.deblock[1], 'payloads': int(tdb)}
         if a.dering is not None:
             extra['dering'] = {'p': a.dering[0], 's': a.dering[1], 'd': a.dering[2], 'payloads': int(tdr)}
+        if a.deband is not None:
+            extra['deband'] = {'t': a.deband[0], 'r': a.deband[1], 'payloads': int(tba)}
         if a.scale is not None:
             extra['scale'] = {'size': '%dx%d' % vr.scale[:2], 'filter': vr.scale[2], 'resized': vr.last_scale is not None,
                               'payloads': vr.last_scale_payloads}

@@ -17,6 +17,7 @@ import torch
 from . import _lib as L
 from . import cadence as K
 from . import colour as CL
+from . import deband as BA
 from . import deblock as DB
 from . import deint as I
 from . import denoise as DN
@@ -122,10 +123,15 @@ class Ingest:
     ``spec.dering`` = (P, S, D) (``demfi_amd.dering``): behind the deblocker and in front of everything else that reads yuv_in.  The filter
     reads a halo of unfiltered samples and cannot work in place: per run of consecutive newly uploaded slots ONE device copy takes the run's
     payloads into ``dr_scratch`` (shaped like yuv_in) and ONE ``demfi_payload_dering`` launch writes them back into yuv_in deringed, every plane
-    (every field of every plane) of ``deblock.plane_table`` on the same grid.  Nothing is kept between payloads; the runner counts ``deringed``."""
+    (every field of every plane) of ``deblock.plane_table`` on the same grid.  Nothing is kept between payloads; the runner counts ``deringed``.
+    ``spec.deband`` = (T, R) (``demfi_amd.deband``): directly behind the deringing filter, in the same manner: per run of consecutive newly
+    uploaded slots ONE device copy into ``bd_scratch`` and ONE ``demfi_payload_deband`` launch back into yuv_in.  With both switches
+    ``bd_scratch`` IS ``dr_scratch``: the two stages run in order on the ingest stream, so one buffer serves both.  The phases of the plane
+    table are carried and ignored.  Nothing is kept between payloads; the runner counts ``debanded``."""
     denoise = clean = None                           # without --denoise: no buffer, table or launch
     deblock = None                                   # without --deblock: no table, launch or counter
     dering = None                                    # without --dering: no buffer, table, launch, copy or counter
+    deband = None                                    # without --deband: no buffer, table, launch, copy or counter
 
     def __init__(self, runner, slots, spec, h, w, tiler=None):
         self.rn, self.slots, self.tiler, self.fh, self.fw = runner, slots, tiler, h, w
@@ -147,7 +153,10 @@ class Ingest:
         if spec.dering is not None:                  # the strengths at the 8-bit scale and the depth; the scratch the launch reads
             self.dering = (spec.depth,) + DR.check_params(*spec.dering)
             self.dr_scratch = torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev)
-        if self.deblock is not None or self.dering is not None:
+        if spec.deband is not None:                  # depth, T at the 8-bit scale, R; the scratch is the deringing filter's where there is one
+            self.deband = (spec.depth,) + BA.check_params(*spec.deband)
+            self.bd_scratch = self.dr_scratch if self.dering is not None else torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev)
+        if self.deblock is not None or self.dering is not None or self.deband is not None:
             self.attach(None)
         # a working depth above the input's (``spec.depths``, ``demfi_amd.bitdepth``): payloads are copied into ``staged`` at the input's sample
         # size, so H2D carries the input's bytes, and ``promote`` writes them into yuv_in at the working depth before anything else reads them
@@ -175,6 +184,9 @@ class Ingest:
         if self.dering is not None:
             self.dr_planes = np.ascontiguousarray(DB.plane_table(self.fh, self.fw, self.layout, self.fields, getattr(yuv, 'crop_rect', None)),
                                                   dtype=np.int64)
+        if self.deband is not None:
+            self.bd_planes = np.ascontiguousarray(DB.plane_table(self.fh, self.fw, self.layout, self.fields, getattr(yuv, 'crop_rect', None)),
+                                                  dtype=np.int64)
 
     def deblocked(self, new, stream):
         """The payloads just copied (and promoted) for the (frame, slot) pairs ``new`` are deblocked in place: ONE ``demfi_payload_deblock``
@@ -197,6 +209,19 @@ class Ingest:
                                                      self.dr_planes.ctypes.data, len(self.dr_planes), self.es, *self.dering,
                                                      stream.cuda_stream), 'payload_dering')
         self.rn.deringed += len(new)
+
+    def debanded(self, new, stream):
+        """The payloads just copied (promoted, deblocked, deringed) for the (frame, slot) pairs ``new`` are debanded: per run of consecutive
+        slots ONE device copy into the scratch on the ingest stream, then ONE ``demfi_payload_deband`` launch from the scratch back into
+        yuv_in."""
+        if self.deband is None or not new:
+            return
+        for s0, cnt in consecutive([sl for _, sl in new]):
+            self.bd_scratch[s0:s0 + cnt].copy_(self.yuv_in[s0:s0 + cnt], non_blocking=True)
+            L.check(self.rn.lib.demfi_payload_deband(self.bd_scratch[s0].data_ptr(), self.Pb, self.yuv_in[s0].data_ptr(), self.Pb, cnt,
+                                                     self.bd_planes.ctypes.data, len(self.bd_planes), self.es, *self.deband,
+                                                     stream.cuda_stream), 'payload_deband')
+        self.rn.debanded += len(new)
 
     def promote(self, new, stream):
         """The payloads just copied for the (frame, slot) pairs ``new`` go from ``staged`` to yuv_in at the working depth: ONE
@@ -223,11 +248,12 @@ class Ingest:
 
     def rebuilt(self, new, stream):
         """The payloads just copied for the (frame, slot) pairs ``new`` become progressive payloads at the working depth: promoted first of
-        all, deblocked (``spec.deblock``), deringed (``spec.dering``), then made progressive.  Returns the pairs that now are (adaptive: the fields just rebuilt, not those
+        all, deblocked (``spec.deblock``), deringed (``spec.dering``), debanded (``spec.deband``), then made progressive.  Returns the pairs that now are (adaptive: the fields just rebuilt, not those
         uploaded)."""
         self.promote(new, stream)
         self.deblocked(new, stream)
         self.deringed(new, stream)
+        self.debanded(new, stream)
         new = self._adaptive(new, stream) if self.adaptive else self.bob(new, stream)
         return self._denoise(new, stream) if self.denoise is not None else new
 

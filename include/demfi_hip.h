@@ -523,6 +523,26 @@ int demfi_payload_deblock(void* payloads, int64_t stride_bytes, int n, const int
 int demfi_payload_dering(const void* src, int64_t src_stride_bytes, void* dst, int64_t dst_stride_bytes, int n, const int64_t* planes,
                          int n_planes, int sample_bytes, int depth, int pri, int sec, int damping, void* stream);
 
+/* ---- debanding of the Y4M edge (csrc/deband.hip; demfi_amd/video.py --deband) -------------------------------------------------------------
+ * payload_deband: the n (>= 0, any number) payloads at src + i*src_stride_bytes are debanded into dst + i*dst_stride_bytes, OUT OF PLACE: the
+ * two ranges must not overlap (sample_bytes = 1, or 2 for 16-bit little-endian samples: even addresses and strides).  planes: the plane
+ * table in HOST memory as for demfi_payload_dering, n_planes (1..6) entries of six int64 each: first sample, rows, cols (1..16384 each),
+ * row pitch in samples (>= cols), x and y phase (0..7; checked, carried and ignored: banding has no grid).  The entries must not share a
+ * sample.  Every entry is filtered as a plane in its own right by a range-limited box mean: for a sample c at (x, y), rx = min(radius, x,
+ * cols - 1 - x), ry = min(radius, y, rows - 1 - y) (the window is clipped symmetrically about the sample and never leaves the plane), N =
+ * the samples v of the source at (x + i, y + j), |i| <= rx, |j| <= ry, with |v - c| < thr8 << (depth - 8), n = |N| >= 1, out =
+ * (2 sum(N) + n) / (2 n) floored: the mean of the near samples rounded to nearest, ties up.  thr8 (0..8) is at the 8-bit scale, radius
+ * (1..16) in samples; depth is 8, 10, 12, 14 or 16 (above 8 needs sample_bytes = 2).  Exact integers; the numpy definition is
+ * deband.deband_payload_np, matched byte for byte.  thr8 == 0 copies the payloads.  Every sample of every entry is written; where the
+ * entries do not name every sample up to the last one they reach, the payloads are copied first, so dst holds whole payloads.  Nothing
+ * between the payloads is read or written.
+ * DEMFI_ERR_ARG, with nothing launched: a NULL buffer, n < 0, sample_bytes not 1 or 2, a depth outside the list or above 8 in bytes, thr8
+ * or radius out of range, n_planes outside 1..6, a plane that starts below sample 0, a side outside 1..16384, a pitch below cols, a phase
+ * outside 0..7, 16-bit samples at an odd address or stride, a stride below the bytes the table reaches or so large that n of them leave
+ * int64, src and dst ranges that overlap.  One launch for all planes of all n payloads; n == 0 does nothing. */
+int demfi_payload_deband(const void* src, int64_t src_stride_bytes, void* dst, int64_t dst_stride_bytes, int n, const int64_t* planes,
+                         int n_planes, int sample_bytes, int depth, int thr8, int radius, void* stream);
+
 /* ---- inverse telecine of the Y4M edge (csrc/ivtc.hip; demfi_amd/video.py --ivtc) ------------------------------------------------
  * A woven frame W(top, bot) has the even rows of the luma plane (the first h*w samples of a payload; sample_bytes = 1, or 2 for
  * 16-bit little-endian samples) of payload `top` and the odd rows of that of payload `bot`; it is read in place, never built.
