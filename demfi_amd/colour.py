@@ -26,7 +26,8 @@ payload as a flat array of 16-bit samples and the scaler (``scale.scale_payload_
 
 ``resolve`` gives the matrix and range a stream leaves with.  Every written sample is made from a BGR frame by the gather (or the encode
 stage), which takes a matrix and a range: binding those to other values than the input's is all ``--out-matrix`` / ``--out-range`` do.
-Not defined here: primaries / gamut conversion, PQ and HLG, working depths 14 and 16."""
+Not defined here: primaries / gamut conversion, PQ and HLG (``--lut`` applies a user's cube that holds them, ``demfi_amd.lut3d``), working
+depths 14 and 16."""
 import numpy as np
 
 from . import scale as SC

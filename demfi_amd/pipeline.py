@@ -25,6 +25,7 @@ from . import deint as I
 from . import denoise as DN
 from . import grain as GR
 from . import interlace as IL
+from . import lut3d as LU
 from . import retime as R
 from . import scale as SC
 from . import scene as S
@@ -62,9 +63,11 @@ class EdgeSpec(_EdgeFields):
     kept beside the tuple like ``denoise`` and ``colour``; S16 = 0 is None.  ``deblock``: None or (A, B) of the deblocking filter at the top of the
     ingest (``demfi_amd.deblock``: thresholds at the 8-bit scale), kept beside the tuple like ``denoise``; A = 0, the identity, is None.  ``dering``: None or (P, S, D) of the deringing filter behind the deblocker
     (``demfi_amd.dering``: strengths at the 8-bit scale), kept beside the tuple like ``deblock``; P = S = 0, the identity, is None.  ``deband``: None or (T, R) of the debanding filter behind the deringing filter
-    (``demfi_amd.deband``: threshold at the 8-bit scale, radius in samples), kept beside the tuple like ``dering``; T = 0, the identity, is None.  ``reach``: how far the frames an ingest stage reads lie from the frame it writes.
+    (``demfi_amd.deband``: threshold at the 8-bit scale, radius in samples), kept beside the tuple like ``dering``; T = 0, the identity, is None.
+    ``lut``: None or the ``lut3d.Cube`` of the 3D colour LUT applied between the scaler and the encode (``demfi_amd.lut3d``), kept beside the tuple
+    like ``grain``; it compares and hashes by its size and its quantised numbers.  ``reach``: how far the frames an ingest stage reads lie from the frame it writes.
     Hashable: (batch, spec) is what a cached ``ClipPipeline`` can be reused for.
-    ``shutter``, ``interlace``, ``scale``, ``depths``, ``shutter_window``, ``denoise``, ``colour``, ``grain``, ``deblock``, ``dering`` and ``deband`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
+    ``shutter``, ``interlace``, ``scale``, ``depths``, ``shutter_window``, ``denoise``, ``colour``, ``grain``, ``deblock``, ``dering``, ``deband`` and ``lut`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
     without them is, item for item, the record it was before there were any, and one with any of them equals no plain tuple.  What the namedtuple makes
     from its items alone does not know them: ``_make``, ``_asdict`` and pickling drop them; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
     shutter = None
@@ -78,10 +81,13 @@ class EdgeSpec(_EdgeFields):
     deblock = None
     dering = None
     deband = None
+    lut = None
 
     def __new__(cls, *args, shutter=None, interlace=None, scale=None, depths=None, shutter_window=None, denoise=None, colour=None, grain=None,
-                deblock=None, dering=None, deband=None, **kw):
+                deblock=None, dering=None, deband=None, lut=None, **kw):
         self = super().__new__(cls, *args, **kw)
+        if lut is not None:
+            self.lut = lut
         if deband is not None and int(deband[0]) != 0:                    # T = 0 changes nothing: the spec without the field
             self.deband = tuple(int(v) for v in deband)
         if dering is not None and (int(dering[0]) != 0 or int(dering[1]) != 0):     # P = S = 0 changes nothing: the spec without the field
@@ -110,9 +116,9 @@ class EdgeSpec(_EdgeFields):
         shutter, interlace, scale = kw.pop('shutter', self.shutter), kw.pop('interlace', self.interlace), kw.pop('scale', self.scale)
         depths, window, denoise = kw.pop('depths', self.depths), kw.pop('shutter_window', self.shutter_window), kw.pop('denoise', self.denoise)
         colour, grain, deblock = kw.pop('colour', self.colour), kw.pop('grain', self.grain), kw.pop('deblock', self.deblock)
-        dering, deband = kw.pop('dering', self.dering), kw.pop('deband', self.deband)
+        dering, deband, lut = kw.pop('dering', self.dering), kw.pop('deband', self.deband), kw.pop('lut', self.lut)
         return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace, scale=scale, depths=depths, shutter_window=window,
-                          denoise=denoise, colour=colour, grain=grain, deblock=deblock, dering=dering, deband=deband)
+                          denoise=denoise, colour=colour, grain=grain, deblock=deblock, dering=dering, deband=deband, lut=lut)
 
     def __eq__(self, other):
         return (tuple.__eq__(self, other) is True and self.shutter == getattr(other, 'shutter', None)
@@ -120,7 +126,8 @@ class EdgeSpec(_EdgeFields):
                 and self.depths == getattr(other, 'depths', None) and self.shutter_window == getattr(other, 'shutter_window', None)
                 and self.denoise == getattr(other, 'denoise', None) and self.colour == getattr(other, 'colour', None)
                 and self.grain == getattr(other, 'grain', None) and self.deblock == getattr(other, 'deblock', None)
-                and self.dering == getattr(other, 'dering', None) and self.deband == getattr(other, 'deband', None))
+                and self.dering == getattr(other, 'dering', None) and self.deband == getattr(other, 'deband', None)
+                and self.lut == getattr(other, 'lut', None))
 
     def __ne__(self, other):
         return not self == other
@@ -135,7 +142,8 @@ class EdgeSpec(_EdgeFields):
         key = key if self.grain is None else key + ('grain', self.grain)
         key = key if self.deblock is None else key + ('deblock', self.deblock)
         key = key if self.dering is None else key + ('dering', self.dering)
-        return hash(key if self.deband is None else key + ('deband', self.deband))
+        key = key if self.deband is None else key + ('deband', self.deband)
+        return hash(key if self.lut is None else key + ('lut', self.lut))
 
     def __repr__(self):
         return super().__repr__()[:-1] + ', shutter=%r%s%s)' % (self.shutter, ', interlace=%r' % (self.interlace,) if self.interlace is not None else '',
@@ -147,7 +155,8 @@ class EdgeSpec(_EdgeFields):
                                                                + (', grain=%r' % (self.grain,) if self.grain is not None else '')
                                                                + (', deblock=%r' % (self.deblock,) if self.deblock is not None else '')
                                                                + (', dering=%r' % (self.dering,) if self.dering is not None else '')
-                                                               + (', deband=%r' % (self.deband,) if self.deband is not None else ''))
+                                                               + (', deband=%r' % (self.deband,) if self.deband is not None else '')
+                                                               + (', lut=%r' % (self.lut,) if self.lut is not None else ''))
 
     @classmethod
     def of(cls, yuv):
@@ -159,7 +168,7 @@ class EdgeSpec(_EdgeFields):
                    interlace=getattr(yuv, 'interlace', None), scale=getattr(yuv, 'scale', None), depths=getattr(yuv, 'depths', None),
                    shutter_window=getattr(yuv, 'shutter_window', None), denoise=getattr(yuv, 'denoise', None), colour=getattr(yuv, 'colour', None),
                    grain=getattr(yuv, 'grain', None), deblock=getattr(yuv, 'deblock', None),
-                   dering=getattr(yuv, 'dering', None), deband=getattr(yuv, 'deband', None))
+                   dering=getattr(yuv, 'dering', None), deband=getattr(yuv, 'deband', None), lut=getattr(yuv, 'lut', None))
 
     hi = property(lambda self: self.depth > 8, doc='16-bit frames: the samples of a stream above 8 bits')
     reach = property(lambda self: DN.reach(self.denoise[2], self.fields is not None) if self.denoise is not None
@@ -177,7 +186,7 @@ class EdgeSpec(_EdgeFields):
         other, edge_only = self.deint_mode != 'bob', self.hi or self.dedup is not None or self.fields is not None
         deint = deint_conflict(self.deint_mode, self.fields is not None, self.dedup is not None)
         sh, il, sc, dp, win, dn, co = self.shutter, self.interlace, self.scale, self.depths, self.shutter_window, self.denoise, self.colour
-        gr, db, dr, bd = self.grain, self.deblock, self.dering, self.deband
+        gr, db, dr, bd, lu = self.grain, self.deblock, self.dering, self.deband, self.lut
         for bad, what in ((self.fields not in (None, 't', 'b'), "fields must be None, 't' or 'b', got %r" % (self.fields,)),
                           (deint, 'deint_mode %r with fields=%r, dedup=%r' % (self.deint_mode, self.fields, self.dedup)),
                           (edge_only and not self.y4m, '16-bit frames, repeated frames and fields are those of the Y4M edge (yuv=...) only'),
@@ -232,7 +241,12 @@ class EdgeSpec(_EdgeFields):
                           (dr is not None and not (retimed and self.y4m), 'deringing needs the Y4M edge on a retimed runner'),
                           (bd is not None and not (len(bd) == 2 and 0 <= bd[0] <= 8 and 1 <= bd[1] <= 16),
                            'deband must be None or (T, R) with 0 <= T <= 8, 1 <= R <= 16, got %r' % (bd,)),
-                          (bd is not None and not (retimed and self.y4m), 'debanding needs the Y4M edge on a retimed runner')):
+                          (bd is not None and not (retimed and self.y4m), 'debanding needs the Y4M edge on a retimed runner'),
+                          (lu is not None and not isinstance(lu, LU.Cube), 'lut must be None or a lut3d.Cube, got %r' % (lu,)),
+                          (lu is not None and not (retimed and self.y4m), 'a 3D LUT needs the Y4M edge on a retimed runner'),
+                          (lu is not None and self.depth > LU.MAX_DEPTH,
+                           'a 3D LUT needs a working depth of at most %d bits, got %d: the gather in front of it keeps its table of at most %d '
+                           'entries in LDS' % (LU.MAX_DEPTH, self.depth, 1 << LU.MAX_DEPTH))):
             if bad:
                 raise ValueError('WindowRunner.run_clip_u8: ' + what)
 

@@ -179,6 +179,7 @@ class WindowRunner:
         self.deringed = 0                            # deringing: payloads deringed at ingest (``demfi_amd.dering``)
         self.debanded = 0                            # debanding: payloads debanded at ingest (``demfi_amd.deband``)
         self.grain_payloads = 0                     # film grain: payloads grained at egress (``y4m_edge.Grain``)
+        self.lut_payloads = 0                       # 3D colour LUT: payloads taken through the cube at egress (``y4m_edge.Lut``)
         self.colour_encoded = 0                      # linear light: payloads taken back to Y'CbCr (``y4m_edge.Encoder``)
         self.last_cuts = []                          # frames that start a scene, as the last run_clip_u8 with scene cuts found them
 

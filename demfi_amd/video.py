@@ -275,6 +275,23 @@ offered: debanding behind ``--denoise`` (that stage is deferred and has its own 
 ``f3kdb`` / ffmpeg's ``deband``; dither or grain at this stage (``--grain`` is the place); per-plane pairs; a radius above 16; bands narrower
 than about R / T; ``demfi_amd.clip``; numeric equality with any ffmpeg filter.  Without the switch no buffer, table, launch, copy or counter
 is added and every byte stays the same.
+
+``--lut FILE.cube`` applies a user's 3D colour LUT to every payload written (``demfi_amd.lut3d``): the edge's colour side stops at two
+transfer curves and two matrices, and a cube covers HDR10 or HLG to SDR, BT.2020 to BT.709, camera log to display, a legaliser or a look
+without the project defining any of them.  With the switch the egress runs on RGB payloads (uint16 [3, h, w], the format of
+``--linear-light``) whether or not the run is in linear light: gather-to-RGB -> mix -> scale -> lut -> encode -> grain -> weave -> requant
+-> D2H.  The gather writes through ``colour.forward_table`` in linear light and through ``lut3d.code_table`` otherwise, the LUT reads through
+the inverse of that same table and writes 16-bit encoded values, the encode reads those through ``inverse_table(code_table)``;
+``demfi_bgr_to_linear_gather`` and ``demfi_linear_to_yuv`` are reused unchanged.  ONE launch per batch (csrc/lut3d.hip ``demfi_rgb_lut3d``, byte
+for byte ``lut3d.lut_payload_np``): tetrahedral interpolation in exact integers, the cube quantised to 16 bits (values outside [0, 1]
+clipped).  An identity cube of any size returns every code, so a run without ``--shutter`` and ``--scale`` writes the bytes of the run without
+the switch.  ``--out-matrix`` and ``--out-range`` bind the encode as before; ``--crop-output pad`` pads behind D2H, so the bars stay exact
+black whatever the cube does to black.  Stateless per payload: any number of ranks.  Refused before anything is allocated: a file that does
+not parse (with its line) and a working depth above 12 bits (the gather keeps its table of at most 4096 entries in LDS, as for
+``--linear-light``; see ``--work-depth``).  Not offered: a LUT in front of the network (log or HDR sources), 1D and shaper LUTs, domains
+other than 0 .. 1, trilinear interpolation, other file formats, a transfer or primaries tag in the header (Y4M has none), working depths
+14 and 16, ``demfi_amd.clip``, numeric equality with ffmpeg's ``lut3d`` or OCIO.  Without the switch no buffer, table, launch or counter is
+added and every byte stays the same.
 """
 import os
 import sys
@@ -295,6 +312,7 @@ from . import dist as D
 from . import grain as GR
 from . import interlace as IL
 from . import letterbox as LB
+from . import lut3d as LU
 from . import retime as R
 from . import scale as SC
 from . import scene as S
@@ -330,13 +348,15 @@ class YuvEdge:
     (``demfi_amd.deblock``); A = 0 is None.  ``crop_rect``: None, or the rectangle (top, bottom, left, right) the payloads handed in were cropped
     to out of their stream, which shifts the block grid of both.  ``dering``: None, or (P, S, D) of the deringing filter behind the deblocker
     (``demfi_amd.dering``); P = S = 0 is None.  ``deband``: None, or (T, R) of the debanding filter behind that (``demfi_amd.deband``); T = 0 is
-    None."""
+    None.  ``lut``: None, or the ``lut3d.Cube`` (or the path of a ``.cube`` file) of the 3D colour LUT applied between the scaler and the encode
+    (``demfi_amd.lut3d``)."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
                  fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None,
                  depths=None, shutter_window=None, denoise=None, linear_light=None, out_matrix=None, out_range=None, grain=None,
-                 deblock=None, crop_rect=None, dering=None, deband=None):
+                 deblock=None, crop_rect=None, dering=None, deband=None, lut=None):
         self.dedup, self.shutter = dedup, shutter
+        self.lut = check_lut(lut)
         self.deblock = check_deblock(deblock)
         self.dering = check_dering(dering)
         self.deband = check_deband(deband)
@@ -551,6 +571,17 @@ def check_deband(deband):
     return tr if tr[0] else None
 
 
+def check_lut(lut=None, work_depth=None):
+    """The LUT switch checked: None, or the ``lut3d.Cube`` of ``lut`` -- a ``Cube`` as it is, else the path of a ``.cube`` file, read and parsed
+    here (ValueError with the file's name and the line for one that does not parse).  ``work_depth``: the working depth where it is known;
+    above 12 bits it is refused in ``lut3d.check_depth``'s words, which point to ``--work-depth``."""
+    if lut is None:
+        return None
+    if work_depth is not None:
+        LU.check_depth(work_depth)
+    return lut if isinstance(lut, LU.Cube) else LU.load_cube(os.fspath(lut))
+
+
 def check_grain(grain=None, size=None, chroma=None, curve=None, seed=None, world=1):
     """The grain switches checked: None (no ``grain``, or S = 0: no stage) or (S16, r, C16, curve, seed) of ``grain.check_grain``.  ``grain``:
     S as a number or a decimal string, 0 .. 8; ``size`` 0, 1 or 2 (None: 1); ``chroma`` C in 0 .. 1 (None: 0.5); ``curve`` 'film' / 'flat' (None:
@@ -565,8 +596,8 @@ def check_grain(grain=None, size=None, chroma=None, curve=None, seed=None, world
 COUNTERS = {'instants_run': None, 'instants_padded': None, 'shutter_mixed': None, 'cut_windows': 'last_cut_windows',
             'shutter_carried': 'last_shutter_carried', 'interlace_carried': 'last_interlace_carried', 'scale_payloads': 'last_scale_payloads',
             'depth_promoted': 'last_depth_promoted', 'depth_requantised': 'last_depth_requantised'}
-# and of the egress stages that came after: linear light (``y4m_edge.Encoder``), film grain (``y4m_edge.Grain``)
-EGRESS_COUNTERS = {'colour_encoded': 'last_colour_encoded', 'grain_payloads': 'last_grain_payloads'}
+# and of the egress stages that came after: linear light (``y4m_edge.Encoder``), film grain (``y4m_edge.Grain``), the 3D LUT (``y4m_edge.Lut``)
+EGRESS_COUNTERS = {'colour_encoded': 'last_colour_encoded', 'grain_payloads': 'last_grain_payloads', 'lut_payloads': 'last_lut_payloads'}
 # the counters of the ingest stages that came after those: kept the same way, in a table of their own
 INGEST_COUNTERS = {'denoised': 'last_denoised', 'deblocked': 'last_deblocked', 'deringed': 'last_deringed', 'debanded': 'last_debanded'}
 
@@ -689,7 +720,11 @@ class VideoRunner:
     ``grain_chroma`` C in 0 .. 1 (None: 0.5), ``grain_curve`` 'film' / 'flat' (None: 'film'), ``grain_seed`` a uint32 (None: 0); any of the four
     without ``grain`` is an error.  One rank (``run_file`` refuses more).  ``grain=0`` builds no stage.  After a run ``last_grain`` = (S16,
     r, C16, curve, seed) or None and ``last_grain_payloads`` = the payloads grained.  Without it no buffer, table, launch or stream is added
-    and every byte stays the same.  ``deblock``: None (default), True (the thresholds 16:4), A (A : (A + 3) // 4), (A, B) or an "A[:B]" string,
+    and every byte stays the same.  ``lut``: None (default), the path of a ``.cube`` file or a ``lut3d.Cube``: a 3D colour LUT applied on the GPU to every
+    payload written, between the scaler and the encode (``demfi_amd.lut3d``; csrc/lut3d.hip ``demfi_rgb_lut3d``, ONE launch per batch); the
+    egress then runs on RGB payloads whether or not the run is in linear light.  A file that does not parse and a working depth above 12
+    bits are refused, the latter at construction where ``work_depth`` says so and else once the header is known.  Any number of ranks.
+    After a run ``last_lut`` = the cube or None and ``last_lut_payloads`` = the payloads taken through it.  ``deblock``: None (default), True (the thresholds 16:4), A (A : (A + 3) // 4), (A, B) or an "A[:B]" string,
     at the 8-bit scale with 0 <= B <= A <= 255: the block edges of every uploaded payload are smoothed in place on the GPU at the top of the
     ingest (``demfi_amd.deblock``, csrc/deblock.hip ``demfi_payload_deblock``, ONE launch per run of uploaded slots), on the grid of 8 of the
     uncropped stream (``crop`` gives the phases), field by field under ``deinterlace``; everything behind runs on the deblocked stream.  Goes
@@ -717,8 +752,10 @@ class VideoRunner:
                  shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, work_depth=None,
                  out_depth=None, dither=None, down=False, shutter_window=None, denoise=None, denoise_radius=None, linear_light=None,
                  out_matrix=None, out_range=None, grain=None, grain_size=None, grain_chroma=None, grain_curve=None, grain_seed=None,
-                 deblock=None, dering=None, deband=None, **runner_kw):
+                 deblock=None, dering=None, deband=None, lut=None, **runner_kw):
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
+        self.lut = check_lut(lut)                        # a ``lut3d.Cube`` or None
+        self.last_lut = None
         self.deblock = check_deblock(deblock)            # (A, B) or None
         self.dering = check_dering(dering)               # (P, S, D) or None
         self.deband = check_deband(deband)               # (T, R) or None
@@ -729,6 +766,7 @@ class VideoRunner:
         self.denoise = check_denoise(denoise, denoise_radius, dedup, deinterlace_mode)   # (A, B, R) or None
         self.down = bool(down)
         self.work_depth, self.out_depth, self.dither = check_depths(work_depth, out_depth, dither)
+        check_lut(self.lut, self.work_depth)             # a working depth above 12 bits is refused here where the switch names it
         self.scale = check_scale(scale, scale_filter, crop, crop_output)  # (w, h, filter) or None
         self.interlace = check_interlace(interlace, interlace_lowpass)    # (order, low-pass mode) or None
         self.shutter = check_shutter(shutter, shutter_samples, dedup)     # (S, D) or None
@@ -991,6 +1029,7 @@ class VideoRunner:
                              '--tile-high-depth (tile_high_depth=True)' % (self.tile, what, 'convert the input to 8 bits' if work == d_in
                                                                            else 'work at 8 bits'))
         self._colour_of(hdr)                         # linear light above 12 bits is refused here
+        check_lut(self.lut, work)                    # and so is a LUT
         self.last_depths = None if BD.is_noop(depths) else depths
         self.last_depth, self.last_layout = out, hdr.layout
 
@@ -1041,6 +1080,7 @@ class VideoRunner:
         self.last_st_frames = added['shutter_mixed'] if self.shutter is not None else st_frames     # the fine frames that went into the mixes
         self.last_shutter, self.last_scale, self.last_shutter_window = self.shutter, self._scale_of(hdr), self.shutter_window
         self.last_interlace, self.last_grain = self.interlace[0] if self.interlace is not None else None, self.grain
+        self.last_lut = self.lut
 
     def _edge(self, hdr, with_s1, order=None):
         depths = self._depths_of(hdr)                # hdr has the input's depth; the edge works at depths[1]
@@ -1049,7 +1089,7 @@ class VideoRunner:
         return YuvEdge(self._in_matrix(hdr), hdr.full_range, hdr.chroma, with_s1,
                        self.scene_cut, self.full_length, depths[1], hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
                        *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths, shutter_window=self.shutter_window,
-                       denoise=self.denoise, grain=self.grain, deblock=self.deblock, dering=self.dering, deband=self.deband,
+                       denoise=self.denoise, grain=self.grain, deblock=self.deblock, dering=self.dering, deband=self.deband, lut=self.lut,
                        crop_rect=self.last_crop if self.deblock is not None or self.dering is not None else None, **kw)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
@@ -1424,6 +1464,12 @@ def parser():
                          'and white; flat is the same everywhere')
     ap.add_argument('--grain-seed', type=_value_arg(GR.parse_seed), default=None, metavar='N',
                     help='with --grain: a 32-bit seed (default 0); the same seed gives the same bytes')
+    ap.add_argument('--lut', default=None, metavar='FILE.cube',
+                    help='apply a 3D colour LUT (Adobe / Resolve .cube, LUT_3D_SIZE 2 .. 65, domain 0 .. 1) on the GPU to every frame written: '
+                         'HDR10 or HLG to SDR, BT.2020 to BT.709, camera log to display, a legaliser or a look, all as data.  Tetrahedral '
+                         'interpolation in exact integers over R\'G\'B\' at full chroma resolution and the working depth (8, 10 or 12 bits, see '
+                         '--work-depth), behind --shutter and --scale and in front of the encode (--out-matrix, --out-range), --grain, '
+                         '--interlace and --out-depth; one launch per batch.  The bars of --crop-output pad stay exact black.  Off by default')
     T.add_arguments(ap)
     return ap
 
@@ -1458,6 +1504,7 @@ def main(argv=None):
         check_deband(a.deband)
         check_colour(a.linear_light, a.out_matrix, a.out_range, auto=True)
         grain = check_grain(a.grain, a.grain_size, a.grain_chroma, a.grain_curve, a.grain_seed)
+        lut = check_lut(a.lut, check_depths(a.work_depth, a.out_depth, a.dither)[0])
     except ValueError as e:
         parser().error(str(e))
     shutter_kw = {k: v for k, v in (('shutter', a.shutter), ('shutter_samples', a.shutter_samples), ('interlace', a.interlace),
@@ -1467,7 +1514,7 @@ def main(argv=None):
                                     ('denoise_radius', a.denoise_radius), ('linear_light', a.linear_light), ('out_matrix', a.out_matrix),
                                     ('out_range', a.out_range), ('grain', a.grain), ('grain_size', a.grain_size),
                                     ('grain_chroma', a.grain_chroma), ('grain_curve', a.grain_curve), ('grain_seed', a.grain_seed),
-                                    ('deblock', a.deblock), ('dering', a.dering), ('deband', a.deband))
+                                    ('deblock', a.deblock), ('dering', a.dering), ('deband', a.deband), ('lut', lut))
                   if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     try:
@@ -1545,6 +1592,8 @@ def main(argv=None):
             g = vr.last_grain
             extra['grain'] = {'payloads': vr.last_grain_payloads} if g is None else {
                 'strength': g[0] / 16, 'size': g[1], 'chroma': g[2] / 16, 'curve': g[3], 'seed': g[4], 'payloads': vr.last_grain_payloads}
+        if a.lut is not None:
+            extra['lut'] = {'size': vr.lut.n, 'payloads': vr.last_lut_payloads}
         if vr.last_colour is not None:
             extra['colour'] = {'linear_light': vr.last_colour[0], 'matrix': vr.last_colour[1], 'range': 'full' if vr.last_colour[2] else 'limited',
                                'encoded': vr.last_colour_encoded}

@@ -1,7 +1,8 @@
 """The Y4M edge of the clip pipeline (``demfi_amd.pipeline``): Y4M payloads in and out, every window on its own plan, all options in
 one ``pipeline.EdgeSpec``.  One stage per job, each with its own buffers: ``Ingest``, ``SceneScores``, ``DedupProbe``, the pure function
 ``plan_batch`` (``plan_fine``), a ``FrameIO`` chosen once and, behind the gather, the ``Stage`` chain that ``egress_layout`` sizes: ``Shutter``,
-``Scaler``, ``Encoder`` (linear light: the gather then writes linear payloads, ``demfi_amd.colour``), ``Grain``, ``Interlacer`` and ``Requantizer``, in
+``Scaler``, ``Lut`` (a 3D colour LUT over RGB payloads, ``demfi_amd.lut3d``), ``Encoder`` (linear light or a LUT: the gather then writes RGB
+payloads, ``demfi_amd.colour``), ``Grain``, ``Interlacer`` and ``Requantizer``, in
 that order, each only when ``spec`` asks for it; ``Y4mEdge`` loops over them and keeps the
 payloads' way out.
 
@@ -24,6 +25,7 @@ from . import denoise as DN
 from . import dering as DR
 from . import grain as GR
 from . import interlace as IL
+from . import lut3d as LU
 from . import retime as R
 from . import scale as SC
 from . import scene as S
@@ -482,6 +484,20 @@ def linear_light(spec, h, w):
             and (spec.shutter is not None or (spec.scale is not None and tuple(spec.scale[:2]) != (w, h))))
 
 
+def rgb_domain(spec, h, w):
+    """Does the egress of a run of ``spec`` work on RGB payloads (``LinearBuffer``s) with an encode stage behind them?  In linear light, and
+    with a LUT (``spec.lut``) whether or not the run is in linear light."""
+    return linear_light(spec, h, w) or spec.lut is not None
+
+
+def rgb_tables(spec, h, w):
+    """(the gather's table, its inverse, the encode's table) of a run of ``spec`` in the RGB domain: the gather writes through
+    ``colour.forward_table`` in linear light and ``lut3d.code_table`` otherwise; the inverse of that same table is the LUT's ``inv_in``;
+    the encode reads through it too, or behind a LUT, whose output is encoded, through the inverse of ``code_table``."""
+    fwd, inv = LU.tables(spec.depth, spec.colour[0] if linear_light(spec, h, w) else None)
+    return fwd, inv, inv if spec.lut is None else CL.inverse_table(LU.code_table(spec.depth))
+
+
 def sample_format(spec, buf):
     """(bytes per sample, [(rows, cols)] of the planes, peak) of the payloads in ``buf``: what a stage that reads it goes by."""
     if isinstance(buf, LinearBuffer):
@@ -491,11 +507,13 @@ def sample_format(spec, buf):
 
 def egress_layout(spec, nout, batch, h, w):
     """The buffers behind the gather of ``nout`` h x w payloads a batch (of ``batch`` windows) by the module's buffer rule, for the stages
-    ``spec`` asks for, in their order mix -> scale -> encode -> grain -> weave -> requant: a ``Buffer`` (name of its producer, free rows in front = the ``lead`` of
+    ``spec`` asks for, in their order mix -> scale -> lut -> encode -> grain -> weave -> requant: a ``Buffer`` (name of its producer, free rows in front = the ``lead`` of
     its consumer, the most payloads its producer writes per batch, bytes of a payload, frame size) for the gather and every stage built, then
     (rows, payload bytes) of the pinned host buffers.  In linear light (``linear_light``) the gather, the mix and the scale buffers are
-    ``LinearBuffer``s and an ``encode`` stage behind them writes the Y'CbCr payloads.  Pure: allocates nothing."""
-    es, chain, lin = 2 if spec.hi else 1, [], linear_light(spec, h, w)
+    ``LinearBuffer``s and an ``encode`` stage behind them writes the Y'CbCr payloads.  With a LUT (``spec.lut``) the chain runs on RGB payloads
+    in the same way whether or not it is in linear light (``rgb_domain``), and a ``lut`` stage with a ``LinearBuffer`` of its own sits in
+    front of the encode.  Pure: allocates nothing."""
+    es, chain, lin = 2 if spec.hi else 1, [], rgb_domain(spec, h, w)
 
     def add(name, lead, rows, es=es, lin=False):     # lead: what the stage itself needs in front of its source's payloads
         chain.append((LinearBuffer if lin else Buffer, name, lead, rows, 6 * h * w if lin else payload_size(h, w, spec.layout) * es, h, w))
@@ -507,6 +525,8 @@ def egress_layout(spec, nout, batch, h, w):
     if spec.scale is not None and tuple(spec.scale[:2]) != (w, h):       # the run's own size: no stage, the bytes of a run without
         w, h = spec.scale[:2]
         add('scale', 0, chain[-1][3], lin=lin)
+    if spec.lut is not None:                         # stateless and pointwise: its source's rows, at the size behind the scaler
+        add('lut', 0, chain[-1][3], lin=True)
     if lin:                                          # linear payloads -> the run's Y'CbCr payloads, in front of everything that reads those
         add('encode', 0, chain[-1][3])
     if spec.grain is not None:                       # every progressive payload of its source, in place of it: the same rows and size
@@ -733,10 +753,11 @@ class Encoder(Stage):
     works on every rank.  The runner counts ``colour_encoded``."""
     counter, too_many = 'colour_encoded', 'encode: %d payloads for %d payload rows'
 
-    def __init__(self, runner, spec, src, own, dev):
+    def __init__(self, runner, spec, src, own, dev, tables=None):
         super().__init__(runner, spec, src, own, dev)
         self.Pb_in, self.depth, self.layout = src.Pb, spec.depth, L.YUV_LAYOUT[spec.layout]
-        self.inv = torch.from_numpy(CL.tables(spec.colour[0], spec.depth)[1].view(np.int16)).to(dev)
+        inv = CL.tables(spec.colour[0], spec.depth)[1] if tables is None else tables[2]      # tables: ``rgb_tables`` at the gather's size
+        self.inv = torch.from_numpy(inv.view(np.int16)).to(dev)
 
     def begin(self, yuv):
         self.matrix, self.full_range = egress_colour(self.spec, yuv)
@@ -748,6 +769,34 @@ class Encoder(Stage):
     def _call(self, src, host, offs, n, dst, stream):
         L.check(self.lib.demfi_linear_to_yuv(src, host, offs, n, self.h, self.w, self.depth, self.layout, self.matrix, self.full_range,
                                              self.inv.data_ptr(), dst, self.Pb, stream), 'linear_to_yuv')
+
+
+class Lut(Stage):
+    """RGB payloads -> RGB payloads through a user's 3D colour LUT (``demfi_amd.lut3d``, ``spec.lut`` = a ``lut3d.Cube``): behind the mix and
+    the scaler, at full chroma resolution and the working depth, and in front of the encode, which reads its 16-bit encoded output through
+    ``colour.inverse_table(lut3d.code_table)``.  ``demfi_rgb_lut3d`` takes all of a batch's payloads through the cube with ONE launch.  The
+    three tables are the only source of the numbers and are uploaded once, here: ``inv_in``, the inverse of the table the gather wrote
+    with (``rgb_tables``), ``lut3d.axis_table`` and ``lut3d.cube_words``.  Stateless per payload, like the scaler: the stage works on every
+    rank.  A cube of up to ``LDS_N`` = 17 lattice points is kept in LDS (``cube_in_lds``: 9 to 35 % faster than reading it through L2,
+    profiles/lut3d.md), a larger one is read through L2.  The runner counts ``lut_payloads``."""
+    counter, too_many, LDS_N = 'lut_payloads', 'lut: %d payloads for %d payload rows', 17
+
+    def __init__(self, runner, spec, src, own, dev, tables=None):
+        super().__init__(runner, spec, src, own, dev)
+        cube = spec.lut
+        self.Pb_in, self.depth, self.n, self.in_lds = src.Pb, spec.depth, cube.n, int(cube.n <= self.LDS_N)
+        inv_in = LU.tables(spec.depth)[1] if tables is None else tables[1]                   # tables: ``rgb_tables`` at the gather's size
+        self.inv_in = torch.from_numpy(inv_in.view(np.int16)).to(dev)
+        self.axt = torch.from_numpy(LU.axis_table(spec.depth, cube.n).view(np.int32)).to(dev)
+        self.cube = torch.from_numpy(LU.cube_words(cube).view(np.int64).reshape(-1)).to(dev)
+
+    def run(self, i, counts, batch, src, stream):
+        self._launch(i, np.arange(sum(counts), dtype=np.int64)[:, None] * self.Pb_in, src, stream)
+        return counts
+
+    def _call(self, src, host, offs, n, dst, stream):
+        L.check(self.lib.demfi_rgb_lut3d(src, host, offs, n, self.h, self.w, self.depth, self.inv_in.data_ptr(), self.n, self.cube.data_ptr(),
+                                         self.axt.data_ptr(), self.in_lds, dst, self.Pb, stream), 'rgb_lut3d')
 
 
 class Grain(Stage):
@@ -796,7 +845,7 @@ class Grain(Stage):
                                              self.h_gains.ctypes.data, self.gains.data_ptr(), dst, self.Pb, stream), 'payload_grain')
 
 
-STAGES = {'mix': Shutter, 'scale': Scaler, 'encode': Encoder, 'grain': Grain, 'weave': Interlacer, 'requant': Requantizer}
+STAGES = {'mix': Shutter, 'scale': Scaler, 'lut': Lut, 'encode': Encoder, 'grain': Grain, 'weave': Interlacer, 'requant': Requantizer}
 
 
 class TileGrid:
@@ -874,12 +923,13 @@ class Y4mEdge:
         *bufs, host = egress_layout(spec, nout, batch, h, w)
         self.lead = bufs[0].lead                     # the free rows in front of the gather
         self.yuv_out = [torch.empty((self.lead + nout, bufs[0].Pb), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.fwd = None                              # linear light: the gather writes linear payloads through this table, uploaded once
-        if isinstance(bufs[0], LinearBuffer):
-            self.fwd = torch.from_numpy(CL.forward_table(spec.colour[0], spec.depth).view(np.int16)).to(dev)
+        self.fwd, tables = None, None                # linear light, a LUT: the gather writes RGB payloads through this table, uploaded once
+        if isinstance(bufs[0], LinearBuffer):        # the gather's frame size decides whether the run is in linear light
+            tables = rgb_tables(spec, h, w)
+            self.fwd = torch.from_numpy(tables[0].view(np.int16)).to(dev)
         self.stages, self.sources, self.written = [], [], self.yuv_out       # sources[j]: the buffers stages[j] reads
         for src, own in zip(bufs, bufs[1:]):
-            st = STAGES[own.name](runner, spec, src, own, dev)
+            st = STAGES[own.name](runner, spec, src, own, dev, **({'tables': tables} if own.name in ('lut', 'encode') else {}))
             self.stages.append(st)
             self.sources.append(self.written)
             self.written = st.out

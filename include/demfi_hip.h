@@ -723,6 +723,29 @@ int demfi_bgr_to_linear_gather(const void* base, const int64_t* src_offsets, uin
 int demfi_linear_to_yuv(const uint8_t* src, const int64_t* offsets, const int64_t* offsets_dev, int n, int h, int w, int depth, int layout,
                         int matrix, int full_range, const uint16_t* inv_table, uint8_t* dst, int64_t dst_stride, void* stream);
 
+/* ---- a 3D colour LUT at the egress of the Y4M edge (csrc/lut3d.hip; demfi_amd/video.py --lut) ---------------------------------------------
+ * rgb_lut3d: written payload i (n per launch) is the RGB payload (uint16 [3, h, w], planes B, G, R: the LINEAR payload's format above) at
+ * src + offsets[i] (int64 BYTE offsets, even) taken through a cube of cube_n^3 lattice points (2..65) by tetrahedral interpolation in
+ * exact integers; the numpy definition is lut3d.lut_payload_np, matched byte for byte.  Per pixel and channel: code = inv_in[v] (DEVICE,
+ * uint16 [65536]: colour.inverse_table of the table the payloads were made with; a value above the peak reads the peak's entry), word =
+ * axis_table[code] (DEVICE, uint32 [2^depth]: lut3d.axis_table, idx << 16 | frac with idx the lattice cell, clamped here to cube_n - 2,
+ * and frac in 0..65535).  With the fractions sorted f1 >= f2 >= f3, v0 the cell's low corner, v1 = v0 plus a step along the axis of f1,
+ * v2 = v1 plus a step along the axis of f2, v3 the high corner, per output channel
+ *   out = (Q[v0] (65535 - f1) + Q[v1] (f1 - f2) + Q[v2] (f2 - f3) + Q[v3] f3 + 32767) / 65535, rounded down, in uint32,
+ * Q = cube (DEVICE, uint16 [cube_n^3][4]: R, G, B, 0 of the lattice point r + cube_n g + cube_n^2 b; lut3d.cube_words; 8-byte aligned).
+ * The written payload, 16-bit encoded values in the same format, lies at dst + i*dst_stride BYTES; the bytes between its end and
+ * dst_stride are not written.  cube_in_lds = 1 (cube_n <= 17 only) keeps the cube in LDS instead of reading it through L2: the same
+ * bytes, another schedule.  The offsets are passed twice with the same content: offsets in HOST memory, checked here before anything is
+ * launched, and offsets_dev in DEVICE memory, read by the kernel.  DEMFI_ERR_ARG, with nothing launched: a NULL buffer, n < 0, a frame
+ * size outside 2..16384, a depth other than 8, 10 or 12, a cube size outside 2..65, cube_in_lds not 0 or 1 or with a cube above 17,
+ * axis_table off a 4-byte or cube off an 8-byte boundary, a dst_stride below the 6 h w bytes of a payload, a negative offset, an odd
+ * address, offset or stride, a dst that overlaps the span of the source payloads (the stage does not work in place).  One launch: a lane
+ * owns 8 pixels of a row, one 16-byte access per plane in and out where the addresses allow; axis_table is copied into LDS once per
+ * workgroup.  No atomics; n == 0 does nothing. */
+int demfi_rgb_lut3d(const uint8_t* src, const int64_t* offsets, const int64_t* offsets_dev, int n, int h, int w, int depth,
+                    const uint16_t* inv_in, int cube_n, const uint16_t* cube, const uint32_t* axis_table, int cube_in_lds, uint8_t* dst,
+                    int64_t dst_stride, void* stream);
+
 /* ---- tiles of large frames (csrc/tile.hip) --------------------------------------------------------------------------
  * Byte movers of the tiled clip pipeline; the numpy definition is demfi_amd/tiling.py (crop_np / stitch_np).  A plan has n_tiles
  * tiles of ONE size th x tw inside the h x w frame (uint8 [h,w,3]; any h, w in 2..16384).  rects: 6 int32 per tile, frame
