@@ -14,7 +14,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../../incl
 XFLAGS="$DEMFI_EXTRA_FLAGS"
 # the HIP units, ONE list, in link order.  conv = the dispatcher (demfi_conv2d); the convolution kernels are units of their own (round 6:
 # they compile in parallel, 2 min -> 1 min)
-HIP_UNITS="pointwise conv conv_general conv_c64 conv_narrow conv_sep conv_wstream metrics fgac_window resblock gru viz yuv frames16 yuv_family tile dedup deint denoise deblock dering deband ivtc crop shutter interlace scale bitdepth grain colour lut3d wsconv"
+HIP_UNITS="pointwise conv conv_general conv_c64 conv_narrow conv_sep conv_wstream metrics fgac_window resblock gru viz yuv frames16 yuv_family tile dedup deint denoise deblock dering nlmeans deband ivtc crop shutter interlace scale bitdepth grain colour lut3d wsconv"
 # the MFMA units: no SLP vectorisation -- the auto-packed v_pk_add_f32 of the epilogues need v_mov shuffles around the accumulator
 # registers (250 instead of 128 VALU in the 64->64 epilogue) and packed f32 VALU is slow beside MFMAs (MI355X_MICROARCH.md)
 NOSLP_UNITS="conv conv_general conv_c64 conv_narrow conv_sep conv_wstream resblock gru wsconv"

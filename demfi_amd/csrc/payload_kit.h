@@ -1,4 +1,4 @@
-// What the payload stages of the Y4M edge share (shutter, denoise, deblock, dering, deband, interlace, bitdepth, grain, scale, crop, ivtc, dedup, tile and,
+// What the payload stages of the Y4M edge share (shutter, denoise, deblock, dering, nlmeans, deband, interlace, bitdepth, grain, scale, crop, ivtc, dedup, tile and,
 // through yuv_common.h, the colour conversions): packed-word typedefs and sample accessors on the device side; on the host side the
 // argument checks every demfi_payload_* entry point makes before its first HIP call, the launch grids and the dispatch from run-time
 // values to template arguments.  The rules differ from entry point to entry point (plane sizes, what an offset row may hold, which

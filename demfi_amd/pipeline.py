@@ -65,9 +65,10 @@ class EdgeSpec(_EdgeFields):
     (``demfi_amd.dering``: strengths at the 8-bit scale), kept beside the tuple like ``deblock``; P = S = 0, the identity, is None.  ``deband``: None or (T, R) of the debanding filter behind the deringing filter
     (``demfi_amd.deband``: threshold at the 8-bit scale, radius in samples), kept beside the tuple like ``dering``; T = 0, the identity, is None.
     ``lut``: None or the ``lut3d.Cube`` of the 3D colour LUT applied between the scaler and the encode (``demfi_amd.lut3d``), kept beside the tuple
-    like ``grain``; it compares and hashes by its size and its quantised numbers.  ``reach``: how far the frames an ingest stage reads lie from the frame it writes.
+    like ``grain``; it compares and hashes by its size and its quantised numbers.  ``nlmeans``: None or (S, P, R) of the spatial denoiser between the deringing filter and the debander
+    (``demfi_amd.nlmeans``: strength at the 8-bit scale, patch and search radius in samples), kept beside the tuple like ``deband``; S = 0, the identity, is None.  ``reach``: how far the frames an ingest stage reads lie from the frame it writes.
     Hashable: (batch, spec) is what a cached ``ClipPipeline`` can be reused for.
-    ``shutter``, ``interlace``, ``scale``, ``depths``, ``shutter_window``, ``denoise``, ``colour``, ``grain``, ``deblock``, ``dering``, ``deband`` and ``lut`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
+    ``shutter``, ``interlace``, ``scale``, ``depths``, ``shutter_window``, ``denoise``, ``colour``, ``grain``, ``deblock``, ``dering``, ``deband``, ``lut`` and ``nlmeans`` come last and by keyword only, and they are kept beside the tuple's eight items, not among them: a spec
     without them is, item for item, the record it was before there were any, and one with any of them equals no plain tuple.  What the namedtuple makes
     from its items alone does not know them: ``_make``, ``_asdict`` and pickling drop them; the constructor, ``of`` and ``_replace`` are the ways to a spec."""
     shutter = None
@@ -82,10 +83,13 @@ class EdgeSpec(_EdgeFields):
     dering = None
     deband = None
     lut = None
+    nlmeans = None
 
     def __new__(cls, *args, shutter=None, interlace=None, scale=None, depths=None, shutter_window=None, denoise=None, colour=None, grain=None,
-                deblock=None, dering=None, deband=None, lut=None, **kw):
+                deblock=None, dering=None, deband=None, lut=None, nlmeans=None, **kw):
         self = super().__new__(cls, *args, **kw)
+        if nlmeans is not None and int(nlmeans[0]) != 0:                  # S = 0 changes nothing: the spec without the field
+            self.nlmeans = tuple(int(v) for v in nlmeans)
         if lut is not None:
             self.lut = lut
         if deband is not None and int(deband[0]) != 0:                    # T = 0 changes nothing: the spec without the field
@@ -117,8 +121,10 @@ class EdgeSpec(_EdgeFields):
         depths, window, denoise = kw.pop('depths', self.depths), kw.pop('shutter_window', self.shutter_window), kw.pop('denoise', self.denoise)
         colour, grain, deblock = kw.pop('colour', self.colour), kw.pop('grain', self.grain), kw.pop('deblock', self.deblock)
         dering, deband, lut = kw.pop('dering', self.dering), kw.pop('deband', self.deband), kw.pop('lut', self.lut)
+        nlmeans = kw.pop('nlmeans', self.nlmeans)
         return type(self)(*super()._replace(**kw), shutter=shutter, interlace=interlace, scale=scale, depths=depths, shutter_window=window,
-                          denoise=denoise, colour=colour, grain=grain, deblock=deblock, dering=dering, deband=deband, lut=lut)
+                          denoise=denoise, colour=colour, grain=grain, deblock=deblock, dering=dering, deband=deband, lut=lut,
+                          nlmeans=nlmeans)
 
     def __eq__(self, other):
         return (tuple.__eq__(self, other) is True and self.shutter == getattr(other, 'shutter', None)
@@ -127,7 +133,7 @@ class EdgeSpec(_EdgeFields):
                 and self.denoise == getattr(other, 'denoise', None) and self.colour == getattr(other, 'colour', None)
                 and self.grain == getattr(other, 'grain', None) and self.deblock == getattr(other, 'deblock', None)
                 and self.dering == getattr(other, 'dering', None) and self.deband == getattr(other, 'deband', None)
-                and self.lut == getattr(other, 'lut', None))
+                and self.lut == getattr(other, 'lut', None) and self.nlmeans == getattr(other, 'nlmeans', None))
 
     def __ne__(self, other):
         return not self == other
@@ -143,7 +149,8 @@ class EdgeSpec(_EdgeFields):
         key = key if self.deblock is None else key + ('deblock', self.deblock)
         key = key if self.dering is None else key + ('dering', self.dering)
         key = key if self.deband is None else key + ('deband', self.deband)
-        return hash(key if self.lut is None else key + ('lut', self.lut))
+        key = key if self.lut is None else key + ('lut', self.lut)
+        return hash(key if self.nlmeans is None else key + ('nlmeans', self.nlmeans))
 
     def __repr__(self):
         return super().__repr__()[:-1] + ', shutter=%r%s%s)' % (self.shutter, ', interlace=%r' % (self.interlace,) if self.interlace is not None else '',
@@ -156,7 +163,8 @@ class EdgeSpec(_EdgeFields):
                                                                + (', deblock=%r' % (self.deblock,) if self.deblock is not None else '')
                                                                + (', dering=%r' % (self.dering,) if self.dering is not None else '')
                                                                + (', deband=%r' % (self.deband,) if self.deband is not None else '')
-                                                               + (', lut=%r' % (self.lut,) if self.lut is not None else ''))
+                                                               + (', lut=%r' % (self.lut,) if self.lut is not None else '')
+                                                               + (', nlmeans=%r' % (self.nlmeans,) if self.nlmeans is not None else ''))
 
     @classmethod
     def of(cls, yuv):
@@ -168,7 +176,8 @@ class EdgeSpec(_EdgeFields):
                    interlace=getattr(yuv, 'interlace', None), scale=getattr(yuv, 'scale', None), depths=getattr(yuv, 'depths', None),
                    shutter_window=getattr(yuv, 'shutter_window', None), denoise=getattr(yuv, 'denoise', None), colour=getattr(yuv, 'colour', None),
                    grain=getattr(yuv, 'grain', None), deblock=getattr(yuv, 'deblock', None),
-                   dering=getattr(yuv, 'dering', None), deband=getattr(yuv, 'deband', None), lut=getattr(yuv, 'lut', None))
+                   dering=getattr(yuv, 'dering', None), deband=getattr(yuv, 'deband', None), lut=getattr(yuv, 'lut', None),
+                   nlmeans=getattr(yuv, 'nlmeans', None))
 
     hi = property(lambda self: self.depth > 8, doc='16-bit frames: the samples of a stream above 8 bits')
     reach = property(lambda self: DN.reach(self.denoise[2], self.fields is not None) if self.denoise is not None
@@ -186,7 +195,7 @@ class EdgeSpec(_EdgeFields):
         other, edge_only = self.deint_mode != 'bob', self.hi or self.dedup is not None or self.fields is not None
         deint = deint_conflict(self.deint_mode, self.fields is not None, self.dedup is not None)
         sh, il, sc, dp, win, dn, co = self.shutter, self.interlace, self.scale, self.depths, self.shutter_window, self.denoise, self.colour
-        gr, db, dr, bd, lu = self.grain, self.deblock, self.dering, self.deband, self.lut
+        gr, db, dr, bd, lu, nl = self.grain, self.deblock, self.dering, self.deband, self.lut, self.nlmeans
         for bad, what in ((self.fields not in (None, 't', 'b'), "fields must be None, 't' or 'b', got %r" % (self.fields,)),
                           (deint, 'deint_mode %r with fields=%r, dedup=%r' % (self.deint_mode, self.fields, self.dedup)),
                           (edge_only and not self.y4m, '16-bit frames, repeated frames and fields are those of the Y4M edge (yuv=...) only'),
@@ -242,6 +251,9 @@ class EdgeSpec(_EdgeFields):
                           (bd is not None and not (len(bd) == 2 and 0 <= bd[0] <= 8 and 1 <= bd[1] <= 16),
                            'deband must be None or (T, R) with 0 <= T <= 8, 1 <= R <= 16, got %r' % (bd,)),
                           (bd is not None and not (retimed and self.y4m), 'debanding needs the Y4M edge on a retimed runner'),
+                          (nl is not None and not (len(nl) == 3 and 0 <= nl[0] <= 16 and 1 <= nl[1] <= 3 and 1 <= nl[2] <= 7),
+                           'nlmeans must be None or (S, P, R) with 0 <= S <= 16, 1 <= P <= 3, 1 <= R <= 7, got %r' % (nl,)),
+                          (nl is not None and not (retimed and self.y4m), 'spatial denoising needs the Y4M edge on a retimed runner'),
                           (lu is not None and not isinstance(lu, LU.Cube), 'lut must be None or a lut3d.Cube, got %r' % (lu,)),
                           (lu is not None and not (retimed and self.y4m), 'a 3D LUT needs the Y4M edge on a retimed runner'),
                           (lu is not None and self.depth > LU.MAX_DEPTH,

@@ -178,6 +178,7 @@ class WindowRunner:
         self.deblocked = 0                           # deblocking: payloads deblocked at ingest (``demfi_amd.deblock``)
         self.deringed = 0                            # deringing: payloads deringed at ingest (``demfi_amd.dering``)
         self.debanded = 0                            # debanding: payloads debanded at ingest (``demfi_amd.deband``)
+        self.nlm_filtered = 0                        # spatial denoising: payloads filtered at ingest (``demfi_amd.nlmeans``)
         self.grain_payloads = 0                     # film grain: payloads grained at egress (``y4m_edge.Grain``)
         self.lut_payloads = 0                       # 3D colour LUT: payloads taken through the cube at egress (``y4m_edge.Lut``)
         self.colour_encoded = 0                      # linear light: payloads taken back to Y'CbCr (``y4m_edge.Encoder``)
@@ -657,6 +658,9 @@ class WindowRunner:
         ``yuv.deband`` = (T, R) (None when absent; ``demfi_amd.deband``): every uploaded payload is debanded on the GPU behind the deringing
         filter and in front of everything else (one device copy into the scratch buffer the deringing filter uses, then
         ``demfi_payload_deband`` back into place); goes with everything.
+        ``yuv.nlmeans`` = (S, P, R) (None when absent; ``demfi_amd.nlmeans``): every uploaded payload is denoised within the frame on the GPU
+        behind the deringing filter and in front of the debander (one device copy into the same scratch buffer, then
+        ``demfi_payload_nlmeans`` back into place); goes with everything.
         Returns the number of windows run."""
         spec = EdgeSpec.of(yuv)
         spec.check(self.retime is not None, window_index is not None, reuse_frames)

@@ -193,7 +193,7 @@ rank's block also reads that many frames before it and after it; no payload is u
 input frames f - R .. f + R only, whatever the batch size and the rank count.  ``--ivtc`` and ``--crop`` are host stages in front: their
 frames are ordinary frames, and they decide on the input's own samples.  Works with every switch above except ``--dedup`` (kept frames are
 staged one at a time, without look-ahead) and ``--deinterlace-mode adaptive`` (two deferred look-ahead stages in a row), both refused
-before anything is allocated.  Not offered: spatial filtering, separate chroma thresholds, motion-compensated averaging, stopping at
+before anything is allocated.  Not offered: spatial filtering in this stage (``--nlmeans`` is that stage), separate chroma thresholds, motion-compensated averaging, stopping at
 detected cuts (the thresholds do that per sample), numeric equality with ffmpeg's ``atadenoise``, decisions of ``--ivtc`` / ``--crop auto`` on
 denoised samples, ``demfi_amd.clip``.  Without the switch no buffer, table, launch or slot is added and every byte stays the same.
 
@@ -292,6 +292,26 @@ not parse (with its line) and a working depth above 12 bits (the gather keeps it
 other than 0 .. 1, trilinear interpolation, other file formats, a transfer or primaries tag in the header (Y4M has none), working depths
 14 and 16, ``demfi_amd.clip``, numeric equality with ffmpeg's ``lut3d`` or OCIO.  Without the switch no buffer, table, launch or counter is
 added and every byte stays the same.
+
+``--nlmeans [S[:P[:R]]]`` denoises every plane within the frame, in front of the network (``demfi_amd.nlmeans``): ``--denoise`` is purely
+temporal and stops at the first difference above A, so on a moving object, a pan or a zoom every sample keeps its grain, and those are the
+samples the flow estimator works on.  The rule is non-local means in exact integers, on every plane as a plane in its own right: a sample
+becomes the weighted mean, rounded to nearest, of the samples of its (2R + 1)^2 search window that lie inside the plane, each weighed by a
+table of 1024 entries (built on the host, 256 exp(-D / (np_ 4^b S^2))) of the summed squared difference D of the (2P + 1)^2 patches around
+the two, the patches replicating the plane's edge.  A patch that differs by more than the table's reach weighs nothing, so a hard edge is
+not seen across; no clip is needed.  S (0 .. 16) is in 8-bit steps, P (1 .. 3) and R (1 .. 7) in samples, one triple for every plane; the
+default 3:2:5 has not been tuned against this network; S alone is S:2:5; ``--nlmeans 0`` builds no stage.  The filter's reach, not bugs: a
+window cut off by a border or an edge is lopsided, so a ramp next to one is biased by a few codes, and a high S costs texture
+(``profiles/nlmeans.md`` has the figures).  The stage sits directly behind the deringing filter and in front of the debander (noise hides
+bands and denoising uncovers them), H2D -> promote -> deblock -> dering -> nlmeans -> deband -> bob / adaptive -> denoise -> frames, tiles,
+scene scores, dedup probe: per run of consecutive newly uploaded slots one device copy takes the payloads into the scratch buffer (the one
+the deringing filter and the debander use where they are given) and ONE launch (csrc/nlmeans.hip ``demfi_payload_nlmeans``, byte for byte
+``nlmeans.nlmeans_payload_np``) writes them back; a run with the switch writes the bytes of a run without it over the stream filtered on
+the host.  Under ``--deinterlace`` (either mode) each field of each plane is a plane of its own.  The stage keeps nothing between payloads
+and needs no look-ahead: every switch above and several ranks work.  Not offered: separate luma / chroma strengths; a noise estimate that
+sets S; temporal or motion-compensated search (that remains ``--denoise``'s side); P above 3 or R above 7; subtraction of the noise variance
+from D; numeric equality with ffmpeg's ``nlmeans``; ``demfi_amd.clip``; decisions of ``--ivtc`` / ``--crop auto`` on filtered samples (they
+decide in front, on the input's own).  Without the switch no buffer, table, launch, copy or counter is added and every byte stays the same.
 """
 import os
 import sys
@@ -313,6 +333,7 @@ from . import grain as GR
 from . import interlace as IL
 from . import letterbox as LB
 from . import lut3d as LU
+from . import nlmeans as NL
 from . import retime as R
 from . import scale as SC
 from . import scene as S
@@ -349,12 +370,14 @@ class YuvEdge:
     to out of their stream, which shifts the block grid of both.  ``dering``: None, or (P, S, D) of the deringing filter behind the deblocker
     (``demfi_amd.dering``); P = S = 0 is None.  ``deband``: None, or (T, R) of the debanding filter behind that (``demfi_amd.deband``); T = 0 is
     None.  ``lut``: None, or the ``lut3d.Cube`` (or the path of a ``.cube`` file) of the 3D colour LUT applied between the scaler and the encode
-    (``demfi_amd.lut3d``)."""
+    (``demfi_amd.lut3d``).  ``nlmeans``: None, or (S, P, R) of the spatial denoiser between the deringing filter and the debander
+    (``demfi_amd.nlmeans``); S = 0 is None."""
 
     def __init__(self, matrix, full_range, siting, with_s1, scene_cut=None, full_length=False, depth=8, layout='420', dedup=None,
                  fields=None, deint_mode='bob', shutter=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None,
                  depths=None, shutter_window=None, denoise=None, linear_light=None, out_matrix=None, out_range=None, grain=None,
-                 deblock=None, crop_rect=None, dering=None, deband=None, lut=None):
+                 deblock=None, crop_rect=None, dering=None, deband=None, lut=None, nlmeans=None):
+        self.nlmeans = check_nlmeans(nlmeans)
         self.dedup, self.shutter = dedup, shutter
         self.lut = check_lut(lut)
         self.deblock = check_deblock(deblock)
@@ -554,6 +577,24 @@ def check_dering(dering):
     return psd if psd[0] or psd[1] else None
 
 
+def check_nlmeans(nlmeans):
+    """The nlmeans switch checked: None (off, or S = 0: no stage), or (S, P, R) of ``nlmeans.check_params``.  ``nlmeans``: None / False
+    (off), True (the defaults 3:2:5, not tuned against this network), S (S:2:5), (S, P, R) or a "S[:P[:R]]" string.  Goes with every other
+    switch and any number of ranks."""
+    if nlmeans is None or nlmeans is False:
+        return None
+    if nlmeans is True:
+        nlmeans = NL.DEFAULTS
+    elif isinstance(nlmeans, str):
+        nlmeans = NL.parse_nlmeans(nlmeans)
+    elif isinstance(nlmeans, int):
+        nlmeans = (nlmeans,)
+    if not isinstance(nlmeans, (tuple, list)) or not 1 <= len(nlmeans) <= 3:
+        raise ValueError('nlmeans must be None, True, S, (S, P, R) or "S[:P[:R]]", got %r' % (nlmeans,))
+    spr = NL.check_params(*nlmeans)
+    return spr if spr[0] else None
+
+
 def check_deband(deband):
     """The deband switch checked: None (off, or T = 0: no stage), or (T, R) of ``deband.check_params``.  ``deband``: None / False (off),
     True (the defaults 2:16), T (T:16), (T, R) or a "T[:R]" string.  Goes with every other switch and any number of ranks."""
@@ -599,7 +640,8 @@ COUNTERS = {'instants_run': None, 'instants_padded': None, 'shutter_mixed': None
 # and of the egress stages that came after: linear light (``y4m_edge.Encoder``), film grain (``y4m_edge.Grain``), the 3D LUT (``y4m_edge.Lut``)
 EGRESS_COUNTERS = {'colour_encoded': 'last_colour_encoded', 'grain_payloads': 'last_grain_payloads', 'lut_payloads': 'last_lut_payloads'}
 # the counters of the ingest stages that came after those: kept the same way, in a table of their own
-INGEST_COUNTERS = {'denoised': 'last_denoised', 'deblocked': 'last_deblocked', 'deringed': 'last_deringed', 'debanded': 'last_debanded'}
+INGEST_COUNTERS = {'denoised': 'last_denoised', 'deblocked': 'last_deblocked', 'deringed': 'last_deringed', 'debanded': 'last_debanded',
+                   'nlm_filtered': 'last_nlm_filtered'}
 
 
 AUTO_NEEDS_A_FILE = ('--crop auto needs a regular input file: the bars of a stream are known only at its end; give the four bar '
@@ -742,7 +784,14 @@ class VideoRunner:
     uploaded slots), field by field under ``deinterlace``; everything behind runs on the debanded stream.  It does its work at a working
     depth above the input's (``work_depth=10`` or more on 8-bit input) and is not refused without.  Goes with every other switch and any
     number of ranks.  ``deband=0`` builds no stage.  After a run ``last_debanded`` = the payloads debanded.  Without it no buffer, table,
-    launch, copy or counter is added and every byte stays the same."""
+    launch, copy or counter is added and every byte stays the same.  ``nlmeans``: None (default), True (3:2:5, not tuned against this
+    network), S (S:2:5), (S, P, R) or a "S[:P[:R]]" string, S in 8-bit steps with 0 <= S <= 16, P and R in samples with 1 <= P <= 3 and
+    1 <= R <= 7: every plane is denoised within the frame on the GPU behind the deringing filter and in front of the debander
+    (``demfi_amd.nlmeans``: non-local means in exact integers; csrc/nlmeans.hip ``demfi_payload_nlmeans``, one device copy into the scratch
+    buffer ``dering`` and ``deband`` use and ONE launch per run of uploaded slots), field by field under ``deinterlace``; everything behind
+    runs on the filtered stream.  Goes with every other switch and any number of ranks.  ``nlmeans=0`` builds no stage.  After a run
+    ``last_nlm_filtered`` = the payloads filtered.  Without it no buffer, table, launch, copy or counter is added and every byte stays the
+    same."""
 
     def __init__(self, model, n_tst=3, mfi=None, batch=4, matrix='auto', fps=None, scene_cut=None, full_length=False, tile=None,
                  tile_margin=T.DEFAULT_MARGIN, high_depth=False, layouts=False, dedup=None, dedup_max_hold=K.DEFAULT_MAX_HOLD,
@@ -752,7 +801,8 @@ class VideoRunner:
                  shutter_samples=None, interlace=None, interlace_lowpass=None, scale=None, scale_filter=None, work_depth=None,
                  out_depth=None, dither=None, down=False, shutter_window=None, denoise=None, denoise_radius=None, linear_light=None,
                  out_matrix=None, out_range=None, grain=None, grain_size=None, grain_chroma=None, grain_curve=None, grain_seed=None,
-                 deblock=None, dering=None, deband=None, lut=None, **runner_kw):
+                 deblock=None, dering=None, deband=None, lut=None, nlmeans=None, **runner_kw):
+        self.nlmeans = check_nlmeans(nlmeans)            # (S, P, R) or None
         check_deinterlace_mode(deinterlace, deinterlace_mode, dedup)
         self.lut = check_lut(lut)                        # a ``lut3d.Cube`` or None
         self.last_lut = None
@@ -1090,6 +1140,7 @@ class VideoRunner:
                        self.scene_cut, self.full_length, depths[1], hdr.layout, self.dedup, order, self.deinterlace_mode, self.shutter,
                        *(self.interlace or (None, None)), self._scale_of(hdr), depths=depths, shutter_window=self.shutter_window,
                        denoise=self.denoise, grain=self.grain, deblock=self.deblock, dering=self.dering, deband=self.deband, lut=self.lut,
+                       nlmeans=self.nlmeans,
                        crop_rect=self.last_crop if self.deblock is not None or self.dering is not None else None, **kw)
 
     def _run_dedup(self, cr, hdr, frames, sink, order=None):
@@ -1431,6 +1482,15 @@ def parser():
                          'one code rounds back to itself.  Bands narrower than about R/T stay.  With --deinterlace every field is filtered on its '
                          'own.  Works with every other switch and any number of ranks.  Off by default'
                          % ((BA.MAX_T, BA.MIN_R, BA.MAX_R) + BA.DEFAULTS))
+    ap.add_argument('--nlmeans', nargs='?', type=_value_arg(NL.parse_nlmeans), const=NL.DEFAULTS, default=None, metavar='S[:P[:R]]',
+                    help='denoise every plane within the frame on the GPU (non-local means in exact integers), behind --dering and in front of '
+                         '--deband: every sample becomes the weighted mean of the samples of its (2R+1)x(2R+1) search window, each weighed by '
+                         'how little its (2P+1)x(2P+1) patch differs; a hard edge is not seen across.  The answer to noise on anything that moves, '
+                         'where --denoise (temporal) stops.  S (0 .. %d) in 8-bit steps, P (%d .. %d) and R (%d .. %d) in samples, one triple for '
+                         'all planes; default %d:%d:%d (not tuned against this network); S alone means S:2:5; 0 builds nothing.  A high S costs '
+                         'texture; a ramp beside a border or an edge is biased by a few codes.  With --deinterlace every field is filtered on '
+                         'its own.  Works with every other switch and any number of ranks.  Off by default'
+                         % ((NL.MAX_S, NL.MIN_P, NL.MAX_P, NL.MIN_R, NL.MAX_R) + NL.DEFAULTS))
     ap.add_argument('--denoise-radius', type=int, default=None, metavar='R',
                     help='with --denoise: the frames looked at on each side, 1 .. %d (default %d); costs R frames of lookahead, 2 R fields '
                          'behind --deinterlace' % (DN.MAX_RADIUS, DN.DEFAULT_RADIUS))
@@ -1502,6 +1562,7 @@ def main(argv=None):
         check_deblock(a.deblock)
         check_dering(a.dering)
         check_deband(a.deband)
+        check_nlmeans(a.nlmeans)
         check_colour(a.linear_light, a.out_matrix, a.out_range, auto=True)
         grain = check_grain(a.grain, a.grain_size, a.grain_chroma, a.grain_curve, a.grain_seed)
         lut = check_lut(a.lut, check_depths(a.work_depth, a.out_depth, a.dither)[0])
@@ -1514,7 +1575,8 @@ def main(argv=None):
                                     ('denoise_radius', a.denoise_radius), ('linear_light', a.linear_light), ('out_matrix', a.out_matrix),
                                     ('out_range', a.out_range), ('grain', a.grain), ('grain_size', a.grain_size),
                                     ('grain_chroma', a.grain_chroma), ('grain_curve', a.grain_curve), ('grain_seed', a.grain_seed),
-                                    ('deblock', a.deblock), ('dering', a.dering), ('deband', a.deband), ('lut', lut))
+                                    ('deblock', a.deblock), ('dering', a.dering), ('deband', a.deband), ('lut', lut),
+                                    ('nlmeans', a.nlmeans))
                   if v is not None}
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (('RANK', 0), ('LOCAL_RANK', 0), ('WORLD_SIZE', 1)))
     try:
@@ -1562,8 +1624,8 @@ def main(argv=None):
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
     counts = [float(nw), float(nf), float(vr.last_st_frames), float(vr.last_instants[0]), float(vr.last_instants[1]),
               float(vr.last_cut_windows), float(vr.last_depth_promoted), float(vr.last_depth_requantised), float(vr.last_denoised), float(vr.last_deblocked),
-              float(vr.last_deringed), float(vr.last_debanded)]
-    tw, tf, tst, ti, tp, tc, tdp, tdq, tdn, tdb, tdr, tba = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
+              float(vr.last_deringed), float(vr.last_debanded), float(vr.last_nlm_filtered)]
+    tw, tf, tst, ti, tp, tc, tdp, tdq, tdn, tdb, tdr, tba, tnl = (D.sum_over_ranks(counts, dev).tolist() if world > 1 else counts)
     if rank == 0:
         if a.crop is not None:
             print('demfi_amd.video: ' + vr.crop_report(), file=sys.stderr)
@@ -1585,6 +1647,8 @@ def main(argv=None):
             extra['dering'] = {'p': a.dering[0], 's': a.dering[1], 'd': a.dering[2], 'payloads': int(tdr)}
         if a.deband is not None:
             extra['deband'] = {'t': a.deband[0], 'r': a.deband[1], 'payloads': int(tba)}
+        if a.nlmeans is not None:
+            extra['nlmeans'] = {'s': a.nlmeans[0], 'p': a.nlmeans[1], 'r': a.nlmeans[2], 'payloads': int(tnl)}
         if a.scale is not None:
             extra['scale'] = {'size': '%dx%d' % vr.scale[:2], 'filter': vr.scale[2], 'resized': vr.last_scale is not None,
                               'payloads': vr.last_scale_payloads}

@@ -26,6 +26,7 @@ from . import dering as DR
 from . import grain as GR
 from . import interlace as IL
 from . import lut3d as LU
+from . import nlmeans as NL
 from . import retime as R
 from . import scale as SC
 from . import scene as S
@@ -129,8 +130,15 @@ class Ingest:
     ``spec.deband`` = (T, R) (``demfi_amd.deband``): directly behind the deringing filter, in the same manner: per run of consecutive newly
     uploaded slots ONE device copy into ``bd_scratch`` and ONE ``demfi_payload_deband`` launch back into yuv_in.  With both switches
     ``bd_scratch`` IS ``dr_scratch``: the two stages run in order on the ingest stream, so one buffer serves both.  The phases of the plane
-    table are carried and ignored.  Nothing is kept between payloads; the runner counts ``debanded``."""
+    table are carried and ignored.  Nothing is kept between payloads; the runner counts ``debanded``.
+    ``spec.nlmeans`` = (S, P, R) (``demfi_amd.nlmeans``): the spatial denoiser, behind the deringing filter and IN FRONT of the debander
+    (noise hides bands and denoising uncovers them), in the same manner: per run of consecutive newly uploaded slots ONE device copy into
+    ``nl_scratch`` and ONE ``demfi_payload_nlmeans`` launch back into yuv_in.  ``nl_scratch`` IS ``dr_scratch`` where there is one;
+    otherwise it is the buffer ``bd_scratch`` would be, and then ``bd_scratch`` IS ``nl_scratch``: one scratch buffer serves every stage
+    that needs one.  The weight table and its shift are ``nlmeans.weight_table`` at the working depth, a host array the entry point reads.
+    Nothing is kept between payloads; the runner counts ``nlm_filtered``."""
     denoise = clean = None                           # without --denoise: no buffer, table or launch
+    nlmeans = None                                   # without --nlmeans: no buffer, table, launch, copy or counter
     deblock = None                                   # without --deblock: no table, launch or counter
     dering = None                                    # without --dering: no buffer, table, launch, copy or counter
     deband = None                                    # without --deband: no buffer, table, launch, copy or counter
@@ -155,10 +163,17 @@ class Ingest:
         if spec.dering is not None:                  # the strengths at the 8-bit scale and the depth; the scratch the launch reads
             self.dering = (spec.depth,) + DR.check_params(*spec.dering)
             self.dr_scratch = torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev)
+        if getattr(spec, 'nlmeans', None) is not None:       # depth, P, R; the weights and their shift; the scratch is the deringing filter's where there is one
+            s, p, r = NL.check_params(*spec.nlmeans)
+            self.nlmeans = (spec.depth, p, r)
+            self.nl_table, self.nl_shift = NL.weight_table(spec.depth, s, p)
+            self.nl_table = np.ascontiguousarray(self.nl_table, dtype=np.uint16)
+            self.nl_scratch = self.dr_scratch if self.dering is not None else torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev)
         if spec.deband is not None:                  # depth, T at the 8-bit scale, R; the scratch is the deringing filter's where there is one
             self.deband = (spec.depth,) + BA.check_params(*spec.deband)
-            self.bd_scratch = self.dr_scratch if self.dering is not None else torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev)
-        if self.deblock is not None or self.dering is not None or self.deband is not None:
+            self.bd_scratch = (self.dr_scratch if self.dering is not None else self.nl_scratch if self.nlmeans is not None
+                               else torch.empty((nsl, self.Pb), dtype=torch.uint8, device=dev))
+        if self.deblock is not None or self.dering is not None or self.deband is not None or self.nlmeans is not None:
             self.attach(None)
         # a working depth above the input's (``spec.depths``, ``demfi_amd.bitdepth``): payloads are copied into ``staged`` at the input's sample
         # size, so H2D carries the input's bytes, and ``promote`` writes them into yuv_in at the working depth before anything else reads them
@@ -189,6 +204,9 @@ class Ingest:
         if self.deband is not None:
             self.bd_planes = np.ascontiguousarray(DB.plane_table(self.fh, self.fw, self.layout, self.fields, getattr(yuv, 'crop_rect', None)),
                                                   dtype=np.int64)
+        if self.nlmeans is not None:
+            self.nl_planes = np.ascontiguousarray(DB.plane_table(self.fh, self.fw, self.layout, self.fields, getattr(yuv, 'crop_rect', None)),
+                                                  dtype=np.int64)
 
     def deblocked(self, new, stream):
         """The payloads just copied (and promoted) for the (frame, slot) pairs ``new`` are deblocked in place: ONE ``demfi_payload_deblock``
@@ -211,6 +229,19 @@ class Ingest:
                                                      self.dr_planes.ctypes.data, len(self.dr_planes), self.es, *self.dering,
                                                      stream.cuda_stream), 'payload_dering')
         self.rn.deringed += len(new)
+
+    def nlm_filtered(self, new, stream):
+        """The payloads just copied (promoted, deblocked, deringed) for the (frame, slot) pairs ``new`` are denoised within the frame: per run
+        of consecutive slots ONE device copy into the scratch on the ingest stream, then ONE ``demfi_payload_nlmeans`` launch from the
+        scratch back into yuv_in."""
+        if self.nlmeans is None or not new:
+            return
+        for s0, cnt in consecutive([sl for _, sl in new]):
+            self.nl_scratch[s0:s0 + cnt].copy_(self.yuv_in[s0:s0 + cnt], non_blocking=True)
+            L.check(self.rn.lib.demfi_payload_nlmeans(self.nl_scratch[s0].data_ptr(), self.Pb, self.yuv_in[s0].data_ptr(), self.Pb, cnt,
+                                                      self.nl_planes.ctypes.data, len(self.nl_planes), self.es, *self.nlmeans,
+                                                      self.nl_table.ctypes.data, self.nl_shift, stream.cuda_stream), 'payload_nlmeans')
+        self.rn.nlm_filtered += len(new)
 
     def debanded(self, new, stream):
         """The payloads just copied (promoted, deblocked, deringed) for the (frame, slot) pairs ``new`` are debanded: per run of consecutive
@@ -250,11 +281,12 @@ class Ingest:
 
     def rebuilt(self, new, stream):
         """The payloads just copied for the (frame, slot) pairs ``new`` become progressive payloads at the working depth: promoted first of
-        all, deblocked (``spec.deblock``), deringed (``spec.dering``), debanded (``spec.deband``), then made progressive.  Returns the pairs that now are (adaptive: the fields just rebuilt, not those
+        all, deblocked (``spec.deblock``), deringed (``spec.dering``), denoised within the frame (``spec.nlmeans``), debanded (``spec.deband``), then made progressive.  Returns the pairs that now are (adaptive: the fields just rebuilt, not those
         uploaded)."""
         self.promote(new, stream)
         self.deblocked(new, stream)
         self.deringed(new, stream)
+        self.nlm_filtered(new, stream)
         self.debanded(new, stream)
         new = self._adaptive(new, stream) if self.adaptive else self.bob(new, stream)
         return self._denoise(new, stream) if self.denoise is not None else new

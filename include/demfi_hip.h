@@ -543,6 +543,30 @@ int demfi_payload_dering(const void* src, int64_t src_stride_bytes, void* dst, i
 int demfi_payload_deband(const void* src, int64_t src_stride_bytes, void* dst, int64_t dst_stride_bytes, int n, const int64_t* planes,
                          int n_planes, int sample_bytes, int depth, int thr8, int radius, void* stream);
 
+/* ---- spatial denoising of the Y4M edge (csrc/nlmeans.hip; demfi_amd/video.py --nlmeans) ---------------------------------------------------
+ * payload_nlmeans: the n (>= 0, any number) payloads at src + i*src_stride_bytes are denoised into dst + i*dst_stride_bytes, OUT OF PLACE:
+ * the two ranges must not overlap (sample_bytes = 1, or 2 for 16-bit little-endian samples: even addresses and strides).  planes: the plane
+ * table in HOST memory as for demfi_payload_deband, n_planes (1..6) entries of six int64 each: first sample, rows, cols (1..16384 each),
+ * row pitch in samples (>= cols), x and y phase (0..7; checked, carried and ignored).  The entries must not share a sample.  Every entry
+ * is filtered as a plane in its own right by non-local means in exact integers.  With u(x, y) the sample of the source at column
+ * clamp(x, 0, cols - 1), row clamp(y, 0, rows - 1), s = depth - 8, b = min(s, 4) and q(t) = min(|t| >> (s - b), 4095): for the sample at
+ * (x, y) and every offset (i, j), |i|, |j| <= search, whose candidate (x + i, y + j) lies inside the plane, D = the sum over |a|, |e| <=
+ * patch of q(u(x + a, y + e) - u(x + i + a, y + j + e))^2, w = table[min(D >> shift, 1023)], v = u(x + i, y + j); out =
+ * (2 sum(w v) + W) / (2 W) floored, W = sum(w): the weighted mean rounded to nearest, ties up.  table: 1024 uint16 in HOST memory, read
+ * before the call returns (nlmeans.weight_table gives it and shift): table[0] = 256, no entry above 256, none above the one before; a
+ * table that is 0 behind table[0] is the identity.  patch is 1..3, search 1..7, shift 0..31; depth is 8, 10, 12, 14 or 16 (above 8 needs
+ * sample_bytes = 2).  Exact integers at every depth (the sums are unsigned 32-bit: sum(w v) <= 225 * 256 * 65535); the numpy definition is
+ * nlmeans.nlmeans_payload_np, matched byte for byte.  Every sample of every entry is written; where the entries do not name every sample
+ * up to the last one they reach, the payloads are copied first, so dst holds whole payloads.  Nothing between the payloads is read or
+ * written.
+ * DEMFI_ERR_ARG, with nothing launched: a NULL buffer or table, n < 0, sample_bytes not 1 or 2, a depth outside the list or above 8 in
+ * bytes, patch, search or shift out of range, a table that does not start at 256, exceeds it or increases, n_planes outside 1..6, a plane
+ * that starts below sample 0, a side outside 1..16384, a pitch below cols, a phase outside 0..7, 16-bit samples at an odd address or
+ * stride, a stride below the bytes the table reaches or so large that n of them leave int64, src and dst ranges that overlap.  One launch
+ * for all planes of all n payloads; n == 0 does nothing. */
+int demfi_payload_nlmeans(const void* src, int64_t src_stride_bytes, void* dst, int64_t dst_stride_bytes, int n, const int64_t* planes,
+                          int n_planes, int sample_bytes, int depth, int patch, int search, const uint16_t* table, int shift, void* stream);
+
 /* ---- inverse telecine of the Y4M edge (csrc/ivtc.hip; demfi_amd/video.py --ivtc) ------------------------------------------------
  * A woven frame W(top, bot) has the even rows of the luma plane (the first h*w samples of a payload; sample_bytes = 1, or 2 for
  * 16-bit little-endian samples) of payload `top` and the odd rows of that of payload `bot`; it is read in place, never built.
